@@ -3,7 +3,8 @@
 256 panoramas = 1024 images per GPU per step; forward + backward + AdamW, haversine-smoothed soft-CE over 12 647
 geocells, reference freeze policy ``freeze_all_but_last_stage``, DropPath 0.2, batch-stat BatchNorm) on N MI355X.
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--dump-outputs DIR]      (the headline only)
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full                    (+ everything below: other modes, roofline, secondary, CPU baseline)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --gpus N ...        (no launcher: starts the line above as a child process and relays its JSON line; exits non-zero
                                          when the machine has fewer than N GPUs -- it never reports an N-GPU number from fewer ranks)
@@ -14,10 +15,11 @@ is folded into the AdamW kernel).  Inputs are synthetic and resident in HBM befo
 
 PRECISION.  The reference computes this path in fp32 (torch defaults), so the headline ``value`` / ``dtype`` of the line
 are measured in the fp32 reference-precision mode (f32 activations, ``v_mfma_f32_16x16x4_f32``, erf GELU through a 1.2-ulp fp32 Phi).  The bf16 mode (bf16
-activations / MFMA operands, fp32 accumulation and master weights -- the mode a production run would use) is measured in the same
+activations / MFMA operands, fp32 accumulation and master weights -- the mode a production run would use) is measured under ``--full`` in the same
 invocation with the same protocol (W warm-up steps, exactly K timed steps between barrier + synchronize) and reported under
 ``"bf16"``.  ``--precision fp32|bf16`` runs one mode only (then ``value`` is that mode's).
 
+``--full`` adds the figures below (a plain run reports them as null).
 ``roofline`` (dominant kernel class = the MFMA GEMMs: every Linear / 1x1 conv / im2col'd conv and their dgrad / wgrad).  Every launch is
 timed with HIP events recorded on the launch stream inside libgg (``gg_prof_*``) over an instrumented replay of the timed steps and
 declares its algorithmic FLOPs (2MNK) and algorithmic bytes (A, B, C once each plus every second tensor its epilogue reads or writes).
@@ -501,8 +503,31 @@ def allreduce_cost(opt, dev, world, reps=5):
                 allreduce_busbw_gbps=round(2 * (world - 1) / world * nbytes / max(ms, 1e-9) / 1e6, 1))
 
 
-def run_mode(precision, args, rank, world, dev, x, lab):
-    """W warm-up steps, exactly K timed steps (barrier + synchronize on both sides, max over ranks), then an instrumented replay."""
+def dump_outputs(dump_dir, model, out):
+    """What the last timed step handed its caller -- the ModelOutput fields and the parameters AdamW wrote -- as float32 / float64 .npy files
+    under `dump_dir` (about 7 MB at the default size), so that two builds can be compared output for output on the same seeded inputs.
+    Integer outputs go out as float64 (exact).  Of the ~16 M trainable parameters a fixed seeded sample of 2^20 is kept, and any output above
+    2^22 elements (larger --panoramas) is sampled the same way, which keeps the total under 64 MB."""
+    import numpy as np
+
+    def sample(a, n):
+        if a.size <= n:
+            return a
+        return a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))]
+
+    os.makedirs(dump_dir, exist_ok=True)
+    f32 = lambda t: t.detach().float().cpu().numpy()
+    f64 = lambda t: t.detach().double().cpu().numpy()
+    arrays = dict(loss=f32(out.loss), preds_LLH=f32(out.preds_LLH), preds_geocell=f64(out.preds_geocell),
+                  top5_values=f32(out.top5_geocells.values), top5_indices=f64(out.top5_geocells.indices), embedding=f32(out.embedding))
+    arrays = {k: sample(a, 1 << 22) for k, a in arrays.items()}
+    arrays["params_sample"] = sample(np.concatenate([f32(p).reshape(-1) for p in model.parameters() if p.requires_grad]), 1 << 20)
+    for name, a in arrays.items():
+        np.save(os.path.join(dump_dir, name + ".npy"), a)
+
+
+def run_mode(precision, args, rank, world, dev, x, lab, dump_dir=None):
+    """W warm-up steps, exactly K timed steps (barrier + synchronize on both sides, max over ranks); with --full an instrumented replay."""
     import torch
     import torch.distributed as dist
     from geoguessr_ai_amd import _lib as L
@@ -550,10 +575,12 @@ def run_mode(precision, args, rank, world, dev, x, lab):
     loss = float(out.loss.detach())
     images = args.steps * N * 4 * world
     res = dict(value=round(images / dt, 2), ms_per_step=round(1e3 * dt / args.steps, 3), loss=round(loss, 5))
-    if world > 1:
+    if dump_dir:
+        dump_outputs(dump_dir, model, out)          # before anything below steps the model again
+    if world > 1 and args.full:
         res.update(allreduce_cost(opt, dev, world))
 
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         lib = L.lib()
         lib.gg_prof_reset(); lib.gg_prof_enable(1)
         sync()
@@ -648,13 +675,20 @@ def main():
     ap.add_argument("--panoramas", type=int, default=256, help="panoramas per GPU per step (BASELINE: 256)")
     ap.add_argument("--model", default="tiny_vit_21m_224")
     ap.add_argument("--precision", default="both", choices=["both", "fp32", "bf16", "fp32_split"],
-                    help="both: fp32_split (headline: f32-accurate, split-bf16 products), fp32 (f32 MFMA GEMMs, under 'fp32') and bf16 (under 'bf16')")
+                    help="both: fp32_split (headline: f32-accurate, split-bf16 products); with --full also fp32 (f32 MFMA GEMMs, under 'fp32') and bf16 (under 'bf16')")
     ap.add_argument("--unfrozen", action="store_true", help="train every parameter instead of the reference freeze policy")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--dump-launches", default=None, help="write the per-launch (category, ms, flops, bytes) list of one instrumented step to PATH.<precision>.json")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the c1 / c4 / c5 secondary timings (N = 1 only, ~15 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the other precisions, the instrumented roofline replay, the all-reduce cost (N > 1), the secondary configs and the "
+                         "CPU baseline (N = 1); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the headline mode's last timed step returned (ModelOutput fields, a seeded sample of the updated parameters) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="(--full) skip the instrumented roofline replay")
+    ap.add_argument("--dump-launches", default=None, help="(--full) write the per-launch (category, ms, flops, bytes) list of one instrumented step to PATH.<precision>.json")
+    ap.add_argument("--no-secondary", action="store_true", help="(--full) skip the c1 / c4 / c5 secondary timings (N = 1 only, ~15 s)")
     args = ap.parse_args()
+    if args.dump_launches and not args.full:
+        ap.error("--dump-launches comes from the instrumented replay of --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))          # `python bench.py --gpus N`: become the launcher, BEFORE anything here touches the GPU
@@ -703,18 +737,20 @@ def main():
     # f32 accumulation) carry 80 % of the GEMM time (every Linear and weight gradient of the transformer blocks, the forward convolutions of the ConvNorms) and the window
     # attention; error against fp64 at or below the f32 MFMA kernels' per shape, the fp32 mode's parity gate at the fp32 mode's tolerances
     # (tests/test_gpu_precision.py::test_fp32_split_mode_passes_the_fp32_gate).  VERDICT r4 item 6 set exactly this bar for the mode to become the headline dtype,
-    # labelled "fp32 (bf16x3 split MFMA)".  The plain f32-MFMA mode is timed in the same run and reported in full under "fp32"; bf16 under "bf16".
-    modes = ["fp32_split", "fp32", "bf16"] if args.precision == "both" else [args.precision]
-    results = {m: run_mode(m, args, rank, world, dev, x, lab) for m in modes}
+    # labelled "fp32 (bf16x3 split MFMA)".  A plain run times the headline mode alone; --full times the plain f32-MFMA mode ("fp32") and bf16 ("bf16") after
+    # it in the same run, so the headline is timed in the same state either way.
+    modes = [args.precision] if args.precision != "both" else ["fp32_split", "fp32", "bf16"] if args.full else ["fp32_split"]
+    dump_dir = args.dump_outputs if rank == 0 else None
+    results = {m: run_mode(m, args, rank, world, dev, x, lab, dump_dir=dump_dir if m == modes[0] else None) for m in modes}
     head = results[modes[0]]
 
     secondary = None
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         import contextlib
         with contextlib.redirect_stdout(sys.stderr):       # the shims print like the reference does; stdout carries the one JSON line only
             secondary = secondary_cases(dev)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline()
 
     if rank == 0:

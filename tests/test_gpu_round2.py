@@ -372,7 +372,7 @@ def test_two_rank_bench_rehearsal_on_one_gpu(precision):
     env = dict(os.environ, GG_DIST_BACKEND="gloo", GG_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--panoramas", "8", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--panoramas", "8", "--full", "--no-cpu-baseline",
            "--no-roofline", "--precision", precision]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -5,7 +5,7 @@ HB=$!
 case "$1" in
 a) python -m pytest tests -m gpu -q > gpurun_out/r06_gputests.log 2>&1; echo "pytest rc=$?" > gpurun_out/r06_final_a.rc
    python __graft_entry__.py smoke > gpurun_out/r06_smoke.log 2>&1; echo "smoke rc=$?" >> gpurun_out/r06_final_a.rc; cat gpurun_out/r06_final_a.rc; tail -3 gpurun_out/r06_gputests.log; tail -4 gpurun_out/r06_smoke.log ;;
-b) python bench.py > gpurun_out/r06_bench_line.json 2> gpurun_out/r06_bench.err; echo "bench rc=$?"; cut -c1-400 gpurun_out/r06_bench_line.json ;;
+b) mkdir -p profile_out; python bench.py --full > profile_out/r06_bench_line.json 2> profile_out/r06_bench.err; echo "bench rc=$?"; cut -c1-400 profile_out/r06_bench_line.json ;;
 c) bash tools/profile_round.sh fp32_split r06_fp32_split > gpurun_out/r06_prof_fp32_split.log 2>&1
    bash tools/pmc_split.sh r06 > gpurun_out/r06_pmc_split.log 2>&1
    bash tools/pmc_split_traffic.sh r06 > gpurun_out/r06_pmc_split_traffic.log 2>&1 ;;
