@@ -1213,15 +1213,7 @@ extern "C" int gg_attention_flash_fwd(const GgAttnArgs* a, int dtype, void* stre
         const size_t lds = sp_lds_fwd(p, 3);
         GG_PROF(GG_CAT_ATTN, 4.0 * a->num_windows * a->num_heads * (double)p.N * p.N * a->head_dim, 16.0 * a->num_windows * a->num_heads * (double)p.N * a->head_dim, stream);
         void (*kern)(FlashParams) = nt16 == 13 ? flash_fwd_split_kernel<float, 3, 13> : nt16 == 9 ? flash_fwd_split_kernel<float, 3, 9> : flash_fwd_split_kernel<float, 3, 4>;
-        if (lds > 64 * 1024) {
-            static bool raised[3] = {false, false, false};
-            const int ri = nt16 == 13 ? 0 : nt16 == 9 ? 1 : 2;
-            if (!raised[ri]) {
-                GG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess,
-                         "gg_attention_flash_fwd: cannot raise the dynamic LDS limit of the split kernel");
-                raised[ri] = true;
-            }
-        }
+        if (lds > 64 * 1024) GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(kern)));
         hipLaunchKernelGGL(kern, dim3((unsigned)(a->num_windows * a->num_heads)), dim3(64 * nt16), lds, (hipStream_t)stream, p);
         GG_LAUNCH_CHECK();
         return 0;
@@ -1236,14 +1228,7 @@ extern "C" int gg_attention_flash_fwd(const GgAttnArgs* a, int dtype, void* stre
             4.0 * es * a->num_windows * a->num_heads * (double)p.N * a->head_dim, stream);
 #define GG_FL_FWD(T_, D_)                                                                                     \
     do {                                                                                                      \
-        if (res && lds > 64 * 1024) {                                                                         \
-            static bool raised = false;                                                                       \
-            if (!raised) {                                                                                    \
-                GG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(flash_fwd_kernel<T_, D_, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess, \
-                         "gg_attention_flash_fwd: cannot raise the dynamic LDS limit");                       \
-                raised = true;                                                                                \
-            }                                                                                                 \
-        }                                                                                                     \
+        if (res && lds > 64 * 1024) GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(flash_fwd_kernel<T_, D_, true>)));      \
         if (res) hipLaunchKernelGGL((flash_fwd_kernel<T_, D_, true>), grid, block, lds, s, p);                \
         else hipLaunchKernelGGL((flash_fwd_kernel<T_, D_, false>), grid, block, lds, s, p);                   \
     } while (0)
@@ -1306,15 +1291,7 @@ int gg_attention_flash_bwd_impl(const GgAttnArgs* a, int dtype, int forward_roun
     } while (0)
             if (dtype == 1) GG_SP_BWD(float, 3); else GG_SP_BWD(bf16, 1);
 #undef GG_SP_BWD
-            if (lds > 64 * 1024) {
-                static bool raised[12] = {};
-                const int ri = (dtype == 1 ? 0 : 6) + (p.dbias != nullptr) * 3 + (nt16 == 13 ? 0 : nt16 == 9 ? 1 : 2);
-                if (!raised[ri]) {
-                    GG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess,
-                             "gg_attention_flash_bwd: cannot raise the dynamic LDS limit of the split kernel");
-                    raised[ri] = true;
-                }
-            }
+            if (lds > 64 * 1024) GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(kern)));
             hipLaunchKernelGGL(kern, dim3((unsigned)(a->num_windows * a->num_heads)), dim3(64 * ((nt16 + 1) / 2)), lds, s, p);
             if (p.dbias && p.dbias_part) {
                 const int Wd = p.nh * p.ws * p.ws;
@@ -1338,15 +1315,7 @@ int gg_attention_flash_bwd_impl(const GgAttnArgs* a, int dtype, int forward_roun
         const int nt_ = p.npad / 16;                                                                          \
         if (p.dbias) kern = nt_ == 13 ? flash_bwd_fused_kernel<T_, D_, true, 13> : nt_ == 4 ? flash_bwd_fused_kernel<T_, D_, true, 4> : flash_bwd_fused_kernel<T_, D_, true, 0>; \
         else kern = nt_ == 13 ? flash_bwd_fused_kernel<T_, D_, false, 13> : nt_ == 4 ? flash_bwd_fused_kernel<T_, D_, false, 4> : flash_bwd_fused_kernel<T_, D_, false, 0>; \
-        if (lds > 64 * 1024) {                                                                                \
-            static bool raised[6] = {false, false, false, false, false, false};                               \
-            const int ri_ = (p.dbias != nullptr) * 3 + (nt_ == 13 ? 1 : nt_ == 4 ? 2 : 0);                     \
-            if (!raised[ri_]) {                                                                               \
-                GG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess, \
-                         "gg_attention_flash_bwd: cannot raise the dynamic LDS limit of the single-pass kernel");  \
-                raised[ri_] = true;                                                                           \
-            }                                                                                                 \
-        }                                                                                                     \
+        if (lds > 64 * 1024) GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(kern)));                  \
         hipLaunchKernelGGL(kern, fgrid, fblock, lds, s, p);                                                   \
     } while (0)
         if (dtype == 1) { if (a->head_dim == 32) GG_FL_FUSED(float, 32); else GG_FL_FUSED(float, 64); }

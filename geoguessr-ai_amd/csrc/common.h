@@ -48,13 +48,30 @@ extern "C" const char* gg_last_error(void);
         if (r_ != 0) return r_; \
     } while (0)
 
-// Development switches (A/B timing of alternative kernels / schedules): read ONLY when GG_DEV_SWITCHES is set, so that a stray variable in a
+// Development switches (forcing one of the default path's own shape fallbacks): read ONLY when GG_DEV_SWITCHES is set, so that a stray variable in a
 // production environment cannot move the library off its tested default path.  Every alternative a switch selects is also a shape fallback of
 // the default path; tests/test_gpu_switches.py runs the parity step under each group of switches.
 #include <stdlib.h>
 static inline const char* gg_dev_env(const char* name) {
     static const bool on = getenv("GG_DEV_SWITCHES") != nullptr;
     return on ? getenv(name) : nullptr;
+}
+// Kernels that take more than 64 KB of dynamic LDS (up to the 160 KB of a CDNA4 CU): raise the kernel's limit once per (device, kernel), under a lock --
+// the attribute belongs to the current device, and launches may come from several host threads.  0, or -1 with the error set.
+#include <mutex>
+#include <set>
+#include <utility>
+inline int gg_allow_lds_160k(const void* kernel) {
+    static std::mutex mu;
+    static std::set<std::pair<int, const void*>> raised;
+    int dev = 0;
+    GG_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(mu);
+    if (raised.count({dev, kernel})) return 0;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    GG_CHECK(e == hipSuccess, "cannot raise the dynamic LDS limit to 160 KB on device %d: %s", dev, hipGetErrorString(e));
+    raised.insert({dev, kernel});
+    return 0;
 }
 // x = a + b + c with three bf16 terms (RNE; exact for every finite f32 whose low terms stay normal: 3 x 8 significand bits).  The first term is formed from x clamped
 // to the largest finite bf16 (3.39e38): bf16(x) alone rounds the top half-ulp of the f32 range (|x| >= 3.3961e38) to inf, which would turn a finite operand into

@@ -47,7 +47,6 @@ struct GemmParams {
     int out_f32;
     int split_k, k_per_split;     // split_k > 1: C is f32 [split][M][N] partials
     int tilesM, tilesN;
-    int debug;                    // timing experiments only: 1 = no operand loads, 2 = no result stores
     const ge_t* A2; int k_split;  // optional second A source for contraction columns k >= k_split (same lda)
     const ge_t* bn_y; const float* bn_stat; const float* bn_gamma; const float* bn_beta; int bn_act;   // EPI_BNBWD
     const float* a_stat; const float* a_gamma; const float* a_beta; int a_act;   // PRO: A := act(BN(A)) while staging
@@ -236,7 +235,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, ge_t* smem, f
         const int row = pass * RPP + rr, m = m0 + row;
         if (m >= p.M || n >= p.N) continue;
         ge8_t v = *reinterpret_cast<const ge8_t*>(Cs + row * CS + chunk * 8);
-        if (EPI == EPI_BNBWD && !(p.debug & 8)) {
+        if (EPI == EPI_BNBWD) {
             // dz = da * act'(gamma*xhat + beta); column sums of dz and dz*xhat (of the stored, bf16-rounded dz)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -252,7 +251,6 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, ge_t* smem, f
 #pragma unroll
             for (int j = 0; j < 4; ++j) { const f32x2 f = {(float)v[2 * j], (float)v[2 * j + 1]}; cs2[j] += f; cq2[j] += f * f; }
         }
-        if (p.debug & 2) continue;
         if (EPI == EPI_GELU) {
             if (p.preact) store8(p.preact, m, v, true);
             if (p.act == GG_ACT_QUICK_GELU) {       // CLIP fc1 in training (uniform branch: the pre-activation copy lives in this epilogue class)
@@ -284,7 +282,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, ge_t* smem, f
         }
         store8(reinterpret_cast<ge_t*>(p.C), m, v);
     }
-    if (stats && !(p.debug & 16)) {
+    if (stats) {
         __syncthreads();
         float cs[8], cq[8];
 #pragma unroll
@@ -393,8 +391,7 @@ __global__ __launch_bounds__(256, MINW) void gemm_nt_kernel(GemmParams p) {
         btab[0 * BN + threadIdx.x] = ga * rstd; btab[1 * BN + threadIdx.x] = be - mu * ga * rstd;
         btab[2 * BN + threadIdx.x] = rstd; btab[3 * BN + threadIdx.x] = -mu * rstd;
     }
-    if (EARLY && !(p.debug & 4)) gemm_ext_load<BM, BN, EPI>(p, m0, n0, ex);
-    if (EARLY && (p.debug & 4)) { for (auto& e : ex) e = (ge8_t){1, 1, 1, 1, 1, 1, 1, 1}; }
+    if (EARLY) gemm_ext_load<BM, BN, EPI>(p, m0, n0, ex);
     u32x4 ra[LA], rb[LB];
     const int nk = (kend - kbeg + BK - 1) / BK;
     auto load_tile = [&](int kt) {
@@ -609,9 +606,8 @@ __device__ __forceinline__ void gemm_dma_epilogue(const GemmParams& p, ge_t* scr
                 for (int j = 0; j < 8; ++j) v[j] = (ge_t)((float)v[j] + (float)e[j]);
             }
             // result stores non-temporal: the tile's rows are not read again by this launch, and kept out of the L2's way they do not evict the weight panel and the A rows
-            // the concurrent tiles share (c4 fp16 12.1 -> 11.9 ms, bf16 11.8 -> 11.55: same-box A/B, profiles/r06_c4_nt_stores.txt; dev: GG_GEMM_DEBUG=32 restores the default policy)
-            if (p.debug & 32) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsC, (int)vo, 0, 0);
-            else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsC, (int)vo, 0, 2);
+            // the concurrent tiles share (c4 fp16 12.1 -> 11.9 ms, bf16 11.8 -> 11.55: same-box A/B, profiles/r06_c4_nt_stores.txt)
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsC, (int)vo, 0, 2);
         }
     }
 }
@@ -625,7 +621,7 @@ template <int N> __device__ __forceinline__ void gemm_wait_vmcnt() { asm volatil
 //   TM = 6, NWN = 2: 192 x 128 tile, four waves, 2 x 80 KB of LDS = two workgroups per CU (above);
 //   TM = 8, NWN = 4: 256 x 256 tile, eight waves of 128 x 64, 128 KB = ONE workgroup per CU: 128 instead of 77 flop per operand byte and 8 instead of 10 DMA
 //     pieces per 64 / 48 MFMAs of a wave -- the long-K, wide-N shapes whose k-loop outweighs the exposed prologue / epilogue of a lone workgroup.
-template <int EPI, bool EXT = false, int TM = 6, int NWN = 2, int ABL = 0>      // EXT: the row phase reads a second tensor (residual / saved pre-activation); ABL (dev, tools/ablate_gemm16.sh): 1 = no operand DMA, 32 = no MFMAs, 64 = per-tile cycle trace into p.colstats
+template <int EPI, bool EXT = false, int TM = 6, int NWN = 2>      // EXT: the row phase reads a second tensor (residual / saved pre-activation)
 __global__ __launch_bounds__(128 * NWN, 2) void gemm_nt_dma_kernel(GemmParams p) {
     constexpr int NW = 2 * NWN, NTHR = 64 * NW;
     constexpr int BM = 2 * TM * 16, BN = NWN * 64, SK = 64, NST = 2;
@@ -661,7 +657,6 @@ __global__ __launch_bounds__(128 * NWN, 2) void gemm_nt_dma_kernel(GemmParams p)
 #pragma unroll
     for (int j = 0; j < PB; ++j) voffB[j] = (unsigned)((wave + NW * j) * 8 + (lane >> 3)) * (unsigned)p.ldb * 2u + dchunk * 16u;
     auto issue_stage = [&](const __amdgpu_buffer_rsrc_t& rsA, const __amdgpu_buffer_rsrc_t& rsB, int st, ge_t* base) {
-        if (ABL & 1) return;
         const int k0 = st * SK;
         const bool kin = k0 + dchunk * 8 < p.K;                  // K % 8 == 0: a chunk is entirely inside or outside K
 #pragma unroll
@@ -687,8 +682,6 @@ __global__ __launch_bounds__(128 * NWN, 2) void gemm_nt_dma_kernel(GemmParams p)
     tile_mn(t, m0, n0);
     __amdgpu_buffer_rsrc_t rsA, rsB;
     make_rs(m0, n0, rsA, rsB);
-    unsigned long long tr_t0 = 0, tr_first = 0, tr_wait = 0, tr_issue = 0, tr_loop = 0, tr_c0 = 0, tr_c1 = 0, tr_rt0 = 0;
-    if (ABL & 64) { tr_t0 = __builtin_readcyclecounter(); tr_rt0 = __builtin_amdgcn_s_memrealtime(); }
     issue_stage(rsA, rsB, 0, smem);
     if (nk > 1) issue_stage(rsA, rsB, 1, smem + STAGE);
     f32x4 acc[TN][TM];
@@ -698,7 +691,6 @@ __global__ __launch_bounds__(128 * NWN, 2) void gemm_nt_dma_kernel(GemmParams p)
         for (int j = 0; j < TM; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (nk > 1) gemm_wait_vmcnt<DPS>(); else gemm_wait_vmcnt<0>();     // stage 0 has landed (stage 1 may be in flight)
     __builtin_amdgcn_s_barrier();
-    if (ABL & 64) { tr_first = __builtin_readcyclecounter(); tr_wait = 0; tr_issue = 0; }
     ge8_t ar[4], bq[2][TN];
 #pragma unroll
     for (int nt = 0; nt < TN; ++nt) bq[0][nt] = *reinterpret_cast<const ge8_t*>(smem + b_off + nt * 16 * SK + kc0);
@@ -725,20 +717,16 @@ __global__ __launch_bounds__(128 * NWN, 2) void gemm_nt_dma_kernel(GemmParams p)
             }
             if (i == 2 * TM - 2) {
                 // every fragment read of stage s has been issued (the last A fragment one m-tile ago)
-                if (ABL & 64) tr_c0 = __builtin_readcyclecounter();
                 if (STEADY || s + 1 < nk) gemm_wait_vmcnt<0>(); // this wave's DMAs of stage s + 1 have landed (nothing else is in flight: ring of two)
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();                   // everybody's have, and everybody has read its fragments of stage s
-                if (ABL & 64) { tr_c1 = __builtin_readcyclecounter(); tr_wait += tr_c1 - tr_c0; }
                 if (STEADY || s + 2 < nk) issue_stage(rsA, rsB, s + 2, cur);
-                if (ABL & 64) tr_issue += __builtin_readcyclecounter() - tr_c1;
 #pragma unroll
                 for (int nt = 0; nt < TN; ++nt) bq[0][nt] = *reinterpret_cast<const ge8_t*>(nxt + b_off + nt * 16 * SK + kc0);
                 ar[0] = *reinterpret_cast<const ge8_t*>(nxt + a_off + kc0);
                 ar[1] = *reinterpret_cast<const ge8_t*>(nxt + a_off + 16 * SK + kc0);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (!(ABL & 32))
 #pragma unroll
             for (int nt = 0; nt < TN; ++nt) acc[nt][mt] = ge_mfma(bq[ks][nt], ar[i & 3], acc[nt][mt]);
             __builtin_amdgcn_sched_barrier(0);
@@ -754,19 +742,9 @@ __global__ __launch_bounds__(128 * NWN, 2) void gemm_nt_dma_kernel(GemmParams p)
         stage(std::false_type{}, s, s & 1);
     }
     __builtin_amdgcn_s_barrier();                               // the ring is idle: no DMA in flight, every fragment read
-    if (ABL & 64) tr_loop = __builtin_readcyclecounter();
     gemm_dma_epi_ready<EPI, TM>(p, e_bs, e_rsv);
     gemm_dma_ext_fetch<EPI, EXT, TM>(p, e_ex, m0, n0, wm, wn, lane);
     gemm_dma_epilogue<EPI, EXT, TM>(p, smem + wave * (2 * 32 * 72), acc, e_bs, e_rsv, e_ex, m0, n0, wm, wn, lane);
-    if ((ABL & 64) && threadIdx.x == 0) {
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        unsigned long long* tt = reinterpret_cast<unsigned long long*>(p.colstats) + (size_t)t * 8;
-        const unsigned long long now = __builtin_readcyclecounter();
-        tt[0] = tr_first - tr_t0; tt[1] = tr_loop - tr_first; tt[2] = tr_wait; tt[3] = tr_issue; tt[4] = now - tr_loop; tt[5] = tr_rt0;
-        tt[6] = hw | ((unsigned long long)(xcc & 0xF) << 32); tt[7] = __builtin_amdgcn_s_memrealtime();
-    }
 }
 
 // ------------------------------------------------------------------------------------------- TN GEMM (weight gradients)
@@ -1131,8 +1109,6 @@ extern "C" int GG_GEMM_NT_NAME(const GgGemmArgs* a, void* stream) {
     kps = (int)gg_align(kps, BK);
     p.k_per_split = kps;
     // tile choice: HBM-bound shapes (short K loop or a single narrow N tile) take the light 128x64 tile
-    static const char* dbg = gg_dev_env("GG_GEMM_DEBUG");
-    p.debug = dbg ? atoi(dbg) : 0;
     static const char* force = gg_dev_env("GG_GEMM_TILE");
     const int rem = a->N % 128;
     bool narrow = a->N <= 64 || (rem != 0 && rem <= 64);     // a 128-wide tile would be at most half full
@@ -1160,14 +1136,11 @@ extern "C" int GG_GEMM_NT_NAME(const GgGemmArgs* a, void* stream) {
     // the MFMA-bound shapes (the transformer Linears and their data gradients) take the LDS-DMA form: 256 x 128 tiles
     // (its epilogue has no general-shape fallbacks: whole 16-byte column chunks, 16-byte aligned rows of every tensor it touches)
     auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-    const char* dma_sw = gg_dev_env("GG_GEMM_DMA");        // (not cached: the dev tools flip it between launches of one process)
-    const int dma_var = dma_sw ? atoi(dma_sw) : 1;
-    bool dma = !p.a_stat && !p.A2 && !p.bn_y && (!p.colstats || dma_var == 6) && split == 1 && !a->out_f32 && a->K >= 192 && a->N >= 128 && a->M >= 1024 &&
+    bool dma = !p.a_stat && !p.A2 && !p.bn_y && !p.colstats && split == 1 && !a->out_f32 && a->K >= 192 && a->N >= 128 && a->M >= 1024 &&
                (rem == 0 || rem > 64) && a->lda * 512 < 0xFFFFFF00LL && a->ldb * 256 < 0xFFFFFF00LL && a->ldc * 512 < 0xFFFFFF00LL &&
                (!a->residual || (a->ldr * 512 < 0xFFFFFF00LL && (a->ldr & 7) == 0 && al16(a->residual))) && (a->N & 7) == 0 && (a->ldc & 7) == 0 && al16(a->C) &&
                (!a->preact || al16(a->preact)) && (!a->dact_preact || al16(a->dact_preact)) && (!a->bias || al16(a->bias));
-    if (dma_sw) dma = dma && dma_var != 0;
-    if (const char* only = gg_dev_env("GG_GEMM_DMA_ONLY")) { int on = 0, ok = 0, oe = -1; sscanf(only, "%d,%d,%d", &on, &ok, &oe); dma = dma && a->N == on && a->K == ok && (oe < 0 || oe == epi); }      // (dev: bisecting)
+    if (const char* dma_sw = gg_dev_env("GG_GEMM_DMA")) dma = dma && atoi(dma_sw) != 0;      // (not cached: tools/bench_gemm16.py flips it between launches of one process)
     if (dma) {
         // the 256 x 256 geometry (one workgroup per CU) where its k-loop outweighs a lone workgroup's exposed prologue / epilogue: measured (tools/bench_gemm16.py,
         // profiles/r05_gemm16_forms.txt) 1.37-1.41 PFLOP/s against 1.13-1.15 at K = 4096 / 8192, a tie at K = 3072 (CLIP fc2), 5-12 % slower at K = 384 ... 768
@@ -1179,16 +1152,7 @@ extern "C" int GG_GEMM_NT_NAME(const GgGemmArgs* a, void* stream) {
         const int bm = big ? 256 : 192, bn = big ? 256 : 128;
         p.tilesM = (int)gg_cdiv(a->M, bm); p.tilesN = (int)gg_cdiv(a->N, bn);
         const dim3 g2((unsigned)(p.tilesM * p.tilesN)), blk(big ? 512 : 256);
-        const char* gm_sw = gg_dev_env("GG_GEMM_GM");
-        p.group_m = gm_sw ? atoi(gm_sw) : (p.tilesN > (big ? 4 : 8) ? (big ? 4 : 8) : 0);
-        if (dma_var > 1 && epi == EPI_PLAIN && !big) {       // dev: ablations / trace (tools/ablate_gemm16.sh, tools/trace_gemm16.py)
-            if (dma_var == 3) hipLaunchKernelGGL((gemm_nt_dma_kernel<EPI_PLAIN, false, 6, 2, 1>), g2, blk, 0, st, p);
-            else if (dma_var == 4) hipLaunchKernelGGL((gemm_nt_dma_kernel<EPI_PLAIN, false, 6, 2, 32>), g2, blk, 0, st, p);
-            else if (dma_var == 6) hipLaunchKernelGGL((gemm_nt_dma_kernel<EPI_PLAIN, false, 6, 2, 64>), g2, blk, 0, st, p);
-            else hipLaunchKernelGGL((gemm_nt_dma_kernel<EPI_PLAIN, false, 6, 2, 33>), g2, blk, 0, st, p);
-            GG_LAUNCH_CHECK();
-            return 0;
-        }
+        p.group_m = p.tilesN > (big ? 4 : 8) ? (big ? 4 : 8) : 0;
 #define GG_DMA_LAUNCH(E, X)                                                                                             \
     do {                                                                                                                \
         if (big) hipLaunchKernelGGL((gemm_nt_dma_kernel<E, X, 8, 4>), g2, blk, 0, st, p);                               \

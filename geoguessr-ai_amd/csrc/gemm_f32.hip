@@ -34,7 +34,7 @@ struct F32GemmParams {
     const float* dact_preact;
     float* colstats;              // [tilesM][2][N]
     int tilesM, tilesN;
-    int debug;                    // timing experiments only (GG_GEMM_F32_DEBUG): 1 no operand loads, 2 no result stores, 4 no LDS staging / barriers
+    int no_pair_store;            // dev (GG_GEMM_F32_NO_PAIR_STORE): the general epilogue's 64-byte-run stores, as every launch with ldc % 32 != 0 takes
     // BatchNorm-backward epilogue (FE_BNBWD): C = dz = acc * act'(BN(bn_y)), colstats <- column sums of (dz, dz*xhat)
     const float* bn_y; const float* bn_stat; const float* bn_gamma; const float* bn_beta; int bn_act;
     // A-operand prologues of the register-staged kernel: PRO 1: A := a_act(BN(A)) (a_stat = [mean | rstd][K], gamma, beta);
@@ -42,7 +42,6 @@ struct F32GemmParams {
     const float* A2; const float* a_stat; const float* a_gamma; const float* a_beta; int a_act;
     unsigned long long* trace;      // dev (gg_gemm_f32_set_trace): per-workgroup [hw_id, xcc_id, t_start, t_first_data, t_loop_end, t_epilogue_end, tile, 0] (100 MHz ticks)
     int quick;          // FE_GELU / FE_DGELU: the activation is QuickGELU (CLIP) instead of erf GELU
-    int swz_plain = 0;  // dev A/B (GG_GEMM_F32_SWZ=0): the ring kernel's tile rows unpermuted (rounds 2-5: 2-way bank conflicts on the fragment reads)
     int splits = 1, k_per_split = 0;      // small-M form: workgroup (split s, tile t) contracts k in [s k_per_split, (s + 1) k_per_split) into slab s of C ([splits][M][ldc])
 };
 
@@ -82,7 +81,7 @@ __device__ __forceinline__ void gemm_f32_epilogue(const F32GemmParams& p, float*
     const bool vec_c = (p.ldc & 3) == 0;
     // full-line stores: a lane's 16 bytes of two neighbouring n-tiles are regrouped (one DPP row rotate) so that a store instruction writes
     // 8 rows x 128 B (whole cache lines) instead of 16 rows x 64 B (every line in two halves, 4 stores apart)
-    const bool pair_store = TN >= 2 && vec_c && (p.ldc & 31) == 0 && (p.debug & 128) == 0;      // (debug 128: the 64-byte-run stores, for A/B)
+    const bool pair_store = TN >= 2 && vec_c && (p.ldc & 31) == 0 && !p.no_pair_store;
         float* red = smem;                                    // [WM][2][BN] column partials (the k-loop's last barrier has passed)
     // the epilogue's second tensor (BatchNorm-backward: saved conv output; GELU': saved pre-activation; linear: residual) for the whole
     // tile, all 16 loads in flight at once -- fetched inside the loop below they were 16 serialised memory round trips per tile
@@ -94,7 +93,7 @@ __device__ __forceinline__ void gemm_f32_epilogue(const F32GemmParams& p, float*
     f32x4 aux[AUX ? GN : 1][AUX ? TMH : 1];
     // whole-line fetch of the second tensor: with two n-tiles per group a load instruction reads 8 rows x 128 B (lanes lr < 8: tile e of row lr & 7,
     // lanes lr >= 8: tile o of the same row; second load: rows 8..15) and one DPP row rotate hands every lane its own fragment
-    const bool pair_aux = AUX && GN == 2 && aux_src != nullptr && aux_vec && (aux_ld & 31) == 0 && (p.N & 31) == 0 && (p.debug & 128) == 0;
+    const bool pair_aux = AUX && GN == 2 && aux_src != nullptr && aux_vec && (aux_ld & 31) == 0 && (p.N & 31) == 0 && !p.no_pair_store;
     const int hh = lr >> 3, l7 = lr & 7;
 #pragma unroll
     for (int mh = 0; mh < MSPLIT; ++mh) {
@@ -217,7 +216,9 @@ __device__ __forceinline__ void gemm_f32_epilogue(const F32GemmParams& p, float*
                     }
                 }
                 if (pair_store && nt < (TN & ~1)) { acc[nt][mt] = v; continue; }      // stored below, two n-tiles at a time
-                if (ok && !((p.debug & 2) && v[0] != 12345.678f)) {
+                // (BatchNorm backward: without this barrier the scheduler merges the store with the dz block above and the 128-column form spills)
+                if constexpr (EPI == FE_BNBWD) __builtin_amdgcn_sched_barrier(0);
+                if (ok) {
                     float* g = p.C + (int64_t)m * p.ldc + n;
                     if (full) *reinterpret_cast<f32x4*>(g) = v;
                     else { for (int r = 0; r < 4; ++r) if (n + r < p.N) g[r] = v[r]; }
@@ -239,7 +240,7 @@ __device__ __forceinline__ void gemm_f32_epilogue(const F32GemmParams& p, float*
         }
     }
     }      // mh
-    if (pair_store && !(p.debug & 2)) {
+    if (pair_store) {
         const int h = hh;
 #pragma unroll
         for (int e = 0; e + 1 < TN; e += 2) {
@@ -460,9 +461,11 @@ __device__ __forceinline__ void gemm_f32_epilogue_rows(const F32GemmParams& p, f
 // PERSISTENT workgroups: the grid is min(tiles, resident workgroups) and a workgroup walks tiles t, t + grid, ...  The operand
 // registers that prefetch the next k-tile are idle during a tile's last k-iteration, so they fetch the NEXT tile's first k-tile
 // there: a tile's prologue (first-load latency, ~10 % of a K = 384 tile, ~25 % of a K = 96 tile when measured by ablation) and its
-// epilogue stores overlap with matrix work instead of adding to it.  Result-independent of the grid size.
-template <int BN, int WM, int WN, int EPI, int PRO = 0, int BNC = BN>      // BNC < BN: compute BNC columns of a BN-row B panel (see the ring kernel)
-__global__ __launch_bounds__(256, PRO != 0 ? 2 : (BN == 128 ? 3 : 4)) void gemm_nt_f32_kernel(F32GemmParams p) {
+// epilogue stores overlap with matrix work instead of adding to it.  Result-independent of the grid size.  Only the A-prologue forms (PRO 1 / 2) are
+// built: without a prologue every launch takes the ring kernel below.
+template <int BN, int WM, int WN, int EPI, int PRO, int BNC = BN>      // BNC < BN: compute BNC columns of a BN-row B panel (see the ring kernel)
+__global__ __launch_bounds__(256, 2) void gemm_nt_f32_kernel(F32GemmParams p) {
+    static_assert(PRO == 1 || PRO == 2, "the register-staged kernel is built for the A prologues only");
     constexpr int BM = 128;
     constexpr int TM = BM / WM / 16, TN = BNC / WN / 16;
     constexpr int LA = BM * 8 / 256, LB = BN * 8 / 256;           // 16-byte chunks per thread per k-tile
@@ -511,7 +514,6 @@ __global__ __launch_bounds__(256, PRO != 0 ? 2 : (BN == 128 ? 3 : 4)) void gemm_
     // operand loads of k-tile kt of the tile at (tm, tn): raw buffer loads, descriptor = the valid rows of that tile (rows beyond M / N
     // read as zeros through the hardware range check), k offset in the scalar soffset, chunks beyond K pushed out of range
     auto load_tile = [&](int tm_, int tn_, int kt) {
-        if (p.debug & 1) return;
         const int m0_ = tm_ * BM, n0_ = tn_ * BNC;
         const unsigned bytesA = (unsigned)min(p.M - m0_, BM) * (unsigned)p.lda * 4u;
         const unsigned bytesB = (unsigned)min(p.N - n0_, BNC) * (unsigned)p.ldb * 4u;
@@ -530,12 +532,6 @@ __global__ __launch_bounds__(256, PRO != 0 ? 2 : (BN == 128 ? 3 : 4)) void gemm_
 #pragma unroll
         for (int i = 0; i < LB; ++i) rb[i] = __builtin_amdgcn_raw_buffer_load_b128(rsB, (int)(kin ? vob[i] : 0xFFFFFFF0u), so, 0);
     };
-    if (p.debug & 1) {
-#pragma unroll
-        for (int i = 0; i < LA; ++i) ra[i] = (u32x4){1, 2, 3, 4};
-#pragma unroll
-        for (int i = 0; i < LB; ++i) rb[i] = (u32x4){1, 2, 3, 4};
-    }
     int t = blockIdx.x;
     int bid = gg_xcd_remap(t, tiles);
     int tm = bid / p.tilesN, tn = bid % p.tilesN;
@@ -574,13 +570,11 @@ __global__ __launch_bounds__(256, PRO != 0 ? 2 : (BN == 128 ? 3 : 4)) void gemm_
                     ra[i] = __builtin_bit_cast(u32x4, v);
                 }
             }
-            if (!(p.debug & 4)) {
 #pragma unroll
-                for (int i = 0; i < LA; ++i) *reinterpret_cast<u32x4*>(As + lds_a[i]) = ra[i];
+            for (int i = 0; i < LA; ++i) *reinterpret_cast<u32x4*>(As + lds_a[i]) = ra[i];
 #pragma unroll
-                for (int i = 0; i < LB; ++i) *reinterpret_cast<u32x4*>(Bs + lds_b[i]) = rb[i];
-                __syncthreads();
-            }
+            for (int i = 0; i < LB; ++i) *reinterpret_cast<u32x4*>(Bs + lds_b[i]) = rb[i];
+            __syncthreads();
             if (kt + 1 < nk) load_tile(tm, tn, kt + 1);
             else if (has_next) load_tile(tm_n, tn_n, 0);              // the next tile's first operands travel under this tile's last MFMAs + epilogue
             const int rounds = (p.K - kt * FBK) > 16 ? 2 : 1;            // skip the all-zero upper half of a K tail
@@ -602,7 +596,7 @@ __global__ __launch_bounds__(256, PRO != 0 ? 2 : (BN == 128 ? 3 : 4)) void gemm_
                                 acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[nt][s], xf[mt][s], acc[nt][mt], 0, 0, 0);
                 }
             }
-            if (!(p.debug & 4)) __syncthreads();
+            __syncthreads();
         }
 
         gemm_f32_epilogue<BM, BNC, WM, WN, EPI>(p, smem, acc, m0, n0, tm, wm, wn, lr, lg);
@@ -612,7 +606,7 @@ __global__ __launch_bounds__(256, PRO != 0 ? 2 : (BN == 128 ? 3 : 4)) void gemm_
 }
 
 // ---------------------------------------------------------------------------------------------- NT, LDS-DMA ring (default)
-// Measured on the register-staged kernel above (GG_GEMM_F32_DEBUG ablations, M = 200 704, N = 1152, K = 384): 119 TFLOP/s as is, 131
+// Measured on the register-staged kernel above (ablations since retired, M = 200 704, N = 1152, K = 384): 119 TFLOP/s as is, 131
 // without operand loads, 132 without stores, 136 without either, 144 without LDS staging / barriers, against 154 sustained by the
 // bare MFMA loop -- its one-k-tile prefetch distance (1.7 us) is shorter than a loaded HBM miss, and every k-tile pays two barriers
 // plus an exposed ds_read.  This kernel removes both: operands travel global -> LDS by LDS-DMA (`buffer_load ... lds`: no
@@ -697,7 +691,7 @@ __global__ __launch_bounds__(256, OCC) void gemm_nt_f32_ring_kernel(F32GemmParam
     // 64-byte tile rows (16 floats): the LDS side of a DMA is lane-linear, so the bank permutation is applied on the SOURCE side -- LDS slot (lane & 3) of row lane / 4
     // receives global chunk slot ^ perm(row quad) -- and undone in the fragment reads below.  perm = {0, 2, 3, 1} is what ds_read_b128's 16-lane service groups
     // ({0-3, 12-15, 20-27}, ...) need for 16 rows x one k-chunk; read straight (as rounds 2-5 did) every fragment read was a 2-way bank conflict
-    const int drow = lane >> 2, dch = (lane & 3) ^ (p.swz_plain ? 0 : ((0x78 >> (2 * (lane >> 4))) & 3));
+    const int drow = lane >> 2, dch = (lane & 3) ^ ((0x78 >> (2 * (lane >> 4))) & 3);
     unsigned voff[IPW];
 #pragma unroll
     for (int j = 0; j < IPW; ++j) {
@@ -721,7 +715,7 @@ __global__ __launch_bounds__(256, OCC) void gemm_nt_f32_ring_kernel(F32GemmParam
         }
     };
     auto issue_stage = [&](int st) { issue_stage_at(st, smem + (st % NST) * STAGE); };
-    const int fch = lg ^ (p.swz_plain ? 0 : ((0x78 >> (2 * ((lr >> 2) & 3))) & 3));      // position of this lane's k-chunk lg in its row
+    const int fch = lg ^ ((0x78 >> (2 * ((lr >> 2) & 3))) & 3);      // position of this lane's k-chunk lg in its row
     const int a_off = (wm * (BM / WM) + lr) * SK + fch * 4, b_off = BM * SK + (wn * WCOLS + lr) * SK + fch * 4;
     auto frag_read_at = [&](const float* base, f32x4 (&xf)[TM], f32x4 (&wf)[TN]) {
 #pragma unroll
@@ -1140,8 +1134,6 @@ extern "C" int gg_gemm_nt_f32(const GgGemmArgs* a, void* stream) {
     p.rowscale = a->rowscale; p.rows_per_scale = a->rows_per_scale; p.residual = (const float*)a->residual; p.ldr = a->ldr;
     p.dact_preact = (const float*)a->dact_preact; p.colstats = a->colstats;
     p.quick = (a->dact_preact ? a->dact : a->act) == GG_ACT_QUICK_GELU;
-    static const char* swz_env = gg_dev_env("GG_GEMM_F32_SWZ");
-    p.swz_plain = swz_env && atoi(swz_env) == 0;
     p.bn_y = (const float*)a->bn_y; p.bn_stat = a->bn_stat; p.bn_gamma = a->bn_gamma; p.bn_beta = a->bn_beta; p.bn_act = a->bn_act;
     p.A2 = (const float*)a->A2; p.a_stat = a->a_bn_stat; p.a_gamma = a->a_bn_gamma; p.a_beta = a->a_bn_beta; p.a_act = a->a_bn_act;
     const int rem = a->N % 128;
@@ -1177,8 +1169,8 @@ extern "C" int gg_gemm_nt_f32(const GgGemmArgs* a, void* stream) {
             else nsplit = 1;
         }
     }
-    static const char* dbg = gg_dev_env("GG_GEMM_F32_DEBUG");
-    p.debug = dbg ? atoi(dbg) : 0;
+    static const char* np_store_env = gg_dev_env("GG_GEMM_F32_NO_PAIR_STORE");      // "1": the 64-byte-run stores everywhere ("0": the default)
+    p.no_pair_store = np_store_env && np_store_env[0] != '0';
     p.trace = g_f32_trace;
     const double mn = (double)a->M * a->N;
     GG_PROF(GG_CAT_GEMM, 2.0 * a->M * (double)a->N * a->K,
@@ -1192,29 +1184,25 @@ extern "C" int gg_gemm_nt_f32(const GgGemmArgs* a, void* stream) {
     else if (a->act == GG_ACT_QUICK_GELU) epi = FE_QGELU;
     else if (a->bias || a->rowscale || a->residual) epi = FE_LINEAR;
     else epi = FE_PLAIN;
-    // default: the LDS-DMA ring kernel, one workgroup per tile.  GG_GEMM_F32_RING=0: the register-staged kernel with persistent
-    // workgroups (at most the resident count, each walks tiles t, t + grid, ...) -- kept for A/B timing and the DEBUG ablations
-    static const char* ring_env = gg_dev_env("GG_GEMM_F32_RING");
+    // the LDS-DMA ring kernel, one workgroup per tile; the register-staged prologue kernels below keep at most their resident count of persistent
+    // workgroups (2 per CU; each walks tiles t, t + grid, ...)
     static const char* np_env = gg_dev_env("GG_GEMM_F32_NO_PERSIST");
-    const bool ring = ((!(ring_env && ring_env[0] == '0') && (p.debug & 5) == 0) || wide96) && !a->a_bn_stat;
-    const int resident = 256 * (a->a_bn_stat ? 2 : (narrow ? 4 : 3));      // workgroups the persistent variants keep resident (launch bounds)
-    dim3 grid((ring || np_env || p.tilesM * p.tilesN <= resident) ? p.tilesM * p.tilesN : resident);
+    const int resident = 256 * 2;
+    const dim3 grid((!a->a_bn_stat || np_env || p.tilesM * p.tilesN <= resident) ? p.tilesM * p.tilesN : resident);
     hipStream_t st = (hipStream_t)stream;
-    // the single-fragment-buffer form (4 workgroups per CU; 6 for the 128 x 64 tile) is the default for every K: +2...+7 % on the model's shapes
-    // against the double-buffered 3-per-CU form (tools/ab_gemm_sb.sh).  GG_GEMM_F32_SB=<K threshold> (0: off) for A/B runs
-    static const char* sb_env = gg_dev_env("GG_GEMM_F32_SB");
-    const int sb_k = sb_env ? atoi(sb_env) : (1 << 30);
-    const bool sb = ring && !wide96 && a->K <= sb_k;
+    // the single-fragment-buffer form (4 workgroups per CU; 6 for the 128 x 64 tile) for every K: +2...+7 % on the model's shapes against the
+    // double-buffered 3-per-CU form (profiles/r03_gemm_forms_ab.txt, profiles/HISTORY.md), which the 96-column tiles keep where the row-layout epilogue does not apply
+    const bool sb = !wide96;
     // row-layout epilogue (gemm_f32_epilogue_rows): every tile interior, 16-byte rows everywhere, at most three DropPath scales per wave.
     // GG_GEMM_F32_ROWS_EPI=0: the general epilogue (A/B, parity of the two forms)
     static const char* rows_env = gg_dev_env("GG_GEMM_F32_ROWS_EPI");
     const float* xsrc = a->bn_y ? (const float*)a->bn_y : (a->dact_preact ? (const float*)a->dact_preact : (const float*)a->residual);
     const int64_t xld = (a->bn_y || a->dact_preact) ? a->ldc : a->ldr;
-    const bool rows_ok = !(rows_env && rows_env[0] == '0') && p.debug == 0 && !p.trace && a->M % 128 == 0 && a->N % bn == 0 && (a->ldc & 3) == 0 && a->ldc < (1 << 23) &&
+    const bool rows_ok = !(rows_env && rows_env[0] == '0') && !p.trace && a->M % 128 == 0 && a->N % bn == 0 && (a->ldc & 3) == 0 && a->ldc < (1 << 23) &&
                           (!xsrc || ((xld & 3) == 0 && xld < (1 << 23))) && (!a->rowscale || a->rows_per_scale >= 32) && (!a->bias || ((uintptr_t)a->bias & 15) == 0) &&
                           (!a->bn_y || ((((uintptr_t)a->bn_stat | (uintptr_t)a->bn_gamma | (uintptr_t)a->bn_beta) & 15) == 0)) && (!a->colstats || ((uintptr_t)a->colstats & 3) == 0);
     const bool rows_epi = sb && rows_ok;
-    const bool sb96 = ring && wide96 && rows_ok && a->K <= sb_k;      // N = 96, 288: the 4 x 1 wave layout of the single-buffer form with the row-layout epilogue
+    const bool sb96 = wide96 && rows_ok;      // N = 96, 288: the 4 x 1 wave layout of the single-buffer form with the row-layout epilogue
 #define GG_LAUNCH_F32(E)                                                                                          \
     do {                                                                                                          \
         if (small) hipLaunchKernelGGL((gemm_nt_f32_ring_kernel<64, 2, 2, E, 4, 4, 64, false, 0, false, 64>), dim3(p.tilesM * p.tilesN), dim3(256), 0, st, p); \
@@ -1223,14 +1211,10 @@ extern "C" int gg_gemm_nt_f32(const GgGemmArgs* a, void* stream) {
         else if (sb && narrow) hipLaunchKernelGGL((gemm_nt_f32_ring_kernel<64, 4, 1, E, 2, (E == FE_BNBWD ? 4 : ((E == FE_DGELU || E == FE_LINEAR) ? 5 : 6)), 64, true>), grid, dim3(256), 0, st, p); \
         else if (sb) hipLaunchKernelGGL((gemm_nt_f32_ring_kernel<128, 2, 2, E, 2, 4, 128, true>), grid, dim3(256), 0, st, p); \
         else if (sb96) hipLaunchKernelGGL((gemm_nt_f32_ring_kernel<128, 4, 1, E, 2, 4, 96, true, 0, true>), grid, dim3(256), 0, st, p); \
-        else if (wide96) hipLaunchKernelGGL((gemm_nt_f32_ring_kernel<128, 2, 2, E, 3, 3, 96>), grid, dim3(256), 0, st, p); \
-        else if (ring && narrow) hipLaunchKernelGGL((gemm_nt_f32_ring_kernel<64, 4, 1, E, 4, 2>), grid, dim3(256), 0, st, p);    \
-        else if (ring) hipLaunchKernelGGL((gemm_nt_f32_ring_kernel<128, 2, 2, E, 3, 3>), grid, dim3(256), 0, st, p);       \
-        else if (narrow) hipLaunchKernelGGL((gemm_nt_f32_kernel<64, 4, 1, E>), grid, dim3(256), 0, st, p);           \
-        else hipLaunchKernelGGL((gemm_nt_f32_kernel<128, 2, 2, E>), grid, dim3(256), 0, st, p);                      \
+        else hipLaunchKernelGGL((gemm_nt_f32_ring_kernel<128, 2, 2, E, 3, 3, 96>), grid, dim3(256), 0, st, p);              \
     } while (0)
     static const char* pro_ring_env = gg_dev_env("GG_GEMM_F32_PRO_RING");      // A/B: "0" = the register-staged prologue kernels
-    if (a->a_bn_stat && a->K <= 384 && !(pro_ring_env && pro_ring_env[0] == '0') && (p.debug & 5) == 0) {
+    if (a->a_bn_stat && a->K <= 384 && !(pro_ring_env && pro_ring_env[0] == '0')) {
         // prologue GEMMs on the LDS-DMA ring (single-buffer form): the transform is applied to the A fragments after the LDS read
         dim3 rgrid(p.tilesM * p.tilesN);
         if (a->A2 && rows_ok) {

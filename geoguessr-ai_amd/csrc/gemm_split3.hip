@@ -11,20 +11,19 @@
 //   * tile 256 x 128, k-stage 32 (one v_mfma_f32_16x16x32_bf16 step), 512 threads = 4 x 2 waves (64 x 64 per wave: 4 x 4 MFMA tiles x 6 products = 96 MFMAs per
 //     24 fragment reads and stage; the 128 x 128 / 64 x 32-per-wave form moves 1.5 x the LDS bytes per MFMA and sits at the LDS-port / MFMA balance point);
 //   * LDS-DMA (`buffer_load ... lds`, 16 B per lane, no VGPR staging) into a 2-stage ring of 6 plane tiles (72 KB per stage: 144 KB, one workgroup per CU), rows of 64 bytes with the
-//     16-byte chunk index XOR-ed with s3_swz((row >> 2) & 3, p.swz_plain) on the SOURCE side of the DMA, so the fragment reads (ds_read_b128: 16 rows x one chunk) are
+//     16-byte chunk index XOR-ed with s3_swz((row >> 2) & 3) on the SOURCE side of the DMA, so the fragment reads (ds_read_b128: 16 rows x one chunk) are
 //     conflict-free without padding (s3_swz: the permutation the instruction's 16-lane service groups need);
 //   * one raw s_barrier per stage, the next stage's DMA in flight under the current stage's 96 MFMAs; two waves per SIMD.
 // Epilogues: the Linear family of the model (bias, GELU with a saved pre-activation, rowscale + residual, x GELU'), results as f32 and / or as planes for the
 // next split GEMM.  The fp32_split mode of csrc/tinyvit.hip runs on the forms further down (gemm_nt_split3a / b_kernel: A as f32, split in the loader); this
 // plane-fed form is what they are checked against bit for bit (tests/test_gpu_kernels.py) and what tools/bench_split3.py times next to the f32-MFMA GEMM.
 // What the A-as-f32 forms add (round 6): compile-time epilogue classes (split3_epilogue_rows_ec), non-temporal result stores, an optional act(BatchNorm(A)) prologue in
-// the loader (gg_gemm_nt_split3_af32_pro), the conflict-free chunk permutation s3_swz, a 32 x 32 x 16 MFMA variant kept as a measured alternative (gemm_nt_split3w_kernel);
-// what bounds them -- the chip's power limit on random data, not a pipe -- is in DESIGN.md 5.
+// the loader (gg_gemm_nt_split3_af32_pro), the conflict-free chunk permutation s3_swz; what bounds them -- the chip's power limit on random data, not a pipe -- is in
+// DESIGN.md 5.  The alternatives measured against these forms (a persistent and a software-pipelined plane-fed form, the plain-XOR swizzle, cache-policy variants,
+// a 32 x 32 x 16 MFMA form, a packed-FMA prologue, skewed / dispatch-order TN walks) were retired; their numbers are in profiles/.
 #include "common.h"
 #include <type_traits>
 #include <algorithm>
-#include <mutex>
-#include <vector>
 #include <stdlib.h>
 #include <string.h>
 #include "../../include/gg.h"
@@ -46,7 +45,6 @@ struct Split3Params {
     const float* dact_preact; int dact;
     bf16* c_planes; int64_t ldp;
     const float* a_stat; const float* a_gamma; const float* a_beta; int a_act;      // A prologue (gemm_nt_split3a_kernel<..., PRO>): A := a_act(BatchNorm(A)), a_stat = [mean | rstd][K]
-    int swz_plain;                     // dev A/B: 1 = the round-5 chunk swizzle (plain XOR with the row quad: 2-way bank conflicts on every fragment read)
     float* colstats;                   // BatchNorm partials [ceil(M / 128)][2][N] (column sums of the result and of its square per 128-row block; plain epilogue only) or null
 };
 
@@ -109,21 +107,16 @@ __device__ __forceinline__ void split3_epilogue4(const Split3Params& p, f32x4 v,
 //   2: pre = acc + bias;  C = GELU(pre)                  (fc1 forward; pre-activation saved)
 //   3: C = acc * GELU'(saved pre-activation) [* scale]   (fc2 data gradient)
 //   4: C = (acc + bias) [* scale] + residual             (proj / fc2 forward)
-template <int BM, int BN, int NTHR, int HINT, int EC>
+// The results (and the saved pre-activation) are stored non-temporally.
+template <int BM, int BN, int NTHR, int EC>
 __device__ __forceinline__ void split3_epilogue_rows_ec(const Split3Params& p, const float* Ct, int m0, int n0) {
     constexpr int LDT = BN + 4, CPR = BN / 8, RPP = NTHR / CPR, NR = (BM + RPP - 1) / RPP;
     if ((int)threadIdx.x >= RPP * CPR) return;
     const int chunk = threadIdx.x % CPR, r0 = threadIdx.x / CPR;
     const int n = n0 + chunk * 8;
     if (n >= p.N) return;                                           // (N % 8 == 0: a chunk is entirely inside or outside)
-    auto ldg = [&](const float* q) -> f32x4 {
-        if constexpr (HINT & 4) return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q));
-        else return *reinterpret_cast<const f32x4*>(q);
-    };
-    auto stg = [&](float* q, f32x4 t) {
-        if constexpr (HINT & 1) __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(q));
-        else *reinterpret_cast<f32x4*>(q) = t;
-    };
+    auto ldg = [&](const float* q) -> f32x4 { return *reinterpret_cast<const f32x4*>(q); };
+    auto stg = [&](float* q, f32x4 t) { __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(q)); };
     f32x4 aux[(EC == 3 || EC == 4) ? NR : 1][2];
     if constexpr (EC == 3 || EC == 4) {
         const float* base = EC == 3 ? p.dact_preact : p.residual;
@@ -160,8 +153,8 @@ __device__ __forceinline__ void split3_epilogue_rows_ec(const Split3Params& p, c
 // Row-layout epilogue of a BM x BN tile: the accumulators cross LDS (the idle ring) so that every global access of the epilogue is a run of whole rows --
 // a lane owns 8 consecutive columns of a row, 16 lanes one 128-column row: 512-byte f32 runs and 256-byte plane runs instead of the MFMA layout's
 // 64- / 32-byte pieces of 16 different rows per instruction (the plane-writing epilogues of fc1 / the fc2 dgrad were slower than the f32 GEMM's with those)
-// HINT bits (cache policy experiments): 1 = result / pre-activation stores non-temporal, 4 = residual / saved-pre-activation loads non-temporal
-template <int BM, int BN, int NTHR, int HINT = 0>
+// NT: result / pre-activation stores non-temporal
+template <int BM, int BN, int NTHR, bool NT = false>
 __device__ __forceinline__ void split3_epilogue_rows(const Split3Params& p, float* Ct, int m0, int n0) {
     constexpr int LDT = BN + 4;                                   // padded row: conflict-free 16-byte column writes from the MFMA layout
     constexpr int CPR = BN / 8;                                   // 8-column chunks per row
@@ -190,9 +183,7 @@ __device__ __forceinline__ void split3_epilogue_rows(const Split3Params& p, floa
         auto ld8 = [&](const float* base, int64_t ld, float (&t)[8]) {
             const float* q = base + (int64_t)m * ld + n;
             if (nfull && (ld & 3) == 0) {
-                f32x4 a, b;
-                if constexpr (HINT & 4) { a = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q)); b = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q + 4)); }
-                else { a = *reinterpret_cast<const f32x4*>(q); b = *reinterpret_cast<const f32x4*>(q + 4); }
+                const f32x4 a = *reinterpret_cast<const f32x4*>(q), b = *reinterpret_cast<const f32x4*>(q + 4);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { t[j] = a[j]; t[4 + j] = b[j]; }
             } else {
@@ -203,7 +194,7 @@ __device__ __forceinline__ void split3_epilogue_rows(const Split3Params& p, floa
         auto st8 = [&](float* base, int64_t ld, const float (&t)[8]) {
             float* q = base + (int64_t)m * ld + n;
             if (nfull && (ld & 3) == 0) {
-                if constexpr (HINT & 1) {
+                if constexpr (NT) {
                     __builtin_nontemporal_store((f32x4){t[0], t[1], t[2], t[3]}, reinterpret_cast<f32x4*>(q));
                     __builtin_nontemporal_store((f32x4){t[4], t[5], t[6], t[7]}, reinterpret_cast<f32x4*>(q + 4));
                 } else {
@@ -297,11 +288,11 @@ constexpr int S3_STAGE = 6 * S3_TILE;                          // a1 a2 a3 b1 b2
 // different positions.  The plain XOR (position = c ^ q) maps (q 0, lg 0) and (q 1, lg 1) to the same position: a 2-way conflict in every group, every
 // fragment read took 8 instead of 4 LDS cycles (SQ_LDS_BANK_CONFLICT = 4 cycles per ds_read_b128, 39 % of the LDS-active cycles:
 // profiles/r06_split_sq_counters.txt).  The permutation q -> {0, 2, 3, 1} makes every group a permutation of the 16 slots.
-__device__ __forceinline__ int s3_swz(int q, int plain = 0) { return plain ? q : (0x78 >> (2 * q)) & 3; }
+__device__ __forceinline__ int s3_swz(int q) { return (0x78 >> (2 * q)) & 3; }
 template <int N> __device__ __forceinline__ void wait_outstanding() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-// BM x BN tile, WM x WN waves (each (BM / WM) x (BN / WN)), NST ring stages; PIPE: fragments of stage s + 1 are read into a second register set under the MFMAs of stage s
-template <int BM, int BN, int WM, int WN, bool PIPE, int NST>
+// BM x BN tile, WM x WN waves (each (BM / WM) x (BN / WN)), NST ring stages
+template <int BM, int BN, int WM, int WN, int NST>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_split3_kernel(Split3Params p) {
     constexpr int NW = WM * WN, TM = BM / WM / 16, TN = BN / WN / 16;
     constexpr int SLA = BM / 16, SLB = BN / 16;                  // 16-row wave-slices (1 KB) of an A / B plane tile
@@ -309,7 +300,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_split3_kernel(Split3Para
     constexpr int DPS = 3 * (IA + IB);                           // ... per stage and wave
     constexpr int TA = BM * S3_SK, TB = BN * S3_SK, STAGE = 3 * (TA + TB);
     static_assert(IA * NW == SLA && IB * NW == SLB && IA >= 1 && IB >= 1, "waves must divide the slices of both plane tiles");
-    static_assert(!PIPE || NST == 3, "the pipelined form walks a 3-stage ring");
     extern __shared__ __attribute__((aligned(16))) bf16 s3mem[];
     const int tiles = p.tilesM * p.tilesN;
     const int bid = gg_xcd_remap(blockIdx.x, tiles);
@@ -320,7 +310,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_split3_kernel(Split3Para
     const int lr = lane & 15, lg = lane >> 4;
     // DMA geometry: slice sl = wave + NW j covers tile rows 16 sl .. 16 sl + 15: lane -> (row 16 sl + lane / 4, LDS chunk slot lane % 4); the slot holds SOURCE chunk
     // slot ^ ((row >> 2) & 3) = slot ^ (lane >> 4) (16 sl does not touch bits 2-3)
-    const int dchunk = (lane & 3) ^ s3_swz(lane >> 4, p.swz_plain);
+    const int dchunk = (lane & 3) ^ s3_swz(lane >> 4);
     const unsigned rowsA = (unsigned)min(p.M - m0, BM), rowsB = (unsigned)min(p.N - n0, BN);
     __amdgpu_buffer_rsrc_t rs[6];
 #pragma unroll
@@ -349,7 +339,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_split3_kernel(Split3Para
         }
     };
     // fragment addresses: row (16 t + lr) of a plane tile, k-chunk lg -> slot lg ^ ((lr >> 2) & 3) (the tile index t does not touch bits 2-3 of the row)
-    const int fslot = (lg ^ s3_swz((lr >> 2) & 3, p.swz_plain)) * 8;
+    const int fslot = (lg ^ s3_swz((lr >> 2) & 3)) * 8;
     const int a_off = (wm * (BM / WM) + lr) * S3_SK + fslot, b_off = 3 * TA + (wn * (BN / WN) + lr) * S3_SK + fslot;
     f32x4 acc[TN][TM];
 #pragma unroll
@@ -377,31 +367,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_split3_kernel(Split3Para
 #undef S3_MFMA
     };
     issue_stage(0, s3mem);
-    if constexpr (PIPE) {
-        // 3-stage ring, software-pipelined: iteration s multiplies the fragments of stage s (already in registers) while the fragments of stage s + 1 are read
-        // from LDS into the other register set and the DMAs of stages s + 2 / s + 3 are in flight
-        bf16x8 xa[3][TM], wa[3][TN], xb[3][TM], wb[3][TN];
-        if (nk > 1) issue_stage(1, s3mem + STAGE);
-        if (nk > 2) issue_stage(2, s3mem + 2 * STAGE);
-        if (nk > 2) wait_outstanding<2 * DPS>(); else if (nk > 1) wait_outstanding<DPS>(); else wait_outstanding<0>();
-        __builtin_amdgcn_s_barrier();
-        frag_read(s3mem, xa, wa);
-        auto iter = [&](int s, int slot, bf16x8 (&xc)[3][TM], bf16x8 (&wc)[3][TN], bf16x8 (&xn)[3][TM], bf16x8 (&wn_)[3][TN]) {
-            const bool more = s + 1 < nk;
-            if (more) { if (s + 2 < nk) wait_outstanding<DPS>(); else wait_outstanding<0>(); }      // stage s + 1 landed
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // own fragment reads of stage s are in registers ...
-            __builtin_amdgcn_s_barrier();                           // ... everybody's are: slot(s) may be refilled; everybody's DMAs of stage s + 1 have landed
-            if (s + 3 < nk) issue_stage(s + 3, s3mem + slot * STAGE);
-            if (more) frag_read(s3mem + (slot == 2 ? 0 : slot + 1) * STAGE, xn, wn_);
-            mfma_stage(xc, wc);
-        };
-        int slot = 0;
-        for (int s = 0; s < nk; s += 2) {
-            iter(s, slot, xa, wa, xb, wb);
-            slot = slot == 2 ? 0 : slot + 1;
-            if (s + 1 < nk) { iter(s + 1, slot, xb, wb, xa, wa); slot = slot == 2 ? 0 : slot + 1; }
-        }
-    } else if constexpr (NST == 3) {
+    if constexpr (NST == 3) {
         // 3-stage ring, two stages in flight: the DMA of stage s + 2 is issued when stage s starts
         if (nk > 1) issue_stage(1, s3mem + STAGE);
         int cb = 0;
@@ -482,94 +448,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_split3_kernel(Split3Para
     }
 }
 
-// Persistent form of the 2 x 4-wave kernel: one workgroup per CU walks tiles t, t + grid, ...; the first two stages of the NEXT tile are issued before the
-// current tile's epilogue, so the result stores and the next operands' latency overlap (with one 144 KB workgroup per CU nothing else would hide them:
-// at K = 384 a tile is 12 stages = 9 us of MFMAs next to ~1.5 us of first-operand latency and ~1 us of stores)
-__global__ __launch_bounds__(512) void gemm_nt_split3_persistent_kernel(Split3Params p) {
-    constexpr int WM = 2, WN = 4, NW = 8, TM = 4, TN = 2, DPS = 6;
-    extern __shared__ __attribute__((aligned(16))) bf16 s3mem[];
-    const int tiles = p.tilesM * p.tilesN;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm = wave / WN, wn = wave % WN;
-    const int lr = lane & 15, lg = lane >> 4;
-    const int dchunk = (lane & 3) ^ s3_swz(lane >> 4, p.swz_plain);
-    const unsigned row = (unsigned)(wave * 16 + (lane >> 2));
-    const unsigned voffA = row * (unsigned)p.lda * 2u + dchunk * 16u, voffB = row * (unsigned)p.ldb * 2u + dchunk * 16u;
-    const int fslot = (lg ^ s3_swz((lr >> 2) & 3, p.swz_plain)) * 8;
-    const int a_off = (wm * 64 + lr) * S3_SK + fslot, b_off = (wn * 32 + lr) * S3_SK + fslot;
-    const int nk = (p.K + S3_SK - 1) / S3_SK;
-    __amdgpu_buffer_rsrc_t rs[6];
-    auto set_tile = [&](int t, int& m0, int& n0) {
-        const int bid = gg_xcd_remap(t, tiles);
-        m0 = (bid / p.tilesN) * S3_BM; n0 = (bid % p.tilesN) * S3_BN;
-        const unsigned rowsA = (unsigned)min(p.M - m0, S3_BM), rowsB = (unsigned)min(p.N - n0, S3_BN);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            rs[i] = __builtin_amdgcn_make_buffer_rsrc((void*)(p.A + i * p.plane_a + (int64_t)m0 * p.lda), 0, (int)(rowsA * (unsigned)p.lda * 2u), 0x00020000);
-            rs[3 + i] = __builtin_amdgcn_make_buffer_rsrc((void*)(p.B + i * p.plane_b + (int64_t)n0 * p.ldb), 0, (int)(rowsB * (unsigned)p.ldb * 2u), 0x00020000);
-        }
-    };
-    auto issue_stage = [&](int st, bf16* base) {
-        const int k0 = st * S3_SK;
-        const bool kin = k0 + dchunk * 8 < p.K;
-#pragma unroll
-        for (int i = 0; i < 6; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[i], (__attribute__((address_space(3))) void*)(base + i * S3_TILE + wave * 512), 16,
-                                                     (int)(kin ? (i < 3 ? voffA : voffB) : 0xFFFFFFF0u), k0 * 2, 0, 0);
-    };
-    int m0, n0;
-    int t = blockIdx.x;
-    if (t >= tiles) return;
-    set_tile(t, m0, n0);
-    issue_stage(0, s3mem);
-    if (nk > 1) issue_stage(1, s3mem + S3_STAGE);
-    for (; t < tiles; t += gridDim.x) {
-        f32x4 acc[TN][TM];
-#pragma unroll
-        for (int i = 0; i < TN; ++i)
-#pragma unroll
-            for (int j = 0; j < TM; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        int cb = 0;
-        for (int s = 0; s < nk; ++s) {
-            bf16* const cur = s3mem + cb * S3_STAGE;
-            // (stage 0 of a tile: the previous tile's result stores were issued after this tile's first DMAs -- in-order return, so wait for everything)
-            if (s + 1 < nk && s > 0) wait_outstanding<DPS>(); else wait_outstanding<0>();
-            __builtin_amdgcn_s_barrier();
-            if (s + 2 < nk) issue_stage(s + 2, s3mem + (cb == 0 ? 2 : cb - 1) * S3_STAGE);
-            cb = cb == 2 ? 0 : cb + 1;
-            bf16x8 xf[3][TM], wf[3][TN];
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) {
-#pragma unroll
-                for (int mt = 0; mt < TM; ++mt) xf[pl][mt] = *reinterpret_cast<const bf16x8*>(cur + pl * S3_TILE + a_off + mt * 16 * S3_SK);
-#pragma unroll
-                for (int nt = 0; nt < TN; ++nt) wf[pl][nt] = *reinterpret_cast<const bf16x8*>(cur + (3 + pl) * S3_TILE + b_off + nt * 16 * S3_SK);
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#define S3_MFMA(PA, PB)                                                                                              \
-    _Pragma("unroll") for (int nt = 0; nt < TN; ++nt) _Pragma("unroll") for (int mt = 0; mt < TM; ++mt)             \
-        acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[PB][nt], xf[PA][mt], acc[nt][mt], 0, 0, 0)
-            S3_MFMA(0, 2); S3_MFMA(1, 1); S3_MFMA(2, 0);
-            S3_MFMA(0, 1); S3_MFMA(1, 0);
-            S3_MFMA(0, 0);
-#undef S3_MFMA
-        }
-        const int em0 = m0, en0 = n0;
-        // next tile's first operands: every wave has read the last stage's fragments once it passes this barrier, so slots 0 / 1 are free
-        // (the next tile starts its ring at slot 0 again)
-        __builtin_amdgcn_s_barrier();
-        if (t + (int)gridDim.x < tiles) {
-            set_tile(t + gridDim.x, m0, n0);
-            issue_stage(0, s3mem);
-            if (nk > 1) issue_stage(1, s3mem + S3_STAGE);
-        }
-#pragma unroll
-        for (int nt = 0; nt < TN; ++nt)
-#pragma unroll
-            for (int mt = 0; mt < TM; ++mt) split3_epilogue4(p, acc[nt][mt], em0 + wm * 64 + mt * 16 + lr, en0 + wn * 32 + nt * 16 + lg * 4);
-    }
-}
-
 // ------------------------------------------------------------------------------------------- A as f32, split while it is staged
 // The form every Linear of the model can take: the activation operand stays the f32 tensor its producer wrote (no plane copy in HBM: 6 instead of 4 bytes per
 // element, and a producer epilogue that has to write it), only the WEIGHT comes as cached planes.  Tile 256 x 128, 4 x 2 waves of 64 x 64, k-stage 32, 2-stage
@@ -583,11 +461,10 @@ template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_wai
 // PRO: the A operand is a saved pre-BatchNorm convolution output and the product wants act(BatchNorm(A)) (MBConv conv3 reading BN2 + GELU of the depthwise conv): the
 // transform rides on the loader, in front of the split -- per element one FMA with the column's (scale, shift) from an LDS table + the f32-accurate GELU; with one N-tile
 // (N = 96) every element is transformed exactly once and the activation tensor is never written (the f32-MFMA form of this fusion applied it to the fragments of every wave)
-template <int ABL, int TN_ = 4, int EC = 0, int PRO = 0>      // PRO: 0 off; 1 + activation code of the prologue (1 BatchNorm only, 2 + GELU, 3 + QuickGELU): compile-time, so a stage carries one activation's code
+template <int TN_ = 4, int EC = 0, int PRO = 0>      // PRO: 0 off; 1 + activation code of the prologue (1 BatchNorm only, 2 + GELU, 3 + QuickGELU): compile-time, so a stage carries one activation's code
 __global__ __launch_bounds__(512) void gemm_nt_split3a_kernel(Split3Params p) {
     constexpr int TN = TN_, BM = 256, BN = 32 * TN, WN = 2, NW = 8, TM = 4;
     constexpr int TA = BM * S3_SK, TB = BN * S3_SK, STAGE = 3 * (TA + TB);
-    constexpr int A_AUX = (ABL & 32) ? 2 : 0;                      // (cache-policy experiment: the f32 operand's loads non-temporal)
     extern __shared__ __attribute__((aligned(16))) bf16 s3mem[];
     const int tiles = p.tilesM * p.tilesN;
     const int bid = gg_xcd_remap(blockIdx.x, tiles);
@@ -598,7 +475,7 @@ __global__ __launch_bounds__(512) void gemm_nt_split3a_kernel(Split3Params p) {
     const int lr = lane & 15, lg = lane >> 4;
     const unsigned rowsA = (unsigned)min(p.M - m0, BM), rowsB = (unsigned)min(p.N - n0, BN);
     // B planes: 16-row slices by LDS-DMA (one per plane and wave: 8 slices = 128 rows), source chunk = slot ^ ((row >> 2) & 3)
-    const int dchunk = (lane & 3) ^ s3_swz(lane >> 4, p.swz_plain);
+    const int dchunk = (lane & 3) ^ s3_swz(lane >> 4);
     __amdgpu_buffer_rsrc_t rsB[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
@@ -613,7 +490,7 @@ __global__ __launch_bounds__(512) void gemm_nt_split3a_kernel(Split3Params p) {
     for (int j = 0; j < 4; ++j) {
         const int row = arow + 64 * j;
         voffA[j] = (unsigned)row * (unsigned)p.ldaf * 4u + kq * 16u;
-        ldsA[j] = row * S3_SK + (((kq >> 1) ^ s3_swz((row >> 2) & 3, p.swz_plain)) << 3) + ((kq & 1) << 2);
+        ldsA[j] = row * S3_SK + (((kq >> 1) ^ s3_swz((row >> 2) & 3)) << 3) + ((kq & 1) << 2);
     }
     // PRO: (scale, shift) per contraction column behind the ring: [2][KT] floats, zero beyond K (the masked stages then transform zeros into act(0) = 0)
     float* const ptab = reinterpret_cast<float*>(s3mem + 2 * STAGE);
@@ -630,7 +507,6 @@ __global__ __launch_bounds__(512) void gemm_nt_split3a_kernel(Split3Params p) {
         if constexpr (PRO) {
             const f32x4 sc = *reinterpret_cast<const f32x4*>(ptab + st * S3_SK + kq * 4), sh = *reinterpret_cast<const f32x4*>(ptab + KT + st * S3_SK + kq * 4);
             // (scalar FMAs on purpose: beside MFMAs a v_pk_fma_f32 costs far more than the two v_fma_f32 it replaces -- MI355X_MICROARCH.md, cycle constants)
-            if constexpr (PRO >= 5) return gg_act_f32_v4(v * sc + sh, PRO - 5);      // (dev A/B: the packed form)
             f32x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = gg_act_f32(fmaf(v[e], sc[e], sh[e]), PRO - 1);
@@ -651,7 +527,7 @@ __global__ __launch_bounds__(512) void gemm_nt_split3a_kernel(Split3Params p) {
         const int k0 = st * S3_SK;
         const bool kin = k0 + kq * 4 < p.K;                     // K % 4 == 0: an f32x4 is entirely inside or outside
 #pragma unroll
-        for (int j = 0; j < 4; ++j) r[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, (int)(kin ? voffA[j] : 0xFFFFFFF0u), k0 * 4, A_AUX));
+        for (int j = 0; j < 4; ++j) r[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, (int)(kin ? voffA[j] : 0xFFFFFFF0u), k0 * 4, 0));
     };
     auto split_store = [&](const f32x4 (&r)[4], bf16* base) {
 #pragma unroll
@@ -668,7 +544,7 @@ __global__ __launch_bounds__(512) void gemm_nt_split3a_kernel(Split3Params p) {
             *reinterpret_cast<bf16x4*>(base + 2 * TA + ldsA[j]) = p3;
         }
     };
-    const int fslot = (lg ^ s3_swz((lr >> 2) & 3, p.swz_plain)) * 8;
+    const int fslot = (lg ^ s3_swz((lr >> 2) & 3)) * 8;
     const int a_off = (wm * 64 + lr) * S3_SK + fslot, b_off = 3 * TA + (wn * 16 * TN + lr) * S3_SK + fslot;
     f32x4 acc[TN][TM];
 #pragma unroll
@@ -700,16 +576,10 @@ __global__ __launch_bounds__(512) void gemm_nt_split3a_kernel(Split3Params p) {
         wait_vm<4>();                                               // B(s) and A(s + 1) have landed; A(s + 2) may be in flight
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // own plane writes of A(s) are done ...
         __builtin_amdgcn_s_barrier();                               // ... everybody's are, and every wave has read its fragments of stage s - 1: that slot is free
-        if (!(ABL & 8)) issue_b(s + 1, nxt);
+        issue_b(s + 1, nxt);
         bf16x8 xf[3][TM], wf[3][TN];
-        if (ABL & 2) {
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-                for (int t = 0; t < 4; ++t) { xf[pl][t] = __builtin_bit_cast(bf16x8, acc[0][t]); if (t < TN) wf[pl][t] = __builtin_bit_cast(bf16x8, acc[1][t]); }
-        }
-        auto rd_a1 = [&](int pl, int mt) { if (!(ABL & 2)) xf[pl][mt] = *reinterpret_cast<const bf16x8*>(cur + pl * TA + a_off + mt * 16 * S3_SK); };
-        auto rd_b1 = [&](int pl, int nt) { if (!(ABL & 2)) wf[pl][nt] = *reinterpret_cast<const bf16x8*>(cur + pl * TB + b_off + nt * 16 * S3_SK); };
+        auto rd_a1 = [&](int pl, int mt) { xf[pl][mt] = *reinterpret_cast<const bf16x8*>(cur + pl * TA + a_off + mt * 16 * S3_SK); };
+        auto rd_b1 = [&](int pl, int nt) { wf[pl][nt] = *reinterpret_cast<const bf16x8*>(cur + pl * TB + b_off + nt * 16 * S3_SK); };
 #pragma unroll
         for (int t = 0; t < 4; ++t) { rd_a1(0, t); if (t < TN) rd_b1(2, t); }
         const int k3 = (s + 3) * S3_SK;
@@ -721,10 +591,7 @@ __global__ __launch_bounds__(512) void gemm_nt_split3a_kernel(Split3Params p) {
 #pragma unroll
             for (int nt = 0; nt < TN; ++nt) {
 #pragma unroll
-                for (int mt = 0; mt < TM; ++mt) {
-                    if (!(ABL & 1)) acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[PB[g]][nt], xf[PA[g]][mt], acc[nt][mt], 0, 0, 0);
-                    else { acc[nt][mt][0] += (float)wf[PB[g]][nt][0]; acc[nt][mt][1] += (float)xf[PA[g]][mt][0]; }
-                }
+                for (int mt = 0; mt < TM; ++mt) acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[PB[g]][nt], xf[PA[g]][mt], acc[nt][mt], 0, 0, 0);
                 constexpr int Q = 6 * TN;                           // quads per stage; the split's 12 slices go to the quads with (12 qi) mod Q < 12
                 const int qi = g * TN + nt;
                 if (g < 2) {                                        // a2, b2 under the first product group; a3, b1 under the second: three reads per quad
@@ -734,7 +601,7 @@ __global__ __launch_bounds__(512) void gemm_nt_split3a_kernel(Split3Params p) {
                         else if (idx - 4 < TN) rd_b1(1 - g, idx - 4);
                     }
                 }
-                if ((qi * 12) % Q < 12 && !(ABL & 4)) {
+                if ((qi * 12) % Q < 12) {
                     const int ms = (qi * 12) / Q, jj = ms / 3, part = ms % 3;
                     if (part < 2) {
                         if (PRO && part == 0) rnext[jj] = pro4(rnext[jj], s + 1);      // (the row's four columns at once: two packed GELU evaluations)
@@ -748,7 +615,7 @@ __global__ __launch_bounds__(512) void gemm_nt_split3a_kernel(Split3Params p) {
                         *reinterpret_cast<bf16x4*>(nxt + ldsA[jj]) = p1;
                         *reinterpret_cast<bf16x4*>(nxt + TA + ldsA[jj]) = p2;
                         *reinterpret_cast<bf16x4*>(nxt + 2 * TA + ldsA[jj]) = p3;
-                        rnext[jj] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, (int)(kin3 ? voffA[jj] : 0xFFFFFFF0u), k3 * 4, A_AUX));
+                        rnext[jj] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, (int)(kin3 ? voffA[jj] : 0xFFFFFFF0u), k3 * 4, 0));
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -770,174 +637,8 @@ __global__ __launch_bounds__(512) void gemm_nt_split3a_kernel(Split3Params p) {
         for (int mt = 0; mt < TM; ++mt)
             *reinterpret_cast<f32x4*>(Ct + (wm * 64 + mt * 16 + lr) * (BN + 4) + wn * 16 * TN + nt * 16 + lg * 4) = acc[nt][mt];
     __syncthreads();
-    if constexpr (EC == 0) split3_epilogue_rows<BM, BN, 512, ((ABL & 16) ? 1 : 0) | ((ABL & 64) ? 4 : 0)>(p, Ct, m0, n0);
-    else split3_epilogue_rows_ec<BM, BN, 512, ((ABL & 16) ? 1 : 0) | ((ABL & 64) ? 4 : 0), EC>(p, Ct, m0, n0);
-}
-
-// The 256 x 128 form on v_mfma_f32_32x32x16_bf16 (the default for 128-column tiles).  Same tile, ring, loader, split and epilogue as gemm_nt_split3a_kernel; a wave's
-// 64 x 64 is 2 x 2 tiles of 32 x 32 and a 32-deep stage is two 16-deep MFMA steps: 48 instructions of 32 cycles instead of 96 of 16.  Why: an MFMA holds the SIMD's
-// vector issue for 8 cycles whatever its shape (MI355X_MICROARCH.md, cycle constants), and this kernel carries ~125 vector instructions per wave and stage next to its
-// MFMAs (the split of A: cvt / shift / subtract, 11 per pair of elements, plus the first-term clamp).  With 16-cycle MFMAs the two waves of a SIMD ask for
-// 2 x (96 x 8 + ~125 x 4.5) = 2 650 of the stage's 3 072 issue cycles -- any slip idles the matrix pipe, and it ran at 61-67 % (SQ counters:
-// profiles/r06_split_sq_counters.txt: wait_inst 0.46, no LDS conflicts left); with 32-cycle MFMAs the same work asks for 1 900.
-// Fragments: lane l holds row (l & 31), k = 8 (l >> 5) + 0..7 of a 32 x 16 operand block; the two 16-byte chunks of a k-step sit at positions (2 ks + (l >> 5)) ^ ((row >> 2) & 3)
-// of the row's 64 bytes -- for 32-row fragments the plain XOR is what ds_read_b128's 16-lane service groups need (rows {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} of one chunk:
-// row quads {0, 3, 5, 6} / {1, 2, 4, 7} take four different positions).  Result tile: lane holds column m = l & 31, rows n = (r & 3) + 8 (r >> 2) + 4 (l >> 5).
-// The k-order of the accumulation differs from the 16 x 16 x 32 kernels' (two 16-deep steps per product instead of one 32-deep): results agree with theirs to rounding, not bit for bit.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-template <int HINT>
-__global__ __launch_bounds__(512) void gemm_nt_split3w_kernel(Split3Params p) {
-    constexpr int BM = 256, BN = 128, WN = 2, TM = 2, TN = 2;
-    constexpr int TA = BM * S3_SK, TB = BN * S3_SK, STAGE = 3 * (TA + TB);
-    constexpr int A_AUX = (HINT & 32) ? 2 : 0;
-    extern __shared__ __attribute__((aligned(16))) bf16 s3mem[];
-    const int tiles = p.tilesM * p.tilesN;
-    const int bid = gg_xcd_remap(blockIdx.x, tiles);
-    const int tm = bid / p.tilesN, tn = bid % p.tilesN;
-    const int m0 = tm * BM, n0 = tn * BN;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wm = wave / WN, wn = wave % WN;
-    const int l32 = lane & 31, lh = lane >> 5;
-    const unsigned rowsA = (unsigned)min(p.M - m0, BM), rowsB = (unsigned)min(p.N - n0, BN);
-    // B planes: 16-row slices by LDS-DMA (one per plane and wave), lane -> (row 16 sl + lane / 4, slot lane % 4); the slot holds SOURCE chunk slot ^ ((row >> 2) & 3) = slot ^ (lane >> 4)
-    const int dchunk = (lane & 3) ^ (lane >> 4);
-    __amdgpu_buffer_rsrc_t rsB[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        rsB[i] = __builtin_amdgcn_make_buffer_rsrc((void*)(p.B + i * p.plane_b + (int64_t)n0 * p.ldb), 0, (int)(rowsB * (unsigned)p.ldb * 2u), 0x00020000);
-    const unsigned voffB = (unsigned)(wave * 16 + (lane >> 2)) * (unsigned)p.ldb * 2u + dchunk * 16u;
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)(p.Af + (int64_t)m0 * p.ldaf), 0, (int)(rowsA * (unsigned)p.ldaf * 4u), 0x00020000);
-    const int kq = threadIdx.x & 7, arow = threadIdx.x >> 3;
-    unsigned voffA[4];
-    int ldsA[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int row = arow + 64 * j;
-        voffA[j] = (unsigned)row * (unsigned)p.ldaf * 4u + kq * 16u;
-        ldsA[j] = row * S3_SK + (((kq >> 1) ^ ((row >> 2) & 3)) << 3) + ((kq & 1) << 2);
-    }
-    auto issue_b = [&](int st, bf16* base) {
-        const int k0 = st * S3_SK;
-        const bool kin = k0 + dchunk * 8 < p.K;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB[i], (__attribute__((address_space(3))) void*)(base + 3 * TA + i * TB + wave * 512), 16,
-                                                     (int)(kin ? voffB : 0xFFFFFFF0u), k0 * 2, 0, 0);
-    };
-    auto load_a = [&](int st, f32x4 (&r)[4]) {
-        const int k0 = st * S3_SK;
-        const bool kin = k0 + kq * 4 < p.K;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) r[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, (int)(kin ? voffA[j] : 0xFFFFFFF0u), k0 * 4, A_AUX));
-    };
-    auto split_store = [&](const f32x4 (&r)[4], bf16* base) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            bf16x4 p1, p2, p3;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                bf16 s1_, s2_, s3_;
-                gg_split3_rne(r[j][e], s1_, s2_, s3_);
-                p1[e] = s1_; p2[e] = s2_; p3[e] = s3_;
-            }
-            *reinterpret_cast<bf16x4*>(base + ldsA[j]) = p1;
-            *reinterpret_cast<bf16x4*>(base + TA + ldsA[j]) = p2;
-            *reinterpret_cast<bf16x4*>(base + 2 * TA + ldsA[j]) = p3;
-        }
-    };
-    // fragment t = 2 tile + ks of a plane: row 32 tile + l32 of the wave's 64, chunk position (2 ks + lh) ^ ((l32 >> 2) & 3)
-    const int fsw = (l32 >> 2) & 3;
-    const int fpos0 = ((0 + lh) ^ fsw) * 8, fpos1 = ((2 + lh) ^ fsw) * 8;
-    const int a_off = (wm * 64 + l32) * S3_SK, b_off = 3 * TA + (wn * 64 + l32) * S3_SK;
-    f32x16 acc[TN][TM];
-#pragma unroll
-    for (int i = 0; i < TN; ++i)
-#pragma unroll
-        for (int j = 0; j < TM; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-    const int nk = (p.K + S3_SK - 1) / S3_SK;
-    f32x4 ra[2][4];
-    issue_b(0, s3mem);
-    load_a(0, ra[0]);
-    load_a(1, ra[1]);
-    wait_vm<4>();                                                   // B(0) and A(0)
-    split_store(ra[0], s3mem);
-    load_a(2, ra[0]);
-    // One stage = 24 units of two MFMAs (one 32 x 32 tile of one plane product, both k-steps), in issue order; between them, on every second unit, a slice of the split
-    // of A(s + 1) (two elements / the plane writes + the reload with A(s + 3)); the fragment reads of the second and third product group ride under the first and second.
-    auto stage = [&](int s, f32x4 (&rnext)[4]) {
-        bf16* const cur = s3mem + (s & 1) * STAGE;
-        bf16* const nxt = s3mem + ((s + 1) & 1) * STAGE;
-        wait_vm<4>();                                               // B(s) and A(s + 1) have landed; A(s + 2) may be in flight
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // own plane writes of A(s) are done ...
-        __builtin_amdgcn_s_barrier();                               // ... everybody's are, and every wave has read its fragments of stage s - 1: that slot is free
-        issue_b(s + 1, nxt);
-        bf16x8 xf[3][4], wf[3][4];
-        auto rd_a1 = [&](int pl, int t) { xf[pl][t] = *reinterpret_cast<const bf16x8*>(cur + pl * TA + a_off + (t >> 1) * 32 * S3_SK + ((t & 1) ? fpos1 : fpos0)); };
-        auto rd_b1 = [&](int pl, int t) { wf[pl][t] = *reinterpret_cast<const bf16x8*>(cur + pl * TB + b_off + (t >> 1) * 32 * S3_SK + ((t & 1) ? fpos1 : fpos0)); };
-#pragma unroll
-        for (int t = 0; t < 4; ++t) { rd_a1(0, t); rd_b1(2, t); }
-        const int k3 = (s + 3) * S3_SK;
-        const bool kin3 = k3 + kq * 4 < p.K;
-        bf16x4 p1, p2, p3;
-        constexpr int PA[6] = {0, 1, 2, 0, 1, 0}, PB[6] = {2, 1, 0, 1, 0, 0};      // small terms first: (a1 b3 + a2 b2 + a3 b1), (a1 b2 + a2 b1), a1 b1
-#pragma unroll
-        for (int g = 0; g < 6; ++g) {
-#pragma unroll
-            for (int nt = 0; nt < TN; ++nt) {
-#pragma unroll
-                for (int mt = 0; mt < TM; ++mt) {
-                    acc[nt][mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[PB[g]][2 * nt], xf[PA[g]][2 * mt], acc[nt][mt], 0, 0, 0);
-                    acc[nt][mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[PB[g]][2 * nt + 1], xf[PA[g]][2 * mt + 1], acc[nt][mt], 0, 0, 0);
-                    const int u = nt * TM + mt, qi = g * 4 + u;     // unit 0 .. 23
-                    if (g < 2) {                                    // a2, b2 under the first product group; a3, b1 under the second: two reads per unit
-#pragma unroll
-                        for (int idx = 2 * u; idx < 2 * u + 2; ++idx) {
-                            if (idx < 4) rd_a1(g + 1, idx);
-                            else rd_b1(1 - g, idx - 4);
-                        }
-                    }
-                    if ((qi & 1) == 0) {                            // the split's 12 slices on the even units
-                        const int ms = qi >> 1, jj = ms / 3, part = ms % 3;
-                        if (part < 2) {
-#pragma unroll
-                            for (int e = 2 * part; e < 2 * part + 2; ++e) {
-                                bf16 s1_, s2_, s3_;
-                                gg_split3_rne(rnext[jj][e], s1_, s2_, s3_);
-                                p1[e] = s1_; p2[e] = s2_; p3[e] = s3_;
-                            }
-                        } else {
-                            *reinterpret_cast<bf16x4*>(nxt + ldsA[jj]) = p1;
-                            *reinterpret_cast<bf16x4*>(nxt + TA + ldsA[jj]) = p2;
-                            *reinterpret_cast<bf16x4*>(nxt + 2 * TA + ldsA[jj]) = p3;
-                            rnext[jj] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, (int)(kin3 ? voffA[jj] : 0xFFFFFFF0u), k3 * 4, A_AUX));
-                        }
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-    };
-    for (int s = 0; s < nk; s += 2) {
-        stage(s, ra[1]);
-        if (s + 1 < nk) stage(s + 1, ra[0]);
-    }
-    wait_vm<0>();                                                   // (the masked loads / DMAs of the stages beyond K: nothing may land in the ring after this)
-    // epilogue: the accumulators cross the idle ring to whole rows (lane: column m = l32 of the tile, rows n = 8 q + 4 lh + 0..3)
-    float* Ct = reinterpret_cast<float*>(s3mem);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-#pragma unroll
-    for (int nt = 0; nt < TN; ++nt)
-#pragma unroll
-        for (int mt = 0; mt < TM; ++mt)
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                *reinterpret_cast<f32x4*>(Ct + (wm * 64 + mt * 32 + l32) * (BN + 4) + wn * 64 + nt * 32 + 8 * q + 4 * lh) =
-                    (f32x4){acc[nt][mt][4 * q], acc[nt][mt][4 * q + 1], acc[nt][mt][4 * q + 2], acc[nt][mt][4 * q + 3]};
-    __syncthreads();
-    split3_epilogue_rows<BM, BN, 512, ((HINT & 16) ? 1 : 0) | ((HINT & 64) ? 4 : 0)>(p, Ct, m0, n0);
+    if constexpr (EC == 0) split3_epilogue_rows<BM, BN, 512, true>(p, Ct, m0, n0);      // (non-temporal result stores)
+    else split3_epilogue_rows_ec<BM, BN, 512, EC>(p, Ct, m0, n0);
 }
 
 // The same product on a 128 x 128 tile with FOUR waves (2 x 2 of 64 x 64) and 72 KB of LDS, so that TWO workgroups share a CU: with one 144 KB workgroup per CU
@@ -960,7 +661,7 @@ __global__ __launch_bounds__(256) void gemm_nt_split3b_kernel(Split3Params p) {
     const int wm = wave / WN, wn = wave % WN;
     const int lr = lane & 15, lg = lane >> 4;
     const unsigned rowsA = (unsigned)min(p.M - m0, BM), rowsB = (unsigned)min(p.N - n0, BN);
-    const int dchunk = (lane & 3) ^ s3_swz(lane >> 4, p.swz_plain);
+    const int dchunk = (lane & 3) ^ s3_swz(lane >> 4);
     __amdgpu_buffer_rsrc_t rsB[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
@@ -976,7 +677,7 @@ __global__ __launch_bounds__(256) void gemm_nt_split3b_kernel(Split3Params p) {
     for (int j = 0; j < 4; ++j) {
         const int row = arow + 32 * j;
         voffA[j] = (unsigned)row * (unsigned)p.ldaf * 4u + kq * 16u;
-        ldsA[j] = row * S3_SK + (((kq >> 1) ^ s3_swz((row >> 2) & 3, p.swz_plain)) << 3) + ((kq & 1) << 2);
+        ldsA[j] = row * S3_SK + (((kq >> 1) ^ s3_swz((row >> 2) & 3)) << 3) + ((kq & 1) << 2);
     }
     auto issue_b = [&](int st) {
         bf16* const base = Bbuf + (st & 1) * 3 * TB;
@@ -1004,7 +705,7 @@ __global__ __launch_bounds__(256) void gemm_nt_split3b_kernel(Split3Params p) {
             p1[e] = s1_; p2[e] = s2_; p3[e] = s3_;
         }
     };
-    const int fslot = (lg ^ s3_swz((lr >> 2) & 3, p.swz_plain)) * 8;
+    const int fslot = (lg ^ s3_swz((lr >> 2) & 3)) * 8;
     const int a_off = (wm * 64 + lr) * S3_SK + fslot, b_off = (wn * 16 * TN + lr) * S3_SK + fslot;
     f32x4 acc[TN][TM];
 #pragma unroll
@@ -1083,8 +784,8 @@ __global__ __launch_bounds__(256) void gemm_nt_split3b_kernel(Split3Params p) {
         for (int mt = 0; mt < TM; ++mt)
             *reinterpret_cast<f32x4*>(Ct + (wm * 64 + mt * 16 + lr) * (BN + 4) + wn * 16 * TN + nt * 16 + lg * 4) = acc[nt][mt];
     __syncthreads();
-    if constexpr (EC == 0) split3_epilogue_rows<BM, BN, 256, 1>(p, Ct, m0, n0);      // (non-temporal result stores, as the 256 x 128 form)
-    else split3_epilogue_rows_ec<BM, BN, 256, 1, EC>(p, Ct, m0, n0);
+    if constexpr (EC == 0) split3_epilogue_rows<BM, BN, 256, true>(p, Ct, m0, n0);      // (non-temporal result stores, as the 256 x 128 form)
+    else split3_epilogue_rows_ec<BM, BN, 256, EC>(p, Ct, m0, n0);
 }
 
 // ------------------------------------------------------------------------------------------- weight gradient (TN), both operands f32
@@ -1101,21 +802,19 @@ struct Split3TnParams {
     float* part; int rows_per_split, tilesN, tilesK;
     int last_scale;                     // (M - 1) / rps: the row-scale index is clamped to it (rows beyond M -- zeros -- in a slab's last stages must not read past the array)
 };
-constexpr int TN3_SUB = 1024 + 32;                                 // elements of one 32-column sub-image of the TN kernel's plane images (skewed: see the kernel)
 __device__ __forceinline__ int s3_img_off(int row, int ch) { return row * 32 + ((ch ^ ((-(row >> 2)) & 3)) << 3); }
-template <int SUB_, bool REMAP>
 __global__ __launch_bounds__(512) void gemm_tn_split3_kernel(Split3TnParams p) {
     constexpr int BN = 256, BK = 128, WK = 2;
-    // plane images of one stage (bf16 elements): dY then X, as sub-images of 32 columns x 32 rows (SUB elements each: 1024, or 1024 + 32 -- the 64-byte skew that puts the
-    // two sub-images a 16-lane group of a plane write touches on different halves of the 128-byte bank window; at a pitch of exactly 2 KB every plane write is a 2-way
-    // conflict, 576 LDS cycles per stage, and yet the unskewed image is the faster one: see gg_gemm_tn_split3)
-    constexpr int SUB = SUB_;
+    // plane images of one stage (bf16 elements): dY then X, as sub-images of 32 columns x 32 rows (SUB = 1024 elements each).  At this pitch of exactly 2 KB every plane
+    // write is a 2-way bank conflict (576 LDS cycles per stage), and yet a 64-byte skew between sub-images, which removes them, measured 5-9 % slower: those conflict
+    // cycles hide under the MFMAs, the larger ring's offsets do not (profiles/r06_tn_split_ab.txt)
+    constexpr int SUB = 1024;
     constexpr int PY = (BN / 32) * SUB, PX = (BK / 32) * SUB, STAGE = 3 * (PY + PX);
     extern __shared__ __attribute__((aligned(16))) bf16 s3mem[];
     // XCD-contiguous walk: the tiles of one row slab are consecutive logical ids, so they run on ONE XCD at about the same time and its L2 serves the slab's dY / X rows to
     // all of them (in dispatch order the K-tiles of a slab sat on different XCDs: dY was fetched once per K-tile and X once per N-tile from HBM, 3-4 x the algorithmic bytes)
     const int tiles = p.tilesN * p.tilesK;
-    const int lid = REMAP ? gg_xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int lid = gg_xcd_remap(blockIdx.x, gridDim.x);
     const int t = lid % tiles, slab = lid / tiles;
     const int tn = t / p.tilesK, tk = t % p.tilesK;
     const int n0 = tn * BN, k0 = tk * BK;
@@ -1303,31 +1002,19 @@ extern "C" int gg_split3_bf16(const float* x, int64_t rows, int cols, int64_t ld
 
 static int split3_launch(Split3Params& p, void* stream) {
     const int M = p.M, N = p.N, K = p.K;
-    p.tilesM = (int)gg_cdiv(M, S3_BM); p.tilesN = (int)gg_cdiv(N, S3_BN);
-    // form: 0 = 128 x 128 tile, 2 x 4 waves, fragments read before the MFMAs, 3-stage ring; 1 = the same, software-pipelined; 2 = 2 x 2 waves (64 x 64 per
-    // wave), pipelined; 3 = form 0 as persistent workgroups with the next tile's first stages issued before the epilogue; 4 = 256 x 128 tile, 4 x 2 waves of
-    // 64 x 64 (96 MFMAs per 24 fragment reads, two waves per SIMD), 2-stage ring (default)
-    static const char* fenv = gg_dev_env("GG_SPLIT3_FORM");
-    const int form = fenv ? atoi(fenv) : (M > 128 ? 4 : 0);      // default: the 256 x 128 tile (64 x 64 per wave), the 128 x 128 one for a single row of tiles
-    const int fi = form >= 0 && form <= 4 ? form : 0;
-    void (*kern)(Split3Params) = fi == 4 ? gemm_nt_split3_kernel<256, 128, 4, 2, false, 2> : fi == 3 ? gemm_nt_split3_persistent_kernel :
-                                 fi == 2 ? gemm_nt_split3_kernel<128, 128, 2, 2, true, 3> : fi == 1 ? gemm_nt_split3_kernel<128, 128, 2, 4, true, 3> :
-                                           gemm_nt_split3_kernel<128, 128, 2, 4, false, 3>;
-    const int bm = fi == 4 ? 256 : 128;
-    p.tilesM = (int)gg_cdiv(M, bm);
-    const size_t lds = fi == 4 ? (size_t)2 * 3 * (256 + 128) * S3_SK * sizeof(bf16) : (size_t)3 * S3_STAGE * sizeof(bf16);
-    static bool raised[5] = {false, false, false, false, false};
-    if (!raised[fi]) {
-        GG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess,
-                 "gg_gemm_nt_split3: cannot raise the dynamic LDS limit");
-        raised[fi] = true;
-    }
+    // 256 x 128 tile, 4 x 2 waves of 64 x 64 (96 MFMAs per 24 fragment reads, two waves per SIMD), 2-stage ring; a single row of tiles (M <= 128) takes the
+    // 128 x 128 tile, 2 x 4 waves, 3-stage ring
+    const bool big = M > 128;
+    void (*kern)(Split3Params) = big ? gemm_nt_split3_kernel<256, 128, 4, 2, 2> : gemm_nt_split3_kernel<128, 128, 2, 4, 3>;
+    p.tilesM = (int)gg_cdiv(M, big ? 256 : 128); p.tilesN = (int)gg_cdiv(N, S3_BN);
+    const size_t lds = big ? (size_t)2 * 3 * (256 + 128) * S3_SK * sizeof(bf16) : (size_t)3 * S3_STAGE * sizeof(bf16);
+    GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(kern)));
     // algorithmic work = the fp32 product it replaces: 2 M N K flop; bytes: three bf16 planes per operand + the result (+ the epilogue's tensors)
     const double mn = (double)M * N;
     GG_PROF(GG_CAT_GEMM | GG_CAT_SPLIT_FLAG, 2.0 * M * (double)N * K,
             6.0 * ((double)M * K + (double)N * K) + 4.0 * mn * ((p.C != nullptr) + (p.preact != nullptr) + (p.residual != nullptr) + (p.dact_preact != nullptr)) +
                 (p.c_planes ? 6.0 * mn : 0.0), stream);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(fi == 3 ? std::min(p.tilesM * p.tilesN, 256) : p.tilesM * p.tilesN)), dim3(fi == 2 ? 256 : 512), lds, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(p.tilesM * p.tilesN)), dim3(512), lds, (hipStream_t)stream, p);
     GG_LAUNCH_CHECK();
     return 0;
 }
@@ -1343,7 +1030,6 @@ extern "C" int gg_gemm_nt_split3_ex(const GgSplit3Args* a, void* stream) {
     GG_CHECK(!a->rowscale || a->rows_per_scale > 0, "gg_gemm_nt_split3: rowscale needs rows_per_scale");
     GG_CHECK(!(a->dact_preact && a->act), "gg_gemm_nt_split3: act and dact_preact are exclusive");
     Split3Params p;
-    p.swz_plain = 0;
     p.a_stat = p.a_gamma = p.a_beta = nullptr; p.a_act = 0;
     p.A = (const bf16*)a->a_planes; p.lda = a->lda; p.plane_a = (int64_t)a->M * a->lda; p.Af = nullptr; p.ldaf = 0;
     p.B = (const bf16*)a->b_planes; p.ldb = a->ldb; p.plane_b = (int64_t)a->N * a->ldb;
@@ -1396,8 +1082,6 @@ static int split3_af32_launch(const GgSplit3Args* a, const float* A, int64_t lda
     GG_CHECK(((uintptr_t)a->preact & 15) == 0 && ((uintptr_t)a->residual & 15) == 0 && ((uintptr_t)a->dact_preact & 15) == 0,
              "gg_gemm_nt_split3_af32: preact, residual and dact_preact must be 16-byte aligned (the row epilogue moves them 16 bytes at a time)");
     Split3Params p;
-    static const char* senv = gg_dev_env("GG_SPLIT3_SWZ");      // dev A/B: 0 = the plain-XOR chunk swizzle of round 5
-    p.swz_plain = senv && atoi(senv) == 0;
     p.colstats = colstats;
     p.a_stat = bn_stat; p.a_gamma = bn_gamma; p.a_beta = bn_beta; p.a_act = bn_act;
     const bool pro = bn_stat != nullptr;
@@ -1417,13 +1101,6 @@ static int split3_af32_launch(const GgSplit3Args* a, const float* A, int64_t lda
     const bool n96 = nenv ? atoi(nenv) == 96 : (w128 - w96 >= 0.2);
     const int bn = n96 ? 96 : 128;
     p.tilesM = (int)gg_cdiv(p.M, big ? 256 : 128); p.tilesN = (int)gg_cdiv(p.N, bn);
-    // dev: ablations of the 256 x 128 form (1-8: results are garbage): 1 no MFMA, 2 no fragment reads, 4 no A path, 8 no B DMA; cache-policy variants (results unchanged):
-    // 16 non-temporal result stores (the default), 32 + non-temporal A loads, 64 + non-temporal epilogue loads, 256 = default-policy stores
-    static const char* aenv = gg_dev_env("GG_SPLIT3A_ABL");
-    const int abl = aenv ? atoi(aenv) : 16;
-    // dev: 32 = the 256 x 128 form on v_mfma_f32_32x32x16_bf16 (gemm_nt_split3w_kernel: 10 % fewer wave cycles, the same wall time at the clock the chip then holds)
-    static const char* menv = gg_dev_env("GG_SPLIT3A_MFMA");
-    const bool wide = menv && atoi(menv) == 32;
     // epilogue class (split3_epilogue_rows_ec) when the shape takes the vector path and the options are one of the model's four combinations; 0 = the generic epilogue
     static const char* eenv = gg_dev_env("GG_SPLIT3_NO_EC");       // dev: the generic epilogue everywhere
     int ec = 0;
@@ -1434,30 +1111,15 @@ static int split3_af32_launch(const GgSplit3Args* a, const float* A, int64_t lda
         else if (!p.act && !p.preact && !p.rowscale && !p.residual && !p.dact_preact) ec = 1;
     }
 #define S3_EC(K, ...) (ec == 1 ? K<__VA_ARGS__, 1> : ec == 2 ? K<__VA_ARGS__, 2> : ec == 3 ? K<__VA_ARGS__, 3> : ec == 4 ? K<__VA_ARGS__, 4> : K<__VA_ARGS__, 0>)
-    static const char* pkenv = gg_dev_env("GG_SPLIT3_PRO_PK");      // dev A/B: the prologue's GELU on packed FMAs
-    void (*kern)(Split3Params) = (pro && pkenv && bn_act == 1) ? (n96 ? gemm_nt_split3a_kernel<16, 3, 0, 6> : gemm_nt_split3a_kernel<16, 4, 0, 6>) : pro ? (n96 ? (bn_act == 1 ? gemm_nt_split3a_kernel<16, 3, 0, 2> : bn_act == 2 ? gemm_nt_split3a_kernel<16, 3, 0, 3> : gemm_nt_split3a_kernel<16, 3, 0, 1>)
-                                            : (bn_act == 1 ? gemm_nt_split3a_kernel<16, 4, 0, 2> : bn_act == 2 ? gemm_nt_split3a_kernel<16, 4, 0, 3> : gemm_nt_split3a_kernel<16, 4, 0, 1>)) :
-                                 !big ? (n96 ? S3_EC(gemm_nt_split3b_kernel, 3) : S3_EC(gemm_nt_split3b_kernel, 4)) : n96 ? S3_EC(gemm_nt_split3a_kernel, 16, 3) :
-                                 (!wide && abl == 16) ? S3_EC(gemm_nt_split3a_kernel, 16, 4) :
-                                 wide ? (abl == 256 ? gemm_nt_split3w_kernel<0> : abl == 48 ? gemm_nt_split3w_kernel<48> : gemm_nt_split3w_kernel<16>) :
-                                 abl == 1 ? gemm_nt_split3a_kernel<1> : abl == 2 ? gemm_nt_split3a_kernel<2> : abl == 4 ? gemm_nt_split3a_kernel<4> :
-                                 abl == 8 ? gemm_nt_split3a_kernel<8> : abl == 6 ? gemm_nt_split3a_kernel<6> : abl == 256 ? gemm_nt_split3a_kernel<0> :
-                                 abl == 32 ? gemm_nt_split3a_kernel<32> : abl == 48 ? gemm_nt_split3a_kernel<48> : abl == 80 ? gemm_nt_split3a_kernel<80> :
-                                 abl == 112 ? gemm_nt_split3a_kernel<112> : gemm_nt_split3a_kernel<16>;
+    void (*kern)(Split3Params) = pro ? (n96 ? (bn_act == 1 ? gemm_nt_split3a_kernel<3, 0, 2> : bn_act == 2 ? gemm_nt_split3a_kernel<3, 0, 3> : gemm_nt_split3a_kernel<3, 0, 1>)
+                                            : (bn_act == 1 ? gemm_nt_split3a_kernel<4, 0, 2> : bn_act == 2 ? gemm_nt_split3a_kernel<4, 0, 3> : gemm_nt_split3a_kernel<4, 0, 1>)) :
+                                 !big ? (n96 ? S3_EC(gemm_nt_split3b_kernel, 3) : S3_EC(gemm_nt_split3b_kernel, 4)) :
+                                        (n96 ? S3_EC(gemm_nt_split3a_kernel, 3) : S3_EC(gemm_nt_split3a_kernel, 4));
 #undef S3_EC
     const size_t lds = (big ? (size_t)2 * 3 * (256 + bn) * S3_SK * sizeof(bf16) : (size_t)3 * (128 + 2 * bn) * S3_SK * sizeof(bf16)) +
                        (pro ? (size_t)2 * (((p.K + 31) & ~31) + 3 * S3_SK) * sizeof(float) : 0);
     GG_CHECK(lds <= 160 * 1024, "gg_gemm_nt_split3_af32: the ring plus the prologue table exceed the LDS");
-    {
-        static std::mutex raised_mu;
-        static std::vector<const void*> raised;                    // kernels whose dynamic LDS limit has been raised (per kernel function, once)
-        std::lock_guard<std::mutex> lk(raised_mu);
-        const void* kp = reinterpret_cast<const void*>(kern);
-        if (std::find(raised.begin(), raised.end(), kp) == raised.end()) {
-            GG_CHECK(hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess, "gg_gemm_nt_split3_af32: cannot raise the dynamic LDS limit");
-            raised.push_back(kp);
-        }
-    }
+    GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(kern)));
     const double mn = (double)p.M * p.N;
     GG_PROF(GG_CAT_GEMM | GG_CAT_SPLIT_FLAG, 2.0 * p.M * (double)p.N * p.K,
             4.0 * (double)p.M * p.K + 6.0 * (double)p.N * p.K + 4.0 * mn * ((p.C != nullptr) + (p.preact != nullptr) + (p.residual != nullptr) + (p.dact_preact != nullptr)) +
@@ -1499,22 +1161,10 @@ extern "C" int gg_gemm_tn_split3(const float* dY, int64_t ldy, const float* X, i
     GG_CHECK((int64_t)p.rows_per_split * (splits - 1) < M, "gg_gemm_tn_split3: more splits than 32-row stages");
     GG_CHECK((int64_t)p.rows_per_split * std::max(ldy, ldx) * 4 < ((int64_t)1 << 31), "gg_gemm_tn_split3: a slab exceeds the 2 GiB descriptor range");
     p.tilesN = (int)gg_cdiv(N, 256); p.tilesK = (int)gg_cdiv(K, 128);
-    // dev A/B (same box, tools/bench_split3_tn.py, profiles/r06_tn_split_ab.txt): bit 0 = dispatch-order walk (no XCD-contiguous remap), bit 1 = sub-images skewed by 64 bytes.
-    // Default: remap, no skew -- the remap is worth 3-5 % (and cuts the HBM fetch 4 x); the skew removes every LDS bank conflict of the plane writes (SQ_LDS_BANK_CONFLICT
-    // 41 M -> 0 per launch) and still LOSES 5-9 %: those conflict cycles were hidden under the MFMAs, the 152 KB ring's larger offsets are not free
-    static const char* tenv = gg_dev_env("GG_SPLIT3_TN");
-    const int tv = tenv ? atoi(tenv) : 0;
-    void (*kern)(Split3TnParams) = tv == 1 ? gemm_tn_split3_kernel<1024, false> : tv == 2 ? gemm_tn_split3_kernel<TN3_SUB, true> : tv == 3 ? gemm_tn_split3_kernel<TN3_SUB, false> :
-                                   gemm_tn_split3_kernel<1024, true>;
-    const int sub = (tv & 2) ? TN3_SUB : 1024;
-    static bool raised[4] = {false, false, false, false};
-    if (!raised[tv & 3]) {
-        GG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess,
-                 "gg_gemm_tn_split3: cannot raise the dynamic LDS limit");
-        raised[tv & 3] = true;
-    }
+    // (the XCD-contiguous slab walk is worth 3-5 % and cuts the HBM fetch 4 x: profiles/r06_tn_split_ab.txt)
+    GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(gemm_tn_split3_kernel)));
     GG_PROF(GG_CAT_GEMM | GG_CAT_SPLIT_FLAG, 2.0 * M * (double)N * K, 4.0 * ((double)M * N + (double)M * K) + 8.0 * splits * (double)N * K, stream);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(p.tilesN * p.tilesK * splits)), dim3(512), (size_t)2 * 3 * (256 / 32 + 128 / 32) * sub * sizeof(bf16), (hipStream_t)stream, p);
+    hipLaunchKernelGGL(gemm_tn_split3_kernel, dim3((unsigned)(p.tilesN * p.tilesK * splits)), dim3(512), (size_t)2 * 3 * (256 / 32 + 128 / 32) * 1024 * sizeof(bf16), (hipStream_t)stream, p);
     GG_LAUNCH_CHECK();
     return 0;
 }

@@ -1,8 +1,9 @@
 """Every development switch of libgg (GG_*; read only when GG_DEV_SWITCHES is set) selects a kernel or schedule that is ALSO a product path --
 the fallback the default schedule takes for shapes its fast kernels do not cover (channel counts that are not multiples of 4, single
-windows, K above the prologue table, ...).  This file runs the same training-step parity check the default path gets (tools/switch_parity.py:
+windows, K above the prologue table, leading dimensions that are not multiples of 32, ...).  This file runs the same training-step parity check the default path gets (tools/switch_parity.py:
 TinyViT-5M step vs the CPU oracle, fp32 and bf16 modes, per-tensor gradients) with the switches set, in groups, one subprocess per group
 (the library reads a switch once per process)."""
+import json
 import os
 import subprocess
 import sys
@@ -16,11 +17,13 @@ GROUPS = {
     # every fusion off, every multi-column / multi-window / resident / ring form replaced by its plain fallback
     "plain_fallbacks": dict(GG_NO_FUSE_DW_S1="1", GG_NO_FUSE_DW_S2="1", GG_NO_FUSE_BNBWD="1", GG_NO_BNGEMM="1", GG_NO_PRO="1", GG_F32_NO_FUSE="1", GG_NO_LN_COLSUM="1",
                             GG_DW_NO_MULTI="1", GG_DW_F32_NO_MULTI="1", GG_ATTN_SMALL="0", GG_ATTN_FLASH_NO_RES="1", GG_ATTN_DQ_QS1="1",
-                            GG_GEMM_F32_SB="0", GG_GEMM_F32_ROWS_EPI="0", GG_ATTN_NO_DS_SCRATCH="1", GG_ATTN_NO_FUSED_BWD="1", GG_ATTN_FWD_NO_TAIL="1", GG_GEMM_F32_PRO_RING="0", GG_GEMM_F32_NO_W96="1",
+                            GG_GEMM_F32_ROWS_EPI="0", GG_ATTN_NO_DS_SCRATCH="1", GG_ATTN_NO_FUSED_BWD="1", GG_ATTN_FWD_NO_TAIL="1", GG_GEMM_F32_PRO_RING="0", GG_GEMM_F32_NO_W96="1",
                             GG_ATTN_NO_SPLIT="1", GG_GEMM_DMA="0", GG_GEMM_TILE="n", GG_GEMM_F32_NO_SMALL="1", GG_SWITCH_PARITY_FROZEN="1"),
-    # the older kernel generation: LDS-tiled depthwise, one-column fused forward, register-staged fp32 GEMM, 64-byte-run stores
-    "older_kernels": dict(GG_DW_TILED="1", GG_FUSE_DW="1", GG_NO_FUSE_BNBWD_EPI="1", GG_GEMM_F32_RING="0", GG_GEMM_F32_NO_PERSIST="1",
-                          GG_GEMM_F32_DEBUG="128", GG_DW_NO_MULTI_PLAIN="1", GG_DW_NO_MULTI_BWD="1", GG_DW_S2_TILED="1", GG_GEMM_TILE="w",
+    # the older kernel generation: LDS-tiled depthwise, one-column fused forward, the fp32 GEMM's general epilogue with 64-byte-run stores, the
+    # register-staged prologue GEMMs (the form K > 384 takes; GG_GEMM_F32_NO_PERSIST gives them one workgroup per tile -- at this test's shapes the
+    # grid is below their resident count either way, so it is exercised, not distinguished)
+    "older_kernels": dict(GG_DW_TILED="1", GG_FUSE_DW="1", GG_NO_FUSE_BNBWD_EPI="1", GG_GEMM_F32_ROWS_EPI="0", GG_GEMM_F32_PRO_RING="0", GG_GEMM_F32_NO_PERSIST="1",
+                          GG_GEMM_F32_NO_PAIR_STORE="1", GG_DW_NO_MULTI_PLAIN="1", GG_DW_NO_MULTI_BWD="1", GG_DW_S2_TILED="1", GG_GEMM_TILE="w",
                           GG_ATTN_NO_FUSED_BWD="1", GG_ATTN_NO_SPLIT="1", GG_GEMM_F32_NO_SPLITK="1", GG_GEMM_F32_SMALL_MAX="64", GG_SWITCH_PARITY_FROZEN="1"),       # (two-pass attention backward with the dS hand-off: the form for windows beyond 256 tokens)
     # the single-pass attention backward with one wave per key strip (no cooperative tail strip): the form every window whose strip count is not 4 n + 1 takes
     "attention_no_tail": dict(GG_ATTN_FUSED_NO_TAIL="1", GG_ATTN_NO_SPLIT="1", GG_SWITCH_PARITY_FROZEN="1"),
@@ -43,10 +46,17 @@ def test_parity_under_switch_group(group):
     assert r.stdout.count("-> ok") == 2
 
 
-def test_switches_are_inert_without_the_dev_gate():
-    """Without GG_DEV_SWITCHES a GG_* switch must not change anything: a timing-experiment value that would corrupt results (GG_GEMM_F32_DEBUG=2
-    drops the GEMM's result stores) still gives the correct step."""
-    env = dict(os.environ, GG_GEMM_F32_DEBUG="2", GG_GEMM_DEBUG="2", GG_SWITCH_PARITY_FROZEN="1")
-    env.pop("GG_DEV_SWITCHES", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "switch_parity.py")], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
-    assert r.returncode == 0 and r.stdout.count("-> ok") == 2, (r.stdout[-2000:], r.stderr[-2000:])
+def test_switches_are_inert_without_the_dev_gate(tmp_path):
+    """Without GG_DEV_SWITCHES a GG_* switch must not change anything: with switches set that would change the launch schedule if the gate leaked
+    (the prologue and depthwise fusions off), the step is correct and issues exactly the launches (category, flop, bytes per launch) of a run
+    without any GG_* switch."""
+    base = {k: v for k, v in os.environ.items() if not k.startswith("GG_") or k == "GG_LIB"}
+    logs = {}
+    for name, switches in (("none", {}), ("ungated", dict(GG_NO_PRO="1", GG_NO_FUSE_DW_S1="1", GG_F32_NO_FUSE="1"))):
+        log = tmp_path / f"{name}.json"
+        env = dict(base, GG_SWITCH_PARITY_FROZEN="1", GG_SWITCH_PARITY_LAUNCH_LOG=str(log), **switches)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "switch_parity.py")], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0 and r.stdout.count("-> ok") == 2, (name, r.stdout[-2000:], r.stderr[-2000:])
+        logs[name] = json.loads(log.read_text())
+    assert len(logs["none"]) > 0
+    assert logs["ungated"] == logs["none"]

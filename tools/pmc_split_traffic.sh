@@ -1,5 +1,5 @@
 # HBM fetch / write bytes per launch of the split-product kernels at the bench shapes (rocprofv3 PMC, FETCH_SIZE and WRITE_SIZE in separate passes; gfx950: FETCH_SIZE x 2,
-# both in KiB).  GPU box: [GG_DEV_SWITCHES=1 GG_SPLIT3A_ABL=16] bash tools/pmc_split_traffic.sh <tag> [kernel filters of tools/run_split_kernels.py ...]
+# both in KiB).  GPU box: bash tools/pmc_split_traffic.sh <tag> [kernel filters of tools/run_split_kernels.py ...]
 TAG=${1:-traffic}; shift
 R=$GRAFT_REPO_ROOT; export TMPDIR=/tmp; cd $R
 OUT=gpurun_out/${TAG}_split_traffic.txt
