@@ -65,7 +65,8 @@ class TinyVitCfg(C.Structure):
     _fields_ = [("img_size", C.c_int), ("in_chans", C.c_int), ("embed_dims", C.c_int * 4), ("depths", C.c_int * 4),
                 ("num_heads", C.c_int * 4), ("window_sizes", C.c_int * 4), ("mlp_ratio", C.c_float),
                 ("mbconv_expand_ratio", C.c_float), ("bn_eps", C.c_float), ("ln_eps", C.c_float),
-                ("bn_momentum", C.c_float), ("act_dtype", C.c_int), ("features_only", C.c_int)]
+                ("bn_momentum", C.c_float), ("act_dtype", C.c_int), ("features_only", C.c_int),
+                ("recompute", C.c_int)]
 
 
 class ClipCfg(C.Structure):

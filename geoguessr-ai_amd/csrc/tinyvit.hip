@@ -221,6 +221,27 @@ struct Plan {
         regs.push_back({name, shared_base, bytes});
         return shared_base;
     }
+    // Activation recompute (GgTinyVitCfg.recompute = 1, training): the tensors inside a segment (an MBConv, a PatchMerging, a TinyVitBlock) --
+    // everything but its output and its ConvNorms' .stat -- are laid out from the start of ONE segment region that every segment reuses (the
+    // backward re-forms a segment's tensors there right before its backward).  The frozen-mask temporaries and the re-formed act1 live there too:
+    // no ring, no gradient buffer aliases them.  `recomputed` holds their names (gg_tinyvit_activation_info refuses them).
+    bool rc = false;
+    int ds_force = -1;                   // rc: whether scratch.attn_ds exists is taken from the recompute-off plan (1 / 0; -1: decided here)
+    int64_t seg_base = 0, seg_cur = 0, max_seg = 0;
+    std::map<std::string, int> recomputed;
+    void seg_begin() { seg_cur = 0; }
+    int64_t alloc_seg(const std::string& name, int64_t bytes) {
+        bytes = gg_align(std::max<int64_t>(bytes, 16), 256);
+        const int64_t off = dry ? 0 : seg_base + seg_cur;
+        seg_cur += bytes;
+        max_seg = std::max(max_seg, seg_cur);
+        recomputed[name] = 1;
+        index[name] = (int)regs.size();
+        regs.push_back({name, off, bytes});
+        return off;
+    }
+    // a segment-internal tensor: the segment region under recompute, else its own storage (training) / the inference ring
+    int64_t alloc_in(const std::string& name, int64_t bytes) { return rc ? alloc_seg(name, bytes) : alloc(name, bytes); }
     // persistent: always gets its own storage; transient activations share a ring in inference mode
     int64_t alloc(const std::string& name, int64_t bytes, bool transient = true) {
         bytes = gg_align(std::max<int64_t>(bytes, 16), 256);
@@ -272,8 +293,8 @@ static void plan_build(const Model& m, int B, Plan& p, Layout& L) {
     int64_t gmax = 0, statmax = 0, bnsmax = 0, lnsmax = 0, csmax = 0;
     const int64_t es = m.es;
     auto track = [&](int64_t elems) { gmax = std::max(gmax, elems * es); };
-    auto bnreg = [&](const std::string& n, Act& a, int64_t M, int C, bool dw, int Bn, int Ho, int Wo) {
-        a.y = p.alloc(n + ".y", M * C * es);
+    auto bnreg = [&](const std::string& n, Act& a, int64_t M, int C, bool dw, int Bn, int Ho, int Wo, bool seg = true) {
+        a.y = seg ? p.alloc_in(n + ".y", M * C * es) : p.alloc(n + ".y", M * C * es);
         a.stat = p.alloc(n + ".stat", 2 * C * 4, false);
         statmax = std::max(statmax, bn_part_floats(M, C, Bn, Ho, Wo, dw) * 4);
         if (dw) statmax = std::max(statmax, (int64_t)gg_stat_rows_capacity(std::max(gg_dwconv_f32_stat_rows(Bn, Ho, Wo, C, 1), gg_dwconv_f32_stat_rows(Bn, Ho, Wo, C, 2))) * 2 * C * 4);
@@ -282,10 +303,10 @@ static void plan_build(const Model& m, int B, Plan& p, Layout& L) {
         track(M * C);
     };
     L.col1 = p.alloc("patch_embed.col1", M1 * 32 * es);
-    bnreg("patch_embed.conv1", L.pe1, M1, d[0] / 2, false, B, H1, H1);
+    bnreg("patch_embed.conv1", L.pe1, M1, d[0] / 2, false, B, H1, H1, false);      // (PatchEmbed is kept whole under recompute too)
     L.col2 = p.alloc("patch_embed.col2", M0 * m.pe2.w.Kp * es);
     track(M0 * m.pe2.w.Kp); track(M1 * 32);
-    bnreg("patch_embed.conv2", L.pe2, M0, d[0], false, B, H0, H0);
+    bnreg("patch_embed.conv2", L.pe2, M0, d[0], false, B, H0, H0, false);
     L.x_pe = p.alloc("patch_embed.out", M0 * d[0] * es);
     const int mid = (int)(d[0] * c.mbconv_expand_ratio);
     L.mb.resize(m.mb.size());
@@ -297,10 +318,11 @@ static void plan_build(const Model& m, int B, Plan& p, Layout& L) {
         // act1 = GELU(BN1(y1)): the fused depthwise forward never writes it (backward re-forms it as a temporary when conv2's taps train); unfused, it
         // is read again only by conv2's weight gradient.  act2 = GELU(BN2(y2)): conv3's input, kept only for conv3's weight gradient.
         const MBConvL& ml = m.mb[i];
+        p.seg_begin();
         bnreg(n + ".conv1", a.c1, M0, mid, false, B, H0, H0);
-        a.a1 = !p.tr(ml.c2.w.t_w) ? p.alloc_temp(n + ".act1", M0 * mid * es) : p.fwd_dw_s1 ? p.alloc_shared(n + ".act1", M0 * mid * es) : p.alloc(n + ".act1", M0 * mid * es);
+        a.a1 = p.rc ? p.alloc_seg(n + ".act1", M0 * mid * es) : !p.tr(ml.c2.w.t_w) ? p.alloc_temp(n + ".act1", M0 * mid * es) : p.fwd_dw_s1 ? p.alloc_shared(n + ".act1", M0 * mid * es) : p.alloc(n + ".act1", M0 * mid * es);
         bnreg(n + ".conv2", a.c2, M0, mid, true, B, H0, H0);
-        a.a2 = !p.tr(ml.c3.w.t_w) ? p.alloc_temp(n + ".act2", M0 * mid * es) : p.alloc(n + ".act2", M0 * mid * es);
+        a.a2 = p.rc ? p.alloc_seg(n + ".act2", M0 * mid * es) : !p.tr(ml.c3.w.t_w) ? p.alloc_temp(n + ".act2", M0 * mid * es) : p.alloc(n + ".act2", M0 * mid * es);
         bnreg(n + ".conv3", a.c3, M0, d[0], false, B, H0, H0);
         a.out = p.alloc(n + ".out", M0 * d[0] * es);
         prev = a.out;
@@ -313,10 +335,11 @@ static void plan_build(const Model& m, int B, Plan& p, Layout& L) {
         const int64_t M = (int64_t)B * st.res * st.res;
         const std::string n = "stages." + std::to_string(s + 1) + ".downsample";
         MergeAct& ma = L.merge[s];
+        p.seg_begin();
         bnreg(n + ".conv1", ma.c1, Mprev, C, false, B, res, res);
-        ma.a1 = !p.tr(st.merge.c2.w.t_w) ? p.alloc_temp(n + ".act1", Mprev * C * es) : p.fwd_dw_s2 ? p.alloc_shared(n + ".act1", Mprev * C * es) : p.alloc(n + ".act1", Mprev * C * es);
+        ma.a1 = p.rc ? p.alloc_seg(n + ".act1", Mprev * C * es) : !p.tr(st.merge.c2.w.t_w) ? p.alloc_temp(n + ".act1", Mprev * C * es) : p.fwd_dw_s2 ? p.alloc_shared(n + ".act1", Mprev * C * es) : p.alloc(n + ".act1", Mprev * C * es);
         bnreg(n + ".conv2", ma.c2, M, C, true, B, st.res, st.res);
-        ma.a2 = !p.tr(st.merge.c3.w.t_w) ? p.alloc_temp(n + ".act2", M * C * es) : p.alloc(n + ".act2", M * C * es);
+        ma.a2 = p.rc ? p.alloc_seg(n + ".act2", M * C * es) : !p.tr(st.merge.c3.w.t_w) ? p.alloc_temp(n + ".act2", M * C * es) : p.alloc(n + ".act2", M * C * es);
         bnreg(n + ".conv3", ma.c3, M, C, false, B, st.res, st.res);
         ma.out = p.alloc(n + ".out", M * C * es);
         prev = ma.out;
@@ -330,20 +353,22 @@ static void plan_build(const Model& m, int B, Plan& p, Layout& L) {
             // inputs of frozen Linears / of the frozen local conv are consumed once, right after they are written: ln1 -> qkv, x1 -> local_conv,
             // ln2 -> fc1, GELU(fc1) -> fc2 (the backward of a frozen block needs x0 / x2 / means for the LayerNorms, qkv / o / lse for the attention,
             // local_conv.y for its BatchNorm and the fc1 pre-activation for GELU'): 7 C of the block's 19 C floats per token
-            a.a = !p.tr(bl.qkv.t_w) ? p.alloc_temp(bn + ".ln1", M * C * es) : p.alloc(bn + ".ln1", M * C * es);
-            a.mean1 = p.alloc(bn + ".mean1", M * 4);
-            a.rstd1 = p.alloc(bn + ".rstd1", M * 4);
-            a.qkv = p.alloc(bn + ".qkv", M * 3 * C * es);
-            a.o = p.alloc(bn + ".attn.out", M * C * es);
-            a.lse = p.alloc(bn + ".attn.lse", M * st.heads * 4);
-            a.x1 = !p.tr(bl.local.w.t_w) ? p.alloc_temp(bn + ".x1", M * C * es) : p.alloc(bn + ".x1", M * C * es);
+            p.seg_begin();
+            auto keep = [&](bool trains, const std::string& nm, int64_t bytes) { return p.rc ? p.alloc_seg(nm, bytes) : !trains ? p.alloc_temp(nm, bytes) : p.alloc(nm, bytes); };
+            a.a = keep(p.tr(bl.qkv.t_w), bn + ".ln1", M * C * es);
+            a.mean1 = p.alloc_in(bn + ".mean1", M * 4);
+            a.rstd1 = p.alloc_in(bn + ".rstd1", M * 4);
+            a.qkv = p.alloc_in(bn + ".qkv", M * 3 * C * es);
+            a.o = p.alloc_in(bn + ".attn.out", M * C * es);
+            a.lse = p.alloc_in(bn + ".attn.lse", M * st.heads * 4);
+            a.x1 = keep(p.tr(bl.local.w.t_w), bn + ".x1", M * C * es);
             bnreg(bn + ".local_conv", a.local, M, C, true, B, st.res, st.res);
-            a.x2 = p.alloc(bn + ".x2", M * C * es);
-            a.b = !p.tr(bl.fc1.t_w) ? p.alloc_temp(bn + ".ln2", M * C * es) : p.alloc(bn + ".ln2", M * C * es);
-            a.mean2 = p.alloc(bn + ".mean2", M * 4);
-            a.rstd2 = p.alloc(bn + ".rstd2", M * 4);
-            a.hpre = p.alloc(bn + ".fc1.pre", M * hid * es);
-            a.h = !p.tr(bl.fc2.t_w) ? p.alloc_temp(bn + ".fc1.act", M * hid * es) : p.alloc(bn + ".fc1.act", M * hid * es);
+            a.x2 = p.alloc_in(bn + ".x2", M * C * es);
+            a.b = keep(p.tr(bl.fc1.t_w), bn + ".ln2", M * C * es);
+            a.mean2 = p.alloc_in(bn + ".mean2", M * 4);
+            a.rstd2 = p.alloc_in(bn + ".rstd2", M * 4);
+            a.hpre = p.alloc_in(bn + ".fc1.pre", M * hid * es);
+            a.h = keep(p.tr(bl.fc2.t_w), bn + ".fc1.act", M * hid * es);
             a.x3 = p.alloc(bn + ".out", M * C * es);
             prev = a.x3;
             track(M * hid); track(M * 3 * C);
@@ -385,7 +410,9 @@ static void plan_build(const Model& m, int B, Plan& p, Layout& L) {
                 if (!gg_attention_flash_single_pass(st.ws * st.ws, 32, st.ws, 1))
                     dsmax = std::max(dsmax, gg_attention_flash_ds_scratch_floats(nw, st.heads, st.ws * st.ws) * 4);
             }
-            if (dsmax > 0 && dsmax <= ((int64_t)4 << 30) && dsmax <= p.total / 8) L.attn_ds = p.alloc("scratch.attn_ds", dsmax, false);
+            // (under recompute the recompute-off plan decides: p.total differs, and the region selects the flash backward's route)
+            const bool ds = p.ds_force >= 0 ? p.ds_force == 1 : (dsmax > 0 && dsmax <= ((int64_t)4 << 30) && dsmax <= p.total / 8);
+            if (ds) L.attn_ds = p.alloc("scratch.attn_ds", dsmax, false);
         }
         int64_t fold = (int64_t)d[0] * 2 * mid;
         for (int s = 0; s < 3; ++s) fold = std::max(fold, (int64_t)(s == 0 ? d[0] : m.stages[s - 1].C) * 2 * m.stages[s].C);
@@ -412,7 +439,22 @@ static void plan_flags(const Model& m, Plan& p) {
     if (m.f32) fuse_dw = false;
     p.fwd_dw_s1 = fuse_dw || s1; p.fwd_dw_s2 = fuse_dw || s2; p.fwd_pro = pro;
 }
-static void plan_make(const Model& m, int B, bool training, Plan& p, Layout& L, const uint8_t* mask = nullptr) {
+static void plan_make(const Model& m, int B, bool training, Plan& p, Layout& L, const uint8_t* mask = nullptr, bool allow_rc = true) {
+    if (training && allow_rc && m.cfg.recompute) {
+        Plan off; Layout Loff;                     // the recompute-off plan: what it decides from its own size, the checkpointed one inherits
+        plan_make(m, B, true, off, Loff, mask, false);
+        Plan q;
+        q.training = true; q.mask = mask; q.rc = true; q.ds_force = Loff.attn_ds >= 0 ? 1 : 0;
+        plan_flags(m, q);
+        Plan dry = q; Layout Ld;                   // first pass: the segment region's size; second pass: the region first, then the rest
+        plan_build(m, B, dry, Ld);
+        q.dry = false; q.seg_base = 0; q.total = dry.max_seg;
+        plan_build(m, B, q, L);
+        q.index["scratch.segment"] = (int)q.regs.size();
+        q.regs.push_back({"scratch.segment", q.seg_base, q.max_seg});
+        p = q;
+        return;
+    }
     p.training = training;
     p.dry = true;
     p.mask = training ? mask : nullptr;
@@ -451,6 +493,9 @@ struct Exec {
     const float* drop;   // [slots][B] or null
     float* grads; const uint8_t* trainable;
     GgStageDoneFn stage_done = nullptr; void* stage_user = nullptr;     // host callback: the gradient of a stage is fully enqueued
+    // activation recompute: the backward runs a segment's forward body again (mbconv_fwd / merge_fwd / block_fwd) -- no BatchNorm statistics are
+    // finalised (the forward's .stat checkpoints are reused, the running buffers are not touched) and the segment's output is not rewritten
+    bool replay = false;
     void done(int stage) const { if (stage_done) stage_done(stage, stage_user); }
     // Fusing BatchNorm+GELU of the producer into the depthwise conv's input load removes one [M,C] write+read, but each input is
     // loaded (and transformed) by its three neighbouring columns: the erf work triples and the conv turns VALU-bound
@@ -556,6 +601,7 @@ static int gemm(const Exec& e, const act_t* A, int64_t lda, const act_t* Bm, int
 
 // BatchNorm statistics for a ConvNorm whose producer wrote `nparts` partial rows into statpart
 static int bn_stats(const Exec& e, const BNP& bn, const Act& a, int nparts, int64_t count) {
+    if (e.replay) return 0;      // recompute: (mean, rstd) are the forward's, already in a.stat
     if (e.training) {
         GG_TRY(gg_bn_finalize(e.F(e.L->statpart), nparts, bn.C, count, e.m->cfg.bn_eps, e.m->cfg.bn_momentum, e.F(a.stat),
                               e.buffers + bn.rm, e.buffers + bn.rv, e.st));
@@ -643,6 +689,91 @@ static void attn_args(const Exec& e, const StageL& st, const BlockL& l, const Bl
 }
 
 // ------------------------------------------------------------------------------------------- forward
+// One segment each: an MBConv of stage 0, a PatchMerging, a TinyVitBlock.  forward_impl runs them in order; under activation recompute
+// (GgTinyVitCfg.recompute = 1) backward_impl runs each again with e.replay right before the segment's backward: the same launches on the same
+// routes (fusion flags, split routing, the trainable-mask conditions), minus the segment's last launch -- the one that writes its output
+// checkpoint, which the segment's backward does not read -- and with no BatchNorm finalisation (bn_stats).
+static int64_t merge_input(const Layout& L, int s) {
+    return s == 0 ? (L.mb.empty() ? L.x_pe : L.mb.back().out) : (L.blocks[s - 1].empty() ? L.merge[s - 1].out : L.blocks[s - 1].back().x3);
+}
+static int mbconv_fwd(const Exec& e, size_t i, int slot) {
+    const Model& m = *e.m; const GgTinyVitCfg& c = m.cfg;
+    const int* d = c.embed_dims;
+    const int B = e.B, H0 = m.res0;
+    const int64_t M0 = (int64_t)B * H0 * H0;
+    const int mid = (int)(d[0] * c.mbconv_expand_ratio);
+    const MBConvL& l = m.mb[i]; const MBAct& a = e.L->mb[i];
+    GG_TRY(conv_dense_fwd(e, l.c1, a.c1, e.A(a.x), d[0], M0));
+    if (e.fuse_dw || e.fuse_dw_s1) {
+        GG_TRY(conv_dw_fwd_fused(e, l.c2, a.c2, l.c1.bn, a.c1, GG_ACT_GELU, B, H0, H0, 1));   // act1 is never materialised
+    } else {
+        GG_TRY(bn_apply(e, l.c1.bn, a.c1, M0, GG_ACT_GELU, e.A(a.a1)));
+        GG_TRY(conv_dw_fwd(e, l.c2, a.c2, e.A(a.a1), B, H0, H0, 1));
+    }
+    // conv3 reads BN2+GELU of conv2's output through its A prologue unless its weight gradient needs that tensor
+    if (e.fuse_pro && !(e.training && e.tr(l.c3.w.t_w)) && l.c3.w.Kp == mid && mid <= 1024 && l.c3.w.N <= 128) {
+        GG_TRY(conv_dense_fwd_pro(e, l.c3, a.c3, l.c2.bn, a.c2, GG_ACT_GELU, M0));
+    } else {
+        GG_TRY(bn_apply(e, l.c2.bn, a.c2, M0, GG_ACT_GELU, e.A(a.a2)));
+        GG_TRY(conv_dense_fwd(e, l.c3, a.c3, e.A(a.a2), mid, M0));
+    }
+    if (e.replay) return 0;
+    return bn_apply(e, l.c3.bn, a.c3, M0, GG_ACT_GELU, e.A(a.out), e.A(a.x), e.training ? e.dropv(slot) : nullptr, H0 * H0);
+}
+static int merge_fwd(const Exec& e, int s) {
+    const Model& m = *e.m; const Layout& L = *e.L;
+    const int B = e.B;
+    const StageL& st = m.stages[s];
+    const int C = st.C;
+    const int res = s == 0 ? m.res0 : m.stages[s - 1].res, Cprev = s == 0 ? m.cfg.embed_dims[0] : m.stages[s - 1].C;
+    const int64_t M = (int64_t)B * st.res * st.res, Mprev = (int64_t)B * res * res;
+    const MergeAct& ma = L.merge[s];
+    GG_TRY(conv_dense_fwd(e, st.merge.c1, ma.c1, e.A(merge_input(L, s)), Cprev, Mprev));
+    if (e.fuse_dw || e.fuse_dw_s2) {
+        GG_TRY(conv_dw_fwd_fused(e, st.merge.c2, ma.c2, st.merge.c1.bn, ma.c1, GG_ACT_GELU, B, res, res, 2));
+    } else {
+        GG_TRY(bn_apply(e, st.merge.c1.bn, ma.c1, Mprev, GG_ACT_GELU, e.A(ma.a1)));
+        GG_TRY(conv_dw_fwd(e, st.merge.c2, ma.c2, e.A(ma.a1), B, res, res, 2));
+    }
+    GG_TRY(bn_apply(e, st.merge.c2.bn, ma.c2, M, GG_ACT_GELU, e.A(ma.a2)));
+    GG_TRY(conv_dense_fwd(e, st.merge.c3, ma.c3, e.A(ma.a2), C, M));
+    if (e.replay) return 0;
+    return bn_apply(e, st.merge.c3.bn, ma.c3, M, GG_ACT_NONE, e.A(ma.out));
+}
+static int block_fwd(const Exec& e, int s, size_t i, int slot) {
+    const Model& m = *e.m; const GgTinyVitCfg& c = m.cfg;
+    const int B = e.B;
+    const StageL& st = m.stages[s];
+    const int C = st.C;
+    const int64_t M = (int64_t)B * st.res * st.res;
+    const int hid = (int)(C * c.mlp_ratio);
+    const int rps = st.res * st.res;
+    const BlockL& l = st.blocks[i]; const BlockAct& a = e.L->blocks[s][i];
+    const float* s1 = e.training ? e.dropv(slot) : nullptr;
+    const float* s2 = e.training ? e.dropv(slot + 1) : nullptr;
+    GG_TRY(gg_layernorm_fwd(e.A(a.x0), e.f32, e.P(l.ln1.t_g), e.P(l.ln1.t_b), M, C, c.ln_eps, e.A(a.a), e.f32, e.F(a.mean1), e.F(a.rstd1), e.st));
+    GG_TRY(gemm(e, e.A(a.a), C, e.Wn(l.qkv), l.qkv.Kp, e.A(a.qkv), 3 * C, M, 3 * C, l.qkv.Kp, e.P(l.qkv.t_b)));
+    GgAttnArgs at;
+    attn_args(e, st, l, a, B, at);
+    GG_TRY(e.f32 ? gg_attention_flash_fwd(&at, 1, e.st) : gg_attention_fwd(&at, e.st));
+    GG_TRY(gemm(e, e.A(a.o), C, e.Wn(l.proj), l.proj.Kp, e.A(a.x1), C, M, C, l.proj.Kp, e.P(l.proj.t_b), 0, nullptr, s1, rps, e.A(a.x0)));
+    GG_TRY(conv_dw_fwd(e, l.local, a.local, e.A(a.x1), B, st.res, st.res, 1));
+    if (C <= 640 && e.f32 && e.fuse_lnbn) {      // BatchNorm apply of local_conv rides on norm2's load (x2 = the residual stream is written there)
+        GG_TRY(gg_layernorm_fwd_bn_f32((const float*)e.A(a.local.y), e.F(a.local.stat), e.P(l.local.bn.t_g), e.P(l.local.bn.t_b), (float*)e.A(a.x2),
+                                       e.P(l.ln2.t_g), e.P(l.ln2.t_b), M, C, c.ln_eps, (float*)e.A(a.b), e.F(a.mean2), e.F(a.rstd2), e.st));
+    } else if (C <= 640 && !e.f32) {
+        GG_TRY(gg_layernorm_fwd_bn(e.A(a.local.y), e.F(a.local.stat), e.P(l.local.bn.t_g), e.P(l.local.bn.t_b), e.A(a.x2), e.P(l.ln2.t_g),
+                                   e.P(l.ln2.t_b), M, C, c.ln_eps, e.A(a.b), e.F(a.mean2), e.F(a.rstd2), e.st));
+    } else {
+        GG_TRY(bn_apply(e, l.local.bn, a.local, M, GG_ACT_NONE, e.A(a.x2)));
+        GG_TRY(gg_layernorm_fwd(e.A(a.x2), e.f32, e.P(l.ln2.t_g), e.P(l.ln2.t_b), M, C, c.ln_eps, e.A(a.b), e.f32, e.F(a.mean2), e.F(a.rstd2), e.st));
+    }
+    GG_TRY(gemm(e, e.A(a.b), C, e.Wn(l.fc1), l.fc1.Kp, e.A(a.h), hid, M, hid, l.fc1.Kp, e.P(l.fc1.t_b), GG_ACT_GELU,
+                e.training ? (void*)e.A(a.hpre) : nullptr));
+    if (e.replay) return 0;
+    return gemm(e, e.A(a.h), hid, e.Wn(l.fc2), l.fc2.Kp, e.A(a.x3), C, M, C, l.fc2.Kp, e.P(l.fc2.t_b), 0, nullptr, s2, rps, e.A(a.x2));
+}
+
 static int forward_impl(Exec& e, const float* x, float* out) {
     const Model& m = *e.m; const Layout& L = *e.L; const GgTinyVitCfg& c = m.cfg;
     const int B = e.B;
@@ -665,78 +796,19 @@ static int forward_impl(Exec& e, const float* x, float* out) {
     GG_TRY(bn_apply(e, m.pe2.bn, L.pe2, M0, GG_ACT_NONE, e.A(L.x_pe)));
 
     // stage 0: MBConv blocks
-    const int mid = (int)(d[0] * c.mbconv_expand_ratio);
     int slot = 0;
-    const int rps0 = H0 * H0;
-    for (size_t i = 0; i < m.mb.size(); ++i) {
-        const MBConvL& l = m.mb[i]; const MBAct& a = L.mb[i];
-        GG_TRY(conv_dense_fwd(e, l.c1, a.c1, e.A(a.x), d[0], M0));
-        if (e.fuse_dw || e.fuse_dw_s1) {
-            GG_TRY(conv_dw_fwd_fused(e, l.c2, a.c2, l.c1.bn, a.c1, GG_ACT_GELU, B, H0, H0, 1));   // act1 is never materialised
-        } else {
-            GG_TRY(bn_apply(e, l.c1.bn, a.c1, M0, GG_ACT_GELU, e.A(a.a1)));
-            GG_TRY(conv_dw_fwd(e, l.c2, a.c2, e.A(a.a1), B, H0, H0, 1));
-        }
-        // conv3 reads BN2+GELU of conv2's output through its A prologue unless its weight gradient needs that tensor
-        if (e.fuse_pro && !(e.training && e.tr(l.c3.w.t_w)) && l.c3.w.Kp == mid && mid <= 1024 && l.c3.w.N <= 128) {
-            GG_TRY(conv_dense_fwd_pro(e, l.c3, a.c3, l.c2.bn, a.c2, GG_ACT_GELU, M0));
-        } else {
-            GG_TRY(bn_apply(e, l.c2.bn, a.c2, M0, GG_ACT_GELU, e.A(a.a2)));
-            GG_TRY(conv_dense_fwd(e, l.c3, a.c3, e.A(a.a2), mid, M0));
-        }
-        GG_TRY(bn_apply(e, l.c3.bn, a.c3, M0, GG_ACT_GELU, e.A(a.out), e.A(a.x), e.training ? e.dropv(slot) : nullptr, rps0));
-        slot++;
-    }
-    int64_t prev = L.mb.empty() ? L.x_pe : L.mb.back().out;
-    int res = H0, Cprev = d[0];
-    int64_t Mprev = M0;
+    for (size_t i = 0; i < m.mb.size(); ++i) GG_TRY(mbconv_fwd(e, i, slot++));
+    int64_t prev = merge_input(L, 0);
+    int res = H0;
     for (int s = 0; s < 3; ++s) {
         const StageL& st = m.stages[s];
-        const int C = st.C;
-        const int64_t M = (int64_t)B * st.res * st.res;
-        const MergeAct& ma = L.merge[s];
-        // PatchMerging
-        GG_TRY(conv_dense_fwd(e, st.merge.c1, ma.c1, e.A(prev), Cprev, Mprev));
-        if (e.fuse_dw || e.fuse_dw_s2) {
-            GG_TRY(conv_dw_fwd_fused(e, st.merge.c2, ma.c2, st.merge.c1.bn, ma.c1, GG_ACT_GELU, B, res, res, 2));
-        } else {
-            GG_TRY(bn_apply(e, st.merge.c1.bn, ma.c1, Mprev, GG_ACT_GELU, e.A(ma.a1)));
-            GG_TRY(conv_dw_fwd(e, st.merge.c2, ma.c2, e.A(ma.a1), B, res, res, 2));
-        }
-        GG_TRY(bn_apply(e, st.merge.c2.bn, ma.c2, M, GG_ACT_GELU, e.A(ma.a2)));
-        GG_TRY(conv_dense_fwd(e, st.merge.c3, ma.c3, e.A(ma.a2), C, M));
-        GG_TRY(bn_apply(e, st.merge.c3.bn, ma.c3, M, GG_ACT_NONE, e.A(ma.out)));
-        const int hid = (int)(C * c.mlp_ratio);
-        const int rps = st.res * st.res;
+        GG_TRY(merge_fwd(e, s));
         for (size_t i = 0; i < st.blocks.size(); ++i) {
-            const BlockL& l = st.blocks[i]; const BlockAct& a = L.blocks[s][i];
-            const float* s1 = e.training ? e.dropv(slot) : nullptr;
-            const float* s2 = e.training ? e.dropv(slot + 1) : nullptr;
+            GG_TRY(block_fwd(e, s, i, slot));
             slot += 2;
-            GG_TRY(gg_layernorm_fwd(e.A(a.x0), e.f32, e.P(l.ln1.t_g), e.P(l.ln1.t_b), M, C, c.ln_eps, e.A(a.a), e.f32, e.F(a.mean1), e.F(a.rstd1), e.st));
-            GG_TRY(gemm(e, e.A(a.a), C, e.Wn(l.qkv), l.qkv.Kp, e.A(a.qkv), 3 * C, M, 3 * C, l.qkv.Kp, e.P(l.qkv.t_b)));
-            GgAttnArgs at;
-            attn_args(e, st, l, a, B, at);
-            GG_TRY(e.f32 ? gg_attention_flash_fwd(&at, 1, e.st) : gg_attention_fwd(&at, e.st));
-            GG_TRY(gemm(e, e.A(a.o), C, e.Wn(l.proj), l.proj.Kp, e.A(a.x1), C, M, C, l.proj.Kp, e.P(l.proj.t_b), 0, nullptr, s1, rps, e.A(a.x0)));
-            GG_TRY(conv_dw_fwd(e, l.local, a.local, e.A(a.x1), B, st.res, st.res, 1));
-            if (C <= 640 && e.f32 && e.fuse_lnbn) {      // BatchNorm apply of local_conv rides on norm2's load (x2 = the residual stream is written there)
-                GG_TRY(gg_layernorm_fwd_bn_f32((const float*)e.A(a.local.y), e.F(a.local.stat), e.P(l.local.bn.t_g), e.P(l.local.bn.t_b), (float*)e.A(a.x2),
-                                               e.P(l.ln2.t_g), e.P(l.ln2.t_b), M, C, c.ln_eps, (float*)e.A(a.b), e.F(a.mean2), e.F(a.rstd2), e.st));
-            } else if (C <= 640 && !e.f32) {
-                GG_TRY(gg_layernorm_fwd_bn(e.A(a.local.y), e.F(a.local.stat), e.P(l.local.bn.t_g), e.P(l.local.bn.t_b), e.A(a.x2), e.P(l.ln2.t_g),
-                                           e.P(l.ln2.t_b), M, C, c.ln_eps, e.A(a.b), e.F(a.mean2), e.F(a.rstd2), e.st));
-            } else {
-                GG_TRY(bn_apply(e, l.local.bn, a.local, M, GG_ACT_NONE, e.A(a.x2)));
-                GG_TRY(gg_layernorm_fwd(e.A(a.x2), e.f32, e.P(l.ln2.t_g), e.P(l.ln2.t_b), M, C, c.ln_eps, e.A(a.b), e.f32, e.F(a.mean2), e.F(a.rstd2), e.st));
-            }
-            GG_TRY(gemm(e, e.A(a.b), C, e.Wn(l.fc1), l.fc1.Kp, e.A(a.h), hid, M, hid, l.fc1.Kp, e.P(l.fc1.t_b), GG_ACT_GELU,
-                        e.training ? (void*)e.A(a.hpre) : nullptr));
-            GG_TRY(gemm(e, e.A(a.h), hid, e.Wn(l.fc2), l.fc2.Kp, e.A(a.x3), C, M, C, l.fc2.Kp, e.P(l.fc2.t_b), 0, nullptr, s2, rps, e.A(a.x2)));
-            prev = a.x3;
         }
-        if (st.blocks.empty()) prev = ma.out;
-        res = st.res; Cprev = C; Mprev = M;
+        prev = st.blocks.empty() ? L.merge[s].out : L.blocks[s].back().x3;
+        res = st.res;
     }
     // head: global average pool -> LayerNorm
     const int T = res * res, C3 = d[3];
@@ -876,6 +948,10 @@ static int backward_impl(Exec& e, const float* d_out) {
     const int H = c.img_size, H1 = H / 2, H0 = m.res0;
     const int64_t M1 = (int64_t)B * H1 * H1, M0 = (int64_t)B * H0 * H0;
     act_t* G0 = e.A(L.G[0]); act_t* G1 = e.A(L.G[1]); act_t* G2 = e.A(L.G[2]); act_t* G3 = e.A(L.G[3]); act_t* G4 = e.A(L.G[4]);
+    // activation recompute: each segment's tensors are re-formed in the segment region right before its backward
+    const bool rc = c.recompute != 0;
+    Exec r = e;
+    r.replay = true;
 
     // drop-path slot bookkeeping mirrors forward
     int nslots = (int)m.mb.size();
@@ -908,6 +984,7 @@ static int backward_impl(Exec& e, const float* d_out) {
         for (int i = (int)st.blocks.size() - 1; i >= 0; --i) {
             const BlockL& l = st.blocks[i]; const BlockAct& a = L.blocks[s][i];
             slot -= 2;
+            if (rc) GG_TRY(block_fwd(r, s, (size_t)i, slot));
             const float* s1 = e.dropv(slot);
             const float* s2 = e.dropv(slot + 1);
             // dx == d(x3).  MLP branch: x3 = x2 + s2*(fc2(gelu(fc1(ln2(x2)))))
@@ -986,11 +1063,11 @@ static int backward_impl(Exec& e, const float* d_out) {
             (void)hid;
         }
         // ---- PatchMerging backward: out = BN3(conv3(a2)); a2 = gelu(BN2(dw s2(a1))); a1 = gelu(BN1(conv1(x))) ----
+        if (rc) GG_TRY(merge_fwd(r, s));
         const MergeAct& ma = L.merge[s];
         act_t* t_a = (dx == G0) ? G1 : G0;
         act_t* t_b = G2; act_t* t_c = G3; act_t* t_d = G4;
-        const int64_t xin = s == 0 ? (L.mb.empty() ? L.x_pe : L.mb.back().out)
-                                   : (L.blocks[s - 1].empty() ? L.merge[s - 1].out : L.blocks[s - 1].back().x3);
+        const int64_t xin = merge_input(L, s);
         GG_TRY(bn_bwd(e, st.merge.c3.bn, ma.c3, M, GG_ACT_NONE, dx, t_b, t_a));                         // dy3 -> t_a
         if (e.tr(st.merge.c3.w.t_w)) GG_TRY(dense_wgrad(e, st.merge.c3.w, e.A(ma.a2), C, t_a, C, M, nullptr, 0, t_b, t_c, false));
         if (e.fuse_bngemm && !e.tr(st.merge.c1.w.t_w) && !e.tr(st.merge.c2.w.t_w) && C % 64 == 0) {
@@ -1035,6 +1112,7 @@ static int backward_impl(Exec& e, const float* d_out) {
     for (int i = (int)m.mb.size() - 1; i >= 0; --i) {
         const MBConvL& l = m.mb[i]; const MBAct& a = L.mb[i];
         slot -= 1;
+        if (rc) GG_TRY(mbconv_fwd(r, (size_t)i, slot));
         const float* s0 = e.dropv(slot);
         act_t* t_a = (dx == G0) ? G1 : G0;
         act_t* t_b = G2; act_t* t_c = G3; act_t* t_d = G4;
@@ -1229,6 +1307,7 @@ extern "C" int gg_tinyvit_activation_info_masked(const GgTinyVitCfg* cfg, int ba
     plan_make(m, batch, true, p, L, trainable);
     auto it = p.index.find(name);
     GG_CHECK(it != p.index.end(), "gg_tinyvit_activation_info: no activation named '%s'", name);
+    GG_CHECK(!p.recomputed.count(name), "gg_tinyvit_activation_info: '%s' is not retained with activation recompute (recompute = 1: a segment-internal tensor that the backward recomputes in the shared segment region)", name);
     GG_CHECK(!p.temps.count(name), "gg_tinyvit_activation_info: '%s' is not retained under this trainable mask (a temporary between its producer and its one consumer)", name);
     if (offset) *offset = p.regs[it->second].offset;
     if (bytes) *bytes = p.regs[it->second].bytes;

@@ -70,6 +70,7 @@ def make_cfg(model_name: str, **overrides) -> tuple:
         raise ValueError(f"precision='{prec}' (known: bf16, fp32)")
     c.act_dtype = PRECISIONS[prec]
     c.features_only = int(bool(v.get("features_only", False)))
+    c.recompute = int(bool(v.get("grad_checkpointing", False)))      # activation recompute (TinyVitBackbone.set_grad_checkpointing)
     return c, v, depths
 
 
@@ -139,6 +140,22 @@ class TinyVitBackbone(FlatStore):
         self._last = None
         self._gen = 0                    # generation of the training workspace contents (one per training forward)
         self._grad_ready_hook = None     # set by optim.AdamW.overlap_allreduce: fn(lo, hi) over flat gradient floats
+        self.grad_checkpointing = bool(self.cfg.recompute)
+
+    def set_grad_checkpointing(self, enable: bool = True):
+        """timm's switch (``model.set_grad_checkpointing()``; the reference's ``adapter.backbone`` is the timm model): activation recompute of the
+        training step (``GgTinyVitCfg.recompute``, include/gg.h).  The workspace keeps each segment's input (an MBConv, a PatchMerging, a
+        TinyVitBlock), the ConvNorms' batch statistics and PatchEmbed; the backward re-forms a segment's other tensors right before its backward.
+        Output, gradients, running statistics and ``num_batches_tracked`` are bit-identical to the step without recompute (the attention-bias
+        gradients only to rounding: the attention backward sums them with float atomics, so they vary in their last bits between any two steps).  Unlike
+        ``torch.utils.checkpoint``, whose recompute runs BatchNorm in train mode again and so updates the running statistics twice, the recompute
+        reuses the forward's batch statistics: the running buffers are updated once per step.  Inference ignores the setting."""
+        enable = bool(enable)
+        if enable != bool(self.cfg.recompute):
+            self.cfg.recompute = int(enable)
+            self._ws.pop(True, None)          # laid out for the other plan: the next training forward sizes a new one
+        self.grad_checkpointing = enable
+        return self
 
     # -- HIP calls ------------------------------------------------------------------------------------------
     def _ensure_weights(self):
@@ -244,6 +261,7 @@ class TinyVitBackbone(FlatStore):
             self._flat_buf_dirty = True
             self._gen += 1
             self._last = (B, drop_scales, self._gen)
+            self._last_recompute = self.cfg.recompute
         return out
 
     def _stage_ranges(self):
@@ -271,8 +289,14 @@ class TinyVitBackbone(FlatStore):
                             "followed by its backward before the next training forward")
         if d_out.shape[0] != B:
             raise L.GgError(f"TinyViT backward: gradient batch {d_out.shape[0]} != forward batch {B}")
+        if self.cfg.recompute != getattr(self, "_last_recompute", self.cfg.recompute):
+            raise L.GgError("set_grad_checkpointing changed between the training forward and its backward: the forward laid out its workspace for "
+                            f"recompute={self._last_recompute} (the checkpointed layout keeps other tensors); run the forward again")
+        ws = self._ws.get(True)
+        if ws is None:
+            raise L.GgError("TinyViT backward: the training workspace was released (set_grad_checkpointing changed since the training forward); "
+                            "run the forward again")
         fg = self.attach_grads()
-        ws = self._ws[True]
         mask = self.trainable_mask()
         if getattr(self, "_train_mask", None) is not None and mask != self._train_mask:
             # the workspace was laid out (and activations were dropped) for the forward's mask: backward must see the same one
@@ -356,7 +380,8 @@ class TinyViTAdapter(nn.Module):
     def __init__(self, model_name: str = "tiny_vit_21m_512.dist_in22k_ft_in1k", pretrained: bool = True,
                  global_pool: str = "avg", features_only: bool = False, **overrides):
         """``overrides`` (not in the reference): ``precision="bf16"|"fp32"`` (default ``$GG_PRECISION`` or fp32), ``seed``,
-        ``drop_path_rate``, ``img_size`` ... (timm ``create_model`` kwargs)."""
+        ``drop_path_rate``, ``img_size`` ... (timm ``create_model`` kwargs), ``grad_checkpointing=True`` (activation recompute from the start;
+        the same as ``adapter.backbone.set_grad_checkpointing()``)."""
         super().__init__()
         if global_pool != "avg":
             raise NotImplementedError("only global_pool='avg' (the reference's setting) is built")

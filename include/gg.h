@@ -449,6 +449,18 @@ typedef struct GgTinyVitCfg {
                                conv forms of stage 0 and the conv weight gradients as mode 1.  Error against fp64 at or below the f32 MFMA GEMM's */
     int features_only;   /* 1: models/tinyvit.py:38-46,139-143 (timm features_only=True): the output is the global-average-pooled
                                last feature map, head.norm is not applied (its parameters stay in the table, unused) */
+    int recompute;       /* activation recompute (gradient checkpointing, timm set_grad_checkpointing) of a training forward / backward pair;
+                            ignored by inference (training = 0).  0: the workspace keeps every activation the backward reads.
+                            1: per-segment checkpoints -- the segments are each MBConv of stage 0, each PatchMerging and each TinyVitBlock.  The
+                               workspace keeps PatchEmbed's tensors, every segment's input (patch_embed.out and the .out of every segment), every
+                               ConvNorm's .stat and the head's pooled / mean / rstd, each in a region of its own; every other tensor of a segment
+                               lives in ONE segment region shared by all segments.  gg_tinyvit_backward runs each segment's forward launches
+                               again (same kernels, same routing, up to the last tensor the segment's backward reads) before that segment's backward.
+                               Contract: output, every parameter gradient, the running statistics and the counters are bit-identical to recompute = 0
+                               (the recompute takes the forward's routes on the same inputs) -- except the attention-bias tables' gradients, with or
+                               without recompute: they are summed with float atomics in LDS, so their last bits vary between ANY two steps.
+                               The recompute reuses the (mean, rstd) the forward saved in each .stat: the BatchNorm running buffers are updated ONCE
+                               per step, by the forward (unlike torch.utils.checkpoint, whose recompute updates them a second time).  The workspace size and layout depend on the field: forward and backward must see the same value. */
 } GgTinyVitCfg;
 enum { GG_KIND_PARAM = 0, GG_KIND_BUFFER = 1, GG_KIND_COUNTER = 2 };
 int gg_tinyvit_num_tensors(const GgTinyVitCfg* cfg);
@@ -467,7 +479,8 @@ int64_t gg_tinyvit_workspace_bytes(const GgTinyVitCfg* cfg, int batch, int train
  * frozen Linears / depthwise convs (ln1, x1, ln2, GELU(fc1) of a TinyVitBlock; act1 / act2 of MBConv and PatchMerging) are read once, right after
  * they are written, and share a two-slot ring instead of being kept for backward.  Under the reference's freeze_all_but_last_stage policy
  * (models/tinyvit.py:106-111) that is 7 of a frozen block's 19 C floats per token.  gg_tinyvit_forward / _backward lay the workspace out for the
- * mask they are CALLED with: pass the same mask to the size query, the forward and its backward. */
+ * mask they are CALLED with: pass the same mask to the size query, the forward and its backward.  With cfg->recompute = 1 the training size is
+ * that of the checkpointed layout (the temporaries above live in the segment region then, and no gradient buffer aliases them). */
 int64_t gg_tinyvit_workspace_bytes_masked(const GgTinyVitCfg* cfg, int batch, int training, const uint8_t* trainable);
 int gg_tinyvit_refresh_weights(const GgTinyVitCfg* cfg, const float* params, void* wcache, void* stream);
 /* the same for a subset: `only` (host, one byte per tensor of gg_tinyvit_tensor_info) marks the tensors that changed (after an optimizer step: the trainable ones) */
@@ -493,7 +506,8 @@ int gg_tinyvit_backward(const GgTinyVitCfg* cfg, int batch, const float* params,
                         GgStageDoneFn stage_done, void* stage_user);
 /* debug / parity: byte offset of a named saved activation inside the workspace (host) */
 int gg_tinyvit_activation_info(const GgTinyVitCfg* cfg, int batch, const char* name, int64_t* offset, int64_t* bytes);
-/* the same for the layout of a trainable mask; a tensor that is only a temporary under that mask is refused */
+/* the same for the layout of a trainable mask; a tensor that is only a temporary under that mask is refused, and so is (cfg->recompute = 1) a
+ * segment-internal tensor that the backward recomputes (its bytes are overwritten by the next segment; "scratch.segment" names the shared region) */
 int gg_tinyvit_activation_info_masked(const GgTinyVitCfg* cfg, int batch, const char* name, const uint8_t* trainable, int64_t* offset, int64_t* bytes);
 
 /* ---------------------------------------------------------------- either side of the encoder ("next" rows)
