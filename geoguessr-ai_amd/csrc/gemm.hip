@@ -1091,6 +1091,8 @@ extern "C" int GG_GEMM_NT_NAME(const GgGemmArgs* a, void* stream) {
                  "gg_gemm_nt: the BatchNorm prologue needs gamma/beta, K <= 1024, no split-K, a single A source");
         GG_CHECK(!(a->bias || a->act || a->rowscale || a->residual || a->dact_preact || a->out_f32 || a->preact || a->bn_y),
                  "gg_gemm_nt: the BatchNorm prologue is built for the plain (+ column statistics) epilogue only");
+        GG_CHECK(a->a_bn_act == GG_ACT_NONE || a->a_bn_act == GG_ACT_GELU,
+                 "gg_gemm_nt: the BatchNorm prologue applies GG_ACT_CODE_NONE or GG_ACT_CODE_GELU only (a_bn_act = %d; gg_gemm_nt_f32 has the QuickGELU form)", a->a_bn_act);
     }
     GemmParams p;
     p.group_m = 0;

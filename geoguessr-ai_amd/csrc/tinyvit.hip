@@ -1219,16 +1219,21 @@ static int backward_impl(Exec& e, const float* d_out) {
     return 0;
 }
 
+// Wn [N][ldn] and Wt [ldn][ldt] (ldn = K rounded up to 8, ldt = N rounded up to 8): the padding columns / rows of both copies are written as zeros
+// here, so the cache needs no zero-initialisation by its owner (the GEMMs contract over ldn, the split-plane copies are taken over the padded shapes)
 template <typename T>
 __global__ void repack_weight_kernel(const float* __restrict__ src, int N, int cin, int taps, T* __restrict__ Wn, int ldn,
                                      T* __restrict__ Wt, int ldt) {
     const int K = cin * taps;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N * K) return;
-    const int co = i / K, k = i % K;
-    const int tap = k / cin, ci = k % cin;
-    const T v = (T)src[((int64_t)co * cin + ci) * taps + tap];
-    Wn[(int64_t)co * ldn + k] = v;
+    if (i >= ldt * ldn) return;
+    const int co = i / ldn, k = i % ldn;
+    T v = (T)0.f;
+    if (co < N && k < K) {
+        const int tap = k / cin, ci = k % cin;
+        v = (T)src[((int64_t)co * cin + ci) * taps + tap];
+    }
+    if (co < N) Wn[(int64_t)co * ldn + k] = v;
     Wt[(int64_t)k * ldt + co] = v;
 }
 __global__ void repack_taps_kernel(const float* __restrict__ src, int C, float* __restrict__ taps) {
@@ -1238,7 +1243,7 @@ __global__ void repack_taps_kernel(const float* __restrict__ src, int C, float* 
     taps[i] = src[c * 9 + t];
 }
 static int repack_dense(const DenseW& w, const float* params, const Model& m, char* wc, hipStream_t st) {
-    const int n = w.N * w.K;
+    const int n = w.Np * w.Kp;        // padded: the kernel zeroes the padding of both copies
     if (m.f32)
         hipLaunchKernelGGL(repack_weight_kernel<float>, dim3((unsigned)gg_cdiv(n, 256)), dim3(256), 0, st, params + m.tensors[w.t_w].offset, w.N,
                            w.cin, w.taps, reinterpret_cast<float*>(wc + w.wn), w.Kp, reinterpret_cast<float*>(wc + w.wt), w.Np);

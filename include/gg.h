@@ -58,7 +58,8 @@ typedef struct GgGemmArgs {
      * colstats <- per M-tile column sums of (dz, dz*xhat) for gg_bn_bwd_finalize. */
     const void* bn_y; const float* bn_stat; const float* bn_gamma; const float* bn_beta; int bn_act;
     /* BatchNorm prologue: A holds the PRE-BatchNorm output of the previous ConvNorm; act(gamma*(A-mean)*rstd+beta) with
-     * a_bn_stat = [mean[K], rstd[K]] is applied while the A tile is staged (plain / colstats epilogue only, K <= 1024). */
+     * a_bn_stat = [mean[K], rstd[K]] is applied while the A tile is staged (plain / colstats epilogue only, K <= 1024).  a_bn_act: GG_ACT_CODE_NONE or
+     * GG_ACT_CODE_GELU in gg_gemm_nt (QuickGELU is refused); all three codes in gg_gemm_nt_f32. */
     const float* a_bn_stat; const float* a_bn_gamma; const float* a_bn_beta; int a_bn_act;
 } GgGemmArgs;
 int gg_gemm_nt(const GgGemmArgs* args, void* stream);
