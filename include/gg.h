@@ -495,7 +495,9 @@ int gg_tinyvit_forward(const GgTinyVitCfg* cfg, int batch, int training, const f
                        const void* wcache, const float* x, const float* drop_scales, void* workspace, float* out,
                        const uint8_t* trainable /* host */, void* stream);
 /* d_out: f32 (batch, C).  grads: flat f32 like params, ACCUMULATED into.  trainable: host uint8[num_tensors]
- * (wgrad computed only where 1; dgrad always flows to patch_embed -- SURVEY.md C1). */
+ * (wgrad computed only where 1; dgrad always flows to patch_embed -- SURVEY.md C1).  Any mask that keeps `x.weight` and `x.bias` together
+ * is scheduled (a half-frozen pair is refused by name); the bytes of `grads` outside the trainable tensors -- frozen tensors and the padding
+ * between tensors -- are never written.  A mask of all zeros is accepted: the call returns 0 and changes no byte of `grads`. */
 /* stage_done (may be NULL): HOST callback, called on the calling thread as soon as every kernel that writes the parameter gradients
  * of a stage has been enqueued on `stream` -- stage ids 3, 2, 1 (TinyVitStage incl. its PatchMerging; 3 also covers head.norm),
  * 0 (the MBConv stage), -1 (patch_embed), in that order.  The data-parallel host uses it to start the RCCL all-reduce of that

@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from tests import guards as G
+from tests import masks as MASKS
 from tests.test_gpu_recompute import _grad_mismatches, _model, _stats, _step
 
 pytestmark = pytest.mark.gpu
@@ -63,6 +64,10 @@ def _drop_scales(bb, S, batch, seed=11, counter=3):
 
 TRAIN = [(name, prec, pol, rc) for name in ("tiny_vit_5m_224", "tiny_vit_21m_224") for prec in ("fp32", "fp32_split", "bf16") for pol in ("freeze", "all")
          for rc in (False, True)]
+# ... and under every mask of tests/masks.py (fp32; the reduced family in bf16): `policy` is the mask's name.  Recompute is covered under the masks by
+# tests/test_gpu_masks.py (recompute on is bit-identical to recompute off), so these run the keep-what-the-mask-needs plan, the one the mask shapes
+TRAIN += [(name, "fp32", pol, False) for name in ("tiny_vit_5m_224", "tiny_vit_21m_224") for pol in MASKS.FAMILY_NAMES]
+TRAIN += [(name, "bf16", pol, False) for name in ("tiny_vit_5m_224", "tiny_vit_21m_224") for pol in MASKS.REDUCED]
 
 
 @pytest.mark.parametrize("name,precision,policy,recompute", TRAIN)
@@ -145,7 +150,9 @@ def _clip_install(tower, S, batch, training, zero):
 
 
 @pytest.mark.parametrize("precision,mode", [("fp32", "eval"), ("bf16", "eval"), ("fp16", "eval"), ("fp32", "finetune_last"), ("bf16", "finetune_last"),
-                                            ("fp32", "finetune_all"), ("bf16", "finetune_all")])
+                                            ("fp32", "finetune_all"), ("bf16", "finetune_all")] +
+                         [("fp32", "mask:" + key) for key in ("biases", "layernorms", "middle_layer", "position_embedding", "class_embedding", "patch_embedding",
+                                                              "layernorm_weights", "random[0]", "random[1]", "random[2]")])
 def test_clip_step_is_independent_of_workspace_contents(golden_dir, precision, mode):
     """gg_clip_forward / gg_clip_backward with the tiny tower of tests/test_gpu_clip.py: inference in the three storage types, and the fine-tune step
     (last encoder layer, as SuperGuessr trains it with a pretrained head; every layer) -- twice in the same workspace.  No atomics in this path: every
@@ -166,6 +173,8 @@ def test_clip_step_is_independent_of_workspace_contents(golden_dir, precision, m
             last = f"encoder.layers.{tower.cfg.num_layers - 1}."
             for n, p in vm._params.items():
                 p.requires_grad = n.startswith(last)
+        elif mode.startswith("mask:"):       # a CLIP mask of tests/masks.py by name (half pairs included: the LayerNorm dump row)
+            MASKS.apply(vm, MASKS.clip_family([t["name"] for t in vm.table], tower.cfg.num_layers)[mode[5:]])
         S = G.GuardSet(fill)
         ws, wc = _clip_install(tower, S, batch, training, zero)
         steps = []

@@ -64,6 +64,9 @@ def _model(name, precision, policy, drop_path_rate=0.1, seed=0):
     m = m.cuda().train()
     if policy == "freeze":
         m.freeze_all_but_last_stage()
+    elif policy != "all":            # a mask of tests/masks.py by name
+        from tests import masks
+        masks.apply(m.backbone, policy)
     return m
 
 
