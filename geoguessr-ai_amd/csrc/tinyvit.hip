@@ -30,8 +30,45 @@ struct MergeL { ConvBNDense c1; ConvBNDw c2; ConvBNDense c3; };
 struct BlockL { int t_ab = -1; int64_t bias_full = 0; LNP ln1; DenseW qkv, proj; LNP ln2; DenseW fc1, fc2; ConvBNDw local; };
 struct StageL { MergeL merge; std::vector<BlockL> blocks; int C, heads, ws, res; };
 
+// Which fused forms the schedule takes.  The workspace plan decides who owns the tensors a fusion removes and the executor decides who writes
+// them, so there is ONE value per C-ABI call: build_model fills Model::sch from the storage type and the dev switches, both read it there.
+struct Schedule { bool fuse_dw, fuse_dw_s2, fuse_dw_s1, fuse_bnbwd, fuse_bnbwd_epi, fuse_bngemm, fuse_pro, fuse_lncol, fuse_lnbn; };
+static Schedule schedule_flags(bool f32) {
+    Schedule k;
+    // Fusing BatchNorm+GELU of the producer into the depthwise conv's input load removes one [M,C] write+read, but each input is
+    // loaded (and transformed) by its three neighbouring columns: the erf work triples and the conv turns VALU-bound
+    // (measured at 1024 images: +4.7 ms conv vs -2.7 ms elementwise) -> off by default, and always off in f32 storage.
+    k.fuse_dw = gg_dev_env("GG_FUSE_DW") != nullptr && !f32;
+    // the stride-2 depthwise conv of PatchMerging stages its input tile in LDS: BatchNorm1 + GELU are applied once per staged element
+    // (17x17 inputs per 8x8 outputs = 1.13x), the apply pass and the activation tensor disappear
+    k.fuse_dw_s2 = gg_dev_env("GG_NO_FUSE_DW_S2") == nullptr;
+    // MBConv.conv2 likewise through the 4-columns-per-thread stride-1 kernel (1.5 BatchNorm+GELU evaluations per input element)
+    k.fuse_dw_s1 = gg_dev_env("GG_NO_FUSE_DW_S1") == nullptr;
+    // Frozen depthwise taps: the data gradient forms BatchNorm backward's apply step (dy = c0*dz + c1*y + c2) while it loads its
+    // input, and (MBConv) emits dz = da*act'(BN(y)) + the reduce sums of the ConvNorm in front: apply and reduce passes and
+    // the dy / da tensors disappear.  GG_NO_FUSE_BNBWD=1 / GG_NO_FUSE_BNBWD_EPI=1 restore the separate passes.
+    k.fuse_bnbwd = gg_dev_env("GG_NO_FUSE_BNBWD") == nullptr;
+    k.fuse_bnbwd_epi = gg_dev_env("GG_NO_FUSE_BNBWD_EPI") == nullptr;
+    // Frozen ConvNorm chains: BatchNorm backward's reduce rides in the epilogue of the conv dgrad that produces its input
+    // gradient, and its apply step is folded into the weights of the 1x1 dgrad that consumes its output gradient.
+    k.fuse_bngemm = gg_dev_env("GG_NO_BNGEMM") == nullptr;
+    k.fuse_pro = gg_dev_env("GG_NO_PRO") == nullptr;              // MBConv conv3 applies BatchNorm2 + GELU in its A prologue (one N tile: each element is transformed once)
+    k.fuse_lncol = gg_dev_env("GG_NO_LN_COLSUM") == nullptr;      // norm2's backward leaves local_conv's BatchNorm-backward column sums (frozen blocks)
+    k.fuse_lnbn = true;                                           // f32 storage: local_conv's BatchNorm apply inside norm2
+    // f32 storage takes the same fusions where an f32 twin exists (MBConv / PatchMerging forward, the stride-1 data gradients, the GEMM-side
+    // BatchNorm epilogue / prologues); GG_F32_NO_FUSE=1 runs every BatchNorm pass on its own (the schedule the fusions are tested against)
+    if (f32 && gg_dev_env("GG_F32_NO_FUSE")) k = Schedule{};
+    return k;
+}
+// One unit of the schedule (and of activation recompute): an MBConv of stage 0, the PatchMerging of stage 1..3, a TinyVitBlock of stage 1..3
+enum { SEG_MBCONV, SEG_MERGE, SEG_BLOCK };
+struct Segment { int kind, stage, index, slot; };       // slot: its first DropPath slot (an MBConv has one, a block two, a PatchMerging none)
+
 struct Model {
     GgTinyVitCfg cfg;
+    Schedule sch;
+    std::vector<Segment> segs;      // in forward order; the backward walks it from the end
+    int drop_slots = 0;
     int es = 2;             // bytes per activation / cached-weight element: 2 (bf16) or 4 (f32, reference-precision mode)
     bool f32 = false;
     bool split = false;     // act_dtype 3 ("fp32_split"): f32 storage and arithmetic; the Linears of the transformer blocks (forward and data gradients) run as fp32-accurate
@@ -108,6 +145,7 @@ static int build_model(const GgTinyVitCfg* cfg, Model& m) {
     m.cfg = *cfg;
     GG_CHECK(cfg->act_dtype == 0 || cfg->act_dtype == 1 || cfg->act_dtype == 3, "tinyvit: act_dtype must be 0 (bf16), 1 (f32) or 3 (f32 storage, split-bf16 Linears)");
     m.f32 = cfg->act_dtype != 0; m.split = cfg->act_dtype == 3; m.es = m.f32 ? 4 : 2;
+    m.sch = schedule_flags(m.f32);
     const int* d = cfg->embed_dims;
     GG_CHECK(cfg->img_size > 0 && cfg->img_size % 32 == 0, "tinyvit: img_size must be a multiple of 32");
     GG_CHECK(cfg->in_chans == 3, "tinyvit: in_chans must be 3");
@@ -127,6 +165,8 @@ static int build_model(const GgTinyVitCfg* cfg, Model& m) {
         make_convbn_dense(m, m.mb[i].c1, p + ".conv1", d[0], mid, 1);
         make_convbn_dw(m, m.mb[i].c2, p + ".conv2", mid);
         make_convbn_dense(m, m.mb[i].c3, p + ".conv3", mid, d[0], 1);
+        m.segs.push_back({SEG_MBCONV, 0, i, m.drop_slots});
+        m.drop_slots += 1;
     }
     int res = m.res0;
     for (int s = 1; s < 4; ++s) {
@@ -140,6 +180,7 @@ static int build_model(const GgTinyVitCfg* cfg, Model& m) {
         make_convbn_dense(m, st.merge.c1, pm + ".conv1", d[s - 1], C, 1);
         make_convbn_dw(m, st.merge.c2, pm + ".conv2", C);
         make_convbn_dense(m, st.merge.c3, pm + ".conv3", C, C, 1);
+        m.segs.push_back({SEG_MERGE, s, 0, m.drop_slots});
         const int hid = (int)(C * cfg->mlp_ratio);
         st.blocks.resize(cfg->depths[s]);
         for (int i = 0; i < cfg->depths[s]; ++i) {
@@ -161,6 +202,8 @@ static int build_model(const GgTinyVitCfg* cfg, Model& m) {
             bn = p + ".mlp.fc2.bias";
             make_dense(m, b.fc2, p + ".mlp.fc2.weight", C, hid, 1, &bn, false);
             make_convbn_dw(m, b.local, p + ".local_conv", C);
+            m.segs.push_back({SEG_BLOCK, s, i, m.drop_slots});
+            m.drop_slots += 2;
             if (m.split) {      // bf16 planes of W and W^T of the block's four Linears (B operand of gg_gemm_nt_split3_af32: forward and data gradients)
                 for (DenseW* w : {&b.qkv, &b.proj, &b.fc1, &b.fc2}) {
                     w->wn3 = wc_alloc(m, (int64_t)3 * w->N * w->Kp * 2);
@@ -191,7 +234,6 @@ struct Plan {
     // was made for -- no weight gradient reads them (the input of a frozen Linear / depthwise conv, the activation tensors the fused forward never
     // writes).  They alternate between TRING slots of the largest one; `temps` holds their names (gg_tinyvit_activation_info refuses them).
     const uint8_t* mask = nullptr;       // one byte per tensor of the model, or null = everything trainable
-    bool fwd_dw_s1 = true, fwd_dw_s2 = true, fwd_pro = true;      // which forward fusions the executor will take (they decide who writes act1 / act2)
     int64_t max_temp = 0, temp_base = 0, gbytes_seen = 0;
     int temp_next = 0;
     bool alias_G = false;
@@ -285,6 +327,16 @@ static int64_t bn_part_floats(int64_t M, int C, int B, int Ho, int Wo, bool dw) 
     return (int64_t)gg_stat_rows_capacity(rows) * 2 * C;
 }
 
+// The forward routes that decide who writes act1 / act2 of an MBConv or a PatchMerging: the plan gives those tensors their storage by the same
+// predicates the forward (and the backward, where it re-forms act1 for the tap gradient) takes its route by.
+// act1 = GELU(BN1(y1)) is never written by the forward: the depthwise conv (stride 1: MBConv, 2: PatchMerging) forms it while staging its input
+static bool act1_fused_away(const Schedule& k, int stride) { return k.fuse_dw || (stride == 1 ? k.fuse_dw_s1 : k.fuse_dw_s2); }
+// MBConv conv3 reads BN2 + GELU of conv2's output through its A prologue and act2 is not written -- unless conv3's weight gradient needs that
+// tensor (w_trains: training and conv3.weight trainable; the plan keeps act2 then, and makes it a temporary otherwise whichever route is taken)
+static bool conv3_takes_prologue(const Schedule& k, const DenseW& w, int mid, bool w_trains) {
+    return k.fuse_pro && !w_trains && w.Kp == mid && mid <= 1024 && w.N <= 128;
+}
+
 static void plan_build(const Model& m, int B, Plan& p, Layout& L) {
     const GgTinyVitCfg& c = m.cfg;
     const int* d = c.embed_dims;
@@ -320,7 +372,7 @@ static void plan_build(const Model& m, int B, Plan& p, Layout& L) {
         const MBConvL& ml = m.mb[i];
         p.seg_begin();
         bnreg(n + ".conv1", a.c1, M0, mid, false, B, H0, H0);
-        a.a1 = p.rc ? p.alloc_seg(n + ".act1", M0 * mid * es) : !p.tr(ml.c2.w.t_w) ? p.alloc_temp(n + ".act1", M0 * mid * es) : p.fwd_dw_s1 ? p.alloc_shared(n + ".act1", M0 * mid * es) : p.alloc(n + ".act1", M0 * mid * es);
+        a.a1 = p.rc ? p.alloc_seg(n + ".act1", M0 * mid * es) : !p.tr(ml.c2.w.t_w) ? p.alloc_temp(n + ".act1", M0 * mid * es) : act1_fused_away(m.sch, 1) ? p.alloc_shared(n + ".act1", M0 * mid * es) : p.alloc(n + ".act1", M0 * mid * es);
         bnreg(n + ".conv2", a.c2, M0, mid, true, B, H0, H0);
         a.a2 = p.rc ? p.alloc_seg(n + ".act2", M0 * mid * es) : !p.tr(ml.c3.w.t_w) ? p.alloc_temp(n + ".act2", M0 * mid * es) : p.alloc(n + ".act2", M0 * mid * es);
         bnreg(n + ".conv3", a.c3, M0, d[0], false, B, H0, H0);
@@ -337,7 +389,7 @@ static void plan_build(const Model& m, int B, Plan& p, Layout& L) {
         MergeAct& ma = L.merge[s];
         p.seg_begin();
         bnreg(n + ".conv1", ma.c1, Mprev, C, false, B, res, res);
-        ma.a1 = p.rc ? p.alloc_seg(n + ".act1", Mprev * C * es) : !p.tr(st.merge.c2.w.t_w) ? p.alloc_temp(n + ".act1", Mprev * C * es) : p.fwd_dw_s2 ? p.alloc_shared(n + ".act1", Mprev * C * es) : p.alloc(n + ".act1", Mprev * C * es);
+        ma.a1 = p.rc ? p.alloc_seg(n + ".act1", Mprev * C * es) : !p.tr(st.merge.c2.w.t_w) ? p.alloc_temp(n + ".act1", Mprev * C * es) : act1_fused_away(m.sch, 2) ? p.alloc_shared(n + ".act1", Mprev * C * es) : p.alloc(n + ".act1", Mprev * C * es);
         bnreg(n + ".conv2", ma.c2, M, C, true, B, st.res, st.res);
         ma.a2 = p.rc ? p.alloc_seg(n + ".act2", M * C * es) : !p.tr(st.merge.c3.w.t_w) ? p.alloc_temp(n + ".act2", M * C * es) : p.alloc(n + ".act2", M * C * es);
         bnreg(n + ".conv3", ma.c3, M, C, false, B, st.res, st.res);
@@ -431,21 +483,12 @@ static void plan_build(const Model& m, int B, Plan& p, Layout& L) {
         }
     }
 }
-// which forward fusions the executor takes (mirrors Exec::exec_init): they decide who writes the MBConv / PatchMerging activation tensors
-static void plan_flags(const Model& m, Plan& p) {
-    bool fuse_dw = gg_dev_env("GG_FUSE_DW") != nullptr, s1 = gg_dev_env("GG_NO_FUSE_DW_S1") == nullptr, s2 = gg_dev_env("GG_NO_FUSE_DW_S2") == nullptr;
-    bool pro = gg_dev_env("GG_NO_PRO") == nullptr;
-    if (m.f32 && gg_dev_env("GG_F32_NO_FUSE")) fuse_dw = s1 = s2 = pro = false;
-    if (m.f32) fuse_dw = false;
-    p.fwd_dw_s1 = fuse_dw || s1; p.fwd_dw_s2 = fuse_dw || s2; p.fwd_pro = pro;
-}
 static void plan_make(const Model& m, int B, bool training, Plan& p, Layout& L, const uint8_t* mask = nullptr, bool allow_rc = true) {
     if (training && allow_rc && m.cfg.recompute) {
         Plan off; Layout Loff;                     // the recompute-off plan: what it decides from its own size, the checkpointed one inherits
         plan_make(m, B, true, off, Loff, mask, false);
         Plan q;
         q.training = true; q.mask = mask; q.rc = true; q.ds_force = Loff.attn_ds >= 0 ? 1 : 0;
-        plan_flags(m, q);
         Plan dry = q; Layout Ld;                   // first pass: the segment region's size; second pass: the region first, then the rest
         plan_build(m, B, dry, Ld);
         q.dry = false; q.seg_base = 0; q.total = dry.max_seg;
@@ -458,12 +501,10 @@ static void plan_make(const Model& m, int B, bool training, Plan& p, Layout& L, 
     p.training = training;
     p.dry = true;
     p.mask = training ? mask : nullptr;
-    plan_flags(m, p);
     plan_build(m, B, p, L);
     if (training && (p.max_temp > 0 || p.max_shared > 0)) {
         Plan q;                                    // second pass: the temporaries' ring (= the first two gradient buffers) first, then the shared act1 region, then the rest
         q.training = true; q.dry = false; q.mask = p.mask; q.temp_base = 0;
-        q.fwd_dw_s1 = p.fwd_dw_s1; q.fwd_dw_s2 = p.fwd_dw_s2; q.fwd_pro = p.fwd_pro;
         q.alias_G = p.max_temp > 0;
         q.max_temp = q.alias_G ? std::max(p.max_temp, p.gbytes_seen) : 0;
         q.shared_base = (int64_t)Plan::TRING * q.max_temp;
@@ -497,38 +538,12 @@ struct Exec {
     // finalised (the forward's .stat checkpoints are reused, the running buffers are not touched) and the segment's output is not rewritten
     bool replay = false;
     void done(int stage) const { if (stage_done) stage_done(stage, stage_user); }
-    // Fusing BatchNorm+GELU of the producer into the depthwise conv's input load removes one [M,C] write+read, but each input is
-    // loaded (and transformed) by its three neighbouring columns: the erf work triples and the conv turns VALU-bound
-    // (measured at 1024 images: +4.7 ms conv vs -2.7 ms elementwise) -> off by default.
-    bool f32 = false;       // reference-precision mode: f32 activations / cached weights, f32 MFMA, every fusion below off (set by exec_init)
-    bool fuse_dw = gg_dev_env("GG_FUSE_DW") != nullptr;
-    // the stride-2 depthwise conv of PatchMerging stages its input tile in LDS: BatchNorm1 + GELU are applied once per staged element
-    // (17x17 inputs per 8x8 outputs = 1.13x), the apply pass and the activation tensor disappear
-    bool fuse_dw_s2 = gg_dev_env("GG_NO_FUSE_DW_S2") == nullptr;
-    // MBConv.conv2 likewise through the 4-columns-per-thread stride-1 kernel (1.5 BatchNorm+GELU evaluations per input element)
-    bool fuse_dw_s1 = gg_dev_env("GG_NO_FUSE_DW_S1") == nullptr;
-    // Frozen depthwise taps: the data gradient forms BatchNorm backward's apply step (dy = c0*dz + c1*y + c2) while it loads its
-    // input, and (MBConv) emits dz = da*act'(BN(y)) + the reduce sums of the ConvNorm in front: apply and reduce passes and
-    // the dy / da tensors disappear.  GG_NO_FUSE_BNBWD=1 / GG_NO_FUSE_BNBWD_EPI=1 restore the separate passes.
-    bool fuse_bnbwd = gg_dev_env("GG_NO_FUSE_BNBWD") == nullptr;
-    bool fuse_bnbwd_epi = gg_dev_env("GG_NO_FUSE_BNBWD_EPI") == nullptr;
-    // Frozen ConvNorm chains: BatchNorm backward's reduce rides in the epilogue of the conv dgrad that produces its input
-    // gradient, and its apply step is folded into the weights of the 1x1 dgrad that consumes its output gradient.
-    bool fuse_bngemm = gg_dev_env("GG_NO_BNGEMM") == nullptr;
-    // MBConv conv3 applies BatchNorm2 + GELU in its A prologue (one N tile: each element is transformed once)
-    bool fuse_pro = gg_dev_env("GG_NO_PRO") == nullptr;
-    bool fuse_lncol = gg_dev_env("GG_NO_LN_COLSUM") == nullptr;   // norm2's backward leaves local_conv's BatchNorm-backward column sums (frozen blocks)
-    bool fuse_lnbn = true;           // fp32: local_conv's BatchNorm apply inside norm2 (off with GG_F32_NO_FUSE)
+    bool f32;               // reference-precision mode: f32 activations / cached weights, f32 MFMA
+    Exec(const Model& model, const Layout& layout, int batch, bool train) : m(&model), L(&layout), B(batch), training(train), f32(model.f32) {}
+    const Schedule& sch() const { return m->sch; }
     const float* P(int t) const { return params + m->tensors[t].offset; }
     float* Gd(int t) const { return grads + m->tensors[t].offset; }
     bool tr(int t) const { return trainable == nullptr || trainable[t] != 0; }
-    void exec_init() {
-        f32 = m->f32;
-        // reference-precision mode: the same fusions where an f32 twin exists (MBConv / PatchMerging forward, the stride-1 data gradients, the
-        // GEMM-side BatchNorm epilogue / prologues); GG_F32_NO_FUSE=1 runs every BatchNorm pass on its own (the schedule the fusions are tested against)
-        if (f32 && gg_dev_env("GG_F32_NO_FUSE")) fuse_dw = fuse_dw_s2 = fuse_dw_s1 = fuse_bnbwd = fuse_bnbwd_epi = fuse_bngemm = fuse_pro = fuse_lnbn = fuse_lncol = false;
-        if (f32) fuse_dw = false;
-    }
     act_t* A(int64_t off) const { return reinterpret_cast<act_t*>(ws + off); }
     float* F(int64_t off) const { return reinterpret_cast<float*>(ws + off); }
     const act_t* Wn(const DenseW& w) const { return reinterpret_cast<const act_t*>(wc + w.wn); }
@@ -537,17 +552,6 @@ struct Exec {
     const float* dropv(int slot) const { return drop ? drop + (int64_t)slot * B : nullptr; }
 };
 
-// conv dgrad with the BatchNorm-backward reduce of the ConvNorm it feeds as epilogue: dz = (dY . W) * act'(BN(y)), partial
-// column sums -> statpart
-static int gemm_bnbwd(const Exec& e, const act_t* dY, int64_t ldy, const act_t* Wt, int64_t ldw, act_t* dz, int64_t M, int N, int K,
-                      const BNP& bn, const Act& a, int act) {
-    GgGemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = dY; g.lda = ldy; g.B = Wt; g.ldb = ldw; g.C = dz; g.ldc = N; g.M = (int)M; g.N = N; g.K = K;
-    g.bn_y = e.A(a.y); g.bn_stat = e.F(a.stat); g.bn_gamma = e.P(bn.t_g); g.bn_beta = e.P(bn.t_b); g.bn_act = act;
-    g.colstats = e.F(e.L->statpart);
-    return e.f32 ? gg_gemm_nt_f32(&g, e.st) : gg_gemm_nt(&g, e.st);
-}
 // 1x1-conv dgrad straight from (dz, y): BatchNorm backward's apply step is folded into the weights (gg_bn_bwd_fold_weights)
 static int gemm_folded_dgrad(const Exec& e, const DenseW& w, const act_t* dz, const act_t* y, const float* coef, const float* stat,
                              act_t* dx, int64_t M, const act_t* residual) {
@@ -568,28 +572,36 @@ static int gemm_folded_dgrad(const Exec& e, const DenseW& w, const act_t* dz, co
     g.M = (int)M; g.N = Cin; g.K = 2 * Cout; g.bias = e.F(e.L->foldb); g.residual = residual; g.ldr = Cin;
     return gg_gemm_nt(&g, e.st);
 }
+// fp32_split mode: the split kernels need at least this many output tiles -- half the CUs' worth -- to beat the f32 GEMM, whose 64 x 64 tiles and
+// split-K fill the chip where a 256- / 128-row split tile would leave most CUs idle
+// (dev: GG_SPLIT_MIN_TILES lowers the threshold so that the oracle gate can take every split route at a batch the CPU oracle finishes in seconds)
+static int64_t split_min_tiles() {
+    static const char* env = gg_dev_env("GG_SPLIT_MIN_TILES");
+    static const int64_t min_tiles = env ? atoll(env) : 128;
+    return min_tiles;
+}
+// the cached bf16 planes of the f32 matrix W of the weight cache, if it has some that cover n rows at pitch ld; else null
+static const Model::PlaneOf* planes_of(const Exec& e, const act_t* W, int64_t ld, int n) {
+    const int64_t off = reinterpret_cast<const char*>(W) - e.wc;
+    for (const Model::PlaneOf& po : e.m->plane_of)
+        if (po.w == off) return po.ld == ld && po.rows >= n ? &po : nullptr;
+    return nullptr;
+}
 static int gemm(const Exec& e, const act_t* A, int64_t lda, const act_t* Bm, int64_t ldb, void* C, int64_t ldc, int64_t M, int N, int K,
                 const float* bias = nullptr, int act = 0, void* preact = nullptr, const float* rowscale = nullptr, int rps = 0,
                 const act_t* residual = nullptr, float* colstats = nullptr, const act_t* dact_pre = nullptr, int dact = 0) {
-    // (launch-bound sizes stay on the f32 GEMM, whose 64 x 64 tiles and split-K fill the chip where a 256- / 128-row split tile would leave most CUs idle:
-    // the split form needs at least half the CUs' worth of tiles)
     const int64_t split_tiles = ((M + (K >= 384 ? 255 : 127)) / (K >= 384 ? 256 : 128)) * ((N + 127) / 128);
-    // (dev: GG_SPLIT_MIN_TILES lowers the threshold so that the oracle gate can take every split route at a batch the CPU oracle finishes in seconds)
-    static const char* min_tiles_env = gg_dev_env("GG_SPLIT_MIN_TILES");
-    static const int64_t min_tiles = min_tiles_env ? atoll(min_tiles_env) : 128;
-    if (e.m->split && split_tiles >= min_tiles && (K & 7) == 0 && (lda & 3) == 0 && (!colstats || !(bias || act || preact || rowscale || residual || dact_pre))) {
+    const Model::PlaneOf* po = nullptr;
+    if (e.m->split && split_tiles >= split_min_tiles() && (K & 7) == 0 && (lda & 3) == 0 && (!colstats || !(bias || act || preact || rowscale || residual || dact_pre)))
+        po = planes_of(e, Bm, ldb, N);
+    if (po) {
         // fp32_split mode: a Linear whose weight operand has cached planes runs as a split product (A = the f32 activation itself, split in the kernel's loader)
-        const int64_t off = reinterpret_cast<const char*>(Bm) - e.wc;
-        for (const Model::PlaneOf& po : e.m->plane_of) {
-            if (po.w != off) continue;
-            if (po.ld != ldb || po.rows < N) break;
-            GgSplit3Args g;
-            memset(&g, 0, sizeof(g));
-            g.b_planes = e.wc + po.planes; g.ldb = ldb; g.M = (int)M; g.N = N; g.K = K; g.C = (float*)C; g.ldc = ldc;
-            g.bias = bias; g.act = act; g.preact = (float*)preact; g.rowscale = rowscale; g.rows_per_scale = rps; g.residual = (const float*)residual; g.ldr = ldc;
-            g.dact_preact = (const float*)dact_pre; g.dact = dact;
-            return gg_gemm_nt_split3_af32_stats(&g, (const float*)A, lda, (int64_t)po.rows * po.ld, colstats, e.st);
-        }
+        GgSplit3Args g;
+        memset(&g, 0, sizeof(g));
+        g.b_planes = e.wc + po->planes; g.ldb = ldb; g.M = (int)M; g.N = N; g.K = K; g.C = (float*)C; g.ldc = ldc;
+        g.bias = bias; g.act = act; g.preact = (float*)preact; g.rowscale = rowscale; g.rows_per_scale = rps; g.residual = (const float*)residual; g.ldr = ldc;
+        g.dact_preact = (const float*)dact_pre; g.dact = dact;
+        return gg_gemm_nt_split3_af32_stats(&g, (const float*)A, lda, (int64_t)po->rows * po->ld, colstats, e.st);
     }
     GgGemmArgs g;
     memset(&g, 0, sizeof(g));
@@ -619,21 +631,17 @@ static int conv_dense_fwd(const Exec& e, const ConvBNDense& c, const Act& a, con
 // dense ConvNorm whose input is act(BN(prev.y)) of the preceding ConvNorm, formed while the GEMM stages its A tile
 static int conv_dense_fwd_pro(const Exec& e, const ConvBNDense& c, const Act& a, const BNP& prev_bn, const Act& prev, int in_act, int64_t M) {
     // fp32_split mode: the same fusion on the split kernels (the transform rides on the loader, in front of the split; 256-row tiles: K >= 384)
-    static const char* min_tiles_env = gg_dev_env("GG_SPLIT_MIN_TILES");
-    const int64_t min_tiles = min_tiles_env ? atoll(min_tiles_env) : 128;
     static const char* nopro_env = gg_dev_env("GG_SPLIT3_NO_PRO");          // dev: the f32-MFMA prologue GEMM in the split mode too
-    if (e.m->split && !nopro_env && c.w.Kp >= 384 && c.w.Kp <= 1024 && (c.w.Kp & 7) == 0 && ((M + 255) / 256) * ((c.w.N + 127) / 128) >= min_tiles) {
-        const int64_t off = reinterpret_cast<const char*>(e.Wn(c.w)) - e.wc;
-        for (const Model::PlaneOf& po : e.m->plane_of) {
-            if (po.w != off) continue;
-            if (po.ld != c.w.Kp || po.rows < c.w.N) break;
-            GgSplit3Args g;
-            memset(&g, 0, sizeof(g));
-            g.b_planes = e.wc + po.planes; g.ldb = c.w.Kp; g.M = (int)M; g.N = c.w.N; g.K = c.w.Kp; g.C = (float*)e.A(a.y); g.ldc = c.w.N;
-            GG_TRY(gg_gemm_nt_split3_af32_pro(&g, (const float*)e.A(prev.y), c.w.Kp, (int64_t)po.rows * po.ld, e.F(prev.stat), e.P(prev_bn.t_g), e.P(prev_bn.t_b), in_act,
-                                              e.training ? e.F(e.L->statpart) : nullptr, e.st));
-            return bn_stats(e, c.bn, a, gg_gemm_colstats_rows((int)M), M);
-        }
+    const Model::PlaneOf* po = nullptr;
+    if (e.m->split && !nopro_env && c.w.Kp >= 384 && c.w.Kp <= 1024 && (c.w.Kp & 7) == 0 && ((M + 255) / 256) * ((c.w.N + 127) / 128) >= split_min_tiles())
+        po = planes_of(e, e.Wn(c.w), c.w.Kp, c.w.N);
+    if (po) {
+        GgSplit3Args g;
+        memset(&g, 0, sizeof(g));
+        g.b_planes = e.wc + po->planes; g.ldb = c.w.Kp; g.M = (int)M; g.N = c.w.N; g.K = c.w.Kp; g.C = (float*)e.A(a.y); g.ldc = c.w.N;
+        GG_TRY(gg_gemm_nt_split3_af32_pro(&g, (const float*)e.A(prev.y), c.w.Kp, (int64_t)po->rows * po->ld, e.F(prev.stat), e.P(prev_bn.t_g), e.P(prev_bn.t_b), in_act,
+                                          e.training ? e.F(e.L->statpart) : nullptr, e.st));
+        return bn_stats(e, c.bn, a, gg_gemm_colstats_rows((int)M), M);
     }
     GgGemmArgs g;
     memset(&g, 0, sizeof(g));
@@ -687,12 +695,30 @@ static void attn_args(const Exec& e, const StageL& st, const BlockL& l, const Bl
     at.scale = kAttnScale;
     at.out = e.A(a.o); at.ldo = C; at.lse = e.F(a.lse);
 }
+static int attention_fwd(const Exec& e, const GgAttnArgs& at) { return e.f32 ? gg_attention_flash_fwd(&at, 1, e.st) : gg_attention_fwd(&at, e.st); }
+static int attention_bwd(const Exec& e, const GgAttnArgs& at) { return e.f32 ? gg_attention_flash_bwd(&at, 1, e.st) : gg_attention_bwd(&at, e.st); }
+// PatchEmbed's gathers: the f32 NCHW image -> col1 [B*(H/2)^2, 32]; act(BN(y)) of an NHWC ConvNorm -> col [B*(H/2)^2, 9 C] (the activation is never written)
+static int im2col_image(const Exec& e, const float* x, act_t* col, int B, int H, int W) {
+    if (e.f32) return gg_im2col_nchw3_f32_f32(x, (float*)col, B, H, W, 2, e.st);
+    return gg_im2col_nchw3_f32(x, col, B, H, W, 2, e.st);
+}
+static int im2col_bn(const Exec& e, const BNP& bn, const Act& a, int act, act_t* col, int B, int H, int W) {
+    if (e.f32) return gg_im2col_nhwc_f32((const float*)e.A(a.y), e.F(a.stat), e.P(bn.t_g), e.P(bn.t_b), act, (float*)col, B, H, W, bn.C, 2, e.st);
+    return gg_im2col_nhwc_bn_bf16(e.A(a.y), e.F(a.stat), e.P(bn.t_g), e.P(bn.t_b), act, col, B, H, W, bn.C, 2, e.st);
+}
+static int token_mean_fwd(const Exec& e, const act_t* x, float* pooled, int B, int T, int C) {
+    return e.f32 ? gg_token_mean_fwd_f32((const float*)x, pooled, B, T, C, e.st) : gg_token_mean_fwd(x, pooled, B, T, C, e.st);
+}
+static int token_mean_bwd(const Exec& e, const float* dpool, act_t* dx, int B, int T, int C) {
+    return e.f32 ? gg_token_mean_bwd_f32(dpool, (float*)dx, B, T, C, e.st) : gg_token_mean_bwd(dpool, dx, B, T, C, e.st);
+}
 
 // ------------------------------------------------------------------------------------------- forward
 // One segment each: an MBConv of stage 0, a PatchMerging, a TinyVitBlock.  forward_impl runs them in order; under activation recompute
 // (GgTinyVitCfg.recompute = 1) backward_impl runs each again with e.replay right before the segment's backward: the same launches on the same
 // routes (fusion flags, split routing, the trainable-mask conditions), minus the segment's last launch -- the one that writes its output
 // checkpoint, which the segment's backward does not read -- and with no BatchNorm finalisation (bn_stats).
+// (the output of everything in front of stages[s]; s = 3: the last feature map, the head's input)
 static int64_t merge_input(const Layout& L, int s) {
     return s == 0 ? (L.mb.empty() ? L.x_pe : L.mb.back().out) : (L.blocks[s - 1].empty() ? L.merge[s - 1].out : L.blocks[s - 1].back().x3);
 }
@@ -704,14 +730,13 @@ static int mbconv_fwd(const Exec& e, size_t i, int slot) {
     const int mid = (int)(d[0] * c.mbconv_expand_ratio);
     const MBConvL& l = m.mb[i]; const MBAct& a = e.L->mb[i];
     GG_TRY(conv_dense_fwd(e, l.c1, a.c1, e.A(a.x), d[0], M0));
-    if (e.fuse_dw || e.fuse_dw_s1) {
+    if (act1_fused_away(e.sch(), 1)) {
         GG_TRY(conv_dw_fwd_fused(e, l.c2, a.c2, l.c1.bn, a.c1, GG_ACT_GELU, B, H0, H0, 1));   // act1 is never materialised
     } else {
         GG_TRY(bn_apply(e, l.c1.bn, a.c1, M0, GG_ACT_GELU, e.A(a.a1)));
         GG_TRY(conv_dw_fwd(e, l.c2, a.c2, e.A(a.a1), B, H0, H0, 1));
     }
-    // conv3 reads BN2+GELU of conv2's output through its A prologue unless its weight gradient needs that tensor
-    if (e.fuse_pro && !(e.training && e.tr(l.c3.w.t_w)) && l.c3.w.Kp == mid && mid <= 1024 && l.c3.w.N <= 128) {
+    if (conv3_takes_prologue(e.sch(), l.c3.w, mid, e.training && e.tr(l.c3.w.t_w))) {
         GG_TRY(conv_dense_fwd_pro(e, l.c3, a.c3, l.c2.bn, a.c2, GG_ACT_GELU, M0));
     } else {
         GG_TRY(bn_apply(e, l.c2.bn, a.c2, M0, GG_ACT_GELU, e.A(a.a2)));
@@ -729,7 +754,7 @@ static int merge_fwd(const Exec& e, int s) {
     const int64_t M = (int64_t)B * st.res * st.res, Mprev = (int64_t)B * res * res;
     const MergeAct& ma = L.merge[s];
     GG_TRY(conv_dense_fwd(e, st.merge.c1, ma.c1, e.A(merge_input(L, s)), Cprev, Mprev));
-    if (e.fuse_dw || e.fuse_dw_s2) {
+    if (act1_fused_away(e.sch(), 2)) {
         GG_TRY(conv_dw_fwd_fused(e, st.merge.c2, ma.c2, st.merge.c1.bn, ma.c1, GG_ACT_GELU, B, res, res, 2));
     } else {
         GG_TRY(bn_apply(e, st.merge.c1.bn, ma.c1, Mprev, GG_ACT_GELU, e.A(ma.a1)));
@@ -755,10 +780,10 @@ static int block_fwd(const Exec& e, int s, size_t i, int slot) {
     GG_TRY(gemm(e, e.A(a.a), C, e.Wn(l.qkv), l.qkv.Kp, e.A(a.qkv), 3 * C, M, 3 * C, l.qkv.Kp, e.P(l.qkv.t_b)));
     GgAttnArgs at;
     attn_args(e, st, l, a, B, at);
-    GG_TRY(e.f32 ? gg_attention_flash_fwd(&at, 1, e.st) : gg_attention_fwd(&at, e.st));
+    GG_TRY(attention_fwd(e, at));
     GG_TRY(gemm(e, e.A(a.o), C, e.Wn(l.proj), l.proj.Kp, e.A(a.x1), C, M, C, l.proj.Kp, e.P(l.proj.t_b), 0, nullptr, s1, rps, e.A(a.x0)));
     GG_TRY(conv_dw_fwd(e, l.local, a.local, e.A(a.x1), B, st.res, st.res, 1));
-    if (C <= 640 && e.f32 && e.fuse_lnbn) {      // BatchNorm apply of local_conv rides on norm2's load (x2 = the residual stream is written there)
+    if (C <= 640 && e.f32 && e.sch().fuse_lnbn) {     // BatchNorm apply of local_conv rides on norm2's load (x2 = the residual stream is written there)
         GG_TRY(gg_layernorm_fwd_bn_f32((const float*)e.A(a.local.y), e.F(a.local.stat), e.P(l.local.bn.t_g), e.P(l.local.bn.t_b), (float*)e.A(a.x2),
                                        e.P(l.ln2.t_g), e.P(l.ln2.t_b), M, C, c.ln_eps, (float*)e.A(a.b), e.F(a.mean2), e.F(a.rstd2), e.st));
     } else if (C <= 640 && !e.f32) {
@@ -774,71 +799,67 @@ static int block_fwd(const Exec& e, int s, size_t i, int slot) {
     return gemm(e, e.A(a.h), hid, e.Wn(l.fc2), l.fc2.Kp, e.A(a.x3), C, M, C, l.fc2.Kp, e.P(l.fc2.t_b), 0, nullptr, s2, rps, e.A(a.x2));
 }
 
-static int forward_impl(Exec& e, const float* x, float* out) {
-    const Model& m = *e.m; const Layout& L = *e.L; const GgTinyVitCfg& c = m.cfg;
-    const int B = e.B;
-    const int* d = c.embed_dims;
-    const int H = c.img_size, H1 = H / 2, H0 = m.res0;
+static int segment_fwd(const Exec& e, const Segment& sg) {
+    if (sg.kind == SEG_MBCONV) return mbconv_fwd(e, (size_t)sg.index, sg.slot);
+    return sg.kind == SEG_MERGE ? merge_fwd(e, sg.stage - 1) : block_fwd(e, sg.stage - 1, (size_t)sg.index, sg.slot);
+}
+// PatchEmbed: conv3x3 s2 + BN + GELU, conv3x3 s2 + BN
+static int patch_embed_fwd(const Exec& e, const float* x) {
+    const Model& m = *e.m; const Layout& L = *e.L;
+    const int B = e.B, H = m.cfg.img_size, H1 = H / 2, H0 = m.res0;
     const int64_t M1 = (int64_t)B * H1 * H1, M0 = (int64_t)B * H0 * H0;
-    // (num_batches_tracked counters are bumped by the host shim: they are int64 bookkeeping, not arithmetic)
-
-    // PatchEmbed: conv3x3 s2 + BN + GELU, conv3x3 s2 + BN
-    if (e.f32) GG_TRY(gg_im2col_nchw3_f32_f32(x, (float*)e.A(L.col1), B, H, H, 2, e.st));
-    else GG_TRY(gg_im2col_nchw3_f32(x, e.A(L.col1), B, H, H, 2, e.st));
+    GG_TRY(im2col_image(e, x, e.A(L.col1), B, H, H));
     GG_TRY(conv_dense_fwd(e, m.pe1, L.pe1, e.A(L.col1), 32, M1));
     GG_CHECK(m.pe2.w.Kp == m.pe2.w.K, "tinyvit: patch_embed.conv2 K=%d must be a multiple of 8", m.pe2.w.K);
     // BN1 + GELU ride on conv2's im2col gather: the activation tensor (M1 x 48, the largest of the model) is never written
-    if (e.f32) GG_TRY(gg_im2col_nhwc_f32((const float*)e.A(L.pe1.y), e.F(L.pe1.stat), e.P(m.pe1.bn.t_g), e.P(m.pe1.bn.t_b), GG_ACT_GELU,
-                                         (float*)e.A(L.col2), B, H1, H1, d[0] / 2, 2, e.st));
-    else GG_TRY(gg_im2col_nhwc_bn_bf16(e.A(L.pe1.y), e.F(L.pe1.stat), e.P(m.pe1.bn.t_g), e.P(m.pe1.bn.t_b), GG_ACT_GELU, e.A(L.col2), B, H1, H1,
-                                       d[0] / 2, 2, e.st));
+    GG_TRY(im2col_bn(e, m.pe1.bn, L.pe1, GG_ACT_GELU, e.A(L.col2), B, H1, H1));
     GG_TRY(conv_dense_fwd(e, m.pe2, L.pe2, e.A(L.col2), m.pe2.w.Kp, M0));
-    GG_TRY(bn_apply(e, m.pe2.bn, L.pe2, M0, GG_ACT_NONE, e.A(L.x_pe)));
-
-    // stage 0: MBConv blocks
-    int slot = 0;
-    for (size_t i = 0; i < m.mb.size(); ++i) GG_TRY(mbconv_fwd(e, i, slot++));
-    int64_t prev = merge_input(L, 0);
-    int res = H0;
-    for (int s = 0; s < 3; ++s) {
-        const StageL& st = m.stages[s];
-        GG_TRY(merge_fwd(e, s));
-        for (size_t i = 0; i < st.blocks.size(); ++i) {
-            GG_TRY(block_fwd(e, s, i, slot));
-            slot += 2;
-        }
-        prev = st.blocks.empty() ? L.merge[s].out : L.blocks[s].back().x3;
-        res = st.res;
-    }
-    // head: global average pool -> LayerNorm
-    const int T = res * res, C3 = d[3];
-    if (e.f32) GG_TRY(gg_token_mean_fwd_f32((const float*)e.A(prev), e.F(L.pooled), B, T, C3, e.st));
-    else GG_TRY(gg_token_mean_fwd(e.A(prev), e.F(L.pooled), B, T, C3, e.st));
+    return bn_apply(e, m.pe2.bn, L.pe2, M0, GG_ACT_NONE, e.A(L.x_pe));
+}
+// head: global average pool -> LayerNorm
+static int head_fwd(const Exec& e, float* out) {
+    const Model& m = *e.m; const Layout& L = *e.L; const GgTinyVitCfg& c = m.cfg;
+    const int B = e.B, res = m.stages[2].res, T = res * res, C3 = c.embed_dims[3];
+    GG_TRY(token_mean_fwd(e, e.A(merge_input(L, 3)), e.F(L.pooled), B, T, C3));
     if (c.features_only) {     // models/tinyvit.py:139-143: the pooled last feature map, no head.norm
         GG_HIP(hipMemcpyAsync(out, e.F(L.pooled), (size_t)B * C3 * sizeof(float), hipMemcpyDeviceToDevice, e.st));
         return 0;
     }
-    GG_TRY(gg_layernorm_fwd(e.F(L.pooled), 1, e.P(m.head.t_g), e.P(m.head.t_b), B, C3, c.ln_eps, out, 1, e.F(L.mean_h), e.F(L.rstd_h), e.st));
-    return 0;
+    return gg_layernorm_fwd(e.F(L.pooled), 1, e.P(m.head.t_g), e.P(m.head.t_b), B, C3, c.ln_eps, out, 1, e.F(L.mean_h), e.F(L.rstd_h), e.st);
+}
+// (num_batches_tracked counters are bumped by the host shim: they are int64 bookkeeping, not arithmetic)
+static int forward_impl(const Exec& e, const float* x, float* out) {
+    GG_TRY(patch_embed_fwd(e, x));
+    for (const Segment& sg : e.m->segs) GG_TRY(segment_fwd(e, sg));
+    return head_fwd(e, out);
 }
 
 // BatchNorm-backward pieces on the shared scratch: partial rows at the start of `bnscratch`, coef [3][C] right behind them
-static float* bn_coef(const Exec& e, int64_t M, int C) { return e.F(e.L->bnscratch) + ((int64_t)gg_bn_bwd_rows(M, C) + 64) * 2 * C; }
-static int bn_bwd_reduce_fin(const Exec& e, const BNP& bn, const Act& a, int64_t M, int act, const act_t* dout, act_t* dz) {
+static float* bn_coef(const Exec& e, int64_t M, int C) { return e.F(e.L->bnscratch) + ((int64_t)gg_bn_bwd_rows(M, C) + GG_REDUCE_SLICES) * 2 * C; }
+// finalize the BatchNorm-backward sums in `rows` partial rows at `part`: coef -> bn_coef(e, M, C), the parameter gradients if they train
+static int bn_bwd_fin(const Exec& e, const BNP& bn, const Act& a, int64_t M, float* part, int rows) {
     const bool tr = e.tr(bn.t_g);
+    return gg_bn_bwd_finalize(part, rows, bn.C, M, e.F(a.stat), e.P(bn.t_g), bn_coef(e, M, bn.C), tr ? e.Gd(bn.t_g) : nullptr,
+                              tr ? e.Gd(bn.t_b) : nullptr, 1, e.st);
+}
+static int bn_bwd_reduce_fin(const Exec& e, const BNP& bn, const Act& a, int64_t M, int act, const act_t* dout, act_t* dz) {
     if (e.f32) GG_TRY(gg_bn_bwd_reduce_f32((const float*)dout, (const float*)e.A(a.y), e.F(a.stat), e.P(bn.t_g), e.P(bn.t_b), M, bn.C, act, nullptr,
                                            nullptr, 0, (float*)dz, e.F(e.L->bnscratch), e.st));
     else GG_TRY(gg_bn_bwd_reduce(dout, e.A(a.y), e.F(a.stat), e.P(bn.t_g), e.P(bn.t_b), M, bn.C, act, nullptr, nullptr, 0, dz,
                             e.F(e.L->bnscratch), e.st));
-    return gg_bn_bwd_finalize(e.F(e.L->bnscratch), gg_bn_bwd_rows(M, bn.C), bn.C, M, e.F(a.stat), e.P(bn.t_g), bn_coef(e, M, bn.C),
-                              tr ? e.Gd(bn.t_g) : nullptr, tr ? e.Gd(bn.t_b) : nullptr, 1, e.st);
+    return bn_bwd_fin(e, bn, a, M, e.F(e.L->bnscratch), gg_bn_bwd_rows(M, bn.C));
 }
-
-// finalize BatchNorm-backward sums that a GEMM epilogue left in statpart
-static int bn_bwd_fin_gemm(const Exec& e, const BNP& bn, const Act& a, int64_t M) {
-    const bool tr = e.tr(bn.t_g);
-    return gg_bn_bwd_finalize(e.F(e.L->statpart), gg_gemm_colstats_rows((int)M), bn.C, M, e.F(a.stat), e.P(bn.t_g), bn_coef(e, M, bn.C),
-                              tr ? e.Gd(bn.t_g) : nullptr, tr ? e.Gd(bn.t_b) : nullptr, 1, e.st);
+// conv dgrad with the BatchNorm-backward reduce of the ConvNorm it feeds as epilogue: dz = (dY . W) * act'(BN(y)), partial
+// column sums -> statpart, then their finalize
+static int gemm_bnbwd(const Exec& e, const act_t* dY, int64_t ldy, const act_t* Wt, int64_t ldw, act_t* dz, int64_t M, int N, int K,
+                      const BNP& bn, const Act& a, int act) {
+    GgGemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.A = dY; g.lda = ldy; g.B = Wt; g.ldb = ldw; g.C = dz; g.ldc = N; g.M = (int)M; g.N = N; g.K = K;
+    g.bn_y = e.A(a.y); g.bn_stat = e.F(a.stat); g.bn_gamma = e.P(bn.t_g); g.bn_beta = e.P(bn.t_b); g.bn_act = act;
+    g.colstats = e.F(e.L->statpart);
+    GG_TRY(e.f32 ? gg_gemm_nt_f32(&g, e.st) : gg_gemm_nt(&g, e.st));
+    return bn_bwd_fin(e, bn, a, M, e.F(e.L->statpart), gg_gemm_colstats_rows((int)M));
 }
 
 __global__ void conv_wgrad_scatter_kernel(const float* __restrict__ src, int N, int Kp, int cin, int taps, float* __restrict__ grad) {
@@ -857,8 +878,7 @@ static int conv_wgrad_scatter(const float* src, int N, int Kp, int cin, int taps
 // ------------------------------------------------------------------------------------------- backward helpers
 // wgrad of a dense weight: dW[N,K] (+)= dY^T[N,M] . X[M,K]   (transposes into scratch, split-K over M)
 static int dense_wgrad(const Exec& e, const DenseW& w, const act_t* X, int64_t ldx, const act_t* dY, int64_t ldy, int64_t M,
-                       const float* rowscale, int rps, act_t* T0, act_t* T1, bool conv_reorder) {
-    (void)T0; (void)T1;
+                       const float* rowscale, int rps, bool conv_reorder) {
     const int K = conv_reorder ? w.Kp : w.K;   // im2col'd operand has Kp columns
     // fp32_split mode: the weight gradient of a block Linear (the tensors that have planes) as split products too, same slab protocol
     static const char* tn_min_env = gg_dev_env("GG_SPLIT_TN_MIN_M");      // (dev: the same for the weight gradients' row threshold)
@@ -878,28 +898,29 @@ static int dense_wgrad(const Exec& e, const DenseW& w, const act_t* X, int64_t l
     }
     return 0;
 }
+// PatchEmbed conv2's col2im (stride 2, onto conv1's [B, H, W] map): plain, and with the BatchNorm-backward reduce of conv1's ConvNorm riding on it
+static int col2im(const Exec& e, const act_t* dcol, act_t* dx, int B, int H, int W, int C) {
+    if (e.f32) return gg_col2im_nhwc_f32((const float*)dcol, (float*)dx, B, H, W, C, 2, e.st);
+    return gg_col2im_nhwc_bf16(dcol, dx, B, H, W, C, 2, e.st);
+}
+static int col2im_bnbwd(const Exec& e, const act_t* dcol, const BNP& bn, const Act& a, int act, act_t* dz, int nparts, int B, int H, int W) {
+    if (e.f32) return gg_col2im_nhwc_bnbwd_f32((const float*)dcol, (const float*)e.A(a.y), e.F(a.stat), e.P(bn.t_g), e.P(bn.t_b), act, (float*)dz,
+                                               e.F(e.L->bnscratch), nparts, B, H, W, bn.C, e.st);
+    return gg_col2im_nhwc_bnbwd_bf16(dcol, e.A(a.y), e.F(a.stat), e.P(bn.t_g), e.P(bn.t_b), act, dz, e.F(e.L->bnscratch), nparts, B, H, W, bn.C, e.st);
+}
 // weight gradient of a ConvNorm whose dy feeds nothing else (the first conv of the network): BatchNorm backward stops after
 // reduce + finalize, and the TN GEMM forms dy = c0*dz + c1*y + c2 from (dz, y) while loading -- no apply pass, no dy tensor
-// (dcol != null: dout does not exist yet -- the reduce rides on the col2im that would have produced it from dcol [B, H, W] stride 2)
-static int convnorm_wgrad_from_dz(const Exec& e, const ConvBNDense& c, const Act& a, int64_t M, int act, const act_t* dout, act_t* dz,
-                                  const act_t* X, int64_t ldx, const act_t* dcol = nullptr, int B = 0, int H = 0, int W = 0) {
-    const BNP& bn = c.bn;
-    const bool tr = e.tr(bn.t_g);
-    float* part = e.F(e.L->bnscratch);
-    const int nb = std::min(gg_bn_bwd_rows(M, bn.C), 65535);
-    float* coef = part + ((int64_t)gg_bn_bwd_rows(M, bn.C) + GG_REDUCE_SLICES) * 2 * bn.C;
-    if (dcol && e.f32) GG_TRY(gg_col2im_nhwc_bnbwd_f32((const float*)dcol, (const float*)e.A(a.y), e.F(a.stat), e.P(bn.t_g), e.P(bn.t_b), act, (float*)dz, part, nb, B, H, W, bn.C, e.st));
-    else if (dcol) GG_TRY(gg_col2im_nhwc_bnbwd_bf16(dcol, e.A(a.y), e.F(a.stat), e.P(bn.t_g), e.P(bn.t_b), act, dz, part, nb, B, H, W, bn.C, e.st));
-    else if (e.f32) GG_TRY(gg_bn_bwd_reduce_f32((const float*)dout, (const float*)e.A(a.y), e.F(a.stat), e.P(bn.t_g), e.P(bn.t_b), M, bn.C, act, nullptr, nullptr, 0, (float*)dz, part, e.st));
-    else GG_TRY(gg_bn_bwd_reduce(dout, e.A(a.y), e.F(a.stat), e.P(bn.t_g), e.P(bn.t_b), M, bn.C, act, nullptr, nullptr, 0, dz, part, e.st));
-    GG_TRY(gg_bn_bwd_finalize(part, nb, bn.C, M, e.F(a.stat), e.P(bn.t_g), coef, tr ? e.Gd(bn.t_g) : nullptr, tr ? e.Gd(bn.t_b) : nullptr, 1, e.st));
-    if (!e.tr(c.w.t_w)) return 0;
-    const DenseW& w = c.w;
-    const int K = w.Kp;
+// The output gradient does not exist yet either: the reduce rides on the col2im that would have produced it from dcol ([B, H, W] map, stride 2).
+static int convnorm_wgrad_from_dz(const Exec& e, const ConvBNDense& c, const Act& a, int64_t M, int act, act_t* dz, const act_t* X, int64_t ldx,
+                                  const act_t* dcol, int B, int H, int W) {
+    const BNP& bn = c.bn; const DenseW& w = c.w;
+    const int nb = std::min(gg_bn_bwd_rows(M, bn.C), 65535), K = w.Kp;
+    GG_TRY(col2im_bnbwd(e, dcol, bn, a, act, dz, nb, B, H, W));
+    GG_TRY(bn_bwd_fin(e, bn, a, M, e.F(e.L->bnscratch), nb));
+    if (!e.tr(w.t_w)) return 0;
     const int split = e.f32 ? gg_gemm_tn_f32_splits((int)M, w.N, K) : gg_gemm_tn_splits((int)M, w.N, K);
-    const act_t* dzs = dz ? dz : dout;      // no activation, no residual: dz == dout and the reduce writes nothing
-    if (e.f32) GG_TRY(gg_gemm_tn_bn_f32(dzs, e.A(a.y), bn.C, coef, X, ldx, (int)M, w.N, K, e.F(e.L->splitk), split, e.st));
-    else GG_TRY(gg_gemm_tn_bn(dzs, e.A(a.y), bn.C, coef, X, ldx, (int)M, w.N, K, e.F(e.L->splitk), split, e.st));
+    if (e.f32) GG_TRY(gg_gemm_tn_bn_f32(dz, e.A(a.y), bn.C, bn_coef(e, M, bn.C), X, ldx, (int)M, w.N, K, e.F(e.L->splitk), split, e.st));
+    else GG_TRY(gg_gemm_tn_bn(dz, e.A(a.y), bn.C, bn_coef(e, M, bn.C), X, ldx, (int)M, w.N, K, e.F(e.L->splitk), split, e.st));
     GG_TRY(gg_splitk_reduce(e.F(e.L->splitk), e.F(e.L->splitk), (int64_t)w.N * K, split, 0, 1.0f, e.st));
     return conv_wgrad_scatter(e.F(e.L->splitk), w.N, K, w.cin, w.taps, e.Gd(w.t_w), e.st);
 }
@@ -929,8 +950,26 @@ static int dw_bwd_data_fused(const Exec& e, const act_t* dz_in, const act_t* y_i
                                                       (const float*)ep_y, ep_stat, ep_gamma, ep_beta, ep_act, ep_part, e.st);
     return gg_dwconv3x3_bwd_data_fused(dz_in, y_in, in_coef, e.Taps(w), out, B, H, W, w.C, ep_y, ep_stat, ep_gamma, ep_beta, ep_act, ep_part, e.st);
 }
-static int dw_fused_rows(const Exec& e, int B, int H, int W, int C, int with_input_fusion) {
-    return e.f32 ? gg_dwconv_f32_stat_rows(B, H, W, C, 1) : gg_dwconv_fused_stat_rows(B, H, W, C, with_input_fusion);
+// The fused depthwise data gradient (stride 1: MBConv, 2: PatchMerging; [B, H, W] = the conv's input map) with its epilogue on, then the finalize of the
+// BatchNorm in front (bn1 / a1): dz1 = da1 * GELU'(BN1(y1)) -> dz1, BN1's backward sums -> statpart -> coef at bn_coef(e, B*H*W, C) and BN1's parameter
+// gradients.  The conv's own input dy2 is formed at its taps from (dz_in, y_in, in_coef), or is dz_in as given (y_in = in_coef = null; stride 1 only).
+static int dw_bwd_data_fused_fin(const Exec& e, const DwW& w, const act_t* dz_in, const act_t* y_in, const float* in_coef, act_t* dz1, int B, int H, int W,
+                                 int stride, const BNP& bn1, const Act& a1) {
+    const int C = w.C;
+    int rows;
+    if (stride == 1) {
+        GG_TRY(dw_bwd_data_fused(e, dz_in, y_in, in_coef, w, dz1, B, H, W, e.A(a1.y), e.F(a1.stat), e.P(bn1.t_g), e.P(bn1.t_b), GG_ACT_GELU, e.F(e.L->statpart)));
+        rows = e.f32 ? gg_dwconv_f32_stat_rows(B, H, W, C, 1) : gg_dwconv_fused_stat_rows(B, H, W, C, in_coef != nullptr);
+    } else if (e.f32) {
+        GG_TRY(gg_dwconv3x3_s2_bwd_data_fused_f32((const float*)dz_in, (const float*)y_in, in_coef, e.Taps(w), (float*)dz1, B, H, W, C, (const float*)e.A(a1.y),
+                                                  e.F(a1.stat), e.P(bn1.t_g), e.P(bn1.t_b), GG_ACT_GELU, e.F(e.L->statpart), e.st));
+        rows = gg_dwconv_f32_s2_fused_stat_rows(B, H, W, C);
+    } else {
+        GG_TRY(gg_dwconv3x3_s2_bwd_data_fused(dz_in, y_in, in_coef, e.Taps(w), dz1, B, H, W, C, e.A(a1.y), e.F(a1.stat), e.P(bn1.t_g), e.P(bn1.t_b),
+                                              GG_ACT_GELU, e.F(e.L->statpart), e.st));
+        rows = gg_dwconv_s2_fused_stat_rows(B, H, W, C);
+    }
+    return bn_bwd_fin(e, bn1, a1, (int64_t)B * H * W, e.F(e.L->statpart), rows);
 }
 static int dw_bwd_data(const Exec& e, const DwW& w, const act_t* dy, act_t* dx, int B, int H, int W, int stride) {
     if (e.f32) return gg_dwconv3x3_bwd_data_f32((const float*)dy, e.Taps(w), (float*)dx, B, H, W, w.C, stride, e.st);
@@ -940,281 +979,244 @@ static int dw_bwd_weight(const Exec& e, const DwW& w, const act_t* x, const act_
     if (e.f32) return gg_dwconv3x3_bwd_weight_f32((const float*)x, (const float*)dy, B, H, W, w.C, stride, e.F(e.L->bnscratch), e.Gd(w.t_w), 1, e.st);
     return gg_dwconv3x3_bwd_weight(x, dy, B, H, W, w.C, stride, e.F(e.L->bnscratch), e.Gd(w.t_w), 1, e.st);
 }
+// tap gradient of conv2 of an MBConv / a PatchMerging, whose input is act1 = GELU(BN1(y1)): re-formed here first where the forward never wrote it
+static int dw_bwd_weight_act1(const Exec& e, const DwW& w, const BNP& bn1, const Act& a1, int64_t act1, const act_t* dy, int B, int H, int W, int stride) {
+    if (act1_fused_away(e.sch(), stride)) GG_TRY(bn_apply(e, bn1, a1, (int64_t)B * H * W, GG_ACT_GELU, e.A(act1)));
+    return dw_bwd_weight(e, w, e.A(act1), dy, B, H, W, stride);
+}
 
-static int backward_impl(Exec& e, const float* d_out) {
+// ------------------------------------------------------------------------------------------- backward
+// One function per segment, mirroring the forward's.  The five gradient buffers (scratch.G0..G4): dx holds the gradient w.r.t. the segment's output
+// when its backward starts and w.r.t. its input when it returns; a..d are temporaries that carry nothing from one segment to the next.
+struct GradBufs { act_t *dx, *a, *b, *c, *d; };
+// head: LayerNorm (f32) + average pool
+static int head_bwd(const Exec& e, const float* d_out, const GradBufs& g) {
     const Model& m = *e.m; const Layout& L = *e.L; const GgTinyVitCfg& c = m.cfg;
-    const int B = e.B;
-    const int* d = c.embed_dims;
-    const int H = c.img_size, H1 = H / 2, H0 = m.res0;
-    const int64_t M1 = (int64_t)B * H1 * H1, M0 = (int64_t)B * H0 * H0;
-    act_t* G0 = e.A(L.G[0]); act_t* G1 = e.A(L.G[1]); act_t* G2 = e.A(L.G[2]); act_t* G3 = e.A(L.G[3]); act_t* G4 = e.A(L.G[4]);
-    // activation recompute: each segment's tensors are re-formed in the segment region right before its backward
-    const bool rc = c.recompute != 0;
-    Exec r = e;
-    r.replay = true;
-
-    // drop-path slot bookkeeping mirrors forward
-    int nslots = (int)m.mb.size();
-    for (int s = 0; s < 3; ++s) nslots += 2 * (int)m.stages[s].blocks.size();
-    int slot = nslots;
-
-    // ---- head: LayerNorm (f32) + average pool ----
-    const int res3 = m.stages[2].res, T = res3 * res3, C3 = d[3];
-    {
-        const bool tr = e.tr(m.head.t_g);
-        float* dpool = reinterpret_cast<float*>(G1);
-        if (c.features_only) GG_HIP(hipMemcpyAsync(dpool, d_out, (size_t)B * C3 * sizeof(float), hipMemcpyDeviceToDevice, e.st));
-        else GG_TRY(gg_layernorm_bwd(d_out, e.F(L.pooled), 1, e.F(L.mean_h), e.F(L.rstd_h), e.P(m.head.t_g), B, C3, nullptr, dpool,
-                                     e.F(L.lnscratch), tr ? e.Gd(m.head.t_g) : nullptr, tr ? e.Gd(m.head.t_b) : nullptr, 1, e.st));
-        if (e.f32) GG_TRY(gg_token_mean_bwd_f32(dpool, (float*)G0, B, T, C3, e.st));
-        else GG_TRY(gg_token_mean_bwd(dpool, G0, B, T, C3, e.st));
+    const int B = e.B, res = m.stages[2].res, T = res * res, C3 = c.embed_dims[3];
+    const bool tr = e.tr(m.head.t_g);
+    float* dpool = reinterpret_cast<float*>(g.a);
+    if (c.features_only) GG_HIP(hipMemcpyAsync(dpool, d_out, (size_t)B * C3 * sizeof(float), hipMemcpyDeviceToDevice, e.st));
+    else GG_TRY(gg_layernorm_bwd(d_out, e.F(L.pooled), 1, e.F(L.mean_h), e.F(L.rstd_h), e.P(m.head.t_g), B, C3, nullptr, dpool,
+                                 e.F(L.lnscratch), tr ? e.Gd(m.head.t_g) : nullptr, tr ? e.Gd(m.head.t_b) : nullptr, 1, e.st));
+    return token_mean_bwd(e, dpool, g.dx, B, T, C3);
+}
+// TinyVitBlock: x1 = x0 + s1*(proj(attn(qkv(ln1(x0))))+b); x2 = BN(dw(x1)); x3 = x2 + s2*(fc2(gelu(fc1(ln2(x2)))))
+static int block_bwd(const Exec& e, int s, size_t i, int slot, const GradBufs& g) {
+    const Model& m = *e.m; const Layout& L = *e.L; const Schedule& k = m.sch;
+    const StageL& st = m.stages[s];
+    const int B = e.B, C = st.C, hid = (int)(C * m.cfg.mlp_ratio), rps = st.res * st.res;
+    const int64_t M = (int64_t)B * rps;
+    const BlockL& l = st.blocks[i]; const BlockAct& a = L.blocks[s][i];
+    const float *s1 = e.dropv(slot), *s2 = e.dropv(slot + 1);
+    act_t *dx = g.dx, *t_a = g.a, *t_b = g.b, *t_c = g.c;
+    // dx == d(x3).  MLP branch: dh = (s2*dx) . W2  * gelu'(hpre)      -> t_b  [M, hid]
+    GG_TRY(gemm(e, dx, C, e.Wt(l.fc2), l.fc2.Np, t_b, hid, M, hid, C, nullptr, 0, nullptr, s2, rps, nullptr, nullptr, e.A(a.hpre), GG_ACT_GELU));
+    if (e.tr(l.fc2.t_w)) {
+        GG_TRY(dense_wgrad(e, l.fc2, e.A(a.h), hid, dx, C, M, s2, rps, false));
+        GG_TRY(bias_grad(e, l.fc2.t_b, dx, C, M, C, s2, rps));
     }
-    act_t* dx = G0;      // gradient w.r.t. the current activation (block output), bf16 [M, C]
-    // free buffers for the block-level temporaries
-    for (int s = 2; s >= 0; --s) {
-        if (s < 2) e.done(s + 2);          // model stage s+2 (blocks + PatchMerging) is enqueued: its parameter gradients are final
-        const StageL& st = m.stages[s];
-        const int C = st.C;
-        const int64_t M = (int64_t)B * st.res * st.res;
-        const int hid = (int)(C * c.mlp_ratio);
-        const int rps = st.res * st.res;
-        const int rin = s == 0 ? H0 : m.stages[s - 1].res;
-        const int Cin = s == 0 ? d[0] : m.stages[s - 1].C;
-        const int64_t Min = (int64_t)B * rin * rin;
-        for (int i = (int)st.blocks.size() - 1; i >= 0; --i) {
-            const BlockL& l = st.blocks[i]; const BlockAct& a = L.blocks[s][i];
-            slot -= 2;
-            if (rc) GG_TRY(block_fwd(r, s, (size_t)i, slot));
-            const float* s1 = e.dropv(slot);
-            const float* s2 = e.dropv(slot + 1);
-            // dx == d(x3).  MLP branch: x3 = x2 + s2*(fc2(gelu(fc1(ln2(x2)))))
-            act_t* t_a = (dx == G0) ? G1 : G0;    // scratch distinct from dx
-            act_t* t_b = G2; act_t* t_c = G3; act_t* t_d = G4;
-            // dh = (s2*dx) . W2  * gelu'(hpre)                      [M, hid]
-            GG_TRY(gemm(e, dx, C, e.Wt(l.fc2), l.fc2.Np, t_b, hid, M, hid, C, nullptr, 0, nullptr, s2, rps, nullptr, nullptr, e.A(a.hpre), GG_ACT_GELU));
-            if (e.tr(l.fc2.t_w)) {
-                GG_TRY(dense_wgrad(e, l.fc2, e.A(a.h), hid, dx, C, M, s2, rps, t_c, t_d, false));
-                GG_TRY(bias_grad(e, l.fc2.t_b, dx, C, M, C, s2, rps));
-            }
-            // db = dh . W1                                           [M, C]
-            GG_TRY(gemm(e, t_b, hid, e.Wt(l.fc1), l.fc1.Np, t_a, C, M, C, hid));
-            if (e.tr(l.fc1.t_w)) {
-                GG_TRY(dense_wgrad(e, l.fc1, e.A(a.b), C, t_b, hid, M, nullptr, 0, t_c, t_d, false));
-                GG_TRY(bias_grad(e, l.fc1.t_b, t_b, hid, M, hid, nullptr, 0));
-            }
-            // dx2 = LN2bwd(db) + dx                                   -> t_b
-            // frozen block: the same kernel also leaves (sum dx2*x2, sum dx2) per column, all that local_conv's BatchNorm backward needs
-            const bool lncol = e.fuse_lncol && e.fuse_bnbwd && C <= 640 && !e.tr(l.local.w.t_w) && !e.tr(l.local.bn.t_g) && !e.tr(l.local.bn.t_b) &&
-                               !e.tr(l.ln2.t_g) && !e.tr(l.ln2.t_b);       // (the fused form produces no LayerNorm / BatchNorm parameter gradients: every one of them must be frozen)
-            if (lncol) {
-                GG_TRY(gg_layernorm_bwd_colsum(t_a, e.A(a.x2), e.f32, e.F(a.mean2), e.F(a.rstd2), e.P(l.ln2.t_g), M, C, dx, t_b, e.F(L.lnscratch), e.st));
-            } else {
-                const bool tr = e.tr(l.ln2.t_g);
-                GG_TRY(gg_layernorm_bwd(t_a, e.A(a.x2), e.f32, e.F(a.mean2), e.F(a.rstd2), e.P(l.ln2.t_g), M, C, dx, t_b, e.F(L.lnscratch),
-                                        tr ? e.Gd(l.ln2.t_g) : nullptr, tr ? e.Gd(l.ln2.t_b) : nullptr, 1, e.st));
-            }
-            // local_conv: x2 = BN(dw(x1)).  dy -> t_a (dz scratch t_c), dx1 = dwT(dy) -> t_c
-            if (e.tr(l.local.w.t_w) || !e.fuse_bnbwd) {
-                GG_TRY(bn_bwd(e, l.local.bn, a.local, M, GG_ACT_NONE, t_b, t_c, t_a));
-                if (e.tr(l.local.w.t_w))
-                    GG_TRY(dw_bwd_weight(e, l.local.w, e.A(a.x1), t_a, B, st.res, st.res, 1));
-                GG_TRY(dw_bwd_data(e, l.local.w, t_a, t_c, B, st.res, st.res, 1));
-            } else {
-                // frozen taps: BN-backward apply is folded into the conv's staging (no dz / dy tensors at all)
-                if (lncol) GG_TRY(gg_bn_bwd_coef_from_x(e.F(L.lnscratch), gg_layernorm_bwd_colsum_rows(M), C, M, e.F(a.local.stat), e.P(l.local.bn.t_g),
-                                                        e.P(l.local.bn.t_b), bn_coef(e, M, C), e.st));
-                else GG_TRY(bn_bwd_reduce_fin(e, l.local.bn, a.local, M, GG_ACT_NONE, t_b, nullptr));
-                GG_TRY(dw_bwd_data_fused(e, t_b, e.A(a.local.y), bn_coef(e, M, C), l.local.w, t_c, B, st.res, st.res,
-                                                   nullptr, nullptr, nullptr, nullptr, 0, nullptr));
-            }
-            act_t* dx1 = t_c;
-            // attention branch: x1 = x0 + s1*(proj(o)+b)
-            // do = (s1*dx1) . Wproj                                   -> t_a  [M, C]
-            GG_TRY(gemm(e, dx1, C, e.Wt(l.proj), l.proj.Np, t_a, C, M, C, C, nullptr, 0, nullptr, s1, rps));
-            if (e.tr(l.proj.t_w)) {
-                GG_TRY(dense_wgrad(e, l.proj, e.A(a.o), C, dx1, C, M, s1, rps, t_b, t_d, false));
-                GG_TRY(bias_grad(e, l.proj.t_b, dx1, C, M, C, s1, rps));
-            }
-            // dqkv                                                     -> t_b  [M, 3C]
-            GgAttnArgs at;
-            attn_args(e, st, l, a, B, at);
-            at.dout = t_a; at.lddo = C; at.dqkv = t_b;
-            at.dbias = e.tr(l.t_ab) ? e.Gd(l.t_ab) : nullptr;
-            const bool flash = e.f32 || at.tokens_per_window > 256 || st.ws > 16;
-            const int64_t prow = flash ? gg_attention_flash_dbias_rows(at.num_windows, at.tokens_per_window) : (int64_t)at.num_windows + 64;
-            if (at.dbias && prow * st.heads * st.ws * st.ws * 4 <= ((int64_t)64 << 20))
-                at.dbias_scratch = e.F(L.splitk);      // per-workgroup partials -> deterministic second stage
-            static const bool ds_off = gg_dev_env("GG_ATTN_NO_DS_SCRATCH") != nullptr;
-            if (e.f32 && L.attn_ds >= 0 && !ds_off) at.ds_scratch = e.F(L.attn_ds);
-            GG_TRY(e.f32 ? gg_attention_flash_bwd(&at, 1, e.st) : gg_attention_bwd(&at, e.st));
-            // da = dqkv . Wqkv                                         -> t_a  [M, C]
-            GG_TRY(gemm(e, t_b, 3 * C, e.Wt(l.qkv), l.qkv.Np, t_a, C, M, C, 3 * C));
-            if (e.tr(l.qkv.t_w)) {
-                act_t* t_e = dx;   // the old block-output gradient is dead by now
-                GG_TRY(dense_wgrad(e, l.qkv, e.A(a.a), C, t_b, 3 * C, M, nullptr, 0, t_e, t_d, false));
-                GG_TRY(bias_grad(e, l.qkv.t_b, t_b, 3 * C, M, 3 * C, nullptr, 0));
-            }
-            // dx0 = LN1bwd(da) + dx1                                   -> old dx buffer
-            {
-                const bool tr = e.tr(l.ln1.t_g);
-                GG_TRY(gg_layernorm_bwd(t_a, e.A(a.x0), e.f32, e.F(a.mean1), e.F(a.rstd1), e.P(l.ln1.t_g), M, C, dx1, dx, e.F(L.lnscratch),
-                                        tr ? e.Gd(l.ln1.t_g) : nullptr, tr ? e.Gd(l.ln1.t_b) : nullptr, 1, e.st));
-            }
-            (void)hid;
-        }
-        // ---- PatchMerging backward: out = BN3(conv3(a2)); a2 = gelu(BN2(dw s2(a1))); a1 = gelu(BN1(conv1(x))) ----
-        if (rc) GG_TRY(merge_fwd(r, s));
-        const MergeAct& ma = L.merge[s];
-        act_t* t_a = (dx == G0) ? G1 : G0;
-        act_t* t_b = G2; act_t* t_c = G3; act_t* t_d = G4;
-        const int64_t xin = merge_input(L, s);
-        GG_TRY(bn_bwd(e, st.merge.c3.bn, ma.c3, M, GG_ACT_NONE, dx, t_b, t_a));                         // dy3 -> t_a
-        if (e.tr(st.merge.c3.w.t_w)) GG_TRY(dense_wgrad(e, st.merge.c3.w, e.A(ma.a2), C, t_a, C, M, nullptr, 0, t_b, t_c, false));
-        if (e.fuse_bngemm && !e.tr(st.merge.c1.w.t_w) && !e.tr(st.merge.c2.w.t_w) && C % 64 == 0) {
-            GG_TRY(gemm_bnbwd(e, t_a, C, e.Wt(st.merge.c3.w), st.merge.c3.w.Np, t_d, M, C, C, st.merge.c2.bn, ma.c2, GG_ACT_GELU));   // dz2 -> t_d
-            GG_TRY(bn_bwd_fin_gemm(e, st.merge.c2.bn, ma.c2, M));
-            if (e.fuse_bnbwd && e.fuse_bnbwd_epi) {
-                // the stride-2 data gradient forms dy2 from (dz2, y2) at its taps and emits dz1 = da1*GELU'(BN1(y1)) + BN1's sums
-                if (e.f32) GG_TRY(gg_dwconv3x3_s2_bwd_data_fused_f32((const float*)t_d, (const float*)e.A(ma.c2.y), bn_coef(e, M, C), e.Taps(st.merge.c2.w),
-                                                                     (float*)t_b, B, rin, rin, C, (const float*)e.A(ma.c1.y), e.F(ma.c1.stat),
-                                                                     e.P(st.merge.c1.bn.t_g), e.P(st.merge.c1.bn.t_b), GG_ACT_GELU, e.F(L.statpart), e.st));
-                else GG_TRY(gg_dwconv3x3_s2_bwd_data_fused(t_d, e.A(ma.c2.y), bn_coef(e, M, C), e.Taps(st.merge.c2.w), t_b, B, rin, rin, C,
-                                                      e.A(ma.c1.y), e.F(ma.c1.stat), e.P(st.merge.c1.bn.t_g), e.P(st.merge.c1.bn.t_b),
-                                                      GG_ACT_GELU, e.F(L.statpart), e.st));                    // dz1 -> t_b
-                const bool tr1 = e.tr(st.merge.c1.bn.t_g);
-                GG_TRY(gg_bn_bwd_finalize(e.F(L.statpart), e.f32 ? gg_dwconv_f32_s2_fused_stat_rows(B, rin, rin, C) : gg_dwconv_s2_fused_stat_rows(B, rin, rin, C), C, Min, e.F(ma.c1.stat),
-                                          e.P(st.merge.c1.bn.t_g), bn_coef(e, Min, C), tr1 ? e.Gd(st.merge.c1.bn.t_g) : nullptr,
-                                          tr1 ? e.Gd(st.merge.c1.bn.t_b) : nullptr, 1, e.st));
-                GG_TRY(gemm_folded_dgrad(e, st.merge.c1.w, t_b, e.A(ma.c1.y), bn_coef(e, Min, C), e.F(ma.c1.stat), dx, Min, nullptr));
-                continue;
-            }
-            GG_TRY(bn_bwd_apply_only(e, t_d, e.A(ma.c2.y), bn_coef(e, M, C), M, C, t_a));       // dy2 -> t_a
-            GG_TRY(dw_bwd_data(e, st.merge.c2.w, t_a, t_b, B, rin, rin, 2));         // da1 -> t_b [Min, C]
-            GG_TRY(bn_bwd_reduce_fin(e, st.merge.c1.bn, ma.c1, Min, GG_ACT_GELU, t_b, t_d));                 // dz1 -> t_d
-            GG_TRY(gemm_folded_dgrad(e, st.merge.c1.w, t_d, e.A(ma.c1.y), bn_coef(e, Min, C), e.F(ma.c1.stat), dx, Min, nullptr));
-            continue;
-        }
-        GG_TRY(gemm(e, t_a, C, e.Wt(st.merge.c3.w), st.merge.c3.w.Np, t_b, C, M, C, C));                 // da2 -> t_b
-        GG_TRY(bn_bwd(e, st.merge.c2.bn, ma.c2, M, GG_ACT_GELU, t_b, t_c, t_a));                          // dy2 -> t_a
-        if (e.tr(st.merge.c2.w.t_w)) {
-            if (e.fuse_dw || e.fuse_dw_s2) GG_TRY(bn_apply(e, st.merge.c1.bn, ma.c1, Min, GG_ACT_GELU, e.A(ma.a1)));      // act1 was fused away in forward
-            GG_TRY(dw_bwd_weight(e, st.merge.c2.w, e.A(ma.a1), t_a, B, rin, rin, 2));
-        }
-        GG_TRY(dw_bwd_data(e, st.merge.c2.w, t_a, t_b, B, rin, rin, 2));        // da1 -> t_b [Min, C]
-        GG_TRY(bn_bwd(e, st.merge.c1.bn, ma.c1, Min, GG_ACT_GELU, t_b, t_c, t_a));                        // dy1 -> t_a
-        if (e.tr(st.merge.c1.w.t_w)) GG_TRY(dense_wgrad(e, st.merge.c1.w, e.A(xin), Cin, t_a, C, Min, nullptr, 0, t_b, t_c, false));
-        GG_TRY(gemm(e, t_a, C, e.Wt(st.merge.c1.w), st.merge.c1.w.Np, dx, Cin, Min, Cin, C));             // dx_in -> dx
+    // db = dh . W1                                                     -> t_a  [M, C]
+    GG_TRY(gemm(e, t_b, hid, e.Wt(l.fc1), l.fc1.Np, t_a, C, M, C, hid));
+    if (e.tr(l.fc1.t_w)) {
+        GG_TRY(dense_wgrad(e, l.fc1, e.A(a.b), C, t_b, hid, M, nullptr, 0, false));
+        GG_TRY(bias_grad(e, l.fc1.t_b, t_b, hid, M, hid, nullptr, 0));
     }
-    e.done(1);
-    // ---- stage 0: MBConv backward ----
-    const int mid = (int)(d[0] * c.mbconv_expand_ratio);
-    const int rps0 = H0 * H0;
-    for (int i = (int)m.mb.size() - 1; i >= 0; --i) {
-        const MBConvL& l = m.mb[i]; const MBAct& a = L.mb[i];
-        slot -= 1;
-        if (rc) GG_TRY(mbconv_fwd(r, (size_t)i, slot));
-        const float* s0 = e.dropv(slot);
-        act_t* t_a = (dx == G0) ? G1 : G0;
-        act_t* t_b = G2; act_t* t_c = G3; act_t* t_d = G4;
-        // out = gelu(x + s*BN3(y3)):  dz(=dpre, also the skip gradient) -> t_b, dy3 -> t_a
-        GG_TRY(bn_bwd(e, l.c3.bn, a.c3, M0, GG_ACT_GELU, dx, t_b, t_a, e.A(a.x), s0, rps0));
-        // (a2 exists: the forward only skips it when its `trainable` mask freezes conv3 -- the two calls must get the same mask)
-        if (e.tr(l.c3.w.t_w)) GG_TRY(dense_wgrad(e, l.c3.w, e.A(a.a2), mid, t_a, d[0], M0, nullptr, 0, t_c, t_d, false));
-        if (e.fuse_bngemm && !e.tr(l.c1.w.t_w) && !e.tr(l.c2.w.t_w) && mid % 64 == 0) {
-            GG_TRY(gemm_bnbwd(e, t_a, d[0], e.Wt(l.c3.w), l.c3.w.Np, t_d, M0, mid, d[0], l.c2.bn, a.c2, GG_ACT_GELU));                   // dz2 -> t_d
-            GG_TRY(bn_bwd_fin_gemm(e, l.c2.bn, a.c2, M0));
-            act_t* dz1;
-            if (e.fuse_bnbwd && e.fuse_bnbwd_epi) {
-                GG_TRY(dw_bwd_data_fused(e, t_d, e.A(a.c2.y), bn_coef(e, M0, mid), l.c2.w, t_c, B, H0, H0, e.A(a.c1.y),
-                                                   e.F(a.c1.stat), e.P(l.c1.bn.t_g), e.P(l.c1.bn.t_b), GG_ACT_GELU, e.F(L.statpart)));   // dz1 -> t_c
-                const bool tr1 = e.tr(l.c1.bn.t_g);
-                GG_TRY(gg_bn_bwd_finalize(e.F(L.statpart), dw_fused_rows(e, B, H0, H0, mid, 1), mid, M0, e.F(a.c1.stat), e.P(l.c1.bn.t_g),
-                                          bn_coef(e, M0, mid), tr1 ? e.Gd(l.c1.bn.t_g) : nullptr, tr1 ? e.Gd(l.c1.bn.t_b) : nullptr, 1, e.st));
-                dz1 = t_c;
-            } else {
-                if (e.fuse_bnbwd) {      // dy2 is formed from (dz2, y2) inside the conv; da1 -> t_c
-                    GG_TRY(dw_bwd_data_fused(e, t_d, e.A(a.c2.y), bn_coef(e, M0, mid), l.c2.w, t_c, B, H0, H0, nullptr,
-                                                       nullptr, nullptr, nullptr, 0, nullptr));
-                } else {
-                    GG_TRY(bn_bwd_apply_only(e, t_d, e.A(a.c2.y), bn_coef(e, M0, mid), M0, mid, t_a));   // dy2 -> t_a
-                    GG_TRY(dw_bwd_data(e, l.c2.w, t_a, t_c, B, H0, H0, 1));             // da1 -> t_c
-                }
-                GG_TRY(bn_bwd_reduce_fin(e, l.c1.bn, a.c1, M0, GG_ACT_GELU, t_c, t_d));                        // dz1 -> t_d
-                dz1 = t_d;
-            }
-            GG_TRY(gemm_folded_dgrad(e, l.c1.w, dz1, e.A(a.c1.y), bn_coef(e, M0, mid), e.F(a.c1.stat), dx, M0, t_b));   // + dpre
-            continue;
-        }
-        if (e.fuse_bngemm && e.fuse_bnbwd && e.fuse_bnbwd_epi && mid % 64 == 0) {
-            // trainable weights: dy2 / dy1 are materialised for the weight gradients, but both BatchNorm-backward REDUCE passes still
-            // ride on the kernels that produce their inputs (conv3's dgrad epilogue, the depthwise data gradient's epilogue)
-            GG_TRY(gemm_bnbwd(e, t_a, d[0], e.Wt(l.c3.w), l.c3.w.Np, t_d, M0, mid, d[0], l.c2.bn, a.c2, GG_ACT_GELU));   // dz2 -> t_d
-            GG_TRY(bn_bwd_fin_gemm(e, l.c2.bn, a.c2, M0));
-            GG_TRY(bn_bwd_apply_only(e, t_d, e.A(a.c2.y), bn_coef(e, M0, mid), M0, mid, t_a));                // dy2 -> t_a
-            if (e.tr(l.c2.w.t_w)) {
-                if (e.fuse_dw || e.fuse_dw_s1) GG_TRY(bn_apply(e, l.c1.bn, a.c1, M0, GG_ACT_GELU, e.A(a.a1)));
-                GG_TRY(dw_bwd_weight(e, l.c2.w, e.A(a.a1), t_a, B, H0, H0, 1));
-            }
-            GG_TRY(dw_bwd_data_fused(e, t_a, nullptr, nullptr, l.c2.w, t_c, B, H0, H0, e.A(a.c1.y), e.F(a.c1.stat),
-                                               e.P(l.c1.bn.t_g), e.P(l.c1.bn.t_b), GG_ACT_GELU, e.F(L.statpart)));   // dz1 -> t_c
-            const bool tr1 = e.tr(l.c1.bn.t_g);
-            GG_TRY(gg_bn_bwd_finalize(e.F(L.statpart), dw_fused_rows(e, B, H0, H0, mid, 0), mid, M0, e.F(a.c1.stat), e.P(l.c1.bn.t_g),
-                                      bn_coef(e, M0, mid), tr1 ? e.Gd(l.c1.bn.t_g) : nullptr, tr1 ? e.Gd(l.c1.bn.t_b) : nullptr, 1, e.st));
-            GG_TRY(bn_bwd_apply_only(e, t_c, e.A(a.c1.y), bn_coef(e, M0, mid), M0, mid, t_a));                // dy1 -> t_a
-            if (e.tr(l.c1.w.t_w)) GG_TRY(dense_wgrad(e, l.c1.w, e.A(a.x), d[0], t_a, mid, M0, nullptr, 0, t_c, t_d, false));
-            GG_TRY(gemm(e, t_a, mid, e.Wt(l.c1.w), l.c1.w.Np, dx, d[0], M0, d[0], mid, nullptr, 0, nullptr, nullptr, 0, t_b));
-            continue;
-        }
-        GG_TRY(gemm(e, t_a, d[0], e.Wt(l.c3.w), l.c3.w.Np, t_c, mid, M0, mid, d[0]));                     // da2 -> t_c [M0, mid]
-        if (e.tr(l.c2.w.t_w) || !e.fuse_bnbwd || !e.fuse_bnbwd_epi) {
-            GG_TRY(bn_bwd(e, l.c2.bn, a.c2, M0, GG_ACT_GELU, t_c, t_d, t_a));                              // dy2 -> t_a
-            if (e.tr(l.c2.w.t_w)) {
-                if (e.fuse_dw || e.fuse_dw_s1) GG_TRY(bn_apply(e, l.c1.bn, a.c1, M0, GG_ACT_GELU, e.A(a.a1)));             // act1 was fused away in forward
-                GG_TRY(dw_bwd_weight(e, l.c2.w, e.A(a.a1), t_a, B, H0, H0, 1));
-            }
-            GG_TRY(dw_bwd_data(e, l.c2.w, t_a, t_c, B, H0, H0, 1));           // da1 -> t_c
-            GG_TRY(bn_bwd(e, l.c1.bn, a.c1, M0, GG_ACT_GELU, t_c, t_d, t_a));                              // dy1 -> t_a
+    // dx2 = LN2bwd(db) + dx                                            -> t_b
+    // frozen block: the same kernel also leaves (sum dx2*x2, sum dx2) per column, all that local_conv's BatchNorm backward needs
+    const bool lncol = k.fuse_lncol && k.fuse_bnbwd && C <= 640 && !e.tr(l.local.w.t_w) && !e.tr(l.local.bn.t_g) && !e.tr(l.local.bn.t_b) &&
+                       !e.tr(l.ln2.t_g) && !e.tr(l.ln2.t_b);       // (the fused form produces no LayerNorm / BatchNorm parameter gradients: every one of them must be frozen)
+    if (lncol) {
+        GG_TRY(gg_layernorm_bwd_colsum(t_a, e.A(a.x2), e.f32, e.F(a.mean2), e.F(a.rstd2), e.P(l.ln2.t_g), M, C, dx, t_b, e.F(L.lnscratch), e.st));
+    } else {
+        const bool tr = e.tr(l.ln2.t_g);
+        GG_TRY(gg_layernorm_bwd(t_a, e.A(a.x2), e.f32, e.F(a.mean2), e.F(a.rstd2), e.P(l.ln2.t_g), M, C, dx, t_b, e.F(L.lnscratch),
+                                tr ? e.Gd(l.ln2.t_g) : nullptr, tr ? e.Gd(l.ln2.t_b) : nullptr, 1, e.st));
+    }
+    // local_conv: x2 = BN(dw(x1)).  dy -> t_a (dz scratch t_c), dx1 = dwT(dy) -> t_c
+    if (e.tr(l.local.w.t_w) || !k.fuse_bnbwd) {
+        GG_TRY(bn_bwd(e, l.local.bn, a.local, M, GG_ACT_NONE, t_b, t_c, t_a));
+        if (e.tr(l.local.w.t_w)) GG_TRY(dw_bwd_weight(e, l.local.w, e.A(a.x1), t_a, B, st.res, st.res, 1));
+        GG_TRY(dw_bwd_data(e, l.local.w, t_a, t_c, B, st.res, st.res, 1));
+    } else {
+        // frozen taps: BN-backward apply is folded into the conv's staging (no dz / dy tensors at all)
+        if (lncol) GG_TRY(gg_bn_bwd_coef_from_x(e.F(L.lnscratch), gg_layernorm_bwd_colsum_rows(M), C, M, e.F(a.local.stat), e.P(l.local.bn.t_g),
+                                                e.P(l.local.bn.t_b), bn_coef(e, M, C), e.st));
+        else GG_TRY(bn_bwd_reduce_fin(e, l.local.bn, a.local, M, GG_ACT_NONE, t_b, nullptr));
+        GG_TRY(dw_bwd_data_fused(e, t_b, e.A(a.local.y), bn_coef(e, M, C), l.local.w, t_c, B, st.res, st.res, nullptr, nullptr, nullptr, nullptr, 0, nullptr));
+    }
+    act_t* dx1 = t_c;
+    // attention branch: do = (s1*dx1) . Wproj                          -> t_a  [M, C]
+    GG_TRY(gemm(e, dx1, C, e.Wt(l.proj), l.proj.Np, t_a, C, M, C, C, nullptr, 0, nullptr, s1, rps));
+    if (e.tr(l.proj.t_w)) {
+        GG_TRY(dense_wgrad(e, l.proj, e.A(a.o), C, dx1, C, M, s1, rps, false));
+        GG_TRY(bias_grad(e, l.proj.t_b, dx1, C, M, C, s1, rps));
+    }
+    // dqkv                                                             -> t_b  [M, 3C]
+    GgAttnArgs at;
+    attn_args(e, st, l, a, B, at);
+    at.dout = t_a; at.lddo = C; at.dqkv = t_b;
+    at.dbias = e.tr(l.t_ab) ? e.Gd(l.t_ab) : nullptr;
+    const bool flash = e.f32 || at.tokens_per_window > 256 || st.ws > 16;
+    const int64_t prow = flash ? gg_attention_flash_dbias_rows(at.num_windows, at.tokens_per_window) : (int64_t)at.num_windows + 64;
+    if (at.dbias && prow * st.heads * st.ws * st.ws * 4 <= ((int64_t)64 << 20))
+        at.dbias_scratch = e.F(L.splitk);      // per-workgroup partials -> deterministic second stage
+    static const bool ds_off = gg_dev_env("GG_ATTN_NO_DS_SCRATCH") != nullptr;
+    if (e.f32 && L.attn_ds >= 0 && !ds_off) at.ds_scratch = e.F(L.attn_ds);
+    GG_TRY(attention_bwd(e, at));
+    // da = dqkv . Wqkv                                                 -> t_a  [M, C]
+    GG_TRY(gemm(e, t_b, 3 * C, e.Wt(l.qkv), l.qkv.Np, t_a, C, M, C, 3 * C));
+    if (e.tr(l.qkv.t_w)) {
+        GG_TRY(dense_wgrad(e, l.qkv, e.A(a.a), C, t_b, 3 * C, M, nullptr, 0, false));
+        GG_TRY(bias_grad(e, l.qkv.t_b, t_b, 3 * C, M, 3 * C, nullptr, 0));
+    }
+    // dx0 = LN1bwd(da) + dx1                                           -> dx (the block-output gradient is dead by now)
+    const bool tr = e.tr(l.ln1.t_g);
+    return gg_layernorm_bwd(t_a, e.A(a.x0), e.f32, e.F(a.mean1), e.F(a.rstd1), e.P(l.ln1.t_g), M, C, dx1, dx, e.F(L.lnscratch),
+                            tr ? e.Gd(l.ln1.t_g) : nullptr, tr ? e.Gd(l.ln1.t_b) : nullptr, 1, e.st);
+}
+// PatchMerging: out = BN3(conv3(a2)); a2 = gelu(BN2(dw s2(a1))); a1 = gelu(BN1(conv1(x)))
+static int merge_bwd(const Exec& e, int s, const GradBufs& g) {
+    const Model& m = *e.m; const Layout& L = *e.L; const Schedule& k = m.sch;
+    const StageL& st = m.stages[s];
+    const ConvBNDense& c1 = st.merge.c1; const ConvBNDw& c2 = st.merge.c2; const ConvBNDense& c3 = st.merge.c3;
+    const MergeAct& ma = L.merge[s];
+    const int B = e.B, C = st.C, rin = s == 0 ? m.res0 : m.stages[s - 1].res, Cin = s == 0 ? m.cfg.embed_dims[0] : m.stages[s - 1].C;
+    const int64_t M = (int64_t)B * st.res * st.res, Min = (int64_t)B * rin * rin;
+    act_t *dx = g.dx, *t_a = g.a, *t_b = g.b, *t_c = g.c, *t_d = g.d;
+    GG_TRY(bn_bwd(e, c3.bn, ma.c3, M, GG_ACT_NONE, dx, t_b, t_a));                                     // dy3 -> t_a
+    if (e.tr(c3.w.t_w)) GG_TRY(dense_wgrad(e, c3.w, e.A(ma.a2), C, t_a, C, M, nullptr, 0, false));
+    if (k.fuse_bngemm && !e.tr(c1.w.t_w) && !e.tr(c2.w.t_w) && C % 64 == 0) {
+        // frozen chain: BatchNorm2's reduce rides on conv3's dgrad, BatchNorm1's apply is folded into conv1's
+        GG_TRY(gemm_bnbwd(e, t_a, C, e.Wt(c3.w), c3.w.Np, t_d, M, C, C, c2.bn, ma.c2, GG_ACT_GELU));   // dz2 -> t_d
+        act_t* dz1;
+        if (k.fuse_bnbwd && k.fuse_bnbwd_epi) {
+            // the stride-2 data gradient forms dy2 from (dz2, y2) at its taps and emits dz1 = da1*GELU'(BN1(y1)) + BN1's sums
+            GG_TRY(dw_bwd_data_fused_fin(e, c2.w, t_d, e.A(ma.c2.y), bn_coef(e, M, C), t_b, B, rin, rin, 2, c1.bn, ma.c1));   // dz1 -> t_b
+            dz1 = t_b;
         } else {
-            // frozen taps: 3 streaming passes instead of 5.  reduce(c2) -> dz2; the depthwise data gradient forms dy2 from
-            // (dz2, y2) while staging and emits dz1 = da1*GELU'(BN1(y1)) + BN1's backward statistics; apply(c1) -> dy1.
-            GG_TRY(bn_bwd_reduce_fin(e, l.c2.bn, a.c2, M0, GG_ACT_GELU, t_c, t_d));                        // dz2 -> t_d
-            GG_TRY(dw_bwd_data_fused(e, t_d, e.A(a.c2.y), bn_coef(e, M0, mid), l.c2.w, t_c, B, H0, H0, e.A(a.c1.y),
-                                               e.F(a.c1.stat), e.P(l.c1.bn.t_g), e.P(l.c1.bn.t_b), GG_ACT_GELU, e.F(L.statpart)));   // dz1 -> t_c
-            const bool tr1 = e.tr(l.c1.bn.t_g);
-            GG_TRY(gg_bn_bwd_finalize(e.F(L.statpart), dw_fused_rows(e, B, H0, H0, mid, 1), mid, M0, e.F(a.c1.stat), e.P(l.c1.bn.t_g),
-                                      bn_coef(e, M0, mid), tr1 ? e.Gd(l.c1.bn.t_g) : nullptr, tr1 ? e.Gd(l.c1.bn.t_b) : nullptr, 1, e.st));
-            GG_TRY(bn_bwd_apply_only(e, t_c, e.A(a.c1.y), bn_coef(e, M0, mid), M0, mid, t_a));                              // dy1 -> t_a
+            GG_TRY(bn_bwd_apply_only(e, t_d, e.A(ma.c2.y), bn_coef(e, M, C), M, C, t_a));              // dy2 -> t_a
+            GG_TRY(dw_bwd_data(e, c2.w, t_a, t_b, B, rin, rin, 2));                                    // da1 -> t_b [Min, C]
+            GG_TRY(bn_bwd_reduce_fin(e, c1.bn, ma.c1, Min, GG_ACT_GELU, t_b, t_d));                    // dz1 -> t_d
+            dz1 = t_d;
         }
-        if (e.tr(l.c1.w.t_w)) GG_TRY(dense_wgrad(e, l.c1.w, e.A(a.x), d[0], t_a, mid, M0, nullptr, 0, t_c, t_d, false));
-        // dx_in = dy1 . W1 + dpre
-        GG_TRY(gemm(e, t_a, mid, e.Wt(l.c1.w), l.c1.w.Np, dx, d[0], M0, d[0], mid, nullptr, 0, nullptr, nullptr, 0, t_b));
+        return gemm_folded_dgrad(e, c1.w, dz1, e.A(ma.c1.y), bn_coef(e, Min, C), e.F(ma.c1.stat), dx, Min, nullptr);
     }
-    e.done(0);
-    // ---- PatchEmbed backward (dgrad only to conv1's output; the image needs no gradient) ----
-    {
-        act_t* t_a = (dx == G0) ? G1 : G0;
-        act_t* t_b = G2; act_t* t_c = G3; act_t* t_d = G4;
-        const bool need1 = e.tr(m.pe1.w.t_w) || e.tr(m.pe1.bn.t_g);
-        const bool need2 = e.tr(m.pe2.w.t_w) || e.tr(m.pe2.bn.t_g) || need1;
-        // (conv2 keeps the three-pass BatchNorm backward: forming dy2 from (dx, y2) inside both of its GEMMs was measured at +1.7 ms of GEMM time
-        // against the 0.75 ms apply pass it removes -- the two-source prologue kernel at K = 96 runs at 62 TFLOP/s, the plain one at 86)
-        if (need2) {
-            GG_TRY(bn_bwd(e, m.pe2.bn, L.pe2, M0, GG_ACT_NONE, dx, t_b, t_a));                             // dy2 -> t_a [M0, C0]
-            if (e.tr(m.pe2.w.t_w)) GG_TRY(dense_wgrad(e, m.pe2.w, e.A(L.col2), m.pe2.w.Kp, t_a, d[0], M0, nullptr, 0, t_b, t_c, true));
-        }
-        if (need1) {
-            GG_TRY(gemm(e, t_a, d[0], e.Wt(m.pe2.w), m.pe2.w.Np, t_b, m.pe2.w.Kp, M0, m.pe2.w.Kp, d[0])); // dcol2 -> t_b
-            if (e.fuse_bnbwd && m.pe1.w.N == m.pe1.bn.C && (m.pe1.bn.C & (e.f32 ? 3 : 7)) == 0) {
-                // col2im + BN1-backward reduce in one pass (dz1 -> t_d; da1 and dy1 are never formed), weight gradient from (dz1, y1, coef)
-                GG_TRY(convnorm_wgrad_from_dz(e, m.pe1, L.pe1, M1, GG_ACT_GELU, nullptr, t_d, e.A(L.col1), 32, t_b, B, H1, H1));
+    GG_TRY(gemm(e, t_a, C, e.Wt(c3.w), c3.w.Np, t_b, C, M, C, C));                                     // da2 -> t_b
+    GG_TRY(bn_bwd(e, c2.bn, ma.c2, M, GG_ACT_GELU, t_b, t_c, t_a));                                    // dy2 -> t_a
+    if (e.tr(c2.w.t_w)) GG_TRY(dw_bwd_weight_act1(e, c2.w, c1.bn, ma.c1, ma.a1, t_a, B, rin, rin, 2));
+    GG_TRY(dw_bwd_data(e, c2.w, t_a, t_b, B, rin, rin, 2));                                            // da1 -> t_b [Min, C]
+    GG_TRY(bn_bwd(e, c1.bn, ma.c1, Min, GG_ACT_GELU, t_b, t_c, t_a));                                  // dy1 -> t_a
+    if (e.tr(c1.w.t_w)) GG_TRY(dense_wgrad(e, c1.w, e.A(merge_input(L, s)), Cin, t_a, C, Min, nullptr, 0, false));
+    return gemm(e, t_a, C, e.Wt(c1.w), c1.w.Np, dx, Cin, Min, Cin, C);                                 // dx_in -> dx
+}
+// MBConv: out = gelu(x + s*BN3(conv3(a2))); a2 = gelu(BN2(dw(a1))); a1 = gelu(BN1(conv1(x)))
+static int mbconv_bwd(const Exec& e, size_t i, int slot, const GradBufs& g) {
+    const Model& m = *e.m; const Layout& L = *e.L; const Schedule& k = m.sch;
+    const int B = e.B, H0 = m.res0, C0 = m.cfg.embed_dims[0];
+    const int64_t M0 = (int64_t)B * H0 * H0;
+    const int mid = (int)(C0 * m.cfg.mbconv_expand_ratio);
+    const MBConvL& l = m.mb[i]; const MBAct& a = L.mb[i];
+    act_t *dx = g.dx, *t_a = g.a, *t_b = g.b, *t_c = g.c, *t_d = g.d;
+    // dz(=dpre, also the skip gradient) -> t_b, dy3 -> t_a
+    GG_TRY(bn_bwd(e, l.c3.bn, a.c3, M0, GG_ACT_GELU, dx, t_b, t_a, e.A(a.x), e.dropv(slot), H0 * H0));
+    // (a2 exists: the forward only skips it when its `trainable` mask freezes conv3 -- the two calls must get the same mask)
+    if (e.tr(l.c3.w.t_w)) GG_TRY(dense_wgrad(e, l.c3.w, e.A(a.a2), mid, t_a, C0, M0, nullptr, 0, false));
+    const bool reduce_on_dgrad = k.fuse_bngemm && mid % 64 == 0;      // BatchNorm2's reduce rides in the epilogue of conv3's dgrad
+    const bool reduce_on_dw = k.fuse_bnbwd && k.fuse_bnbwd_epi;       // BatchNorm1's reduce rides in the epilogue of the depthwise data gradient
+    if (reduce_on_dgrad && !e.tr(l.c1.w.t_w) && !e.tr(l.c2.w.t_w)) {
+        // frozen chain: no dy tensor at all -- BatchNorm1's apply is folded into conv1's dgrad
+        GG_TRY(gemm_bnbwd(e, t_a, C0, e.Wt(l.c3.w), l.c3.w.Np, t_d, M0, mid, C0, l.c2.bn, a.c2, GG_ACT_GELU));             // dz2 -> t_d
+        act_t* dz1;
+        if (reduce_on_dw) {
+            GG_TRY(dw_bwd_data_fused_fin(e, l.c2.w, t_d, e.A(a.c2.y), bn_coef(e, M0, mid), t_c, B, H0, H0, 1, l.c1.bn, a.c1));   // dz1 -> t_c
+            dz1 = t_c;
+        } else {
+            if (k.fuse_bnbwd) {      // dy2 is formed from (dz2, y2) inside the conv; da1 -> t_c
+                GG_TRY(dw_bwd_data_fused(e, t_d, e.A(a.c2.y), bn_coef(e, M0, mid), l.c2.w, t_c, B, H0, H0, nullptr, nullptr, nullptr, nullptr, 0, nullptr));
             } else {
-                if (e.f32) GG_TRY(gg_col2im_nhwc_f32((const float*)t_b, (float*)t_c, B, H1, H1, d[0] / 2, 2, e.st));
-                else GG_TRY(gg_col2im_nhwc_bf16(t_b, t_c, B, H1, H1, d[0] / 2, 2, e.st));                  // da1 -> t_c [M1, C0/2]
-                GG_TRY(bn_bwd(e, m.pe1.bn, L.pe1, M1, GG_ACT_GELU, t_c, t_d, t_a));                         // dy1 -> t_a
-                if (e.tr(m.pe1.w.t_w)) GG_TRY(dense_wgrad(e, m.pe1.w, e.A(L.col1), 32, t_a, d[0] / 2, M1, nullptr, 0, t_b, t_c, true));
+                GG_TRY(bn_bwd_apply_only(e, t_d, e.A(a.c2.y), bn_coef(e, M0, mid), M0, mid, t_a));                         // dy2 -> t_a
+                GG_TRY(dw_bwd_data(e, l.c2.w, t_a, t_c, B, H0, H0, 1));                                                    // da1 -> t_c
             }
+            GG_TRY(bn_bwd_reduce_fin(e, l.c1.bn, a.c1, M0, GG_ACT_GELU, t_c, t_d));                                        // dz1 -> t_d
+            dz1 = t_d;
         }
+        return gemm_folded_dgrad(e, l.c1.w, dz1, e.A(a.c1.y), bn_coef(e, M0, mid), e.F(a.c1.stat), dx, M0, t_b);           // + dpre
     }
+    // dy1 in t_a: conv1's weight gradient, then dx_in = dy1 . W1 + dpre -> dx
+    auto conv1_bwd = [&]() -> int {
+        if (e.tr(l.c1.w.t_w)) GG_TRY(dense_wgrad(e, l.c1.w, e.A(a.x), C0, t_a, mid, M0, nullptr, 0, false));
+        return gemm(e, t_a, mid, e.Wt(l.c1.w), l.c1.w.Np, dx, C0, M0, C0, mid, nullptr, 0, nullptr, nullptr, 0, t_b);
+    };
+    if (reduce_on_dgrad && reduce_on_dw) {
+        // trainable weights: dy2 / dy1 are materialised for the weight gradients, but both BatchNorm-backward REDUCE passes still
+        // ride on the kernels that produce their inputs (conv3's dgrad epilogue, the depthwise data gradient's epilogue)
+        GG_TRY(gemm_bnbwd(e, t_a, C0, e.Wt(l.c3.w), l.c3.w.Np, t_d, M0, mid, C0, l.c2.bn, a.c2, GG_ACT_GELU));             // dz2 -> t_d
+        GG_TRY(bn_bwd_apply_only(e, t_d, e.A(a.c2.y), bn_coef(e, M0, mid), M0, mid, t_a));                                 // dy2 -> t_a
+        if (e.tr(l.c2.w.t_w)) GG_TRY(dw_bwd_weight_act1(e, l.c2.w, l.c1.bn, a.c1, a.a1, t_a, B, H0, H0, 1));
+        GG_TRY(dw_bwd_data_fused_fin(e, l.c2.w, t_a, nullptr, nullptr, t_c, B, H0, H0, 1, l.c1.bn, a.c1));                 // dz1 -> t_c
+        GG_TRY(bn_bwd_apply_only(e, t_c, e.A(a.c1.y), bn_coef(e, M0, mid), M0, mid, t_a));                                 // dy1 -> t_a
+        return conv1_bwd();
+    }
+    GG_TRY(gemm(e, t_a, C0, e.Wt(l.c3.w), l.c3.w.Np, t_c, mid, M0, mid, C0));                                              // da2 -> t_c [M0, mid]
+    if (e.tr(l.c2.w.t_w) || !reduce_on_dw) {
+        GG_TRY(bn_bwd(e, l.c2.bn, a.c2, M0, GG_ACT_GELU, t_c, t_d, t_a));                                                  // dy2 -> t_a
+        if (e.tr(l.c2.w.t_w)) GG_TRY(dw_bwd_weight_act1(e, l.c2.w, l.c1.bn, a.c1, a.a1, t_a, B, H0, H0, 1));
+        GG_TRY(dw_bwd_data(e, l.c2.w, t_a, t_c, B, H0, H0, 1));                                                            // da1 -> t_c
+        GG_TRY(bn_bwd(e, l.c1.bn, a.c1, M0, GG_ACT_GELU, t_c, t_d, t_a));                                                  // dy1 -> t_a
+    } else {
+        // frozen taps: 3 streaming passes instead of 5.  reduce(c2) -> dz2; the depthwise data gradient forms dy2 from
+        // (dz2, y2) while staging and emits dz1 = da1*GELU'(BN1(y1)) + BN1's backward statistics; apply(c1) -> dy1.
+        GG_TRY(bn_bwd_reduce_fin(e, l.c2.bn, a.c2, M0, GG_ACT_GELU, t_c, t_d));                                            // dz2 -> t_d
+        GG_TRY(dw_bwd_data_fused_fin(e, l.c2.w, t_d, e.A(a.c2.y), bn_coef(e, M0, mid), t_c, B, H0, H0, 1, l.c1.bn, a.c1)); // dz1 -> t_c
+        GG_TRY(bn_bwd_apply_only(e, t_c, e.A(a.c1.y), bn_coef(e, M0, mid), M0, mid, t_a));                                 // dy1 -> t_a
+    }
+    return conv1_bwd();
+}
+// PatchEmbed (dgrad only to conv1's output; the image needs no gradient)
+static int patch_embed_bwd(const Exec& e, const GradBufs& g) {
+    const Model& m = *e.m; const Layout& L = *e.L;
+    const int B = e.B, H1 = m.cfg.img_size / 2, H0 = m.res0, C0 = m.cfg.embed_dims[0];
+    const int64_t M1 = (int64_t)B * H1 * H1, M0 = (int64_t)B * H0 * H0;
+    act_t *dx = g.dx, *t_a = g.a, *t_b = g.b, *t_c = g.c, *t_d = g.d;
+    const bool need1 = e.tr(m.pe1.w.t_w) || e.tr(m.pe1.bn.t_g);
+    const bool need2 = e.tr(m.pe2.w.t_w) || e.tr(m.pe2.bn.t_g) || need1;
+    // (conv2 keeps the three-pass BatchNorm backward: forming dy2 from (dx, y2) inside both of its GEMMs was measured at +1.7 ms of GEMM time
+    // against the 0.75 ms apply pass it removes -- the two-source prologue kernel at K = 96 runs at 62 TFLOP/s, the plain one at 86)
+    if (need2) {
+        GG_TRY(bn_bwd(e, m.pe2.bn, L.pe2, M0, GG_ACT_NONE, dx, t_b, t_a));                             // dy2 -> t_a [M0, C0]
+        if (e.tr(m.pe2.w.t_w)) GG_TRY(dense_wgrad(e, m.pe2.w, e.A(L.col2), m.pe2.w.Kp, t_a, C0, M0, nullptr, 0, true));
+    }
+    if (!need1) return 0;
+    GG_TRY(gemm(e, t_a, C0, e.Wt(m.pe2.w), m.pe2.w.Np, t_b, m.pe2.w.Kp, M0, m.pe2.w.Kp, C0));          // dcol2 -> t_b
+    if (m.sch.fuse_bnbwd && m.pe1.w.N == m.pe1.bn.C && (m.pe1.bn.C & (e.f32 ? 3 : 7)) == 0) {
+        // col2im + BN1-backward reduce in one pass (dz1 -> t_d; da1 and dy1 are never formed), weight gradient from (dz1, y1, coef)
+        return convnorm_wgrad_from_dz(e, m.pe1, L.pe1, M1, GG_ACT_GELU, t_d, e.A(L.col1), 32, t_b, B, H1, H1);
+    }
+    GG_TRY(col2im(e, t_b, t_c, B, H1, H1, C0 / 2));                                                    // da1 -> t_c [M1, C0/2]
+    GG_TRY(bn_bwd(e, m.pe1.bn, L.pe1, M1, GG_ACT_GELU, t_c, t_d, t_a));                                // dy1 -> t_a
+    if (e.tr(m.pe1.w.t_w)) GG_TRY(dense_wgrad(e, m.pe1.w, e.A(L.col1), 32, t_a, C0 / 2, M1, nullptr, 0, true));
+    return 0;
+}
+static int segment_bwd(const Exec& e, const Segment& sg, const GradBufs& g) {
+    if (sg.kind == SEG_MBCONV) return mbconv_bwd(e, (size_t)sg.index, sg.slot, g);
+    return sg.kind == SEG_MERGE ? merge_bwd(e, sg.stage - 1, g) : block_bwd(e, sg.stage - 1, (size_t)sg.index, sg.slot, g);
+}
+// The driver: the forward's segments from the end, each replayed first under activation recompute (its tensors are re-formed in the segment
+// region right before its backward).  done(S): every launch of model stage S is enqueued, its parameter gradients are final (-1: all of them).
+static int backward_impl(const Exec& e, const float* d_out) {
+    const Model& m = *e.m; const Layout& L = *e.L;
+    const GradBufs g = {e.A(L.G[0]), e.A(L.G[1]), e.A(L.G[2]), e.A(L.G[3]), e.A(L.G[4])};
+    Exec r = e;          // the replaying executor takes e's routes: same flags, same mask, training
+    r.replay = true;
+    GG_TRY(head_bwd(e, d_out, g));
+    int stage = 3;
+    for (auto sg = m.segs.rbegin(); sg != m.segs.rend(); ++sg) {
+        for (; stage > sg->stage; --stage) e.done(stage);
+        if (m.cfg.recompute) GG_TRY(segment_fwd(r, *sg));
+        GG_TRY(segment_bwd(e, *sg, g));
+    }
+    for (; stage >= 0; --stage) e.done(stage);
+    GG_TRY(patch_embed_bwd(e, g));
     e.done(-1);
     return 0;
 }
@@ -1285,13 +1287,7 @@ extern "C" int gg_tinyvit_tensor_info(const GgTinyVitCfg* cfg, int i, char* name
 extern "C" int64_t gg_tinyvit_param_floats(const GgTinyVitCfg* cfg) { Model m; return build_model(cfg, m) ? -1 : m.param_floats; }
 extern "C" int64_t gg_tinyvit_buffer_floats(const GgTinyVitCfg* cfg) { Model m; return build_model(cfg, m) ? -1 : m.buffer_floats; }
 extern "C" int gg_tinyvit_num_counters(const GgTinyVitCfg* cfg) { Model m; return build_model(cfg, m) ? -1 : m.num_counters; }
-extern "C" int gg_tinyvit_num_drop_slots(const GgTinyVitCfg* cfg) {
-    Model m;
-    if (build_model(cfg, m)) return -1;
-    int n = (int)m.mb.size();
-    for (int s = 0; s < 3; ++s) n += 2 * (int)m.stages[s].blocks.size();
-    return n;
-}
+extern "C" int gg_tinyvit_num_drop_slots(const GgTinyVitCfg* cfg) { Model m; return build_model(cfg, m) ? -1 : m.drop_slots; }
 extern "C" int64_t gg_tinyvit_wcache_bytes(const GgTinyVitCfg* cfg) { Model m; return build_model(cfg, m) ? -1 : m.wcache_bytes; }
 extern "C" int64_t gg_tinyvit_workspace_bytes_masked(const GgTinyVitCfg* cfg, int batch, int training, const uint8_t* trainable) {
     Model m;
@@ -1380,11 +1376,10 @@ extern "C" int gg_tinyvit_forward(const GgTinyVitCfg* cfg, int batch, int traini
     Plan p; Layout L;
     plan_make(m, batch, training != 0, p, L, trainable);
     auto body = [&](hipStream_t st) -> int {
-        Exec e;
-        e.m = &m; e.L = &L; e.B = batch; e.training = training != 0; e.params = params; e.buffers = buffers; e.counters = counters;
+        Exec e(m, L, batch, training != 0);
+        e.params = params; e.buffers = buffers; e.counters = counters;
         e.wc = (const char*)wcache; e.ws = (char*)workspace; e.st = st; e.drop = drop_scales; e.grads = nullptr;
         e.trainable = trainable;       // NULL: keep every activation a weight gradient could need
-        e.exec_init();
         return forward_impl(e, x, out);
     };
     // launch-bound sizes (a serving panorama, small training batches: a few hundred launches of microseconds each) replay a captured graph
@@ -1402,8 +1397,8 @@ extern "C" int gg_tinyvit_backward(const GgTinyVitCfg* cfg, int batch, const flo
     GG_CHECK(batch > 0 && params && wcache && workspace && d_out && grads, "gg_tinyvit_backward: null pointer / bad batch");
     Plan p; Layout L;
     plan_make(m, batch, true, p, L, trainable);          // the SAME mask the training forward was called with: it decides the workspace layout
-    Exec e;
-    e.m = &m; e.L = &L; e.B = batch; e.training = true; e.params = params; e.buffers = nullptr; e.counters = nullptr;
+    Exec e(m, L, batch, true);
+    e.params = params; e.buffers = nullptr; e.counters = nullptr;
     e.wc = (const char*)wcache; e.ws = (char*)workspace; e.st = (hipStream_t)stream; e.drop = drop_scales; e.grads = grads;
     e.trainable = trainable; e.stage_done = stage_done; e.stage_user = stage_user;
     if (trainable) {
@@ -1421,14 +1416,11 @@ extern "C" int gg_tinyvit_backward(const GgTinyVitCfg* cfg, int batch, const flo
                      "gg_tinyvit_backward: %s and %s must be trainable or frozen together (requires_grad differs within the pair)", n.c_str(), it->first.c_str());
         }
     }
-    if (stage_done || !gg_graph_wanted((int64_t)batch * cfg->img_size * cfg->img_size <= (int64_t)64 * 224 * 224)) {      // a host callback per stage (N > 1): eager
-        e.exec_init();
+    if (stage_done || !gg_graph_wanted((int64_t)batch * cfg->img_size * cfg->img_size <= (int64_t)64 * 224 * 224))      // a host callback per stage (N > 1): eager
         return backward_impl(e, d_out);
-    }
     auto body = [&](hipStream_t st) -> int {
         Exec g = e;
         g.st = st;
-        g.exec_init();
         return backward_impl(g, d_out);
     };
     GgGraphKey key;

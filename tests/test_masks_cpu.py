@@ -48,7 +48,7 @@ def test_family_is_well_formed(L, name):
 
 
 # Groups of tr(...) sites of csrc/tinyvit.hip, as tensor-name patterns of ONE instance of the layer: the site's condition is "none of these trains"
-# (plan_make's keep() / alloc_temp per tensor, backward_impl's fused forms per group).  The family must hold a mask that makes it true and one that
+# (plan_build's keep() / alloc_temp per tensor, the fused forms of block_bwd / merge_bwd / mbconv_bwd / patch_embed_bwd per group).  The family must hold a mask that makes it true and one that
 # makes it false; the two policies alone leave most of them one-sided inside the frozen stages.
 SITE_GROUPS = {
     "plan: ln1 is a temporary (qkv frozen)": [r"^stages\.1\.blocks\.0\.attn\.qkv\.weight$"],
