@@ -71,7 +71,8 @@ class TinyVitCfg(C.Structure):
 
 class ClipCfg(C.Structure):
     _fields_ = [("hidden_size", C.c_int), ("intermediate_size", C.c_int), ("num_layers", C.c_int), ("num_heads", C.c_int),
-                ("image_size", C.c_int), ("patch_size", C.c_int), ("ln_eps", C.c_float), ("act_dtype", C.c_int)]
+                ("image_size", C.c_int), ("patch_size", C.c_int), ("ln_eps", C.c_float), ("act_dtype", C.c_int),
+                ("recompute", C.c_int)]
 
 
 STAGE_DONE_FN = C.CFUNCTYPE(None, C.c_int, C.c_void_p)      # GgStageDoneFn (host callback of gg_tinyvit_backward)

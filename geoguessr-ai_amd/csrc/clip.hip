@@ -12,7 +12,12 @@
 // pre-activation copy the backward pass needs), residual adds on out_proj's and fc2's.  Training keeps, for every layer from the first
 // trainable one up, the tensors its backward pass reads (layer input, both LayerNorm outputs + statistics, qkv, attention output + row
 // log-sum-exp, fc1 pre-activation and activation): sized for HBM, nothing is recomputed.  Frozen layers below run in place on scratch.
+// With activation recompute (GgClipCfg.recompute = 1) those layers keep only their input: everything else of a layer lives in ONE layer-sized
+// segment region all of them share, and the backward runs a layer's forward body again (the same launches on the same inputs) right before that
+// layer's backward -- the top layer excepted, whose tensors are still in the region from the forward.
 #include <algorithm>
+#include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 #include <string.h>
@@ -267,8 +272,11 @@ struct CPlan {
     int64_t xfinal;
     int64_t g_x0, g_x1, g_a, g_qkv, g_o, g_h, splitk, colsum, lnscr, lndump, attn_ds = -1;      // lndump: where a frozen LayerNorm tensor's half of a (gamma, beta) gradient pair goes      // backward scratch (attn_ds: GgAttnArgs.ds_scratch)
     int64_t total;
+    bool rc = false;                                          // checkpointed layout: every la[i] of a kept layer names the shared segment region but .xin
 };
-static void plan(const CModel& m, int B, const Train& tr, bool training, CPlan& L) {
+// ds_force: whether attn_ds exists is taken from the recompute-off plan of the same (batch, mask) (1 / 0; -1: decided here) -- its test depends on
+// the planned size, and both settings must take the same route through the attention backward
+static void plan(const CModel& m, int B, const Train& tr, bool training, CPlan& L, int ds_force = -1) {
     const int D = m.cfg.hidden_size, I = m.cfg.intermediate_size, nl = m.cfg.num_layers;
     const int64_t Mp = (int64_t)B * m.G * m.G, M = (int64_t)B * m.T, es = m.es;
     int64_t off = 0;
@@ -278,14 +286,28 @@ static void plan(const CModel& m, int B, const Train& tr, bool training, CPlan& 
     L.la.assign(nl, LayerA{});
     L.xfinal = L.s_x;
     const bool bwd = training && tr.l0 < nl;
+    L.rc = bwd && m.cfg.recompute != 0;
+    if (L.rc && ds_force < 0) {
+        CModel m0 = m; m0.cfg.recompute = 0;
+        CPlan L0; plan(m0, B, tr, training, L0);
+        ds_force = L0.attn_ds >= 0;
+    }
     if (bwd) {
-        for (int i = tr.l0; i < nl; ++i) {
-            LayerA& a = L.la[i];
-            a.xin = al(M * D * es); a.a1 = al(M * D * es); a.qkv = al(M * 3 * D * es); a.o = al(M * D * es);
+        auto inner = [&](LayerA& a) {
+            a.a1 = al(M * D * es); a.qkv = al(M * 3 * D * es); a.o = al(M * D * es);
             a.lse = al(M * m.cfg.num_heads * 4); a.xmid = al(M * D * es); a.a2 = al(M * D * es); a.pre = al(M * I * es); a.h = al(M * I * es);
             a.mean1 = al(M * 4); a.rstd1 = al(M * 4); a.mean2 = al(M * 4); a.rstd2 = al(M * 4);
+        };
+        if (!L.rc) {
+            for (int i = tr.l0; i < nl; ++i) { L.la[i].xin = al(M * D * es); inner(L.la[i]); }
+            L.xfinal = al(M * D * es);
+        } else {
+            for (int i = tr.l0; i < nl; ++i) L.la[i].xin = al(M * D * es);
+            L.xfinal = al(M * D * es);
+            LayerA seg{};
+            inner(seg);                                        // the segment region: one layer's worth, re-formed per layer by the backward
+            for (int i = tr.l0; i < nl; ++i) { seg.xin = L.la[i].xin; L.la[i] = seg; }
         }
-        L.xfinal = al(M * D * es);
         L.g_x0 = al(M * D * es); L.g_x1 = al(M * D * es); L.g_a = al(M * D * es); L.g_qkv = al(M * 3 * D * es); L.g_o = al(M * D * es);
         L.g_h = al(M * I * es);
         auto splits = [&](int64_t Mm, int N, int K) { return (int64_t)(m.f32 ? gg_gemm_tn_f32_splits((int)Mm, N, K) : gg_gemm_tn_splits((int)Mm, N, K)) * N * K; };
@@ -299,7 +321,9 @@ static void plan(const CModel& m, int B, const Train& tr, bool training, CPlan& 
         // 50-token towers run the single-pass kernel --, and only while it stays at most 4 GB and 1/8 of the workspace planned so far
         const int64_t dsb = gg_attention_flash_ds_scratch_floats(B, m.cfg.num_heads, m.T) * 4;
         static const bool ds_off = gg_dev_env("GG_ATTN_NO_DS_SCRATCH") != nullptr;
-        if (!ds_off && !gg_attention_flash_single_pass(m.T, D / m.cfg.num_heads, 0, 0) && dsb <= ((int64_t)4 << 30) && dsb <= off / 8) L.attn_ds = al(dsb);
+        const bool ds = ds_force >= 0 ? ds_force != 0
+                                      : !ds_off && !gg_attention_flash_single_pass(m.T, D / m.cfg.num_heads, 0, 0) && dsb <= ((int64_t)4 << 30) && dsb <= off / 8;
+        if (ds) L.attn_ds = al(dsb);
     }
     L.total = off;
 }
@@ -368,6 +392,62 @@ template <typename T> static int embed_fwd(const Exec& e, const float* x, void* 
                        B, m.T, D);
     GG_LAUNCH_CHECK();
     return 0;
+}
+// One encoder layer's forward from `cur`: LN1, qkv, attention, out_proj + residual, LN2, fc1 with QuickGELU (+ the pre-activation when kept), and
+// fc2 + residual into `next` (next < 0: skipped -- the recompute of a kept layer, whose fc2 output is the next layer's kept input).  sv: the layer's
+// tensors are kept in L.la[i] for its backward.  gg_clip_forward and the recompute of gg_clip_backward both come through here: same entry points,
+// same arguments.
+static int layer_fwd(const Exec& e, int i, int64_t cur, int64_t next, bool sv) {
+    const CModel& m = *e.m; const CPlan& L = *e.L;
+    const LayerP& l = m.layers[i];
+    const LayerA& a = L.la[i];
+    const int D = m.cfg.hidden_size, I = m.cfg.intermediate_size, T = m.T;
+    const int64_t M = (int64_t)e.B * T;
+    const int64_t A1 = sv ? a.a1 : L.s_a, QKV = sv ? a.qkv : L.s_qkv, O = sv ? a.o : L.s_o, XMID = sv ? a.xmid : cur, A2 = sv ? a.a2 : L.s_a,
+                  H = sv ? a.h : L.s_h;
+    GG_TRY(e.ln_fwd(e.A(cur), l.ln1_g, l.ln1_b, M, e.A(A1), sv ? e.F(a.mean1) : nullptr, sv ? e.F(a.rstd1) : nullptr));
+    GG_TRY(e.gemm(e.A(A1), D, e.W(l.wqkv), D, e.A(QKV), 3 * D, M, 3 * D, D, (const float*)e.W(l.bqkv)));
+    GgAttnArgs at;
+    e.attn_args(at, e.A(QKV), e.A(O), sv ? e.F(a.lse) : nullptr);
+    if (m.f16) GG_TRY(gg_attention_fwd_f16(&at, e.st));      // fp16 MFMA for towers of at most 256 tokens (ViT-B/32: 50); beyond: fp16 storage, f32 arithmetic
+    else if (m.f32 || sv || T > 256) GG_TRY(gg_attention_flash_fwd(&at, m.f32 ? 1 : 0, e.st));
+    else GG_TRY(gg_attention_fwd(&at, e.st));
+    // x_mid = x + out_proj(o)   (in place when nothing is kept: each element is read then written by the same lane)
+    GG_TRY(e.gemm(e.A(O), D, e.W(l.wo), D, e.A(XMID), D, M, D, D, e.P(l.o_b), 0, nullptr, e.A(cur)));
+    GG_TRY(e.ln_fwd(e.A(XMID), l.ln2_g, l.ln2_b, M, e.A(A2), sv ? e.F(a.mean2) : nullptr, sv ? e.F(a.rstd2) : nullptr));
+    GG_TRY(e.gemm(e.A(A2), D, e.W(l.w1), D, e.A(H), I, M, I, D, e.P(l.fc1_b), GG_ACT_CODE_QUICK_GELU, sv ? e.A(a.pre) : nullptr));
+    if (next >= 0) GG_TRY(e.gemm(e.A(H), I, e.W(l.w2), I, e.A(next), D, M, D, I, e.P(l.fc2_b), 0, nullptr, e.A(XMID)));
+    return 0;
+}
+
+// What the library has seen happen to a training workspace, by its address (host side): WS_RC -- the training forward that last wrote it ran the
+// checkpointed layout; WS_TOP -- the segment region still holds that forward's top layer (no backward has re-formed a lower layer in it since).
+// gg_clip_backward refuses the other layout, whose offsets name other bytes, and skips the top layer's recompute only while WS_TOP stands; a
+// workspace it knows nothing of (-1) is neither refused nor trusted: every layer is re-formed.  So the table only ever saves work or adds a
+// refusal, results never depend on it.  It is process-global state in an otherwise stateless API, bounded by dropping everything at 4096
+// entries; keys outlive the allocations they named (a freed and reused address keeps its entry until the next training forward there rewrites
+// it -- a backward is only defined after such a forward).
+enum { WS_RC = 1, WS_TOP = 2 };
+static std::mutex g_ws_mu;
+static std::map<const void*, int> g_ws_state;
+static void ws_forget(const void* ws) {
+    std::lock_guard<std::mutex> lk(g_ws_mu);
+    g_ws_state.erase(ws);
+}
+static void ws_note(const void* ws, int state) {
+    std::lock_guard<std::mutex> lk(g_ws_mu);
+    if (g_ws_state.size() >= 4096 && !g_ws_state.count(ws)) g_ws_state.clear();
+    g_ws_state[ws] = state;
+}
+static int ws_state(const void* ws) {      // -1: unknown
+    std::lock_guard<std::mutex> lk(g_ws_mu);
+    auto it = g_ws_state.find(ws);
+    return it == g_ws_state.end() ? -1 : it->second;
+}
+static void ws_clear_top(const void* ws) {      // (an unknown workspace stays unknown)
+    std::lock_guard<std::mutex> lk(g_ws_mu);
+    auto it = g_ws_state.find(ws);
+    if (it != g_ws_state.end()) it->second &= ~WS_TOP;
 }
 }  // namespace
 
@@ -461,32 +541,17 @@ extern "C" int gg_clip_forward(const GgClipCfg* cfg, int batch, int training, co
     GG_CHECK(!(m.f16 && training && tr.l0 < m.cfg.num_layers), "gg_clip_forward: the fp16 mode is inference-only (train in fp32 or bf16)");
     CPlan L; plan(m, batch, tr, training != 0, L);
     Exec e{&m, &L, batch, (hipStream_t)stream, params, (const char*)wcache, (char*)workspace, nullptr, trainable};
-    const int D = m.cfg.hidden_size, I = m.cfg.intermediate_size, T = m.T, B = batch, nl = m.cfg.num_layers;
+    const int D = m.cfg.hidden_size, T = m.T, B = batch, nl = m.cfg.num_layers;
     const int64_t M = (int64_t)B * T;
     const bool keep = training && tr.l0 < nl;
+    if (keep) ws_forget(workspace);                 // until every launch below is enqueued, the workspace holds no forward the table could vouch for
     auto saved = [&](int i) { return keep && i >= tr.l0; };
     GG_TRY(m.f32 ? embed_fwd<float>(e, x, e.A(L.tok)) : (m.f16 ? embed_fwd<f16>(e, x, e.A(L.tok)) : embed_fwd<bf16>(e, x, e.A(L.tok))));
     int64_t cur = saved(0) ? L.la[0].xin : L.s_x;
     GG_TRY(e.ln_fwd(e.A(L.tok), m.pre_g, m.pre_b, M, e.A(cur), keep && tr.embed ? e.F(L.mean0) : nullptr, keep && tr.embed ? e.F(L.rstd0) : nullptr));
     for (int i = 0; i < nl; ++i) {
-        const LayerP& l = m.layers[i];
-        const bool sv = saved(i);
-        const LayerA& a = L.la[i];
-        const int64_t A1 = sv ? a.a1 : L.s_a, QKV = sv ? a.qkv : L.s_qkv, O = sv ? a.o : L.s_o, XMID = sv ? a.xmid : cur, A2 = sv ? a.a2 : L.s_a,
-                      H = sv ? a.h : L.s_h;
         const int64_t next = (keep && i + 1 >= tr.l0) ? (i + 1 < nl ? L.la[i + 1].xin : L.xfinal) : cur;
-        GG_TRY(e.ln_fwd(e.A(cur), l.ln1_g, l.ln1_b, M, e.A(A1), sv ? e.F(a.mean1) : nullptr, sv ? e.F(a.rstd1) : nullptr));
-        GG_TRY(e.gemm(e.A(A1), D, e.W(l.wqkv), D, e.A(QKV), 3 * D, M, 3 * D, D, (const float*)e.W(l.bqkv)));
-        GgAttnArgs at;
-        e.attn_args(at, e.A(QKV), e.A(O), sv ? e.F(a.lse) : nullptr);
-        if (m.f16) GG_TRY(gg_attention_fwd_f16(&at, e.st));      // fp16 MFMA for towers of at most 256 tokens (ViT-B/32: 50); beyond: fp16 storage, f32 arithmetic
-        else if (m.f32 || sv || T > 256) GG_TRY(gg_attention_flash_fwd(&at, m.f32 ? 1 : 0, e.st));
-        else GG_TRY(gg_attention_fwd(&at, e.st));
-        // x_mid = x + out_proj(o)   (in place when nothing is kept: each element is read then written by the same lane)
-        GG_TRY(e.gemm(e.A(O), D, e.W(l.wo), D, e.A(XMID), D, M, D, D, e.P(l.o_b), 0, nullptr, e.A(cur)));
-        GG_TRY(e.ln_fwd(e.A(XMID), l.ln2_g, l.ln2_b, M, e.A(A2), sv ? e.F(a.mean2) : nullptr, sv ? e.F(a.rstd2) : nullptr));
-        GG_TRY(e.gemm(e.A(A2), D, e.W(l.w1), D, e.A(H), I, M, I, D, e.P(l.fc1_b), GG_ACT_CODE_QUICK_GELU, sv ? e.A(a.pre) : nullptr));
-        GG_TRY(e.gemm(e.A(H), I, e.W(l.w2), I, e.A(next), D, M, D, I, e.P(l.fc2_b), 0, nullptr, e.A(XMID)));
+        GG_TRY(layer_fwd(e, i, cur, next, saved(i)));
         cur = next;
     }
     if (m.f32) {
@@ -499,6 +564,7 @@ extern "C" int gg_clip_forward(const GgClipCfg* cfg, int batch, int training, co
         GG_TRY(gg_token_mean_fwd(e.A(cur), out, B, T, D, e.st));
         if (last_hidden) GG_TRY(gg_cast_bf16_to_f32(e.A(cur), last_hidden, M * D, e.st));
     }
+    if (keep) ws_note(workspace, (L.rc ? WS_RC : 0) | WS_TOP);
     return 0;
 }
 
@@ -515,6 +581,13 @@ extern "C" int gg_clip_backward(const GgClipCfg* cfg, int batch, const float* pa
     if (tr.l0 >= nl) return 0;                    // nothing in the tower is trainable
     GG_CHECK(!m.f16, "gg_clip_backward: the fp16 mode is inference-only");
     CPlan L; plan(m, batch, tr, true, L);
+    const int seen = ws_state(workspace);
+    GG_CHECK(seen < 0 || ((seen & WS_RC) != 0) == L.rc, "gg_clip_backward: cfg->recompute = %d, but the forward that last wrote this workspace ran with recompute = %d "
+             "(the checkpointed layout keeps other tensors); run the forward again", L.rc ? 1 : 0, seen & WS_RC);
+    // The top layer is the one layer whose tensors the forward leaves in the segment region.  Re-forming a lower layer overwrites them, so a further backward of
+    // the same forward (retain_graph, d_out and d_last_hidden in two calls) re-forms the top layer as well -- as does a backward that cannot tell.
+    const bool top_in_region = seen >= 0 && (seen & WS_TOP) != 0;
+    if (L.rc && tr.l0 < nl - 1) ws_clear_top(workspace);
     Exec e{&m, &L, batch, (hipStream_t)stream, params, (const char*)wcache, (char*)workspace, grads, trainable};
     const int D = m.cfg.hidden_size, I = m.cfg.intermediate_size, T = m.T, B = batch;
     const int64_t M = (int64_t)B * T, Mp = (int64_t)B * m.G * m.G;
@@ -525,6 +598,9 @@ extern "C" int gg_clip_backward(const GgClipCfg* cfg, int batch, const float* pa
     for (int i = nl - 1; i >= tr.l0; --i) {
         const LayerP& l = m.layers[i];
         const LayerA& a = L.la[i];
+        // activation recompute: the layer's tensors are re-formed in the segment region from its kept input (the top layer's are still the forward's in the first
+        // backward after it)
+        if (L.rc && (i < nl - 1 || !top_in_region)) GG_TRY(layer_fwd(e, i, a.xin, -1, true));
         // ---- MLP: x_out = x_mid + fc2(quick_gelu(fc1(LN2(x_mid))))
         GG_TRY(e.wgrad(l.fc2_w, e.A(dx), D, e.A(a.h), I, M, D, I));
         GG_TRY(e.bgrad(l.fc2_b, e.A(dx), D, M, D));

@@ -7,7 +7,8 @@
 * ``CLIPVisionTower``: the base model of ``SuperGuessr`` for CLIP runs (models/super_guessr.py:134-150: ``config._name_or_path`` contains
   "clip-vit", ``config.hidden_size``, ``vision_model.encoder.layers``).  It trains: the whole forward and backward are one C call each
   (``gg_clip_forward`` / ``gg_clip_backward``), parameters are views into one flat fp32 buffer like the TinyViT backbone's, so
-  ``optim.AdamW`` and the RCCL gradient exchange treat both encoders alike.
+  ``optim.AdamW`` and the RCCL gradient exchange treat both encoders alike.  ``gradient_checkpointing_enable()`` (HF's call) turns on
+  activation recompute (``GgClipCfg.recompute``): the workspace keeps each trained layer's input instead of its eight activations.
 
 Arithmetic: ``precision="fp32"`` (default; the reference runs the tower in fp32), ``"bf16"``, or ``"fp16"`` (inference only: the precision BASELINE
 config c4 names).  No hub download: weights come from a
@@ -76,12 +77,16 @@ class _VisionModel(FlatStore):
         self._register_table(init)
         self._wcache, self._wcache_version, self._ws = None, -1, {}
         self._last = None
+        self._toggled_since_forward = False      # a gradient_checkpointing toggle released the workspace of a training forward (until the next one)
         self._gen = 0
         self._grad_ready_hook = None      # (optim.AdamW.overlap_allreduce sets it; the CLIP backward has no stage callback: buckets leave after it)
 
 
 class CLIPVisionTower(nn.Module):
-    def __init__(self, model_name: str = "openai/clip-vit-base-patch32", seed: int = 0, precision: Optional[str] = None, **cfg_overrides):
+    supports_gradient_checkpointing = True          # (transformers PreTrainedModel's class attribute)
+
+    def __init__(self, model_name: str = "openai/clip-vit-base-patch32", seed: int = 0, precision: Optional[str] = None,
+                 gradient_checkpointing: bool = False, **cfg_overrides):
         super().__init__()
         kw = dict(CLIP_CONFIGS.get(model_name, CLIP_CONFIGS["openai/clip-vit-base-patch32"]))
         kw.update(cfg_overrides)
@@ -89,11 +94,37 @@ class CLIPVisionTower(nn.Module):
         c.hidden_size, c.intermediate_size, c.num_layers, c.num_heads = kw["hidden_size"], kw["intermediate_size"], kw["num_layers"], kw["num_heads"]
         c.image_size, c.patch_size, c.ln_eps = kw["image_size"], kw["patch_size"], 1e-5
         c.act_dtype = _precision_code(precision)
+        c.recompute = int(bool(gradient_checkpointing))
         self.cfg = c
         self.precision = {0: "bf16", 1: "fp32", 2: "fp16"}[c.act_dtype]
         self.config = SimpleNamespace(hidden_size=kw["hidden_size"], _name_or_path=model_name, **{k: v for k, v in kw.items() if k != "hidden_size"})
         self.vision_model = _VisionModel(c, seed)
         self.num_tokens = (c.image_size // c.patch_size) ** 2 + 1
+
+    # ---- activation recompute -----------------------------------------------------------------------------------------------------------
+    @property
+    def is_gradient_checkpointing(self) -> bool:
+        return bool(self.cfg.recompute)
+
+    def _set_gradient_checkpointing(self, enable: bool):
+        vm = self.vision_model
+        if enable != bool(self.cfg.recompute):
+            if vm._last is not None:
+                vm._toggled_since_forward = True
+            self.cfg.recompute = int(enable)
+            vm._ws.pop(True, None)            # laid out for the other plan: the next training forward sizes a new one
+            vm._last = None
+
+    def gradient_checkpointing_enable(self, gradient_checkpointing_kwargs=None):
+        """transformers' switch (``model.gradient_checkpointing_enable()``): activation recompute of the training step (``GgClipCfg.recompute``,
+        include/gg.h).  The workspace keeps the input of every encoder layer from the first trainable one up; the backward re-forms a layer's
+        other tensors (LayerNorm outputs, qkv, attention output, the MLP activations) right before its backward.  ``pooled_mean``,
+        ``last_hidden_state`` and every gradient are bit-identical to the step without recompute.  ``gradient_checkpointing_kwargs`` (HF's
+        ``use_reentrant``) has no counterpart here and is ignored.  Inference ignores the setting."""
+        self._set_gradient_checkpointing(True)
+
+    def gradient_checkpointing_disable(self):
+        self._set_gradient_checkpointing(False)
 
     # ---- weights ----------------------------------------------------------------------------------------------------------------------
     @property
@@ -156,11 +187,15 @@ class CLIPVisionTower(nn.Module):
         if training:
             vm._gen += 1
             vm._last = (B, mask, vm._gen)
+            vm._toggled_since_forward = False
         return out, last
 
     def backward_hip(self, d_out: Optional[Tensor], d_last: Optional[Tensor], gen: int):
         vm = self.vision_model
         if vm._last is None:
+            if vm._toggled_since_forward:
+                raise L.GgError(f"gradient checkpointing was toggled since the training forward (now recompute={self.cfg.recompute}): its workspace was "
+                                "released, the other layout keeps other tensors; run the forward again")
             raise L.GgError("CLIP backward without a training forward")
         B, mask, last_gen = vm._last
         if gen != last_gen:

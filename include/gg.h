@@ -543,11 +543,28 @@ int gg_segment_mean(const float* emb, int64_t ld, const int64_t* ptr, const int6
  * accumulation (2: inference only -- BASELINE config c4 names fp16).
  * Parameters: one flat f32 buffer, HF state-dict names without the "vision_model." prefix (gg_clip_tensor_info).  `trainable` (host,
  * one byte per tensor, NULL = all) selects the tensors whose gradients gg_clip_backward accumulates; a training forward keeps the
- * activations of every layer from the first trainable one up (gg_clip_first_trained_layer), frozen layers below run in place. */
+ * activations of every layer from the first trainable one up (gg_clip_first_trained_layer), frozen layers below run in place; with
+ * cfg->recompute = 1 it keeps only those layers' inputs and gg_clip_workspace_bytes is the size of the checkpointed layout. */
 typedef struct GgClipCfg {
     int hidden_size, intermediate_size, num_layers, num_heads, image_size, patch_size;
     float ln_eps;
     int act_dtype;                         /* 0 bf16, 1 fp32, 2 fp16 (inference only) */
+    int recompute;       /* activation recompute (gradient checkpointing, HF gradient_checkpointing_enable) of a training forward / backward pair;
+                            ignored by inference (training = 0).  0: the workspace keeps every activation the backward reads.
+                            1: per-layer checkpoints -- the segments are the encoder layers from the first trainable one up.  The workspace keeps
+                               the embedding side (col, patches, the tokens before pre_layrnorm and its statistics), every such layer's input and
+                               the last layer's output, each in a region of its own; every other tensor of a layer (both LayerNorm outputs and
+                               their statistics, qkv, the attention output and its row log-sum-exp, x_mid, the fc1 pre-activation and activation)
+                               lives in ONE segment region shared by all layers.  gg_clip_backward runs each layer's forward launches again
+                               (same kernels, same routing, up to fc1: fc2's output is the next layer's kept input) before that layer's backward;
+                               the top layer's tensors are still the forward's in the first backward after it.  Further backwards of the same
+                               forward (d_out and d_last_hidden in two calls, retain_graph) are as valid as with recompute = 0: they re-form the
+                               top layer too, as does any backward on a workspace whose forward this process has not seen.
+                               Contract: out, last_hidden and every parameter gradient are bit-identical to recompute = 0 (the recompute takes the
+                               forward's routes on the same inputs; the CLIP backward has no atomics, so there is no exemption).  Whether the
+                               attention backward's dS hand-off exists is taken from the recompute = 0 plan of the same batch and mask.
+                               The workspace size and layout depend on the field: forward and backward must see the same value
+                               (gg_clip_backward refuses the other value for a workspace whose last training forward it has seen). */
 } GgClipCfg;
 int gg_clip_num_tensors(const GgClipCfg* cfg);
 int gg_clip_tensor_info(const GgClipCfg* cfg, int i, char* name, int name_cap, int64_t* offset, int64_t* numel, int* ndim, int64_t* shape4);
