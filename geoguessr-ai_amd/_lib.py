@@ -28,7 +28,7 @@ class GemmArgs(C.Structure):
                 ("a_bn_act", C.c_int)]
 
 
-class Split3Args(C.Structure):          # GgSplit3Args (experiment: fp32-accurate GEMM from three bf16 planes per operand)
+class Split3Args(C.Structure):          # GgSplit3Args (the fp32_split mode's GEMM: fp32-accurate from three bf16 planes per operand)
     _fields_ = [("a_planes", C.c_void_p), ("lda", C.c_int64), ("b_planes", C.c_void_p), ("ldb", C.c_int64), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
                 ("C", C.c_void_p), ("ldc", C.c_int64), ("c_planes", C.c_void_p), ("ldp", C.c_int64), ("bias", C.c_void_p), ("act", C.c_int),
                 ("preact", C.c_void_p), ("rowscale", C.c_void_p), ("rows_per_scale", C.c_int), ("residual", C.c_void_p), ("ldr", C.c_int64),

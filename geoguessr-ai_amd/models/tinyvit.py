@@ -14,13 +14,13 @@ import math
 import os
 import warnings
 from types import SimpleNamespace
-from typing import Dict, List, Optional
+from typing import List, Optional
 
 import torch
 import torch.nn as nn
 
 from .. import _lib as L
-from .flat import FlatStore, _Tree
+from .flat import EncoderNode, EncoderRuntime
 
 # timm variants; drop_path_rate is timm's per-variant default
 VARIANTS = {
@@ -67,7 +67,7 @@ def make_cfg(model_name: str, **overrides) -> tuple:
     c.bn_eps, c.ln_eps, c.bn_momentum = 1e-5, 1e-5, 0.1
     prec = v.get("precision") or default_precision()
     if prec not in PRECISIONS:
-        raise ValueError(f"precision='{prec}' (known: bf16, fp32)")
+        raise ValueError(f"precision='{prec}' (known: {', '.join(PRECISIONS)})")
     c.act_dtype = PRECISIONS[prec]
     c.features_only = int(bool(v.get("features_only", False)))
     c.recompute = int(bool(v.get("grad_checkpointing", False)))      # activation recompute (TinyVitBackbone.set_grad_checkpointing)
@@ -110,8 +110,9 @@ def _init_tensor(name: str, shape, g: torch.Generator) -> torch.Tensor:
     raise AssertionError(name)
 
 
-class TinyVitBackbone(FlatStore):
+class TinyVitBackbone(EncoderRuntime):
     """Owner of the flat parameter / buffer storage and of the HIP workspace (``self.backbone`` of the adapter)."""
+    _name, _switch, _gen_why = "TinyViT", "set_grad_checkpointing", "saved activations live in ONE workspace per backbone, so "
 
     def __init__(self, model_name: str, seed: Optional[int] = None, **overrides):
         super().__init__()
@@ -134,13 +135,8 @@ class TinyVitBackbone(FlatStore):
         self.drop_rates = slot_rates
         g = torch.Generator().manual_seed(torch.initial_seed() if seed is None else seed)
         self._register_table(lambda name, shape: _init_tensor(name, shape, g))
-        self._wcache = None
-        self._wcache_version = -1
-        self._ws: Dict[bool, torch.Tensor] = {}
-        self._last = None
-        self._gen = 0                    # generation of the training workspace contents (one per training forward)
-        self._grad_ready_hook = None     # set by optim.AdamW.overlap_allreduce: fn(lo, hi) over flat gradient floats
-        self.grad_checkpointing = bool(self.cfg.recompute)
+
+    grad_checkpointing = property(lambda self: bool(self.cfg.recompute))          # (timm's attribute)
 
     def set_grad_checkpointing(self, enable: bool = True):
         """timm's switch (``model.set_grad_checkpointing()``; the reference's ``adapter.backbone`` is the timm model): activation recompute of the
@@ -150,45 +146,22 @@ class TinyVitBackbone(FlatStore):
         gradients only to rounding: the attention backward sums them with float atomics, so they vary in their last bits between any two steps).  Unlike
         ``torch.utils.checkpoint``, whose recompute runs BatchNorm in train mode again and so updates the running statistics twice, the recompute
         reuses the forward's batch statistics: the running buffers are updated once per step.  Inference ignores the setting."""
-        enable = bool(enable)
-        if enable != bool(self.cfg.recompute):
-            self.cfg.recompute = int(enable)
-            self._ws.pop(True, None)          # laid out for the other plan: the next training forward sizes a new one
-        self.grad_checkpointing = enable
+        self.set_recompute(enable)
         return self
 
     # -- HIP calls ------------------------------------------------------------------------------------------
-    def _ensure_weights(self):
-        lib = L.lib()
-        if self._wcache is None:
-            nbytes = lib.gg_tinyvit_wcache_bytes(C.byref(self.cfg))
-            self._wcache = torch.zeros(nbytes, dtype=torch.uint8, device=self._flat.device)
-            self._wcache_version = -1
-            self._dirty_all = True
-        ver = self._param_version()
-        if self._wcache_version != ver:
-            # full rebuild unless the only writers since the last sync were masked raw-pointer writers (the fused optimizer) AND torch's own
-            # version counters did not move (no load_state_dict / copy_ / torch.optim step in between)
-            only = None if (getattr(self, "_dirty_all", True) or getattr(self, "_synced_ver", None) != ver) else getattr(self, "_dirty_only", None)
-            if only is None:
-                L.check(lib.gg_tinyvit_refresh_weights(C.byref(self.cfg), L.ptr(self._flat, torch.float32, "params"),
-                                                       L.ptr(self._wcache), L.stream()), "gg_tinyvit_refresh_weights")
-            else:
-                L.check(lib.gg_tinyvit_refresh_weights_masked(C.byref(self.cfg), L.ptr(self._flat, torch.float32, "params"),
-                                                              L.ptr(self._wcache), only, L.stream()), "gg_tinyvit_refresh_weights_masked")
-            self._wcache_version = self._synced_ver = ver
-            self._dirty_all, self._dirty_only = False, None
+    def _wcache_bytes(self) -> int:
+        return L.lib().gg_tinyvit_wcache_bytes(C.byref(self.cfg))
 
-    def _workspace(self, batch: int, training: bool, mask=None) -> torch.Tensor:
-        need = L.lib().gg_tinyvit_workspace_bytes_masked(C.byref(self.cfg), batch, int(training), mask)
-        if need < 0:
-            raise L.GgError(L.lib().gg_last_error().decode())
-        ws = self._ws.get(training)
-        if ws is None or ws.numel() < need or ws.device != self._flat.device:
-            self._ws[training] = None
-            ws = torch.empty(need, dtype=torch.uint8, device=self._flat.device)
-            self._ws[training] = ws
-        return ws
+    def _refresh(self, only):
+        a = (C.byref(self.cfg), L.ptr(self._flat, torch.float32, "params"), L.ptr(self._wcache))
+        if only is None:
+            L.check(L.lib().gg_tinyvit_refresh_weights(*a, L.stream()), "gg_tinyvit_refresh_weights")
+        else:
+            L.check(L.lib().gg_tinyvit_refresh_weights_masked(*a, only, L.stream()), "gg_tinyvit_refresh_weights_masked")
+
+    def _workspace_bytes(self, batch: int, training: bool, mask) -> int:
+        return L.lib().gg_tinyvit_workspace_bytes_masked(C.byref(self.cfg), batch, int(training), mask)
 
     def make_drop_scales(self, batch: int, generator: Optional[torch.Generator] = None) -> Optional[torch.Tensor]:
         """timm DropPath (scale_by_keep): per-sample Bernoulli(1-p)/(1-p), one row per slot, drawn by ``gg_drop_path_scales`` (a counter-based
@@ -243,25 +216,17 @@ class TinyVitBackbone(FlatStore):
             raise L.GgError("TinyViTAdapter parameters are on the CPU; call .to('cuda') -- there is no CPU fallback")
         x = x.to(device=self._flat.device, dtype=torch.float32).contiguous()
         B = x.shape[0]
-        self._ensure_weights()
-        mask = self.trainable_mask() if training else None      # the workspace keeps no activation that only a frozen weight's gradient would read
-        ws = self._workspace(B, training, mask)
+        mask, ws = self._prepare(B, training)
         out = torch.empty((B, self.num_features), dtype=torch.float32, device=x.device)
         if drop_scales is not None:
             assert drop_scales.shape == (self.num_drop_slots, B) and drop_scales.dtype == torch.float32
-        self._fwd_mask = mask
-        if training:
-            self._train_mask = mask          # (an eval forward in between does not change what the training workspace was laid out for)
         L.check(L.lib().gg_tinyvit_forward(C.byref(self.cfg), B, int(training), L.ptr(self._flat), L.ptr(self._flat_buf),
                                            L.ptr(self._counters), L.ptr(self._wcache), L.ptr(x), L.ptr(drop_scales), L.ptr(ws),
                                            L.ptr(out), mask, L.stream()),
                 "gg_tinyvit_forward")
         if training:
             self._counters += 1          # num_batches_tracked (int64 bookkeeping)
-            self._flat_buf_dirty = True
-            self._gen += 1
-            self._last = (B, drop_scales, self._gen)
-            self._last_recompute = self.cfg.recompute
+            self._record_forward(B, mask, drop_scales)
         return out
 
     def _stage_ranges(self):
@@ -280,30 +245,9 @@ class TinyVitBackbone(FlatStore):
         return self._stage_rng
 
     def backward_hip(self, d_out: torch.Tensor, gen: Optional[int] = None):
-        if self._last is None:
-            raise L.GgError("TinyViT backward without a training forward")
-        B, drop, last_gen = self._last
-        if gen is not None and gen != last_gen:
-            raise L.GgError(f"TinyViT backward for training forward #{gen}, but the workspace now holds the activations of forward "
-                            f"#{last_gen}: saved activations live in ONE workspace per backbone, so every training forward must be "
-                            "followed by its backward before the next training forward")
-        if d_out.shape[0] != B:
-            raise L.GgError(f"TinyViT backward: gradient batch {d_out.shape[0]} != forward batch {B}")
-        if self.cfg.recompute != getattr(self, "_last_recompute", self.cfg.recompute):
-            raise L.GgError("set_grad_checkpointing changed between the training forward and its backward: the forward laid out its workspace for "
-                            f"recompute={self._last_recompute} (the checkpointed layout keeps other tensors); run the forward again")
-        ws = self._ws.get(True)
-        if ws is None:
-            raise L.GgError("TinyViT backward: the training workspace was released (set_grad_checkpointing changed since the training forward); "
-                            "run the forward again")
+        B, drop, ws = self._pending(gen, d_out.shape[0])
         fg = self.attach_grads()
-        mask = self.trainable_mask()
-        if getattr(self, "_train_mask", None) is not None and mask != self._train_mask:
-            # the workspace was laid out (and activations were dropped) for the forward's mask: backward must see the same one
-            changed = [t["name"] for t, a, b in zip([t for t in self.table], mask, self._train_mask) if bool(a) != bool(b)]
-            raise L.GgError("requires_grad changed between forward and backward for " + ", ".join(changed[:4]) +
-                            " ...: the training forward laid out its workspace for the mask it saw (activations only a frozen weight's gradient "
-                            "needs are not kept); run the forward again")
+        mask = self._same_mask()
         hook = self._grad_ready_hook
         cb = L.STAGE_DONE_FN(0)
         failed = []
@@ -331,26 +275,16 @@ class TinyVitBackbone(FlatStore):
     def activation(self, name: str, batch: int) -> torch.Tensor:
         """Raw bytes of a saved activation of the last training forward (parity tests)."""
         off, nbytes = C.c_int64(), C.c_int64()
-        L.check(L.lib().gg_tinyvit_activation_info_masked(C.byref(self.cfg), batch, name.encode(), getattr(self, "_train_mask", None), C.byref(off),
+        L.check(L.lib().gg_tinyvit_activation_info_masked(C.byref(self.cfg), batch, name.encode(), self._train_mask, C.byref(off),
                                                           C.byref(nbytes)), "gg_tinyvit_activation_info")
         return self._ws[True][off.value:off.value + nbytes.value]
 
     def forward(self, x):
-        need = torch.is_grad_enabled() and any(p.requires_grad for p in self._params.values())
-        return _EncoderFn.apply(self, x, _anchor(self) if need else _anchor(self).detach())
+        return _EncoderFn.apply(self, x, self._anchor() if self.wants_grad() else self._anchor().detach())
 
 
-def _anchor(bb: TinyVitBackbone) -> torch.Tensor:
-    a = getattr(bb, "_anchor_t", None)
-    if a is None or a.device != bb._flat.device:
-        a = torch.zeros((), device=bb._flat.device, requires_grad=True)
-        bb._anchor_t = a
-    return a
-
-
-class _EncoderFn(torch.autograd.Function):
-    """Whole-encoder autograd node.  Parameter gradients are accumulated straight into the flat gradient buffer
-    (``p.grad`` views), not returned through autograd; the zero-dim ``anchor`` input only keeps the node alive."""
+class _EncoderFn(EncoderNode):
+    """Whole-encoder autograd node (``EncoderRuntime._anchor``)."""
 
     @staticmethod
     def forward(ctx, bb: TinyVitBackbone, x: torch.Tensor, anchor: torch.Tensor):
@@ -358,18 +292,8 @@ class _EncoderFn(torch.autograd.Function):
         training = bb.training
         drop = bb.make_drop_scales(x.shape[0]) if training else None
         out = bb.forward_hip(x, training, drop)
-        ctx.bb = bb
-        ctx.valid = training and need_grad
-        ctx.gen = bb._gen
+        bb._enter_node(ctx, training and need_grad)
         return out
-
-    @staticmethod
-    def backward(ctx, d_out):
-        if not ctx.valid:
-            raise L.GgError("backward through a TinyViT forward that ran in eval mode (running-stat BatchNorm keeps no "
-                            "activations); call .train() before the forward pass")
-        ctx.bb.backward_hip(d_out, ctx.gen)
-        return None, None, torch.zeros((), device=d_out.device)
 
 
 class TinyViTAdapter(nn.Module):

@@ -23,7 +23,7 @@ import torch
 from torch import Tensor, nn
 
 from .. import _lib as L
-from ..models.flat import FlatStore
+from ..models.flat import EncoderNode, EncoderRuntime
 
 CLIP_CONFIGS = {
     "openai/clip-vit-base-patch32": dict(hidden_size=768, intermediate_size=3072, num_layers=12, num_heads=12, image_size=224, patch_size=32),
@@ -43,10 +43,13 @@ def _precision_code(precision: Optional[str]) -> int:
     return PRECISIONS[p]
 
 
-class _VisionModel(FlatStore):
-    """``vision_model`` of the HF module tree: owner of the flat storage.  Its children (``embeddings``, ``pre_layrnorm``,
+class _VisionModel(EncoderRuntime):
+    """``vision_model`` of the HF module tree: owner of the flat storage and of the HIP workspace.  Its children (``embeddings``, ``pre_layrnorm``,
     ``encoder.layers.N....``, ``post_layernorm``) are rebuilt from the tensor names, so ``encoder.layers[i].parameters()`` is what
     ``SuperGuessr._freeze_params`` expects."""
+    _name, _switch = "CLIP", "gradient_checkpointing"
+    _mask_changed = "requires_grad changed between the CLIP forward and its backward; run the forward again"
+    _toggled_gen = None               # generation of a training forward that a gradient_checkpointing toggle made the runtime forget
 
     def __init__(self, cfg: L.ClipCfg, seed: int):
         super().__init__()
@@ -75,11 +78,57 @@ class _VisionModel(FlatStore):
                 return torch.zeros(shape)
             return torch.randn(shape, generator=g) * 0.02
         self._register_table(init)
-        self._wcache, self._wcache_version, self._ws = None, -1, {}
-        self._last = None
-        self._toggled_since_forward = False      # a gradient_checkpointing toggle released the workspace of a training forward (until the next one)
-        self._gen = 0
-        self._grad_ready_hook = None      # (optim.AdamW.overlap_allreduce sets it; the CLIP backward has no stage callback: buckets leave after it)
+
+    def _wcache_bytes(self) -> int:
+        return L.lib().gg_clip_wcache_bytes(C.byref(self.cfg))
+
+    def _refresh(self, only):             # (no masked refresh: the whole cache is rebuilt)
+        L.check(L.lib().gg_clip_refresh_weights(C.byref(self.cfg), L.ptr(self._flat), L.ptr(self._wcache), L.stream()), "gg_clip_refresh_weights")
+
+    def _workspace_bytes(self, batch: int, training: bool, mask) -> int:
+        return L.lib().gg_clip_workspace_bytes(C.byref(self.cfg), batch, int(training), mask)
+
+    def set_recompute(self, enable: bool) -> bool:
+        changed = super().set_recompute(enable)
+        if changed and self._last is not None:
+            self._last, self._toggled_gen = None, self._gen
+        return changed
+
+    def _pending(self, gen, batch=None):
+        if self._last is None and self._toggled_gen == self._gen:
+            raise L.GgError(f"gradient checkpointing was toggled since the training forward (now recompute={self.cfg.recompute}): its workspace was "
+                            "released, the other layout keeps other tensors; run the forward again")
+        return super()._pending(gen, batch)
+
+    def forward_hip(self, x: Tensor, training: bool, return_last_hidden: bool):
+        L.require_gpu()
+        if not self._flat.is_cuda:
+            raise L.GgError("CLIPVisionTower parameters are on the CPU; call .to('cuda') -- there is no CPU fallback")
+        S = self.cfg.image_size
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != S or x.shape[3] != S:
+            raise L.GgError(f"CLIPVisionTower expects (B,3,{S},{S}) pixel_values, got {tuple(x.shape)}")
+        x = x.to(device=self._flat.device, dtype=torch.float32).contiguous()
+        B = x.shape[0]
+        mask, ws = self._prepare(B, training)
+        D, T = self.cfg.hidden_size, (S // self.cfg.patch_size) ** 2 + 1
+        out = torch.empty((B, D), dtype=torch.float32, device=x.device)
+        last = torch.empty((B, T, D), dtype=torch.float32, device=x.device) if return_last_hidden else None
+        L.check(L.lib().gg_clip_forward(C.byref(self.cfg), B, int(training), L.ptr(self._flat), L.ptr(self._wcache), L.ptr(x), L.ptr(ws), L.ptr(out),
+                                        L.ptr(last), mask, L.stream()), "gg_clip_forward")
+        if training:
+            self._record_forward(B, mask)
+        return out, last
+
+    def backward_hip(self, d_out: Optional[Tensor], d_last: Optional[Tensor], gen: int):
+        B, _, ws = self._pending(gen)
+        mask = self._same_mask()
+        fg = self.attach_grads()
+        f = lambda t: None if t is None else t.to(torch.float32).contiguous()
+        d_out, d_last = f(d_out), f(d_last)
+        L.check(L.lib().gg_clip_backward(C.byref(self.cfg), B, L.ptr(self._flat), L.ptr(self._wcache), L.ptr(ws), L.ptr(d_out), L.ptr(d_last),
+                                         L.ptr(fg), mask, L.stream()), "gg_clip_backward")
+        if self._grad_ready_hook is not None:          # (no stage callback in the CLIP backward: the buckets leave after it)
+            self._grad_ready_hook(0, self.param_floats)
 
 
 class CLIPVisionTower(nn.Module):
@@ -106,25 +155,16 @@ class CLIPVisionTower(nn.Module):
     def is_gradient_checkpointing(self) -> bool:
         return bool(self.cfg.recompute)
 
-    def _set_gradient_checkpointing(self, enable: bool):
-        vm = self.vision_model
-        if enable != bool(self.cfg.recompute):
-            if vm._last is not None:
-                vm._toggled_since_forward = True
-            self.cfg.recompute = int(enable)
-            vm._ws.pop(True, None)            # laid out for the other plan: the next training forward sizes a new one
-            vm._last = None
-
     def gradient_checkpointing_enable(self, gradient_checkpointing_kwargs=None):
         """transformers' switch (``model.gradient_checkpointing_enable()``): activation recompute of the training step (``GgClipCfg.recompute``,
         include/gg.h).  The workspace keeps the input of every encoder layer from the first trainable one up; the backward re-forms a layer's
         other tensors (LayerNorm outputs, qkv, attention output, the MLP activations) right before its backward.  ``pooled_mean``,
         ``last_hidden_state`` and every gradient are bit-identical to the step without recompute.  ``gradient_checkpointing_kwargs`` (HF's
         ``use_reentrant``) has no counterpart here and is ignored.  Inference ignores the setting."""
-        self._set_gradient_checkpointing(True)
+        self.vision_model.set_recompute(True)
 
     def gradient_checkpointing_disable(self):
-        self._set_gradient_checkpointing(False)
+        self.vision_model.set_recompute(False)
 
     # ---- weights ----------------------------------------------------------------------------------------------------------------------
     @property
@@ -132,7 +172,7 @@ class CLIPVisionTower(nn.Module):
         return self.vision_model
 
     def named_views(self) -> Dict[str, Tensor]:
-        return {n: p.data for n, p in self.vision_model._params.items()}
+        return {n: p.data for n, p in self.vision_model.named_parameters()}
 
     def load_hf_state_dict(self, sd: Dict[str, Tensor]):
         """HF ``CLIPVisionModel`` keys; a leading ``vision_model.`` (transformers 4.x nesting) is stripped.  Unknown keys (``position_ids``) are ignored."""
@@ -144,109 +184,33 @@ class CLIPVisionTower(nn.Module):
                     views[k].copy_(torch.as_tensor(v).to(views[k].device, torch.float32))
         self.vision_model.mark_params_dirty()
 
-    # ---- HIP calls --------------------------------------------------------------------------------------------------------------------
-    def _ensure_weights(self):
-        vm, lib = self.vision_model, L.lib()
-        if vm._wcache is None or vm._wcache.device != vm._flat.device:
-            vm._wcache = torch.zeros(lib.gg_clip_wcache_bytes(C.byref(self.cfg)), dtype=torch.uint8, device=vm._flat.device)
-            vm._wcache_version = -1
-        ver = vm._param_version()
-        if vm._wcache_version != ver:
-            L.check(lib.gg_clip_refresh_weights(C.byref(self.cfg), L.ptr(vm._flat), L.ptr(vm._wcache), L.stream()), "gg_clip_refresh_weights")
-            vm._wcache_version = ver
-
-    def _workspace(self, batch: int, training: bool, mask) -> Tensor:
-        vm = self.vision_model
-        need = L.lib().gg_clip_workspace_bytes(C.byref(self.cfg), batch, int(training), mask)
-        if need < 0:
-            raise L.GgError(L.lib().gg_last_error().decode())
-        ws = vm._ws.get(training)
-        if ws is None or ws.numel() < need or ws.device != vm._flat.device:
-            vm._ws[training] = None
-            ws = vm._ws[training] = torch.empty(need, dtype=torch.uint8, device=vm._flat.device)
-        return ws
-
-    def forward_hip(self, x: Tensor, training: bool, return_last_hidden: bool):
-        L.require_gpu()
-        vm = self.vision_model
-        if not vm._flat.is_cuda:
-            raise L.GgError("CLIPVisionTower parameters are on the CPU; call .to('cuda') -- there is no CPU fallback")
-        S = self.cfg.image_size
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != S or x.shape[3] != S:
-            raise L.GgError(f"CLIPVisionTower expects (B,3,{S},{S}) pixel_values, got {tuple(x.shape)}")
-        x = x.to(device=vm._flat.device, dtype=torch.float32).contiguous()
-        B = x.shape[0]
-        self._ensure_weights()
-        mask = vm.trainable_mask() if training else None
-        ws = self._workspace(B, training, mask)
-        D, T = self.cfg.hidden_size, self.num_tokens
-        out = torch.empty((B, D), dtype=torch.float32, device=x.device)
-        last = torch.empty((B, T, D), dtype=torch.float32, device=x.device) if return_last_hidden else None
-        L.check(L.lib().gg_clip_forward(C.byref(self.cfg), B, int(training), L.ptr(vm._flat), L.ptr(vm._wcache), L.ptr(x), L.ptr(ws), L.ptr(out),
-                                        L.ptr(last), mask, L.stream()), "gg_clip_forward")
-        if training:
-            vm._gen += 1
-            vm._last = (B, mask, vm._gen)
-            vm._toggled_since_forward = False
-        return out, last
+    def forward_hip(self, x: Tensor, training: bool, return_last_hidden: bool):          # (the HIP calls are the vision model's)
+        return self.vision_model.forward_hip(x, training, return_last_hidden)
 
     def backward_hip(self, d_out: Optional[Tensor], d_last: Optional[Tensor], gen: int):
-        vm = self.vision_model
-        if vm._last is None:
-            if vm._toggled_since_forward:
-                raise L.GgError(f"gradient checkpointing was toggled since the training forward (now recompute={self.cfg.recompute}): its workspace was "
-                                "released, the other layout keeps other tensors; run the forward again")
-            raise L.GgError("CLIP backward without a training forward")
-        B, mask, last_gen = vm._last
-        if gen != last_gen:
-            raise L.GgError(f"CLIP backward for training forward #{gen}, but the workspace now holds the activations of forward #{last_gen}: every "
-                            "training forward must be followed by its backward before the next training forward")
-        if vm.trainable_mask() != mask:
-            raise L.GgError("requires_grad changed between the CLIP forward and its backward; run the forward again")
-        fg = vm.attach_grads()
-        f = lambda t: None if t is None else t.to(torch.float32).contiguous()
-        d_out, d_last = f(d_out), f(d_last)
-        L.check(L.lib().gg_clip_backward(C.byref(self.cfg), B, L.ptr(vm._flat), L.ptr(vm._wcache), L.ptr(vm._ws[True]), L.ptr(d_out), L.ptr(d_last),
-                                         L.ptr(fg), mask, L.stream()), "gg_clip_backward")
-        hook = vm._grad_ready_hook
-        if hook is not None:
-            hook(0, vm.param_floats)
+        self.vision_model.backward_hip(d_out, d_last, gen)
 
     def forward(self, pixel_values: Tensor = None, return_last_hidden: bool = True):
         vm = self.vision_model
-        need = torch.is_grad_enabled() and any(p.requires_grad for p in vm._params.values())      # (no dropout / BatchNorm: train and eval compute the same)
+        need = vm.wants_grad()      # (no dropout / BatchNorm: train and eval compute the same)
         if need and self.precision == "fp16":
             raise L.GgError("CLIPVisionTower(precision='fp16') is inference-only: run under torch.no_grad() / freeze it, or train in fp32 / bf16")
         if not need:
-            out, last = self.forward_hip(pixel_values, False, return_last_hidden)
+            out, last = vm.forward_hip(pixel_values, False, return_last_hidden)
         else:
-            out, last = _ClipFn.apply(self, pixel_values, _anchor(vm), return_last_hidden)
+            out, last = _ClipFn.apply(vm, pixel_values, vm._anchor(), return_last_hidden)
         return SimpleNamespace(last_hidden_state=last, pooled_mean=out, pooler_output=out)
 
 
-def _anchor(vm: _VisionModel) -> Tensor:
-    a = getattr(vm, "_anchor_t", None)
-    if a is None or a.device != vm._flat.device:
-        a = vm._anchor_t = torch.zeros((), device=vm._flat.device, requires_grad=True)
-    return a
-
-
-class _ClipFn(torch.autograd.Function):
-    """Whole-tower autograd node (the counterpart of the TinyViT backbone's): parameter gradients are accumulated straight into the flat
-    gradient buffer the parameters' ``.grad`` views point into; the zero-dim ``anchor`` input only keeps the node alive."""
+class _ClipFn(EncoderNode):
+    """Whole-tower autograd node (the counterpart of the TinyViT backbone's; ``EncoderRuntime._anchor``)."""
 
     @staticmethod
-    def forward(ctx, tower: CLIPVisionTower, x: Tensor, anchor: Tensor, want_last: bool):
-        out, last = tower.forward_hip(x, True, want_last)
-        ctx.tower, ctx.gen = tower, tower.vision_model._gen
+    def forward(ctx, vm: _VisionModel, x: Tensor, anchor: Tensor, want_last: bool):
+        out, last = vm.forward_hip(x, True, want_last)
+        vm._enter_node(ctx)
         ctx.set_materialize_grads(False)          # an unused last_hidden_state must not cost a (B,T,D) zero gradient
         return out, last
-
-    @staticmethod
-    def backward(ctx, d_out, d_last):
-        ctx.tower.backward_hip(d_out, d_last, ctx.gen)
-        dev = (d_out if d_out is not None else d_last).device
-        return None, None, torch.zeros((), device=dev), None
 
 
 def clip_preprocess(images, size: int, device) -> Tensor:

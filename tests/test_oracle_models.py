@@ -1,9 +1,9 @@
-import pytest
 """Oracle self-checks: CLIP restatement pinned to transformers; TinyViT restatement (parity
 UNPINNED, timm absent) checked by invariants from SURVEY.md App. A.  CPU only."""
 import os
 
 import numpy as np
+import pytest
 import torch
 
 from oracle import clip_ref as C
