@@ -1114,6 +1114,7 @@ __global__ __launch_bounds__(NT ? (NT < 4 ? 256 : 64 * NT) : 1024) void flash_bw
 }
 
 #include "attention_split.h"
+#include "attention_split64.h"
 
 __global__ void flash_dbias_final_kernel(const float* __restrict__ rows, int nrows, int W, float* __restrict__ dbias) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1125,7 +1126,12 @@ __global__ void flash_dbias_final_kernel(const float* __restrict__ rows, int nro
 
 int flash_fill(FlashParams& p, const GgAttnArgs* a, int dtype, const char* who) {
     GG_CHECK(a && a->qkv, "%s: null qkv", who);
-    GG_CHECK(dtype == 0 || dtype == 1 || dtype == 2, "%s: dtype must be 0 (bf16), 1 (f32) or 2 (fp16, forward only)", who);
+    GG_CHECK(dtype >= 0 && dtype <= 3, "%s: dtype must be 0 (bf16), 1 (f32), 2 (fp16, forward only) or 3 (f32 storage, split-bf16 products)", who);
+    // dtype 3 is one pair of kernels (attention_split64.h): what they do not implement is refused here, before anything is launched
+    GG_CHECK(dtype != 3 || (a->head_dim == 64 && a->window_size == 0 && !a->bias_table && !a->dbias),
+             "%s: dtype 3 (split-bf16 products) is head dim 64 without windows or bias (got head_dim %d, window_size %d)", who, a->head_dim, a->window_size);
+    GG_CHECK(dtype != 3 || (int64_t)a->tokens_per_window * std::max(std::max(a->ld, a->ldo), a->lddo) * 4 < ((int64_t)1 << 31),
+             "%s: dtype 3: one image's rows exceed the 2 GiB descriptor range", who);
     GG_CHECK(a->head_dim == 32 || a->head_dim == 64, "%s: head_dim must be 32 or 64 (got %d)", who, a->head_dim);
     GG_CHECK(a->tokens_per_window > 0 && a->num_windows > 0 && a->num_heads > 0, "%s: bad window/head/token count", who);
     GG_CHECK((a->ld & 3) == 0 && (a->q_off & 3) == 0 && (a->k_off & 3) == 0 && (a->v_off & 3) == 0 && (a->head_stride & 3) == 0,
@@ -1207,6 +1213,13 @@ extern "C" int gg_attention_flash_fwd(const GgAttnArgs* a, int dtype, void* stre
     // fp32 storage, head dim 32, windows of 4 / 9 / 13 tiles (7 x 7, 12 x 12, 14 x 14): the products run as split-bf16 MFMAs (attention_split.h).  (The same
     // kernel instantiated for bf16 storage -- one plane -- measured 403 us per 14 x 14 layer with a wave per strip and 497 us with two strips per wave, against
     // 301 us of attention.hip's attn_fwd_kernel: the bf16 forward stays there.)
+    if (dtype == 3) {
+        const size_t lds = sp64_lds(3, false);
+        GG_PROF(GG_CAT_ATTN, 4.0 * a->num_windows * a->num_heads * (double)p.N * p.N * a->head_dim, 16.0 * a->num_windows * a->num_heads * (double)p.N * a->head_dim, stream);
+        hipLaunchKernelGGL((flash64_split_q_kernel<3, false>), dim3((unsigned)(a->num_windows * a->num_heads * p.ntile)), dim3(256), lds, (hipStream_t)stream, p);
+        GG_LAUNCH_CHECK();
+        return 0;
+    }
     static const bool nosplit = gg_dev_env("GG_ATTN_NO_SPLIT") != nullptr;
     const int nt16 = p.npad / 16;
     if (dtype == 1 && a->head_dim == 32 && !nosplit && (nt16 == 4 || nt16 == 9 || nt16 == 13)) {
@@ -1265,6 +1278,15 @@ int gg_attention_flash_bwd_impl(const GgAttnArgs* a, int dtype, int forward_roun
     GG_CHECK(a->dout && a->dqkv && (a->lddo & 3) == 0 && ((uintptr_t)a->dout & 15) == 0 && ((uintptr_t)a->dqkv & 15) == 0,
              "gg_attention_flash_bwd: bad dout/dqkv");
     GG_CHECK(a->lse && a->out && (a->ldo & 3) == 0, "gg_attention_flash_bwd: needs the forward's lse and out");
+    if (dtype == 3) {
+        // two passes at every length (dQ; dK, dV), each recomputing P from lse: no dS hand-off (ds_scratch is not read), no atomics
+        GG_PROF(GG_CAT_ATTN, 10.0 * a->num_windows * a->num_heads * (double)p.N * p.N * a->head_dim, 32.0 * a->num_windows * a->num_heads * (double)p.N * a->head_dim, stream);
+        const dim3 g3((unsigned)(a->num_windows * a->num_heads * p.ntile));
+        hipLaunchKernelGGL((flash64_split_q_kernel<3, true>), g3, dim3(256), sp64_lds(3, false), (hipStream_t)stream, p);
+        hipLaunchKernelGGL((flash64_split_dkv_kernel<3>), g3, dim3(256), sp64_lds(3, true), (hipStream_t)stream, p);
+        GG_LAUNCH_CHECK();
+        return 0;
+    }
     // resident form also for single-tile windows (7 x 7) when a dS scratch is there: the dQ phase then runs inside the dK/dV kernel
     const bool res = flash_resident(p, a->head_dim, p.dbias != nullptr) || (p.ds_scratch != nullptr && p.ntile == 1);
     const dim3 grid((unsigned)(a->num_windows * a->num_heads * (res ? 1 : p.ntile))), block(res ? 64 * std::min(16, p.npad / 16) : 256);

@@ -3,9 +3,13 @@
 // for SuperGuessr with a CLIP base (models/super_guessr.py:134-150,323-325: the last encoder layer is fine-tuned when the pretrained
 // head exists, every layer otherwise; main_coordinator_idun_s3.py:183-203 builds that model for training).
 //
-// A static schedule of libgg launches on one stream, in one of three arithmetic modes (GgClipCfg.act_dtype):
+// A static schedule of libgg launches on one stream, in one of four arithmetic modes (GgClipCfg.act_dtype):
 //   1  fp32 -- the reference's precision: f32 activations, v_mfma_f32_16x16x4_f32 GEMMs (gg_gemm_nt_f32 / gg_gemm_tn_f32), f32 LayerNorm, f32
 //      online-softmax attention (head dim 64);
+//   3  fp32_split -- mode 1's storage and workspace; every GEMM as an f32-accurate split product on the bf16 MFMA (x = x1 + x2 + x3 in bf16, six
+//      v_mfma_f32_16x16x32_bf16 per f32 product): forward and data gradients through gg_gemm_nt_split3_af32 against cached weight planes, weight
+//      gradients through gg_gemm_tn_split3, attention through the split kernels of attention_split64.h (gg_attention_flash_fwd / _bwd, dtype 3);
+//      LayerNorm, token assembly, column sums and pooling are mode 1's f32 kernels;
 //   0  bf16 -- bf16 activations / MFMA operands, f32 accumulation, f32 statistics;
 //   2  fp16 -- the same with fp16 storage / v_mfma_f32_16x16x32_f16 (BASELINE config c4 names fp16), inference only.
 // Patch embedding is a pure GEMM (stride == kernel); q/k/v projections are one [3D, D] GEMM; QuickGELU rides on fc1's epilogue (with the
@@ -30,16 +34,17 @@ struct TInfo { std::string name; int64_t offset, numel; int ndim; int64_t shape[
 struct LayerP {
     int q_w, q_b, k_w, k_b, v_w, v_b, o_w, o_b, ln1_g, ln1_b, fc1_w, fc1_b, fc2_w, fc2_b, ln2_g, ln2_b;      // tensor ids
     int64_t wqkv, bqkv, wqkvT, wo, woT, w1, w1T, w2, w2T;                                                     // weight-cache offsets
+    int64_t wqkv3 = -1, wqkvT3 = -1, wo3 = -1, woT3 = -1, w13 = -1, w1T3 = -1, w23 = -1, w2T3 = -1;           // fp32_split: bf16 planes [3][N][K] of the same matrices
 };
 struct CModel {
     GgClipCfg cfg;
     std::vector<TInfo> t;
     int64_t floats = 0, wc_bytes = 0;
     int cls, patch_w, pos, pre_g, pre_b, post_g, post_b;
-    int64_t wpatch;
+    int64_t wpatch, wpatch3 = -1;
     std::vector<LayerP> layers;
     int T, G, Kpatch, Kraw;
-    bool f32, f16; int es;             // activation / cached-weight element size: 4 (fp32 mode) or 2 (bf16 / fp16 modes)
+    bool f32, f16, split; int es;      // f32: f32 storage (fp32 and fp32_split modes); split: fp32_split; activation / cached-weight element size: 4 or 2 (bf16 / fp16 modes)
 };
 static int addt(CModel& m, const std::string& n, std::initializer_list<int64_t> shape) {
     TInfo t; t.name = n; t.ndim = (int)shape.size(); t.numel = 1;
@@ -55,8 +60,8 @@ static int64_t wca(CModel& m, int64_t bytes) { int64_t o = m.wc_bytes; m.wc_byte
 static int build(const GgClipCfg* c, CModel& m) {
     GG_CHECK(c, "clip: null config");
     m.cfg = *c;
-    GG_CHECK(c->act_dtype >= 0 && c->act_dtype <= 2, "clip: act_dtype must be 0 (bf16), 1 (fp32) or 2 (fp16), got %d", c->act_dtype);
-    m.f32 = c->act_dtype == 1; m.f16 = c->act_dtype == 2; m.es = m.f32 ? 4 : 2;
+    GG_CHECK(c->act_dtype >= 0 && c->act_dtype <= 3, "clip: act_dtype must be 0 (bf16), 1 (fp32), 2 (fp16) or 3 (fp32_split), got %d", c->act_dtype);
+    m.split = c->act_dtype == 3; m.f32 = c->act_dtype == 1 || m.split; m.f16 = c->act_dtype == 2; m.es = m.f32 ? 4 : 2;
     const int D = c->hidden_size, I = c->intermediate_size, P = c->patch_size;
     GG_CHECK(D > 0 && D % 64 == 0 && D <= 1024 && c->num_heads > 0 && D / c->num_heads == 64, "clip: head_dim must be 64 and hidden <= 1024 (hidden %d, heads %d)", D, c->num_heads);
     GG_CHECK(P > 0 && c->image_size % P == 0 && I % 8 == 0 && c->num_layers > 0, "clip: bad patch/image/intermediate size or layer count");
@@ -68,6 +73,8 @@ static int build(const GgClipCfg* c, CModel& m) {
     m.pos = addt(m, "embeddings.position_embedding.weight", {m.T, D});
     m.pre_g = addt(m, "pre_layrnorm.weight", {D}); m.pre_b = addt(m, "pre_layrnorm.bias", {D});
     m.wpatch = wca(m, (int64_t)D * m.Kpatch * m.es);
+    auto planes = [&](int64_t n) { return m.split ? wca(m, 3 * n * 2) : (int64_t)-1; };      // fp32_split: bf16 planes [3][n] of a cached matrix
+    m.wpatch3 = planes((int64_t)D * m.Kpatch);                                              // (no W^T of the patch embedding in either mode: the pixels take no gradient)
     m.layers.resize(c->num_layers);
     for (int i = 0; i < c->num_layers; ++i) {
         LayerP& l = m.layers[i];
@@ -86,6 +93,8 @@ static int build(const GgClipCfg* c, CModel& m) {
         l.wo = wca(m, (int64_t)D * D * m.es); l.woT = wca(m, (int64_t)D * D * m.es);
         l.w1 = wca(m, (int64_t)I * D * m.es); l.w1T = wca(m, (int64_t)I * D * m.es);
         l.w2 = wca(m, (int64_t)D * I * m.es); l.w2T = wca(m, (int64_t)D * I * m.es);
+        l.wqkv3 = planes((int64_t)3 * D * D); l.wqkvT3 = planes((int64_t)3 * D * D); l.wo3 = planes((int64_t)D * D); l.woT3 = planes((int64_t)D * D);
+        l.w13 = planes((int64_t)I * D); l.w1T3 = planes((int64_t)I * D); l.w23 = planes((int64_t)D * I); l.w2T3 = planes((int64_t)D * I);
     }
     m.post_g = addt(m, "post_layernorm.weight", {D}); m.post_b = addt(m, "post_layernorm.bias", {D});
     return 0;
@@ -310,7 +319,9 @@ static void plan(const CModel& m, int B, const Train& tr, bool training, CPlan& 
         }
         L.g_x0 = al(M * D * es); L.g_x1 = al(M * D * es); L.g_a = al(M * D * es); L.g_qkv = al(M * 3 * D * es); L.g_o = al(M * D * es);
         L.g_h = al(M * I * es);
-        auto splits = [&](int64_t Mm, int N, int K) { return (int64_t)(m.f32 ? gg_gemm_tn_f32_splits((int)Mm, N, K) : gg_gemm_tn_splits((int)Mm, N, K)) * N * K; };
+        auto splits = [&](int64_t Mm, int N, int K) {
+            return (int64_t)(m.split ? gg_gemm_tn_split3_splits((int)Mm, N, K) : m.f32 ? gg_gemm_tn_f32_splits((int)Mm, N, K) : gg_gemm_tn_splits((int)Mm, N, K)) * N * K;
+        };
         int64_t sk = std::max(std::max(splits(M, D, I), splits(M, I, D)), splits(M, D, D));
         if (tr.embed) sk = std::max(sk, splits(Mp, D, m.Kpatch));
         L.splitk = al(sk * 4);
@@ -321,7 +332,8 @@ static void plan(const CModel& m, int B, const Train& tr, bool training, CPlan& 
         // 50-token towers run the single-pass kernel --, and only while it stays at most 4 GB and 1/8 of the workspace planned so far
         const int64_t dsb = gg_attention_flash_ds_scratch_floats(B, m.cfg.num_heads, m.T) * 4;
         static const bool ds_off = gg_dev_env("GG_ATTN_NO_DS_SCRATCH") != nullptr;
-        const bool ds = ds_force >= 0 ? ds_force != 0
+        // (the fp32_split mode's attention backward recomputes P in both passes: no hand-off at any length)
+        const bool ds = m.split ? false : ds_force >= 0 ? ds_force != 0
                                       : !ds_off && !gg_attention_flash_single_pass(m.T, D / m.cfg.num_heads, 0, 0) && dsb <= ((int64_t)4 << 30) && dsb <= off / 8;
         if (ds) L.attn_ds = al(dsb);
     }
@@ -338,13 +350,31 @@ struct Exec {
     void* A(int64_t o) const { return ws + o; }
     float* F(int64_t o) const { return reinterpret_cast<float*>(ws + o); }
     const void* W(int64_t o) const { return wc + o; }
+    const void* W(int64_t o, int64_t o3) const { return wc + (m->split ? o3 : o); }      // a GEMM's weight operand: the cached matrix, or its bf16 planes (fp32_split)
     int gemm(const void* Am, int64_t lda, const void* Bm, int64_t ldb, void* C, int64_t ldc, int64_t Mm, int N, int K, const float* bias, int act = 0,
              void* preact = nullptr, const void* residual = nullptr, const void* dact_preact = nullptr, int dact = 0) const {
         GgGemmArgs g;
         memset(&g, 0, sizeof(g));
         g.A = Am; g.lda = lda; g.B = Bm; g.ldb = ldb; g.C = C; g.ldc = ldc; g.M = (int)Mm; g.N = N; g.K = K;
         g.bias = bias; g.act = act; g.preact = preact; g.residual = residual; g.ldr = ldc; g.dact_preact = dact_preact; g.dact = dact;
+        if (m->split) {      // Bm: planes [3][N][ldb]
+            GgSplit3Args s;
+            memset(&s, 0, sizeof(s));
+            s.b_planes = Bm; s.ldb = ldb; s.M = (int)Mm; s.N = N; s.K = K; s.C = (float*)C; s.ldc = ldc; s.bias = bias; s.act = act; s.preact = (float*)preact;
+            s.residual = (const float*)residual; s.ldr = ldc; s.dact_preact = (const float*)dact_preact; s.dact = dact;
+            return gg_gemm_nt_split3_af32(&s, (const float*)Am, lda, 0, st);
+        }
         return m->f32 ? gg_gemm_nt_f32(&g, st) : (m->f16 ? gg_gemm_nt_f16(&g, st) : gg_gemm_nt(&g, st));
+    }
+    // partials[splits][N][K] of dY^T . X in the mode's weight-gradient form
+    int tn(const void* dY, int64_t ldy, const void* X, int64_t ldx, int64_t M, int N, int K, int* splits) const {
+        if (m->split) {
+            *splits = gg_gemm_tn_split3_splits((int)M, N, K);
+            return gg_gemm_tn_split3((const float*)dY, ldy, (const float*)X, ldx, (int)M, N, K, nullptr, 0, F(L->splitk), *splits, st);
+        }
+        *splits = m->f32 ? gg_gemm_tn_f32_splits((int)M, N, K) : gg_gemm_tn_splits((int)M, N, K);
+        if (m->f32) return gg_gemm_tn_f32(dY, ldy, X, ldx, (int)M, N, K, nullptr, 0, F(L->splitk), *splits, st);
+        return gg_gemm_tn(dY, ldy, X, ldx, (int)M, N, K, nullptr, 0, F(L->splitk), *splits, st);
     }
     int ln_fwd(const void* x, int tg, int tb, int64_t M, void* out, float* mean, float* rstd) const {
         if (m->f16) return gg_layernorm_fwd_f16(x, P(tg), P(tb), M, m->cfg.hidden_size, m->cfg.ln_eps, out, st);
@@ -361,9 +391,8 @@ struct Exec {
     // dW[N,K] += dY[M,N]^T . X[M,K]
     int wgrad(int tw, const void* dY, int64_t ldy, const void* X, int64_t ldx, int64_t M, int N, int K) const {
         if (!tr(tw)) return 0;
-        const int sp = m->f32 ? gg_gemm_tn_f32_splits((int)M, N, K) : gg_gemm_tn_splits((int)M, N, K);
-        if (m->f32) GG_TRY(gg_gemm_tn_f32(dY, ldy, X, ldx, (int)M, N, K, nullptr, 0, F(L->splitk), sp, st));
-        else GG_TRY(gg_gemm_tn(dY, ldy, X, ldx, (int)M, N, K, nullptr, 0, F(L->splitk), sp, st));
+        int sp;
+        GG_TRY(tn(dY, ldy, X, ldx, M, N, K, &sp));
         return gg_splitk_reduce(F(L->splitk), Gd(tw), (int64_t)N * K, sp, 1, 1.0f, st);
     }
     int bgrad(int tb, const void* dY, int64_t ld, int64_t M, int N) const {
@@ -387,7 +416,7 @@ template <typename T> static int embed_fwd(const Exec& e, const float* x, void* 
     if (pvec) hipLaunchKernelGGL((patchify_kernel<T, true>), dim3(grid1d(Mp * (m.Kpatch / 8))), dim3(256), 0, e.st, x, (T*)e.A(L.col), B, m.cfg.image_size, m.cfg.patch_size, m.G, m.Kpatch);
     else hipLaunchKernelGGL((patchify_kernel<T, false>), dim3(grid1d(Mp * (m.Kpatch / 8))), dim3(256), 0, e.st, x, (T*)e.A(L.col), B, m.cfg.image_size, m.cfg.patch_size, m.G, m.Kpatch);
     GG_LAUNCH_CHECK();
-    GG_TRY(e.gemm(e.A(L.col), m.Kpatch, e.W(m.wpatch), m.Kpatch, e.A(L.patches), D, Mp, D, m.Kpatch, nullptr));
+    GG_TRY(e.gemm(e.A(L.col), m.Kpatch, e.W(m.wpatch, m.wpatch3), m.Kpatch, e.A(L.patches), D, Mp, D, m.Kpatch, nullptr));
     hipLaunchKernelGGL(assemble_tokens_kernel<T>, dim3(grid1d(M * D / 4)), dim3(256), 0, e.st, (const T*)e.A(L.patches), e.P(m.cls), e.P(m.pos), (T*)tok_out,
                        B, m.T, D);
     GG_LAUNCH_CHECK();
@@ -406,17 +435,18 @@ static int layer_fwd(const Exec& e, int i, int64_t cur, int64_t next, bool sv) {
     const int64_t A1 = sv ? a.a1 : L.s_a, QKV = sv ? a.qkv : L.s_qkv, O = sv ? a.o : L.s_o, XMID = sv ? a.xmid : cur, A2 = sv ? a.a2 : L.s_a,
                   H = sv ? a.h : L.s_h;
     GG_TRY(e.ln_fwd(e.A(cur), l.ln1_g, l.ln1_b, M, e.A(A1), sv ? e.F(a.mean1) : nullptr, sv ? e.F(a.rstd1) : nullptr));
-    GG_TRY(e.gemm(e.A(A1), D, e.W(l.wqkv), D, e.A(QKV), 3 * D, M, 3 * D, D, (const float*)e.W(l.bqkv)));
+    GG_TRY(e.gemm(e.A(A1), D, e.W(l.wqkv, l.wqkv3), D, e.A(QKV), 3 * D, M, 3 * D, D, (const float*)e.W(l.bqkv)));
     GgAttnArgs at;
     e.attn_args(at, e.A(QKV), e.A(O), sv ? e.F(a.lse) : nullptr);
-    if (m.f16) GG_TRY(gg_attention_fwd_f16(&at, e.st));      // fp16 MFMA for towers of at most 256 tokens (ViT-B/32: 50); beyond: fp16 storage, f32 arithmetic
+    if (m.split) GG_TRY(gg_attention_flash_fwd(&at, 3, e.st));      // split products at every token count
+    else if (m.f16) GG_TRY(gg_attention_fwd_f16(&at, e.st));      // fp16 MFMA for towers of at most 256 tokens (ViT-B/32: 50); beyond: fp16 storage, f32 arithmetic
     else if (m.f32 || sv || T > 256) GG_TRY(gg_attention_flash_fwd(&at, m.f32 ? 1 : 0, e.st));
     else GG_TRY(gg_attention_fwd(&at, e.st));
     // x_mid = x + out_proj(o)   (in place when nothing is kept: each element is read then written by the same lane)
-    GG_TRY(e.gemm(e.A(O), D, e.W(l.wo), D, e.A(XMID), D, M, D, D, e.P(l.o_b), 0, nullptr, e.A(cur)));
+    GG_TRY(e.gemm(e.A(O), D, e.W(l.wo, l.wo3), D, e.A(XMID), D, M, D, D, e.P(l.o_b), 0, nullptr, e.A(cur)));
     GG_TRY(e.ln_fwd(e.A(XMID), l.ln2_g, l.ln2_b, M, e.A(A2), sv ? e.F(a.mean2) : nullptr, sv ? e.F(a.rstd2) : nullptr));
-    GG_TRY(e.gemm(e.A(A2), D, e.W(l.w1), D, e.A(H), I, M, I, D, e.P(l.fc1_b), GG_ACT_CODE_QUICK_GELU, sv ? e.A(a.pre) : nullptr));
-    if (next >= 0) GG_TRY(e.gemm(e.A(H), I, e.W(l.w2), I, e.A(next), D, M, D, I, e.P(l.fc2_b), 0, nullptr, e.A(XMID)));
+    GG_TRY(e.gemm(e.A(A2), D, e.W(l.w1, l.w13), D, e.A(H), I, M, I, D, e.P(l.fc1_b), GG_ACT_CODE_QUICK_GELU, sv ? e.A(a.pre) : nullptr));
+    if (next >= 0) GG_TRY(e.gemm(e.A(H), I, e.W(l.w2, l.w23), I, e.A(next), D, M, D, I, e.P(l.fc2_b), 0, nullptr, e.A(XMID)));
     return 0;
 }
 
@@ -489,7 +519,11 @@ extern "C" int gg_clip_first_trained_layer(const GgClipCfg* cfg, const uint8_t* 
     if (build(cfg, m)) return -1;
     return train_of(m, 1, trainable).l0;
 }
-extern "C" int gg_clip_refresh_weights(const GgClipCfg* cfg, const float* params, void* wcache, void* stream) {
+static int refresh_weights(const GgClipCfg* cfg, const float* params, void* wcache, const uint8_t* only, void* stream);
+extern "C" int gg_clip_refresh_weights(const GgClipCfg* cfg, const float* params, void* wcache, void* stream) { return refresh_weights(cfg, params, wcache, nullptr, stream); }
+// `only` (host, one byte per tensor, or NULL = every tensor): the tensors whose cached forms -- copy, transpose and, in the fp32_split mode, the bf16 planes of both --
+// are rebuilt.  The public entry point rebuilds everything; a masked one (the per-step refresh of a last-layer fine-tune skipping every frozen layer) needs only an export.
+static int refresh_weights(const GgClipCfg* cfg, const float* params, void* wcache, const uint8_t* only, void* stream) {
     CModel m;
     GG_TRY(build(cfg, m));
     GG_CHECK(params && wcache, "gg_clip_refresh_weights: null pointer");
@@ -498,7 +532,14 @@ extern "C" int gg_clip_refresh_weights(const GgClipCfg* cfg, const float* params
     const int D = m.cfg.hidden_size, I = m.cfg.intermediate_size;
     auto P = [&](int t) { return params + m.t[t].offset; };
     // W f32 [R][C] -> cache copy [R][C] at `n` (row offset r0 of a taller [.., C] image) and transpose [C][ldt] at `t` (column offset c0)
-    auto put = [&](const float* W, int R, int C, int64_t n, int64_t r0, int64_t t, int64_t ldt, int64_t c0) -> int {
+    auto ch = [&](int t) { return only == nullptr || only[t] != 0; };
+    // planes of a cached f32 matrix [R][C] (fp32_split; the matrix was just rebuilt)
+    auto split3 = [&](int64_t src, int64_t R, int C, int64_t dst) -> int {
+        return m.split ? gg_split3_bf16((const float*)(wc + src), R, C, C, wc + dst, st) : 0;
+    };
+    auto put = [&](int tw, int R, int C, int64_t n, int64_t r0, int64_t t, int64_t ldt, int64_t c0) -> int {
+        if (!ch(tw)) return 0;
+        const float* W = P(tw);
         if (m.f32) {
             GG_HIP(hipMemcpyAsync(wc + n + r0 * C * 4, W, (size_t)R * C * 4, hipMemcpyDeviceToDevice, st));
             return gg_transpose_f32(W, R, C, (float*)(wc + t) + c0, ldt, st);
@@ -511,21 +552,30 @@ extern "C" int gg_clip_refresh_weights(const GgClipCfg* cfg, const float* params
         }
         return gg_cast_transpose_f32(W, R, C, (bf16*)(wc + n) + r0 * C, C, (bf16*)(wc + t) + c0, ldt, st);
     };
-    if (m.f16) hipLaunchKernelGGL(cast_pad_rows_kernel<f16>, dim3(grid1d((int64_t)D * m.Kpatch)), dim3(256), 0, st, P(m.patch_w), (f16*)(wc + m.wpatch), D, m.Kraw, m.Kpatch);
+    if (!ch(m.patch_w)) {}
+    else if (m.f16) hipLaunchKernelGGL(cast_pad_rows_kernel<f16>, dim3(grid1d((int64_t)D * m.Kpatch)), dim3(256), 0, st, P(m.patch_w), (f16*)(wc + m.wpatch), D, m.Kraw, m.Kpatch);
     else if (m.f32) hipLaunchKernelGGL(cast_pad_rows_kernel<float>, dim3(grid1d((int64_t)D * m.Kpatch)), dim3(256), 0, st, P(m.patch_w), (float*)(wc + m.wpatch), D, m.Kraw, m.Kpatch);
     else hipLaunchKernelGGL(cast_pad_rows_kernel<bf16>, dim3(grid1d((int64_t)D * m.Kpatch)), dim3(256), 0, st, P(m.patch_w), (bf16*)(wc + m.wpatch), D, m.Kraw, m.Kpatch);
     GG_LAUNCH_CHECK();
+    if (ch(m.patch_w)) GG_TRY(split3(m.wpatch, D, m.Kpatch, m.wpatch3));
     for (auto& l : m.layers) {
-        GG_TRY(put(P(l.q_w), D, D, l.wqkv, 0, l.wqkvT, 3 * D, 0));
-        GG_TRY(put(P(l.k_w), D, D, l.wqkv, D, l.wqkvT, 3 * D, D));
-        GG_TRY(put(P(l.v_w), D, D, l.wqkv, 2 * D, l.wqkvT, 3 * D, 2 * D));
+        GG_TRY(put(l.q_w, D, D, l.wqkv, 0, l.wqkvT, 3 * D, 0));
+        GG_TRY(put(l.k_w, D, D, l.wqkv, D, l.wqkvT, 3 * D, D));
+        GG_TRY(put(l.v_w, D, D, l.wqkv, 2 * D, l.wqkvT, 3 * D, 2 * D));
+        if (ch(l.q_w) || ch(l.k_w) || ch(l.v_w)) {      // (the three projections share one [3D][D] image)
+            GG_TRY(split3(l.wqkv, 3 * D, D, l.wqkv3));
+            GG_TRY(split3(l.wqkvT, D, 3 * D, l.wqkvT3));
+        }
         float* bq = (float*)(wc + l.bqkv);
-        hipLaunchKernelGGL(copy_f32_kernel, dim3((unsigned)gg_cdiv(D, 256)), dim3(256), 0, st, P(l.q_b), bq, D);
-        hipLaunchKernelGGL(copy_f32_kernel, dim3((unsigned)gg_cdiv(D, 256)), dim3(256), 0, st, P(l.k_b), bq + D, D);
-        hipLaunchKernelGGL(copy_f32_kernel, dim3((unsigned)gg_cdiv(D, 256)), dim3(256), 0, st, P(l.v_b), bq + 2 * D, D);
-        GG_TRY(put(P(l.o_w), D, D, l.wo, 0, l.woT, D, 0));
-        GG_TRY(put(P(l.fc1_w), I, D, l.w1, 0, l.w1T, I, 0));
-        GG_TRY(put(P(l.fc2_w), D, I, l.w2, 0, l.w2T, D, 0));
+        if (ch(l.q_b)) hipLaunchKernelGGL(copy_f32_kernel, dim3((unsigned)gg_cdiv(D, 256)), dim3(256), 0, st, P(l.q_b), bq, D);
+        if (ch(l.k_b)) hipLaunchKernelGGL(copy_f32_kernel, dim3((unsigned)gg_cdiv(D, 256)), dim3(256), 0, st, P(l.k_b), bq + D, D);
+        if (ch(l.v_b)) hipLaunchKernelGGL(copy_f32_kernel, dim3((unsigned)gg_cdiv(D, 256)), dim3(256), 0, st, P(l.v_b), bq + 2 * D, D);
+        GG_TRY(put(l.o_w, D, D, l.wo, 0, l.woT, D, 0));
+        GG_TRY(put(l.fc1_w, I, D, l.w1, 0, l.w1T, I, 0));
+        GG_TRY(put(l.fc2_w, D, I, l.w2, 0, l.w2T, D, 0));
+        if (ch(l.o_w)) { GG_TRY(split3(l.wo, D, D, l.wo3)); GG_TRY(split3(l.woT, D, D, l.woT3)); }
+        if (ch(l.fc1_w)) { GG_TRY(split3(l.w1, I, D, l.w13)); GG_TRY(split3(l.w1T, D, I, l.w1T3)); }
+        if (ch(l.fc2_w)) { GG_TRY(split3(l.w2, D, I, l.w23)); GG_TRY(split3(l.w2T, I, D, l.w2T3)); }
     }
     GG_LAUNCH_CHECK();
     return 0;
@@ -604,21 +654,21 @@ extern "C" int gg_clip_backward(const GgClipCfg* cfg, int batch, const float* pa
         // ---- MLP: x_out = x_mid + fc2(quick_gelu(fc1(LN2(x_mid))))
         GG_TRY(e.wgrad(l.fc2_w, e.A(dx), D, e.A(a.h), I, M, D, I));
         GG_TRY(e.bgrad(l.fc2_b, e.A(dx), D, M, D));
-        GG_TRY(e.gemm(e.A(dx), D, e.W(l.w2T), D, e.A(L.g_h), I, M, I, D, nullptr, 0, nullptr, nullptr, e.A(a.pre), GG_ACT_CODE_QUICK_GELU));   // d pre
+        GG_TRY(e.gemm(e.A(dx), D, e.W(l.w2T, l.w2T3), D, e.A(L.g_h), I, M, I, D, nullptr, 0, nullptr, nullptr, e.A(a.pre), GG_ACT_CODE_QUICK_GELU));   // d pre
         GG_TRY(e.wgrad(l.fc1_w, e.A(L.g_h), I, e.A(a.a2), D, M, I, D));
         GG_TRY(e.bgrad(l.fc1_b, e.A(L.g_h), I, M, I));
-        GG_TRY(e.gemm(e.A(L.g_h), I, e.W(l.w1T), I, e.A(L.g_a), D, M, D, I, nullptr));                                                        // d LN2 out
+        GG_TRY(e.gemm(e.A(L.g_h), I, e.W(l.w1T, l.w1T3), I, e.A(L.g_a), D, M, D, I, nullptr));                                                        // d LN2 out
         GG_TRY(e.ln_bwd(e.A(L.g_a), e.A(a.xmid), e.F(a.mean2), e.F(a.rstd2), l.ln2_g, l.ln2_b, M, e.A(dx), e.A(other)));                       // d x_mid
         std::swap(dx, other);
         // ---- attention: x_mid = x_in + out_proj(attn(qkv(LN1(x_in))))
         GG_TRY(e.wgrad(l.o_w, e.A(dx), D, e.A(a.o), D, M, D, D));
         GG_TRY(e.bgrad(l.o_b, e.A(dx), D, M, D));
-        GG_TRY(e.gemm(e.A(dx), D, e.W(l.woT), D, e.A(L.g_o), D, M, D, D, nullptr));                                                            // d o
+        GG_TRY(e.gemm(e.A(dx), D, e.W(l.woT, l.woT3), D, e.A(L.g_o), D, M, D, D, nullptr));                                                            // d o
         GgAttnArgs at;
         e.attn_args(at, e.A(a.qkv), e.A(a.o), e.F(a.lse));
         at.dout = e.A(L.g_o); at.lddo = D; at.dqkv = e.A(L.g_qkv);
         if (L.attn_ds >= 0) at.ds_scratch = e.F(L.attn_ds);
-        GG_TRY(gg_attention_flash_bwd(&at, m.f32 ? 1 : 0, e.st));
+        GG_TRY(gg_attention_flash_bwd(&at, m.split ? 3 : m.f32 ? 1 : 0, e.st));
         const char* dq = (const char*)e.A(L.g_qkv);
         GG_TRY(e.wgrad(l.q_w, dq, 3 * D, e.A(a.a1), D, M, D, D));
         GG_TRY(e.wgrad(l.k_w, dq + (int64_t)D * m.es, 3 * D, e.A(a.a1), D, M, D, D));
@@ -626,7 +676,7 @@ extern "C" int gg_clip_backward(const GgClipCfg* cfg, int batch, const float* pa
         GG_TRY(e.bgrad(l.q_b, dq, 3 * D, M, D));
         GG_TRY(e.bgrad(l.k_b, dq + (int64_t)D * m.es, 3 * D, M, D));
         GG_TRY(e.bgrad(l.v_b, dq + (int64_t)2 * D * m.es, 3 * D, M, D));
-        GG_TRY(e.gemm(e.A(L.g_qkv), 3 * D, e.W(l.wqkvT), 3 * D, e.A(L.g_a), D, M, D, 3 * D, nullptr));                                          // d LN1 out
+        GG_TRY(e.gemm(e.A(L.g_qkv), 3 * D, e.W(l.wqkvT, l.wqkvT3), 3 * D, e.A(L.g_a), D, M, D, 3 * D, nullptr));                                          // d LN1 out
         GG_TRY(e.ln_bwd(e.A(L.g_a), e.A(a.xin), e.F(a.mean1), e.F(a.rstd1), l.ln1_g, l.ln1_b, M, e.A(dx), e.A(other)));                         // d x_in
         std::swap(dx, other);
     }
@@ -642,9 +692,8 @@ extern "C" int gg_clip_backward(const GgClipCfg* cfg, int batch, const float* pa
                             wp ? (bf16*)e.A(L.g_a) : nullptr, B, T, D);
     GG_LAUNCH_CHECK();
     if (wp) {
-        const int sp = m.f32 ? gg_gemm_tn_f32_splits((int)Mp, D, m.Kpatch) : gg_gemm_tn_splits((int)Mp, D, m.Kpatch);
-        if (m.f32) GG_TRY(gg_gemm_tn_f32(e.A(L.g_a), D, e.A(L.col), m.Kpatch, (int)Mp, D, m.Kpatch, nullptr, 0, e.F(L.splitk), sp, e.st));
-        else GG_TRY(gg_gemm_tn(e.A(L.g_a), D, e.A(L.col), m.Kpatch, (int)Mp, D, m.Kpatch, nullptr, 0, e.F(L.splitk), sp, e.st));
+        int sp;
+        GG_TRY(e.tn(e.A(L.g_a), D, e.A(L.col), m.Kpatch, Mp, D, m.Kpatch, &sp));
         GG_TRY(gg_splitk_reduce(e.F(L.splitk), e.F(L.splitk), (int64_t)D * m.Kpatch, sp, 0, 1.0f, e.st));
         hipLaunchKernelGGL(patch_wgrad_scatter_kernel, dim3((unsigned)gg_cdiv((int64_t)D * m.Kraw, 256)), dim3(256), 0, e.st, e.F(L.splitk), D, m.Kpatch,
                            m.Kraw, e.Gd(m.patch_w));

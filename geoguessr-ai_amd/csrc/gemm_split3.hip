@@ -107,10 +107,13 @@ __device__ __forceinline__ void split3_epilogue4(const Split3Params& p, f32x4 v,
 //   2: pre = acc + bias;  C = GELU(pre)                  (fc1 forward; pre-activation saved)
 //   3: C = acc * GELU'(saved pre-activation) [* scale]   (fc2 data gradient)
 //   4: C = (acc + bias) [* scale] + residual             (proj / fc2 forward)
+//   5, 6: classes 2 and 3 with QuickGELU / QuickGELU' in place of the erf GELU (the CLIP tower's fc1 forward and fc2 data gradient)
 // The results (and the saved pre-activation) are stored non-temporally.
-template <int BM, int BN, int NTHR, int EC>
+template <int BM, int BN, int NTHR, int EC_>
 __device__ __forceinline__ void split3_epilogue_rows_ec(const Split3Params& p, const float* Ct, int m0, int n0) {
     constexpr int LDT = BN + 4, CPR = BN / 8, RPP = NTHR / CPR, NR = (BM + RPP - 1) / RPP;
+    constexpr int ACT = (EC_ == 5 || EC_ == 6) ? 2 : 1;            // activation code of classes 2 / 3 (erf GELU) and 5 / 6 (QuickGELU)
+    constexpr int EC = EC_ == 5 ? 2 : EC_ == 6 ? 3 : EC_;
     if ((int)threadIdx.x >= RPP * CPR) return;
     const int chunk = threadIdx.x % CPR, r0 = threadIdx.x / CPR;
     const int n = n0 + chunk * 8;
@@ -139,9 +142,9 @@ __device__ __forceinline__ void split3_epilogue_rows_ec(const Split3Params& p, c
         if constexpr (EC == 2) {
             float* const pre = p.preact + (int64_t)m * p.ldc + n;
             stg(pre, v0); stg(pre + 4, v1);
-            v0 = gg_act_f32_v4(v0, 1); v1 = gg_act_f32_v4(v1, 1);
+            v0 = gg_act_f32_v4(v0, ACT); v1 = gg_act_f32_v4(v1, ACT);
         }
-        if constexpr (EC == 3) { v0 = v0 * gg_act_grad_f32_v4(aux[i][0], 1); v1 = v1 * gg_act_grad_f32_v4(aux[i][1], 1); }
+        if constexpr (EC == 3) { v0 = v0 * gg_act_grad_f32_v4(aux[i][0], ACT); v1 = v1 * gg_act_grad_f32_v4(aux[i][1], ACT); }
         if constexpr (EC == 3 || EC == 4) {
             if (p.rowscale) { const float sc = p.rowscale[m / p.rows_per_scale]; v0 = v0 * sc; v1 = v1 * sc; }
         }
@@ -1101,16 +1104,16 @@ static int split3_af32_launch(const GgSplit3Args* a, const float* A, int64_t lda
     const bool n96 = nenv ? atoi(nenv) == 96 : (w128 - w96 >= 0.2);
     const int bn = n96 ? 96 : 128;
     p.tilesM = (int)gg_cdiv(p.M, big ? 256 : 128); p.tilesN = (int)gg_cdiv(p.N, bn);
-    // epilogue class (split3_epilogue_rows_ec) when the shape takes the vector path and the options are one of the model's four combinations; 0 = the generic epilogue
+    // epilogue class (split3_epilogue_rows_ec) when the shape takes the vector path and the options are one of the models' six combinations; 0 = the generic epilogue
     static const char* eenv = gg_dev_env("GG_SPLIT3_NO_EC");       // dev: the generic epilogue everywhere
     int ec = 0;
     if (!eenv && p.C && !p.c_planes && !p.colstats && (p.N & 7) == 0 && (p.ldc & 3) == 0 && (!p.residual || (p.ldr & 3) == 0) && (!p.bias || ((uintptr_t)p.bias & 15) == 0)) {
-        if (p.act == 1 && p.preact && !p.rowscale && !p.residual && !p.dact_preact) ec = 2;
-        else if (p.dact_preact && p.dact == 1 && !p.bias && !p.act && !p.preact && !p.residual) ec = 3;
+        if ((p.act == 1 || p.act == 2) && p.preact && !p.rowscale && !p.residual && !p.dact_preact) ec = p.act == 1 ? 2 : 5;
+        else if (p.dact_preact && (p.dact == 1 || p.dact == 2) && !p.bias && !p.act && !p.preact && !p.residual) ec = p.dact == 1 ? 3 : 6;
         else if (p.residual && !p.act && !p.preact && !p.dact_preact) ec = 4;
         else if (!p.act && !p.preact && !p.rowscale && !p.residual && !p.dact_preact) ec = 1;
     }
-#define S3_EC(K, ...) (ec == 1 ? K<__VA_ARGS__, 1> : ec == 2 ? K<__VA_ARGS__, 2> : ec == 3 ? K<__VA_ARGS__, 3> : ec == 4 ? K<__VA_ARGS__, 4> : K<__VA_ARGS__, 0>)
+#define S3_EC(K, ...) (ec == 1 ? K<__VA_ARGS__, 1> : ec == 2 ? K<__VA_ARGS__, 2> : ec == 3 ? K<__VA_ARGS__, 3> : ec == 4 ? K<__VA_ARGS__, 4> : ec == 5 ? K<__VA_ARGS__, 5> : ec == 6 ? K<__VA_ARGS__, 6> : K<__VA_ARGS__, 0>)
     void (*kern)(Split3Params) = pro ? (n96 ? (bn_act == 1 ? gemm_nt_split3a_kernel<3, 0, 2> : bn_act == 2 ? gemm_nt_split3a_kernel<3, 0, 3> : gemm_nt_split3a_kernel<3, 0, 1>)
                                             : (bn_act == 1 ? gemm_nt_split3a_kernel<4, 0, 2> : bn_act == 2 ? gemm_nt_split3a_kernel<4, 0, 3> : gemm_nt_split3a_kernel<4, 0, 1>)) :
                                  !big ? (n96 ? S3_EC(gemm_nt_split3b_kernel, 3) : S3_EC(gemm_nt_split3b_kernel, 4)) :

@@ -46,7 +46,7 @@ def default_precision() -> str:
     or "bf16" (bf16 activations / MFMA operands, fp32 accumulation and master weights: 3.4x the throughput, bf16-level parity)."""
     p = os.environ.get("GG_PRECISION", "fp32").lower()
     if p not in PRECISIONS:
-        raise ValueError(f"GG_PRECISION='{p}' (known: bf16, fp32)")
+        raise ValueError(f"GG_PRECISION='{p}' (known: bf16, fp32, fp32_split)")
     return p
 
 

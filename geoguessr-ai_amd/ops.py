@@ -505,10 +505,11 @@ def view_mean_f32(emb):
 
 def attention_flash(qkv, *, num_windows, tokens_per_window, num_heads, head_dim, q_off, k_off, v_off, head_stride,
                     window_size=0, map_h=0, map_w=0, bias_table=None, scale=None, dout=None, want_dbias=False, out=None, lse=None,
-                    want_lse=False, deterministic_dbias=True, ds_handoff=False):
+                    want_lse=False, deterministic_dbias=True, ds_handoff=False, split=False):
     """Online-softmax attention (any tokens_per_window; bf16 or f32 storage by ``qkv.dtype``).  Forward when ``dout`` is None
     (returns out, or (out, lse)); else backward given the forward's ``out`` and ``lse`` -> (dqkv, dbias).  ``ds_handoff``: give the
-    backward a dS scratch (the dK/dV pass then hands dS to a one-product dQ pass)."""
+    backward a dS scratch (the dK/dV pass then hands dS to a one-product dQ pass).  ``split`` (f32 storage): dtype 3 of the C entry points --
+    every product as a split-bf16 product (head dim 64, no windows, no bias: the CLIP tower's fp32_split attention)."""
     L.require_gpu()
     DT = qkv.dtype
     a = L.AttnArgs()
@@ -520,6 +521,10 @@ def attention_flash(qkv, *, num_windows, tokens_per_window, num_heads, head_dim,
     a.bias_table = _p(bias_table, F32, "bias_table")
     tokens = qkv.shape[0]
     dt = int(DT == F32)
+    if split:
+        if DT != F32:
+            raise L.GgError("attention_flash: split=True takes f32 storage")
+        dt = 3
     if dout is None:
         out = torch.empty((tokens, num_heads * head_dim), dtype=DT, device=qkv.device)
         a.out, a.ldo = _p(out), out.stride(0)

@@ -10,8 +10,9 @@
   ``optim.AdamW`` and the RCCL gradient exchange treat both encoders alike.  ``gradient_checkpointing_enable()`` (HF's call) turns on
   activation recompute (``GgClipCfg.recompute``): the workspace keeps each trained layer's input instead of its eight activations.
 
-Arithmetic: ``precision="fp32"`` (default; the reference runs the tower in fp32), ``"bf16"``, or ``"fp16"`` (inference only: the precision BASELINE
-config c4 names).  No hub download: weights come from a
+Arithmetic: ``precision="fp32"`` (default; the reference runs the tower in fp32), ``"fp32_split"`` (f32 storage, every GEMM and the attention as
+f32-accurate split-bf16 products: ``GgClipCfg.act_dtype`` 3), ``"bf16"``, or ``"fp16"`` (inference only: the precision BASELINE
+config c4 names); the default is ``$GG_PRECISION``.  No hub download: weights come from a
 state dict (HF names, with or without the leading ``vision_model.``)."""
 from __future__ import annotations
 
@@ -31,6 +32,7 @@ CLIP_CONFIGS = {
 }
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)      # CLIPProcessor's image_mean / image_std (openai/clip-vit-*)
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+PRECISION_NAMES = {0: "bf16", 1: "fp32", 2: "fp16", 3: "fp32_split"}      # GgClipCfg.act_dtype -> the name ``.precision`` reports
 
 
 def _precision_code(precision: Optional[str]) -> int:
@@ -39,7 +41,7 @@ def _precision_code(precision: Optional[str]) -> int:
     if p in ("fp16", "f16", "float16", "half"):
         return 2                      # CLIP only, inference only (BASELINE config c4: "MFMA fp16")
     if p not in PRECISIONS:
-        raise ValueError(f"precision='{p}' (known: bf16, fp16, fp32)")
+        raise ValueError(f"precision='{p}' (known: bf16, fp16, fp32, fp32_split)")
     return PRECISIONS[p]
 
 
@@ -54,7 +56,8 @@ class _VisionModel(EncoderRuntime):
     def __init__(self, cfg: L.ClipCfg, seed: int):
         super().__init__()
         self.cfg = cfg
-        self.precision = {0: "bf16", 1: "fp32", 2: "fp16"}[cfg.act_dtype]
+        self.precision = PRECISION_NAMES[cfg.act_dtype]
+        self.split = cfg.act_dtype == 3
         lib = L.lib()
         n = lib.gg_clip_num_tensors(C.byref(cfg))
         if n < 0:
@@ -82,7 +85,7 @@ class _VisionModel(EncoderRuntime):
     def _wcache_bytes(self) -> int:
         return L.lib().gg_clip_wcache_bytes(C.byref(self.cfg))
 
-    def _refresh(self, only):             # (no masked refresh: the whole cache is rebuilt)
+    def _refresh(self, only):             # (no masked refresh: the whole cache is rebuilt, in the fp32_split mode the bf16 planes with it)
         L.check(L.lib().gg_clip_refresh_weights(C.byref(self.cfg), L.ptr(self._flat), L.ptr(self._wcache), L.stream()), "gg_clip_refresh_weights")
 
     def _workspace_bytes(self, batch: int, training: bool, mask) -> int:
@@ -145,7 +148,7 @@ class CLIPVisionTower(nn.Module):
         c.act_dtype = _precision_code(precision)
         c.recompute = int(bool(gradient_checkpointing))
         self.cfg = c
-        self.precision = {0: "bf16", 1: "fp32", 2: "fp16"}[c.act_dtype]
+        self.precision = PRECISION_NAMES[c.act_dtype]
         self.config = SimpleNamespace(hidden_size=kw["hidden_size"], _name_or_path=model_name, **{k: v for k, v in kw.items() if k != "hidden_size"})
         self.vision_model = _VisionModel(c, seed)
         self.num_tokens = (c.image_size // c.patch_size) ** 2 + 1

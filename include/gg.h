@@ -211,10 +211,14 @@ int gg_attention_bwd(const GgAttnArgs* args, void* stream);
 int gg_attention_fwd_f16(const GgAttnArgs* args, void* stream);
 /* Online-softmax (flash) form for ANY tokens_per_window (1024-token windows of the reference's default tiny_vit_21m_512, config.py:9;
  * 577 tokens of CLIP ViT-L/14-336, config.py:6) and for the reference-precision mode: dtype 0 = bf16, 1 = f32, 2 = fp16 (forward only) storage of
- * qkv / out / dout / dqkv; arithmetic is f32-accurate either way: f32 MFMA, or -- fp32 storage, head dim 32, 7 x 7 / 12 x 12 / 14 x 14 windows --
+ * qkv / out / dout / dqkv, 3 = f32 storage with every product as a split-bf16 product (below); arithmetic is f32-accurate either way: f32 MFMA, or -- fp32 storage, head dim 32, 7 x 7 / 12 x 12 / 14 x 14 windows --
  * split products on the bf16 MFMA (x = x1 + x2 + x3 in bf16, six products per f32 product: DESIGN.md 5 has the error table); bf16 storage of those
  * window shapes runs the same single-pass backward with plain bf16 products.  window_size <= 32.  dbias_scratch (optional): f32
- * [gg_attention_flash_dbias_rows(num_windows, tokens_per_window)][num_heads][ws*ws]. */
+ * [gg_attention_flash_dbias_rows(num_windows, tokens_per_window)][num_heads][ws*ws].
+ * dtype 3 (the CLIP tower's fp32_split mode, GgClipCfg.act_dtype 3): f32 qkv / out / dout / dqkv, head_dim 64, ANY tokens_per_window, window_size 0, no bias
+ * (bias_table, dbias NULL) -- any other shape is refused and nothing is written.  Forward: online softmax over 64-key tiles, writes out and lse (lse may be
+ * NULL).  Backward: two passes at every length (dQ; dK, dV), each recomputing P from lse; ds_scratch is not read; no atomics -- two backwards of one forward
+ * give the same bits.  Error against fp64 at or below dtype 1's. */
 int gg_attention_flash_fwd(const GgAttnArgs* args, int dtype, void* stream);
 int gg_attention_flash_bwd(const GgAttnArgs* args, int dtype, void* stream);
 int64_t gg_attention_flash_dbias_rows(int num_windows, int tokens_per_window);
@@ -540,7 +544,14 @@ int gg_segment_mean(const float* emb, int64_t ld, const int64_t* ptr, const int6
  * pretrain/clip_embedder.py:51-66) and the trainable base model of SuperGuessr (models/super_guessr.py:134-150,323-325: the last
  * encoder layer is fine-tuned when the pretrained head exists, every layer otherwise; main_coordinator_idun_s3.py:183-203).
  * act_dtype 1 = fp32 (the reference's precision: f32 activations, f32 MFMA), 0 = bf16 and 2 = fp16 activations / MFMA operands with f32
- * accumulation (2: inference only -- BASELINE config c4 names fp16).
+ * accumulation (2: inference only -- BASELINE config c4 names fp16), 3 = fp32_split: mode 1's storage, workspace layout and element size, with every GEMM as
+ * an f32-accurate split product on the bf16 MFMA (x = x1 + x2 + x3 in bf16, six v_mfma_f32_16x16x32_bf16 per f32 product) -- the patch embedding,
+ * qkv, out_proj, fc1 and fc2 forward and their data gradients through gg_gemm_nt_split3_af32 (QuickGELU and QuickGELU' in its compile-time epilogue classes),
+ * the weight gradients through gg_gemm_tn_split3 (slab count from gg_gemm_tn_split3_splits: the split-K slab is the one workspace region whose size differs
+ * from mode 1's, besides the dS hand-off of the attention backward, which mode 3 does not plan), attention through gg_attention_flash_fwd / _bwd with dtype 3 at
+ * every token count.  LayerNorm, token assembly, column sums, pooling and the optimizer are mode 1's f32 kernels; recompute, trainable masks and the
+ * workspace refusals behave as in mode 1.  The weight cache additionally holds the bf16 planes [3][N][K] (gg_split3_bf16) of every cached matrix: W of the
+ * patch embedding, W and W^T of qkv, out_proj, fc1 and fc2 -- gg_clip_wcache_bytes grows by 6 bytes per cached weight element (256-byte aligned per matrix).
  * Parameters: one flat f32 buffer, HF state-dict names without the "vision_model." prefix (gg_clip_tensor_info).  `trainable` (host,
  * one byte per tensor, NULL = all) selects the tensors whose gradients gg_clip_backward accumulates; a training forward keeps the
  * activations of every layer from the first trainable one up (gg_clip_first_trained_layer), frozen layers below run in place; with
@@ -548,7 +559,7 @@ int gg_segment_mean(const float* emb, int64_t ld, const int64_t* ptr, const int6
 typedef struct GgClipCfg {
     int hidden_size, intermediate_size, num_layers, num_heads, image_size, patch_size;
     float ln_eps;
-    int act_dtype;                         /* 0 bf16, 1 fp32, 2 fp16 (inference only) */
+    int act_dtype;                         /* 0 bf16, 1 fp32, 2 fp16 (inference only), 3 fp32_split (f32 storage, split-bf16 products) */
     int recompute;       /* activation recompute (gradient checkpointing, HF gradient_checkpointing_enable) of a training forward / backward pair;
                             ignored by inference (training = 0).  0: the workspace keeps every activation the backward reads.
                             1: per-layer checkpoints -- the segments are the encoder layers from the first trainable one up.  The workspace keeps

@@ -144,8 +144,9 @@ def main():
     for c in cases:
         print(json.dumps(run_case(*c, steps=args.steps, warmup=args.warmup)), flush=True)
     if "clip" in want:
-        for precision in ("fp32", "bf16"):
-            p = clip_largest_panoramas(precision)
+        for precision in ("fp32", "fp32_split", "bf16"):
+            # (fp32_split at the fp32 batch: the same f32 workspace, so that the two modes' step times compare image for image)
+            p = clip_largest_panoramas("fp32" if precision == "fp32_split" else precision)
             off = run_case("clip", CLIP_MODEL, p, precision, "all", False, args.steps, args.warmup)
             print(json.dumps(off), flush=True)
             on = run_case("clip", CLIP_MODEL, p, precision, "all", True, args.steps, args.warmup)

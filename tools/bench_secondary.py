@@ -2,7 +2,8 @@
 """Secondary numbers of SURVEY.md 8(d) on one MI355X (the headline c2 line is bench.py's):
   c1  TinyViT-5M-224, batch 8, forward + geocell hard-CE + backward + AdamW (panorama=False)
   c2u TinyViT-21M-224, 256 panoramas, every parameter trainable
-  c4  CLIP ViT-B/32 vision tower, batch 1024, inference (random weights; fp32 = the reference's precision, bf16 = 16-bit MFMA operands)
+  c4  CLIP ViT-B/32 vision tower, batch 1024, inference (random weights; fp32 = the reference's precision, fp32_split = f32 storage with split-bf16
+      products (--fp32_split), bf16 = 16-bit MFMA operands)
   c4-train  SuperGuessr on the CLIP ViT-B/32 base, 64 panoramas, reference freeze policy with the head file present, forward + backward + AdamW
   c5  SuperGuessr head (serving) + ProtoRefiner on precomputed embeddings, batch 4096
 Prints one JSON object per case.  Synthetic inputs as in bench.py."""
@@ -19,7 +20,7 @@ from geoguessr_ai_amd.optim import AdamW
 L.require_gpu()
 dev = torch.device("cuda", 0)
 cases = [a for a in sys.argv[1:] if not a.startswith("--")] or ["c1", "c2u", "c4", "c5"]
-precisions = ["fp32", "bf16"] if "--both" in sys.argv or not any(a.startswith("--") for a in sys.argv[1:]) else [a[2:] for a in sys.argv[1:] if a in ("--fp32", "--bf16")]
+precisions = ["fp32", "bf16"] if "--both" in sys.argv or not any(a.startswith("--") for a in sys.argv[1:]) else [a[2:] for a in sys.argv[1:] if a in ("--fp32", "--fp32_split", "--bf16")]
 
 
 def timed(fn, steps, warmup):
