@@ -75,6 +75,18 @@ class ClipCfg(C.Structure):
                 ("recompute", C.c_int)]
 
 
+class ClipTextCfg(C.Structure):          # GgClipTextCfg (include/gg_clip_text.h)
+    _fields_ = [("hidden_size", C.c_int), ("intermediate_size", C.c_int), ("num_layers", C.c_int), ("num_heads", C.c_int),
+                ("vocab_size", C.c_int), ("max_positions", C.c_int), ("ln_eps", C.c_float), ("act_dtype", C.c_int)]
+
+
+class ContrastiveArgs(C.Structure):      # GgContrastiveArgs
+    _fields_ = [("img", C.c_void_p), ("ldi", C.c_int64), ("txt", C.c_void_p), ("ldt", C.c_int64), ("Bi", C.c_int), ("Bt", C.c_int), ("P", C.c_int),
+                ("logit_scale", C.c_void_p), ("img_n", C.c_void_p), ("txt_n", C.c_void_p), ("logits_per_text", C.c_void_p),
+                ("logits_per_image", C.c_void_p), ("want_loss", C.c_int), ("d_loss_scale", C.c_float), ("loss", C.c_void_p),
+                ("d_logit_scale", C.c_void_p), ("d_img", C.c_void_p), ("d_txt", C.c_void_p), ("scratch", C.c_void_p)]
+
+
 STAGE_DONE_FN = C.CFUNCTYPE(None, C.c_int, C.c_void_p)      # GgStageDoneFn (host callback of gg_tinyvit_backward)
 
 # every exported symbol of include/gg.h: name -> (restype, argtypes)
@@ -247,6 +259,25 @@ SIGNATURES = {
 }
 SYMBOLS = list(SIGNATURES)
 
+# every exported symbol of include/gg_clip_text.h (the contrastive pre-training stage), bound from the same libgg.so
+TEXT_SIGNATURES = {
+    "gg_attention_causal_fwd": (_I, [C.POINTER(AttnArgs), _I, _P]),
+    "gg_clip_text_num_tensors": (_I, [C.POINTER(ClipTextCfg)]),
+    "gg_clip_text_tensor_info": (_I, [C.POINTER(ClipTextCfg), _I, C.c_char_p, _I, C.POINTER(_L), C.POINTER(_L), C.POINTER(_I), C.POINTER(_L)]),
+    "gg_clip_text_param_floats": (_L, [C.POINTER(ClipTextCfg)]),
+    "gg_clip_text_wcache_bytes": (_L, [C.POINTER(ClipTextCfg)]),
+    "gg_clip_text_workspace_bytes": (_L, [C.POINTER(ClipTextCfg), _I, _I]),
+    "gg_clip_text_refresh_weights": (_I, [C.POINTER(ClipTextCfg), _P, _P, _P]),
+    "gg_clip_text_forward": (_I, [C.POINTER(ClipTextCfg), _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gg_clip_contrastive_scratch_floats": (_L, [_I, _I, _I]),
+    "gg_clip_contrastive": (_I, [C.POINTER(ContrastiveArgs), _P]),
+    "gg_row_gather_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "gg_row_scatter_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "gg_grad_sq_norm_scratch_doubles": (_L, [_L]),
+    "gg_grad_sq_norm": (_I, [_P, _L, _P, _P, _I, _P]),
+}
+TEXT_SYMBOLS = list(TEXT_SIGNATURES)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -255,7 +286,7 @@ def lib() -> C.CDLL:
             raise GgError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the library lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -301,6 +332,7 @@ def source_hash() -> str:
     root = os.path.dirname(os.path.abspath(__file__))
     files = sorted(os.path.join(root, "csrc", f) for f in os.listdir(os.path.join(root, "csrc")) if f.endswith((".hip", ".h", ".cpp", "Makefile")))
     files.append(os.path.join(os.path.dirname(root), "include", "gg.h"))
+    files.append(os.path.join(os.path.dirname(root), "include", "gg_clip_text.h"))
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

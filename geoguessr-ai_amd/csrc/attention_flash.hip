@@ -17,6 +17,7 @@
 // summed per workgroup in LDS.  The backward pass runs in two passes (dQ; dK,dV): no atomics on dq/dk/dv, deterministic.
 #include "common.h"
 #include "../../include/gg.h"
+#include "../../include/gg_clip_text.h"
 
 namespace {
 
@@ -216,8 +217,11 @@ __device__ __forceinline__ void fl_stage_coords(const FlashParams& p, int t0, in
 // LDS carve-up (dynamic): [R][RS] x 2 operand images, the bias table (p.nbpad floats), coordinates and per-row scalars; R = RES ? npad : 64.
 
 // ------------------------------------------------------------------------------------------- forward
-template <typename T, int D, bool RES>
+// CAUSAL (streaming form only; gg_attention_causal_fwd, bf16 storage): query t sees keys 0..t -- key tiles above the workgroup's query tile are not visited,
+// the diagonal tile's scores above the diagonal are -inf before the running maximum.
+template <typename T, int D, bool RES, bool CAUSAL = false>
 __global__ __launch_bounds__(RES ? 1024 : 256) void flash_fwd_kernel(FlashParams p) {
+    static_assert(!(CAUSAL && RES), "the causal form is the streaming one");
     constexpr int RS = D + 4, DC = D / 16;
     extern __shared__ __attribute__((aligned(16))) float fsm[];
     const int R = RES ? p.npad : 64;
@@ -278,7 +282,8 @@ __global__ __launch_bounds__(RES ? 1024 : 256) void flash_fwd_kernel(FlashParams
 #pragma unroll
     for (int c = 0; c < DC; ++c) oacc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    for (int kt0 = 0; kt0 < p.ntile; ++kt0) {
+    const int nkt0 = CAUSAL ? qt + 1 : p.ntile;
+    for (int kt0 = 0; kt0 < nkt0; ++kt0) {
         const int t0 = kt0 * 64;
         if (!RES) {
             __syncthreads();
@@ -328,7 +333,8 @@ __global__ __launch_bounds__(RES ? 1024 : 256) void flash_fwd_kernel(FlashParams
         for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {          // scores in the exp2 domain: s * scale * log2 e + bias * log2 e
-                const float s = fmaf(st[kt][r], sc2, bia[kt][r]);
+                float s = fmaf(st[kt][r], sc2, bia[kt][r]);
+                if constexpr (CAUSAL) { if (kt0 == qt && t0 + 16 * kt + 4 * lg + r > qi) s = -INFINITY; }
                 st[kt][r] = s;
                 tmax = fmaxf(tmax, s);
             }
@@ -1249,6 +1255,27 @@ extern "C" int gg_attention_flash_fwd(const GgAttnArgs* a, int dtype, void* stre
     else if (dtype == 2) { if (a->head_dim == 32) GG_FL_FWD(f16, 32); else GG_FL_FWD(f16, 64); }
     else { if (a->head_dim == 32) GG_FL_FWD(bf16, 32); else GG_FL_FWD(bf16, 64); }
 #undef GG_FL_FWD
+    GG_LAUNCH_CHECK();
+    return 0;
+}
+// Causal forward (CLIP text tower; include/gg_clip_text.h).  f32 storage (dtype 1 and 3): the split-product kernel of dtype 3; bf16 storage: the streaming
+// online-softmax forward.  Everything else is refused before flash_fill's own checks can pass a shape these two instantiations do not cover.
+extern "C" int gg_attention_causal_fwd(const GgAttnArgs* a, int dtype, void* stream) {
+    GG_CHECK(a, "gg_attention_causal_fwd: null args");
+    GG_CHECK(dtype == 0 || dtype == 1 || dtype == 3, "gg_attention_causal_fwd: dtype must be 0 (bf16), 1 (f32) or 3 (f32, split products); got %d", dtype);
+    GG_CHECK(a->head_dim == 64 && a->window_size == 0 && !a->bias && !a->bias_table && !a->dbias,
+             "gg_attention_causal_fwd: head dim 64, linear tokens, no bias (got head_dim %d, window_size %d)", a->head_dim, a->window_size);
+    GG_CHECK(a->tokens_per_window <= GG_CLIP_TEXT_MAX_POSITIONS, "gg_attention_causal_fwd: %d tokens exceed the position table (%d)", a->tokens_per_window,
+             GG_CLIP_TEXT_MAX_POSITIONS);
+    FlashParams p;
+    GG_TRY(flash_fill(p, a, dtype == 0 ? 0 : 3, "gg_attention_causal_fwd"));
+    GG_CHECK(a->out && (a->ldo & 3) == 0 && ((uintptr_t)a->out & 15) == 0 && a->ldo >= (int64_t)a->num_heads * 64, "gg_attention_causal_fwd: bad out");
+    GG_CHECK(a->ld >= 64 && a->head_stride >= 0, "gg_attention_causal_fwd: bad qkv pitch");
+    const dim3 grid((unsigned)(a->num_windows * a->num_heads * p.ntile));
+    // (declared work: the lower triangle, half of the 4 N^2 D flops of the full forward)
+    GG_PROF(GG_CAT_ATTN, 2.0 * a->num_windows * a->num_heads * (double)p.N * p.N * 64, (dtype == 0 ? 8.0 : 16.0) * a->num_windows * a->num_heads * (double)p.N * 64, stream);
+    if (dtype == 0) hipLaunchKernelGGL((flash_fwd_kernel<bf16, 64, false, true>), grid, dim3(256), flash_lds_fwd(p, 64, 64), (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((flash64_split_q_kernel<3, false, true>), grid, dim3(256), sp64_lds(3, false), (hipStream_t)stream, p);
     GG_LAUNCH_CHECK();
     return 0;
 }

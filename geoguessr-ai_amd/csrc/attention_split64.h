@@ -37,8 +37,11 @@ template <int NPL> __device__ __forceinline__ void sp64_commit(const Sp64Regs& r
 
 // ------------------------------------------------------------------------------------------- forward / dQ pass
 // DQ = false: out, lse.  DQ = true: dQ of the tile's queries (reads out, dout, lse).
-template <int NPL, bool DQ>
+// CAUSAL (forward of the CLIP text tower, gg_attention_causal_fwd): query t sees keys 0..t.  Key tiles above the query tile are not visited (the bound is the
+// workgroup's own tile: the barriers stay uniform), the diagonal tile's scores above the diagonal become -inf before the running maximum -- their P is an exact 0.
+template <int NPL, bool DQ, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void flash64_split_q_kernel(FlashParams p) {
+    static_assert(!(CAUSAL && DQ), "the causal form is forward only");
     typedef Sp8T<NPL> Sp8;
     extern __shared__ __attribute__((aligned(16))) float fsm[];
     bf16* Kp = reinterpret_cast<bf16*>(fsm);
@@ -94,13 +97,14 @@ __global__ __launch_bounds__(256) void flash64_split_q_kernel(FlashParams p) {
     f32x4 acc[4];                                                  // O^T / dQ^T [d = 16 c + 4 lg + r][q = lr]
 #pragma unroll
     for (int c = 0; c < 4; ++c) acc[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int t = 0; t < p.ntile; ++t) {
+    const int nt = CAUSAL ? tile + 1 : p.ntile;                    // key tiles this workgroup walks
+    for (int t = 0; t < nt; ++t) {
         const int t0 = t * 64;
         __syncthreads();                                           // every wave is done with the previous tile's images
         sp64_commit<NPL>(kr, Kp);
         sp64_commit<NPL>(vr, Vp);
         __syncthreads();
-        if (t + 1 < p.ntile) {
+        if (t + 1 < nt) {
             sp64_issue(p, rsQKV, t0 + 64, ldb, (p.k_off + hc) * 4, kr);
             sp64_issue(p, rsQKV, t0 + 64, ldb, (p.v_off + hc) * 4, vr);
         }
@@ -123,6 +127,7 @@ __global__ __launch_bounds__(256) void flash64_split_q_kernel(FlashParams p) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     s[r] = DQ ? fmaf(s[r], sc2, nlse) : s[r] * sc2;      // exp2 domain; the backward's exponent is complete here
+                    if constexpr (CAUSAL) { if (t == tile && t0 + 16 * kt + 4 * lg + r > qi) s[r] = -INFINITY; }      // (key 0 <= every query: the maximum stays finite)
                     tmax = fmaxf(tmax, s[r]);
                 }
             }

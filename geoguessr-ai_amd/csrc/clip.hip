@@ -28,6 +28,7 @@
 #include <stdio.h>
 #include "common.h"
 #include "../../include/gg.h"
+#include "../../include/gg_clip_text.h"
 
 namespace {
 struct TInfo { std::string name; int64_t offset, numel; int ndim; int64_t shape[4]; };
@@ -44,6 +45,8 @@ struct CModel {
     int64_t wpatch, wpatch3 = -1;
     std::vector<LayerP> layers;
     int T, G, Kpatch, Kraw;
+    // the text tower (gg_clip_text_*) is the same layer stack over T = the call's token count with causal attention: embeddings and the final norm differ
+    bool causal = false; int tok_emb = -1, fin_g = -1, fin_b = -1, vocab = 0;
     bool f32, f16, split; int es;      // f32: f32 storage (fp32 and fp32_split modes); split: fp32_split; activation / cached-weight element size: 4 or 2 (bf16 / fp16 modes)
 };
 static int addt(CModel& m, const std::string& n, std::initializer_list<int64_t> shape) {
@@ -57,26 +60,12 @@ static int addt(CModel& m, const std::string& n, std::initializer_list<int64_t> 
 }
 static int64_t wca(CModel& m, int64_t bytes) { int64_t o = m.wc_bytes; m.wc_bytes += gg_align(bytes, 256); return o; }
 
-static int build(const GgClipCfg* c, CModel& m) {
-    GG_CHECK(c, "clip: null config");
-    m.cfg = *c;
-    GG_CHECK(c->act_dtype >= 0 && c->act_dtype <= 3, "clip: act_dtype must be 0 (bf16), 1 (fp32), 2 (fp16) or 3 (fp32_split), got %d", c->act_dtype);
-    m.split = c->act_dtype == 3; m.f32 = c->act_dtype == 1 || m.split; m.f16 = c->act_dtype == 2; m.es = m.f32 ? 4 : 2;
-    const int D = c->hidden_size, I = c->intermediate_size, P = c->patch_size;
-    GG_CHECK(D > 0 && D % 64 == 0 && D <= 1024 && c->num_heads > 0 && D / c->num_heads == 64, "clip: head_dim must be 64 and hidden <= 1024 (hidden %d, heads %d)", D, c->num_heads);
-    GG_CHECK(P > 0 && c->image_size % P == 0 && I % 8 == 0 && c->num_layers > 0, "clip: bad patch/image/intermediate size or layer count");
-    // patch-embedding contraction 3*P*P is padded to a multiple of 8 (ViT-L/14: 588 -> 592 zero columns); sequences beyond 256 tokens
-    // (ViT-L/14-336: 577, the reference's CLIP_MODEL, config.py:6) run on the online-softmax attention kernels
-    m.G = c->image_size / P; m.T = m.G * m.G + 1; m.Kraw = 3 * P * P; m.Kpatch = (int)gg_align(m.Kraw, 8);
-    m.cls = addt(m, "embeddings.class_embedding", {D});
-    m.patch_w = addt(m, "embeddings.patch_embedding.weight", {D, 3, P, P});
-    m.pos = addt(m, "embeddings.position_embedding.weight", {m.T, D});
-    m.pre_g = addt(m, "pre_layrnorm.weight", {D}); m.pre_b = addt(m, "pre_layrnorm.bias", {D});
-    m.wpatch = wca(m, (int64_t)D * m.Kpatch * m.es);
+// the encoder layers' tensors (HF state-dict order) and their weight-cache images: shared by the vision and the text tower
+static void add_layers(CModel& m) {
+    const int D = m.cfg.hidden_size, I = m.cfg.intermediate_size;
     auto planes = [&](int64_t n) { return m.split ? wca(m, 3 * n * 2) : (int64_t)-1; };      // fp32_split: bf16 planes [3][n] of a cached matrix
-    m.wpatch3 = planes((int64_t)D * m.Kpatch);                                              // (no W^T of the patch embedding in either mode: the pixels take no gradient)
-    m.layers.resize(c->num_layers);
-    for (int i = 0; i < c->num_layers; ++i) {
+    m.layers.resize(m.cfg.num_layers);
+    for (int i = 0; i < m.cfg.num_layers; ++i) {
         LayerP& l = m.layers[i];
         const std::string p = "encoder.layers." + std::to_string(i);
         l.k_w = addt(m, p + ".self_attn.k_proj.weight", {D, D}); l.k_b = addt(m, p + ".self_attn.k_proj.bias", {D});
@@ -96,7 +85,49 @@ static int build(const GgClipCfg* c, CModel& m) {
         l.wqkv3 = planes((int64_t)3 * D * D); l.wqkvT3 = planes((int64_t)3 * D * D); l.wo3 = planes((int64_t)D * D); l.woT3 = planes((int64_t)D * D);
         l.w13 = planes((int64_t)I * D); l.w1T3 = planes((int64_t)I * D); l.w23 = planes((int64_t)D * I); l.w2T3 = planes((int64_t)D * I);
     }
+}
+
+static int build(const GgClipCfg* c, CModel& m) {
+    GG_CHECK(c, "clip: null config");
+    m.cfg = *c;
+    GG_CHECK(c->act_dtype >= 0 && c->act_dtype <= 3, "clip: act_dtype must be 0 (bf16), 1 (fp32), 2 (fp16) or 3 (fp32_split), got %d", c->act_dtype);
+    m.split = c->act_dtype == 3; m.f32 = c->act_dtype == 1 || m.split; m.f16 = c->act_dtype == 2; m.es = m.f32 ? 4 : 2;
+    const int D = c->hidden_size, I = c->intermediate_size, P = c->patch_size;
+    GG_CHECK(D > 0 && D % 64 == 0 && D <= 1024 && c->num_heads > 0 && D / c->num_heads == 64, "clip: head_dim must be 64 and hidden <= 1024 (hidden %d, heads %d)", D, c->num_heads);
+    GG_CHECK(P > 0 && c->image_size % P == 0 && I % 8 == 0 && c->num_layers > 0, "clip: bad patch/image/intermediate size or layer count");
+    // patch-embedding contraction 3*P*P is padded to a multiple of 8 (ViT-L/14: 588 -> 592 zero columns); sequences beyond 256 tokens
+    // (ViT-L/14-336: 577, the reference's CLIP_MODEL, config.py:6) run on the online-softmax attention kernels
+    m.G = c->image_size / P; m.T = m.G * m.G + 1; m.Kraw = 3 * P * P; m.Kpatch = (int)gg_align(m.Kraw, 8);
+    m.cls = addt(m, "embeddings.class_embedding", {D});
+    m.patch_w = addt(m, "embeddings.patch_embedding.weight", {D, 3, P, P});
+    m.pos = addt(m, "embeddings.position_embedding.weight", {m.T, D});
+    m.pre_g = addt(m, "pre_layrnorm.weight", {D}); m.pre_b = addt(m, "pre_layrnorm.bias", {D});
+    m.wpatch = wca(m, (int64_t)D * m.Kpatch * m.es);
+    m.wpatch3 = m.split ? wca(m, 3 * (int64_t)D * m.Kpatch * 2) : (int64_t)-1;              // fp32_split: bf16 planes [3][n] of a cached matrix (no W^T of the patch embedding in either mode: the pixels take no gradient)
+    add_layers(m);
     m.post_g = addt(m, "post_layernorm.weight", {D}); m.post_b = addt(m, "post_layernorm.bias", {D});
+    return 0;
+}
+// the text tower's model over `tokens` positions per sequence (the tensor table does not depend on it)
+static int build_text(const GgClipTextCfg* c, int tokens, CModel& m) {
+    GG_CHECK(c, "clip_text: null config");
+    GG_CHECK(c->act_dtype == 0 || c->act_dtype == 1 || c->act_dtype == 3, "clip_text: act_dtype must be 0 (bf16), 1 (fp32) or 3 (fp32_split), got %d (fp16 is not built)", c->act_dtype);
+    const int D = c->hidden_size, I = c->intermediate_size;
+    GG_CHECK(D > 0 && D % 64 == 0 && D <= 1024 && c->num_heads > 0 && D / c->num_heads == 64 && D % c->num_heads == 0,
+             "clip_text: head_dim must be 64 and hidden <= 1024 (hidden %d, heads %d)", D, c->num_heads);
+    GG_CHECK(I > 0 && I % 8 == 0 && c->num_layers > 0 && c->vocab_size > 0, "clip_text: bad intermediate size, layer count or vocabulary");
+    GG_CHECK(c->max_positions > 0 && c->max_positions <= GG_CLIP_TEXT_MAX_POSITIONS, "clip_text: max_positions must be 1 ... %d, got %d", GG_CLIP_TEXT_MAX_POSITIONS, c->max_positions);
+    GG_CHECK(tokens > 0 && tokens <= c->max_positions, "clip_text: %d tokens per sequence, the position table holds %d", tokens, c->max_positions);
+    memset(&m.cfg, 0, sizeof(m.cfg));
+    m.cfg.hidden_size = D; m.cfg.intermediate_size = I; m.cfg.num_layers = c->num_layers; m.cfg.num_heads = c->num_heads; m.cfg.ln_eps = c->ln_eps;
+    m.cfg.act_dtype = c->act_dtype;
+    m.split = c->act_dtype == 3; m.f32 = c->act_dtype == 1 || m.split; m.f16 = false; m.es = m.f32 ? 4 : 2;
+    m.causal = true; m.vocab = c->vocab_size; m.T = tokens; m.G = 0; m.Kraw = m.Kpatch = 0;
+    m.cls = m.patch_w = m.pre_g = m.pre_b = m.post_g = m.post_b = -1; m.wpatch = -1;
+    m.tok_emb = addt(m, "embeddings.token_embedding.weight", {c->vocab_size, D});
+    m.pos = addt(m, "embeddings.position_embedding.weight", {c->max_positions, D});
+    add_layers(m);
+    m.fin_g = addt(m, "final_layer_norm.weight", {D}); m.fin_b = addt(m, "final_layer_norm.bias", {D});
     return 0;
 }
 
@@ -438,7 +469,8 @@ static int layer_fwd(const Exec& e, int i, int64_t cur, int64_t next, bool sv) {
     GG_TRY(e.gemm(e.A(A1), D, e.W(l.wqkv, l.wqkv3), D, e.A(QKV), 3 * D, M, 3 * D, D, (const float*)e.W(l.bqkv)));
     GgAttnArgs at;
     e.attn_args(at, e.A(QKV), e.A(O), sv ? e.F(a.lse) : nullptr);
-    if (m.split) GG_TRY(gg_attention_flash_fwd(&at, 3, e.st));      // split products at every token count
+    if (m.causal) GG_TRY(gg_attention_causal_fwd(&at, m.split ? 3 : m.f32 ? 1 : 0, e.st));      // the text tower (forward only: sv is never set)
+    else if (m.split) GG_TRY(gg_attention_flash_fwd(&at, 3, e.st));      // split products at every token count
     else if (m.f16) GG_TRY(gg_attention_fwd_f16(&at, e.st));      // fp16 MFMA for towers of at most 256 tokens (ViT-B/32: 50); beyond: fp16 storage, f32 arithmetic
     else if (m.f32 || sv || T > 256) GG_TRY(gg_attention_flash_fwd(&at, m.f32 ? 1 : 0, e.st));
     else GG_TRY(gg_attention_fwd(&at, e.st));
@@ -519,13 +551,16 @@ extern "C" int gg_clip_first_trained_layer(const GgClipCfg* cfg, const uint8_t* 
     if (build(cfg, m)) return -1;
     return train_of(m, 1, trainable).l0;
 }
-static int refresh_weights(const GgClipCfg* cfg, const float* params, void* wcache, const uint8_t* only, void* stream);
-extern "C" int gg_clip_refresh_weights(const GgClipCfg* cfg, const float* params, void* wcache, void* stream) { return refresh_weights(cfg, params, wcache, nullptr, stream); }
-// `only` (host, one byte per tensor, or NULL = every tensor): the tensors whose cached forms -- copy, transpose and, in the fp32_split mode, the bf16 planes of both --
-// are rebuilt.  The public entry point rebuilds everything; a masked one (the per-step refresh of a last-layer fine-tune skipping every frozen layer) needs only an export.
-static int refresh_weights(const GgClipCfg* cfg, const float* params, void* wcache, const uint8_t* only, void* stream) {
+static int refresh_model(const CModel& m, const float* params, void* wcache, const uint8_t* only, void* stream);
+extern "C" int gg_clip_refresh_weights(const GgClipCfg* cfg, const float* params, void* wcache, void* stream) {
     CModel m;
     GG_TRY(build(cfg, m));
+    return refresh_model(m, params, wcache, nullptr, stream);
+}
+// `only` (host, one byte per tensor, or NULL = every tensor): the tensors whose cached forms -- copy, transpose and, in the fp32_split mode, the bf16 planes of both --
+// are rebuilt.  The public entry point rebuilds everything; a masked one (the per-step refresh of a last-layer fine-tune skipping every frozen layer) needs only an export.
+// (the text tower comes through here too: it has no patch embedding)
+static int refresh_model(const CModel& m, const float* params, void* wcache, const uint8_t* only, void* stream) {
     GG_CHECK(params && wcache, "gg_clip_refresh_weights: null pointer");
     char* wc = (char*)wcache;
     hipStream_t st = (hipStream_t)stream;
@@ -552,12 +587,12 @@ static int refresh_weights(const GgClipCfg* cfg, const float* params, void* wcac
         }
         return gg_cast_transpose_f32(W, R, C, (bf16*)(wc + n) + r0 * C, C, (bf16*)(wc + t) + c0, ldt, st);
     };
-    if (!ch(m.patch_w)) {}
+    if (m.causal || !ch(m.patch_w)) {}
     else if (m.f16) hipLaunchKernelGGL(cast_pad_rows_kernel<f16>, dim3(grid1d((int64_t)D * m.Kpatch)), dim3(256), 0, st, P(m.patch_w), (f16*)(wc + m.wpatch), D, m.Kraw, m.Kpatch);
     else if (m.f32) hipLaunchKernelGGL(cast_pad_rows_kernel<float>, dim3(grid1d((int64_t)D * m.Kpatch)), dim3(256), 0, st, P(m.patch_w), (float*)(wc + m.wpatch), D, m.Kraw, m.Kpatch);
     else hipLaunchKernelGGL(cast_pad_rows_kernel<bf16>, dim3(grid1d((int64_t)D * m.Kpatch)), dim3(256), 0, st, P(m.patch_w), (bf16*)(wc + m.wpatch), D, m.Kraw, m.Kpatch);
     GG_LAUNCH_CHECK();
-    if (ch(m.patch_w)) GG_TRY(split3(m.wpatch, D, m.Kpatch, m.wpatch3));
+    if (!m.causal && ch(m.patch_w)) GG_TRY(split3(m.wpatch, D, m.Kpatch, m.wpatch3));
     for (auto& l : m.layers) {
         GG_TRY(put(l.q_w, D, D, l.wqkv, 0, l.wqkvT, 3 * D, 0));
         GG_TRY(put(l.k_w, D, D, l.wqkv, D, l.wqkvT, 3 * D, D));
@@ -700,4 +735,125 @@ extern "C" int gg_clip_backward(const GgClipCfg* cfg, int batch, const float* pa
         GG_LAUNCH_CHECK();
     }
     return 0;
+}
+
+// ================================================================== CLIP text tower (include/gg_clip_text.h): forward for frozen weights
+// transformers CLIPTextModel as pretrain_idun.py:205-300 runs it inside CLIPModel.forward: token + position embedding, the encoder layers above with the causal
+// attention, final_layer_norm, the row at the EOS position.  Inference schedule only: the residual stream and the layer temporaries recycle five regions.
+namespace {
+// tokens[b,t,:] = token_embedding[id[b,t]] + position_embedding[t]; a lane owns 4 consecutive channels (one 16-byte load of each table).  An id outside
+// [0, vocab) is clamped: the Python layer refuses such input, the kernel must not read outside the table either way.
+template <typename T>
+__global__ __launch_bounds__(256) void text_embed_kernel(const int32_t* __restrict__ ids, const float* __restrict__ tok, const float* __restrict__ pos,
+                                                         T* __restrict__ out, int64_t rows, int Tn, int D, int vocab) {
+    const int D4 = D / 4;
+    const int64_t total = rows * D4;
+    typedef T t4 __attribute__((ext_vector_type(4)));
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int dd = (int)(i % D4) * 4;
+        const int64_t bt = i / D4;
+        const int t = (int)(bt % Tn);
+        const int id = min(max(ids[bt], 0), vocab - 1);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(tok + (int64_t)id * D + dd) + *reinterpret_cast<const f32x4*>(pos + (int64_t)t * D + dd);
+        t4 w;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[j] = from_f<T>(v[j]);
+        *reinterpret_cast<t4*>(out + bt * D + dd) = w;
+    }
+}
+// pooled[b,:] = x[b, pos[b], :] (GATHER) / dx[b,t,:] = t == pos[b] ? dpooled[b,:] : 0 (the backward: every element of dx is written)
+template <bool GATHER>
+__global__ __launch_bounds__(256) void row_pick_kernel(const float* __restrict__ src, const int32_t* __restrict__ pos, float* __restrict__ dst, int B, int Tn, int C) {
+    const int C4 = C / 4;
+    const int64_t total = GATHER ? (int64_t)B * C4 : (int64_t)B * Tn * C4;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int dd = (int)(i % C4) * 4;
+        const int64_t r = i / C4;
+        if (GATHER) {
+            const int t = pos ? min(max(pos[r], 0), Tn - 1) : 0;
+            *reinterpret_cast<f32x4*>(dst + r * C + dd) = *reinterpret_cast<const f32x4*>(src + (r * Tn + t) * C + dd);
+        } else {
+            const int64_t b = r / Tn;
+            const int t = (int)(r % Tn), tp = pos ? min(max(pos[b], 0), Tn - 1) : 0;
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (t == tp) v = *reinterpret_cast<const f32x4*>(src + b * C + dd);
+            *reinterpret_cast<f32x4*>(dst + r * C + dd) = v;
+        }
+    }
+}
+struct TextPlan : CPlan { int64_t fin; };
+static void plan_text(const CModel& m, int B, TextPlan& L) {
+    const int D = m.cfg.hidden_size, I = m.cfg.intermediate_size;
+    const int64_t M = (int64_t)B * m.T, es = m.es;
+    int64_t off = 0;
+    auto al = [&](int64_t bytes) { int64_t o = off; off += gg_align(std::max<int64_t>(bytes, 1), 256); return o; };
+    L.s_x = al(M * D * es); L.s_a = al(M * D * es); L.s_qkv = al(M * 3 * D * es); L.s_o = al(M * D * es); L.s_h = al(M * I * es);
+    L.fin = al(M * D * 4);                                    // final_layer_norm's f32 rows when the caller does not take last_hidden
+    L.la.assign(m.cfg.num_layers, LayerA{});
+    L.xfinal = L.s_x;
+    L.total = off;
+}
+}  // namespace
+
+extern "C" int gg_row_gather_f32(const float* x, const int32_t* pos, float* pooled, int B, int T, int C, void* stream) {
+    GG_CHECK(x && pooled && B > 0 && T > 0 && C > 0 && (C & 3) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)pooled & 15) == 0, "gg_row_gather_f32: bad args (C %% 4, 16-byte alignment)");
+    GG_PROF(GG_CAT_MOVE, 0, 8.0 * B * C, stream);
+    hipLaunchKernelGGL(row_pick_kernel<true>, dim3(grid1d((int64_t)B * C / 4)), dim3(256), 0, (hipStream_t)stream, x, pos, pooled, B, T, C);
+    GG_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int gg_row_scatter_f32(const float* dpooled, const int32_t* pos, float* dx, int B, int T, int C, void* stream) {
+    GG_CHECK(dpooled && dx && B > 0 && T > 0 && C > 0 && (C & 3) == 0 && ((uintptr_t)dx & 15) == 0 && ((uintptr_t)dpooled & 15) == 0, "gg_row_scatter_f32: bad args (C %% 4, 16-byte alignment)");
+    GG_PROF(GG_CAT_MOVE, 0, 4.0 * B * T * C, stream);
+    hipLaunchKernelGGL(row_pick_kernel<false>, dim3(grid1d((int64_t)B * T * C / 4)), dim3(256), 0, (hipStream_t)stream, dpooled, pos, dx, B, T, C);
+    GG_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int gg_clip_text_num_tensors(const GgClipTextCfg* cfg) { CModel m; return build_text(cfg, 1, m) ? -1 : (int)m.t.size(); }
+extern "C" int gg_clip_text_tensor_info(const GgClipTextCfg* cfg, int i, char* name, int cap, int64_t* offset, int64_t* numel, int* ndim, int64_t* shape4) {
+    CModel m;
+    GG_TRY(build_text(cfg, 1, m));
+    GG_CHECK(i >= 0 && i < (int)m.t.size(), "gg_clip_text_tensor_info: index out of range");
+    if (name && cap > 0) snprintf(name, cap, "%s", m.t[i].name.c_str());
+    if (offset) *offset = m.t[i].offset;
+    if (numel) *numel = m.t[i].numel;
+    if (ndim) *ndim = m.t[i].ndim;
+    if (shape4) for (int j = 0; j < 4; ++j) shape4[j] = m.t[i].shape[j];
+    return 0;
+}
+extern "C" int64_t gg_clip_text_param_floats(const GgClipTextCfg* cfg) { CModel m; return build_text(cfg, 1, m) ? -1 : m.floats; }
+extern "C" int64_t gg_clip_text_wcache_bytes(const GgClipTextCfg* cfg) { CModel m; return build_text(cfg, 1, m) ? -1 : m.wc_bytes; }
+extern "C" int64_t gg_clip_text_workspace_bytes(const GgClipTextCfg* cfg, int batch, int tokens) {
+    CModel m;
+    if (build_text(cfg, tokens, m)) return -1;
+    if (batch <= 0) { gg_set_error("gg_clip_text_workspace_bytes: batch must be > 0"); return -1; }
+    TextPlan L; plan_text(m, batch, L);
+    return L.total;
+}
+extern "C" int gg_clip_text_refresh_weights(const GgClipTextCfg* cfg, const float* params, void* wcache, void* stream) {
+    CModel m;
+    GG_TRY(build_text(cfg, 1, m));
+    return refresh_model(m, params, wcache, nullptr, stream);
+}
+extern "C" int gg_clip_text_forward(const GgClipTextCfg* cfg, int batch, int tokens, const float* params, const void* wcache, const int32_t* input_ids,
+                                    const int32_t* eos_pos, void* workspace, float* last_hidden, float* pooled, void* stream) {
+    CModel m;
+    GG_TRY(build_text(cfg, tokens, m));
+    GG_CHECK(batch > 0 && params && wcache && input_ids && eos_pos && workspace && pooled, "gg_clip_text_forward: null pointer / bad batch");
+    GG_CHECK(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)wcache & 255) == 0, "gg_clip_text_forward: workspace / wcache must be 256-byte aligned");
+    GG_CHECK(((uintptr_t)pooled & 15) == 0 && ((uintptr_t)last_hidden & 15) == 0 && ((uintptr_t)params & 15) == 0, "gg_clip_text_forward: params / last_hidden / pooled must be 16-byte aligned");
+    TextPlan L; plan_text(m, batch, L);
+    Exec e{&m, &L, batch, (hipStream_t)stream, params, (const char*)wcache, (char*)workspace, nullptr, nullptr};
+    const int D = m.cfg.hidden_size, T = m.T;
+    const int64_t M = (int64_t)batch * T;
+    {      // (a scope of its own: the profiler times a scope, and the launches below carry their own)
+    GG_PROF(GG_CAT_MOVE, 0, (4.0 + m.es) * M * D, stream);
+    if (m.f32) hipLaunchKernelGGL(text_embed_kernel<float>, dim3(grid1d(M * D / 4)), dim3(256), 0, e.st, input_ids, e.P(m.tok_emb), e.P(m.pos), (float*)e.A(L.s_x), M, T, D, m.vocab);
+    else hipLaunchKernelGGL(text_embed_kernel<bf16>, dim3(grid1d(M * D / 4)), dim3(256), 0, e.st, input_ids, e.P(m.tok_emb), e.P(m.pos), (bf16*)e.A(L.s_x), M, T, D, m.vocab);
+    GG_LAUNCH_CHECK();
+    }
+    for (int i = 0; i < m.cfg.num_layers; ++i) GG_TRY(layer_fwd(e, i, L.s_x, L.s_x, false));      // in place, as the vision tower's inference layers
+    float* fin = last_hidden ? last_hidden : e.F(L.fin);
+    GG_TRY(gg_layernorm_fwd(e.A(L.s_x), m.f32, e.P(m.fin_g), e.P(m.fin_b), M, D, m.cfg.ln_eps, fin, 1, nullptr, nullptr, e.st));
+    return gg_row_gather_f32(fin, eos_pos, pooled, batch, T, D, e.st);
 }

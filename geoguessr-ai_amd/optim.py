@@ -31,6 +31,15 @@ def cosine_warm_restarts_lr(epoch: float, base_lr: float, T_0: int = 10, T_mult:
     return eta_min + (base_lr - eta_min) * (1 + math.cos(math.pi * t_cur / t_i)) / 2
 
 
+def linear_warmup_lr(step: int, total: int, warmup_ratio: float, base_lr: float) -> float:
+    """Closed form of ``transformers.get_linear_schedule_with_warmup`` as HF's Trainer builds it from ``warmup_ratio`` (``PRETRAIN_ARGS``, config.py:105-136:
+    20 % warm-up): ``ceil(total * warmup_ratio)`` warm-up steps rising linearly from 0, then a linear decay to 0 at ``total``.  ``step`` = optimizer steps taken."""
+    warm = math.ceil(total * warmup_ratio)
+    if step < warm:
+        return base_lr * step / max(1, warm)
+    return base_lr * max(0.0, (total - step) / max(1, total - warm))
+
+
 class _NativeWork:
     """Work handle of the buckets sent through the C-ABI communicator (``async_op=True``): ``wait()`` orders the current compute stream
     behind the communicator's stream, the same contract as a ``torch.distributed`` work object on the GPU."""
@@ -62,6 +71,26 @@ class AdamW:
         self.loose: List[torch.nn.Parameter] = [p for p in model.parameters() if p.requires_grad and id(p) not in flat_ids]
         self.state = {}
         self._inflight, self._covered = {}, {}
+        self._clip_coef = 1.0               # set by clip_grad_norm_, folded into the next step()'s grad_scale
+
+    def clip_grad_norm_(self, max_norm: float) -> float:
+        """``torch.nn.utils.clip_grad_norm_(parameters, max_norm)`` (HF Trainer's ``max_grad_norm``) over ``grad_buffers()``: the 2-norm comes from the deterministic
+        two-stage sum of squares ``gg_grad_sq_norm``; the coefficient ``min(1, max_norm / (norm + 1e-6))`` is not applied to the gradients in memory but folded
+        into the next ``step()``'s ``grad_scale``.  Returns the norm (before clipping)."""
+        from . import _lib as L
+        bufs = [b for b in self.grad_buffers() if b is not None and b.numel() > 0]
+        if not bufs:
+            self._clip_coef = 1.0
+            return 0.0
+        dev = bufs[0].device
+        acc = torch.zeros((), dtype=torch.float64, device=dev)
+        scratch = torch.empty((max(L.lib().gg_grad_sq_norm_scratch_doubles(b.numel()) for b in bufs),), dtype=torch.float64, device=dev)
+        for b in bufs:
+            b = b.contiguous().view(-1)
+            L.check(L.lib().gg_grad_sq_norm(L.ptr(b, torch.float32, "gradient"), b.numel(), L.ptr(scratch), L.ptr(acc), 1, L.stream()), "gg_grad_sq_norm")
+        norm = math.sqrt(float(acc))
+        self._clip_coef = min(1.0, float(max_norm) / (norm + 1e-6))
+        return norm
 
     def _st(self, key, like):
         if key not in self.state or self.state[key][0].device != like.device:
@@ -72,8 +101,10 @@ class AdamW:
         """Every gradient tensor an all-reduce must cover (flat trainable ranges + loose parameter grads)."""
         out = []
         for bb in self.backbones:
-            fg = bb.flat_grads()
-            out += [fg[s:e] for s, e in bb.trainable_ranges()]
+            ranges = bb.trainable_ranges()
+            if ranges:                                  # (a frozen tower gets no flat gradient buffer allocated on its behalf)
+                fg = bb.flat_grads()
+                out += [fg[s:e] for s, e in ranges]
         out += [p.grad for p in self.loose if p.grad is not None]
         return out
 
@@ -210,13 +241,17 @@ class AdamW:
             grad_scale = 1.0
             if dist.is_available() and dist.is_initialized():
                 grad_scale = 1.0 / dist.get_world_size()
+        grad_scale, self._clip_coef = grad_scale * self._clip_coef, 1.0
         self.step_count += 1
         kw = dict(step=self.step_count, lr=g["lr"], beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"],
                   weight_decay=g["weight_decay"], grad_scale=grad_scale)
         for i, bb in enumerate(self.backbones):
+            ranges = bb.trainable_ranges()
+            if not ranges:                              # a wholly frozen tower (the CLIP text tower always is): no moments, no gradient buffer, nothing to refresh
+                continue
             fp, fg = bb.flat_params, bb.flat_grads()
             m, v = self._st(("bb", i), fp)
-            for s, e in bb.trainable_ranges():
+            for s, e in ranges:
                 ops.adamw_step(fp[s:e], fg[s:e], m[s:e], v[s:e], **kw)
             bb.mark_params_dirty(only=bb.trainable_mask())          # only these tensors' cached forms need rebuilding
         for p in self.loose:
