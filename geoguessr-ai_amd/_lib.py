@@ -278,6 +278,18 @@ TEXT_SIGNATURES = {
 }
 TEXT_SYMBOLS = list(TEXT_SIGNATURES)
 
+# every exported symbol of include/gg_clip_text_train.h (training the text tower), bound from the same libgg.so
+TEXT_TRAIN_SIGNATURES = {
+    "gg_attention_causal_bwd": (_I, [C.POINTER(AttnArgs), _I, _P]),
+    "gg_embedding_scatter_add_scratch_bytes": (_L, [_L]),
+    "gg_embedding_scatter_add_f32": (_I, [_P, _P, _P, _L, _I, _I, _P, _P]),
+    "gg_clip_text_train_workspace_bytes": (_L, [C.POINTER(ClipTextCfg), _I, _I, C.c_char_p]),
+    "gg_clip_text_first_trained_layer": (_I, [C.POINTER(ClipTextCfg), C.c_char_p]),
+    "gg_clip_text_forward_train": (_I, [C.POINTER(ClipTextCfg), _I, _I, _P, _P, _P, _P, _P, _P, _P, C.c_char_p, _P]),
+    "gg_clip_text_backward": (_I, [C.POINTER(ClipTextCfg), _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, C.c_char_p, _P]),
+}
+TEXT_TRAIN_SYMBOLS = list(TEXT_TRAIN_SIGNATURES)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -286,7 +298,7 @@ def lib() -> C.CDLL:
             raise GgError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the library lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -333,6 +345,7 @@ def source_hash() -> str:
     files = sorted(os.path.join(root, "csrc", f) for f in os.listdir(os.path.join(root, "csrc")) if f.endswith((".hip", ".h", ".cpp", "Makefile")))
     files.append(os.path.join(os.path.dirname(root), "include", "gg.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_clip_text.h"))
+    files.append(os.path.join(os.path.dirname(root), "include", "gg_clip_text_train.h"))
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

@@ -18,6 +18,7 @@
 #include "common.h"
 #include "../../include/gg.h"
 #include "../../include/gg_clip_text.h"
+#include "../../include/gg_clip_text_train.h"
 
 namespace {
 
@@ -928,8 +929,13 @@ __global__ __launch_bounds__(RES ? 1024 : 256) void flash_bwd_dkv_kernel(FlashPa
 // key strip is worked off after the main loop by all of them together: wave w forms P / dS of (tile w, last strip) and the dQ product, leaves both
 // tiles in LDS, and after a barrier 2 D / 16 waves (one per accumulator tile, one per SIMD) contract them with dO / Q into dV / dK of the strip.
 // LDS: 3 window images + bias table (+ gradient bins) + row scalars + two 1.25 KB slots per tile = 128 KB for 14 x 14 windows, 38 KB for 7 x 7.
-template <typename T, int D, bool DBIAS, int NT>
+//
+// CAUSAL (gg_attention_causal_bwd, bf16 storage, linear tokens, a wave per key strip and no tail): key strip s is seen by the query tiles s.. only -- a wave
+// sits out the steps whose tile lies below its strip (wave-uniform; the step's barrier is kept), and on the diagonal (tile == strip) a score with key > query
+// becomes -inf before the exponent: P and dS are exact zeros there.
+template <typename T, int D, bool DBIAS, int NT, bool CAUSAL = false>
 __global__ __launch_bounds__(NT ? (NT < 4 ? 256 : 64 * NT) : 1024) void flash_bwd_fused_kernel(FlashParams p) {
+    static_assert(!(CAUSAL && DBIAS), "the causal form has no bias");
     constexpr int RS = D + 4, DC = D / 16, TS = 20, ES = (int)sizeof(T);
     extern __shared__ __attribute__((aligned(16))) float fsm[];
     const int R = NT ? 16 * NT : p.npad;                           // NT = tiles of the window as a compile-time constant (0: any): LDS offsets become immediates
@@ -995,7 +1001,7 @@ __global__ __launch_bounds__(NT ? (NT < 4 ? 256 : 64 * NT) : 1024) void flash_bw
         klin = has_bias ? fl_lin4(p, min(ki, p.N - 1)) - 4 * (p.ws - 1) * 2 * p.ws : 0;
     };
     // S, dP, P, dS of (query tile, loaded key strip); lane holds [q = 16 tile + 4 lg + r][key = lr].  dS goes to `gslot` ([q][TS]), P to `pslot` if given
-    auto scores = [&](int tile, f32x4& pr, f32x4& ds, float* gslot, float* pslot) {
+    auto scores = [&](int tile, f32x4& pr, f32x4& ds, float* gslot, float* pslot, int strip = -1) {
         const float* Qt = Qs + tile * 16 * RS;
         const float* Ot = Os + tile * 16 * RS;
         const int q4 = tile * 16 + 4 * lg;
@@ -1020,7 +1026,9 @@ __global__ __launch_bounds__(NT ? (NT < 4 ? 256 : 64 * NT) : 1024) void flash_bw
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float e = __builtin_amdgcn_exp2f(fmaf(st[r], sc2, bia[r] + nl4[r]));     // -inf for padded queries -> 0
+            float x = fmaf(st[r], sc2, bia[r] + nl4[r]);                      // -inf for padded queries -> 0
+            if constexpr (CAUSAL) { if (tile == strip && strip * 16 + lr > q4 + r) x = -INFINITY; }
+            const float e = __builtin_amdgcn_exp2f(x);
             const float g = e * dp[r];
             pr[r] = e;
             ds[r] = g;                                                         // the softmax scale is applied once, to dK and dQ
@@ -1052,8 +1060,9 @@ __global__ __launch_bounds__(NT ? (NT < 4 ? 256 : 64 * NT) : 1024) void flash_bw
 
     int tile = wave;
     for (int t = 0; t < ntiles; ++t) {
+        if (!CAUSAL || tile >= wave) {
         f32x4 pr, ds;
-        scores(tile, pr, ds, slot, nullptr);
+        scores(tile, pr, ds, slot, nullptr, wave);
         const float* Qt = Qs + tile * 16 * RS;
         const float* Ot = Os + tile * 16 * RS;
 #pragma unroll
@@ -1066,6 +1075,7 @@ __global__ __launch_bounds__(NT ? (NT < 4 ? 256 : 64 * NT) : 1024) void flash_bw
                 dk[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(qf, ds[r], dk[c], 0, 0, 0);
             }
         dq_update(tile, slot);
+        }
         __syncthreads();                                                       // the tile's next writer (the wave one strip down) reads after this
         tile = tile + 1 == ntiles ? 0 : tile + 1;
     }
@@ -1074,7 +1084,7 @@ __global__ __launch_bounds__(NT ? (NT < 4 ? 256 : 64 * NT) : 1024) void flash_bw
         Bld<T>::store(rsDQKV, kok ? krow + (p.k_off + hc + 16 * c + 4 * lg) * ES : FL_OOB, dk[c] * p.scale);
         Bld<T>::store(rsDQKV, kok ? krow + (p.v_off + hc + 16 * c + 4 * lg) * ES : FL_OOB, dv[c]);
     }
-    if (NW < ntiles) {
+    if (!CAUSAL && NW < ntiles) {
         // cooperative tail: key strip ntiles - 1.  Phase 1: wave w forms P / dS of (tile w [+ NW], tail strip), leaves them in the tile's slots and
         // adds its dQ product (tile w is this wave's alone in this phase)
         const int ts = ntiles - 1;
@@ -1276,6 +1286,41 @@ extern "C" int gg_attention_causal_fwd(const GgAttnArgs* a, int dtype, void* str
     GG_PROF(GG_CAT_ATTN, 2.0 * a->num_windows * a->num_heads * (double)p.N * p.N * 64, (dtype == 0 ? 8.0 : 16.0) * a->num_windows * a->num_heads * (double)p.N * 64, stream);
     if (dtype == 0) hipLaunchKernelGGL((flash_fwd_kernel<bf16, 64, false, true>), grid, dim3(256), flash_lds_fwd(p, 64, 64), (hipStream_t)stream, p);
     else hipLaunchKernelGGL((flash64_split_q_kernel<3, false, true>), grid, dim3(256), sp64_lds(3, false), (hipStream_t)stream, p);
+    GG_LAUNCH_CHECK();
+    return 0;
+}
+// Causal backward (include/gg_clip_text_train.h): the backward of gg_attention_causal_fwd on the same geometry.  f32 storage (dtype 1 and 3): the two split-product
+// passes of dtype 3 (dQ; dK, dV), each recomputing P from lse; bf16 storage: the single-pass kernel (at most 80 padded tokens: five key strips, one wave each).
+// Neither reads ds_scratch, neither uses an atomic: two runs give the same bits.  Every refusal comes before the first launch.
+extern "C" int gg_attention_causal_bwd(const GgAttnArgs* a, int dtype, void* stream) {
+    GG_CHECK(a, "gg_attention_causal_bwd: null args");
+    GG_CHECK(dtype == 0 || dtype == 1 || dtype == 3, "gg_attention_causal_bwd: dtype must be 0 (bf16), 1 (f32) or 3 (f32, split products); got %d", dtype);
+    GG_CHECK(a->head_dim == 64 && a->window_size == 0 && !a->bias && !a->bias_table && !a->dbias,
+             "gg_attention_causal_bwd: head dim 64, linear tokens, no bias (got head_dim %d, window_size %d)", a->head_dim, a->window_size);
+    GG_CHECK(a->tokens_per_window <= GG_CLIP_TEXT_MAX_POSITIONS, "gg_attention_causal_bwd: %d tokens exceed the position table (%d)", a->tokens_per_window,
+             GG_CLIP_TEXT_MAX_POSITIONS);
+    FlashParams p;
+    GG_TRY(flash_fill(p, a, dtype == 0 ? 0 : 3, "gg_attention_causal_bwd"));
+    GG_CHECK(a->dout && a->dqkv && (a->lddo & 3) == 0 && ((uintptr_t)a->dout & 15) == 0 && ((uintptr_t)a->dqkv & 15) == 0 && a->lddo >= (int64_t)a->num_heads * 64,
+             "gg_attention_causal_bwd: bad dout/dqkv");
+    GG_CHECK(a->lse && a->out && (a->ldo & 3) == 0 && ((uintptr_t)a->out & 15) == 0 && a->ldo >= (int64_t)a->num_heads * 64, "gg_attention_causal_bwd: needs the forward's lse and out");
+    GG_CHECK(a->ld >= 64 && a->head_stride >= 0, "gg_attention_causal_bwd: bad qkv pitch");
+    hipStream_t s = (hipStream_t)stream;
+    // (declared work: the lower triangle, half of the 10 N^2 D flops of the full backward)
+    GG_PROF(GG_CAT_ATTN, 5.0 * a->num_windows * a->num_heads * (double)p.N * p.N * 64, (dtype == 0 ? 16.0 : 32.0) * a->num_windows * a->num_heads * (double)p.N * 64, stream);
+    if (dtype != 0) {
+        const dim3 g3((unsigned)(a->num_windows * a->num_heads * p.ntile));
+        hipLaunchKernelGGL((flash64_split_q_kernel<3, true, true>), g3, dim3(256), sp64_lds(3, false), s, p);
+        hipLaunchKernelGGL((flash64_split_dkv_kernel<3, true>), g3, dim3(256), sp64_lds(3, true), s, p);
+        GG_LAUNCH_CHECK();
+        return 0;
+    }
+    static_assert(GG_CLIP_TEXT_MAX_POSITIONS <= 256, "the single-pass kernel holds a sequence of at most 256 tokens");
+    const size_t lds = flash_lds_fused(p, 64, false);
+    GG_CHECK(lds <= 160 * 1024, "gg_attention_causal_bwd: %zu bytes of LDS", lds);
+    void (*kern)(FlashParams) = flash_bwd_fused_kernel<bf16, 64, false, 0, true>;
+    if (lds > 64 * 1024) GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(kern)));
+    hipLaunchKernelGGL(kern, dim3((unsigned)(a->num_windows * a->num_heads)), dim3(64 * (p.npad / 16)), lds, s, p);
     GG_LAUNCH_CHECK();
     return 0;
 }

@@ -37,11 +37,11 @@ template <int NPL> __device__ __forceinline__ void sp64_commit(const Sp64Regs& r
 
 // ------------------------------------------------------------------------------------------- forward / dQ pass
 // DQ = false: out, lse.  DQ = true: dQ of the tile's queries (reads out, dout, lse).
-// CAUSAL (forward of the CLIP text tower, gg_attention_causal_fwd): query t sees keys 0..t.  Key tiles above the query tile are not visited (the bound is the
-// workgroup's own tile: the barriers stay uniform), the diagonal tile's scores above the diagonal become -inf before the running maximum -- their P is an exact 0.
+// CAUSAL (the CLIP text tower, gg_attention_causal_fwd / _bwd): query t sees keys 0..t.  Key tiles above the query tile are not visited (the bound is the
+// workgroup's own tile: the barriers stay uniform), the diagonal tile's scores above the diagonal become -inf before the running maximum / the exponent -- their
+// P is an exact 0, and so is their dS.  The dQ pass also skips, on the diagonal tile, the 16-key sub-tiles wholly above the wave's own strip (wave-uniform).
 template <int NPL, bool DQ, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void flash64_split_q_kernel(FlashParams p) {
-    static_assert(!(CAUSAL && DQ), "the causal form is forward only");
     typedef Sp8T<NPL> Sp8;
     extern __shared__ __attribute__((aligned(16))) float fsm[];
     bf16* Kp = reinterpret_cast<bf16*>(fsm);
@@ -109,7 +109,8 @@ __global__ __launch_bounds__(256) void flash64_split_q_kernel(FlashParams p) {
             sp64_issue(p, rsQKV, t0 + 64, ldb, (p.v_off + hc) * 4, vr);
         }
         if (!live) continue;
-        const int nkt = min(4, (p.N - t0 + 15) >> 4);              // 16-key sub-tiles of this tile that hold a key
+        int nkt = min(4, (p.N - t0 + 15) >> 4);                    // 16-key sub-tiles of this tile that hold a key
+        if constexpr (CAUSAL && DQ) { if (t == tile) nkt = min(nkt, wave + 1); }      // (sub-tiles above the strip's diagonal: every P is 0)
         // S^T[key][q]: lane holds keys t0 + 16 kt + 4 lg + r of query lr; padded keys are masked through the initial value
         f32x4 st[4];
         float tmax = -INFINITY;
@@ -195,7 +196,9 @@ __global__ __launch_bounds__(256) void flash64_split_q_kernel(FlashParams p) {
 // One workgroup per (image, head, 64-key tile), a wave per 16-key strip (K / V rows split once in registers); Q and dO walk through LDS in tiles of 64 queries
 // with their row scalars (-lse in the exp2 domain, -delta).  Unswapped scores: a lane owns a key, P / dS of two query sub-tiles side by side are the B operand
 // of the products over the 32 queries.
-template <int NPL>
+// CAUSAL: key k is seen by queries k.. -- query tiles below the key tile are not visited (workgroup-uniform bound), on the diagonal tile the pairs of 16-query
+// sub-tiles wholly below the wave's key strip are skipped (wave-uniform, no barrier inside) and a score with key > query becomes -inf before the exponent.
+template <int NPL, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void flash64_split_dkv_kernel(FlashParams p) {
     typedef Sp8T<NPL> Sp8;
     extern __shared__ __attribute__((aligned(16))) float fsm[];
@@ -227,7 +230,8 @@ __global__ __launch_bounds__(256) void flash64_split_dkv_kernel(FlashParams p) {
             lsev[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsLSE, (tok < p.N && (id & 7) == 0) ? (tok * p.nh + h) * 4 : FL_OOB, 0, 0));
         }
     };
-    issue(0);
+    const int tfirst = CAUSAL ? tile : 0;                          // query tiles this workgroup walks: tfirst .. ntile - 1
+    issue(tfirst * 64);
     const int ki = tile * 64 + wave * 16 + lr;
     const bool kok = ki < p.N;
     const bool live = tile * 64 + wave * 16 < p.N;
@@ -244,7 +248,7 @@ __global__ __launch_bounds__(256) void flash64_split_dkv_kernel(FlashParams p) {
     f32x4 dk[4], dv[4];                                            // dK^T / dV^T [d = 16 c + 4 lg + r][key = lr]
 #pragma unroll
     for (int c = 0; c < 4; ++c) dk[c] = dv[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int t = 0; t < p.ntile; ++t) {
+    for (int t = tfirst; t < p.ntile; ++t) {
         const int t0 = t * 64;
         __syncthreads();
         sp64_commit<NPL>(qr, Qp);
@@ -273,6 +277,7 @@ __global__ __launch_bounds__(256) void flash64_split_dkv_kernel(FlashParams p) {
 #pragma unroll
         for (int qt = 0; qt < 4; qt += 2) {
             if (qt >= nqt) break;
+            if constexpr (CAUSAL) { if (t == tile && qt + 2 <= wave) continue; }      // every query of the pair precedes the strip's first key
             f32x4 pr[2], ds[2];                                    // lane holds [q = t0 + 16 (qt + a) + 4 lg + r][key = lr]
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
@@ -286,7 +291,9 @@ __global__ __launch_bounds__(256) void flash64_split_dkv_kernel(FlashParams p) {
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float e = __builtin_amdgcn_exp2f(fmaf(s[r], sc2, nl4[r]));
+                    float x = fmaf(s[r], sc2, nl4[r]);
+                    if constexpr (CAUSAL) { if (t == tile && ki > t0 + q0 + 4 * lg + r) x = -INFINITY; }
+                    const float e = __builtin_amdgcn_exp2f(x);
                     pr[a][r] = e;
                     ds[a][r] = e * dp[r];                          // (a padded key's column is finite; its dK / dV rows are dropped by the range check)
                 }

@@ -29,6 +29,7 @@
 #include "common.h"
 #include "../../include/gg.h"
 #include "../../include/gg_clip_text.h"
+#include "../../include/gg_clip_text_train.h"
 
 namespace {
 struct TInfo { std::string name; int64_t offset, numel; int ndim; int64_t shape[4]; };
@@ -289,17 +290,21 @@ struct Train {
     bool embed;      // any embedding-side tensor trainable: the backward pass runs through every layer and the patch / position embeddings
     int l0;          // first layer whose activations are kept (num_layers: none)
 };
+static int first_trained_layer(const CModel& m, const uint8_t* mask) {
+    auto on = [&](int t) { return mask == nullptr || mask[t] != 0; };
+    for (int i = 0; i < m.cfg.num_layers; ++i) {
+        const LayerP& l = m.layers[i];
+        const int ids[] = {l.q_w, l.q_b, l.k_w, l.k_b, l.v_w, l.v_b, l.o_w, l.o_b, l.ln1_g, l.ln1_b, l.fc1_w, l.fc1_b, l.fc2_w, l.fc2_b, l.ln2_g, l.ln2_b};
+        for (int t : ids) if (on(t)) return i;
+    }
+    return m.cfg.num_layers;
+}
 static Train train_of(const CModel& m, int training, const uint8_t* mask) {
     Train tr{false, m.cfg.num_layers};
     if (!training) return tr;
     auto on = [&](int t) { return mask == nullptr || mask[t] != 0; };
     tr.embed = on(m.cls) || on(m.patch_w) || on(m.pos) || on(m.pre_g) || on(m.pre_b);
-    if (tr.embed) { tr.l0 = 0; return tr; }
-    for (int i = 0; i < m.cfg.num_layers; ++i) {
-        const LayerP& l = m.layers[i];
-        const int ids[] = {l.q_w, l.q_b, l.k_w, l.k_b, l.v_w, l.v_b, l.o_w, l.o_b, l.ln1_g, l.ln1_b, l.fc1_w, l.fc1_b, l.fc2_w, l.fc2_b, l.ln2_g, l.ln2_b};
-        for (int t : ids) if (on(t)) { tr.l0 = i; return tr; }
-    }
+    tr.l0 = tr.embed ? 0 : first_trained_layer(m, mask);
     return tr;
 }
 
@@ -354,7 +359,7 @@ static void plan(const CModel& m, int B, const Train& tr, bool training, CPlan& 
             return (int64_t)(m.split ? gg_gemm_tn_split3_splits((int)Mm, N, K) : m.f32 ? gg_gemm_tn_f32_splits((int)Mm, N, K) : gg_gemm_tn_splits((int)Mm, N, K)) * N * K;
         };
         int64_t sk = std::max(std::max(splits(M, D, I), splits(M, I, D)), splits(M, D, D));
-        if (tr.embed) sk = std::max(sk, splits(Mp, D, m.Kpatch));
+        if (tr.embed && !m.causal) sk = std::max(sk, splits(Mp, D, m.Kpatch));
         L.splitk = al(sk * 4);
         L.colsum = al(std::max(gg_colsum_scratch_floats((int)M, I), gg_colsum_scratch_floats((int)M, D)) * 4);
         L.lnscr = al(gg_layernorm_bwd_scratch_floats(M, D) * 4);
@@ -364,7 +369,8 @@ static void plan(const CModel& m, int B, const Train& tr, bool training, CPlan& 
         const int64_t dsb = gg_attention_flash_ds_scratch_floats(B, m.cfg.num_heads, m.T) * 4;
         static const bool ds_off = gg_dev_env("GG_ATTN_NO_DS_SCRATCH") != nullptr;
         // (the fp32_split mode's attention backward recomputes P in both passes: no hand-off at any length)
-        const bool ds = m.split ? false : ds_force >= 0 ? ds_force != 0
+        // (nor does the text tower's causal backward, at most 77 tokens, read one)
+        const bool ds = m.split || m.causal ? false : ds_force >= 0 ? ds_force != 0
                                       : !ds_off && !gg_attention_flash_single_pass(m.T, D / m.cfg.num_heads, 0, 0) && dsb <= ((int64_t)4 << 30) && dsb <= off / 8;
         if (ds) L.attn_ds = al(dsb);
     }
@@ -469,7 +475,7 @@ static int layer_fwd(const Exec& e, int i, int64_t cur, int64_t next, bool sv) {
     GG_TRY(e.gemm(e.A(A1), D, e.W(l.wqkv, l.wqkv3), D, e.A(QKV), 3 * D, M, 3 * D, D, (const float*)e.W(l.bqkv)));
     GgAttnArgs at;
     e.attn_args(at, e.A(QKV), e.A(O), sv ? e.F(a.lse) : nullptr);
-    if (m.causal) GG_TRY(gg_attention_causal_fwd(&at, m.split ? 3 : m.f32 ? 1 : 0, e.st));      // the text tower (forward only: sv is never set)
+    if (m.causal) GG_TRY(gg_attention_causal_fwd(&at, m.split ? 3 : m.f32 ? 1 : 0, e.st));      // the text tower
     else if (m.split) GG_TRY(gg_attention_flash_fwd(&at, 3, e.st));      // split products at every token count
     else if (m.f16) GG_TRY(gg_attention_fwd_f16(&at, e.st));      // fp16 MFMA for towers of at most 256 tokens (ViT-B/32: 50); beyond: fp16 storage, f32 arithmetic
     else if (m.f32 || sv || T > 256) GG_TRY(gg_attention_flash_fwd(&at, m.f32 ? 1 : 0, e.st));
@@ -477,8 +483,60 @@ static int layer_fwd(const Exec& e, int i, int64_t cur, int64_t next, bool sv) {
     // x_mid = x + out_proj(o)   (in place when nothing is kept: each element is read then written by the same lane)
     GG_TRY(e.gemm(e.A(O), D, e.W(l.wo, l.wo3), D, e.A(XMID), D, M, D, D, e.P(l.o_b), 0, nullptr, e.A(cur)));
     GG_TRY(e.ln_fwd(e.A(XMID), l.ln2_g, l.ln2_b, M, e.A(A2), sv ? e.F(a.mean2) : nullptr, sv ? e.F(a.rstd2) : nullptr));
+    if (m.causal && !m.f32 && sv) {
+        // bf16 text tower, kept layer: the bf16 GEMM's pre-activation epilogue applies QuickGELU to the ROUNDED pre-activation, the inference epilogue to the f32
+        // accumulator.  The training forward must give the inference forward's bits, so fc1 runs the inference epilogue, and a second, linear pass leaves the copy
+        GG_TRY(e.gemm(e.A(A2), D, e.W(l.w1, l.w13), D, e.A(H), I, M, I, D, e.P(l.fc1_b), GG_ACT_CODE_QUICK_GELU, nullptr));
+        GG_TRY(e.gemm(e.A(A2), D, e.W(l.w1, l.w13), D, e.A(a.pre), I, M, I, D, e.P(l.fc1_b)));
+    } else
     GG_TRY(e.gemm(e.A(A2), D, e.W(l.w1, l.w13), D, e.A(H), I, M, I, D, e.P(l.fc1_b), GG_ACT_CODE_QUICK_GELU, sv ? e.A(a.pre) : nullptr));
     if (next >= 0) GG_TRY(e.gemm(e.A(H), I, e.W(l.w2, l.w23), I, e.A(next), D, M, D, I, e.P(l.fc2_b), 0, nullptr, e.A(XMID)));
+    return 0;
+}
+
+// The backward of the encoder layers nl - 1 .. l0 (gg_clip_backward and gg_clip_text_backward both come through here).  In: `dx` holds the gradient of the top
+// layer's output; out: `dx` names the region with the gradient of layer l0's input (dx / other swap between L.g_x0 and L.g_x1).  The towers differ in the
+// attention backward only (causal for the text tower).
+static int layers_bwd(const Exec& e, int l0, bool top_in_region, int64_t& dx, int64_t& other) {
+    const CModel& m = *e.m; const CPlan& L = *e.L;
+    const int D = m.cfg.hidden_size, I = m.cfg.intermediate_size, nl = m.cfg.num_layers;
+    const int64_t M = (int64_t)e.B * m.T;
+    for (int i = nl - 1; i >= l0; --i) {
+        const LayerP& l = m.layers[i];
+        const LayerA& a = L.la[i];
+        // activation recompute: the layer's tensors are re-formed in the segment region from its kept input (the top layer's are still the forward's in the first
+        // backward after it)
+        if (L.rc && (i < nl - 1 || !top_in_region)) GG_TRY(layer_fwd(e, i, a.xin, -1, true));
+        // ---- MLP: x_out = x_mid + fc2(quick_gelu(fc1(LN2(x_mid))))
+        GG_TRY(e.wgrad(l.fc2_w, e.A(dx), D, e.A(a.h), I, M, D, I));
+        GG_TRY(e.bgrad(l.fc2_b, e.A(dx), D, M, D));
+        GG_TRY(e.gemm(e.A(dx), D, e.W(l.w2T, l.w2T3), D, e.A(L.g_h), I, M, I, D, nullptr, 0, nullptr, nullptr, e.A(a.pre), GG_ACT_CODE_QUICK_GELU));   // d pre
+        GG_TRY(e.wgrad(l.fc1_w, e.A(L.g_h), I, e.A(a.a2), D, M, I, D));
+        GG_TRY(e.bgrad(l.fc1_b, e.A(L.g_h), I, M, I));
+        GG_TRY(e.gemm(e.A(L.g_h), I, e.W(l.w1T, l.w1T3), I, e.A(L.g_a), D, M, D, I, nullptr));                                                        // d LN2 out
+        GG_TRY(e.ln_bwd(e.A(L.g_a), e.A(a.xmid), e.F(a.mean2), e.F(a.rstd2), l.ln2_g, l.ln2_b, M, e.A(dx), e.A(other)));                       // d x_mid
+        std::swap(dx, other);
+        // ---- attention: x_mid = x_in + out_proj(attn(qkv(LN1(x_in))))
+        GG_TRY(e.wgrad(l.o_w, e.A(dx), D, e.A(a.o), D, M, D, D));
+        GG_TRY(e.bgrad(l.o_b, e.A(dx), D, M, D));
+        GG_TRY(e.gemm(e.A(dx), D, e.W(l.woT, l.woT3), D, e.A(L.g_o), D, M, D, D, nullptr));                                                            // d o
+        GgAttnArgs at;
+        e.attn_args(at, e.A(a.qkv), e.A(a.o), e.F(a.lse));
+        at.dout = e.A(L.g_o); at.lddo = D; at.dqkv = e.A(L.g_qkv);
+        if (L.attn_ds >= 0) at.ds_scratch = e.F(L.attn_ds);
+        if (m.causal) GG_TRY(gg_attention_causal_bwd(&at, m.split ? 3 : m.f32 ? 1 : 0, e.st));      // the text tower
+        else GG_TRY(gg_attention_flash_bwd(&at, m.split ? 3 : m.f32 ? 1 : 0, e.st));
+        const char* dq = (const char*)e.A(L.g_qkv);
+        GG_TRY(e.wgrad(l.q_w, dq, 3 * D, e.A(a.a1), D, M, D, D));
+        GG_TRY(e.wgrad(l.k_w, dq + (int64_t)D * m.es, 3 * D, e.A(a.a1), D, M, D, D));
+        GG_TRY(e.wgrad(l.v_w, dq + (int64_t)2 * D * m.es, 3 * D, e.A(a.a1), D, M, D, D));
+        GG_TRY(e.bgrad(l.q_b, dq, 3 * D, M, D));
+        GG_TRY(e.bgrad(l.k_b, dq + (int64_t)D * m.es, 3 * D, M, D));
+        GG_TRY(e.bgrad(l.v_b, dq + (int64_t)2 * D * m.es, 3 * D, M, D));
+        GG_TRY(e.gemm(e.A(L.g_qkv), 3 * D, e.W(l.wqkvT, l.wqkvT3), 3 * D, e.A(L.g_a), D, M, D, 3 * D, nullptr));                                          // d LN1 out
+        GG_TRY(e.ln_bwd(e.A(L.g_a), e.A(a.xin), e.F(a.mean1), e.F(a.rstd1), l.ln1_g, l.ln1_b, M, e.A(dx), e.A(other)));                         // d x_in
+        std::swap(dx, other);
+    }
     return 0;
 }
 
@@ -680,41 +738,7 @@ extern "C" int gg_clip_backward(const GgClipCfg* cfg, int batch, const float* pa
     else hipLaunchKernelGGL(pool_bwd_kernel<bf16>, dim3(grid1d(M * D)), dim3(256), 0, e.st, d_out, d_last_hidden, (bf16*)e.A(L.g_x0), B, T, D);
     GG_LAUNCH_CHECK();
     int64_t dx = L.g_x0, other = L.g_x1;
-    for (int i = nl - 1; i >= tr.l0; --i) {
-        const LayerP& l = m.layers[i];
-        const LayerA& a = L.la[i];
-        // activation recompute: the layer's tensors are re-formed in the segment region from its kept input (the top layer's are still the forward's in the first
-        // backward after it)
-        if (L.rc && (i < nl - 1 || !top_in_region)) GG_TRY(layer_fwd(e, i, a.xin, -1, true));
-        // ---- MLP: x_out = x_mid + fc2(quick_gelu(fc1(LN2(x_mid))))
-        GG_TRY(e.wgrad(l.fc2_w, e.A(dx), D, e.A(a.h), I, M, D, I));
-        GG_TRY(e.bgrad(l.fc2_b, e.A(dx), D, M, D));
-        GG_TRY(e.gemm(e.A(dx), D, e.W(l.w2T, l.w2T3), D, e.A(L.g_h), I, M, I, D, nullptr, 0, nullptr, nullptr, e.A(a.pre), GG_ACT_CODE_QUICK_GELU));   // d pre
-        GG_TRY(e.wgrad(l.fc1_w, e.A(L.g_h), I, e.A(a.a2), D, M, I, D));
-        GG_TRY(e.bgrad(l.fc1_b, e.A(L.g_h), I, M, I));
-        GG_TRY(e.gemm(e.A(L.g_h), I, e.W(l.w1T, l.w1T3), I, e.A(L.g_a), D, M, D, I, nullptr));                                                        // d LN2 out
-        GG_TRY(e.ln_bwd(e.A(L.g_a), e.A(a.xmid), e.F(a.mean2), e.F(a.rstd2), l.ln2_g, l.ln2_b, M, e.A(dx), e.A(other)));                       // d x_mid
-        std::swap(dx, other);
-        // ---- attention: x_mid = x_in + out_proj(attn(qkv(LN1(x_in))))
-        GG_TRY(e.wgrad(l.o_w, e.A(dx), D, e.A(a.o), D, M, D, D));
-        GG_TRY(e.bgrad(l.o_b, e.A(dx), D, M, D));
-        GG_TRY(e.gemm(e.A(dx), D, e.W(l.woT, l.woT3), D, e.A(L.g_o), D, M, D, D, nullptr));                                                            // d o
-        GgAttnArgs at;
-        e.attn_args(at, e.A(a.qkv), e.A(a.o), e.F(a.lse));
-        at.dout = e.A(L.g_o); at.lddo = D; at.dqkv = e.A(L.g_qkv);
-        if (L.attn_ds >= 0) at.ds_scratch = e.F(L.attn_ds);
-        GG_TRY(gg_attention_flash_bwd(&at, m.split ? 3 : m.f32 ? 1 : 0, e.st));
-        const char* dq = (const char*)e.A(L.g_qkv);
-        GG_TRY(e.wgrad(l.q_w, dq, 3 * D, e.A(a.a1), D, M, D, D));
-        GG_TRY(e.wgrad(l.k_w, dq + (int64_t)D * m.es, 3 * D, e.A(a.a1), D, M, D, D));
-        GG_TRY(e.wgrad(l.v_w, dq + (int64_t)2 * D * m.es, 3 * D, e.A(a.a1), D, M, D, D));
-        GG_TRY(e.bgrad(l.q_b, dq, 3 * D, M, D));
-        GG_TRY(e.bgrad(l.k_b, dq + (int64_t)D * m.es, 3 * D, M, D));
-        GG_TRY(e.bgrad(l.v_b, dq + (int64_t)2 * D * m.es, 3 * D, M, D));
-        GG_TRY(e.gemm(e.A(L.g_qkv), 3 * D, e.W(l.wqkvT, l.wqkvT3), 3 * D, e.A(L.g_a), D, M, D, 3 * D, nullptr));                                          // d LN1 out
-        GG_TRY(e.ln_bwd(e.A(L.g_a), e.A(a.xin), e.F(a.mean1), e.F(a.rstd1), l.ln1_g, l.ln1_b, M, e.A(dx), e.A(other)));                         // d x_in
-        std::swap(dx, other);
-    }
+    GG_TRY(layers_bwd(e, tr.l0, top_in_region, dx, other));
     if (!tr.embed) return 0;
     // ---- embeddings: x_0 = pre_layrnorm(tokens), tokens = [cls ; patches . W^T] + pos
     GG_TRY(e.ln_bwd(e.A(dx), e.A(L.tok), e.F(L.mean0), e.F(L.rstd0), m.pre_g, m.pre_b, M, nullptr, e.A(other)));
@@ -856,4 +880,219 @@ extern "C" int gg_clip_text_forward(const GgClipTextCfg* cfg, int batch, int tok
     float* fin = last_hidden ? last_hidden : e.F(L.fin);
     GG_TRY(gg_layernorm_fwd(e.A(L.s_x), m.f32, e.P(m.fin_g), e.P(m.fin_b), M, D, m.cfg.ln_eps, fin, 1, nullptr, nullptr, e.st));
     return gg_row_gather_f32(fin, eos_pos, pooled, batch, T, D, e.st);
+}
+
+// ================================================================== CLIP text tower, training (include/gg_clip_text_train.h)
+// The vision tower's machinery over the text model: plan / LayerA keep the tensors of the layers from the first trained one up, layer_fwd(sv = true) fills them,
+// layers_bwd walks them back with the causal attention backward.  Around it: the head (d_pooled scattered to the EOS rows + d_last_hidden, final_layer_norm's
+// backward) and the tail (token-embedding scatter-add, position sum).  No activation recompute.
+namespace {
+struct TextTrain { bool any, embed, fin; int l0; };      // anything trainable; an embedding table; final_layer_norm; first kept layer
+static TextTrain text_train_of(const CModel& m, const uint8_t* mask) {
+    auto on = [&](int t) { return mask == nullptr || mask[t] != 0; };
+    TextTrain tt;
+    tt.embed = on(m.tok_emb) || on(m.pos);
+    tt.fin = on(m.fin_g) || on(m.fin_b);
+    tt.l0 = tt.embed ? 0 : first_trained_layer(m, mask);
+    tt.any = tt.embed || tt.fin || tt.l0 < m.cfg.num_layers;
+    return tt;
+}
+struct TextTrainPlan : CPlan { int64_t fin, fmean, frstd, dx32 = -1; };
+// plan()'s layout (its embedding-side regions are empty here) + final_layer_norm's output and statistics; with no layer kept, the few regions its backward needs
+static void plan_text_train(const CModel& m, int B, const TextTrain& tt, TextTrainPlan& L) {
+    const int D = m.cfg.hidden_size, nl = m.cfg.num_layers;
+    const int64_t M = (int64_t)B * m.T, es = m.es;
+    plan(m, B, Train{tt.embed, tt.l0}, true, L);
+    int64_t off = L.total;
+    auto al = [&](int64_t bytes) { int64_t o = off; off += gg_align(std::max<int64_t>(bytes, 1), 256); return o; };
+    L.fin = al(M * D * 4); L.fmean = al(M * 4); L.frstd = al(M * 4);
+    if (tt.l0 >= nl) {      // only final_layer_norm trains
+        L.g_a = al(M * D * es); L.g_x0 = al(M * D * es);
+        L.lnscr = al(gg_layernorm_bwd_scratch_floats(M, D) * 4); L.lndump = al((int64_t)D * 4);
+    }
+    if (tt.embed && !m.f32) L.dx32 = al(M * D * 4);      // the scatter-add reads f32 rows
+    L.total = off;
+}
+// dy[b,t,:] = (t == eos[b] ? d_pooled[b,:] : 0) + d_last[b,t,:] in the storage type (either source may be NULL); every element of dy is written
+template <typename T>
+__global__ __launch_bounds__(256) void text_head_bwd_kernel(const float* __restrict__ dpool, const float* __restrict__ dlast, const int32_t* __restrict__ pos,
+                                                            T* __restrict__ dy, int B, int Tn, int D) {
+    const int D4 = D / 4;
+    const int64_t total = (int64_t)B * Tn * D4;
+    typedef T t4 __attribute__((ext_vector_type(4)));
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int dd = (int)(i % D4) * 4;
+        const int64_t r = i / D4, b = r / Tn;
+        const int t = (int)(r % Tn);
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (dpool && t == min(max(pos[b], 0), Tn - 1)) v = *reinterpret_cast<const f32x4*>(dpool + b * D + dd);
+        if (dlast) v += *reinterpret_cast<const f32x4*>(dlast + r * D + dd);
+        t4 w;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[j] = from_f<T>(v[j]);
+        *reinterpret_cast<t4*>(dy + r * D + dd) = w;
+    }
+}
+// scatter-add, pass 1: cid[r] = the clamped id, lead[r] = no earlier row carries it (a wave's lanes walk the earlier rows together: broadcast loads)
+__global__ __launch_bounds__(256) void scatter_lead_kernel(const int32_t* __restrict__ ids, int64_t rows, int vocab, int32_t* __restrict__ cid, int32_t* __restrict__ lead) {
+    const int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    const int id = min(max(ids[r], 0), vocab - 1);
+    int first = 1;
+    for (int64_t q = 0; q < r; ++q)
+        if (min(max(ids[q], 0), vocab - 1) == id) { first = 0; break; }
+    cid[r] = id;
+    lead[r] = first;
+}
+// pass 2: one workgroup per row; a leader's adds the rows r.. that carry its id, in index order, and then the sum onto the table row.  Rows are matched 256 at a
+// time (one per thread, a ballot per wave), then every thread walks the set bits -- the same order in every thread, whatever the launch.
+__global__ __launch_bounds__(256) void scatter_add_kernel(const float* __restrict__ dx, const int32_t* __restrict__ cid, const int32_t* __restrict__ lead,
+                                                          float* __restrict__ dtable, int64_t rows, int D) {
+    __shared__ unsigned long long hit[4];
+    const int64_t r = blockIdx.x;
+    if (!lead[r]) return;                                          // (workgroup-uniform)
+    const int id = cid[r];
+    const int D4 = D / 4, wave = threadIdx.x >> 6;
+    f32x4 acc[4];                                                  // columns 4 (threadIdx.x + 256 j): D <= 4096
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int64_t r0 = r; r0 < rows; r0 += 256) {
+        const int64_t q = r0 + threadIdx.x;
+        const unsigned long long b = __ballot(q < rows && cid[q] == id);
+        __syncthreads();                                           // the previous chunk's masks have been read
+        if ((threadIdx.x & 63) == 0) hit[wave] = b;
+        __syncthreads();
+        for (int w = 0; w < 4; ++w) {
+            unsigned long long mk = hit[w];
+            while (mk) {
+                const int bit = __builtin_ctzll(mk);
+                mk &= mk - 1;
+                const float* src = dx + (r0 + 64 * w + bit) * D;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int c4 = threadIdx.x + 256 * j;
+                    if (c4 < D4) acc[j] += *reinterpret_cast<const f32x4*>(src + 4 * c4);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c4 = threadIdx.x + 256 * j;
+        if (c4 < D4) {
+            f32x4* dst = reinterpret_cast<f32x4*>(dtable + (int64_t)id * D + 4 * c4);
+            *dst = *dst + acc[j];
+        }
+    }
+}
+}  // namespace
+
+extern "C" int64_t gg_embedding_scatter_add_scratch_bytes(int64_t rows) {
+    if (rows <= 0) { gg_set_error("gg_embedding_scatter_add_scratch_bytes: rows must be > 0"); return -1; }
+    return gg_align(rows * 8, 256);                                // int32 cid[rows] | int32 lead[rows]
+}
+extern "C" int gg_embedding_scatter_add_f32(const float* dx, const int32_t* ids, float* dtable, int64_t rows, int D, int vocab, void* scratch, void* stream) {
+    GG_CHECK(dx && ids && dtable && scratch && rows > 0 && rows < ((int64_t)1 << 31) && vocab > 0, "gg_embedding_scatter_add_f32: null pointer / bad row or vocabulary count");
+    GG_CHECK(D > 0 && (D & 3) == 0 && D <= 4096, "gg_embedding_scatter_add_f32: D must be a multiple of 4, at most 4096 (got %d)", D);
+    GG_CHECK(((uintptr_t)dx & 15) == 0 && ((uintptr_t)dtable & 15) == 0 && ((uintptr_t)scratch & 15) == 0, "gg_embedding_scatter_add_f32: dx / dtable / scratch must be 16-byte aligned");
+    int32_t* cid = (int32_t*)scratch;
+    int32_t* lead = cid + rows;
+    GG_PROF(GG_CAT_MOVE, 0, 4.0 * rows * D * 3, stream);
+    hipLaunchKernelGGL(scatter_lead_kernel, dim3((unsigned)gg_cdiv(rows, 256)), dim3(256), 0, (hipStream_t)stream, ids, rows, vocab, cid, lead);
+    hipLaunchKernelGGL(scatter_add_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, dx, cid, lead, dtable, rows, D);
+    GG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int64_t gg_clip_text_train_workspace_bytes(const GgClipTextCfg* cfg, int batch, int tokens, const uint8_t* trainable) {
+    CModel m;
+    if (build_text(cfg, tokens, m)) return -1;
+    if (batch <= 0) { gg_set_error("gg_clip_text_train_workspace_bytes: batch must be > 0"); return -1; }
+    const TextTrain tt = text_train_of(m, trainable);
+    if (!tt.any) { TextPlan L; plan_text(m, batch, L); return L.total; }
+    TextTrainPlan L; plan_text_train(m, batch, tt, L);
+    return L.total;
+}
+extern "C" int gg_clip_text_first_trained_layer(const GgClipTextCfg* cfg, const uint8_t* trainable) {
+    CModel m;
+    if (build_text(cfg, 1, m)) return -1;
+    return text_train_of(m, trainable).l0;
+}
+extern "C" int gg_clip_text_forward_train(const GgClipTextCfg* cfg, int batch, int tokens, const float* params, const void* wcache, const int32_t* input_ids,
+                                          const int32_t* eos_pos, void* workspace, float* last_hidden, float* pooled, const uint8_t* trainable, void* stream) {
+    CModel m;
+    GG_TRY(build_text(cfg, tokens, m));
+    const TextTrain tt = text_train_of(m, trainable);
+    if (!tt.any) return gg_clip_text_forward(cfg, batch, tokens, params, wcache, input_ids, eos_pos, workspace, last_hidden, pooled, stream);      // nothing is kept
+    GG_CHECK(batch > 0 && params && wcache && input_ids && eos_pos && workspace && pooled, "gg_clip_text_forward_train: null pointer / bad batch");
+    GG_CHECK(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)wcache & 255) == 0, "gg_clip_text_forward_train: workspace / wcache must be 256-byte aligned");
+    GG_CHECK(((uintptr_t)pooled & 15) == 0 && ((uintptr_t)last_hidden & 15) == 0 && ((uintptr_t)params & 15) == 0, "gg_clip_text_forward_train: params / last_hidden / pooled must be 16-byte aligned");
+    TextTrainPlan L; plan_text_train(m, batch, tt, L);
+    Exec e{&m, &L, batch, (hipStream_t)stream, params, (const char*)wcache, (char*)workspace, nullptr, trainable};
+    const int D = m.cfg.hidden_size, T = m.T, nl = m.cfg.num_layers;
+    const int64_t M = (int64_t)batch * T;
+    const bool keep = tt.l0 < nl;
+    auto saved = [&](int i) { return keep && i >= tt.l0; };
+    int64_t cur = saved(0) ? L.la[0].xin : L.s_x;
+    {
+    GG_PROF(GG_CAT_MOVE, 0, (4.0 + m.es) * M * D, stream);
+    if (m.f32) hipLaunchKernelGGL(text_embed_kernel<float>, dim3(grid1d(M * D / 4)), dim3(256), 0, e.st, input_ids, e.P(m.tok_emb), e.P(m.pos), (float*)e.A(cur), M, T, D, m.vocab);
+    else hipLaunchKernelGGL(text_embed_kernel<bf16>, dim3(grid1d(M * D / 4)), dim3(256), 0, e.st, input_ids, e.P(m.tok_emb), e.P(m.pos), (bf16*)e.A(cur), M, T, D, m.vocab);
+    GG_LAUNCH_CHECK();
+    }
+    for (int i = 0; i < nl; ++i) {
+        const int64_t next = (keep && i + 1 >= tt.l0) ? (i + 1 < nl ? L.la[i + 1].xin : L.xfinal) : cur;
+        GG_TRY(layer_fwd(e, i, cur, next, saved(i)));
+        cur = next;
+    }
+    float* fin = last_hidden ? last_hidden : e.F(L.fin);
+    GG_TRY(gg_layernorm_fwd(e.A(cur), m.f32, e.P(m.fin_g), e.P(m.fin_b), M, D, m.cfg.ln_eps, fin, 1, e.F(L.fmean), e.F(L.frstd), e.st));
+    return gg_row_gather_f32(fin, eos_pos, pooled, batch, T, D, e.st);
+}
+extern "C" int gg_clip_text_backward(const GgClipTextCfg* cfg, int batch, int tokens, const float* params, const void* wcache, const int32_t* input_ids,
+                                     const int32_t* eos_pos, void* workspace, const float* d_pooled, const float* d_last_hidden, float* grads,
+                                     const uint8_t* trainable, void* stream) {
+    CModel m;
+    GG_TRY(build_text(cfg, tokens, m));
+    const TextTrain tt = text_train_of(m, trainable);
+    if (!tt.any) return 0;                          // nothing in the tower is trainable
+    GG_CHECK(batch > 0 && params && wcache && workspace && grads && (d_pooled || d_last_hidden), "gg_clip_text_backward: null pointer / bad batch");
+    GG_CHECK(!d_pooled || eos_pos, "gg_clip_text_backward: d_pooled needs eos_pos");
+    GG_CHECK(!tt.embed || input_ids, "gg_clip_text_backward: a trainable embedding table needs input_ids");
+    GG_CHECK(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)wcache & 255) == 0, "gg_clip_text_backward: workspace / wcache must be 256-byte aligned");
+    GG_CHECK(((uintptr_t)d_pooled & 15) == 0 && ((uintptr_t)d_last_hidden & 15) == 0 && ((uintptr_t)params & 15) == 0 && ((uintptr_t)grads & 15) == 0,
+             "gg_clip_text_backward: params / grads / d_pooled / d_last_hidden must be 16-byte aligned");
+    TextTrainPlan L; plan_text_train(m, batch, tt, L);
+    Exec e{&m, &L, batch, (hipStream_t)stream, params, (const char*)wcache, (char*)workspace, grads, trainable};
+    const int D = m.cfg.hidden_size, T = m.T, B = batch, nl = m.cfg.num_layers;
+    const int64_t M = (int64_t)B * T;
+    // ---- head: pooled = final_layer_norm(x)[eos]
+    {
+    GG_PROF(GG_CAT_MOVE, 0, (4.0 + m.es) * M * D, stream);
+    if (m.f32) hipLaunchKernelGGL(text_head_bwd_kernel<float>, dim3(grid1d(M * D / 4)), dim3(256), 0, e.st, d_pooled, d_last_hidden, eos_pos, (float*)e.A(L.g_a), B, T, D);
+    else hipLaunchKernelGGL(text_head_bwd_kernel<bf16>, dim3(grid1d(M * D / 4)), dim3(256), 0, e.st, d_pooled, d_last_hidden, eos_pos, (bf16*)e.A(L.g_a), B, T, D);
+    GG_LAUNCH_CHECK();
+    }
+    const int64_t xfin = tt.l0 < nl ? L.xfinal : L.s_x;
+    GG_TRY(e.ln_bwd(e.A(L.g_a), e.A(xfin), e.F(L.fmean), e.F(L.frstd), m.fin_g, m.fin_b, M, nullptr, e.A(L.g_x0)));
+    if (tt.l0 >= nl) return 0;
+    int64_t dx = L.g_x0, other = L.g_x1;
+    GG_TRY(layers_bwd(e, tt.l0, true, dx, other));
+    if (!tt.embed) return 0;
+    // ---- embeddings: x_0[b,t,:] = token_embedding[id[b,t]] + position_embedding[t]
+    if (e.tr(m.pos)) {
+        GG_PROF(GG_CAT_MOVE, 0, (double)m.es * M * D, stream);
+        if (m.f32) hipLaunchKernelGGL(embed_bwd_kernel<float>, dim3((unsigned)gg_cdiv((int64_t)T * D, 256)), dim3(256), 0, e.st, (const float*)e.A(dx), e.Gd(m.pos), (float*)nullptr,
+                                      (float*)nullptr, B, T, D);
+        else hipLaunchKernelGGL(embed_bwd_kernel<bf16>, dim3((unsigned)gg_cdiv((int64_t)T * D, 256)), dim3(256), 0, e.st, (const bf16*)e.A(dx), e.Gd(m.pos), (float*)nullptr,
+                                (bf16*)nullptr, B, T, D);
+        GG_LAUNCH_CHECK();
+    }
+    if (e.tr(m.tok_emb)) {
+        const float* dx32 = (const float*)e.A(dx);
+        if (!m.f32) { GG_TRY(gg_cast_bf16_to_f32(e.A(dx), e.F(L.dx32), M * D, e.st)); dx32 = e.F(L.dx32); }
+        // (the clamped ids and leader flags, 8 bytes a row, go where d attention-output was, at least 128 bytes a row: the layers are done with it)
+        GG_TRY(gg_embedding_scatter_add_f32(dx32, input_ids, e.Gd(m.tok_emb), M, D, m.vocab, e.A(L.g_o), e.st));
+    }
+    return 0;
 }

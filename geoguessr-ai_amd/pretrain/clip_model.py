@@ -3,9 +3,13 @@
 
 * ``vision_model``: the flat-storage owner of the existing ``CLIPVisionTower`` (``csrc/clip.hip``), trainable under every mask ``gg_clip_backward`` supports,
   gradient checkpointing included.  ``pooler_output = post_layernorm(last_hidden_state[:, 0])`` is formed here from ``gg_layernorm_fwd`` / ``_bwd``.
-* ``text_model``: the text tower (``gg_clip_text_forward``: causal attention, final_layer_norm, the row at the EOS position).  Forward only: a text tensor that
-  still has ``requires_grad=True`` when a loss is back-propagated raises ``GgError`` naming it (training it needs a causal attention backward and a token-embedding
-  scatter, which are not built).
+* ``text_model``: the text tower (``gg_clip_text_forward``: causal attention, final_layer_norm, the row at the EOS position).  By default it is forward only:
+  a text tensor that still has ``requires_grad=True`` when a loss is back-propagated raises ``GgError`` naming it.  ``CLIPModel(..., train_text=True)`` /
+  ``set_text_training(True)`` opt in to training it (``include/gg_clip_text_train.h``): when grad mode is on and some text tensor requires grad, the forward is
+  ``gg_clip_text_forward_train`` (same bits, the layers from the first trained one up keep their activations) behind a whole-tower autograd node whose backward,
+  ``gg_clip_text_backward`` (causal attention backward, token-embedding scatter-add, position sum), accumulates into the tower's flat gradient buffer under any
+  trainable mask; ``optim.AdamW(model)`` finds the tower through ``trainable_ranges``.  With the switch off, or every text tensor frozen, the five-region
+  inference forward runs as before.  No activation recompute for the text tower; the data-parallel exchange of text gradients (``comm.py``) is out of scope.
 * ``visual_projection`` / ``text_projection``: bias-free ``nn.Linear``-shaped weights; the projections and their weight gradients are library GEMMs.
 * ``logit_scale``: ln(1 / 0.07).  The contrastive head (normalisation, both logit matrices, the symmetric cross-entropy and its whole backward) is one C call,
   ``gg_clip_contrastive``.
@@ -25,7 +29,7 @@ from torch import Tensor, nn
 
 from .. import _lib as L
 from .. import ops
-from ..models.flat import EncoderRuntime
+from ..models.flat import EncoderNode, EncoderRuntime
 from .clip_embedder import CLIP_CONFIGS, PRECISION_NAMES, CLIPVisionTower, _precision_code
 
 CLIP_TEXT_CONFIGS = {
@@ -49,12 +53,16 @@ def _is_norm_weight(n: str) -> bool:
 
 
 class _TextModel(EncoderRuntime):
-    """``text_model`` of the HF module tree: flat storage, weight cache and inference workspace of the text tower."""
-    _name = "CLIP text tower"
+    """``text_model`` of the HF module tree: flat storage, weight cache, the inference workspace and (``train_text``) the training workspace of the text tower."""
+    _name, _switch = "CLIP text tower", "text training"
+    _mask_changed = "requires_grad changed between the CLIP text forward and its backward for {changed} ...; run the forward again"
+    _toggled_gen = None               # generation of a training forward that a set_training toggle made the runtime forget
 
     def __init__(self, cfg: L.ClipTextCfg, seed: int, eos_token_id: int):
         super().__init__()
         self.cfg = cfg
+        self.cfg.recompute = 0            # (a plain attribute, not a field of GgClipTextCfg: the step lifecycle reads it; the text tower has no checkpointing)
+        self.train_text = False
         self.eos_token_id = eos_token_id
         self.precision = PRECISION_NAMES[cfg.act_dtype]
         lib = L.lib()
@@ -81,8 +89,28 @@ class _TextModel(EncoderRuntime):
             return torch.randn(shape, generator=g) * 0.02
         self._register_table(init)
 
-    def set_recompute(self, enable: bool) -> bool:      # (inference only: nothing to checkpoint)
+    def set_recompute(self, enable: bool) -> bool:      # (nothing to checkpoint: the training forward keeps every tensor its backward reads)
         return False
+
+    def set_training(self, enable: bool) -> bool:
+        """The opt-in switch of text-tower training.  True if it changed: the training workspace is released and a pending training forward is forgotten
+        (its backward is refused)."""
+        changed = bool(enable) != self.train_text
+        if changed:
+            self.train_text = bool(enable)
+            self._ws.pop(True, None)
+            if self._last is not None:
+                self._last, self._toggled_gen = None, self._gen
+        return changed
+
+    def _pending(self, gen, batch=None):
+        if self._last is None and self._toggled_gen == self._gen:
+            raise L.GgError(f"text training was toggled since the training forward (now train_text={self.train_text}): its workspace was released; "
+                            "run the forward again")
+        return super()._pending(gen, batch)
+
+    def wants_training(self) -> bool:
+        return self.train_text and self.wants_grad()
 
     def _wcache_bytes(self) -> int:
         return L.lib().gg_clip_text_wcache_bytes(C.byref(self.cfg))
@@ -100,7 +128,17 @@ class _TextModel(EncoderRuntime):
             ws = self._ws[False] = torch.empty(need, dtype=torch.uint8, device=self._flat.device)
         return ws
 
-    def forward_hip(self, input_ids: Tensor, eos_pos: Optional[Tensor] = None, return_last_hidden: bool = False):
+    def _train_workspace(self, B: int, T: int, mask: bytes) -> Tensor:      # its own buffer: an inference forward in between leaves the kept activations alone
+        need = L.lib().gg_clip_text_train_workspace_bytes(C.byref(self.cfg), B, T, mask)
+        if need < 0:
+            raise L.GgError(L.lib().gg_last_error().decode())
+        ws = self._ws.get(True)
+        if ws is None or ws.numel() < need or ws.device != self._flat.device:
+            ws = self._ws[True] = None
+            ws = self._ws[True] = torch.empty(need, dtype=torch.uint8, device=self._flat.device)
+        return ws
+
+    def forward_hip(self, input_ids: Tensor, eos_pos: Optional[Tensor] = None, return_last_hidden: bool = False, training: bool = False):
         L.require_gpu()
         if not self._flat.is_cuda:
             raise L.GgError("CLIP text tower parameters are on the CPU; call .to('cuda') -- there is no CPU fallback")
@@ -126,17 +164,47 @@ class _TextModel(EncoderRuntime):
             raise L.GgError(f"eos_pos outside the sequence [0, {T}): min {elo}, max {ehi}")
         ids = input_ids.to(torch.int32).contiguous()
         self._ensure_weights()
-        ws = self._text_workspace(B, T)
         D = self.cfg.hidden_size
         pooled = torch.empty((B, D), dtype=torch.float32, device=ids.device)
         last = torch.empty((B, T, D), dtype=torch.float32, device=ids.device) if return_last_hidden else None
+        if training:
+            mask = self.trainable_mask()
+            ws = self._train_workspace(B, T, mask)
+            L.check(L.lib().gg_clip_text_forward_train(C.byref(self.cfg), B, T, L.ptr(self._flat), L.ptr(self._wcache), L.ptr(ids), L.ptr(eos_pos), L.ptr(ws),
+                                                       L.ptr(last), L.ptr(pooled), mask, L.stream()), "gg_clip_text_forward_train")
+            self._record_forward(B, mask, (ids, eos_pos, T))
+            return pooled, last
+        ws = self._text_workspace(B, T)
         L.check(L.lib().gg_clip_text_forward(C.byref(self.cfg), B, T, L.ptr(self._flat), L.ptr(self._wcache), L.ptr(ids), L.ptr(eos_pos), L.ptr(ws),
                                              L.ptr(last), L.ptr(pooled), L.stream()), "gg_clip_text_forward")
         return pooled, last
 
+    def backward_hip(self, d_pooled: Optional[Tensor], d_last: Optional[Tensor], gen: int):
+        B, (ids, eos_pos, T), ws = self._pending(gen)
+        mask = self._same_mask()
+        fg = self.attach_grads()
+        f = lambda t: None if t is None else t.to(torch.float32).contiguous()
+        d_pooled, d_last = f(d_pooled), f(d_last)
+        L.check(L.lib().gg_clip_text_backward(C.byref(self.cfg), B, T, L.ptr(self._flat), L.ptr(self._wcache), L.ptr(ids), L.ptr(eos_pos), L.ptr(ws),
+                                              L.ptr(d_pooled), L.ptr(d_last), L.ptr(fg), mask, L.stream()), "gg_clip_text_backward")
+
     def forward(self, input_ids: Tensor = None, attention_mask=None, **_):
-        pooled, last = self.forward_hip(input_ids, None, True)
+        if self.wants_training():
+            pooled, last = _TextFn.apply(self, input_ids, self._anchor(), True)
+        else:
+            pooled, last = self.forward_hip(input_ids, None, True)
         return SimpleNamespace(last_hidden_state=last, pooler_output=pooled)
+
+
+class _TextFn(EncoderNode):
+    """Whole-tower autograd node of the text tower (the counterpart of the vision tower's ``_ClipFn``; ``EncoderRuntime._anchor``)."""
+
+    @staticmethod
+    def forward(ctx, tm: _TextModel, input_ids: Tensor, anchor: Tensor, want_last: bool):
+        pooled, last = tm.forward_hip(input_ids, None, want_last, training=True)
+        tm._enter_node(ctx)
+        ctx.set_materialize_grads(False)          # an unused last_hidden_state must not cost a (B,T,D) zero gradient
+        return pooled, last
 
 
 def _row0(x: Tensor) -> Tensor:
@@ -244,14 +312,17 @@ class _HeadFn(torch.autograd.Function):
         if d_loss is None or not ctx.grads:
             return (None,) * 8
         model = ctx.model
+        need = ctx.needs_input_grad          # (model, pooled_img, pooled_txt, w_img, w_txt, logit_scale, want_loss, grads)
         hot = [n for n, p in model.text_model.named_parameters() if p.requires_grad]
-        if hot:
-            raise L.GgError(f"text_model.{hot[0]} has requires_grad=True ({len(hot)} text tensors in all): the text tower is forward-only (training it needs a "
-                            "causal attention backward and a token-embedding scatter); freeze it, e.g. with freeze_backbone_keep_head")
+        if hot and not model.text_model.train_text:
+            raise L.GgError(f"text_model.{hot[0]} has requires_grad=True ({len(hot)} text tensors in all): the text tower is forward-only by default; freeze it, "
+                            "e.g. with freeze_backbone_keep_head, or opt in to training it with CLIPModel(..., train_text=True) / set_text_training(True)")
+        if hot and not need[2]:
+            raise L.GgError(f"text_model.{hot[0]} has requires_grad=True, but this loss came from the text tower's inference forward (text training or "
+                            "requires_grad was switched on since the forward); run the forward again")
         pooled_img, pooled_txt, w_img, w_txt, d_img, d_txt, d_ls = ctx.saved_tensors
-        need = ctx.needs_input_grad          # (model, pooled_img, pooled_txt, w_img, w_txt, logit_scale, want_loss)
         g = d_loss.to(torch.float32)
-        d_pool = d_wi = d_wt = d_l = None
+        d_pool = d_pool_txt = d_wi = d_wt = d_l = None
         if need[3]:
             d_wi = ops.gemm_tn(d_img, pooled_img.contiguous()) * g
         if need[4]:
@@ -260,14 +331,17 @@ class _HeadFn(torch.autograd.Function):
             d_l = (d_ls * g).reshape(ctx.model.logit_scale.shape)
         if need[1]:
             d_pool = ops.gemm_nt(d_img, _transpose(w_img.detach().contiguous())) * g
-        return None, d_pool, None, d_wi, d_wt, d_l, None, None
+        if need[2]:
+            d_pool_txt = ops.gemm_nt(d_txt, _transpose(w_txt.detach().contiguous())) * g
+        return None, d_pool, d_pool_txt, d_wi, d_wt, d_l, None, None
 
 
 class CLIPModel(nn.Module):
     supports_gradient_checkpointing = True
 
-    def __init__(self, model_name: str = "openai/clip-vit-base-patch32", seed: int = 0, precision: Optional[str] = None, config: Optional[dict] = None):
-        """``config`` (tests): ``dict(text=dict(hidden_size, intermediate_size, num_layers, num_heads[, vocab_size, max_positions, eos_token_id]),
+    def __init__(self, model_name: str = "openai/clip-vit-base-patch32", seed: int = 0, precision: Optional[str] = None, config: Optional[dict] = None,
+                 train_text: bool = False):
+        """``train_text``: opt in to training the text tower (see ``set_text_training``).  ``config`` (tests): ``dict(text=dict(hidden_size, intermediate_size, num_layers, num_heads[, vocab_size, max_positions, eos_token_id]),
         vision=dict(hidden_size, intermediate_size, num_layers, num_heads, image_size, patch_size), projection_dim=P)``."""
         super().__init__()
         if config is None:
@@ -290,6 +364,7 @@ class CLIPModel(nn.Module):
         c.hidden_size, c.intermediate_size, c.num_layers, c.num_heads = tk["hidden_size"], tk["intermediate_size"], tk["num_layers"], tk["num_heads"]
         c.vocab_size, c.max_positions, c.ln_eps, c.act_dtype = tk["vocab_size"], tk["max_positions"], 1e-5, code
         self.text_model = _TextModel(c, seed + 1, tk["eos_token_id"])
+        self.text_model.set_training(train_text)
         g = torch.Generator().manual_seed(seed + 2)
         self.visual_projection = nn.Linear(vk["hidden_size"], P, bias=False)
         self.text_projection = nn.Linear(tk["hidden_size"], P, bias=False)
@@ -307,6 +382,17 @@ class CLIPModel(nn.Module):
 
     def gradient_checkpointing_disable(self):
         self.vision_tower.gradient_checkpointing_disable()
+
+    # ---- text-tower training: opt-in ----------------------------------------------------------------------------------------------------------
+    @property
+    def train_text(self) -> bool:
+        return self.text_model.train_text
+
+    def set_text_training(self, enable: bool) -> bool:
+        """With it on, a forward in grad mode with some ``text_model`` tensor trainable runs the text tower's training forward, and ``loss.backward()`` reaches its
+        parameters; with it off (the default) such a backward is refused and the tower always runs its inference forward.  Toggling it between a forward and its
+        backward makes that backward refuse.  Returns whether the setting changed."""
+        return self.text_model.set_training(enable)
 
     # ---- weights -------------------------------------------------------------------------------------------------------------------------
     def load_hf_state_dict(self, sd: Dict[str, Tensor]):
@@ -331,7 +417,10 @@ class CLIPModel(nn.Module):
                                  save_stats=False)[0]
 
     def _text_pooled(self, input_ids: Tensor) -> Tensor:
-        return self.text_model.forward_hip(input_ids, None, False)[0]
+        tm = self.text_model
+        if tm.wants_training():      # train_text on, grad mode on, some text tensor requires grad
+            return _TextFn.apply(tm, input_ids, tm._anchor(), False)[0]
+        return tm.forward_hip(input_ids, None, False)[0]
 
     def get_image_features(self, pixel_values: Tensor = None, **_) -> Tensor:
         with torch.no_grad():
