@@ -87,6 +87,12 @@ class ContrastiveArgs(C.Structure):      # GgContrastiveArgs
                 ("d_logit_scale", C.c_void_p), ("d_img", C.c_void_p), ("d_txt", C.c_void_p), ("scratch", C.c_void_p)]
 
 
+class ClsHeadArgs(C.Structure):          # GgClsHeadArgs (include/gg_cls.h)
+    _fields_ = [("logits", C.c_void_p), ("ldl", C.c_int64), ("N", C.c_int), ("C", C.c_int), ("labels", C.c_void_p), ("grad_scale", C.c_float),
+                ("upstream", C.c_void_p), ("loss_rows", C.c_void_p), ("loss", C.c_void_p), ("dlogits", C.c_void_p), ("ldd", C.c_int64),
+                ("dlogits_f32", C.c_int), ("rank", C.c_void_p), ("preds", C.c_void_p)]
+
+
 STAGE_DONE_FN = C.CFUNCTYPE(None, C.c_int, C.c_void_p)      # GgStageDoneFn (host callback of gg_tinyvit_backward)
 
 # every exported symbol of include/gg.h: name -> (restype, argtypes)
@@ -290,6 +296,13 @@ TEXT_TRAIN_SIGNATURES = {
 }
 TEXT_TRAIN_SYMBOLS = list(TEXT_TRAIN_SIGNATURES)
 
+# every exported symbol of include/gg_cls.h (the TinyViT classifier fine-tune), bound from the same libgg.so
+CLS_SIGNATURES = {
+    "gg_cls_head": (_I, [C.POINTER(ClsHeadArgs), _P]),
+    "gg_tinyvit_last_map_info": (_I, [C.POINTER(TinyVitCfg), _I, C.POINTER(_L), C.POINTER(_L), C.POINTER(_I), C.POINTER(_I)]),
+}
+CLS_SYMBOLS = list(CLS_SIGNATURES)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -298,7 +311,7 @@ def lib() -> C.CDLL:
             raise GgError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the library lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -346,6 +359,7 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(root), "include", "gg.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_clip_text.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_clip_text_train.h"))
+    files.append(os.path.join(os.path.dirname(root), "include", "gg_cls.h"))
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

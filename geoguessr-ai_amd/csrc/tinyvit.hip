@@ -13,6 +13,7 @@
 #include "common.h"
 #include "graph.h"
 #include "../../include/gg.h"
+#include "../../include/gg_cls.h"
 
 namespace {
 
@@ -1316,6 +1317,23 @@ extern "C" int gg_tinyvit_activation_info_masked(const GgTinyVitCfg* cfg, int ba
 }
 extern "C" int gg_tinyvit_activation_info(const GgTinyVitCfg* cfg, int batch, const char* name, int64_t* offset, int64_t* bytes) {
     return gg_tinyvit_activation_info_masked(cfg, batch, name, nullptr, offset, bytes);
+}
+// include/gg_cls.h: where the inference forward leaves the last TinyVitBlock's output (timm forward_features).  Nothing after that block takes a slot of
+// the inference ring (head.* and the scratch regions are persistent), so the map survives until the next forward on this workspace.
+extern "C" int gg_tinyvit_last_map_info(const GgTinyVitCfg* cfg, int batch, int64_t* offset, int64_t* bytes, int* res, int* channels) {
+    Model m;
+    GG_TRY(build_model(cfg, m));
+    GG_CHECK(batch > 0, "gg_tinyvit_last_map_info: batch must be > 0");
+    Plan p; Layout L;
+    plan_make(m, batch, false, p, L, nullptr);
+    const std::string name = "stages.3.blocks." + std::to_string(m.stages[2].blocks.size() - 1) + ".out";
+    auto it = p.index.find(name);
+    GG_CHECK(it != p.index.end(), "gg_tinyvit_last_map_info: no activation named '%s'", name.c_str());
+    if (offset) *offset = p.regs[it->second].offset;
+    if (bytes) *bytes = (int64_t)batch * m.stages[2].res * m.stages[2].res * m.stages[2].C * m.es;
+    if (res) *res = m.stages[2].res;
+    if (channels) *channels = m.stages[2].C;
+    return 0;
 }
 // `only` (host, one byte per tensor, or NULL = every tensor): the tensors whose cached forms are rebuilt.  After an optimizer step only the
 // trainable tensors changed -- under the reference freeze policy 14 of the 52 cached matrices -- so the per-step refresh skips the frozen ones.

@@ -208,8 +208,14 @@ class TinyVitBackbone(EncoderRuntime):
         if state and state.get("drop_seed") is not None:
             self._drop_seed, self._drop_counter = int(state["drop_seed"]), int(state.get("drop_counter", 0))
 
-    def forward_hip(self, x: torch.Tensor, training: bool, drop_scales: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def forward_hip(self, x: torch.Tensor, training: bool, drop_scales: Optional[torch.Tensor] = None, features_only: Optional[bool] = None) -> torch.Tensor:
+        """``features_only`` (None: the backbone's own setting): this ONE call returns the pooled last feature map without head.norm (True) or with it
+        (False) from the same parameters, weight cache and workspace -- the plan does not depend on the flag (TinyViTClassifier.pooled_features)."""
         L.require_gpu()
+        cfg = self.cfg
+        if features_only is not None and int(bool(features_only)) != cfg.features_only:
+            cfg = L.TinyVitCfg.from_buffer_copy(self.cfg)
+            cfg.features_only = int(bool(features_only))
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != self.cfg.img_size or x.shape[3] != self.cfg.img_size:
             raise L.GgError(f"TinyViT expects (B,3,{self.cfg.img_size},{self.cfg.img_size}) pixel_values, got {tuple(x.shape)}")
         if not self._flat.is_cuda:
@@ -220,7 +226,7 @@ class TinyVitBackbone(EncoderRuntime):
         out = torch.empty((B, self.num_features), dtype=torch.float32, device=x.device)
         if drop_scales is not None:
             assert drop_scales.shape == (self.num_drop_slots, B) and drop_scales.dtype == torch.float32
-        L.check(L.lib().gg_tinyvit_forward(C.byref(self.cfg), B, int(training), L.ptr(self._flat), L.ptr(self._flat_buf),
+        L.check(L.lib().gg_tinyvit_forward(C.byref(cfg), B, int(training), L.ptr(self._flat), L.ptr(self._flat_buf),
                                            L.ptr(self._counters), L.ptr(self._wcache), L.ptr(x), L.ptr(drop_scales), L.ptr(ws),
                                            L.ptr(out), mask, L.stream()),
                 "gg_tinyvit_forward")

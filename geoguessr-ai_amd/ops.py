@@ -625,6 +625,38 @@ def geo_head(logits, centroids, *, labels=None, labels_clf=None, mode=0, smoothi
     return r
 
 
+def cls_head(logits, labels, *, num_classes=None, grad_scale=None, upstream=None, want_loss=True, want_dlogits=False, dlogits_f32=True, ldd=None,
+             want_rank=True, want_preds=True):
+    """Fused classification head (``gg_cls_head``, include/gg_cls.h): cross-entropy rows and their mean, d(mean loss)/d(logits), the rank of the label
+    (top-k hit <=> rank < k) and the arg-max of f32 logits (N, C) whose rows may be strided (a column slice of a wider buffer).  ``grad_scale`` defaults
+    to 1 / N; ``upstream`` is a device scalar multiplied into it.  Returns a dict of device tensors (only what was asked for)."""
+    L.require_gpu()
+    N = logits.shape[0]
+    C_ = logits.shape[1] if num_classes is None else num_classes
+    dev = logits.device
+    r = {}
+    a = L.ClsHeadArgs()
+    a.logits, a.ldl, a.N, a.C = _pr(logits, F32, "logits"), logits.stride(0), N, C_
+    a.labels = _p(labels, I64, "labels")
+    a.grad_scale = (1.0 / max(N, 1)) if grad_scale is None else grad_scale
+    a.upstream = _p(upstream, F32, "upstream")
+    if want_loss:
+        r["loss_rows"], r["loss"] = torch.empty((N,), dtype=F32, device=dev), torch.empty((1,), dtype=F32, device=dev)
+        a.loss_rows, a.loss = _p(r["loss_rows"]), _p(r["loss"])
+    if want_dlogits:
+        ldd = (C_ + 7) // 8 * 8 if ldd is None else ldd
+        r["dlogits"] = torch.empty((N, ldd), dtype=F32 if dlogits_f32 else BF16, device=dev)
+        a.dlogits, a.ldd, a.dlogits_f32 = _p(r["dlogits"]), ldd, int(dlogits_f32)
+    if want_rank:
+        r["rank"] = torch.empty((N,), dtype=torch.int32, device=dev)
+        a.rank = _p(r["rank"])
+    if want_preds:
+        r["preds"] = torch.empty((N,), dtype=I64, device=dev)
+        a.preds = _p(r["preds"])
+    L.check(L.lib().gg_cls_head(C.byref(a), L.stream()), "gg_cls_head")
+    return r
+
+
 def haversine_matrix(x, centroids):
     """models/utils.py:39 with y given as (K,2) centroids (the reference passes centroids.t())."""
     N, K = x.shape[0], centroids.shape[0]
