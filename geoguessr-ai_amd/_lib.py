@@ -32,7 +32,8 @@ class Split3Args(C.Structure):          # GgSplit3Args (the fp32_split mode's GE
     _fields_ = [("a_planes", C.c_void_p), ("lda", C.c_int64), ("b_planes", C.c_void_p), ("ldb", C.c_int64), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
                 ("C", C.c_void_p), ("ldc", C.c_int64), ("c_planes", C.c_void_p), ("ldp", C.c_int64), ("bias", C.c_void_p), ("act", C.c_int),
                 ("preact", C.c_void_p), ("rowscale", C.c_void_p), ("rows_per_scale", C.c_int), ("residual", C.c_void_p), ("ldr", C.c_int64),
-                ("dact_preact", C.c_void_p), ("dact", C.c_int)]
+                ("dact_preact", C.c_void_p), ("dact", C.c_int),
+                ("groups_dev", C.c_void_p), ("group_rows", C.c_int), ("a_map", C.c_void_p), ("c_map", C.c_void_p)]      # row compaction (device-side live row count, row maps)
 
 
 class AttnArgs(C.Structure):
@@ -41,7 +42,8 @@ class AttnArgs(C.Structure):
                 ("tokens_per_window", C.c_int), ("window_size", C.c_int), ("map_h", C.c_int), ("map_w", C.c_int),
                 ("bias", C.c_void_p), ("scale", C.c_float), ("out", C.c_void_p), ("ldo", C.c_int64),
                 ("dout", C.c_void_p), ("lddo", C.c_int64), ("dqkv", C.c_void_p), ("dbias", C.c_void_p), ("dbias_scratch", C.c_void_p),
-                ("lse", C.c_void_p), ("bias_table", C.c_void_p), ("ds_scratch", C.c_void_p)]
+                ("lse", C.c_void_p), ("bias_table", C.c_void_p), ("ds_scratch", C.c_void_p),
+                ("window_map", C.c_void_p), ("num_windows_dev", C.c_void_p)]
 
 
 class GeoHeadArgs(C.Structure):
@@ -303,6 +305,17 @@ CLS_SIGNATURES = {
 }
 CLS_SYMBOLS = list(CLS_SIGNATURES)
 
+# every exported symbol of include/gg_drop.h (DropPath row compaction of the fp32_split TinyViT step), bound from the same libgg.so
+DROP_LIST_HEAD = 4                        # GG_DROP_LIST_HEAD: a kept list is [count, batch, 0, 0][kept: batch][pos: batch] int32
+DROP_SIGNATURES = {
+    "gg_drop_list_ints": (_I, [_I]),
+    "gg_drop_kept_lists": (_I, [_P, _I, _I, _P, _P]),
+    "gg_layernorm_fwd_bn_f32_map": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _P, _P, _P, _P, _I, _P, _P]),
+    "gg_layernorm_bwd_map": (_I, [_P, _P, _P, _P, _P, _L, _I, _P, _P, _P, _P, _I, _P]),
+    "gg_tinyvit_set_drop_compact": (_I, [_I]),
+}
+DROP_SYMBOLS = list(DROP_SIGNATURES)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -311,7 +324,7 @@ def lib() -> C.CDLL:
             raise GgError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the library lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -360,6 +373,7 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(root), "include", "gg_clip_text.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_clip_text_train.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_cls.h"))
+    files.append(os.path.join(os.path.dirname(root), "include", "gg_drop.h"))
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

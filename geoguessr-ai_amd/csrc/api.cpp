@@ -47,6 +47,14 @@ GgProfScope::~GgProfScope() {
     if (idx_ >= 0) hipEventRecord(g_recs[idx_].b, (hipStream_t)stream_);
 }
 bool gg_prof_is_on() { return g_on; }
+int gg_prof_live_groups(const int* count_dev, int full, void* stream) {
+    if (!g_on || !count_dev) return full;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return full;
+    int n = full;
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || hipMemcpy(&n, count_dev, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return full;
+    return n < 0 ? 0 : n > full ? full : n;
+}
 extern "C" int gg_prof_enable(int on) { g_on = on != 0; return 0; }
 extern "C" int gg_prof_reset(void) { g_recs.clear(); g_pool_next = 0; return 0; }
 extern "C" int gg_prof_count(void) { return (int)g_recs.size(); }

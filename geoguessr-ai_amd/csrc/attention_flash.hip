@@ -43,6 +43,7 @@ struct FlashParams {
     uint32_t rcp_img, rcp_nwx;        // ceil(2^32 / windows per image), ceil(2^32 / windows per row) (0: divisor 1): window -> (image, row, column) in scalar arithmetic
     float neg_inv_scale;              // -1 / scale
     int round_bias;                   // bf16 storage, expanded bias table also given: the forward was attention.hip's (bias added as bf16(bias / scale)); the backward recomputes P with the same value
+    const int* window_map; const int* nwin_dev;      // row compaction (flash_bwd_split_kernel only): physical window of compact window w; device-side live window count
 };
 // integer division by a launch constant without the ~30-instruction software divide (fp32 MFMA and VALU share the SIMD's issue: the divides of the
 // staging loops were most of the vector instructions of a 7 x 7 window's workgroup)
@@ -1140,7 +1141,7 @@ __global__ void flash_dbias_final_kernel(const float* __restrict__ rows, int nro
     dbias[i] += (float)s;
 }
 
-int flash_fill(FlashParams& p, const GgAttnArgs* a, int dtype, const char* who) {
+int flash_fill(FlashParams& p, const GgAttnArgs* a, int dtype, const char* who, bool takes_map = false) {
     GG_CHECK(a && a->qkv, "%s: null qkv", who);
     GG_CHECK(dtype >= 0 && dtype <= 3, "%s: dtype must be 0 (bf16), 1 (f32), 2 (fp16, forward only) or 3 (f32 storage, split-bf16 products)", who);
     // dtype 3 is one pair of kernels (attention_split64.h): what they do not implement is refused here, before anything is launched
@@ -1176,6 +1177,9 @@ int flash_fill(FlashParams& p, const GgAttnArgs* a, int dtype, const char* who) 
     p.rcp_ws = p.rcp_w2 = p.rcp_img = p.rcp_nwx = 0;
     p.neg_inv_scale = -1.0f / p.scale;
     p.round_bias = 0;                                     // (set by gg_attention_flash_bwd_impl when the forward was attention.hip's)
+    p.window_map = nullptr; p.nwin_dev = nullptr;         // (likewise, for the one kernel that takes a window map)
+    GG_CHECK((a->window_map != nullptr) == (a->num_windows_dev != nullptr), "%s: window_map and num_windows_dev go together", who);
+    GG_CHECK(takes_map || !a->window_map, "%s: window_map is a form of gg_attention_flash_bwd only", who);
     {
         auto magic = [](int d) { return d <= 1 ? 0u : (uint32_t)((((uint64_t)1 << 32) + d - 1) / d); };      // exact for numerators < 2^32 / d
         p.rcp_img = magic(p.nWx * p.nWy); p.rcp_nwx = magic(p.nWx);
@@ -1345,8 +1349,9 @@ extern "C" int gg_attention_flash_bwd(const GgAttnArgs* a, int dtype, void* stre
 int gg_attention_flash_bwd_impl(const GgAttnArgs* a, int dtype, int forward_rounded_bias, void* stream) {
     FlashParams p;
     GG_CHECK(dtype != 2, "gg_attention_flash_bwd: fp16 storage is inference-only");
-    GG_TRY(flash_fill(p, a, dtype, "gg_attention_flash_bwd"));
+    GG_TRY(flash_fill(p, a, dtype, "gg_attention_flash_bwd", true));
     p.round_bias = (forward_rounded_bias && dtype == 0 && a->bias != nullptr) ? 1 : 0;
+    bool map_taken = false;
     GG_CHECK(a->dout && a->dqkv && (a->lddo & 3) == 0 && ((uintptr_t)a->dout & 15) == 0 && ((uintptr_t)a->dqkv & 15) == 0,
              "gg_attention_flash_bwd: bad dout/dqkv");
     GG_CHECK(a->lse && a->out && (a->ldo & 3) == 0, "gg_attention_flash_bwd: needs the forward's lse and out");
@@ -1374,8 +1379,15 @@ int gg_attention_flash_bwd_impl(const GgAttnArgs* a, int dtype, int forward_roun
         if ((dtype == 1 || dtype == 0) && a->head_dim == 32 && !nosplit && (nt16 == 4 || nt16 == 9 || nt16 == 13) && sp_lds_bwd(p, p.dbias != nullptr, npl) <= 160 * 1024) {
             GG_CHECK(dtype == 1 || ((a->ld & 7) == 0 && (a->ldo & 7) == 0 && (a->lddo & 7) == 0 && ((a->q_off | a->k_off | a->v_off | a->head_stride) & 7) == 0),
                      "gg_attention_flash_bwd: bf16 rows must be 16-byte aligned");
-            GG_PROF(GG_CAT_ATTN, 10.0 * a->num_windows * a->num_heads * (double)p.N * p.N * a->head_dim,
-                    8.0 * es * a->num_windows * a->num_heads * (double)p.N * a->head_dim, stream);
+            double nwin = a->num_windows;
+            if (a->window_map) {
+                GG_CHECK(dtype == 1 && !p.dbias, "gg_attention_flash_bwd: window_map is f32 storage without a bias gradient");
+                p.window_map = a->window_map; p.nwin_dev = a->num_windows_dev;
+                map_taken = true;
+                nwin = gg_prof_live_groups(a->num_windows_dev, a->num_windows, stream);      // declared work: the live windows'
+            }
+            GG_PROF(GG_CAT_ATTN, 10.0 * nwin * a->num_heads * (double)p.N * p.N * a->head_dim,
+                    8.0 * es * nwin * a->num_heads * (double)p.N * a->head_dim, stream);
             const size_t lds = sp_lds_bwd(p, p.dbias != nullptr, npl);
             void (*kern)(FlashParams);
 #define GG_SP_BWD(T_, N_)                                                                                                                     \
@@ -1397,6 +1409,7 @@ int gg_attention_flash_bwd_impl(const GgAttnArgs* a, int dtype, int forward_roun
             return 0;
         }
     }
+    GG_CHECK(a->window_map == nullptr || map_taken, "gg_attention_flash_bwd: window_map needs the single-pass split kernel (f32 storage, head dim 32, 7 x 7 / 12 x 12 / 14 x 14 windows)");
     if (flash_fused_ok(p, a->head_dim, p.dbias != nullptr)) {
         // windows of at most 256 tokens: the single-pass kernel (no dS scratch, no second phase)
         GG_PROF(GG_CAT_ATTN, 10.0 * a->num_windows * a->num_heads * (double)p.N * p.N * a->head_dim,

@@ -247,9 +247,16 @@ __global__ __launch_bounds__(64 * ((NT + 1) / 2)) void flash_bwd_split_kernel(Fl
     float* Gt = reinterpret_cast<float*>(qlin + R);                // per wave: one dS slot [16 q][TS] (the two key strips take turns)
     const int wh = blockIdx.x;
     const int h = wh % p.nh, w = wh / p.nh;
+    // row compaction (GgAttnArgs.window_map; DBIAS off): the grid covers every window, only the first *nwin_dev are live; window w takes the forward's tensors of
+    // physical window window_map[w] and its gradients at window w itself
+    int wp = w;
+    if (p.window_map) {
+        if (w >= *p.nwin_dev) return;
+        wp = p.window_map[w];
+    }
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lr = lane & 15, lg = lane >> 4;
-    const int64_t origin = fl_origin(p, w);
+    const int64_t origin = fl_origin(p, wp), origin_g = fl_origin(p, w);
     const int hc = h * p.head_stride;
     const bool has_bias = p.bias_table != nullptr;
     const int nb = p.ws * p.ws;
@@ -257,10 +264,10 @@ __global__ __launch_bounds__(64 * ((NT + 1) / 2)) void flash_bwd_split_kernel(Fl
     const int span = fl_span(p);
     const int ldb = (int)p.ld * ES, lddob = (int)p.lddo * ES, ldob = (int)p.ldo * ES;
     const __amdgpu_buffer_rsrc_t rsQKV = fl_rsrc(reinterpret_cast<const T*>(p.qkv) + origin * p.ld, span * ldb);
-    const __amdgpu_buffer_rsrc_t rsDO = fl_rsrc(reinterpret_cast<const T*>(p.dout) + origin * p.lddo, span * lddob);
+    const __amdgpu_buffer_rsrc_t rsDO = fl_rsrc(reinterpret_cast<const T*>(p.dout) + origin_g * p.lddo, span * lddob);
     const __amdgpu_buffer_rsrc_t rsO = fl_rsrc(reinterpret_cast<const T*>(p.out) + origin * p.ldo, span * ldob);
     const __amdgpu_buffer_rsrc_t rsLSE = fl_rsrc(p.lse + origin * p.nh, span * p.nh * 4);
-    const __amdgpu_buffer_rsrc_t rsDQKV = fl_rsrc(reinterpret_cast<T*>(p.dqkv) + origin * p.ld, span * ldb);
+    const __amdgpu_buffer_rsrc_t rsDQKV = fl_rsrc(reinterpret_cast<T*>(p.dqkv) + origin_g * p.ld, span * ldb);
     // every global load of the workgroup is issued before anything waits: Q, dO and O rows (two 8-column chunks per thread: R * 4 chunks over 64 NP threads),
     // lse, then (below) the K / V strips; the LDS-only setup runs under their latency
     f32x4 qv[2][2], gv[2][2], ov[2][2];

@@ -46,7 +46,13 @@ struct Split3Params {
     bf16* c_planes; int64_t ldp;
     const float* a_stat; const float* a_gamma; const float* a_beta; int a_act;      // A prologue (gemm_nt_split3a_kernel<..., PRO>): A := a_act(BatchNorm(A)), a_stat = [mean | rstd][K]
     float* colstats;                   // BatchNorm partials [ceil(M / 128)][2][N] (column sums of the result and of its square per 128-row block; plain epilogue only) or null
+    // Row compaction (gemm_nt_split3a_kernel<..., MAP>; GgSplit3Args.groups_dev): the live rows are the first *groups_dev * group_rows of M, known only on the device.
+    // a_map / c_map (kept lists, ascending group indices): compact row r <-> physical row map[r / group_rows] * group_rows + r % group_rows of A / of C and the residual
+    const int* groups_dev; int group_rows;
+    const int* a_map; const int* c_map;
 };
+// what the row epilogues need of the compaction: live rows, the C / residual row map, the map of the row-scale index (c_map, else a_map)
+struct S3RowMap { int M; const int* cmap; const int* smap; int rps; };
 
 // one 4-column group of one row in the MFMA result layout (lane: row m, columns n .. n + 3)
 __device__ __forceinline__ void split3_epilogue4(const Split3Params& p, f32x4 v, int m, int n) {
@@ -109,8 +115,18 @@ __device__ __forceinline__ void split3_epilogue4(const Split3Params& p, f32x4 v,
 //   4: C = (acc + bias) [* scale] + residual             (proj / fc2 forward)
 //   5, 6: classes 2 and 3 with QuickGELU / QuickGELU' in place of the erf GELU (the CLIP tower's fc1 forward and fc2 data gradient)
 // The results (and the saved pre-activation) are stored non-temporally.
-template <int BM, int BN, int NTHR, int EC_>
-__device__ __forceinline__ void split3_epilogue_rows_ec(const Split3Params& p, const float* Ct, int m0, int n0) {
+template <int BM, int BN, int NTHR, int EC_, bool MAP = false>
+__device__ __forceinline__ void split3_epilogue_rows_ec(const Split3Params& p, const float* Ct, int m0, int n0, S3RowMap rm = S3RowMap{}) {
+    const int Mlive = MAP ? rm.M : p.M;
+    // (MAP) physical row of C / the residual and the row-scale index of compact row m; the saved pre-activation stays compact
+    auto crow = [&](int m) -> int64_t {
+        if constexpr (MAP) { if (rm.cmap) { const int g = m / rm.rps; return (int64_t)rm.cmap[g] * rm.rps + (m - g * rm.rps); } }
+        return m;
+    };
+    auto srow = [&](int m) -> int {
+        if constexpr (MAP) { if (rm.smap) return rm.smap[m / rm.rps]; }
+        return m / p.rows_per_scale;
+    };
     constexpr int LDT = BN + 4, CPR = BN / 8, RPP = NTHR / CPR, NR = (BM + RPP - 1) / RPP;
     constexpr int ACT = (EC_ == 5 || EC_ == 6) ? 2 : 1;            // activation code of classes 2 / 3 (erf GELU) and 5 / 6 (QuickGELU)
     constexpr int EC = EC_ == 5 ? 2 : EC_ == 6 ? 3 : EC_;
@@ -127,7 +143,7 @@ __device__ __forceinline__ void split3_epilogue_rows_ec(const Split3Params& p, c
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
             const int rr = r0 + i * RPP, m = m0 + rr;
-            if (rr < BM && m < p.M) { aux[i][0] = ldg(base + (int64_t)m * ld + n); aux[i][1] = ldg(base + (int64_t)m * ld + n + 4); }
+            if (rr < BM && m < Mlive) { const int64_t ma = EC == 4 ? crow(m) : (int64_t)m; aux[i][0] = ldg(base + ma * ld + n); aux[i][1] = ldg(base + ma * ld + n + 4); }
             else aux[i][0] = aux[i][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
     }
@@ -136,9 +152,9 @@ __device__ __forceinline__ void split3_epilogue_rows_ec(const Split3Params& p, c
 #pragma unroll
     for (int i = 0; i < NR; ++i) {
         const int rr = r0 + i * RPP, m = m0 + rr;
-        if (rr >= BM || m >= p.M) break;
+        if (rr >= BM || m >= Mlive) break;
         f32x4 v0 = *reinterpret_cast<const f32x4*>(Ct + rr * LDT + chunk * 8) + b0, v1 = *reinterpret_cast<const f32x4*>(Ct + rr * LDT + chunk * 8 + 4) + b1;
-        float* const c = p.C + (int64_t)m * p.ldc + n;
+        float* const c = p.C + crow(m) * p.ldc + n;
         if constexpr (EC == 2) {
             float* const pre = p.preact + (int64_t)m * p.ldc + n;
             stg(pre, v0); stg(pre + 4, v1);
@@ -146,7 +162,7 @@ __device__ __forceinline__ void split3_epilogue_rows_ec(const Split3Params& p, c
         }
         if constexpr (EC == 3) { v0 = v0 * gg_act_grad_f32_v4(aux[i][0], ACT); v1 = v1 * gg_act_grad_f32_v4(aux[i][1], ACT); }
         if constexpr (EC == 3 || EC == 4) {
-            if (p.rowscale) { const float sc = p.rowscale[m / p.rows_per_scale]; v0 = v0 * sc; v1 = v1 * sc; }
+            if (p.rowscale) { const float sc = p.rowscale[srow(m)]; v0 = v0 * sc; v1 = v1 * sc; }
         }
         if constexpr (EC == 4) { v0 = v0 + aux[i][0]; v1 = v1 + aux[i][1]; }
         stg(c, v0); stg(c + 4, v1);
@@ -157,8 +173,9 @@ __device__ __forceinline__ void split3_epilogue_rows_ec(const Split3Params& p, c
 // a lane owns 8 consecutive columns of a row, 16 lanes one 128-column row: 512-byte f32 runs and 256-byte plane runs instead of the MFMA layout's
 // 64- / 32-byte pieces of 16 different rows per instruction (the plane-writing epilogues of fc1 / the fc2 dgrad were slower than the f32 GEMM's with those)
 // NT: result / pre-activation stores non-temporal
-template <int BM, int BN, int NTHR, bool NT = false>
-__device__ __forceinline__ void split3_epilogue_rows(const Split3Params& p, float* Ct, int m0, int n0) {
+template <int BM, int BN, int NTHR, bool NT = false, bool MAP = false>
+__device__ __forceinline__ void split3_epilogue_rows(const Split3Params& p, float* Ct, int m0, int n0, S3RowMap rm = S3RowMap{}) {
+    const int Mlive = MAP ? rm.M : p.M;
     constexpr int LDT = BN + 4;                                   // padded row: conflict-free 16-byte column writes from the MFMA layout
     constexpr int CPR = BN / 8;                                   // 8-column chunks per row
     constexpr int RPP = NTHR / CPR;                               // rows per pass
@@ -176,15 +193,19 @@ __device__ __forceinline__ void split3_epilogue_rows(const Split3Params& p, floa
     for (int j = 0; j < 8; ++j) cs[0][j] = cs[1][j] = cq[0][j] = cq[1][j] = 0.f;
     for (int rr = r0; rr < BM && live; rr += RPP) {
         const int m = m0 + rr;
-        if (m >= p.M || n >= p.N) continue;
+        if (m >= Mlive || n >= p.N) continue;
+        int64_t mc = m;                                               // (MAP) physical row of C / the residual
+        if constexpr (MAP) {
+            if (rm.cmap) { const int g = m / rm.rps; mc = (int64_t)rm.cmap[g] * rm.rps + (m - g * rm.rps); }
+        }
         float v[8];
         {
             const f32x4 a = *reinterpret_cast<const f32x4*>(Ct + rr * LDT + chunk * 8), b = *reinterpret_cast<const f32x4*>(Ct + rr * LDT + chunk * 8 + 4);
 #pragma unroll
             for (int j = 0; j < 4; ++j) { v[j] = a[j] + bv[j]; v[4 + j] = b[j] + bv[4 + j]; }
         }
-        auto ld8 = [&](const float* base, int64_t ld, float (&t)[8]) {
-            const float* q = base + (int64_t)m * ld + n;
+        auto ld8 = [&](const float* base, int64_t ld, float (&t)[8], int64_t row) {
+            const float* q = base + row * ld + n;
             if (nfull && (ld & 3) == 0) {
                 const f32x4 a = *reinterpret_cast<const f32x4*>(q), b = *reinterpret_cast<const f32x4*>(q + 4);
 #pragma unroll
@@ -194,8 +215,8 @@ __device__ __forceinline__ void split3_epilogue_rows(const Split3Params& p, floa
                 for (int j = 0; j < 8; ++j) t[j] = n + j < p.N ? q[j] : 0.f;
             }
         };
-        auto st8 = [&](float* base, int64_t ld, const float (&t)[8]) {
-            float* q = base + (int64_t)m * ld + n;
+        auto st8 = [&](float* base, int64_t ld, const float (&t)[8], int64_t row) {
+            float* q = base + row * ld + n;
             if (nfull && (ld & 3) == 0) {
                 if constexpr (NT) {
                     __builtin_nontemporal_store((f32x4){t[0], t[1], t[2], t[3]}, reinterpret_cast<f32x4*>(q));
@@ -209,11 +230,11 @@ __device__ __forceinline__ void split3_epilogue_rows(const Split3Params& p, floa
                 for (int j = 0; j < 8; ++j) if (n + j < p.N) q[j] = t[j];
             }
         };
-        if (p.preact) st8(p.preact, p.ldc, v);
+        if (p.preact) st8(p.preact, p.ldc, v, m);
         // (the packed forms: GELU / GELU' on two lanes of a v_pk_* instruction -- the scalar forms were a third of these launches' time at K = 192)
         if (p.dact_preact) {
             float t[8];
-            ld8(p.dact_preact, p.ldc, t);
+            ld8(p.dact_preact, p.ldc, t, m);
             const f32x4 g0 = gg_act_grad_f32_v4((f32x4){t[0], t[1], t[2], t[3]}, p.dact), g1 = gg_act_grad_f32_v4((f32x4){t[4], t[5], t[6], t[7]}, p.dact);
 #pragma unroll
             for (int j = 0; j < 4; ++j) { v[j] *= g0[j]; v[4 + j] *= g1[j]; }
@@ -223,17 +244,19 @@ __device__ __forceinline__ void split3_epilogue_rows(const Split3Params& p, floa
             for (int j = 0; j < 4; ++j) { v[j] = a0[j]; v[4 + j] = a1[j]; }
         }
         if (p.rowscale) {
-            const float sc = p.rowscale[m / p.rows_per_scale];
+            int ms = m / p.rows_per_scale;
+            if constexpr (MAP) { if (rm.smap) ms = rm.smap[m / rm.rps]; }      // (the scale of the PHYSICAL sample)
+            const float sc = p.rowscale[ms];
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] *= sc;
         }
         if (p.residual) {
             float t[8];
-            ld8(p.residual, p.ldr, t);
+            ld8(p.residual, p.ldr, t, mc);
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] += t[j];
         }
-        if (p.C) st8(p.C, p.ldc, v);
+        if (p.C) st8(p.C, p.ldc, v, mc);
         if (p.colstats) {
             const float hi = rr >= 128 ? 1.f : 0.f, lo = 1.f - hi;
 #pragma unroll
@@ -464,19 +487,27 @@ template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_wai
 // PRO: the A operand is a saved pre-BatchNorm convolution output and the product wants act(BatchNorm(A)) (MBConv conv3 reading BN2 + GELU of the depthwise conv): the
 // transform rides on the loader, in front of the split -- per element one FMA with the column's (scale, shift) from an LDS table + the f32-accurate GELU; with one N-tile
 // (N = 96) every element is transformed exactly once and the activation tensor is never written (the f32-MFMA form of this fusion applied it to the fragments of every wave)
-template <int TN_ = 4, int EC = 0, int PRO = 0>      // PRO: 0 off; 1 + activation code of the prologue (1 BatchNorm only, 2 + GELU, 3 + QuickGELU): compile-time, so a stage carries one activation's code
+// MAP: row compaction (Split3Params.groups_dev / a_map / c_map).  The grid is sized for all M rows; the live row count is read from device memory, the workgroups beyond
+// the live tiles return first thing and the XCD walk is taken over the live tiles only (so that every XCD keeps an equal share).  The A-row map is applied once per tile,
+// where the loader forms its row offsets; the k-loop is the unmapped kernel's.
+template <int TN_ = 4, int EC = 0, int PRO = 0, bool MAP = false>      // PRO: 0 off; 1 + activation code of the prologue (1 BatchNorm only, 2 + GELU, 3 + QuickGELU): compile-time, so a stage carries one activation's code
 __global__ __launch_bounds__(512) void gemm_nt_split3a_kernel(Split3Params p) {
     constexpr int TN = TN_, BM = 256, BN = 32 * TN, WN = 2, NW = 8, TM = 4;
     constexpr int TA = BM * S3_SK, TB = BN * S3_SK, STAGE = 3 * (TA + TB);
     extern __shared__ __attribute__((aligned(16))) bf16 s3mem[];
-    const int tiles = p.tilesM * p.tilesN;
+    int tiles = p.tilesM * p.tilesN, Mlive = p.M;
+    if constexpr (MAP) {
+        Mlive = min(p.M, max(*p.groups_dev, 0) * p.group_rows);
+        tiles = ((Mlive + BM - 1) / BM) * p.tilesN;
+        if ((int)blockIdx.x >= tiles) return;
+    }
     const int bid = gg_xcd_remap(blockIdx.x, tiles);
     const int tm = bid / p.tilesN, tn = bid % p.tilesN;
     const int m0 = tm * BM, n0 = tn * BN;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int lr = lane & 15, lg = lane >> 4;
-    const unsigned rowsA = (unsigned)min(p.M - m0, BM), rowsB = (unsigned)min(p.N - n0, BN);
+    const unsigned rowsA = (unsigned)min(Mlive - m0, BM), rowsB = (unsigned)min(p.N - n0, BN);
     // B planes: 16-row slices by LDS-DMA (one per plane and wave: 8 slices = 128 rows), source chunk = slot ^ ((row >> 2) & 3)
     const int dchunk = (lane & 3) ^ s3_swz(lane >> 4);
     __amdgpu_buffer_rsrc_t rsB[3];
@@ -485,7 +516,10 @@ __global__ __launch_bounds__(512) void gemm_nt_split3a_kernel(Split3Params p) {
         rsB[i] = __builtin_amdgcn_make_buffer_rsrc((void*)(p.B + i * p.plane_b + (int64_t)n0 * p.ldb), 0, (int)(rowsB * (unsigned)p.ldb * 2u), 0x00020000);
     const unsigned voffB = (unsigned)(wave * 16 + (lane >> 2)) * (unsigned)p.ldb * 2u + dchunk * 16u;
     // A: thread -> f32x4 number kq of rows (tid >> 3) + 64 j; its bf16x4 goes to chunk (kq >> 1) ^ ((row >> 2) & 3), half kq & 1 of the plane row
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)(p.Af + (int64_t)m0 * p.ldaf), 0, (int)(rowsA * (unsigned)p.ldaf * 4u), 0x00020000);
+    // (a mapped A: the descriptor spans the whole physical tensor -- M rows, the host checks the 2 GiB range -- and a row's offset is its physical row's)
+    const bool amap = MAP && p.a_map != nullptr;
+    const __amdgpu_buffer_rsrc_t rsA = amap ? __builtin_amdgcn_make_buffer_rsrc((void*)p.Af, 0, (int)((unsigned)p.M * (unsigned)p.ldaf * 4u), 0x00020000)
+                                            : __builtin_amdgcn_make_buffer_rsrc((void*)(p.Af + (int64_t)m0 * p.ldaf), 0, (int)(rowsA * (unsigned)p.ldaf * 4u), 0x00020000);
     const int kq = threadIdx.x & 7, arow = threadIdx.x >> 3;
     unsigned voffA[4];
     int ldsA[4];
@@ -493,6 +527,12 @@ __global__ __launch_bounds__(512) void gemm_nt_split3a_kernel(Split3Params p) {
     for (int j = 0; j < 4; ++j) {
         const int row = arow + 64 * j;
         voffA[j] = (unsigned)row * (unsigned)p.ldaf * 4u + kq * 16u;
+        if constexpr (MAP) {
+            if (amap) {
+                const int m = m0 + row, g = min(m, Mlive - 1) / p.group_rows;      // (Mlive > m0 >= 0 here; rows beyond the live extent: no access, zeros)
+                voffA[j] = m < Mlive ? (unsigned)(p.a_map[g] * p.group_rows + (m - g * p.group_rows)) * (unsigned)p.ldaf * 4u + kq * 16u : 0xFFFFFFF0u;
+            }
+        }
         ldsA[j] = row * S3_SK + (((kq >> 1) ^ s3_swz((row >> 2) & 3)) << 3) + ((kq & 1) << 2);
     }
     // PRO: (scale, shift) per contraction column behind the ring: [2][KT] floats, zero beyond K (the masked stages then transform zeros into act(0) = 0)
@@ -640,8 +680,14 @@ __global__ __launch_bounds__(512) void gemm_nt_split3a_kernel(Split3Params p) {
         for (int mt = 0; mt < TM; ++mt)
             *reinterpret_cast<f32x4*>(Ct + (wm * 64 + mt * 16 + lr) * (BN + 4) + wn * 16 * TN + nt * 16 + lg * 4) = acc[nt][mt];
     __syncthreads();
-    if constexpr (EC == 0) split3_epilogue_rows<BM, BN, 512, true>(p, Ct, m0, n0);      // (non-temporal result stores)
-    else split3_epilogue_rows_ec<BM, BN, 512, EC>(p, Ct, m0, n0);
+    if constexpr (MAP) {
+        const S3RowMap rm = {Mlive, p.c_map, p.c_map ? p.c_map : p.a_map, p.group_rows};
+        if constexpr (EC == 0) split3_epilogue_rows<BM, BN, 512, true, true>(p, Ct, m0, n0, rm);
+        else split3_epilogue_rows_ec<BM, BN, 512, EC, true>(p, Ct, m0, n0, rm);
+    } else {
+        if constexpr (EC == 0) split3_epilogue_rows<BM, BN, 512, true>(p, Ct, m0, n0);      // (non-temporal result stores)
+        else split3_epilogue_rows_ec<BM, BN, 512, EC>(p, Ct, m0, n0);
+    }
 }
 
 // The same product on a 128 x 128 tile with FOUR waves (2 x 2 of 64 x 64) and 72 KB of LDS, so that TWO workgroups share a CU: with one 144 KB workgroup per CU
@@ -1039,6 +1085,8 @@ extern "C" int gg_gemm_nt_split3_ex(const GgSplit3Args* a, void* stream) {
     p.C = a->C; p.ldc = a->ldc ? a->ldc : a->N; p.bias = a->bias; p.M = a->M; p.N = a->N; p.K = a->K;
     p.act = a->act; p.preact = a->preact; p.rowscale = a->rowscale; p.rows_per_scale = a->rows_per_scale; p.residual = a->residual; p.ldr = a->ldr;
     p.dact_preact = a->dact_preact; p.dact = a->dact; p.c_planes = (bf16*)a->c_planes; p.ldp = a->ldp; p.colstats = nullptr;
+    GG_CHECK(!a->groups_dev && !a->a_map && !a->c_map, "gg_gemm_nt_split3: row compaction is a form of gg_gemm_nt_split3_af32 only");
+    p.groups_dev = nullptr; p.group_rows = 0; p.a_map = p.c_map = nullptr;
     return split3_launch(p, stream);
 }
 
@@ -1071,6 +1119,20 @@ extern "C" int gg_gemm_nt_split3_af32_pro(const GgSplit3Args* a, const float* A,
     GG_CHECK(!(a->bias || a->act || a->rowscale || a->residual || a->dact_preact || a->preact || a->c_planes), "gg_gemm_nt_split3_af32_pro: plain epilogue only");
     return split3_af32_launch(a, A, lda, b_plane_stride, colstats, bn_stat, bn_gamma, bn_beta, bn_act, stream);
 }
+// the tile form split3_af32_launch picks for (N, K) without a prologue: 256-row tiles from K = 384 on, 96-column tiles where they save a fifth of the columns
+static void split3_af32_form(int N, int K, bool& big, bool& n96) {
+    static const char* tenv = gg_dev_env("GG_SPLIT3A_TILE");      // dev: 256 / 128 forces one form
+    big = tenv ? atoi(tenv) == 256 : K >= 384;
+    static const char* nenv = gg_dev_env("GG_SPLIT3A_BN");          // dev: 96 / 128 forces one width
+    const double w128 = 1.0 - (double)N / ((double)gg_cdiv(N, 128) * 128), w96 = 1.0 - (double)N / ((double)gg_cdiv(N, 96) * 96);
+    n96 = nenv ? atoi(nenv) == 96 : (w128 - w96 >= 0.2);
+}
+// (csrc/tinyvit.hip asks before it plans a compacted block)
+bool gg_split3_af32_takes_rowmap(int N, int K) {
+    bool big, n96;
+    split3_af32_form(N, K, big, n96);
+    return big && !n96;
+}
 static int split3_af32_launch(const GgSplit3Args* a, const float* A, int64_t lda, int64_t b_plane_stride, float* colstats, const float* bn_stat, const float* bn_gamma,
                               const float* bn_beta, int bn_act, void* stream) {
     GG_CHECK(a && A && a->b_planes && (a->C || a->c_planes) && a->M > 0 && a->N > 0 && a->K > 0, "gg_gemm_nt_split3_af32: null pointer / bad shape");
@@ -1084,8 +1146,18 @@ static int split3_af32_launch(const GgSplit3Args* a, const float* A, int64_t lda
     GG_CHECK(!colstats || !(a->bias || a->act || a->rowscale || a->residual || a->dact_preact || a->preact || a->c_planes), "gg_gemm_nt_split3_af32: colstats needs the plain epilogue");
     GG_CHECK(((uintptr_t)a->preact & 15) == 0 && ((uintptr_t)a->residual & 15) == 0 && ((uintptr_t)a->dact_preact & 15) == 0,
              "gg_gemm_nt_split3_af32: preact, residual and dact_preact must be 16-byte aligned (the row epilogue moves them 16 bytes at a time)");
+    // row compaction: the device-side live row count and the optional row maps (the 256 x 128 form without prologue, 128-column tiles, f32 result)
+    const bool mapped = a->groups_dev != nullptr;
+    GG_CHECK(mapped || (!a->a_map && !a->c_map), "gg_gemm_nt_split3_af32: a_map / c_map need groups_dev");
+    if (mapped) {
+        GG_CHECK(a->group_rows > 0 && a->M % a->group_rows == 0, "gg_gemm_nt_split3_af32: groups_dev needs group_rows > 0 that divides M");
+        GG_CHECK(a->C && !a->c_planes && !colstats && !bn_stat, "gg_gemm_nt_split3_af32: row compaction takes the f32 result only (no planes, column statistics or prologue)");
+        GG_CHECK(!a->rowscale || !(a->a_map || a->c_map) || a->rows_per_scale == a->group_rows, "gg_gemm_nt_split3_af32: with a row map the row scale is per group (rows_per_scale == group_rows)");
+        GG_CHECK(!a->a_map || (int64_t)a->M * lda * 4 < ((int64_t)1 << 31), "gg_gemm_nt_split3_af32: a mapped A must stay below 2 GiB");
+    }
     Split3Params p;
     p.colstats = colstats;
+    p.groups_dev = a->groups_dev; p.group_rows = a->group_rows; p.a_map = a->a_map; p.c_map = a->c_map;
     p.a_stat = bn_stat; p.a_gamma = bn_gamma; p.a_beta = bn_beta; p.a_act = bn_act;
     const bool pro = bn_stat != nullptr;
     p.A = nullptr; p.lda = 0; p.plane_a = 0; p.Af = A; p.ldaf = lda;
@@ -1095,14 +1167,13 @@ static int split3_af32_launch(const GgSplit3Args* a, const float* A, int64_t lda
     p.dact_preact = a->dact_preact; p.dact = a->dact; p.c_planes = (bf16*)a->c_planes; p.ldp = a->ldp;
     // 256 x 128 (one 144 KB workgroup per CU) from K = 384 on; 128 x 128 (two per CU) for the short contractions of stage 1, where a tile lives only 6 stages and
     // the second workgroup hides its prologue / epilogue (K = 192: 1.30 x against 1.22 x the f32-MFMA GEMM; at K >= 384 the big tile wins by 1-2 %)
-    static const char* tenv = gg_dev_env("GG_SPLIT3A_TILE");      // dev: 256 / 128 forces one form
-    const bool big = pro || (tenv ? atoi(tenv) == 256 : p.K >= 384);
     // 96-column tiles where 128-column ones would waste a fifth or more of their work on columns beyond N that 96-column ones do not (N = 192: 25 % -> -8...-11 %
     // in time; N = 576, 10 %: the narrower tile's higher LDS traffic per MFMA costs more than the waste)
-    static const char* nenv = gg_dev_env("GG_SPLIT3A_BN");          // dev: 96 / 128 forces one width
-    const double w128 = 1.0 - (double)p.N / ((double)gg_cdiv(p.N, 128) * 128), w96 = 1.0 - (double)p.N / ((double)gg_cdiv(p.N, 96) * 96);
-    const bool n96 = nenv ? atoi(nenv) == 96 : (w128 - w96 >= 0.2);
+    bool big, n96;
+    split3_af32_form(p.N, p.K, big, n96);
+    big = big || pro;
     const int bn = n96 ? 96 : 128;
+    GG_CHECK(!mapped || (big && !n96), "gg_gemm_nt_split3_af32: row compaction runs on the 256 x 128 form only (K >= 384, N not better served by 96-column tiles; got N %d K %d)", p.N, p.K);
     p.tilesM = (int)gg_cdiv(p.M, big ? 256 : 128); p.tilesN = (int)gg_cdiv(p.N, bn);
     // epilogue class (split3_epilogue_rows_ec) when the shape takes the vector path and the options are one of the models' six combinations; 0 = the generic epilogue
     static const char* eenv = gg_dev_env("GG_SPLIT3_NO_EC");       // dev: the generic epilogue everywhere
@@ -1118,14 +1189,21 @@ static int split3_af32_launch(const GgSplit3Args* a, const float* A, int64_t lda
                                             : (bn_act == 1 ? gemm_nt_split3a_kernel<4, 0, 2> : bn_act == 2 ? gemm_nt_split3a_kernel<4, 0, 3> : gemm_nt_split3a_kernel<4, 0, 1>)) :
                                  !big ? (n96 ? S3_EC(gemm_nt_split3b_kernel, 3) : S3_EC(gemm_nt_split3b_kernel, 4)) :
                                         (n96 ? S3_EC(gemm_nt_split3a_kernel, 3) : S3_EC(gemm_nt_split3a_kernel, 4));
+    if (mapped) {
+        if (ec > 4) ec = 0;                                         // (the QuickGELU classes have no compacted user: the generic epilogue serves them)
+        kern = ec == 1 ? gemm_nt_split3a_kernel<4, 1, 0, true> : ec == 2 ? gemm_nt_split3a_kernel<4, 2, 0, true> : ec == 3 ? gemm_nt_split3a_kernel<4, 3, 0, true> :
+               ec == 4 ? gemm_nt_split3a_kernel<4, 4, 0, true> : gemm_nt_split3a_kernel<4, 0, 0, true>;
+    }
 #undef S3_EC
     const size_t lds = (big ? (size_t)2 * 3 * (256 + bn) * S3_SK * sizeof(bf16) : (size_t)3 * (128 + 2 * bn) * S3_SK * sizeof(bf16)) +
                        (pro ? (size_t)2 * (((p.K + 31) & ~31) + 3 * S3_SK) * sizeof(float) : 0);
     GG_CHECK(lds <= 160 * 1024, "gg_gemm_nt_split3_af32: the ring plus the prologue table exceed the LDS");
     GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(kern)));
-    const double mn = (double)p.M * p.N;
-    GG_PROF(GG_CAT_GEMM | GG_CAT_SPLIT_FLAG, 2.0 * p.M * (double)p.N * p.K,
-            4.0 * (double)p.M * p.K + 6.0 * (double)p.N * p.K + 4.0 * mn * ((p.C != nullptr) + (p.preact != nullptr) + (p.residual != nullptr) + (p.dact_preact != nullptr)) +
+    // (declared work: the live rows' -- while the profiling hooks are on the count is read back, a blocking copy)
+    const double Mp = mapped ? (double)gg_prof_live_groups(a->groups_dev, p.M / a->group_rows, stream) * a->group_rows : (double)p.M;
+    const double mn = Mp * p.N;
+    GG_PROF(GG_CAT_GEMM | GG_CAT_SPLIT_FLAG, 2.0 * Mp * (double)p.N * p.K,
+            4.0 * Mp * p.K + 6.0 * (double)p.N * p.K + 4.0 * mn * ((p.C != nullptr) + (p.preact != nullptr) + (p.residual != nullptr) + (p.dact_preact != nullptr)) +
                 (p.c_planes ? 6.0 * mn : 0.0), stream);
     hipLaunchKernelGGL(kern, dim3((unsigned)(p.tilesM * p.tilesN)), dim3(big ? 512 : 256), lds, (hipStream_t)stream, p);
     GG_LAUNCH_CHECK();

@@ -6,6 +6,7 @@
 // Backward:  bn_bwd_reduce (dz, per-channel sum g, sum g*xhat)  ->  bn_bwd_finalize  ->  bn_bwd_apply.
 #include "common.h"
 #include "../../include/gg.h"
+#include "../../include/gg_drop.h"
 
 // storage-type helpers: 8 consecutive elements per lane (16 bytes of bf16, 32 bytes of f32)
 template <typename T> struct Vec8;
@@ -337,13 +338,17 @@ __device__ __forceinline__ float gg_group16_sum(float v) {
 template <typename T> __device__ __forceinline__ float ln_round(float v) { return sizeof(T) == 2 ? (float)(bf16)v : v; }   // storage rounding of T
 // PL3 (experiment, DESIGN.md 5 "the bf16 x 3 split"): the result leaves as three bf16 planes [3][M][C] (o = p1 + p2 + p3 to 24 bits) for gg_gemm_nt_split3
 // instead of one f32 tensor: 6 instead of 4 bytes per element written by a kernel that reads 4
-template <typename T, int NCH, bool BNIN = false, bool PL3 = false>
+// MAP (DropPath row compaction, BNIN only): pos[sample] is the sample's index among the kept ones or -1 (gg_drop_kept_lists).  xout, mean and rstd are written for every
+// row; `out` only for the kept samples' rows, at compact row pos * rps + (row within the sample); a dropped sample's BN(y) rows are also copied to xcopy (the block's
+// output: its MLP branch contributes nothing), when given.
+template <typename T, int NCH, bool BNIN = false, bool PL3 = false, bool MAP = false>
 __global__ __launch_bounds__(256) void layernorm_fwd_g16_kernel(const T* __restrict__ x, const float* __restrict__ gamma,
                                                                 const float* __restrict__ beta, int64_t M, int C, float eps,
                                                                 T* __restrict__ out, float* __restrict__ mean_out,
                                                                 float* __restrict__ rstd_out, const float* __restrict__ bn_stat = nullptr,
                                                                 const float* __restrict__ bn_gamma = nullptr,
-                                                                const float* __restrict__ bn_beta = nullptr, T* __restrict__ xout = nullptr) {
+                                                                const float* __restrict__ bn_beta = nullptr, T* __restrict__ xout = nullptr,
+                                                                const int* __restrict__ pos = nullptr, int rps = 1, T* __restrict__ xcopy = nullptr) {
     const int l16 = threadIdx.x & 15;
     const int nch = C >> 3;
     float g[NCH][8], b[NCH][8];
@@ -365,6 +370,13 @@ __global__ __launch_bounds__(256) void layernorm_fwd_g16_kernel(const T* __restr
     const float invC = 1.f / (float)C;
     for (int64_t m = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4); m < M; m += (int64_t)gridDim.x * 16) {
         float v[NCH][8];
+        int64_t mo = m;                                               // row of `out`
+        bool kept = true;
+        if constexpr (MAP) {
+            const int smp = (int)m / rps, c = pos[smp];
+            kept = c >= 0;
+            mo = (int64_t)c * rps + ((int)m - smp * rps);
+        }
 #pragma unroll
         for (int k = 0; k < NCH; ++k) {
             const int ch = l16 + 16 * k;
@@ -382,6 +394,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_g16_kernel(const T* __restr
                     v[k][j + 4] = ln_round<T>(v[k][j + 4] * s1[j] + h1[j]);
                 }
                 Vec8<T>::store(xout + m * C + ch * 8, v[k]);
+                if constexpr (MAP) { if (!kept && xcopy) Vec8<T>::store(xcopy + m * C + ch * 8, v[k]); }
             }
         }
         float s = 0.f;
@@ -417,8 +430,8 @@ __global__ __launch_bounds__(256) void layernorm_fwd_g16_kernel(const T* __restr
                     *reinterpret_cast<bf16x8*>(pl + m * C + ch * 8) = p1;
                     *reinterpret_cast<bf16x8*>(pl + M * C + m * C + ch * 8) = p2;
                     *reinterpret_cast<bf16x8*>(pl + 2 * M * C + m * C + ch * 8) = p3;
-                } else
-                Vec8<T>::store(out + m * C + ch * 8, o);
+                } else if (kept)
+                Vec8<T>::store(out + mo * C + ch * 8, o);
             }
         }
         if (mean_out && l16 == 0) { mean_out[m] = mean; rstd_out[m] = rstd; }
@@ -427,12 +440,15 @@ __global__ __launch_bounds__(256) void layernorm_fwd_g16_kernel(const T* __restr
 // backward, same geometry.  PARAMS 1: accumulate (sum dout*xhat, sum dout) per channel -> part [gridDim.x][2][C] (the LayerNorm's own
 // parameter gradients).  PARAMS 2: accumulate (sum dx*x, sum dx) of the RESULT dx against the raw input x instead -- the column sums the
 // BatchNorm in front of this LayerNorm needs for its backward (gg_bn_bwd_coef_from_x), so that no separate reduce pass reads dx again
-template <typename T, int NCH, int PARAMS>
+// MAP (DropPath row compaction; PARAMS 0 or 2): dout holds only the kept samples' rows, compact (row pos[sample] * rps + row within the sample); a dropped sample's rows
+// stand for dout = 0 -- the zeros the uncompacted branch hands over -- without reading it: dx = dres there.  PARAMS 2 adds their column-sum terms as the uncompacted
+// kernel forms them (x, mean and rstd are read; same order); PARAMS 0 reads nothing but dres.  The kept rows run the unmapped kernel's row body unchanged.
+template <typename T, int NCH, int PARAMS, bool MAP = false>
 __global__ __launch_bounds__(256) void layernorm_bwd_g16_kernel(const T* __restrict__ dout, const T* __restrict__ x,
                                                                 const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
                                                                 const float* __restrict__ gamma, int64_t M, int C,
                                                                 const T* __restrict__ dres, T* __restrict__ dx,
-                                                                float* __restrict__ part) {
+                                                                float* __restrict__ part, const int* __restrict__ pos = nullptr, int rps = 1) {
     extern __shared__ float sred[];   // [4 waves][2][C] when PARAMS
     const int l16 = threadIdx.x & 15;
     const int nch = C >> 3;
@@ -453,13 +469,46 @@ __global__ __launch_bounds__(256) void layernorm_bwd_g16_kernel(const T* __restr
     const float invC = 1.f / (float)C;
     for (int64_t m = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4); m < M; m += (int64_t)gridDim.x * 16) {
         float xh[NCH][8], dxh[NCH][8], rr[NCH][8];
+        int64_t md = m;                                               // row of dout
+        bool kept = true;
+        if constexpr (MAP) {
+            const int smp = (int)m / rps, c = pos[smp];
+            kept = c >= 0;
+            md = (int64_t)c * rps + ((int)m - smp * rps);
+        }
+        if constexpr (MAP) {
+            if (!kept) {
+                // a dropped sample's row: with dout = 0 the arithmetic below gives dx = 0 + dres, and the column-sum terms of that dx against the input as the
+                // kernel reconstructs it (explicit fused operations only: nothing here is left to the compiler's contraction)
+                float mean = 0.f, rstd = 1.f, inv_rstd = 1.f;
+                if (PARAMS == 2) { mean = mean_in[m]; rstd = rstd_in[m]; inv_rstd = 1.f / rstd; }
+#pragma unroll
+                for (int k = 0; k < NCH; ++k) {
+                    const int ch = l16 + 16 * k;
+                    if (ch < nch) {
+                        float o[8], xr[8];
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) o[j] = xr[j] = 0.f;
+                        if (dres) Vec8<T>::load(dres + m * C + ch * 8, o);
+                        if (PARAMS == 2) Vec8<T>::load(x + m * C + ch * 8, xr);
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) {
+                            o[j] += 0.f;
+                            if (PARAMS == 2) { dg[k][j] = fmaf(o[j], fmaf((xr[j] - mean) * rstd, inv_rstd, mean), dg[k][j]); db[k][j] += o[j]; }
+                        }
+                        Vec8<T>::store(dx + m * C + ch * 8, o);
+                    }
+                }
+                continue;
+            }
+        }
 #pragma unroll
         for (int k = 0; k < NCH; ++k) {
             const int ch = l16 + 16 * k;
             const bool ok = ch < nch;
             if (ok) {
                 Vec8<T>::load(x + m * C + ch * 8, xh[k]);
-                Vec8<T>::load(dout + m * C + ch * 8, dxh[k]);
+                Vec8<T>::load(dout + md * C + ch * 8, dxh[k]);
                 if (dres) Vec8<T>::load(dres + m * C + ch * 8, rr[k]);
             } else {
 #pragma unroll
@@ -952,6 +1001,77 @@ extern "C" int gg_layernorm_bwd_colsum(const void* dout, const void* x, int f32,
     switch ((C / 8 + 15) / 16) { case 1: GG_LN_BWD(1); break; case 2: GG_LN_BWD(2); break; case 3: GG_LN_BWD(3); break; case 4: GG_LN_BWD(4); break; default: GG_LN_BWD(5); }
 #undef GG_LN_BWD
 #undef GG_LN_BWD2
+    GG_LAUNCH_CHECK();
+    return 0;
+}
+// ------------------------------------------------------------------------------------------- DropPath row compaction (include/gg.h)
+// One workgroup per slot: kept <=> scale != 0.  Every thread counts the kept samples of its contiguous run of the batch, a block scan turns the counts into
+// offsets, and the thread writes its run's indices in ascending order -- no atomics, so the lists (and every column sum taken in their order) are deterministic.
+__global__ __launch_bounds__(256) void drop_kept_lists_kernel(const float* __restrict__ scales, int batch, int stride, int* __restrict__ lists) {
+    __shared__ int cnt[256];
+    const float* sc = scales + (int64_t)blockIdx.x * batch;
+    int* L = lists + (int64_t)blockIdx.x * stride;
+    const int per = (batch + 255) / 256, b0 = min((int)threadIdx.x * per, batch), b1 = min(b0 + per, batch);
+    int n = 0;
+    for (int b = b0; b < b1; ++b) n += sc[b] != 0.f;
+    cnt[threadIdx.x] = n;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {                             // inclusive Hillis-Steele scan
+        const int v = (int)threadIdx.x >= d ? cnt[threadIdx.x - d] : 0;
+        __syncthreads();
+        cnt[threadIdx.x] += v;
+        __syncthreads();
+    }
+    int o = cnt[threadIdx.x] - n;
+    for (int b = b0; b < b1; ++b) {
+        const bool k = sc[b] != 0.f;
+        L[GG_DROP_LIST_HEAD + batch + b] = k ? o : -1;
+        if (k) L[GG_DROP_LIST_HEAD + o++] = b;
+    }
+    if (threadIdx.x == 255) { L[0] = cnt[255]; L[1] = batch; L[2] = L[3] = 0; }
+}
+extern "C" int gg_drop_list_ints(int batch) { return batch > 0 ? GG_DROP_LIST_HEAD + 2 * (int)gg_align(batch, 4) : -1; }
+extern "C" int gg_drop_kept_lists(const float* scales, int slots, int batch, int* lists, void* stream) {
+    GG_CHECK(scales && lists && slots > 0 && batch > 0, "gg_drop_kept_lists: bad args");
+    // (a list is [count, batch, 0, 0][kept: batch][pos: batch]; the stride rounds the batch up to 4 -- the two arrays sit back to back at the batch itself)
+    hipLaunchKernelGGL(drop_kept_lists_kernel, dim3((unsigned)slots), dim3(256), 0, (hipStream_t)stream, scales, batch, gg_drop_list_ints(batch), lists);
+    GG_LAUNCH_CHECK();
+    return 0;
+}
+// gg_layernorm_fwd_bn_f32 under row compaction: `out` compact (kept samples only), xout / mean / rstd for every row, xcopy (optional) := xout on the dropped samples' rows
+extern "C" int gg_layernorm_fwd_bn_f32_map(const float* y, const float* bn_stat, const float* bn_gamma, const float* bn_beta, float* xout, const float* gamma,
+                                           const float* beta, int64_t M, int C, float eps, float* out, float* mean, float* rstd, const int* pos, int rows_per_sample,
+                                           float* xcopy, void* stream) {
+    GG_CHECK(y && bn_stat && bn_gamma && bn_beta && xout && gamma && beta && out && mean && rstd && pos && M > 0 && (C & 7) == 0, "gg_layernorm_fwd_bn_f32_map: bad args");
+    GG_CHECK(rows_per_sample > 0 && M % rows_per_sample == 0 && M < ((int64_t)1 << 31), "gg_layernorm_fwd_bn_f32_map: M must be whole samples, below 2^31 rows");
+    const int nchl = (C / 8 + 15) / 16;
+    GG_CHECK(nchl <= 5, "gg_layernorm_fwd_bn_f32_map: C <= 640");
+    GG_PROF(GG_CAT_NORM, 0, 12.0 * M * C, stream);
+    const dim3 g16((unsigned)std::min<int64_t>(gg_cdiv(M, 16), 8192)), block(256);
+    hipStream_t s = (hipStream_t)stream;
+#define GG_LN_FWD(N_) hipLaunchKernelGGL((layernorm_fwd_g16_kernel<float, N_, true, false, true>), g16, block, 0, s, y, gamma, beta, M, C, eps, out, mean, rstd, bn_stat, bn_gamma, bn_beta, xout, pos, rows_per_sample, xcopy)
+    switch (nchl) { case 1: GG_LN_FWD(1); break; case 2: GG_LN_FWD(2); break; case 3: GG_LN_FWD(3); break; case 4: GG_LN_FWD(4); break; default: GG_LN_FWD(5); }
+#undef GG_LN_FWD
+    GG_LAUNCH_CHECK();
+    return 0;
+}
+// gg_layernorm_bwd (no parameter gradients; part == NULL) / gg_layernorm_bwd_colsum (part given) under row compaction, f32: dout compact, x / dres / dx physical;
+// the launch geometry and the order of the column partials are the unmapped calls'
+extern "C" int gg_layernorm_bwd_map(const float* dout, const float* x, const float* mean, const float* rstd, const float* gamma, int64_t M, int C, const float* dres,
+                                    float* dx, float* part, const int* pos, int rows_per_sample, void* stream) {
+    GG_CHECK(dout && x && mean && rstd && gamma && dx && pos && M > 0 && (C & 7) == 0 && C <= 640, "gg_layernorm_bwd_map: bad args (C %% 8, C <= 640)");
+    GG_CHECK(rows_per_sample > 0 && M % rows_per_sample == 0 && M < ((int64_t)1 << 31), "gg_layernorm_bwd_map: M must be whole samples, below 2^31 rows");
+    const int nb = part ? gg_layernorm_bwd_colsum_rows(M) : ln_blocks(M);
+    GG_PROF(GG_CAT_NORM, 0, (dres ? 4.0 : 3.0) * 4.0 * M * C, stream);
+    const size_t lds = part ? (size_t)4 * 2 * C * sizeof(float) : 0;
+    hipStream_t s = (hipStream_t)stream;
+#define GG_LN_BWD(N_)                                                                                                                                              \
+    do {                                                                                                                                                           \
+        if (part) hipLaunchKernelGGL((layernorm_bwd_g16_kernel<float, N_, 2, true>), dim3(nb), dim3(256), lds, s, dout, x, mean, rstd, gamma, M, C, dres, dx, part, pos, rows_per_sample); \
+        else hipLaunchKernelGGL((layernorm_bwd_g16_kernel<float, N_, 0, true>), dim3(nb), dim3(256), 0, s, dout, x, mean, rstd, gamma, M, C, dres, dx, part, pos, rows_per_sample);     \
+    } while (0)
+    switch ((C / 8 + 15) / 16) { case 1: GG_LN_BWD(1); break; case 2: GG_LN_BWD(2); break; case 3: GG_LN_BWD(3); break; case 4: GG_LN_BWD(4); break; default: GG_LN_BWD(5); }
+#undef GG_LN_BWD
     GG_LAUNCH_CHECK();
     return 0;
 }

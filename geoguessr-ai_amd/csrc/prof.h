@@ -9,3 +9,6 @@ struct GgProfScope {
     int idx_; void* stream_;
 };
 #define GG_PROF(cat, flops, bytes, stream) GgProfScope gg_prof_scope_((cat), (double)(flops), (double)(bytes), (stream))
+// Row compaction (kernels whose live extent is a device-side count): the count the roofline should price a launch by -- `full` unless the profiling hooks are
+// on and the stream is not capturing; then the device value, read back with a blocking copy behind the stream's earlier work.
+int gg_prof_live_groups(const int* count_dev, int full, void* stream);

@@ -10,12 +10,19 @@
 #include <string.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <atomic>
 #include "common.h"
 #include "graph.h"
 #include "../../include/gg.h"
 #include "../../include/gg_cls.h"
+#include "../../include/gg_drop.h"
+
+bool gg_split3_af32_takes_rowmap(int N, int K);      // gemm_split3.hip: the form gg_gemm_nt_split3_af32 would run this shape on accepts row compaction
 
 namespace {
+
+// DropPath row compaction of frozen stage-2 blocks (gg_tinyvit_set_drop_compact; block_compacts below)
+std::atomic<int> g_drop_compact{1};
 
 struct TensorInfo { std::string name; int64_t offset; int64_t numel; int ndim; int64_t shape[4]; int kind; };
 static const float kAttnScale = 0.17677669529663687f;   // head_dim 32 ^ -0.5; the expanded bias tables are divided by it
@@ -318,6 +325,7 @@ struct Layout {
     // scratch
     int64_t statpart, bnscratch, lnscratch, colsum, splitk, attn_ds = -1, G[5];
     int64_t foldw, foldb;        // BatchNorm-backward-folded dgrad weights bf16 [Cin][2*Cout] and bias f32 [Cin]
+    int64_t colsum_bytes = 0;    // (scratch.colsum also holds the two kept lists of a compacted block while that block runs: block_compacts)
     int64_t gbytes;
 };
 
@@ -451,7 +459,8 @@ static void plan_build(const Model& m, int B, Plan& p, Layout& L) {
         }
         L.bnscratch = p.alloc("scratch.bn", std::max(bnsmax, dwmax), false);
         L.lnscratch = p.alloc("scratch.ln", lnsmax, false);
-        L.colsum = p.alloc("scratch.colsum", std::max<int64_t>(csmax, 1024), false);
+        L.colsum_bytes = std::max<int64_t>(csmax, 1024);
+        L.colsum = p.alloc("scratch.colsum", L.colsum_bytes, false);
         L.splitk = p.alloc("scratch.splitk", (int64_t)128 << 20, false);      // gg_gemm_tn_f32_splits sizes its slabs against this
         if (m.f32) {     // dS hand-off between the two passes of the flash attention backward (GgAttnArgs.ds_scratch): the largest stage decides
             // only windows beyond 256 tokens use it (the single-pass backward keeps dS on the CU), and only while it stays a small part of the workspace:
@@ -538,6 +547,7 @@ struct Exec {
     // activation recompute: the backward runs a segment's forward body again (mbconv_fwd / merge_fwd / block_fwd) -- no BatchNorm statistics are
     // finalised (the forward's .stat checkpoints are reused, the running buffers are not touched) and the segment's output is not rewritten
     bool replay = false;
+    bool compact = false;   // DropPath row compaction is on for this call (the process-global switch, read once per call)
     void done(int stage) const { if (stage_done) stage_done(stage, stage_user); }
     bool f32;               // reference-precision mode: f32 activations / cached weights, f32 MFMA
     Exec(const Model& model, const Layout& layout, int batch, bool train) : m(&model), L(&layout), B(batch), training(train), f32(model.f32) {}
@@ -551,7 +561,12 @@ struct Exec {
     const act_t* Wt(const DenseW& w) const { return reinterpret_cast<const act_t*>(wc + w.wt); }
     const float* Taps(const DwW& w) const { return reinterpret_cast<const float*>(wc + w.taps); }
     const float* dropv(int slot) const { return drop ? drop + (int64_t)slot * B : nullptr; }
+    // the kept lists of the block that is running (k = 0: its attention slot, 1: its MLP slot): [count, ...][kept][pos] (include/gg_drop.h).  They live in
+    // scratch.colsum, which only the bias gradients of TRAINABLE Linears use: a compacted block is frozen, so nothing touches the region while it runs
+    int* drop_list(int k) const { return reinterpret_cast<int*>(ws + L->colsum) + (int64_t)k * gg_drop_list_ints(B); }
 };
+// Row compaction of one Linear launch: the slot's kept list and which side(s) go through the row map (GgSplit3Args.groups_dev / a_map / c_map)
+struct RowMap { const int* list; int rps; bool a, c; };
 
 // 1x1-conv dgrad straight from (dz, y): BatchNorm backward's apply step is folded into the weights (gg_bn_bwd_fold_weights)
 static int gemm_folded_dgrad(const Exec& e, const DenseW& w, const act_t* dz, const act_t* y, const float* coef, const float* stat,
@@ -590,7 +605,7 @@ static const Model::PlaneOf* planes_of(const Exec& e, const act_t* W, int64_t ld
 }
 static int gemm(const Exec& e, const act_t* A, int64_t lda, const act_t* Bm, int64_t ldb, void* C, int64_t ldc, int64_t M, int N, int K,
                 const float* bias = nullptr, int act = 0, void* preact = nullptr, const float* rowscale = nullptr, int rps = 0,
-                const act_t* residual = nullptr, float* colstats = nullptr, const act_t* dact_pre = nullptr, int dact = 0) {
+                const act_t* residual = nullptr, float* colstats = nullptr, const act_t* dact_pre = nullptr, int dact = 0, const RowMap* rm = nullptr) {
     const int64_t split_tiles = ((M + (K >= 384 ? 255 : 127)) / (K >= 384 ? 256 : 128)) * ((N + 127) / 128);
     const Model::PlaneOf* po = nullptr;
     if (e.m->split && split_tiles >= split_min_tiles() && (K & 7) == 0 && (lda & 3) == 0 && (!colstats || !(bias || act || preact || rowscale || residual || dact_pre)))
@@ -602,8 +617,13 @@ static int gemm(const Exec& e, const act_t* A, int64_t lda, const act_t* Bm, int
         g.b_planes = e.wc + po->planes; g.ldb = ldb; g.M = (int)M; g.N = N; g.K = K; g.C = (float*)C; g.ldc = ldc;
         g.bias = bias; g.act = act; g.preact = (float*)preact; g.rowscale = rowscale; g.rows_per_scale = rps; g.residual = (const float*)residual; g.ldr = ldc;
         g.dact_preact = (const float*)dact_pre; g.dact = dact;
+        if (rm) {
+            g.groups_dev = rm->list; g.group_rows = rm->rps;
+            g.a_map = rm->a ? rm->list + GG_DROP_LIST_HEAD : nullptr; g.c_map = rm->c ? rm->list + GG_DROP_LIST_HEAD : nullptr;
+        }
         return gg_gemm_nt_split3_af32_stats(&g, (const float*)A, lda, (int64_t)po->rows * po->ld, colstats, e.st);
     }
+    GG_CHECK(!rm, "tinyvit: a compacted Linear (M %lld N %d K %d) did not take the split route", (long long)M, N, K);
     GgGemmArgs g;
     memset(&g, 0, sizeof(g));
     g.A = A; g.lda = lda; g.B = Bm; g.ldb = ldb; g.C = C; g.ldc = ldc; g.M = (int)M; g.N = N; g.K = K;
@@ -766,6 +786,40 @@ static int merge_fwd(const Exec& e, int s) {
     if (e.replay) return 0;
     return bn_apply(e, st.merge.c3.bn, ma.c3, M, GG_ACT_NONE, e.A(ma.out));
 }
+// DropPath row compaction.  A dropped sample's branch is multiplied by zero in forward and receives a zero gradient in backward; in a block that
+// qualifies the kept samples' rows are compacted (row r <-> physical row kept[r / rps] * rps + r % rps) and the MLP branch -- forward and backward -- and the backward
+// of the attention branch run over them only.  The attention branch's FORWARD still covers every sample in map order (its output is a tap of the block).
+// A block qualifies when: fp32_split training with a drop array; it is a stage-2 block of width >= 384 with one window per image; every parameter of it is frozen (no weight,
+// bias, LayerNorm / BatchNorm or attention-bias gradient reads a branch tensor); the fused norm2 forms are on; and all eight Linear launches (four forward, four data
+// gradients) take the 256 x 128 split GEMM.  Forward, recompute replay and backward evaluate this from the same inputs.
+// The kept lists (count, kept sample indices in ascending order, each sample's compact position) are derived on the device from the caller's scales -- kept <=> scale != 0 --
+// by one small launch in front of the block's forward, replay and backward (block_lists); no host synchronisation: grids are sized for all rows and read the count.
+static bool block_compacts(const Exec& e, int s, size_t i) {
+    const Model& m = *e.m; const Schedule& k = m.sch;
+    const StageL& st = m.stages[s];
+    const BlockL& l = st.blocks[i];
+    const int C = st.C, hid = (int)(C * m.cfg.mlp_ratio), rps = st.res * st.res;
+    const int64_t M = (int64_t)e.B * rps;
+    if (!e.compact || !m.split || !e.training || !e.drop || !e.trainable || (int64_t)2 * gg_drop_list_ints(e.B) * 4 > e.L->colsum_bytes) return false;
+    if (s != 1 || C < 384 || C > 640 || st.res != st.ws || M * hid * 4 >= ((int64_t)1 << 31)) return false;
+    for (int t : {l.t_ab, l.ln1.t_g, l.ln1.t_b, l.qkv.t_w, l.qkv.t_b, l.proj.t_w, l.proj.t_b, l.ln2.t_g, l.ln2.t_b, l.fc1.t_w, l.fc1.t_b, l.fc2.t_w, l.fc2.t_b,
+                  l.local.w.t_w, l.local.bn.t_g, l.local.bn.t_b})
+        if (e.tr(t)) return false;
+    if (!(k.fuse_lnbn && k.fuse_lncol && k.fuse_bnbwd)) return false;
+    static const bool attn_nosplit = gg_dev_env("GG_ATTN_NO_SPLIT") != nullptr;      // (dev: the attention backward would leave the kernel that takes the window map)
+    const int nt16 = (int)gg_align(rps, 16) / 16;                                      // (the window shapes of the single-pass split attention backward: 14 x 14, 12 x 12, 7 x 7)
+    if (attn_nosplit || (nt16 != 13 && nt16 != 9 && nt16 != 4)) return false;
+    struct Lin { const DenseW* w; bool t; int N, K; };
+    const Lin lins[8] = {{&l.qkv, false, 3 * C, l.qkv.Kp}, {&l.proj, false, C, l.proj.Kp}, {&l.fc1, false, hid, l.fc1.Kp}, {&l.fc2, false, C, l.fc2.Kp},
+                         {&l.fc2, true, hid, C}, {&l.fc1, true, C, hid}, {&l.proj, true, C, C}, {&l.qkv, true, C, 3 * C}};
+    for (const Lin& x : lins) {
+        const int64_t tiles = ((M + 255) / 256) * ((x.N + 127) / 128);
+        if (x.K < 384 || (x.K & 7) || tiles < split_min_tiles() || !gg_split3_af32_takes_rowmap(x.N, x.K)) return false;
+        if (!planes_of(e, x.t ? e.Wt(*x.w) : e.Wn(*x.w), x.t ? x.w->Np : x.w->Kp, x.N)) return false;
+    }
+    return true;
+}
+static int block_lists(const Exec& e, int slot) { return gg_drop_kept_lists(e.dropv(slot), 2, e.B, e.drop_list(0), e.st); }
 static int block_fwd(const Exec& e, int s, size_t i, int slot) {
     const Model& m = *e.m; const GgTinyVitCfg& c = m.cfg;
     const int B = e.B;
@@ -777,6 +831,8 @@ static int block_fwd(const Exec& e, int s, size_t i, int slot) {
     const BlockL& l = st.blocks[i]; const BlockAct& a = e.L->blocks[s][i];
     const float* s1 = e.training ? e.dropv(slot) : nullptr;
     const float* s2 = e.training ? e.dropv(slot + 1) : nullptr;
+    const bool compacts = block_compacts(e, s, i);
+    if (compacts) GG_TRY(block_lists(e, slot));
     GG_TRY(gg_layernorm_fwd(e.A(a.x0), e.f32, e.P(l.ln1.t_g), e.P(l.ln1.t_b), M, C, c.ln_eps, e.A(a.a), e.f32, e.F(a.mean1), e.F(a.rstd1), e.st));
     GG_TRY(gemm(e, e.A(a.a), C, e.Wn(l.qkv), l.qkv.Kp, e.A(a.qkv), 3 * C, M, 3 * C, l.qkv.Kp, e.P(l.qkv.t_b)));
     GgAttnArgs at;
@@ -784,6 +840,19 @@ static int block_fwd(const Exec& e, int s, size_t i, int slot) {
     GG_TRY(attention_fwd(e, at));
     GG_TRY(gemm(e, e.A(a.o), C, e.Wn(l.proj), l.proj.Kp, e.A(a.x1), C, M, C, l.proj.Kp, e.P(l.proj.t_b), 0, nullptr, s1, rps, e.A(a.x0)));
     GG_TRY(conv_dw_fwd(e, l.local, a.local, e.A(a.x1), B, st.res, st.res, 1));
+    if (compacts) {
+        // MLP branch over the kept samples' rows: norm2 writes x2 for every row, `b` compact, and the block's output x3 := x2 for the dropped samples (not in a replay:
+        // x3 is the checkpoint); fc1 runs compact to compact; fc2's residual epilogue reads x2 and writes x3 through the row map
+        const int* list = e.drop_list(1);
+        const RowMap cc = {list, rps, false, false}, out = {list, rps, false, true};
+        GG_TRY(gg_layernorm_fwd_bn_f32_map((const float*)e.A(a.local.y), e.F(a.local.stat), e.P(l.local.bn.t_g), e.P(l.local.bn.t_b), (float*)e.A(a.x2), e.P(l.ln2.t_g),
+                                           e.P(l.ln2.t_b), M, C, c.ln_eps, (float*)e.A(a.b), e.F(a.mean2), e.F(a.rstd2), list + GG_DROP_LIST_HEAD + B, rps,
+                                           e.replay ? nullptr : (float*)e.A(a.x3), e.st));
+        GG_TRY(gemm(e, e.A(a.b), C, e.Wn(l.fc1), l.fc1.Kp, e.A(a.h), hid, M, hid, l.fc1.Kp, e.P(l.fc1.t_b), GG_ACT_GELU, (void*)e.A(a.hpre), nullptr, 0, nullptr, nullptr,
+                    nullptr, 0, &cc));
+        if (e.replay) return 0;
+        return gemm(e, e.A(a.h), hid, e.Wn(l.fc2), l.fc2.Kp, e.A(a.x3), C, M, C, l.fc2.Kp, e.P(l.fc2.t_b), 0, nullptr, s2, rps, e.A(a.x2), nullptr, nullptr, 0, &out);
+    }
     if (C <= 640 && e.f32 && e.sch().fuse_lnbn) {     // BatchNorm apply of local_conv rides on norm2's load (x2 = the residual stream is written there)
         GG_TRY(gg_layernorm_fwd_bn_f32((const float*)e.A(a.local.y), e.F(a.local.stat), e.P(l.local.bn.t_g), e.P(l.local.bn.t_b), (float*)e.A(a.x2),
                                        e.P(l.ln2.t_g), e.P(l.ln2.t_b), M, C, c.ln_eps, (float*)e.A(a.b), e.F(a.mean2), e.F(a.rstd2), e.st));
@@ -1010,6 +1079,30 @@ static int block_bwd(const Exec& e, int s, size_t i, int slot, const GradBufs& g
     const BlockL& l = st.blocks[i]; const BlockAct& a = L.blocks[s][i];
     const float *s1 = e.dropv(slot), *s2 = e.dropv(slot + 1);
     act_t *dx = g.dx, *t_a = g.a, *t_b = g.b, *t_c = g.c;
+    if (block_compacts(e, s, i)) {
+        // the frozen block over the kept samples' rows (block_compacts): the same launches as below, the branch tensors dh / db / do / dqkv / da compact
+        GG_TRY(block_lists(e, slot));
+        const int *l1 = e.drop_list(0), *l2 = e.drop_list(1);
+        const RowMap in2 = {l2, rps, true, false}, cc2 = {l2, rps, false, false}, in1 = {l1, rps, true, false}, cc1 = {l1, rps, false, false};
+        // dh = (s2*dx)[kept] . W2 * gelu'(hpre)  -> t_b;  db = dh . W1  -> t_a;  dx2 = LN2bwd(db) + dx (dropped samples: dx) + local_conv's column sums  -> t_b
+        GG_TRY(gemm(e, dx, C, e.Wt(l.fc2), l.fc2.Np, t_b, hid, M, hid, C, nullptr, 0, nullptr, s2, rps, nullptr, nullptr, e.A(a.hpre), GG_ACT_GELU, &in2));
+        GG_TRY(gemm(e, t_b, hid, e.Wt(l.fc1), l.fc1.Np, t_a, C, M, C, hid, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, &cc2));
+        GG_TRY(gg_layernorm_bwd_map((const float*)t_a, (const float*)e.A(a.x2), e.F(a.mean2), e.F(a.rstd2), e.P(l.ln2.t_g), M, C, (const float*)dx, (float*)t_b,
+                                    e.F(L.lnscratch), l2 + GG_DROP_LIST_HEAD + B, rps, e.st));
+        GG_TRY(gg_bn_bwd_coef_from_x(e.F(L.lnscratch), gg_layernorm_bwd_colsum_rows(M), C, M, e.F(a.local.stat), e.P(l.local.bn.t_g), e.P(l.local.bn.t_b),
+                                     bn_coef(e, M, C), e.st));
+        GG_TRY(dw_bwd_data_fused(e, t_b, e.A(a.local.y), bn_coef(e, M, C), l.local.w, t_c, B, st.res, st.res, nullptr, nullptr, nullptr, nullptr, 0, nullptr));
+        // do = (s1*dx1)[kept] . Wproj  -> t_a;  dqkv  -> t_b (the forward's qkv / out / lse at the physical window);  da = dqkv . Wqkv  -> t_a;  dx0 = LN1bwd(da) + dx1
+        GG_TRY(gemm(e, t_c, C, e.Wt(l.proj), l.proj.Np, t_a, C, M, C, C, nullptr, 0, nullptr, s1, rps, nullptr, nullptr, nullptr, 0, &in1));
+        GgAttnArgs at;
+        attn_args(e, st, l, a, B, at);
+        at.dout = t_a; at.lddo = C; at.dqkv = t_b;
+        at.window_map = l1 + GG_DROP_LIST_HEAD; at.num_windows_dev = l1;
+        GG_TRY(attention_bwd(e, at));
+        GG_TRY(gemm(e, t_b, 3 * C, e.Wt(l.qkv), l.qkv.Np, t_a, C, M, C, 3 * C, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, &cc1));
+        return gg_layernorm_bwd_map((const float*)t_a, (const float*)e.A(a.x0), e.F(a.mean1), e.F(a.rstd1), e.P(l.ln1.t_g), M, C, (const float*)t_c, (float*)dx, nullptr,
+                                    l1 + GG_DROP_LIST_HEAD + B, rps, e.st);
+    }
     // dx == d(x3).  MLP branch: dh = (s2*dx) . W2  * gelu'(hpre)      -> t_b  [M, hid]
     GG_TRY(gemm(e, dx, C, e.Wt(l.fc2), l.fc2.Np, t_b, hid, M, hid, C, nullptr, 0, nullptr, s2, rps, nullptr, nullptr, e.A(a.hpre), GG_ACT_GELU));
     if (e.tr(l.fc2.t_w)) {
@@ -1384,6 +1477,7 @@ static int refresh_weights(const GgTinyVitCfg* cfg, const float* params, void* w
     }
     return 0;
 }
+extern "C" int gg_tinyvit_set_drop_compact(int on) { return g_drop_compact.exchange(on != 0 ? 1 : 0); }
 extern "C" int gg_tinyvit_forward(const GgTinyVitCfg* cfg, int batch, int training, const float* params, float* buffers,
                                   int64_t* counters, const void* wcache, const float* x, const float* drop_scales, void* workspace,
                                   float* out, const uint8_t* trainable, void* stream) {
@@ -1393,17 +1487,19 @@ extern "C" int gg_tinyvit_forward(const GgTinyVitCfg* cfg, int batch, int traini
     GG_CHECK(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)wcache & 255) == 0, "gg_tinyvit_forward: workspace/wcache must be 256-byte aligned");
     Plan p; Layout L;
     plan_make(m, batch, training != 0, p, L, trainable);
+    const bool compact = g_drop_compact.load() != 0;
     auto body = [&](hipStream_t st) -> int {
         Exec e(m, L, batch, training != 0);
         e.params = params; e.buffers = buffers; e.counters = counters;
         e.wc = (const char*)wcache; e.ws = (char*)workspace; e.st = st; e.drop = drop_scales; e.grads = nullptr;
         e.trainable = trainable;       // NULL: keep every activation a weight gradient could need
+        e.compact = compact;
         return forward_impl(e, x, out);
     };
     // launch-bound sizes (a serving panorama, small training batches: a few hundred launches of microseconds each) replay a captured graph
     if (!gg_graph_wanted((int64_t)batch * cfg->img_size * cfg->img_size <= (int64_t)64 * 224 * 224)) return body((hipStream_t)stream);
     GgGraphKey key;
-    key.add('F').add_bytes(cfg, sizeof(*cfg)).add(batch).add(training).add(params).add(buffers).add(counters).add(wcache).add(x).add(drop_scales).add(workspace).add(out)
+    key.add('F').add_bytes(cfg, sizeof(*cfg)).add(batch).add(training).add(params).add(buffers).add(counters).add(wcache).add(x).add(drop_scales).add(workspace).add(out).add((int)compact)
        .add_bytes(trainable, trainable ? m.tensors.size() : 0);
     return gg_graph_run(key, (hipStream_t)stream, body);
 }
@@ -1419,6 +1515,7 @@ extern "C" int gg_tinyvit_backward(const GgTinyVitCfg* cfg, int batch, const flo
     e.params = params; e.buffers = nullptr; e.counters = nullptr;
     e.wc = (const char*)wcache; e.ws = (char*)workspace; e.st = (hipStream_t)stream; e.drop = drop_scales; e.grads = grads;
     e.trainable = trainable; e.stage_done = stage_done; e.stage_user = stage_user;
+    e.compact = g_drop_compact.load() != 0;
     if (trainable) {
         // The schedule forms the two gradients of a (weight, bias) / (gamma, beta) pair together (BatchNorm / LayerNorm finalize kernels, the fused
         // frozen-chain forms): a mask that trains one tensor of a pair and freezes the other has no schedule -- refuse it by name instead of silently
@@ -1442,7 +1539,7 @@ extern "C" int gg_tinyvit_backward(const GgTinyVitCfg* cfg, int batch, const flo
         return backward_impl(g, d_out);
     };
     GgGraphKey key;
-    key.add('B').add_bytes(cfg, sizeof(*cfg)).add(batch).add(params).add(wcache).add(drop_scales).add(workspace).add(d_out).add(grads)
+    key.add('B').add_bytes(cfg, sizeof(*cfg)).add(batch).add(params).add(wcache).add(drop_scales).add(workspace).add(d_out).add(grads).add((int)e.compact)
        .add_bytes(trainable, trainable ? m.tensors.size() : 0);
     return gg_graph_run(key, (hipStream_t)stream, body);
 }

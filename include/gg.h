@@ -10,7 +10,8 @@
  *     gg_graph_clear() is the teardown and must run before the buffers a captured graph refers to are freed), the launch log of the profiling
  *     hooks (gg_prof_*: off unless enabled), and lazily allocated 16 MiB split-K slab buffers of gg_gemm_nt_f32: one per (device, stream) that issued the form, at
  *     most 8 (least recently used released), plus one per captured graph whose launches use the form; gg_graph_clear() releases them all.  Under a CALLER's own
- *     stream capture no slab can be handed out and the form runs unsplit (same product, different rounding than the eager call);
+ *     stream capture no slab can be handed out and the form runs unsplit (same product, different rounding than the eager call); and the DropPath row-compaction
+ *     switch gg_tinyvit_set_drop_compact of include/gg_drop.h (default on; it selects between two schedules of the fp32_split TinyViT training step whose results are bit-identical);
  *   - `stream` is a hipStream_t; work is only enqueued, nothing here synchronises;
  *   - bf16 tensors are passed as void*; matrices are row-major with an explicit leading dimension
  *     in ELEMENTS; activations are NHWC / [tokens, channels].
@@ -199,6 +200,11 @@ typedef struct GgAttnArgs {
                                              [gg_attention_flash_ds_scratch_floats(...)] = 4 * windows * heads * roundup16(tokens)^2 bytes (22 MB per image at
                                              CLIP ViT-L/14-336).  With it the dK/dV pass runs first and hands dS to the dQ pass, which then is ONE product
                                              (dQ = scale * dS K) instead of three plus a second round of exponentials; NULL: both passes recompute the scores */
+    const int* window_map;                /* row compaction of gg_attention_flash_bwd, with num_windows_dev (both device, both or neither; dtype 1, head dim 32,
+                                             7 x 7 / 12 x 12 / 14 x 14 windows, dbias NULL -- any other call with them is refused): only the first *num_windows_dev
+                                             windows are processed; window w reads qkv / out / lse at physical window window_map[w], reads dout and writes dqkv
+                                             at window w itself (compact).  num_windows stays the full count: it sizes the grid, nothing is read back */
+    const int* num_windows_dev;
 } GgAttnArgs;
 int gg_attention_padded_tokens(int tokens_per_window);
 /* full[h][q][k] = bf16(table[h][|dy|*ws+|dx|] / scale) (-inf for padded keys): the kernels start their score accumulators from it,
@@ -253,6 +259,15 @@ typedef struct {
     const float* rowscale; int rows_per_scale;
     const float* residual; int64_t ldr;
     const float* dact_preact; int dact;     /* v = acc * act'(dact_preact[m][n]) */
+    /* Row compaction (gg_gemm_nt_split3_af32 / _stats only; the 256 x 128 form: K >= 384; f32 result, no planes / colstats).  groups_dev (device, or NULL = off):
+     * the number of live row groups; only the first *groups_dev * group_rows rows of the product exist -- rows beyond them are neither read nor written.  M stays the
+     * full extent (a multiple of group_rows): the grid is sized by it and nothing is read back.  a_map / c_map (device, optional; ascending group indices, as
+     * gg_drop_kept_lists of include/gg_drop.h writes them): row r of the product reads A at physical row a_map[r / group_rows] * group_rows + r % group_rows, and writes C / reads the
+     * residual at the row c_map gives likewise; preact / dact_preact always use the compact row.  With a map, rowscale is indexed by the PHYSICAL group
+     * (c_map, else a_map; rows_per_scale == group_rows).  Every live row goes through the unmapped call's arithmetic: results are bit-identical to the call on
+     * pre-gathered operands. */
+    const int* groups_dev; int group_rows;
+    const int* a_map; const int* c_map;
 } GgSplit3Args;
 int gg_gemm_nt_split3_ex(const GgSplit3Args* args, void* stream);
 /* the same with the A operand as the f32 tensor itself ([M][lda], split into its three bf16 terms while the kernel stages it: no plane copy of an
