@@ -316,6 +316,14 @@ DROP_SIGNATURES = {
 }
 DROP_SYMBOLS = list(DROP_SIGNATURES)
 
+# every exported symbol of include/gg_pad.h (padded attention windows of TinyViT: a token map the window does not divide), bound from the same libgg.so
+PAD_SIGNATURES = {
+    "gg_window_pad": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "gg_window_crop_add": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+}
+PAD_SYMBOLS = list(PAD_SIGNATURES)
+PROF_CAT_PAD = 7                          # GG_CAT_PAD (csrc/prof.h): the launch profiler's category of the two kernels
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -324,7 +332,7 @@ def lib() -> C.CDLL:
             raise GgError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the library lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -374,6 +382,7 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(root), "include", "gg_clip_text_train.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_cls.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_drop.h"))
+    files.append(os.path.join(os.path.dirname(root), "include", "gg_pad.h"))
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

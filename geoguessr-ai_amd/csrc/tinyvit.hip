@@ -16,6 +16,7 @@
 #include "../../include/gg.h"
 #include "../../include/gg_cls.h"
 #include "../../include/gg_drop.h"
+#include "../../include/gg_pad.h"
 
 bool gg_split3_af32_takes_rowmap(int N, int K);      // gemm_split3.hip: the form gg_gemm_nt_split3_af32 would run this shape on accepts row compaction
 
@@ -36,7 +37,7 @@ struct ConvBNDw { DwW w; BNP bn; };
 struct MBConvL { ConvBNDense c1; ConvBNDw c2; ConvBNDense c3; };
 struct MergeL { ConvBNDense c1; ConvBNDw c2; ConvBNDense c3; };
 struct BlockL { int t_ab = -1; int64_t bias_full = 0; LNP ln1; DenseW qkv, proj; LNP ln2; DenseW fc1, fc2; ConvBNDw local; };
-struct StageL { MergeL merge; std::vector<BlockL> blocks; int C, heads, ws, res; };
+struct StageL { MergeL merge; std::vector<BlockL> blocks; int C, heads, ws, res, pres; };      // pres: the map side the attention branch runs at -- res rounded up to a multiple of ws (timm pads bottom / right)
 
 // Which fused forms the schedule takes.  The workspace plan decides who owns the tensors a fusion removes and the executor decides who writes
 // them, so there is ONE value per C-ABI call: build_model fills Model::sch from the storage type and the dev switches, both read it there.
@@ -181,8 +182,8 @@ static int build_model(const GgTinyVitCfg* cfg, Model& m) {
         StageL& st = m.stages[s - 1];
         const int C = d[s], ws = cfg->window_sizes[s], nh = cfg->num_heads[s];
         res /= 2;
-        st.C = C; st.heads = nh; st.ws = ws; st.res = res;
-        GG_CHECK(res % ws == 0, "tinyvit: stage %d map %d not divisible by window %d (padding path not built)", s, res, ws);
+        GG_CHECK(ws > 0, "tinyvit: window_sizes[%d] must be > 0", s);
+        st.C = C; st.heads = nh; st.ws = ws; st.res = res; st.pres = (int)gg_align(res, ws);
         GG_CHECK(ws <= 32, "tinyvit: window %d unsupported (max 32x32 tokens)", ws);
         const std::string pm = "stages." + std::to_string(s) + ".downsample";
         make_convbn_dense(m, st.merge.c1, pm + ".conv1", d[s - 1], C, 1);
@@ -315,7 +316,8 @@ struct Act {   // offsets (bytes) of the saved tensors of one ConvNorm
 };
 struct MBAct { int64_t x, a1, a2, out; Act c1, c2, c3; };
 struct MergeAct { int64_t a1, a2, out; Act c1, c2, c3; };
-struct BlockAct { int64_t x0, a, mean1, rstd1, qkv, o, lse, x1, x2, b, mean2, rstd2, hpre, h, x3; Act local; };
+struct BlockAct { int64_t x0, a, mean1, rstd1, qkv, o, lse, x1, x2, b, mean2, rstd2, hpre, h, x3; Act local;
+                  int64_t xpad = -1; };      // padded block (pres != res): x0 zero-padded to the padded map; a / mean1 / rstd1 / qkv / o / lse then hold B * pres^2 rows in padded map order
 struct Layout {
     int64_t col1, col2, x_pe; Act pe1, pe2;
     std::vector<MBAct> mb;
@@ -324,6 +326,7 @@ struct Layout {
     int64_t pooled, mean_h, rstd_h;
     // scratch
     int64_t statpart, bnscratch, lnscratch, colsum, splitk, attn_ds = -1, G[5];
+    int64_t padtmp = -1;         // padded blocks: proj's output on the padded map, between the GEMM and the crop (one region for all of them; absent when every map divides)
     int64_t foldw, foldb;        // BatchNorm-backward-folded dgrad weights bf16 [Cin][2*Cout] and bias f32 [Cin]
     int64_t colsum_bytes = 0;    // (scratch.colsum also holds the two kept lists of a compacted block while that block runs: block_compacts)
     int64_t gbytes;
@@ -351,7 +354,7 @@ static void plan_build(const Model& m, int B, Plan& p, Layout& L) {
     const int* d = c.embed_dims;
     const int H1 = c.img_size / 2, H0 = m.res0;
     const int64_t M1 = (int64_t)B * H1 * H1, M0 = (int64_t)B * H0 * H0;
-    int64_t gmax = 0, statmax = 0, bnsmax = 0, lnsmax = 0, csmax = 0;
+    int64_t gmax = 0, statmax = 0, bnsmax = 0, lnsmax = 0, csmax = 0, padmax = 0;
     const int64_t es = m.es;
     auto track = [&](int64_t elems) { gmax = std::max(gmax, elems * es); };
     auto bnreg = [&](const std::string& n, Act& a, int64_t M, int C, bool dw, int Bn, int Ho, int Wo, bool seg = true) {
@@ -393,7 +396,7 @@ static void plan_build(const Model& m, int B, Plan& p, Layout& L) {
     for (int s = 0; s < 3; ++s) {
         const StageL& st = m.stages[s];
         const int C = st.C;
-        const int64_t M = (int64_t)B * st.res * st.res;
+        const int64_t M = (int64_t)B * st.res * st.res, Mp = (int64_t)B * st.pres * st.pres;      // Mp: rows of the attention branch (= M unless the map is padded)
         const std::string n = "stages." + std::to_string(s + 1) + ".downsample";
         MergeAct& ma = L.merge[s];
         p.seg_begin();
@@ -416,12 +419,19 @@ static void plan_build(const Model& m, int B, Plan& p, Layout& L) {
             // local_conv.y for its BatchNorm and the fc1 pre-activation for GELU'): 7 C of the block's 19 C floats per token
             p.seg_begin();
             auto keep = [&](bool trains, const std::string& nm, int64_t bytes) { return p.rc ? p.alloc_seg(nm, bytes) : !trains ? p.alloc_temp(nm, bytes) : p.alloc(nm, bytes); };
-            a.a = keep(p.tr(bl.qkv.t_w), bn + ".ln1", M * C * es);
-            a.mean1 = p.alloc_in(bn + ".mean1", M * 4);
-            a.rstd1 = p.alloc_in(bn + ".rstd1", M * 4);
-            a.qkv = p.alloc_in(bn + ".qkv", M * 3 * C * es);
-            a.o = p.alloc_in(bn + ".attn.out", M * C * es);
-            a.lse = p.alloc_in(bn + ".attn.lse", M * st.heads * 4);
+            // padded block: the attention branch runs on the zero-padded map (Mp rows).  xpad is LayerNorm1's input: the backward reads it again, and re-forms it from x0
+            // when neither LayerNorm1 nor qkv trains (then it is a temporary like ln1)
+            if (st.pres != st.res) {
+                a.xpad = keep(p.tr(bl.qkv.t_w) || p.tr(bl.ln1.t_g), bn + ".attn.xpad", Mp * C * es);
+                padmax = std::max(padmax, Mp * C * es);
+                track(Mp * 3 * C);
+            }
+            a.a = keep(p.tr(bl.qkv.t_w), bn + ".ln1", Mp * C * es);
+            a.mean1 = p.alloc_in(bn + ".mean1", Mp * 4);
+            a.rstd1 = p.alloc_in(bn + ".rstd1", Mp * 4);
+            a.qkv = p.alloc_in(bn + ".qkv", Mp * 3 * C * es);
+            a.o = p.alloc_in(bn + ".attn.out", Mp * C * es);
+            a.lse = p.alloc_in(bn + ".attn.lse", Mp * st.heads * 4);
             a.x1 = keep(p.tr(bl.local.w.t_w), bn + ".x1", M * C * es);
             bnreg(bn + ".local_conv", a.local, M, C, true, B, st.res, st.res);
             a.x2 = p.alloc_in(bn + ".x2", M * C * es);
@@ -433,9 +443,9 @@ static void plan_build(const Model& m, int B, Plan& p, Layout& L) {
             a.x3 = p.alloc(bn + ".out", M * C * es);
             prev = a.x3;
             track(M * hid); track(M * 3 * C);
-            lnsmax = std::max(lnsmax, gg_layernorm_bwd_scratch_floats(M, C) * 4);
+            lnsmax = std::max(lnsmax, gg_layernorm_bwd_scratch_floats(Mp, C) * 4);
             csmax = std::max(csmax, gg_colsum_scratch_floats((int)M, hid) * 4);
-            csmax = std::max(csmax, gg_colsum_scratch_floats((int)M, 3 * C) * 4);
+            csmax = std::max(csmax, gg_colsum_scratch_floats((int)Mp, 3 * C) * 4);
         }
         res = st.res;
         Mprev = M;
@@ -445,6 +455,7 @@ static void plan_build(const Model& m, int B, Plan& p, Layout& L) {
     L.rstd_h = p.alloc("head.rstd", (int64_t)B * 4, false);
     lnsmax = std::max(lnsmax, gg_layernorm_bwd_scratch_floats(B, d[3]) * 4);
     L.statpart = p.alloc("scratch.statpart", statmax, false);
+    if (padmax > 0) L.padtmp = p.alloc("scratch.padtmp", padmax, false);
     if (p.training) {
         // dw wgrad scratch may exceed the BN scratch
         int64_t dwmax = 0;
@@ -468,7 +479,7 @@ static void plan_build(const Model& m, int B, Plan& p, Layout& L) {
             int64_t dsmax = 0;
             for (int s = 1; s < 4; ++s) {
                 const auto& st = m.stages[s - 1];
-                const int nw = B * (st.res / st.ws) * (st.res / st.ws);
+                const int nw = B * (st.pres / st.ws) * (st.pres / st.ws);
                 if (!gg_attention_flash_single_pass(st.ws * st.ws, 32, st.ws, 1))
                     dsmax = std::max(dsmax, gg_attention_flash_ds_scratch_floats(nw, st.heads, st.ws * st.ws) * 4);
             }
@@ -709,8 +720,8 @@ static void attn_args(const Exec& e, const StageL& st, const BlockL& l, const Bl
     memset(&at, 0, sizeof(at));
     at.qkv = e.A(a.qkv); at.ld = 3 * C; at.q_off = 0; at.k_off = 32; at.v_off = 64; at.head_stride = 96; at.head_dim = 32;
     at.num_heads = st.heads; at.tokens_per_window = st.ws * st.ws;
-    at.num_windows = B * (st.res / st.ws) * (st.res / st.ws);
-    at.window_size = st.ws; at.map_h = st.res; at.map_w = st.res;
+    at.num_windows = B * (st.pres / st.ws) * (st.pres / st.ws);
+    at.window_size = st.ws; at.map_h = st.pres; at.map_w = st.pres;      // (a padded block: the padded map)
     at.bias = l.bias_full >= 0 ? e.wc + l.bias_full : nullptr;      // expanded bf16 table (register-resident kernels)
     at.bias_table = e.P(l.t_ab);                                     // compact f32 parameter (online-softmax kernels)
     at.scale = kAttnScale;
@@ -718,6 +729,15 @@ static void attn_args(const Exec& e, const StageL& st, const BlockL& l, const Bl
 }
 static int attention_fwd(const Exec& e, const GgAttnArgs& at) { return e.f32 ? gg_attention_flash_fwd(&at, 1, e.st) : gg_attention_fwd(&at, e.st); }
 static int attention_bwd(const Exec& e, const GgAttnArgs& at) { return e.f32 ? gg_attention_flash_bwd(&at, 1, e.st) : gg_attention_bwd(&at, e.st); }
+// padded block: zero-pad a [B, res, res, C] map of the stage to [B, pres, pres, C]; crop such a map back: y = res_in + rowscale[b] * t (y may be res_in)
+static int window_pad(const Exec& e, const StageL& st, const act_t* x, act_t* y) {
+    return gg_window_pad(x, y, e.B, st.res, st.res, st.pres, st.pres, st.C, e.f32 ? 1 : 0, e.st);
+}
+static int window_crop_add(const Exec& e, const StageL& st, const act_t* t, const act_t* res_in, const float* rowscale, act_t* y) {
+    return gg_window_crop_add(t, res_in, rowscale, y, e.B, st.res, st.res, st.pres, st.pres, st.C, e.f32 ? 1 : 0, e.st);
+}
+// the padded input of LayerNorm1 survives into the backward (its own storage, or the segment region under recompute) unless neither LayerNorm1 nor qkv trains
+static bool xpad_kept(const Exec& e, const BlockL& l) { return e.m->cfg.recompute || e.tr(l.qkv.t_w) || e.tr(l.ln1.t_g); }
 // PatchEmbed's gathers: the f32 NCHW image -> col1 [B*(H/2)^2, 32]; act(BN(y)) of an NHWC ConvNorm -> col [B*(H/2)^2, 9 C] (the activation is never written)
 static int im2col_image(const Exec& e, const float* x, act_t* col, int B, int H, int W) {
     if (e.f32) return gg_im2col_nchw3_f32_f32(x, (float*)col, B, H, W, 2, e.st);
@@ -794,6 +814,7 @@ static int merge_fwd(const Exec& e, int s) {
 // gradients) take the 256 x 128 split GEMM.  Forward, recompute replay and backward evaluate this from the same inputs.
 // The kept lists (count, kept sample indices in ascending order, each sample's compact position) are derived on the device from the caller's scales -- kept <=> scale != 0 --
 // by one small launch in front of the block's forward, replay and backward (block_lists); no host synchronisation: grids are sized for all rows and read the count.
+// A padded block (pres != res: the window does not divide the map) never compacts: one window per image means res == ws, and such a map is not padded.
 static bool block_compacts(const Exec& e, int s, size_t i) {
     const Model& m = *e.m; const Schedule& k = m.sch;
     const StageL& st = m.stages[s];
@@ -801,7 +822,7 @@ static bool block_compacts(const Exec& e, int s, size_t i) {
     const int C = st.C, hid = (int)(C * m.cfg.mlp_ratio), rps = st.res * st.res;
     const int64_t M = (int64_t)e.B * rps;
     if (!e.compact || !m.split || !e.training || !e.drop || !e.trainable || (int64_t)2 * gg_drop_list_ints(e.B) * 4 > e.L->colsum_bytes) return false;
-    if (s != 1 || C < 384 || C > 640 || st.res != st.ws || M * hid * 4 >= ((int64_t)1 << 31)) return false;
+    if (s != 1 || C < 384 || C > 640 || st.res != st.ws || st.pres != st.res || M * hid * 4 >= ((int64_t)1 << 31)) return false;
     for (int t : {l.t_ab, l.ln1.t_g, l.ln1.t_b, l.qkv.t_w, l.qkv.t_b, l.proj.t_w, l.proj.t_b, l.ln2.t_g, l.ln2.t_b, l.fc1.t_w, l.fc1.t_b, l.fc2.t_w, l.fc2.t_b,
                   l.local.w.t_w, l.local.bn.t_g, l.local.bn.t_b})
         if (e.tr(t)) return false;
@@ -833,12 +854,22 @@ static int block_fwd(const Exec& e, int s, size_t i, int slot) {
     const float* s2 = e.training ? e.dropv(slot + 1) : nullptr;
     const bool compacts = block_compacts(e, s, i);
     if (compacts) GG_TRY(block_lists(e, slot));
-    GG_TRY(gg_layernorm_fwd(e.A(a.x0), e.f32, e.P(l.ln1.t_g), e.P(l.ln1.t_b), M, C, c.ln_eps, e.A(a.a), e.f32, e.F(a.mean1), e.F(a.rstd1), e.st));
-    GG_TRY(gemm(e, e.A(a.a), C, e.Wn(l.qkv), l.qkv.Kp, e.A(a.qkv), 3 * C, M, 3 * C, l.qkv.Kp, e.P(l.qkv.t_b)));
+    // padded block (the window does not divide the map): x0 is zero-padded in front of LayerNorm1 -- a pad token leaves the norm as norm.bias and takes part in its
+    // window as key and value, nothing masks it -- the branch runs at Mp rows, and proj's result is cropped back where the residual is added
+    const bool padded = st.pres != st.res;
+    const int64_t Mp = (int64_t)B * st.pres * st.pres;
+    if (padded) GG_TRY(window_pad(e, st, e.A(a.x0), e.A(a.xpad)));
+    GG_TRY(gg_layernorm_fwd(e.A(padded ? a.xpad : a.x0), e.f32, e.P(l.ln1.t_g), e.P(l.ln1.t_b), Mp, C, c.ln_eps, e.A(a.a), e.f32, e.F(a.mean1), e.F(a.rstd1), e.st));
+    GG_TRY(gemm(e, e.A(a.a), C, e.Wn(l.qkv), l.qkv.Kp, e.A(a.qkv), 3 * C, Mp, 3 * C, l.qkv.Kp, e.P(l.qkv.t_b)));
     GgAttnArgs at;
     attn_args(e, st, l, a, B, at);
     GG_TRY(attention_fwd(e, at));
-    GG_TRY(gemm(e, e.A(a.o), C, e.Wn(l.proj), l.proj.Kp, e.A(a.x1), C, M, C, l.proj.Kp, e.P(l.proj.t_b), 0, nullptr, s1, rps, e.A(a.x0)));
+    if (padded) {
+        GG_TRY(gemm(e, e.A(a.o), C, e.Wn(l.proj), l.proj.Kp, e.A(e.L->padtmp), C, Mp, C, l.proj.Kp, e.P(l.proj.t_b)));
+        GG_TRY(window_crop_add(e, st, e.A(e.L->padtmp), e.A(a.x0), s1, e.A(a.x1)));
+    } else {
+        GG_TRY(gemm(e, e.A(a.o), C, e.Wn(l.proj), l.proj.Kp, e.A(a.x1), C, M, C, l.proj.Kp, e.P(l.proj.t_b), 0, nullptr, s1, rps, e.A(a.x0)));
+    }
     GG_TRY(conv_dw_fwd(e, l.local, a.local, e.A(a.x1), B, st.res, st.res, 1));
     if (compacts) {
         // MLP branch over the kept samples' rows: norm2 writes x2 for every row, `b` compact, and the block's output x3 := x2 for the dropped samples (not in a replay:
@@ -1139,6 +1170,40 @@ static int block_bwd(const Exec& e, int s, size_t i, int slot, const GradBufs& g
         GG_TRY(dw_bwd_data_fused(e, t_b, e.A(a.local.y), bn_coef(e, M, C), l.local.w, t_c, B, st.res, st.res, nullptr, nullptr, nullptr, nullptr, 0, nullptr));
     }
     act_t* dx1 = t_c;
+    if (st.pres != st.res) {
+        // padded block: the crop's adjoint is zero padding -- the branch runs at Mp rows on the padded map, the pad keys / values send their gradient into qkv's and
+        // LayerNorm1's parameters (a pad query has dO = 0), and the gradient at the pad positions of the padded input is dropped by the crop
+        const int rpsp = st.pres * st.pres;
+        const int64_t Mp = (int64_t)B * rpsp;
+        act_t* t_d = g.d;
+        GG_TRY(window_pad(e, st, dx1, t_d));                                                               // dx1 on the padded map -> t_d  [Mp, C]
+        GG_TRY(gemm(e, t_d, C, e.Wt(l.proj), l.proj.Np, t_a, C, Mp, C, C, nullptr, 0, nullptr, s1, rpsp));  // do -> t_a
+        if (e.tr(l.proj.t_w)) {
+            GG_TRY(dense_wgrad(e, l.proj, e.A(a.o), C, t_d, C, Mp, s1, rpsp, false));
+            GG_TRY(bias_grad(e, l.proj.t_b, t_d, C, Mp, C, s1, rpsp));
+        }
+        GgAttnArgs at;
+        attn_args(e, st, l, a, B, at);
+        at.dout = t_a; at.lddo = C; at.dqkv = t_b;                                                         // dqkv -> t_b  [Mp, 3C]
+        at.dbias = e.tr(l.t_ab) ? e.Gd(l.t_ab) : nullptr;
+        const bool flash = e.f32 || at.tokens_per_window > 256 || st.ws > 16;
+        const int64_t prow = flash ? gg_attention_flash_dbias_rows(at.num_windows, at.tokens_per_window) : (int64_t)at.num_windows + 64;
+        if (at.dbias && prow * st.heads * st.ws * st.ws * 4 <= ((int64_t)64 << 20)) at.dbias_scratch = e.F(L.splitk);
+        static const bool ds_off_p = gg_dev_env("GG_ATTN_NO_DS_SCRATCH") != nullptr;
+        if (e.f32 && L.attn_ds >= 0 && !ds_off_p) at.ds_scratch = e.F(L.attn_ds);
+        GG_TRY(attention_bwd(e, at));
+        GG_TRY(gemm(e, t_b, 3 * C, e.Wt(l.qkv), l.qkv.Np, t_a, C, Mp, C, 3 * C));                          // da -> t_a  [Mp, C]
+        if (e.tr(l.qkv.t_w)) {
+            GG_TRY(dense_wgrad(e, l.qkv, e.A(a.a), C, t_b, 3 * C, Mp, nullptr, 0, false));
+            GG_TRY(bias_grad(e, l.qkv.t_b, t_b, 3 * C, Mp, 3 * C, nullptr, 0));
+        }
+        const act_t* xp = e.A(a.xpad);
+        if (!xpad_kept(e, l)) { GG_TRY(window_pad(e, st, e.A(a.x0), t_d)); xp = t_d; }                     // (the forward's xpad was a temporary: formed again)
+        const bool trp = e.tr(l.ln1.t_g);
+        GG_TRY(gg_layernorm_bwd(t_a, xp, e.f32, e.F(a.mean1), e.F(a.rstd1), e.P(l.ln1.t_g), Mp, C, nullptr, t_b, e.F(L.lnscratch),
+                                trp ? e.Gd(l.ln1.t_g) : nullptr, trp ? e.Gd(l.ln1.t_b) : nullptr, 1, e.st));  // d(xpad) -> t_b  [Mp, C]
+        return window_crop_add(e, st, t_b, dx1, nullptr, dx);                                              // dx0 = dx1 + crop(d(xpad))
+    }
     // attention branch: do = (s1*dx1) . Wproj                          -> t_a  [M, C]
     GG_TRY(gemm(e, dx1, C, e.Wt(l.proj), l.proj.Np, t_a, C, M, C, C, nullptr, 0, nullptr, s1, rps));
     if (e.tr(l.proj.t_w)) {

@@ -137,6 +137,19 @@ class TinyVitBackbone(EncoderRuntime):
         self._register_table(lambda name, shape: _init_tensor(name, shape, g))
 
     grad_checkpointing = property(lambda self: bool(self.cfg.recompute))          # (timm's attribute)
+    img_size = property(lambda self: int(self.cfg.img_size))                      # the input side the model was built for (``img_size=`` override or the variant's own)
+
+    @property
+    def padded_maps(self) -> tuple:
+        """``(stage, res, padded_res)`` of every stage whose token map the attention window does not divide (``img_size=`` other than the variant's own): its
+        TinyVitBlocks zero-pad the map at the bottom and right to ``padded_res`` in front of the attention module and crop the result back (timm
+        ``TinyVitBlock.forward``; csrc/window_pad.hip).  Empty for sizes that divide -- those take the schedule without a pad or crop launch."""
+        out = []
+        for s in (1, 2, 3):
+            res, ws = self.cfg.img_size // (4 * 2 ** s), self.cfg.window_sizes[s]
+            if res % ws:
+                out.append((s, res, -(-res // ws) * ws))
+        return tuple(out)
 
     def set_grad_checkpointing(self, enable: bool = True):
         """timm's switch (``model.set_grad_checkpointing()``; the reference's ``adapter.backbone`` is the timm model): activation recompute of the
@@ -310,7 +323,8 @@ class TinyViTAdapter(nn.Module):
     def __init__(self, model_name: str = "tiny_vit_21m_512.dist_in22k_ft_in1k", pretrained: bool = True,
                  global_pool: str = "avg", features_only: bool = False, **overrides):
         """``overrides`` (not in the reference): ``precision="bf16"|"fp32"`` (default ``$GG_PRECISION`` or fp32), ``seed``,
-        ``drop_path_rate``, ``img_size`` ... (timm ``create_model`` kwargs), ``grad_checkpointing=True`` (activation recompute from the start;
+        ``drop_path_rate``, ``img_size`` (any multiple of 32: where the attention window does not divide a stage's map the blocks pad it --
+        ``backbone.padded_maps``) ... (timm ``create_model`` kwargs), ``grad_checkpointing=True`` (activation recompute from the start;
         the same as ``adapter.backbone.set_grad_checkpointing()``)."""
         super().__init__()
         if global_pool != "avg":

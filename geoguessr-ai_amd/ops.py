@@ -458,6 +458,26 @@ def layernorm_bwd(dout, x, mean, rstd, gamma, dres=None, want_param_grads=True):
     return dx, dg, db
 
 
+def window_pad(x, padded_h, padded_w):
+    """(B, H, W, C) f32 / bf16 -> (B, padded_h, padded_w, C): the map zero-padded at the bottom and right (``gg_window_pad``, include/gg_pad.h: the padded attention
+    windows of a TinyVitBlock whose map the window does not divide).  Every element of the result is written."""
+    B, H, W, Cc = x.shape
+    y = torch.empty((B, padded_h, padded_w, Cc), dtype=x.dtype, device=x.device)
+    L.check(L.lib().gg_window_pad(_p(x), _p(y), B, H, W, padded_h, padded_w, Cc, int(x.dtype == F32), L.stream()), "gg_window_pad")
+    return y
+
+
+def window_crop_add(t, H, W, res=None, rowscale=None, out=None):
+    """``res + rowscale[b] * t[:, :H, :W]`` for a padded map t (B, Hp, Wp, C) (``gg_window_crop_add``): the crop of the padded attention branch fused with the block's
+    residual add and DropPath scale.  ``res`` and ``rowscale`` (f32 (B,)) are optional; ``out`` may be ``res``."""
+    B, Hp, Wp, Cc = t.shape
+    if out is None:
+        out = torch.empty((B, H, W, Cc), dtype=t.dtype, device=t.device)
+    L.check(L.lib().gg_window_crop_add(_p(t), _p(res, t.dtype), _p(rowscale, F32), _p(out, t.dtype), B, H, W, Hp, Wp, Cc, int(t.dtype == F32), L.stream()),
+            "gg_window_crop_add")
+    return out
+
+
 def layernorm_bwd_colsum(dout, x, mean, rstd, gamma, dres=None):
     """LayerNorm backward that also leaves the per-block column sums (sum dx*x, sum dx) of its result; returns (dx, part, rows)."""
     M, Cc = x.shape

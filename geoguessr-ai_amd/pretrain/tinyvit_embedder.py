@@ -8,16 +8,18 @@ from __future__ import annotations
 import torch
 from torch import Tensor
 
-from ..models.tinyvit import TinyViTAdapter
+from ..models.tinyvit import VARIANTS, TinyViTAdapter
 
 
 class TinyViTEmbedding(torch.nn.Module):
     def __init__(self, model_name: str = "tiny_vit_21m_512.dist_in22k_ft_in1k", device: str = "cuda", load_checkpoint: bool = False,
-                 panorama: bool = False):
+                 panorama: bool = False, img_size: int = None):
+        """``img_size`` (not in the reference): run the checkpoint at another input side (a multiple of 32; ``TinyViTAdapter``'s override) -- the preprocessing
+        resizes to that side, with the crop settings of the checkpoint's own variant."""
         super().__init__()
         self.device, self.panorama, self.model_name = device, panorama, model_name
         arch = "tiny_vit_21m_224" if load_checkpoint else model_name
-        self.tinyvit_model = TinyViTAdapter(arch, pretrained=not load_checkpoint)
+        self.tinyvit_model = TinyViTAdapter(arch, pretrained=not load_checkpoint, **({} if img_size is None else dict(img_size=int(img_size))))
         if load_checkpoint:
             self.tinyvit_model.backbone.load_state_dict(torch.load(model_name, map_location="cpu"))
             print("Loaded embedder from checkpoint:", model_name)
@@ -32,9 +34,11 @@ class TinyViTEmbedding(torch.nn.Module):
             bb = self.tinyvit_model.backbone
             # timm's published default_cfgs (timm/models/tiny_vit.py; timm itself is not in the image): crop_pct 0.95 for the 224 variants, 1.0 for the 384 one,
             # 1.0 with crop_mode "squash" for the 512 one; bicubic everywhere
-            crop = 0.95 if bb.cfg.img_size == 224 else 1.0
-            pixel_values = images_to_pixel_values(image, bb.cfg.img_size, TINYVIT_MEAN, TINYVIT_STD, bb.flat_params.device, crop_pct=crop, pipeline="timm",
-                                                  crop_mode="squash" if bb.cfg.img_size == 512 else "center")
+            # (keyed on the variant's own size: an ``img_size=`` override changes the target side, not the checkpoint's transform)
+            native = VARIANTS[bb.model_name]["img_size"]
+            crop = 0.95 if native == 224 else 1.0
+            pixel_values = images_to_pixel_values(image, bb.img_size, TINYVIT_MEAN, TINYVIT_STD, bb.flat_params.device, crop_pct=crop, pipeline="timm",
+                                                  crop_mode="squash" if native == 512 else "center")
         with torch.no_grad():
             return self.tinyvit_model(pixel_values=pixel_values).pooler_output
 
