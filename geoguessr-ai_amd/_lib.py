@@ -95,6 +95,25 @@ class ClsHeadArgs(C.Structure):          # GgClsHeadArgs (include/gg_cls.h)
                 ("dlogits_f32", C.c_int), ("rank", C.c_void_p), ("preds", C.c_void_p)]
 
 
+AUG_MAX_LAYERS = 4                        # GG_AUG_MAX_LAYERS (include/gg_aug.h)
+
+
+class AugOp(C.Structure):                # GgAugOp: one RandAugment op slot with its resolved arguments
+    _fields_ = [("op", C.c_int32), ("applied", C.c_int32), ("iarg", C.c_int32), ("factor", C.c_float), ("m", C.c_double * 6), ("resample", C.c_int32),
+                ("fill", C.c_uint8 * 3), ("reserved", C.c_uint8)]
+
+
+class AugRecord(C.Structure):            # GgAugRecord: crop box, flip flag and the op slots of one image
+    _fields_ = [("top", C.c_int32), ("left", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("flip", C.c_int32), ("num_layers", C.c_int32),
+                ("ops", AugOp * AUG_MAX_LAYERS)]
+
+
+class AugArgs(C.Structure):              # GgAugArgs
+    _fields_ = [("src", C.c_void_p), ("src_bytes", C.c_int64), ("offsets", C.c_void_p), ("heights", C.c_void_p), ("widths", C.c_void_p), ("B", C.c_int), ("S", C.c_int),
+                ("filter", C.c_int), ("mean", C.c_float * 3), ("std", C.c_float * 3), ("records", C.c_void_p), ("dst", C.c_void_p), ("dst_u8", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 STAGE_DONE_FN = C.CFUNCTYPE(None, C.c_int, C.c_void_p)      # GgStageDoneFn (host callback of gg_tinyvit_backward)
 
 # every exported symbol of include/gg.h: name -> (restype, argtypes)
@@ -324,6 +343,13 @@ PAD_SIGNATURES = {
 PAD_SYMBOLS = list(PAD_SIGNATURES)
 PROF_CAT_PAD = 7                          # GG_CAT_PAD (csrc/prof.h): the launch profiler's category of the two kernels
 
+# every exported symbol of include/gg_aug.h (the device-side training transform of the classifier fine-tune: crop, flip, RandAugment, normalise), bound from the same libgg.so
+AUG_SIGNATURES = {
+    "gg_aug_workspace_bytes": (_L, [C.POINTER(AugArgs)]),
+    "gg_aug_batch": (_I, [C.POINTER(AugArgs), _P]),
+}
+AUG_SYMBOLS = list(AUG_SIGNATURES)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -332,7 +358,7 @@ def lib() -> C.CDLL:
             raise GgError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the library lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -383,6 +409,7 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(root), "include", "gg_cls.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_drop.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_pad.h"))
+    files.append(os.path.join(os.path.dirname(root), "include", "gg_aug.h"))
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")
