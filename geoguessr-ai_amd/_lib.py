@@ -350,6 +350,14 @@ AUG_SIGNATURES = {
 }
 AUG_SYMBOLS = list(AUG_SIGNATURES)
 
+# every exported symbol of include/gg_fp8.h (the CLIP tower's fp8 inference mode: W8A8 e4m3 GEMM, row quantiser, LayerNorm + quantiser), bound from the same libgg.so
+FP8_SIGNATURES = {
+    "gg_gemm_nt_e4m3": (_I, [C.POINTER(GemmArgs), _P, _P, _P]),
+    "gg_quant_rows_e4m3": (_I, [_P, _I, _L, _L, _I, _P, _L, _P, _P]),
+    "gg_layernorm_fwd_e4m3": (_I, [_P, _P, _P, _L, _I, _F, _P, _L, _P, _P]),
+}
+FP8_SYMBOLS = list(FP8_SIGNATURES)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -358,7 +366,7 @@ def lib() -> C.CDLL:
             raise GgError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the library lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -410,6 +418,7 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(root), "include", "gg_drop.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_pad.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_aug.h"))
+    files.append(os.path.join(os.path.dirname(root), "include", "gg_fp8.h"))
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

@@ -3,7 +3,7 @@
 // for SuperGuessr with a CLIP base (models/super_guessr.py:134-150,323-325: the last encoder layer is fine-tuned when the pretrained
 // head exists, every layer otherwise; main_coordinator_idun_s3.py:183-203 builds that model for training).
 //
-// A static schedule of libgg launches on one stream, in one of four arithmetic modes (GgClipCfg.act_dtype):
+// A static schedule of libgg launches on one stream, in one of five arithmetic modes (GgClipCfg.act_dtype):
 //   1  fp32 -- the reference's precision: f32 activations, v_mfma_f32_16x16x4_f32 GEMMs (gg_gemm_nt_f32 / gg_gemm_tn_f32), f32 LayerNorm, f32
 //      online-softmax attention (head dim 64);
 //   3  fp32_split -- mode 1's storage and workspace; every GEMM as an f32-accurate split product on the bf16 MFMA (x = x1 + x2 + x3 in bf16, six
@@ -11,7 +11,10 @@
 //      gradients through gg_gemm_tn_split3, attention through the split kernels of attention_split64.h (gg_attention_flash_fwd / _bwd, dtype 3);
 //      LayerNorm, token assembly, column sums and pooling are mode 1's f32 kernels;
 //   0  bf16 -- bf16 activations / MFMA operands, f32 accumulation, f32 statistics;
-//   2  fp16 -- the same with fp16 storage / v_mfma_f32_16x16x32_f16 (BASELINE config c4 names fp16), inference only.
+//   2  fp16 -- the same with fp16 storage / v_mfma_f32_16x16x32_f16 (BASELINE config c4 names fp16), inference only;
+//   8  fp8 -- mode 2's storage and schedule with the four Linears of every encoder layer (qkv, out_proj, fc1, fc2) as W8A8 e4m3 products
+//      (include/gg_fp8.h: one f32 scale per token row and per output channel, v_mfma_scale_f32_16x16x128_f8f6f4); LN1 / LN2 leave codes + scales directly,
+//      the attention output and the QuickGELU output are quantised by a pass of their own.  The vision tower only, inference only.
 // Patch embedding is a pure GEMM (stride == kernel); q/k/v projections are one [3D, D] GEMM; QuickGELU rides on fc1's epilogue (with the
 // pre-activation copy the backward pass needs), residual adds on out_proj's and fc2's.  Training keeps, for every layer from the first
 // trainable one up, the tensors its backward pass reads (layer input, both LayerNorm outputs + statistics, qkv, attention output + row
@@ -30,6 +33,7 @@
 #include "../../include/gg.h"
 #include "../../include/gg_clip_text.h"
 #include "../../include/gg_clip_text_train.h"
+#include "../../include/gg_fp8.h"
 
 namespace {
 struct TInfo { std::string name; int64_t offset, numel; int ndim; int64_t shape[4]; };
@@ -37,6 +41,7 @@ struct LayerP {
     int q_w, q_b, k_w, k_b, v_w, v_b, o_w, o_b, ln1_g, ln1_b, fc1_w, fc1_b, fc2_w, fc2_b, ln2_g, ln2_b;      // tensor ids
     int64_t wqkv, bqkv, wqkvT, wo, woT, w1, w1T, w2, w2T;                                                     // weight-cache offsets
     int64_t wqkv3 = -1, wqkvT3 = -1, wo3 = -1, woT3 = -1, w13 = -1, w1T3 = -1, w23 = -1, w2T3 = -1;           // fp32_split: bf16 planes [3][N][K] of the same matrices
+    int64_t wqkv8 = -1, wo8 = -1, w18 = -1, w28 = -1, sqkv = -1, so = -1, s1 = -1, s2 = -1;                   // fp8: e4m3 images [N][K] of the forward matrices and their f32 scales [N]
 };
 struct CModel {
     GgClipCfg cfg;
@@ -48,7 +53,7 @@ struct CModel {
     int T, G, Kpatch, Kraw;
     // the text tower (gg_clip_text_*) is the same layer stack over T = the call's token count with causal attention: embeddings and the final norm differ
     bool causal = false; int tok_emb = -1, fin_g = -1, fin_b = -1, vocab = 0;
-    bool f32, f16, split; int es;      // f32: f32 storage (fp32 and fp32_split modes); split: fp32_split; activation / cached-weight element size: 4 or 2 (bf16 / fp16 modes)
+    bool f32, f16, split, fp8 = false; int es;      // fp8: the fp16 mode (f16 is set too) with the encoder Linears as e4m3 products; f32: f32 storage (fp32 and fp32_split modes); split: fp32_split; activation / cached-weight element size: 4 or 2 (bf16 / fp16 modes)
 };
 static int addt(CModel& m, const std::string& n, std::initializer_list<int64_t> shape) {
     TInfo t; t.name = n; t.ndim = (int)shape.size(); t.numel = 1;
@@ -85,15 +90,20 @@ static void add_layers(CModel& m) {
         l.w2 = wca(m, (int64_t)D * I * m.es); l.w2T = wca(m, (int64_t)D * I * m.es);
         l.wqkv3 = planes((int64_t)3 * D * D); l.wqkvT3 = planes((int64_t)3 * D * D); l.wo3 = planes((int64_t)D * D); l.woT3 = planes((int64_t)D * D);
         l.w13 = planes((int64_t)I * D); l.w1T3 = planes((int64_t)I * D); l.w23 = planes((int64_t)D * I); l.w2T3 = planes((int64_t)D * I);
+        if (m.fp8) {      // (beside the fp16 images: the mode keeps mode 2's cache layout and adds to it)
+            l.wqkv8 = wca(m, (int64_t)3 * D * D); l.wo8 = wca(m, (int64_t)D * D); l.w18 = wca(m, (int64_t)I * D); l.w28 = wca(m, (int64_t)D * I);
+            l.sqkv = wca(m, (int64_t)3 * D * 4); l.so = wca(m, (int64_t)D * 4); l.s1 = wca(m, (int64_t)I * 4); l.s2 = wca(m, (int64_t)D * 4);
+        }
     }
 }
 
 static int build(const GgClipCfg* c, CModel& m) {
     GG_CHECK(c, "clip: null config");
     m.cfg = *c;
-    GG_CHECK(c->act_dtype >= 0 && c->act_dtype <= 3, "clip: act_dtype must be 0 (bf16), 1 (fp32), 2 (fp16) or 3 (fp32_split), got %d", c->act_dtype);
-    m.split = c->act_dtype == 3; m.f32 = c->act_dtype == 1 || m.split; m.f16 = c->act_dtype == 2; m.es = m.f32 ? 4 : 2;
+    GG_CHECK((c->act_dtype >= 0 && c->act_dtype <= 3) || c->act_dtype == GG_CLIP_ACT_FP8, "clip: act_dtype must be 0 (bf16), 1 (fp32), 2 (fp16), 3 (fp32_split) or 8 (fp8: include/gg_fp8.h), got %d", c->act_dtype);
+    m.split = c->act_dtype == 3; m.f32 = c->act_dtype == 1 || m.split; m.fp8 = c->act_dtype == GG_CLIP_ACT_FP8; m.f16 = c->act_dtype == 2 || m.fp8; m.es = m.f32 ? 4 : 2;
     const int D = c->hidden_size, I = c->intermediate_size, P = c->patch_size;
+    GG_CHECK(!m.fp8 || (D % 128 == 0 && I % 128 == 0), "clip: the fp8 mode needs hidden_size and intermediate_size multiples of 128 (one K = 128 e4m3 MFMA per stage), got %d / %d", D, I);
     GG_CHECK(D > 0 && D % 64 == 0 && D <= 1024 && c->num_heads > 0 && D / c->num_heads == 64, "clip: head_dim must be 64 and hidden <= 1024 (hidden %d, heads %d)", D, c->num_heads);
     GG_CHECK(P > 0 && c->image_size % P == 0 && I % 8 == 0 && c->num_layers > 0, "clip: bad patch/image/intermediate size or layer count");
     // patch-embedding contraction 3*P*P is padded to a multiple of 8 (ViT-L/14: 588 -> 592 zero columns); sequences beyond 256 tokens
@@ -112,7 +122,7 @@ static int build(const GgClipCfg* c, CModel& m) {
 // the text tower's model over `tokens` positions per sequence (the tensor table does not depend on it)
 static int build_text(const GgClipTextCfg* c, int tokens, CModel& m) {
     GG_CHECK(c, "clip_text: null config");
-    GG_CHECK(c->act_dtype == 0 || c->act_dtype == 1 || c->act_dtype == 3, "clip_text: act_dtype must be 0 (bf16), 1 (fp32) or 3 (fp32_split), got %d (fp16 is not built)", c->act_dtype);
+    GG_CHECK(c->act_dtype == 0 || c->act_dtype == 1 || c->act_dtype == 3, "clip_text: act_dtype must be 0 (bf16), 1 (fp32) or 3 (fp32_split), got %d (fp16 and fp8 are not built for the text tower)", c->act_dtype);
     const int D = c->hidden_size, I = c->intermediate_size;
     GG_CHECK(D > 0 && D % 64 == 0 && D <= 1024 && c->num_heads > 0 && D / c->num_heads == 64 && D % c->num_heads == 0,
              "clip_text: head_dim must be 64 and hidden <= 1024 (hidden %d, heads %d)", D, c->num_heads);
@@ -313,6 +323,7 @@ struct LayerA { int64_t xin, a1, qkv, o, lse, xmid, a2, pre, h, mean1, rstd1, me
 struct CPlan {
     int64_t col, patches, tok, mean0, rstd0;                  // embedding side (tok = tokens before pre_layrnorm)
     int64_t s_x, s_a, s_qkv, s_o, s_h;                        // scratch of the layers that keep nothing (in-place residual stream)
+    int64_t q8 = -1, qs = -1;                                 // fp8: the e4m3 codes of the Linear input at hand (M x max(D, I) bytes, reused) and its scale row
     std::vector<LayerA> la;
     int64_t xfinal;
     int64_t g_x0, g_x1, g_a, g_qkv, g_o, g_h, splitk, colsum, lnscr, lndump, attn_ds = -1;      // lndump: where a frozen LayerNorm tensor's half of a (gamma, beta) gradient pair goes      // backward scratch (attn_ds: GgAttnArgs.ds_scratch)
@@ -328,6 +339,7 @@ static void plan(const CModel& m, int B, const Train& tr, bool training, CPlan& 
     auto al = [&](int64_t bytes) { int64_t o = off; off += gg_align(std::max<int64_t>(bytes, 1), 256); return o; };
     L.col = al(Mp * m.Kpatch * es); L.patches = al(Mp * D * es); L.tok = al(M * D * es); L.mean0 = al(M * 4); L.rstd0 = al(M * 4);
     L.s_x = al(M * D * es); L.s_a = al(M * D * es); L.s_qkv = al(M * 3 * D * es); L.s_o = al(M * D * es); L.s_h = al(M * I * es);
+    if (m.fp8) { L.q8 = al(M * std::max(D, I)); L.qs = al(M * 4); }
     L.la.assign(nl, LayerA{});
     L.xfinal = L.s_x;
     const bool bwd = training && tr.l0 < nl;
@@ -413,6 +425,18 @@ struct Exec {
         if (m->f32) return gg_gemm_tn_f32(dY, ldy, X, ldx, (int)M, N, K, nullptr, 0, F(L->splitk), *splits, st);
         return gg_gemm_tn(dY, ldy, X, ldx, (int)M, N, K, nullptr, 0, F(L->splitk), *splits, st);
     }
+    // fp8: C fp16 = epi(sa * sw * (codes of A in L->q8 . W8^T) + bias); the codes and L->qs were left by ln_fwd8 / quant8
+    int gemm8(int64_t w8, int64_t sw, void* C, int64_t ldc, int64_t Mm, int N, int K, const float* bias, int act = 0, const void* residual = nullptr) const {
+        GgGemmArgs g;
+        memset(&g, 0, sizeof(g));
+        g.A = A(L->q8); g.lda = K; g.B = W(w8); g.ldb = K; g.C = C; g.ldc = ldc; g.M = (int)Mm; g.N = N; g.K = K;
+        g.bias = bias; g.act = act; g.residual = residual; g.ldr = ldc;
+        return gg_gemm_nt_e4m3(&g, F(L->qs), (const float*)W(sw), st);
+    }
+    int quant8(const void* x, int64_t M, int K) const { return gg_quant_rows_e4m3(x, 0, K, M, K, A(L->q8), K, F(L->qs), st); }
+    int ln_fwd8(const void* x, int tg, int tb, int64_t M) const {
+        return gg_layernorm_fwd_e4m3(x, P(tg), P(tb), M, m->cfg.hidden_size, m->cfg.ln_eps, A(L->q8), m->cfg.hidden_size, F(L->qs), st);
+    }
     int ln_fwd(const void* x, int tg, int tb, int64_t M, void* out, float* mean, float* rstd) const {
         if (m->f16) return gg_layernorm_fwd_f16(x, P(tg), P(tb), M, m->cfg.hidden_size, m->cfg.ln_eps, out, st);
         return gg_layernorm_fwd(x, m->f32, P(tg), P(tb), M, m->cfg.hidden_size, m->cfg.ln_eps, out, m->f32, mean, rstd, st);
@@ -471,6 +495,22 @@ static int layer_fwd(const Exec& e, int i, int64_t cur, int64_t next, bool sv) {
     const int64_t M = (int64_t)e.B * T;
     const int64_t A1 = sv ? a.a1 : L.s_a, QKV = sv ? a.qkv : L.s_qkv, O = sv ? a.o : L.s_o, XMID = sv ? a.xmid : cur, A2 = sv ? a.a2 : L.s_a,
                   H = sv ? a.h : L.s_h;
+    if (m.fp8) {
+        // mode 2's layer with each Linear's input as e4m3 codes + row scales in L.q8 / L.qs (one buffer: every Linear consumes its input before the next is formed)
+        GG_CHECK(!sv && next >= 0, "clip: the fp8 mode is inference-only");
+        GG_TRY(e.ln_fwd8(e.A(cur), l.ln1_g, l.ln1_b, M));
+        GG_TRY(e.gemm8(l.wqkv8, l.sqkv, e.A(QKV), 3 * D, M, 3 * D, D, (const float*)e.W(l.bqkv)));
+        GgAttnArgs at8;
+        e.attn_args(at8, e.A(QKV), e.A(O), nullptr);
+        GG_TRY(gg_attention_fwd_f16(&at8, e.st));
+        GG_TRY(e.quant8(e.A(O), M, D));
+        GG_TRY(e.gemm8(l.wo8, l.so, e.A(XMID), D, M, D, D, e.P(l.o_b), 0, e.A(cur)));
+        GG_TRY(e.ln_fwd8(e.A(XMID), l.ln2_g, l.ln2_b, M));
+        GG_TRY(e.gemm8(l.w18, l.s1, e.A(H), I, M, I, D, e.P(l.fc1_b), GG_ACT_CODE_QUICK_GELU));
+        GG_TRY(e.quant8(e.A(H), M, I));
+        GG_TRY(e.gemm8(l.w28, l.s2, e.A(next), D, M, D, I, e.P(l.fc2_b), 0, e.A(XMID)));
+        return 0;
+    }
     GG_TRY(e.ln_fwd(e.A(cur), l.ln1_g, l.ln1_b, M, e.A(A1), sv ? e.F(a.mean1) : nullptr, sv ? e.F(a.rstd1) : nullptr));
     GG_TRY(e.gemm(e.A(A1), D, e.W(l.wqkv, l.wqkv3), D, e.A(QKV), 3 * D, M, 3 * D, D, (const float*)e.W(l.bqkv)));
     GgAttnArgs at;
@@ -669,6 +709,13 @@ static int refresh_model(const CModel& m, const float* params, void* wcache, con
         if (ch(l.o_w)) { GG_TRY(split3(l.wo, D, D, l.wo3)); GG_TRY(split3(l.woT, D, D, l.woT3)); }
         if (ch(l.fc1_w)) { GG_TRY(split3(l.w1, I, D, l.w13)); GG_TRY(split3(l.w1T, D, I, l.w1T3)); }
         if (ch(l.fc2_w)) { GG_TRY(split3(l.w2, D, I, l.w23)); GG_TRY(split3(l.w2T, I, D, l.w2T3)); }
+        if (m.fp8) {      // e4m3 images from the f32 master weights, one scale per output channel (the three projections are rows of one image)
+            auto q8 = [&](int tw, int64_t R, int C, int64_t img, int64_t sc, int64_t r0) -> int {
+                return ch(tw) ? gg_quant_rows_e4m3(P(tw), 1, C, R, C, wc + img + r0 * C, C, (float*)(wc + sc) + r0, st) : 0;
+            };
+            GG_TRY(q8(l.q_w, D, D, l.wqkv8, l.sqkv, 0)); GG_TRY(q8(l.k_w, D, D, l.wqkv8, l.sqkv, D)); GG_TRY(q8(l.v_w, D, D, l.wqkv8, l.sqkv, 2 * D));
+            GG_TRY(q8(l.o_w, D, D, l.wo8, l.so, 0)); GG_TRY(q8(l.fc1_w, I, D, l.w18, l.s1, 0)); GG_TRY(q8(l.fc2_w, D, I, l.w28, l.s2, 0));
+        }
     }
     GG_LAUNCH_CHECK();
     return 0;
@@ -681,6 +728,7 @@ extern "C" int gg_clip_forward(const GgClipCfg* cfg, int batch, int training, co
     GG_CHECK(batch > 0 && params && wcache && x && workspace && out, "gg_clip_forward: null pointer / bad batch");
     GG_CHECK(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)wcache & 255) == 0, "gg_clip_forward: workspace / wcache must be 256-byte aligned");
     const Train tr = train_of(m, training, trainable);
+    GG_CHECK(!(m.fp8 && training), "gg_clip_forward: the fp8 mode is inference-only (training = 1 refused; train in fp32 or bf16)");
     GG_CHECK(!(m.f16 && training && tr.l0 < m.cfg.num_layers), "gg_clip_forward: the fp16 mode is inference-only (train in fp32 or bf16)");
     CPlan L; plan(m, batch, tr, training != 0, L);
     Exec e{&m, &L, batch, (hipStream_t)stream, params, (const char*)wcache, (char*)workspace, nullptr, trainable};
@@ -719,6 +767,7 @@ extern "C" int gg_clip_backward(const GgClipCfg* cfg, int batch, const float* pa
     CModel m;
     GG_TRY(build(cfg, m));
     GG_CHECK(batch > 0 && params && wcache && workspace && grads && (d_out || d_last_hidden), "gg_clip_backward: null pointer / bad batch");
+    GG_CHECK(!m.fp8, "gg_clip_backward: the fp8 mode is inference-only");
     const Train tr = train_of(m, 1, trainable);
     const int nl = m.cfg.num_layers;
     if (tr.l0 >= nl) return 0;                    // nothing in the tower is trainable

@@ -772,3 +772,48 @@ def dwconv3x3_s2_bwd_data_fused(dz_in, y_in, in_coef, taps, H, W, ep_y=None, ep_
     L.check(fn(_p(dz_in, DT), _p(y_in, DT), _p(in_coef, F32), _p(taps, F32), _p(out), B, H, W, Cc, _p(ep_y, DT), _p(ep_stat, F32), _p(ep_gamma, F32),
                _p(ep_beta, F32), ACT[ep_act], _p(part), L.stream()), "gg_dwconv3x3_s2_bwd_data_fused")
     return out, (part[:rows_fn(B, H, W, Cc)] if part is not None else None)
+
+
+# ---- FP8 (e4m3) kernels of the CLIP tower's fp8 inference mode (include/gg_fp8.h) -------------------------------------------------------------
+def quant_rows_e4m3(x, K=None, q=None, scale=None):
+    """Rows of ``x`` (fp16 or f32, 2-D, rows may be strided) -> (codes uint8 [M, K] (``q``: a strided destination), scale f32 [M]): one f32 scale per row,
+    e4m3fn codes (the contract of include/gg_fp8.h)."""
+    L.require_gpu()
+    M = x.shape[0]
+    K = x.shape[1] if K is None else K
+    if x.dtype not in (torch.float16, F32):
+        raise L.GgError(f"quant_rows_e4m3: x must be fp16 or f32, got {x.dtype}")
+    q = torch.empty((M, K), dtype=torch.uint8, device=x.device) if q is None else q
+    scale = torch.empty(M, dtype=F32, device=x.device) if scale is None else scale
+    L.check(L.lib().gg_quant_rows_e4m3(_pr(x, None, "x"), int(x.dtype == F32), x.stride(0), M, K, _pr(q, torch.uint8, "q"), q.stride(0), _p(scale, F32, "scale"),
+                                       L.stream()), "gg_quant_rows_e4m3")
+    return q, scale
+
+
+def layernorm_fwd_e4m3(x, gamma, beta, eps=1e-5, q=None, scale=None):
+    """LayerNorm of fp16 ``x`` [M, C] (gg_layernorm_fwd_f16's arithmetic) quantised in the same pass -> (codes uint8 [M, C], scale f32 [M])."""
+    L.require_gpu()
+    M, Cc = x.shape
+    q = torch.empty((M, Cc), dtype=torch.uint8, device=x.device) if q is None else q
+    scale = torch.empty(M, dtype=F32, device=x.device) if scale is None else scale
+    L.check(L.lib().gg_layernorm_fwd_e4m3(_p(x, torch.float16, "x"), _p(gamma, F32, "gamma"), _p(beta, F32, "beta"), M, Cc, L.f32(eps), _pr(q, torch.uint8, "q"),
+                                          q.stride(0), _p(scale, F32, "scale"), L.stream()), "gg_layernorm_fwd_e4m3")
+    return q, scale
+
+
+def gemm_nt_e4m3(A, B, sa, sw, *, bias=None, act=None, residual=None, out=None, M=None, N=None, K=None):
+    """C fp16 [M, N] = epi(sa[m] * sw[n] * (A[M, K] @ B[N, K]^T) + bias[n]) with A, B e4m3fn codes (uint8, rows may be strided); ``act`` None or
+    "quick_gelu"; ``residual`` fp16 (``out`` may be the same tensor)."""
+    L.require_gpu()
+    M = A.shape[0] if M is None else M
+    K = A.shape[1] if K is None else K
+    N = B.shape[0] if N is None else N
+    out = torch.empty((M, N), dtype=torch.float16, device=A.device) if out is None else out
+    a = L.GemmArgs()
+    a.A, a.lda, a.B, a.ldb, a.C, a.ldc = _pr(A, torch.uint8, "A"), A.stride(0), _pr(B, torch.uint8, "B"), B.stride(0), _pr(out, torch.float16, "out"), out.stride(0)
+    a.M, a.N, a.K = M, N, K
+    a.bias, a.act = _p(bias, F32, "bias"), ACT[act]
+    a.residual, a.ldr = _pr(residual, torch.float16, "residual"), (residual.stride(0) if residual is not None else 0)
+    a.split_k = 1
+    L.check(L.lib().gg_gemm_nt_e4m3(C.byref(a), _p(sa, F32, "sa"), _p(sw, F32, "sw"), L.stream()), "gg_gemm_nt_e4m3")
+    return out

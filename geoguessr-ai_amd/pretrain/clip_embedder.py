@@ -11,8 +11,9 @@
   activation recompute (``GgClipCfg.recompute``): the workspace keeps each trained layer's input instead of its eight activations.
 
 Arithmetic: ``precision="fp32"`` (default; the reference runs the tower in fp32), ``"fp32_split"`` (f32 storage, every GEMM and the attention as
-f32-accurate split-bf16 products: ``GgClipCfg.act_dtype`` 3), ``"bf16"``, or ``"fp16"`` (inference only: the precision BASELINE
-config c4 names); the default is ``$GG_PRECISION``.  No hub download: weights come from a
+f32-accurate split-bf16 products: ``GgClipCfg.act_dtype`` 3), ``"bf16"``, ``"fp16"`` (inference only: the precision BASELINE
+config c4 names), or ``"fp8"`` (inference only: fp16's storage and schedule with the four Linears of every encoder layer as W8A8 e4m3 products,
+``GgClipCfg.act_dtype`` 8, include/gg_fp8.h; resolved by ``tower_precision_code``); the default is ``$GG_PRECISION``.  No hub download: weights come from a
 state dict (HF names, with or without the leading ``vision_model.``)."""
 from __future__ import annotations
 
@@ -32,7 +33,7 @@ CLIP_CONFIGS = {
 }
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)      # CLIPProcessor's image_mean / image_std (openai/clip-vit-*)
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
-PRECISION_NAMES = {0: "bf16", 1: "fp32", 2: "fp16", 3: "fp32_split"}      # GgClipCfg.act_dtype -> the name ``.precision`` reports
+PRECISION_NAMES = {0: "bf16", 1: "fp32", 2: "fp16", 3: "fp32_split", 8: "fp8"}      # GgClipCfg.act_dtype -> the name ``.precision`` reports
 
 
 def _precision_code(precision: Optional[str]) -> int:
@@ -43,6 +44,20 @@ def _precision_code(precision: Optional[str]) -> int:
     if p not in PRECISIONS:
         raise ValueError(f"precision='{p}' (known: bf16, fp16, fp32, fp32_split)")
     return PRECISIONS[p]
+
+
+FP8_CODE = 8                          # GG_CLIP_ACT_FP8 (include/gg_fp8.h)
+
+
+def tower_precision_code(precision: Optional[str]) -> int:
+    """``_precision_code`` plus the one name only the VISION tower takes: ``"fp8"`` / ``"e4m3"`` (inference only: W8A8 e4m3 Linears on fp16 storage).  The name is
+    an explicit argument only: ``$GG_PRECISION`` and ``_precision_code`` (shared with the text tower's callers) keep refusing it."""
+    if precision in ("fp8", "e4m3"):
+        return FP8_CODE
+    try:
+        return _precision_code(precision)
+    except ValueError as e:
+        raise ValueError(f"{e}; CLIPVisionTower / CLIPEmbedding also take fp8") from None
 
 
 class _VisionModel(EncoderRuntime):
@@ -145,7 +160,7 @@ class CLIPVisionTower(nn.Module):
         c = L.ClipCfg()
         c.hidden_size, c.intermediate_size, c.num_layers, c.num_heads = kw["hidden_size"], kw["intermediate_size"], kw["num_layers"], kw["num_heads"]
         c.image_size, c.patch_size, c.ln_eps = kw["image_size"], kw["patch_size"], 1e-5
-        c.act_dtype = _precision_code(precision)
+        c.act_dtype = tower_precision_code(precision)
         c.recompute = int(bool(gradient_checkpointing))
         self.cfg = c
         self.precision = PRECISION_NAMES[c.act_dtype]
@@ -196,8 +211,8 @@ class CLIPVisionTower(nn.Module):
     def forward(self, pixel_values: Tensor = None, return_last_hidden: bool = True):
         vm = self.vision_model
         need = vm.wants_grad()      # (no dropout / BatchNorm: train and eval compute the same)
-        if need and self.precision == "fp16":
-            raise L.GgError("CLIPVisionTower(precision='fp16') is inference-only: run under torch.no_grad() / freeze it, or train in fp32 / bf16")
+        if need and self.precision in ("fp16", "fp8"):
+            raise L.GgError(f"CLIPVisionTower(precision='{self.precision}') is inference-only: run under torch.no_grad() / freeze it, or train in fp32 / bf16")
         if not need:
             out, last = vm.forward_hip(pixel_values, False, return_last_hidden)
         else:

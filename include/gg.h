@@ -574,7 +574,8 @@ int gg_segment_mean(const float* emb, int64_t ld, const int64_t* ptr, const int6
 typedef struct GgClipCfg {
     int hidden_size, intermediate_size, num_layers, num_heads, image_size, patch_size;
     float ln_eps;
-    int act_dtype;                         /* 0 bf16, 1 fp32, 2 fp16 (inference only), 3 fp32_split (f32 storage, split-bf16 products) */
+    int act_dtype;                         /* 0 bf16, 1 fp32, 2 fp16 (inference only), 3 fp32_split (f32 storage, split-bf16 products), 8 fp8 (GG_CLIP_ACT_FP8; inference only, vision tower only:
+                                              mode 2 with qkv / out_proj / fc1 / fc2 as W8A8 e4m3 products, include/gg_fp8.h; hidden and intermediate size multiples of 128) */
     int recompute;       /* activation recompute (gradient checkpointing, HF gradient_checkpointing_enable) of a training forward / backward pair;
                             ignored by inference (training = 0).  0: the workspace keeps every activation the backward reads.
                             1: per-layer checkpoints -- the segments are the encoder layers from the first trainable one up.  The workspace keeps
