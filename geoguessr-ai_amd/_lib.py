@@ -114,6 +114,16 @@ class AugArgs(C.Structure):              # GgAugArgs
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class EvalGeom(C.Structure):             # GgEvalGeom (include/gg_eval.h): resized size of the whole image, crop origin inside it
+    _fields_ = [("Hr", C.c_int32), ("Wr", C.c_int32), ("top", C.c_int32), ("left", C.c_int32)]
+
+
+class EvalArgs(C.Structure):             # GgEvalArgs
+    _fields_ = [("src", C.c_void_p), ("src_bytes", C.c_int64), ("offsets", C.c_void_p), ("heights", C.c_void_p), ("widths", C.c_void_p), ("geom", C.c_void_p),
+                ("B", C.c_int), ("Hc", C.c_int), ("Wc", C.c_int), ("filter", C.c_int), ("mul_rescale", C.c_int), ("normalize", C.c_int), ("mean", C.c_float * 3),
+                ("std", C.c_float * 3), ("dst", C.c_void_p), ("dst_u8", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 STAGE_DONE_FN = C.CFUNCTYPE(None, C.c_int, C.c_void_p)      # GgStageDoneFn (host callback of gg_tinyvit_backward)
 
 # every exported symbol of include/gg.h: name -> (restype, argtypes)
@@ -358,6 +368,13 @@ FP8_SIGNATURES = {
 }
 FP8_SYMBOLS = list(FP8_SIGNATURES)
 
+# every exported symbol of include/gg_eval.h (the eval transform of the raw-image path for whole batches: Pillow resize, crop, 1/255, normalise), bound from the same libgg.so
+EVAL_SIGNATURES = {
+    "gg_eval_workspace_bytes": (_L, [C.POINTER(EvalArgs)]),
+    "gg_eval_batch": (_I, [C.POINTER(EvalArgs), _P]),
+}
+EVAL_SYMBOLS = list(EVAL_SIGNATURES)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -366,7 +383,7 @@ def lib() -> C.CDLL:
             raise GgError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the library lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -419,6 +436,7 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(root), "include", "gg_pad.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_aug.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_fp8.h"))
+    files.append(os.path.join(os.path.dirname(root), "include", "gg_eval.h"))
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

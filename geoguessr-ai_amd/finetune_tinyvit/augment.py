@@ -270,3 +270,20 @@ class augmented:
             if not torch.is_tensor(labels):
                 labels = torch.as_tensor(labels, dtype=torch.int64)
             yield {"pixel_values": self.transform(batch["images"]), "labels": labels.to(self.transform.device)}
+
+
+class eval_transformed:
+    """The twin of ``augmented`` for the validation side -- the reference's ``collate_val``: ``{"images", "labels"}`` batches -> ``{"pixel_values", "labels"}``
+    batches, lazily, one ``transform`` call (``training.preprocess.DeviceEvalTransform``: one ``gg_eval_batch``) per batch, so
+    ``evaluate(model, eval_transformed(raw_val, tfm))`` and ``extract_embeddings(model, eval_transformed(...))`` run on raw images.  Nothing is drawn: every walk
+    yields the same batches."""
+
+    def __init__(self, batches: Iterable, transform):
+        self.batches, self.transform = batches, transform
+
+    def __iter__(self):
+        for batch in self.batches:
+            labels = batch["labels"]
+            if not torch.is_tensor(labels):
+                labels = torch.as_tensor(labels, dtype=torch.int64)
+            yield {"pixel_values": self.transform(batch["images"]), "labels": labels.to(self.transform.device)}

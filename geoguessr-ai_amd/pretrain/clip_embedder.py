@@ -241,9 +241,13 @@ def clip_preprocess(images, size: int, device) -> Tensor:
 
 class CLIPEmbedding(nn.Module):
     def __init__(self, model_name: str = "openai/clip-vit-base-patch32", device: str = "cuda", load_checkpoint: bool = False,
-                 panorama: bool = False, state_dict: Optional[Dict[str, Tensor]] = None, precision: Optional[str] = None, **cfg_overrides):
+                 panorama: bool = False, state_dict: Optional[Dict[str, Tensor]] = None, precision: Optional[str] = None, batch_transform: bool = False,
+                 **cfg_overrides):
+        """``batch_transform`` (not in the reference): raw images -- a list of any sizes, or the four panorama views together -- go through ONE ``gg_eval_batch``
+        call (``training.preprocess.DeviceEvalTransform``) instead of one ``gg_preprocess_pil`` call per image; same arithmetic."""
         super().__init__()
         self.device = device
+        self.batch_transform, self._transform = bool(batch_transform), None
         self.panorama = panorama
         self.clip_model = CLIPVisionTower(model_name if not load_checkpoint else "openai/clip-vit-base-patch32", precision=precision, **cfg_overrides)
         if load_checkpoint:
@@ -256,12 +260,21 @@ class CLIPEmbedding(nn.Module):
             p.requires_grad = False
         self.eval()
 
+    def _eval_transform(self):
+        """The processor's tensor side as a batch transform (``batch_transform=True``); it keeps its workspace from call to call."""
+        if self._transform is None:
+            from ..training.preprocess import DeviceEvalTransform
+            self._transform = DeviceEvalTransform(self.clip_model.cfg.image_size, CLIP_MEAN, CLIP_STD, "clip", device=next(self.clip_model.parameters()).device)
+        return self._transform
+
     def _get_embedding(self, image) -> Tensor:
         """A float tensor is taken as ``pixel_values`` (pretrain/clip_embedder.py:58-59); anything else -- PIL image, uint8 array / tensor, list of
         images -- goes through the processor's tensor side on the device (:55-57)."""
         dev = next(self.clip_model.parameters()).device
         if torch.is_tensor(image) and image.is_floating_point():
             pixel_values = image
+        elif self.batch_transform:
+            pixel_values = self._eval_transform()(image)
         else:
             pixel_values = clip_preprocess(image, self.clip_model.cfg.image_size, dev)
         with torch.no_grad():
@@ -270,5 +283,8 @@ class CLIPEmbedding(nn.Module):
     def forward(self, image, **kwargs) -> Tensor:
         if "image_2" not in kwargs:
             return self._get_embedding(image)
-        embs = [self._get_embedding(image)] + [self._get_embedding(kwargs[c]) for c in ("image_2", "image_3", "image_4")]
-        return torch.stack(embs, dim=1)
+        views = [image] + [kwargs[c] for c in ("image_2", "image_3", "image_4")]
+        if self.batch_transform:
+            from .tinyvit_embedder import _transform_views
+            views = _transform_views(views, self._eval_transform())
+        return torch.stack([self._get_embedding(v) for v in views], dim=1)

@@ -13,11 +13,14 @@ from ..models.tinyvit import VARIANTS, TinyViTAdapter
 
 class TinyViTEmbedding(torch.nn.Module):
     def __init__(self, model_name: str = "tiny_vit_21m_512.dist_in22k_ft_in1k", device: str = "cuda", load_checkpoint: bool = False,
-                 panorama: bool = False, img_size: int = None):
+                 panorama: bool = False, img_size: int = None, batch_transform: bool = False):
         """``img_size`` (not in the reference): run the checkpoint at another input side (a multiple of 32; ``TinyViTAdapter``'s override) -- the preprocessing
-        resizes to that side, with the crop settings of the checkpoint's own variant."""
+        resizes to that side, with the crop settings of the checkpoint's own variant.  ``batch_transform`` (not in the reference): raw images -- a list of any
+        sizes, or the four panorama views together -- go through ONE ``gg_eval_batch`` call (``training.preprocess.DeviceEvalTransform``) instead of one
+        ``gg_preprocess_pil`` call per image; same arithmetic."""
         super().__init__()
         self.device, self.panorama, self.model_name = device, panorama, model_name
+        self.batch_transform, self._transform = bool(batch_transform), None
         arch = "tiny_vit_21m_224" if load_checkpoint else model_name
         self.tinyvit_model = TinyViTAdapter(arch, pretrained=not load_checkpoint, **({} if img_size is None else dict(img_size=int(img_size))))
         if load_checkpoint:
@@ -26,9 +29,21 @@ class TinyViTEmbedding(torch.nn.Module):
         self.tinyvit_model = self.tinyvit_model.to(device if isinstance(device, str) else f"cuda:{device}")
         self.eval()
 
+    def _eval_transform(self):
+        """The batch transform with this checkpoint's crop settings (``batch_transform=True``); it keeps its workspace from call to call."""
+        if self._transform is None:
+            from ..training.preprocess import TINYVIT_MEAN, TINYVIT_STD, DeviceEvalTransform
+            bb = self.tinyvit_model.backbone
+            native = VARIANTS[bb.model_name]["img_size"]
+            self._transform = DeviceEvalTransform(bb.img_size, TINYVIT_MEAN, TINYVIT_STD, "timm", 0.95 if native == 224 else 1.0,
+                                                  "squash" if native == 512 else "center", bb.flat_params.device)
+        return self._transform
+
     def _get_embedding(self, image) -> Tensor:
         if isinstance(image, Tensor) and image.is_floating_point():
             pixel_values = image
+        elif self.batch_transform:
+            pixel_values = self._eval_transform()(image)
         else:
             from ..training.preprocess import TINYVIT_MEAN, TINYVIT_STD, images_to_pixel_values
             bb = self.tinyvit_model.backbone
@@ -45,5 +60,32 @@ class TinyViTEmbedding(torch.nn.Module):
     def forward(self, image, **kwargs) -> Tensor:
         if "image_2" not in kwargs:
             return self._get_embedding(image)
-        embs = [self._get_embedding(image)] + [self._get_embedding(kwargs[c]) for c in ("image_2", "image_3", "image_4")]
-        return torch.stack(embs, dim=1)
+        views = [image] + [kwargs[c] for c in ("image_2", "image_3", "image_4")]
+        if self.batch_transform:
+            views = _transform_views(views, self._eval_transform())
+        return torch.stack([self._get_embedding(v) for v in views], dim=1)
+
+
+def _host_raw_list(v):
+    """A view's raw host images as a list of (H, W, 3) uint8 tensors, or None when the view keeps its own path (float tensors are pixel_values already; a device
+    tensor is transformed where it lives)."""
+    from ..training.preprocess import _rgb_hwc
+    if isinstance(v, Tensor):
+        if v.is_floating_point() or v.is_cuda or v.dtype != torch.uint8 or v.dim() not in (3, 4):
+            return None
+        return [im.permute(1, 2, 0).contiguous() for im in (v if v.dim() == 4 else v.unsqueeze(0))]
+    return [_rgb_hwc(im) for im in (v if isinstance(v, (list, tuple)) else [v])]
+
+
+def _transform_views(views, transform):
+    """The panorama views' raw host images through ONE transform call: they are joined into one list, transformed together and handed back as per-view
+    ``pixel_values``."""
+    lists = [_host_raw_list(v) for v in views]
+    flat = [im.numpy() for l in lists if l is not None for im in l]
+    if not flat:
+        return views
+    pv, out, at = transform(flat), [], 0
+    for v, l in zip(views, lists):
+        out.append(v if l is None else pv[at:at + len(l)])
+        at += 0 if l is None else len(l)
+    return out

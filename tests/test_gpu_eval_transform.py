@@ -1,0 +1,346 @@
+"""The batched eval transform (include/gg_eval.h, csrc/eval_transform.hip, training/preprocess.py::DeviceEvalTransform) on the GPU: the uint8 crops BYTE-IDENTICAL to
+Pillow's own outputs (tests/golden/eval_batch_pil.npz, tests/golden/preprocess_pil.npz) and to the numpy restatement (oracle/preprocess_ref.py) for arbitrary
+geometry, pixel_values within 1e-6 (the gate of test_preprocess_pil_matches_pillow_and_transformers_golden), the per-image path next to it, independence of the
+batch / the record chunking / the workspace's earlier contents, the row range of the horizontal pass, the refusals, and the consumers.  Every image is at most ~300
+pixels a side (two strips are wider, 8 and 9 rows high: the horizontal pass changes its path where a row's span outgrows the LDS)."""
+import ctypes as C
+import hashlib
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import preprocess_ref as P
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TV_MEAN, TV_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+CL_MEAN, CL_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
+STATS = {"timm": (TV_MEAN, TV_STD), "clip": (CL_MEAN, CL_STD), "torchvision": (CL_MEAN, CL_STD)}
+
+
+@pytest.fixture(scope="module")
+def L():
+    from geoguessr_ai_amd import _lib
+    _lib.require_gpu()
+    return _lib
+
+
+@pytest.fixture(scope="module")
+def fx():
+    """The fixture and, per image, the numpy restatement's pixel_values (computed once, never changed)."""
+    g = np.load(os.path.join(ROOT, "tests", "golden", "eval_batch_pil.npz"))
+    cases = []
+    for i in range(len(g["size"])):
+        pipe, size, pct, mode = str(g["pipeline"][i]), int(g["size"][i]), float(g["crop_pct"][i]), str(g["crop_mode"][i])
+        u8, pv = P.raw_image_pixel_values(g[f"src{i}"], pipe, size, STATS[pipe][0], STATS[pipe][1], pct, mode)
+        assert np.array_equal(u8, g[f"crop{i}"])
+        cases.append(dict(i=i, src=g[f"src{i}"], crop=g[f"crop{i}"], pv=pv, pipeline=pipe, size=size, crop_pct=pct, crop_mode=mode, geom=tuple(int(v) for v in g["geom"][i]),
+                          filter=int(g["filter"][i])))
+    for c in cases:
+        c["crop"].setflags(write=False); c["pv"].setflags(write=False)          # (the sources go through torch.from_numpy, which wants writable arrays)
+    return cases
+
+
+def eval_batch(L, srcs, geoms, Hc, Wc, flt, mul_rescale=0, mean=TV_MEAN, std=TV_STD, normalize=1, gap=0, lead=0, ws_fill=None, want_u8=True, extra_ws=0):
+    """One gg_eval_batch call through the ABI: images packed `lead` bytes into the buffer with `gap` bytes between them.  -> (pv (B,3,Hc,Wc), u8 (B,Hc,Wc,3)) numpy."""
+    B = len(srcs)
+    offsets, at = [], lead
+    for s in srcs:
+        offsets.append(at)
+        at += s.size + gap
+    host = np.full(at, 0xA5, np.uint8)
+    for s, o in zip(srcs, offsets):
+        host[o:o + s.size] = s.reshape(-1)
+    packed = torch.from_numpy(host).cuda()
+    offsets = np.array(offsets, np.int64)
+    heights, widths = np.array([s.shape[0] for s in srcs], np.int32), np.array([s.shape[1] for s in srcs], np.int32)
+    geom = np.ascontiguousarray(np.array(geoms, np.int32).reshape(B, 4))
+    dst = torch.empty(B, 3, Hc, Wc, device="cuda")
+    dst_u8 = torch.empty(B, Hc, Wc, 3, dtype=torch.uint8, device="cuda") if want_u8 else None
+    a = L.EvalArgs()
+    a.src, a.src_bytes = packed.data_ptr(), packed.numel()
+    a.offsets, a.heights, a.widths, a.geom = offsets.ctypes.data, heights.ctypes.data, widths.ctypes.data, geom.ctypes.data
+    a.B, a.Hc, a.Wc, a.filter, a.mul_rescale, a.normalize = B, Hc, Wc, flt, mul_rescale, normalize
+    a.mean, a.std = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    need = L.lib().gg_eval_workspace_bytes(C.byref(a))
+    assert need > 0, L.lib().gg_last_error()
+    ws = torch.full((need + extra_ws,), 0 if ws_fill is None else ws_fill, dtype=torch.uint8, device="cuda")
+    a.dst, a.dst_u8, a.workspace, a.workspace_bytes = dst.data_ptr(), dst_u8.data_ptr() if want_u8 else None, ws.data_ptr(), ws.numel()
+    L.check(L.lib().gg_eval_batch(C.byref(a), L.stream()), "gg_eval_batch")
+    torch.cuda.synchronize()
+    assert torch.equal(packed.cpu(), torch.from_numpy(host))
+    return dst.cpu().numpy(), dst_u8.cpu().numpy() if want_u8 else None
+
+
+# ------------------------------------------------------------------------------------------------- 1. the fixture, whole file in batches
+def test_fixture_in_batches_matches_pillow_bit_for_bit(L, fx):
+    """Every fixture image, none skipped.  (a) One gg_eval_batch call per (pipeline, size) through the ABI with the fixture's own geometry; (b) through
+    DeviceEvalTransform(..., return_u8=True), one call per (pipeline, size, crop_pct, crop mode) -- a transform has one crop setting.  uint8 crops bit-identical to
+    Pillow, pixel_values within 1e-6 of the numpy restatement."""
+    from geoguessr_ai_amd.training.preprocess import DeviceEvalTransform
+    seen_a, seen_b, worst = set(), set(), 0.0
+    for key in sorted({(c["pipeline"], c["size"]) for c in fx}):
+        grp = [c for c in fx if (c["pipeline"], c["size"]) == key]
+        pv, u8 = eval_batch(L, [c["src"] for c in grp], [c["geom"] for c in grp], key[1], key[1], grp[0]["filter"], int(key[0] == "clip"), *STATS[key[0]])
+        for k, c in enumerate(grp):
+            assert np.array_equal(u8[k], c["crop"]), ("abi", c["i"], int((u8[k] != c["crop"]).sum()))
+            err = float(np.abs(pv[k] - c["pv"]).max())
+            worst = max(worst, err)
+            assert err <= 1e-6, ("abi", c["i"], err)
+            seen_a.add(c["i"])
+    for key in sorted({(c["pipeline"], c["size"], c["crop_pct"], c["crop_mode"]) for c in fx}):
+        grp = [c for c in fx if (c["pipeline"], c["size"], c["crop_pct"], c["crop_mode"]) == key]
+        tfm = DeviceEvalTransform(key[1], *STATS[key[0]], pipeline=key[0], crop_pct=key[2], crop_mode=key[3])
+        pv, u8 = tfm([c["src"] for c in grp], return_u8=True)
+        assert pv.shape == (len(grp), 3, key[1], key[1]) and u8.shape == (len(grp), key[1], key[1], 3) and pv.is_cuda
+        pv, u8 = pv.cpu().numpy(), u8.cpu().numpy()
+        for k, c in enumerate(grp):
+            assert np.array_equal(u8[k], c["crop"]), ("transform", c["i"], int((u8[k] != c["crop"]).sum()))
+            err = float(np.abs(pv[k] - c["pv"]).max())
+            worst = max(worst, err)
+            assert err <= 1e-6, ("transform", c["i"], err)
+            seen_b.add(c["i"])
+    print(f"\n[eval fixture] 14 images, max |pixel_values - restatement| = {worst:.3e}")
+    assert seen_a == seen_b == set(range(14))
+
+
+# ------------------------------------------------------------------------------------------------- 2. the existing golden, batched
+def test_existing_golden_in_one_call_per_pipeline(L):
+    """tests/golden/preprocess_pil.npz (Pillow's and transformers' own outputs): every image that has a pipeline's key goes into ONE call for that pipeline -- all
+    seven for clip 224 and timm 224 at 0.95, the pairs of timm 512 squash and inference 336 together -- and is checked as the per-image test checks it."""
+    from geoguessr_ai_amd.training.preprocess import DeviceEvalTransform
+    g = np.load(os.path.join(ROOT, "tests", "golden", "preprocess_pil.npz"))
+    names = sorted({k.split(".")[0] for k in g.files})
+    imgs = {n: P.to_rgb(g[n + ".img"], "".join(chr(c) for c in g[n + ".mode"])) for n in names}
+    assert len(names) == 7
+    checked, sizes = 0, {}
+    for key, pipe, size, kw in (("clip", "clip", 224, {}), ("timm224", "timm", 224, dict(crop_pct=0.95)), ("timm512", "timm", 512, dict(crop_pct=1.0, crop_mode="squash")),
+                                ("inf336", "torchvision", 336, {}), ("timm384", "timm", 384, dict(crop_pct=1.0))):
+        grp = [n for n in names if any(f"{n}.{key}_{suf}" in g.files for suf in ("u8", "sha"))]
+        sizes[key] = len(grp)
+        if not grp:
+            continue
+        pvs, u8s = DeviceEvalTransform(size, *STATS[pipe], pipeline=pipe, **kw)([imgs[n] for n in grp], return_u8=True)
+        pvs, u8s = pvs.cpu().numpy(), u8s.cpu().numpy()
+        for k, n in enumerate(grp):
+            pv, u8 = pvs[k], u8s[k]
+            if f"{n}.{key}_u8" in g.files:
+                assert np.array_equal(u8, g[f"{n}.{key}_u8"]), (n, key, int((u8 != g[f"{n}.{key}_u8"]).sum()))
+            else:
+                assert hashlib.sha256(np.ascontiguousarray(u8).tobytes()).digest() == g[f"{n}.{key}_sha"].tobytes(), (n, key)
+            if f"{n}.{key}_pv" in g.files:
+                assert np.abs(pv - g[f"{n}.{key}_pv"]).max() <= 1e-6, (n, key)
+            elif f"{n}.{key}_pv_sum" in g.files:
+                cs = np.asarray([pv.astype(np.float64).sum(), np.abs(pv.astype(np.float64)).sum()])
+                assert np.abs(cs - g[f"{n}.{key}_pv_sum"]).max() <= 1e-6 * g[f"{n}.{key}_pv_sum"][1], (n, key)
+            checked += 1
+    assert checked == 19 and sizes["clip"] == 7 and sizes["timm224"] == 7 and sizes["timm512"] == 2 and sizes["inf336"] == 2, sizes
+
+
+# ------------------------------------------------------------------------------------------------- 3. against the per-image path
+def test_batched_keyword_matches_the_per_image_path(L, fx):
+    """images_to_pixel_values(batched=False) and (batched=True) on the same lists: uint8 equal, f32 within 1e-6; both against Pillow, so a difference names its side.
+    A host (N,3,H,W) tensor, a device tensor and a single image take the batch path too."""
+    from geoguessr_ai_amd.training.preprocess import images_to_pixel_values
+    old_bad, new_bad = [], []
+    for key in sorted({(c["pipeline"], c["size"], c["crop_pct"], c["crop_mode"]) for c in fx}):
+        grp = [c for c in fx if (c["pipeline"], c["size"], c["crop_pct"], c["crop_mode"]) == key]
+        kw = dict(crop_pct=key[2], pipeline=key[0], crop_mode=key[3], return_u8=True)
+        pv0, u0 = images_to_pixel_values([c["src"] for c in grp], key[1], *STATS[key[0]], "cuda", **kw)
+        pv1, u1 = images_to_pixel_values([c["src"] for c in grp], key[1], *STATS[key[0]], "cuda", batched=True, **kw)
+        for k, c in enumerate(grp):
+            if not np.array_equal(u0[k].cpu().numpy(), c["crop"]):
+                old_bad.append(c["i"])
+            if not np.array_equal(u1[k].cpu().numpy(), c["crop"]):
+                new_bad.append(c["i"])
+        assert not new_bad, f"the batch path differs from Pillow on fixture images {new_bad}"
+        assert not old_bad, f"the PER-IMAGE path (gg_preprocess_pil) differs from Pillow on fixture images {old_bad} where the batch path matches"
+        assert torch.equal(u0, u1), key
+        assert float((pv0 - pv1).abs().max()) <= 1e-6, key
+    c = fx[0]
+    kw = dict(crop_pct=c["crop_pct"], pipeline="timm", return_u8=True)
+    chw = torch.from_numpy(np.stack([c["src"], c["src"][::-1].copy()])).permute(0, 3, 1, 2).contiguous()
+    ref_pv, ref_u8 = images_to_pixel_values(chw, 32, TV_MEAN, TV_STD, "cuda", **kw)
+    for form in (chw, chw.cuda(), [c["src"], c["src"][::-1].copy()]):
+        pv, u8 = images_to_pixel_values(form, 32, TV_MEAN, TV_STD, "cuda", batched=True, **kw)
+        assert torch.equal(u8, ref_u8) and float((pv - ref_pv).abs().max()) <= 1e-6
+    one = images_to_pixel_values(c["src"], 32, TV_MEAN, TV_STD, "cuda", crop_pct=c["crop_pct"], batched=True)
+    assert one.shape == (1, 3, 32, 32) and torch.equal(one, pv[:1])
+    with pytest.raises(L.GgError, match="a 40x40 image resizes to 25x25, smaller than the 32x32 crop"):          # crop_pct > 1: the upstream transform pads
+        images_to_pixel_values(np.zeros((40, 40, 3), np.uint8), 32, TV_MEAN, TV_STD, "cuda", crop_pct=1.25, batched=True)
+
+
+# ------------------------------------------------------------------------------------------------- 4. batch independence and chunking
+def test_batch_of_23_is_independent_of_batch_chunks_and_workspace_contents(L, fx):
+    """B = 23 (more than one chunk of the table, which travels 16 images per launch) of the twelve 32 x 32 fixture geometries in shuffled order, packed with 1-byte
+    gaps behind a 1-byte lead (unaligned offsets), one filter for the call: every image's u8 and f32 are bit-identical to its own B = 1 call and the u8 to the numpy
+    restatement; the call into a workspace of 0xFF bytes and into one of 0x00 bytes gives the same bits."""
+    pool = [c for c in fx if c["size"] == 32]
+    order = np.random.default_rng(5).permutation(23) % len(pool)
+    assert len(pool) == 12 and len(set(order.tolist())) == 12
+    srcs, geoms = [pool[k]["src"] for k in order], [pool[k]["geom"] for k in order]
+    runs = [eval_batch(L, srcs, geoms, 32, 32, 3, gap=1, lead=1, ws_fill=fill) for fill in (0xFF, 0x00, 0xFF)]
+    for pv, u8 in runs[1:]:
+        assert np.array_equal(pv.view(np.uint32), runs[0][0].view(np.uint32)) and np.array_equal(u8, runs[0][1])
+    singles = {}
+    for k in sorted(set(order.tolist())):
+        c = pool[k]
+        singles[k] = eval_batch(L, [c["src"]], [c["geom"]], 32, 32, 3, ws_fill=0x47)
+        hr, wr, top, left = c["geom"]
+        assert np.array_equal(singles[k][1][0], P.pil_resize(c["src"], wr, hr, 3)[top:top + 32, left:left + 32]), c["i"]
+    for b, k in enumerate(order.tolist()):
+        assert np.array_equal(runs[0][1][b], singles[k][1][0]), (b, k)
+        assert np.array_equal(runs[0][0][b].view(np.uint32), singles[k][0][0].view(np.uint32)), (b, k)
+
+
+# ------------------------------------------------------------------------------------------------- 5. the row range of the horizontal pass
+def test_row_windows_first_interior_last_and_spans_beyond_the_lds(L):
+    """Arbitrary geometry through the ABI, the numpy restatement as the oracle, uint8 exact.  120 x 40 -> 60 x 20 with a 16 x 16 window at rows 22 (interior), 0 (the
+    first source rows) and 44 (the last); bilinear too.  Two strips whose row span is at / beyond what a workgroup stages in LDS (10 920 columns: one staged row per
+    workgroup; 12 000 columns: read from global memory), one with a vertical pass, one without.  A Hc != Wc window."""
+    g = np.random.default_rng(9)
+    img = g.integers(0, 256, (120, 40, 3), dtype=np.uint8)
+    img[30:60, 10:25] = 255
+    img[60:64] = 0
+    for flt in (3, 2):
+        full = P.pil_resize(img, 20, 60, flt)
+        tops = (22, 0, 44)
+        _, u8 = eval_batch(L, [img] * 3, [(60, 20, t, 2) for t in tops], 16, 16, flt, ws_fill=0xFF)
+        for k, t in enumerate(tops):
+            assert np.array_equal(u8[k], full[t:t + 16, 2:18]), (flt, t, int((u8[k] != full[t:t + 16, 2:18]).sum()))
+    _, u8 = eval_batch(L, [img], [(60, 20, 7, 1)], 40, 12, 3, ws_fill=0xFF)                 # Hc = 40, Wc = 12
+    assert np.array_equal(u8[0], P.pil_resize(img, 20, 60, 3)[7:47, 1:13])
+    for H, W, Hr, top, Hc in ((9, 10920, 6, 1, 4), (8, 12000, 8, 0, 8)):
+        strip = g.integers(0, 256, (H, W, 3), dtype=np.uint8)
+        strip[:, W // 3:W // 2] = 255
+        want = P.pil_resize(strip, 16, Hr, 3)[top:top + Hc]
+        pv, u8 = eval_batch(L, [strip], [(Hr, 16, top, 0)], Hc, 16, 3, normalize=0, ws_fill=0xFF)
+        assert np.array_equal(u8[0], want), (W, int((u8[0] != want).sum()))
+        assert np.array_equal(pv[0], (want.astype(np.float32) / np.float32(255)).transpose(2, 0, 1))      # normalize = 0: u8 / 255 alone
+
+
+# ------------------------------------------------------------------------------------------------- 6. refusals
+def test_refused_arguments_write_nothing(L, fx):
+    """Each refused argument set of include/gg_eval.h answers < 0 with its message before any launch: dst, dst_u8 and the workspace keep their sentinel."""
+    lib = L.lib()
+    grp = [c for c in fx if c["size"] == 32][:3]
+    srcs = [c["src"] for c in grp]
+    packed = torch.from_numpy(np.concatenate([s.reshape(-1) for s in srcs])).cuda()
+    sizes = [s.size for s in srcs]
+    dst = torch.full((3, 3, 32, 32), 7.25, device="cuda")
+    dst_u8 = torch.full((3, 32, 32, 3), 0x5A, dtype=torch.uint8, device="cuda")
+    ws = torch.full((1 << 20,), 0x33, dtype=torch.uint8, device="cuda")
+
+    def args(**kw):
+        t = dict(offsets=np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64), heights=np.array([s.shape[0] for s in srcs], np.int32),
+                 widths=np.array([s.shape[1] for s in srcs], np.int32), geom=np.ascontiguousarray(np.array([c["geom"] for c in grp], np.int32)))
+        for k in list(kw):
+            if k.startswith("edit_"):
+                kw.pop(k)(t)
+        a = L.EvalArgs()
+        a.src, a.src_bytes = packed.data_ptr(), packed.numel()
+        a.offsets, a.heights, a.widths, a.geom = (t[k].ctypes.data for k in ("offsets", "heights", "widths", "geom"))
+        a.B, a.Hc, a.Wc, a.filter, a.mul_rescale, a.normalize = 3, 32, 32, 3, 0, 1
+        a.mean, a.std = (C.c_float * 3)(*TV_MEAN), (C.c_float * 3)(*TV_STD)
+        a.dst, a.dst_u8, a.workspace, a.workspace_bytes = dst.data_ptr(), dst_u8.data_ptr(), ws.data_ptr(), ws.numel()
+        for k, v in kw.items():
+            setattr(a, k, v)
+        return a, t
+
+    a, keep = args()
+    need = lib.gg_eval_workspace_bytes(C.byref(a))
+    assert 0 < need <= ws.numel()
+
+    def wide(t):
+        t["heights"][0], t["widths"][0] = 1, sizes[0] // 3          # the first image read as one row of 1961 pixels ...
+        t["geom"][0] = (32, 32, 0, 0)
+
+    def too_wide(t):
+        t["heights"][0], t["widths"][0] = 1, 30000000               # ... and as 30 000 000 columns -> 32: ksize beyond the limit of gg_preprocess_pil
+        t["geom"][0] = (32, 32, 0, 0)
+    refused = [
+        (dict(src=None), b"null src / dst / workspace"), (dict(dst=None), b"null src / dst / workspace"), (dict(workspace=None), b"null src / dst / workspace"),
+        (dict(offsets=None), b"null offsets"), (dict(widths=None), b"null offsets"), (dict(geom=None), b"null geom"),
+        (dict(B=0), b"B=0"), (dict(B=-3), b"B=-3"), (dict(B=4097), b"B=4097"), (dict(Hc=0), b"Hc=0"), (dict(Wc=0), b"Wc=0"), (dict(Hc=2049), b"Hc=2049"),
+        (dict(filter=0), b"filter must be 2"), (dict(filter=1), b"filter must be 2"), (dict(std=(C.c_float * 3)(0.2, 0.0, 0.2)), b"zero std"),
+        (dict(src_bytes=packed.numel() - 1), b"image 2"), (dict(edit_=lambda t: t["offsets"].__setitem__(1, -4)), b"image 1"),
+        (dict(edit_=lambda t: t["geom"].__setitem__((2, 2), int(t["geom"][2, 0]) - 31)), b"image 2: the crop window"),
+        (dict(edit_=lambda t: t["geom"].__setitem__((0, 3), -1)), b"image 0: the crop window"), (dict(Hc=33), b"the crop window"),
+        (dict(edit_=lambda t: t["geom"].__setitem__((1, 1), 1 << 21)), b"image 1: resized size"),
+        (dict(edit_=too_wide, src_bytes=1 << 40), b"image 0: reduction factor too large"),
+        (dict(workspace_bytes=need - 1), b"the workspace has"),
+    ]
+    for kw, msg in refused:
+        a, keep = args(**kw)
+        rc = lib.gg_eval_batch(C.byref(a), L.stream())
+        assert rc < 0 and msg in lib.gg_last_error(), (msg, rc, lib.gg_last_error())
+    assert lib.gg_eval_batch(None, L.stream()) < 0 and b"null args" in lib.gg_last_error()
+    torch.cuda.synchronize()
+    assert bool((dst == 7.25).all()) and bool((dst_u8 == 0x5A).all()) and bool((ws == 0x33).all())
+    a, keep = args(edit_=wide)                                        # the sentinel check is not vacuous: an accepted call does write
+    L.check(lib.gg_eval_batch(C.byref(a), L.stream()), "gg_eval_batch")
+    torch.cuda.synchronize()
+    assert not bool((dst == 7.25).any()) and not bool((dst_u8[0] == 0x5A).all())
+
+
+# ------------------------------------------------------------------------------------------------- 7. consumers
+def _raw3():
+    g = np.random.default_rng(21)
+    return [g.integers(0, 256, s + (3,), dtype=np.uint8) for s in ((40, 61), (75, 50), (33, 33))]
+
+
+def test_tinyvit_embedder_batch_transform(L):
+    """TinyViTEmbedding(batch_transform=True) at tiny_vit_5m dims and the smallest size the model accepts (32), 3 raw images of different sizes: the embedding
+    equals (torch.equal) the embedder fed the transform's own pixel_values; the four panorama views go through one transform call."""
+    import warnings
+    from geoguessr_ai_amd.pretrain.tinyvit_embedder import TinyViTEmbedding
+    from geoguessr_ai_amd.training.preprocess import DeviceEvalTransform
+    torch.manual_seed(0)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        emb = TinyViTEmbedding(model_name="tiny_vit_5m_224", device="cuda", load_checkpoint=False, panorama=True, img_size=32, batch_transform=True)
+    raw = _raw3()
+    tfm = DeviceEvalTransform(32, TV_MEAN, TV_STD, "timm", 0.95)
+    pv = tfm(raw)
+    a, b = emb(raw), emb(pv)
+    assert a.shape == (3, 320) and torch.isfinite(a).all() and torch.equal(a, b)
+    calls = []
+    inner = emb._eval_transform()
+    emb._transform = lambda images, **kw: calls.append(len(images)) or inner(images, **kw)
+    views = [raw[0], raw[1], raw[2], raw[0][::-1].copy()]
+    p = emb(views[0], image_2=views[1], image_3=views[2], image_4=views[3])
+    assert calls == [4] and p.shape == (1, 4, 320)
+    q = torch.stack([emb(tfm(v)) for v in views], dim=1)
+    assert torch.equal(p, q)
+
+
+def test_clip_embedder_batch_transform(L):
+    """CLIPEmbedding(batch_transform=True) on the tiny CLIP configuration (3 layers of B/32), 3 raw images of different sizes."""
+    from geoguessr_ai_amd.pretrain.clip_embedder import CLIPEmbedding, clip_preprocess
+    from geoguessr_ai_amd.training.preprocess import DeviceEvalTransform
+    emb = CLIPEmbedding("openai/clip-vit-base-patch32", device="cuda", precision="fp32", num_layers=3, batch_transform=True)
+    g = np.random.default_rng(22)
+    raw = [g.integers(0, 256, s + (3,), dtype=np.uint8) for s in ((240, 301), (275, 250), (224, 224))]
+    pv = DeviceEvalTransform(224, CL_MEAN, CL_STD, "clip")(raw)
+    a, b = emb(raw), emb(pv)
+    assert a.shape == (3, 768) and torch.isfinite(a).all() and torch.equal(a, b)
+    assert float((pv - clip_preprocess(raw, 224, "cuda")).abs().max()) <= 1e-6          # the per-image processor path next to it
+
+
+def test_evaluate_on_eval_transformed_batches(L):
+    """evaluate(model, eval_transformed(raw, tfm)) equals evaluate on the pre-transformed batches; extract_embeddings likewise."""
+    from geoguessr_ai_amd import finetune_tinyvit as FT
+    from geoguessr_ai_amd.models.tinyvit_classifier import TinyViTClassifier
+    from geoguessr_ai_amd.training.preprocess import DeviceEvalTransform
+    model = TinyViTClassifier("tiny_vit_5m_224", num_classes=3, precision="fp32_split", img_size=32, seed=1).cuda().eval()
+    tfm = DeviceEvalTransform(32, TV_MEAN, TV_STD, "timm", 0.95)
+    raw = _raw3()
+    raw_batches = [{"images": raw[:2], "labels": [0, 2]}, {"images": torch.from_numpy(raw[2]).permute(2, 0, 1), "labels": torch.tensor([1])}]
+    pre = [{"pixel_values": tfm(b["images"]), "labels": torch.as_tensor(b["labels"]).cuda()} for b in raw_batches]
+    seen = list(FT.eval_transformed(raw_batches, tfm))
+    assert [set(b) for b in seen] == [{"pixel_values", "labels"}] * 2 and all(torch.equal(s["pixel_values"], p["pixel_values"]) for s, p in zip(seen, pre))
+    assert seen[0]["labels"].is_cuda and seen[0]["labels"].dtype == torch.int64
+    assert FT.evaluate(model, FT.eval_transformed(raw_batches, tfm)) == FT.evaluate(model, pre)
+    assert np.array_equal(FT.extract_embeddings(model, FT.eval_transformed(raw_batches, tfm)), FT.extract_embeddings(model, pre))
