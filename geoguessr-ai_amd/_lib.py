@@ -124,6 +124,11 @@ class EvalArgs(C.Structure):             # GgEvalArgs
                 ("std", C.c_float * 3), ("dst", C.c_void_p), ("dst_u8", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class JpegInfo(C.Structure):             # GgJpegInfo (include/gg_jpeg.h): what the host-side plan found out about one file
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("components", C.c_int32), ("hs", C.c_int32), ("vs", C.c_int32), ("segments", C.c_int32),
+                ("refusal", C.c_int32), ("reserved", C.c_int32), ("out_offset", C.c_int64), ("stream_offset", C.c_int64)]
+
+
 STAGE_DONE_FN = C.CFUNCTYPE(None, C.c_int, C.c_void_p)      # GgStageDoneFn (host callback of gg_tinyvit_backward)
 
 # every exported symbol of include/gg.h: name -> (restype, argtypes)
@@ -375,6 +380,23 @@ EVAL_SIGNATURES = {
 }
 EVAL_SYMBOLS = list(EVAL_SIGNATURES)
 
+# every exported symbol of include/gg_jpeg.h (baseline JPEG decoding of whole batches: host-side plan, entropy decode, inverse DCT, upsample + colour + pack), bound from the same libgg.so
+JPEG_MAX_B = 4096                         # GG_JPEG_MAX_B
+JPEG_SIGNATURES = {
+    "gg_jpeg_refusal_name": (C.c_char_p, [_I]),
+    "gg_jpeg_plan_create": (_I, [_P, _P, _I, C.POINTER(_P)]),
+    "gg_jpeg_plan_destroy": (_I, [_P]),
+    "gg_jpeg_plan_info": (_I, [_P, _I, C.POINTER(JpegInfo)]),
+    "gg_jpeg_plan_first_refused": (_I, [_P]),
+    "gg_jpeg_plan_stream_bytes": (_L, [_P]),
+    "gg_jpeg_plan_table_bytes": (_L, [_P]),
+    "gg_jpeg_plan_output_bytes": (_L, [_P]),
+    "gg_jpeg_plan_fill": (_I, [_P, _P, _P]),
+    "gg_jpeg_workspace_bytes": (_L, [_P]),
+    "gg_jpeg_decode": (_I, [_P, _P, _L, _P, _L, _P, _P, _L, _P]),
+}
+JPEG_SYMBOLS = list(JPEG_SIGNATURES)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -383,7 +405,7 @@ def lib() -> C.CDLL:
             raise GgError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the library lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -437,6 +459,7 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(root), "include", "gg_aug.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_fp8.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_eval.h"))
+    files.append(os.path.join(os.path.dirname(root), "include", "gg_jpeg.h"))
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

@@ -200,7 +200,8 @@ class DeviceTrainTransform:
     """``create_transform(is_training=True, auto_augment=..., interpolation=...)`` for batches, on the device.  ``__call__(images, params=None)``: PIL images, (H, W, 3)
     uint8 arrays, a list of those or an (N,3,H,W) uint8 tensor -> (N,3,S,S) float32 ``pixel_values`` on ``device`` (with ``return_u8=True`` also the (N,S,S,3) uint8
     batch after the last op).  ``params``: a record table to replay (``sample_params``' layout); otherwise one is drawn from the transform's own generator and kept in
-    ``.last_params``.  The workspace is the transform's own and is reused from call to call (it grows when a batch needs more)."""
+    ``.last_params``.  The workspace is the transform's own and is reused from call to call (it grows when a batch needs more).  ``images`` may also be a list in
+    which every item is a JPEG file as bytes (decoded on the device by a ``training.jpeg.DeviceJpegDecoder`` the transform owns) or that decoder's ``PackedImages``."""
 
     def __init__(self, img_size: int = 224, mean: Sequence[float] = TINYVIT_MEAN, std: Sequence[float] = TINYVIT_STD, auto_augment: str = "rand-m9-mstd0.5-inc1",
                  interpolation: str = "bicubic", seed: int = 0, device="cuda"):
@@ -212,6 +213,7 @@ class DeviceTrainTransform:
         self.generator = np.random.default_rng(seed)
         self.last_params: Optional[np.ndarray] = None
         self._workspace: Optional[torch.Tensor] = None
+        self._decoder = None                              # training.jpeg.DeviceJpegDecoder, made when file bytes first arrive
 
     def _filter(self) -> int:
         if self.interpolation == "random":
@@ -220,20 +222,31 @@ class DeviceTrainTransform:
 
     def __call__(self, images, params: Optional[np.ndarray] = None, return_u8: bool = False):
         _lib.require_gpu()
-        hwc = _as_hwc_list(images)
-        sizes = [(int(im.shape[0]), int(im.shape[1])) for im in hwc]
+        from ..training.jpeg import DeviceJpegDecoder, PackedImages, is_file_bytes, is_file_bytes_list
+        if is_file_bytes(images):
+            images = [images]
+        if is_file_bytes_list(images):                    # JPEG files as bytes: decoded on the device, consumed where the decoded batch lies
+            if self._decoder is None:
+                self._decoder = DeviceJpegDecoder(self.device)
+            images = self._decoder.decode(images)
+        decoded = images if isinstance(images, PackedImages) else None
+        hwc = [] if decoded is not None else _as_hwc_list(images)
+        sizes = [(int(h), int(w)) for h, w in decoded.sizes] if decoded is not None else [(int(im.shape[0]), int(im.shape[1])) for im in hwc]
         if params is None:
             params = sample_params(sizes, self.img_size, self.auto_augment, self.generator, self.mean, self.interpolation)
         params = np.ascontiguousarray(params, RECORD_DTYPE)
-        if len(params) != len(hwc):
-            raise GgError(f"DeviceTrainTransform: {len(params)} records for {len(hwc)} images")
+        if len(params) != len(sizes):
+            raise GgError(f"DeviceTrainTransform: {len(params)} records for {len(sizes)} images")
         self.last_params = params.copy()
-        nbytes = [3 * h * w for h, w in sizes]
-        offsets = np.concatenate([[0], np.cumsum([(n + 255) // 256 * 256 for n in nbytes])]).astype(np.int64)
-        packed = torch.empty(int(offsets[-1]), dtype=torch.uint8, device=self.device)
-        for im, off, n in zip(hwc, offsets, nbytes):
-            packed[int(off):int(off) + n].copy_(im.reshape(-1), non_blocking=True)
-        B, S = len(hwc), self.img_size
+        if decoded is not None:
+            packed, offsets = decoded.packed, np.ascontiguousarray(decoded.offsets, np.int64)
+        else:
+            nbytes = [3 * h * w for h, w in sizes]
+            offsets = np.concatenate([[0], np.cumsum([(n + 255) // 256 * 256 for n in nbytes])]).astype(np.int64)
+            packed = torch.empty(int(offsets[-1]), dtype=torch.uint8, device=self.device)
+            for im, off, n in zip(hwc, offsets, nbytes):
+                packed[int(off):int(off) + n].copy_(im.reshape(-1), non_blocking=True)
+        B, S = len(sizes), self.img_size
         dst = torch.empty(B, 3, S, S, dtype=torch.float32, device=self.device)
         dst_u8 = torch.empty(B, S, S, 3, dtype=torch.uint8, device=self.device) if return_u8 else None
         heights, widths = np.array([s[0] for s in sizes], np.int32), np.array([s[1] for s in sizes], np.int32)

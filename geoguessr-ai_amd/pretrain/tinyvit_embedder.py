@@ -80,6 +80,12 @@ def _host_raw_list(v):
 def _transform_views(views, transform):
     """The panorama views' raw host images through ONE transform call: they are joined into one list, transformed together and handed back as per-view
     ``pixel_values``."""
+    from ..training.jpeg import is_file_bytes_list
+    if all(is_file_bytes_list(v) for v in views):         # JPEG files as bytes: one device decode and one transform call for all the views
+        pv, out, at = transform([f for v in views for f in v]), [], 0
+        for v in views:
+            out.append(pv[at:at + len(v)]); at += len(v)
+        return out
     lists = [_host_raw_list(v) for v in views]
     flat = [im.numpy() for l in lists if l is not None for im in l]
     if not flat:

@@ -1,0 +1,170 @@
+"""The device JPEG decoder (gg_jpeg_decode, include/gg_jpeg.h) next to the host path it replaces, PIL.Image.open(...).convert("RGB"): batches of 640 x 640 4:2:0
+quality-90 files, B = 256 and B = 1024, each without restart markers (what real camera files look like) and with one restart interval per MCU row.
+
+Prints one JSON line per row and appends them to --out; per (B, restart) configuration:
+  pillow_1_thread    ms per image, decoded one after the other on one core (at most --one-thread-files of the batch)
+  pillow_16_threads  ms per batch in a pool of 16 threads (Pillow releases the GIL while it decodes): the only way before this decoder, the thing being replaced
+  device             wall-clock ms per DeviceJpegDecoder.decode(files) call, synchronised: the host plan, filling the pinned buffer, the upload, the four kernels and the
+                     status read-back; images / s, the ratio to pillow_16_threads, and whether every decoded byte equals Pillow's.  THE GATE (B = 1024 without
+                     restart markers): device takes no longer than pillow_16_threads (exit status 1 otherwise)
+  device_stages      one profiled call (gg_prof_*: HIP events around every stage, in launch order): entropy, inverse DCT, status + upsample + colour + pack
+  end_to_end         file bytes -> TinyViTEmbedding('tiny_vit_5m_224', batch_transform=True) embeddings: host decode (the 16-thread pool) against device decode
+Timing: the variants alternate within one process after --warmup calls, --repeats times; every row reports the median and the spread (min, max).
+    python tools/bench_jpeg_decode.py [--batches 256 1024 --src 640 --quality 90] [--out profiles/jpeg_decode_bench.jsonl]
+The files: --unique seeded synthetic images (smooth structure plus noise, tools/bench_augment.py's generator), encoded once and repeated to fill the batch; every
+copy is decoded on its own."""
+import argparse
+import ctypes as C
+import io
+import json
+import os
+import statistics
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+def spread(v):
+    return dict(ms=round(statistics.median(v), 4), ms_min=round(min(v), 4), ms_max=round(max(v), 4), repeats=len(v))
+
+
+def wall(fn):
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t) * 1e3
+
+
+def pil_decode(f):
+    from PIL import Image
+    return np.asarray(Image.open(io.BytesIO(f)).convert("RGB"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, nargs="+", default=[256, 1024])
+    ap.add_argument("--src", type=int, default=640)
+    ap.add_argument("--quality", type=int, default=90)
+    ap.add_argument("--unique", type=int, default=64)
+    ap.add_argument("--one-thread-files", type=int, default=128)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--e2e-repeats", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import warnings
+    from PIL import Image
+    from bench_augment import make_sources
+    from geoguessr_ai_amd import _lib as L
+    from geoguessr_ai_amd.pretrain.tinyvit_embedder import TinyViTEmbedding
+    from geoguessr_ai_amd.training.jpeg import DeviceJpegDecoder
+    L.require_gpu()
+    lib = L.lib()
+    H = a.src
+    common = dict(tool="bench_jpeg_decode", src=f"{H}x{H}", quality=a.quality, subsampling="4:2:0", unique=a.unique, seed=a.seed, threads=a.threads,
+                  device=torch.cuda.get_device_name(0), source_hash=L.source_hash()[:12])
+    src = make_sources(a.unique, H, H, a.seed).cpu().numpy()
+    encoded = {}
+    for restart in (False, True):
+        out = []
+        for im in src:
+            buf = io.BytesIO()
+            Image.fromarray(im).save(buf, "JPEG", quality=a.quality, subsampling="4:2:0", **({"restart_marker_rows": 1} if restart else {}))
+            out.append(buf.getvalue())
+        encoded[restart] = out
+    pool = ThreadPoolExecutor(a.threads)
+    dec = DeviceJpegDecoder("cuda")
+    torch.manual_seed(0)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        emb = TinyViTEmbedding(model_name="tiny_vit_5m_224", device="cuda", batch_transform=True)
+    rows, gate_ok = [], True
+    for B in a.batches:
+        for restart in (False, True):
+            files = [encoded[restart][b % a.unique] for b in range(B)]
+            cfg = dict(common, batch=B, restart="one interval per MCU row" if restart else "none", file_kib=round(sum(len(f) for f in files) / B / 1024, 1))
+            ref = [pil_decode(f) for f in encoded[restart]]
+            p = dec.decode(files)
+            got = dec.unpack(p)
+            identical = all(np.array_equal(got[b].cpu().numpy(), ref[b % a.unique]) for b in range(B))
+            del got, p
+            one = files[:min(B, a.one_thread_files)]
+
+            def host16():
+                return list(pool.map(pil_decode, files))
+
+            def device():
+                return dec.decode(files)
+            for _ in range(a.warmup):
+                host16(); device()
+            t1, t16, td = [], [], []
+            for _ in range(a.repeats):                                    # the variants alternate: a drift of the machine reaches all of them
+                t = time.perf_counter()
+                for f in one:
+                    pil_decode(f)
+                t1.append((time.perf_counter() - t) * 1e3 / len(one))
+                t = time.perf_counter()
+                host16()
+                t16.append((time.perf_counter() - t) * 1e3)
+                td.append(wall(device))
+            s1, s16, sd = spread(t1), spread(t16), spread(td)
+            rows.append(dict(cfg, row="pillow_1_thread", **s1, unit="ms per image", files=len(one), images_per_s=round(1e3 / s1["ms"], 1)))
+            rows.append(dict(cfg, row="pillow_16_threads", **s16, unit="ms per batch", images_per_s=round(B / s16["ms"] * 1e3, 1)))
+            gated = B == 1024 and not restart
+            ok = bool(sd["ms"] <= s16["ms"])
+            rows.append(dict(cfg, row="device", **sd, unit="ms per batch, wall clock, synchronised", images_per_s=round(B / sd["ms"] * 1e3, 1),
+                             pillow_16_threads_over_device=round(s16["ms"] / sd["ms"], 2), byte_identical_to_pillow=identical, gated=gated, device_no_slower=ok))
+            gate_ok = gate_ok and identical and (ok or not gated)
+            # one profiled call: a scope per stage, in launch order
+            names = ["entropy", "idct", "status_upsample_colour_pack"]
+            lib.gg_prof_reset()
+            lib.gg_prof_enable(1)
+            device()
+            torch.cuda.synchronize()
+            lib.gg_prof_enable(0)
+            assert lib.gg_prof_count() == len(names), lib.gg_prof_count()
+            stages, ms = {}, C.c_double()
+            for i, n in enumerate(names):
+                L.check(lib.gg_prof_record(i, None, C.byref(ms), None, None), "gg_prof_record")
+                stages[n] = round(ms.value, 4)
+            lib.gg_prof_reset()
+            rows.append(dict(cfg, row="device_stages", stage_ms=stages, stage_sum_ms=round(sum(stages.values()), 4), dominant_stage=max(stages, key=stages.get)))
+
+            # end to end: file bytes -> embeddings
+            def e2e_host():
+                return emb(host16())
+
+            def e2e_device():
+                return emb(files)
+            x, y = e2e_host(), e2e_device()
+            same = bool(torch.equal(x, y))
+            th, tdv = [], []
+            for _ in range(a.e2e_repeats):
+                th.append(wall(e2e_host)); tdv.append(wall(e2e_device))
+            rows.append(dict(cfg, row="end_to_end", model="tiny_vit_5m_224", host_decode=spread(th), device_decode=spread(tdv),
+                             speedup=round(statistics.median(th) / statistics.median(tdv), 2), embeddings_identical=same))
+            del x, y
+    for r in rows:
+        print(json.dumps(r))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+    if not gate_ok:
+        print("GATE FAILED: the device decode is slower than the 16-thread Pillow pool at B = 1024 without restart markers, or its bytes differ", file=sys.stderr)
+        sys.exit(1)
+
+
+if __name__ == "__main__":
+    main()
