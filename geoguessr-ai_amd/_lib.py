@@ -397,6 +397,17 @@ JPEG_SIGNATURES = {
 }
 JPEG_SYMBOLS = list(JPEG_SIGNATURES)
 
+# every exported symbol of include/gg_jscan.h (the JPEG decoder's opt-in mode with many lanes inside one scan: a plan with a sub-segment table, speculate / resolve / write / DC passes), bound from the same libgg.so
+JSCAN_MIN_SPLIT, JSCAN_MAX_SPLIT = 8, 1 << 20        # GG_JSCAN_MIN_SPLIT, GG_JSCAN_MAX_SPLIT
+JSCAN_SIGNATURES = {
+    "gg_jscan_plan_create": (_I, [_P, _P, _I, _I, C.POINTER(_P)]),
+    "gg_jscan_plan_subsegments": (_I, [_P, _I]),
+    "gg_jscan_plan_total_subsegments": (_L, [_P]),
+    "gg_jscan_workspace_bytes": (_L, [_P]),
+    "gg_jscan_decode": (_I, [_P, _P, _L, _P, _L, _P, _P, _P, _L, _P]),
+}
+JSCAN_SYMBOLS = list(JSCAN_SIGNATURES)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -405,7 +416,7 @@ def lib() -> C.CDLL:
             raise GgError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JSCAN_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the library lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -460,6 +471,7 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(root), "include", "gg_fp8.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_eval.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_jpeg.h"))
+    files.append(os.path.join(os.path.dirname(root), "include", "gg_jscan.h"))
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

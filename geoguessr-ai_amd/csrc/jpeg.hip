@@ -8,9 +8,13 @@
 //   jpeg_status_kernel    status[b] = the worst status of image b's segments
 //   jpeg_pack_kernel      fancy upsampling over the components' real downsampled sizes, Y'CbCr -> RGB, four pixels = three dword stores per lane; zeros for a failed image
 // Everything is integer arithmetic: no layout choice here can change a byte of the result.
+// The opt-in mode of include/gg_jscan.h (a plan with a sub-segment table; gg_jscan_decode) puts four passes in the place of jpeg_entropy_kernel for segments that are
+// long enough to be cut -- jscan_speculate_kernel, jscan_resolve_kernel, jscan_write_kernel, jscan_dc_prefix_kernel + jscan_dc_apply_kernel: their lanes run the
+// jscan_* functions of jpeg_entropy.h -- and keeps the other three kernels.
 #include "common.h"
 #include "../../include/gg.h"
 #include "../../include/gg_jpeg.h"
+#include "../../include/gg_jscan.h"
 #include "jpeg_entropy.h"
 #include <string.h>
 #include <algorithm>
@@ -222,6 +226,146 @@ __global__ __launch_bounds__(256) void jpeg_pack_kernel(const JpegImgDev* __rest
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- kernels: many lanes inside one segment
+// (include/gg_jscan.h; the lanes' statements are jpeg_entropy.h's jscan_* functions).  A segment of one sub-segment is decoded by its write lane alone, with
+// jpeg_decode_segment: the speculate, resolve and DC lanes of such a segment return at once.
+static_assert(sizeof(JscanSub) == 48 && sizeof(JscanRec) == 32 && sizeof(JscanOut) == 16, "table layout");
+static_assert(JSCAN_MIN_SPLIT == GG_JSCAN_MIN_SPLIT && JSCAN_MAX_SPLIT == GG_JSCAN_MAX_SPLIT, "split range");
+
+__device__ __forceinline__ JscanSeg jscan_seg(const uint8_t* stream, const JpegImgDev& d, const JpegSegDev& sg, const uint32_t* tabs) {
+    JscanSeg g;
+    g.data = stream + sg.begin; g.nbytes = sg.end - sg.begin; g.nblocks = (int64_t)sg.mcus * d.bpm;
+    g.bpm = d.bpm; g.b0 = d.hs * d.vs; g.b01 = g.b0 + (d.ncomp == 3 ? 1 : 0); g.pad = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { g.dc[c] = tabs + d.dc[c] * JPEG_HUFF_WORDS; g.ac[c] = tabs + d.ac[c] * JPEG_HUFF_WORDS; }
+    return g;
+}
+__device__ __forceinline__ int16_t* jscan_coef(int16_t* coef, const JpegImgDev& d, const JpegSegDev& sg) { return coef + (d.coef_off >> 1) + (int64_t)sg.mcu0 * d.bpm * 64; }
+
+// lane L = sub-segment L / JSCAN_PHASES, phase L % JSCAN_PHASES
+template <bool LDS>
+__global__ __launch_bounds__(64) void jscan_speculate_kernel(const uint8_t* __restrict__ stream, const JpegImgDev* __restrict__ imgs, const JpegSegDev* __restrict__ segs,
+                                                             const JscanSub* __restrict__ subs, const uint32_t* __restrict__ huff, int nhuff, int64_t total, int lanes,
+                                                             JscanRec* __restrict__ recs) {
+    extern __shared__ uint32_t jpeg_lds[];
+    const uint32_t* tabs = huff;
+    if (LDS) {
+        for (int i = threadIdx.x; i < nhuff * JPEG_HUFF_WORDS; i += 64) jpeg_lds[i] = huff[i];
+        __syncthreads();
+        tabs = jpeg_lds;
+    }
+    if ((int)threadIdx.x >= lanes) return;
+    const int64_t L = (int64_t)blockIdx.x * lanes + threadIdx.x;
+    if (L >= total) return;
+    const int64_t G = L / JSCAN_PHASES;
+    const int ph = (int)(L - G * JSCAN_PHASES);
+    const JscanSub sub = subs[G];
+    if (sub.idx + 1 >= sub.nsub || (sub.idx == 0 && ph > 0)) return;
+    const JpegSegDev sg = segs[sub.seg];
+    const JpegImgDev& d = imgs[sg.img];
+    if (ph >= d.bpm) return;
+    const JscanSeg g = jscan_seg(stream, d, sg, tabs);
+    JscanRec R;
+    jscan_speculate(g, subs + (G - sub.idx), sub.idx, ph, R);
+    recs[L] = R;
+}
+
+// one lane per segment; the tables are read through the cache: the slow path is the exception
+__global__ __launch_bounds__(64) void jscan_resolve_kernel(const uint8_t* __restrict__ stream, const JpegImgDev* __restrict__ imgs, const JpegSegDev* __restrict__ segs,
+                                                           const int32_t* __restrict__ seg_sub0, const JscanSub* __restrict__ subs, const uint32_t* __restrict__ huff,
+                                                           int nseg, int lanes, const JscanRec* __restrict__ recs, JscanOut* __restrict__ outs,
+                                                           int32_t* __restrict__ seg_status, int32_t* __restrict__ seg_slow) {
+    if ((int)threadIdx.x >= lanes) return;
+    const int s = blockIdx.x * lanes + threadIdx.x;
+    if (s >= nseg) return;
+    const int64_t G0 = seg_sub0[s];
+    if (subs[G0].nsub == 1) { seg_slow[s] = 0; return; }                    // its write lane decodes it and reports its status
+    const JpegSegDev sg = segs[s];
+    const JscanSeg g = jscan_seg(stream, imgs[sg.img], sg, huff);
+    int32_t slow = 0;
+    seg_status[s] = jscan_resolve(g, subs + G0, recs + G0 * JSCAN_PHASES, outs + G0, &slow);
+    seg_slow[s] = slow;
+}
+
+// one lane per sub-segment
+template <bool LDS>
+__global__ __launch_bounds__(64) void jscan_write_kernel(const uint8_t* __restrict__ stream, const JpegImgDev* __restrict__ imgs, const JpegSegDev* __restrict__ segs,
+                                                         const JscanSub* __restrict__ subs, const uint32_t* __restrict__ huff, int nhuff, int64_t nsub, int lanes,
+                                                         const JscanOut* __restrict__ outs, int16_t* __restrict__ coef, int32_t* __restrict__ sums,
+                                                         int32_t* __restrict__ seg_status) {
+    extern __shared__ uint32_t jpeg_lds[];
+    const uint32_t* tabs = huff;
+    if (LDS) {
+        for (int i = threadIdx.x; i < nhuff * JPEG_HUFF_WORDS; i += 64) jpeg_lds[i] = huff[i];
+        __syncthreads();
+        tabs = jpeg_lds;
+    }
+    if ((int)threadIdx.x >= lanes) return;
+    const int64_t G = (int64_t)blockIdx.x * lanes + threadIdx.x;
+    if (G >= nsub) return;
+    const JscanSub sub = subs[G];
+    const JpegSegDev sg = segs[sub.seg];
+    const JpegImgDev& d = imgs[sg.img];
+    if (sub.nsub == 1) {                                                    // the whole segment: the lane of jpeg_entropy_kernel
+        JpegSegJob job;
+        job.data = stream + sg.begin;
+        job.nbytes = sg.end - sg.begin;
+        job.mcus = sg.mcus;
+        job.ncomp = d.ncomp;
+        job.blocks[0] = d.hs * d.vs; job.blocks[1] = job.blocks[2] = d.ncomp == 3 ? 1 : 0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { job.dc[c] = tabs + d.dc[c] * JPEG_HUFF_WORDS; job.ac[c] = tabs + d.ac[c] * JPEG_HUFF_WORDS; }
+        job.coef = jscan_coef(coef, d, sg);
+        seg_status[sub.seg] = jpeg_decode_segment(job);
+        return;
+    }
+    const JscanOut o = outs[G];
+    if (o.skip) return;
+    const JscanSeg g = jscan_seg(stream, d, sg, tabs);
+    int32_t s3[3];
+    jscan_write(g, subs + (G - sub.idx), sub.idx, o, jscan_coef(coef, d, sg), s3);
+    sums[4 * G] = s3[0]; sums[4 * G + 1] = s3[1]; sums[4 * G + 2] = s3[2];
+}
+
+__global__ __launch_bounds__(64) void jscan_dc_prefix_kernel(const int32_t* __restrict__ seg_sub0, const JscanSub* __restrict__ subs, int nseg, int lanes,
+                                                             const JscanOut* __restrict__ outs, int32_t* __restrict__ sums) {
+    if ((int)threadIdx.x >= lanes) return;
+    const int s = blockIdx.x * lanes + threadIdx.x;
+    if (s >= nseg) return;
+    const int64_t G0 = seg_sub0[s];
+    const int n = subs[G0].nsub;
+    if (n == 1) return;
+    jscan_dc_prefix(outs + G0, n, sums + 4 * G0);
+}
+__global__ __launch_bounds__(64) void jscan_dc_apply_kernel(const JpegImgDev* __restrict__ imgs, const JpegSegDev* __restrict__ segs, const JscanSub* __restrict__ subs,
+                                                            int64_t nsub, int lanes, const JscanOut* __restrict__ outs, const int32_t* __restrict__ sums,
+                                                            int16_t* __restrict__ coef) {
+    if ((int)threadIdx.x >= lanes) return;
+    const int64_t G = (int64_t)blockIdx.x * lanes + threadIdx.x;
+    if (G >= nsub) return;
+    const JscanSub sub = subs[G];
+    if (sub.nsub == 1) return;
+    const JscanOut o = outs[G];
+    if (o.skip) return;
+    const JpegSegDev sg = segs[sub.seg];
+    const JpegImgDev& d = imgs[sg.img];
+    JscanSeg g;                                                             // the block layout is all this pass reads
+    g.data = nullptr; g.nbytes = 0; g.nblocks = (int64_t)sg.mcus * d.bpm;
+    g.bpm = d.bpm; g.b0 = d.hs * d.vs; g.b01 = g.b0 + (d.ncomp == 3 ? 1 : 0); g.pad = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) g.dc[c] = g.ac[c] = nullptr;
+    jscan_dc_apply(g, o, sums + 4 * G, jscan_coef(coef, d, sg));
+}
+__global__ __launch_bounds__(64) void jscan_slow_kernel(const JpegImgDev* __restrict__ imgs, const int32_t* __restrict__ seg_slow, int32_t* __restrict__ slow) {
+    const int b = blockIdx.x;
+    const int seg0 = imgs[b].seg0, nseg = imgs[b].nseg;
+    int n = 0;
+    for (int i = threadIdx.x; i < nseg; i += 64) n += seg_slow[seg0 + i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+    if (threadIdx.x == 0) slow[b] = n;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host: parsing
 static const char* const JPEG_REFUSAL_NAMES[GG_JPEG_NUM_REFUSALS] = {
     "ok", "not a JPEG (no SOI)", "progressive (SOF2)", "unsupported SOF (lossless or hierarchical)", "arithmetic coding", "sample precision is not 8 bits",
@@ -391,11 +535,18 @@ struct GgJpegPlan {
     int64_t stream_bytes = 0, out_bytes = 0;
     int64_t ws_status = 0, ws_coef = 0, ws_planes = 0, ws_total = 0;        // regions of the workspace
     int64_t max_blocks = 1, max_pixels = 1, coef_bytes = 0, plane_bytes = 0, file_bytes = 0;
+    // gg_jscan_plan_create only (split > 0): the sub-segment table behind the Huffman tables, and the lanes' regions behind the workspace of gg_jpeg_decode
+    int split = 0;
+    int64_t nsub = 0, segsub_off = 0, sub_off = 0;
+    std::vector<int32_t> img_subs;
+    int64_t ws_slow = 0, ws_recs = 0, ws_outs = 0, ws_sums = 0, ws_scan_total = 0;
 };
 static int64_t jpeg_align(int64_t b, int64_t a = 256) { return (b + a - 1) / a * a; }
 
-static int jpeg_plan_build(const void* const* files, const int64_t* lengths, int B, GgJpegPlan* pl) {
+static int jpeg_plan_build(const void* const* files, const int64_t* lengths, int B, int split, GgJpegPlan* pl) {
     pl->B = B;
+    pl->split = split;
+    pl->img_subs.assign(B, 0);
     pl->info.resize(B);
     pl->len.assign(lengths, lengths + B);
     std::vector<JpegImgDev> imgs(B);
@@ -467,6 +618,37 @@ static int jpeg_plan_build(const void* const* files, const int64_t* lengths, int
     pl->seg_off = off; off += jpeg_align(std::max<int64_t>(nseg, 1) * sizeof(JpegSegDev));
     pl->quant_off = off; off += jpeg_align((int64_t)quant.size() * 2);
     pl->huff_off = off; off += jpeg_align(std::max<int64_t>((int64_t)huff.size(), 1) * 4);
+    // the sub-segments: every segment cut by the walk over its bytes (the files are read here, where the offsets inside them are still at hand)
+    std::vector<JscanSub> subs;
+    std::vector<int32_t> seg_sub0;
+    if (split > 0) {
+        std::vector<int64_t> begins, dbegs;
+        for (int b = 0; b < B; ++b) {
+            if (pl->info[b].refusal != GG_JPEG_OK) continue;
+            const JpegParsed& P = parsed[b];
+            for (size_t i = 0; i < P.segs.size(); ++i) {
+                const uint8_t* p = (const uint8_t*)files[b] + P.segs[i].first;
+                const int64_t n = P.segs[i].second - P.segs[i].first;
+                int64_t dtotal = 0;
+                const int64_t cap = jscan_cut_cap(n, split);
+                if ((int64_t)begins.size() < cap) { begins.resize((size_t)cap); dbegs.resize((size_t)cap); }
+                const int64_t count = jscan_cut(p, n, split, begins.data(), dbegs.data(), cap, &dtotal);
+                GG_CHECK((int64_t)subs.size() + count < (1LL << 31) / JSCAN_PHASES, "gg_jscan_plan_create: too many sub-segments (split_bytes=%d)", split);
+                seg_sub0.push_back((int32_t)subs.size());
+                for (int64_t j = 0; j < count; ++j) {
+                    JscanSub s;
+                    s.begin = begins[j]; s.end = j + 1 < count ? begins[j + 1] : n;
+                    s.dbeg = dbegs[j]; s.dend = j + 1 < count ? dbegs[j + 1] : dtotal;
+                    s.seg = (int32_t)seg_sub0.size() - 1; s.idx = (int32_t)j; s.nsub = (int32_t)count; s.pad = 0;
+                    subs.push_back(s);
+                }
+                pl->img_subs[b] += (int32_t)count;
+            }
+        }
+        pl->nsub = (int64_t)subs.size();
+        pl->segsub_off = off; off += jpeg_align(std::max<int64_t>((int64_t)seg_sub0.size(), 1) * 4);
+        pl->sub_off = off; off += jpeg_align(std::max<int64_t>(pl->nsub, 1) * (int64_t)sizeof(JscanSub));
+    }
     const int64_t table_bytes = off;
     for (int b = 0; b < B; ++b) {
         pl->info[b].stream_offset = off;
@@ -498,27 +680,48 @@ static int jpeg_plan_build(const void* const* files, const int64_t* lengths, int
     pl->ws_coef = w; w += coef_off;
     pl->ws_planes = w; w += plane_off;
     pl->ws_total = std::max<int64_t>(w, 256);
+    if (split > 0) {
+        if (!seg_sub0.empty()) memcpy(&pl->tables[pl->segsub_off], seg_sub0.data(), seg_sub0.size() * 4);
+        if (!subs.empty()) memcpy(&pl->tables[pl->sub_off], subs.data(), subs.size() * sizeof(JscanSub));
+        w = pl->ws_total;
+        pl->ws_slow = w; w += jpeg_align(std::max<int64_t>(pl->nseg, 1) * 4);
+        pl->ws_recs = w; w += jpeg_align(std::max<int64_t>(pl->nsub, 1) * JSCAN_PHASES * (int64_t)sizeof(JscanRec));
+        pl->ws_outs = w; w += jpeg_align(std::max<int64_t>(pl->nsub, 1) * (int64_t)sizeof(JscanOut));
+        pl->ws_sums = w; w += jpeg_align(std::max<int64_t>(pl->nsub, 1) * 16);
+        pl->ws_scan_total = w;
+    }
     return 0;
 }
 // the C boundary: nothing is thrown across it; running out of host memory is an error like any other
-extern "C" int gg_jpeg_plan_create(const void* const* files, const int64_t* lengths, int B, GgJpegPlan** out) {
-    GG_CHECK(files && lengths && out, "gg_jpeg_plan_create: null files / lengths / plan");
-    GG_CHECK(B > 0 && B <= GG_JPEG_MAX_B, "gg_jpeg_plan_create: B=%d outside [1, %d]", B, GG_JPEG_MAX_B);
-    for (int b = 0; b < B; ++b) GG_CHECK(files[b] && lengths[b] >= 0, "gg_jpeg_plan_create: file %d is null or has a negative length", b);
+static int jpeg_plan_create(const char* who, const void* const* files, const int64_t* lengths, int B, int split, GgJpegPlan** out) {
+    GG_CHECK(files && lengths && out, "%s: null files / lengths / plan", who);
+    GG_CHECK(B > 0 && B <= GG_JPEG_MAX_B, "%s: B=%d outside [1, %d]", who, B, GG_JPEG_MAX_B);
+    for (int b = 0; b < B; ++b) GG_CHECK(files[b] && lengths[b] >= 0, "%s: file %d is null or has a negative length", who, b);
     GgJpegPlan* pl = nullptr;
     int rc = -1;
     try {
         pl = new GgJpegPlan;
-        rc = jpeg_plan_build(files, lengths, B, pl);
+        rc = jpeg_plan_build(files, lengths, B, split, pl);
     } catch (const std::bad_alloc&) {
-        gg_set_error("gg_jpeg_plan_create: out of host memory for a plan of %d files", B);
+        gg_set_error("%s: out of host memory for a plan of %d files", who, B);
     } catch (const std::exception& e) {
-        gg_set_error("gg_jpeg_plan_create: %s", e.what());
+        gg_set_error("%s: %s", who, e.what());
     }
     if (rc != 0) { delete pl; return -1; }
     *out = pl;
     return 0;
 }
+extern "C" int gg_jpeg_plan_create(const void* const* files, const int64_t* lengths, int B, GgJpegPlan** out) {
+    return jpeg_plan_create("gg_jpeg_plan_create", files, lengths, B, 0, out);
+}
+extern "C" int gg_jscan_plan_create(const void* const* files, const int64_t* lengths, int B, int split_bytes, GgJpegPlan** out) {
+    GG_CHECK(split_bytes >= GG_JSCAN_MIN_SPLIT && split_bytes <= GG_JSCAN_MAX_SPLIT, "gg_jscan_plan_create: split_bytes=%d outside [%d, %d]", split_bytes,
+             GG_JSCAN_MIN_SPLIT, GG_JSCAN_MAX_SPLIT);
+    return jpeg_plan_create("gg_jscan_plan_create", files, lengths, B, split_bytes, out);
+}
+extern "C" int gg_jscan_plan_subsegments(const GgJpegPlan* plan, int b) { return plan && plan->split > 0 && b >= 0 && b < plan->B ? plan->img_subs[b] : -1; }
+extern "C" int64_t gg_jscan_plan_total_subsegments(const GgJpegPlan* plan) { return plan && plan->split > 0 ? plan->nsub : -1; }
+extern "C" int64_t gg_jscan_workspace_bytes(const GgJpegPlan* plan) { return plan && plan->split > 0 ? plan->ws_scan_total : -1; }
 extern "C" int gg_jpeg_plan_destroy(GgJpegPlan* plan) { delete plan; return 0; }
 extern "C" int gg_jpeg_plan_info(const GgJpegPlan* plan, int b, GgJpegInfo* info) {
     GG_CHECK(plan && info, "gg_jpeg_plan_info: null plan / info");
@@ -543,6 +746,90 @@ extern "C" int gg_jpeg_plan_fill(const GgJpegPlan* plan, const void* const* file
         const int64_t next = b + 1 < plan->B ? plan->info[b + 1].stream_offset : plan->stream_bytes;
         memset(o + at, 0, (size_t)(next - at));
     }
+    return 0;
+}
+
+// the lanes of a launch with one lane per item: spread over JPEG_TARGET_WAVES waves when there are few items
+static int jpeg_lanes(int64_t items) { return (int)std::min<int64_t>(64, std::max<int64_t>(1, gg_cdiv(items, JPEG_TARGET_WAVES))); }
+
+extern "C" int gg_jscan_decode(const GgJpegPlan* plan, const void* stream_buf, int64_t stream_bytes, void* out, int64_t out_bytes, int32_t* status, int32_t* slow,
+                               void* workspace, int64_t workspace_bytes, void* stream) {
+    GG_CHECK(plan, "gg_jscan_decode: null plan");
+    GG_CHECK(plan->split > 0, "gg_jscan_decode: the plan has no sub-segment table (it was made by gg_jpeg_plan_create, not gg_jscan_plan_create)");
+    if (plan->first_refused >= 0) {
+        const int b = plan->first_refused;
+        GG_CHECK(false, "gg_jscan_decode: image %d is refused: %s", b, gg_jpeg_refusal_name(plan->info[b].refusal));
+    }
+    GG_CHECK(stream_buf && out && status && workspace, "gg_jscan_decode: null stream buffer / out / status / workspace");
+    GG_CHECK((((uintptr_t)stream_buf | (uintptr_t)out | (uintptr_t)workspace) & 15) == 0 && (((uintptr_t)status | (uintptr_t)slow) & 3) == 0,
+             "gg_jscan_decode: the stream buffer, the output and the workspace must be 16-byte aligned");
+    GG_CHECK(stream_bytes >= plan->stream_bytes, "gg_jscan_decode: the stream buffer has %lld bytes, the plan needs %lld (gg_jpeg_plan_stream_bytes)", (long long)stream_bytes,
+             (long long)plan->stream_bytes);
+    GG_CHECK(out_bytes >= plan->out_bytes, "gg_jscan_decode: the output has %lld bytes, the plan needs %lld (gg_jpeg_plan_output_bytes)", (long long)out_bytes,
+             (long long)plan->out_bytes);
+    GG_CHECK(workspace_bytes >= plan->ws_scan_total, "gg_jscan_decode: the workspace has %lld bytes, the plan needs %lld (gg_jscan_workspace_bytes)", (long long)workspace_bytes,
+             (long long)plan->ws_scan_total);
+    hipStream_t st = (hipStream_t)stream;
+    const uint8_t* sb = (const uint8_t*)stream_buf;
+    const JpegImgDev* imgs = (const JpegImgDev*)(sb + plan->img_off);
+    const JpegSegDev* segs = (const JpegSegDev*)(sb + plan->seg_off);
+    const uint16_t* quant = (const uint16_t*)(sb + plan->quant_off);
+    const uint32_t* huff = (const uint32_t*)(sb + plan->huff_off);
+    const int32_t* seg_sub0 = (const int32_t*)(sb + plan->segsub_off);
+    const JscanSub* subs = (const JscanSub*)(sb + plan->sub_off);
+    char* w = (char*)workspace;
+    int32_t* seg_status = (int32_t*)(w + plan->ws_status);
+    int16_t* coef = (int16_t*)(w + plan->ws_coef);
+    uint8_t* planes = (uint8_t*)(w + plan->ws_planes);
+    int32_t* seg_slow = (int32_t*)(w + plan->ws_slow);
+    JscanRec* recs = (JscanRec*)(w + plan->ws_recs);
+    JscanOut* outs = (JscanOut*)(w + plan->ws_outs);
+    int32_t* sums = (int32_t*)(w + plan->ws_sums);
+    const int B = plan->B, nseg = plan->nseg;
+    const int64_t nsub = plan->nsub;
+    const size_t lds = (size_t)plan->nhuff * JPEG_HUFF_WORDS * 4;
+    const bool use_lds = lds <= JPEG_LDS_MAX_BYTES;
+    // one profiler scope per stage, in launch order (tools/bench_jpeg_decode.py names them by position): speculate, resolve, write, DC, inverse DCT, status + pack
+    {
+        GG_PROF(GG_CAT_MOVE, 0, 2.0 * JSCAN_PHASES * (double)plan->file_bytes, stream);
+        const int64_t total = nsub * JSCAN_PHASES;
+        const int lanes = jpeg_lanes(total);
+        const unsigned blocks = (unsigned)gg_cdiv(total, lanes);
+        if (use_lds) hipLaunchKernelGGL(jscan_speculate_kernel<true>, dim3(blocks), dim3(64), lds, st, sb, imgs, segs, subs, huff, plan->nhuff, total, lanes, recs);
+        else hipLaunchKernelGGL(jscan_speculate_kernel<false>, dim3(blocks), dim3(64), 0, st, sb, imgs, segs, subs, huff, plan->nhuff, total, lanes, recs);
+    }
+    {
+        GG_PROF(GG_CAT_MOVE, 0, (double)nsub * JSCAN_PHASES * sizeof(JscanRec), stream);
+        const int lanes = jpeg_lanes(nseg);
+        hipLaunchKernelGGL(jscan_resolve_kernel, dim3((unsigned)gg_cdiv(nseg, lanes)), dim3(64), 0, st, sb, imgs, segs, seg_sub0, subs, huff, nseg, lanes, recs, outs,
+                           seg_status, seg_slow);
+    }
+    {
+        GG_PROF(GG_CAT_MOVE, 0, (double)plan->file_bytes + (double)plan->coef_bytes, stream);
+        const int lanes = jpeg_lanes(nsub);
+        const unsigned blocks = (unsigned)gg_cdiv(nsub, lanes);
+        if (use_lds) hipLaunchKernelGGL(jscan_write_kernel<true>, dim3(blocks), dim3(64), lds, st, sb, imgs, segs, subs, huff, plan->nhuff, nsub, lanes, outs, coef, sums, seg_status);
+        else hipLaunchKernelGGL(jscan_write_kernel<false>, dim3(blocks), dim3(64), 0, st, sb, imgs, segs, subs, huff, plan->nhuff, nsub, lanes, outs, coef, sums, seg_status);
+    }
+    {
+        GG_PROF(GG_CAT_MOVE, 0, (double)plan->coef_bytes / 32, stream);
+        int lanes = jpeg_lanes(nseg);
+        hipLaunchKernelGGL(jscan_dc_prefix_kernel, dim3((unsigned)gg_cdiv(nseg, lanes)), dim3(64), 0, st, seg_sub0, subs, nseg, lanes, outs, sums);
+        lanes = jpeg_lanes(nsub);
+        hipLaunchKernelGGL(jscan_dc_apply_kernel, dim3((unsigned)gg_cdiv(nsub, lanes)), dim3(64), 0, st, imgs, segs, subs, nsub, lanes, outs, sums, coef);
+    }
+    {
+        GG_PROF(GG_CAT_MOVE, 0, (double)plan->coef_bytes + (double)plan->plane_bytes, stream);
+        hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)std::min<int64_t>(gg_cdiv(plan->max_blocks, 256), 1024), (unsigned)B), dim3(256), 0, st, imgs, quant, coef, planes);
+    }
+    {
+        GG_PROF(GG_CAT_MOVE, 0, (double)plan->plane_bytes + (double)plan->out_bytes, stream);
+        hipLaunchKernelGGL(jpeg_status_kernel, dim3((unsigned)B), dim3(64), 0, st, imgs, seg_status, status);
+        if (slow) hipLaunchKernelGGL(jscan_slow_kernel, dim3((unsigned)B), dim3(64), 0, st, imgs, seg_slow, slow);
+        hipLaunchKernelGGL(jpeg_pack_kernel, dim3((unsigned)std::min<int64_t>(gg_cdiv(gg_cdiv(plan->max_pixels, 4), 256), 1024), (unsigned)B), dim3(256), 0, st, imgs, planes,
+                           status, (uint8_t*)out);
+    }
+    GG_LAUNCH_CHECK();
     return 0;
 }
 

@@ -201,10 +201,11 @@ class DeviceTrainTransform:
     uint8 arrays, a list of those or an (N,3,H,W) uint8 tensor -> (N,3,S,S) float32 ``pixel_values`` on ``device`` (with ``return_u8=True`` also the (N,S,S,3) uint8
     batch after the last op).  ``params``: a record table to replay (``sample_params``' layout); otherwise one is drawn from the transform's own generator and kept in
     ``.last_params``.  The workspace is the transform's own and is reused from call to call (it grows when a batch needs more).  ``images`` may also be a list in
-    which every item is a JPEG file as bytes (decoded on the device by a ``training.jpeg.DeviceJpegDecoder`` the transform owns) or that decoder's ``PackedImages``."""
+    which every item is a JPEG file as bytes (decoded on the device by a ``training.jpeg.DeviceJpegDecoder`` the transform owns) or that decoder's ``PackedImages``.
+    ``jpeg_split_bytes`` is that decoder's ``split_bytes`` (0, the default: one lane per restart segment; positive: many lanes inside a scan, the same pixels)."""
 
     def __init__(self, img_size: int = 224, mean: Sequence[float] = TINYVIT_MEAN, std: Sequence[float] = TINYVIT_STD, auto_augment: str = "rand-m9-mstd0.5-inc1",
-                 interpolation: str = "bicubic", seed: int = 0, device="cuda"):
+                 interpolation: str = "bicubic", seed: int = 0, device="cuda", jpeg_split_bytes: int = 0):
         if interpolation not in ("bilinear", "bicubic", "random"):
             raise ValueError(f"DeviceTrainTransform: interpolation must be bilinear, bicubic or random, got {interpolation!r}")
         parse_config(auto_augment)
@@ -214,6 +215,7 @@ class DeviceTrainTransform:
         self.last_params: Optional[np.ndarray] = None
         self._workspace: Optional[torch.Tensor] = None
         self._decoder = None                              # training.jpeg.DeviceJpegDecoder, made when file bytes first arrive
+        self.jpeg_split_bytes = int(jpeg_split_bytes)
 
     def _filter(self) -> int:
         if self.interpolation == "random":
@@ -227,7 +229,7 @@ class DeviceTrainTransform:
             images = [images]
         if is_file_bytes_list(images):                    # JPEG files as bytes: decoded on the device, consumed where the decoded batch lies
             if self._decoder is None:
-                self._decoder = DeviceJpegDecoder(self.device)
+                self._decoder = DeviceJpegDecoder(self.device, self.jpeg_split_bytes)
             images = self._decoder.decode(images)
         decoded = images if isinstance(images, PackedImages) else None
         hwc = [] if decoded is not None else _as_hwc_list(images)
@@ -269,13 +271,20 @@ class DeviceTrainTransform:
         return (dst, dst_u8) if return_u8 else dst
 
 
+def _hand_split_bytes(transform, jpeg_split_bytes: int) -> None:
+    if jpeg_split_bytes and getattr(transform, "jpeg_split_bytes", 0) != int(jpeg_split_bytes):
+        transform.jpeg_split_bytes, transform._decoder = int(jpeg_split_bytes), None
+
+
 class augmented:
     """``{"images", "labels"}`` batches -> ``{"pixel_values", "labels"}`` batches, lazily, one ``transform`` call per batch: ``train(model, augmented(raw_batches,
     tfm), val_batches, ...)`` is the reference's loop with its training transform.  Iterating is a generator over ``batches``; like a DataLoader the object can be
-    walked once per epoch (when ``batches`` can), and every walk draws new records."""
+    walked once per epoch (when ``batches`` can), and every walk draws new records.  ``jpeg_split_bytes`` other than 0 is handed to the transform (its decoder of
+    file bytes is made anew with it); 0 leaves the transform as it is."""
 
-    def __init__(self, batches: Iterable, transform: DeviceTrainTransform):
+    def __init__(self, batches: Iterable, transform: DeviceTrainTransform, jpeg_split_bytes: int = 0):
         self.batches, self.transform = batches, transform
+        _hand_split_bytes(transform, jpeg_split_bytes)
 
     def __iter__(self):
         for batch in self.batches:
@@ -289,10 +298,11 @@ class eval_transformed:
     """The twin of ``augmented`` for the validation side -- the reference's ``collate_val``: ``{"images", "labels"}`` batches -> ``{"pixel_values", "labels"}``
     batches, lazily, one ``transform`` call (``training.preprocess.DeviceEvalTransform``: one ``gg_eval_batch``) per batch, so
     ``evaluate(model, eval_transformed(raw_val, tfm))`` and ``extract_embeddings(model, eval_transformed(...))`` run on raw images.  Nothing is drawn: every walk
-    yields the same batches."""
+    yields the same batches.  ``jpeg_split_bytes``: as in ``augmented``."""
 
-    def __init__(self, batches: Iterable, transform):
+    def __init__(self, batches: Iterable, transform, jpeg_split_bytes: int = 0):
         self.batches, self.transform = batches, transform
+        _hand_split_bytes(transform, jpeg_split_bytes)
 
     def __iter__(self):
         for batch in self.batches:

@@ -242,12 +242,16 @@ def clip_preprocess(images, size: int, device) -> Tensor:
 class CLIPEmbedding(nn.Module):
     def __init__(self, model_name: str = "openai/clip-vit-base-patch32", device: str = "cuda", load_checkpoint: bool = False,
                  panorama: bool = False, state_dict: Optional[Dict[str, Tensor]] = None, precision: Optional[str] = None, batch_transform: bool = False,
-                 **cfg_overrides):
+                 jpeg_split_bytes: int = 0, **cfg_overrides):
         """``batch_transform`` (not in the reference): raw images -- a list of any sizes, or the four panorama views together -- go through ONE ``gg_eval_batch``
-        call (``training.preprocess.DeviceEvalTransform``) instead of one ``gg_preprocess_pil`` call per image; same arithmetic."""
+        call (``training.preprocess.DeviceEvalTransform``) instead of one ``gg_preprocess_pil`` call per image; same arithmetic.  ``jpeg_split_bytes`` (with
+        ``batch_transform`` only): the ``split_bytes`` of the decoder that takes JPEG files given as bytes (``DeviceEvalTransform``'s keyword)."""
         super().__init__()
         self.device = device
         self.batch_transform, self._transform = bool(batch_transform), None
+        if jpeg_split_bytes and not batch_transform:
+            raise ValueError("CLIPEmbedding: jpeg_split_bytes needs batch_transform=True")
+        self.jpeg_split_bytes = int(jpeg_split_bytes)
         self.panorama = panorama
         self.clip_model = CLIPVisionTower(model_name if not load_checkpoint else "openai/clip-vit-base-patch32", precision=precision, **cfg_overrides)
         if load_checkpoint:
@@ -264,7 +268,8 @@ class CLIPEmbedding(nn.Module):
         """The processor's tensor side as a batch transform (``batch_transform=True``); it keeps its workspace from call to call."""
         if self._transform is None:
             from ..training.preprocess import DeviceEvalTransform
-            self._transform = DeviceEvalTransform(self.clip_model.cfg.image_size, CLIP_MEAN, CLIP_STD, "clip", device=next(self.clip_model.parameters()).device)
+            self._transform = DeviceEvalTransform(self.clip_model.cfg.image_size, CLIP_MEAN, CLIP_STD, "clip", device=next(self.clip_model.parameters()).device,
+                                                  jpeg_split_bytes=self.jpeg_split_bytes)
         return self._transform
 
     def _get_embedding(self, image) -> Tensor:

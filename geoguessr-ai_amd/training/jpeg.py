@@ -2,7 +2,12 @@
 takes a list of JPEG files as ``bytes`` / ``bytearray`` / ``memoryview`` and returns a ``PackedImages``: the packed HWC uint8 RGB batch that ``gg_eval_batch`` and
 ``gg_aug_batch`` take as ``src`` (``DeviceEvalTransform`` and ``DeviceTrainTransform`` accept it, or the list of file bytes itself), byte for byte what
 ``PIL.Image.open(f).convert("RGB")`` gives.  The host parses the headers and finds the restart segments (``plan``: no GPU needed), ONE pinned upload moves the tables and
-the files, four kernels decode.  Nothing comes back to the host but the per-image status."""
+the files, four kernels decode.  Nothing comes back to the host but the per-image status.
+
+``split_bytes`` (``JpegPlan``, ``DeviceJpegDecoder``; 0, the default, is the path above, call for call) turns on the decode with many lanes inside one scan
+(include/gg_jscan.h): every restart segment -- the whole scan of a file without restart markers -- is cut into sub-segments of about that many bytes, and
+speculate / resolve / write / DC passes take the place of the one-lane-per-segment entropy kernel.  The bytes are the same whatever the value; ``PackedImages.slow``
+then counts, per image, the sub-segments no speculative lane reached in the true decoder state."""
 import ctypes as C
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
@@ -21,6 +26,7 @@ class PackedImages(NamedTuple):
     offsets: np.ndarray                   # int64 [B], multiples of 256
     sizes: List[Tuple[int, int]]          # (height, width)
     status: torch.Tensor                  # int32 [B] on the device: 0, or why the image's bytes are all 0
+    slow: Optional[torch.Tensor] = None   # int32 [B] on the device, decodes with split_bytes > 0 only: sub-segments that took the resolve pass's slow path
 
 
 def is_file_bytes(x) -> bool:
@@ -34,9 +40,11 @@ def is_file_bytes_list(x) -> bool:
 
 class JpegPlan:
     """The host-side plan of one batch (``gg_jpeg_plan_create``): ``info`` (one ``_lib.JpegInfo`` per file: height, width, components, hs, vs, segments, refusal,
-    out_offset, stream_offset), ``stream_bytes`` / ``table_bytes`` / ``output_bytes`` / ``workspace_bytes``.  Needs no GPU."""
+    out_offset, stream_offset), ``stream_bytes`` / ``table_bytes`` / ``output_bytes`` / ``workspace_bytes``.  Needs no GPU.  With ``split_bytes`` > 0 the plan is
+    ``gg_jscan_plan_create``'s: the same answers, a sub-segment table in the table block, ``subsegments`` (per image), ``total_subsegments`` and a
+    ``workspace_bytes`` that is ``gg_jscan_decode``'s (``base_workspace_bytes`` stays ``gg_jpeg_decode``'s, which takes such a plan too)."""
 
-    def __init__(self, files: Sequence):
+    def __init__(self, files: Sequence, split_bytes: int = 0):
         if not is_file_bytes_list(files):
             raise GgError("JpegPlan: files must be a non-empty list of bytes / bytearray / memoryview")
         if len(files) > _lib.JPEG_MAX_B:
@@ -47,7 +55,11 @@ class JpegPlan:
         self._ptrs = (C.c_void_p * B)(*[v.ctypes.data if v.size else C.addressof(_EMPTY) for v in self._views])
         self._lens = (C.c_int64 * B)(*[v.size for v in self._views])
         self._h = C.c_void_p()
-        _lib.check(lib.gg_jpeg_plan_create(self._ptrs, self._lens, B, C.byref(self._h)), "gg_jpeg_plan_create")
+        self.split_bytes = int(split_bytes)
+        if self.split_bytes:
+            _lib.check(lib.gg_jscan_plan_create(self._ptrs, self._lens, B, self.split_bytes, C.byref(self._h)), "gg_jscan_plan_create")
+        else:
+            _lib.check(lib.gg_jpeg_plan_create(self._ptrs, self._lens, B, C.byref(self._h)), "gg_jpeg_plan_create")
         self.B = B
         self.info = []
         for b in range(B):
@@ -57,6 +69,12 @@ class JpegPlan:
         self.stream_bytes, self.table_bytes = lib.gg_jpeg_plan_stream_bytes(self._h), lib.gg_jpeg_plan_table_bytes(self._h)
         self.output_bytes, self.workspace_bytes = lib.gg_jpeg_plan_output_bytes(self._h), lib.gg_jpeg_workspace_bytes(self._h)
         self.first_refused = lib.gg_jpeg_plan_first_refused(self._h)
+        self.base_workspace_bytes = self.workspace_bytes
+        self.subsegments, self.total_subsegments = None, None
+        if self.split_bytes:
+            self.subsegments = [lib.gg_jscan_plan_subsegments(self._h, b) for b in range(B)]
+            self.total_subsegments = lib.gg_jscan_plan_total_subsegments(self._h)
+            self.workspace_bytes = lib.gg_jscan_workspace_bytes(self._h)
 
     def refusal_name(self, b: int) -> str:
         return _lib.lib().gg_jpeg_refusal_name(self.info[b].refusal).decode()
@@ -92,17 +110,19 @@ class DeviceJpegDecoder:
     reason before anything is launched; with ``check=True`` (the default) a file whose entropy data is damaged raises the same way after the decode (one int32 per image
     is read back), with ``check=False`` its image is all zeros and ``status`` says why.  The read-back of ``check=True`` waits for the decode: one host
     synchronisation per batch, also on the transforms' and embedders' paths, which decode with the default; a pipeline that must not wait decodes with
-    ``check=False`` itself, hands the ``PackedImages`` on and looks at ``status`` later."""
+    ``check=False`` itself, hands the ``PackedImages`` on and looks at ``status`` later.  ``split_bytes`` > 0: the decode with many lanes inside one scan
+    (``gg_jscan_decode``), for files without restart markers; the same bytes, and ``PackedImages.slow``."""
 
-    def __init__(self, device="cuda"):
+    def __init__(self, device="cuda", split_bytes: int = 0):
         self.device = torch.device(device)
+        self.split_bytes = int(split_bytes)
         self._staging: Optional[torch.Tensor] = None
         self._uploaded: Optional[torch.cuda.Event] = None
         self._workspace: Optional[torch.Tensor] = None
 
     def decode(self, files: Sequence, check: bool = True) -> PackedImages:
         _lib.require_gpu()
-        plan = JpegPlan(list(files) if isinstance(files, (list, tuple)) else [files])
+        plan = JpegPlan(list(files) if isinstance(files, (list, tuple)) else [files], self.split_bytes)
         try:
             plan.require_accepted()
             if self._uploaded is not None:
@@ -119,8 +139,14 @@ class DeviceJpegDecoder:
                     self._workspace = torch.empty(plan.workspace_bytes, dtype=torch.uint8, device=self.device)
                 packed = torch.empty(max(plan.output_bytes, 1), dtype=torch.uint8, device=self.device)
                 status = torch.empty(plan.B, dtype=torch.int32, device=self.device)
-                _lib.check(_lib.lib().gg_jpeg_decode(plan.handle, stream_buf.data_ptr(), stream_buf.numel(), packed.data_ptr(), packed.numel(), status.data_ptr(),
-                                                     self._workspace.data_ptr(), self._workspace.numel(), _lib.stream()), "gg_jpeg_decode")
+                slow = None
+                if self.split_bytes:
+                    slow = torch.empty(plan.B, dtype=torch.int32, device=self.device)
+                    _lib.check(_lib.lib().gg_jscan_decode(plan.handle, stream_buf.data_ptr(), stream_buf.numel(), packed.data_ptr(), packed.numel(), status.data_ptr(),
+                                                          slow.data_ptr(), self._workspace.data_ptr(), self._workspace.numel(), _lib.stream()), "gg_jscan_decode")
+                else:
+                    _lib.check(_lib.lib().gg_jpeg_decode(plan.handle, stream_buf.data_ptr(), stream_buf.numel(), packed.data_ptr(), packed.numel(), status.data_ptr(),
+                                                         self._workspace.data_ptr(), self._workspace.numel(), _lib.stream()), "gg_jpeg_decode")
             offsets = np.array([i.out_offset for i in plan.info], np.int64)
             sizes = [(int(i.height), int(i.width)) for i in plan.info]
         finally:
@@ -130,7 +156,7 @@ class DeviceJpegDecoder:
             bad = np.nonzero(st)[0]
             if len(bad):
                 raise GgError(f"DeviceJpegDecoder: image {int(bad[0])} failed to decode: {STATUS_NAMES.get(int(st[bad[0]]), 'unknown')}")
-        return PackedImages(packed, offsets, sizes, status)
+        return PackedImages(packed, offsets, sizes, status, slow)
 
     def unpack(self, p: PackedImages) -> List[torch.Tensor]:
         """The images as (H, W, 3) uint8 views of the packed buffer (on the device)."""

@@ -9,8 +9,15 @@ Prints one JSON line per row and appends them to --out; per (B, restart) configu
                      restart markers): device takes no longer than pillow_16_threads (exit status 1 otherwise)
   device_stages      one profiled call (gg_prof_*: HIP events around every stage, in launch order): entropy, inverse DCT, status + upsample + colour + pack
   end_to_end         file bytes -> TinyViTEmbedding('tiny_vit_5m_224', batch_transform=True) embeddings: host decode (the 16-thread pool) against device decode
+  device_split       with --split-bytes S [S ...], per value: the same call through DeviceJpegDecoder(split_bytes=S) (gg_jscan_decode, include/gg_jscan.h: many
+                     lanes inside one scan), timed in the same repeats as the rows above; the sub-segments and speculative lanes of the batch, the share of
+                     sub-segments that took the resolve pass's slow path, the ratios to device (split_bytes = 0) and to pillow_16_threads.  THE GATES (without
+                     restart markers): at B = 256 the best split takes no longer than pillow_16_threads, at B = 1024 no longer than device
+  device_split_stages  one profiled call per value: speculate, resolve, write, DC, inverse DCT, status + upsample + colour + pack
+  split_summary      per configuration: the split_bytes that wins
 Timing: the variants alternate within one process after --warmup calls, --repeats times; every row reports the median and the spread (min, max).
     python tools/bench_jpeg_decode.py [--batches 256 1024 --src 640 --quality 90] [--out profiles/jpeg_decode_bench.jsonl]
+    python tools/bench_jpeg_decode.py --batches 64 256 1024 --split-bytes 256 512 1024 2048 --skip-e2e --out profiles/jpeg_split_bench.jsonl
 The files: --unique seeded synthetic images (smooth structure plus noise, tools/bench_augment.py's generator), encoded once and repeated to fill the batch; every
 copy is decoded on its own."""
 import argparse
@@ -61,13 +68,15 @@ def main():
     ap.add_argument("--e2e-repeats", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--split-bytes", type=int, nargs="*", default=[], help="also time DeviceJpegDecoder(split_bytes=S) for every S given")
+    ap.add_argument("--skip-e2e", action="store_true", help="leave out the end_to_end rows (and the embedder they need)")
     a = ap.parse_args()
     import warnings
     from PIL import Image
     from bench_augment import make_sources
     from geoguessr_ai_amd import _lib as L
     from geoguessr_ai_amd.pretrain.tinyvit_embedder import TinyViTEmbedding
-    from geoguessr_ai_amd.training.jpeg import DeviceJpegDecoder
+    from geoguessr_ai_amd.training.jpeg import DeviceJpegDecoder, JpegPlan
     L.require_gpu()
     lib = L.lib()
     H = a.src
@@ -84,10 +93,13 @@ def main():
         encoded[restart] = out
     pool = ThreadPoolExecutor(a.threads)
     dec = DeviceJpegDecoder("cuda")
+    split_decs = {S: DeviceJpegDecoder("cuda", split_bytes=S) for S in a.split_bytes}
     torch.manual_seed(0)
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        emb = TinyViTEmbedding(model_name="tiny_vit_5m_224", device="cuda", batch_transform=True)
+    emb = None
+    if not a.skip_e2e:
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            emb = TinyViTEmbedding(model_name="tiny_vit_5m_224", device="cuda", batch_transform=True)
     rows, gate_ok = [], True
     for B in a.batches:
         for restart in (False, True):
@@ -98,6 +110,17 @@ def main():
             got = dec.unpack(p)
             identical = all(np.array_equal(got[b].cpu().numpy(), ref[b % a.unique]) for b in range(B))
             del got, p
+            split_info = {}
+            for S, sdec in split_decs.items():                           # the same bytes, the slow-path share and the lane counts, before anything is timed
+                p = sdec.decode(files)
+                got = sdec.unpack(p)
+                same = all(np.array_equal(got[b].cpu().numpy(), ref[b % a.unique]) for b in range(B))
+                plan = JpegPlan(files, split_bytes=S)
+                lanes = sum(n * (6 if i.components == 3 and i.hs * i.vs == 4 else (4 if i.components == 3 and i.hs * i.vs == 2 else i.components)) for n, i in zip(plan.subsegments, plan.info))
+                split_info[S] = dict(byte_identical_to_pillow=same, sub_segments=int(plan.total_subsegments), speculate_lanes_at_most=int(lanes),
+                                     slow_sub_segments=int(p.slow.sum()), slow_share=round(float(p.slow.sum()) / plan.total_subsegments, 5))
+                plan.close()
+                del got, p
             one = files[:min(B, a.one_thread_files)]
 
             def host16():
@@ -107,7 +130,9 @@ def main():
                 return dec.decode(files)
             for _ in range(a.warmup):
                 host16(); device()
-            t1, t16, td = [], [], []
+                for sdec in split_decs.values():
+                    sdec.decode(files)
+            t1, t16, td, ts = [], [], [], {S: [] for S in split_decs}
             for _ in range(a.repeats):                                    # the variants alternate: a drift of the machine reaches all of them
                 t = time.perf_counter()
                 for f in one:
@@ -117,6 +142,8 @@ def main():
                 host16()
                 t16.append((time.perf_counter() - t) * 1e3)
                 td.append(wall(device))
+                for S, sdec in split_decs.items():
+                    ts[S].append(wall(lambda: sdec.decode(files)))
             s1, s16, sd = spread(t1), spread(t16), spread(td)
             rows.append(dict(cfg, row="pillow_1_thread", **s1, unit="ms per image", files=len(one), images_per_s=round(1e3 / s1["ms"], 1)))
             rows.append(dict(cfg, row="pillow_16_threads", **s16, unit="ms per batch", images_per_s=round(B / s16["ms"] * 1e3, 1)))
@@ -125,6 +152,23 @@ def main():
             rows.append(dict(cfg, row="device", **sd, unit="ms per batch, wall clock, synchronised", images_per_s=round(B / sd["ms"] * 1e3, 1),
                              pillow_16_threads_over_device=round(s16["ms"] / sd["ms"], 2), byte_identical_to_pillow=identical, gated=gated, device_no_slower=ok))
             gate_ok = gate_ok and identical and (ok or not gated)
+            best = None
+            for S in split_decs:
+                ss = spread(ts[S])
+                rows.append(dict(cfg, row="device_split", split_bytes=S, **ss, unit="ms per batch, wall clock, synchronised", images_per_s=round(B / ss["ms"] * 1e3, 1),
+                                 device_over_split=round(sd["ms"] / ss["ms"], 2), pillow_16_threads_over_split=round(s16["ms"] / ss["ms"], 2), **split_info[S]))
+                gate_ok = gate_ok and split_info[S]["byte_identical_to_pillow"]
+                if best is None or ss["ms"] < best[1]["ms"]:
+                    best = (S, ss)
+            if best is not None:
+                gate = None
+                if not restart and B == 256:
+                    gate = dict(gate="split no slower than pillow_16_threads", passed=bool(best[1]["ms"] <= s16["ms"]))
+                if not restart and B == 1024:
+                    gate = dict(gate="split no slower than device (split_bytes = 0)", passed=bool(best[1]["ms"] <= sd["ms"]))
+                rows.append(dict(cfg, row="split_summary", winning_split_bytes=best[0], winning_ms=best[1]["ms"], device_ms=sd["ms"], pillow_16_threads_ms=s16["ms"],
+                                 **(gate or {})))
+                gate_ok = gate_ok and (gate is None or gate["passed"])
             # one profiled call: a scope per stage, in launch order
             names = ["entropy", "idct", "status_upsample_colour_pack"]
             lib.gg_prof_reset()
@@ -139,6 +183,24 @@ def main():
                 stages[n] = round(ms.value, 4)
             lib.gg_prof_reset()
             rows.append(dict(cfg, row="device_stages", stage_ms=stages, stage_sum_ms=round(sum(stages.values()), 4), dominant_stage=max(stages, key=stages.get)))
+
+            for S, sdec in split_decs.items():
+                snames = ["speculate", "resolve", "write", "dc", "idct", "status_upsample_colour_pack"]
+                lib.gg_prof_reset()
+                lib.gg_prof_enable(1)
+                sdec.decode(files)
+                torch.cuda.synchronize()
+                lib.gg_prof_enable(0)
+                assert lib.gg_prof_count() == len(snames), lib.gg_prof_count()
+                stages = {}
+                for i, n in enumerate(snames):
+                    L.check(lib.gg_prof_record(i, None, C.byref(ms), None, None), "gg_prof_record")
+                    stages[n] = round(ms.value, 4)
+                lib.gg_prof_reset()
+                rows.append(dict(cfg, row="device_split_stages", split_bytes=S, stage_ms=stages, stage_sum_ms=round(sum(stages.values()), 4),
+                                 dominant_stage=max(stages, key=stages.get)))
+            if emb is None:
+                continue
 
             # end to end: file bytes -> embeddings
             def e2e_host():
@@ -162,7 +224,8 @@ def main():
             for r in rows:
                 f.write(json.dumps(r) + "\n")
     if not gate_ok:
-        print("GATE FAILED: the device decode is slower than the 16-thread Pillow pool at B = 1024 without restart markers, or its bytes differ", file=sys.stderr)
+        print("GATE FAILED: the device decode is slower than the 16-thread Pillow pool at B = 1024 without restart markers, a split decode misses its gate "
+              "(split_summary rows), or bytes differ", file=sys.stderr)
         sys.exit(1)
 
 
