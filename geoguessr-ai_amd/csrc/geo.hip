@@ -11,36 +11,60 @@
 
 #define GEO_NT 256
 
+// degrees -> radians with the product ROUNDED, as torch.deg2rad rounds it.  Under -ffp-contract=fast the backend otherwise fuses x * d2r into the subtraction
+// that follows (lat1 - lat2 = fma(x, d2r, -lat2)): two identical points are then the product's rounding error apart (1 cm) instead of 0.
+__device__ __forceinline__ float deg2rad_f32(float deg) {
+    float r = deg * 0.017453292519943295f;
+    asm("" : "+v"(r));   // opaque to the optimiser (no fusion through it), free to be scheduled
+    return r;
+}
 __device__ __forceinline__ float haversine_km_f32(float lon1r, float lat1r, float coslat1, float lon2r, float lat2r, float coslat2) {
     // models/utils.py:48-56 in fp32: a = sin^2(dlat/2) + cos(lat1) cos(lat2) sin^2(dlon/2)
     const float sdlat = sinf((lat1r - lat2r) * 0.5f);
     const float sdlon = sinf((lon1r - lon2r) * 0.5f);
     float a = sdlat * sdlat + (coslat1 * coslat2) * (sdlon * sdlon);
-    a = fminf(a, 1.0f);   // exact antipodes can round above 1 (asin -> NaN); documented divergence
+    a = a > 1.0f ? 1.0f : a;   // exact antipodes can round above 1 (asin -> NaN); documented divergence.  A NaN coordinate stays NaN (fminf would make it pi R)
     const float c = 2.0f * asinf(sqrtf(a));
     return (6378137.0f * c) / 1000.0f;
 }
 
-struct ArgVal { float v; int i; };
-__device__ __forceinline__ ArgVal argmax_better(ArgVal a, ArgVal b) {   // larger value, then smaller index
+// (value, index) pairs and their block-wide best: the larger value, then the smaller index.  T = float ranks distances (a NaN never wins), T = int ranks
+// the order-preserving keys of the logits below.
+template <typename T> struct ArgBest { T v; int i; };
+using ArgVal = ArgBest<float>;
+using ArgKey = ArgBest<int>;
+template <typename T>
+__device__ __forceinline__ ArgBest<T> arg_better(ArgBest<T> a, ArgBest<T> b) {
     return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
 }
-__device__ __forceinline__ ArgVal block_argmax(ArgVal x, float* sv, int* si) {
+template <typename T>
+__device__ __forceinline__ ArgBest<T> block_arg_best(ArgBest<T> x, T* sv, int* si) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-        ArgVal y;
+        ArgBest<T> y;
         y.v = __shfl_xor(x.v, o, 64);
         y.i = __shfl_xor(x.i, o, 64);
-        x = argmax_better(x, y);
+        x = arg_better(x, y);
     }
     __syncthreads();
     if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = x.v; si[threadIdx.x >> 6] = x.i; }
     __syncthreads();
-    ArgVal r = {sv[0], si[0]};
+    ArgBest<T> r = {sv[0], si[0]};
 #pragma unroll
-    for (int k = 1; k < GEO_NT / 64; ++k) r = argmax_better(r, (ArgVal){sv[k], si[k]});
+    for (int k = 1; k < GEO_NT / 64; ++k) r = arg_better(r, (ArgBest<T>){sv[k], si[k]});
     return r;
 }
+
+// top-k order: torch.topk / argmax semantics -- a NaN ranks above every number, then the larger value, then the lower index.  Logits are ranked through
+// an order-preserving integer key: NaN (either sign) -> INT_MAX, -0 == +0, negative floats mirrored.  INT_MIN is no float's key: it marks a padded
+// column and a retired winner, and a round that finds nothing else returns {TOPK_NONE, INT_MAX} -- which the host excludes (num_candidates <= K).
+#define TOPK_NONE ((int)0x80000000)
+__device__ __forceinline__ int topk_key(float v) {
+    if (v != v) return 0x7fffffff;
+    const int b = __float_as_int(v);
+    return b < 0 ? (b == TOPK_NONE ? 0 : b ^ 0x7fffffff) : b;
+}
+__device__ __forceinline__ float topk_value(int key) { return __int_as_float(key < 0 ? key ^ 0x7fffffff : key); }
 
 struct GeoParams {
     const float* logits; int64_t ldl;
@@ -67,6 +91,7 @@ __global__ __launch_bounds__(GEO_NT) void geo_head_kernel(GeoParams p) {
     __shared__ float red[GEO_NT / 64];
     __shared__ float sv[GEO_NT / 64];
     __shared__ int si[GEO_NT / 64];
+    __shared__ int sk[GEO_NT / 64];
     const int n = blockIdx.x;
     const int tid = threadIdx.x;
     const float* zrow = p.logits + (int64_t)n * p.ldl;
@@ -84,12 +109,13 @@ __global__ __launch_bounds__(GEO_NT) void geo_head_kernel(GeoParams p) {
 #pragma unroll
     for (int e = 0; e < E; ++e) se += __expf(z[e] - zmax);
     se = gg_block_sum<GEO_NT>(se, red);
-    const float lse = zmax + logf(se);
+    // log-sum-exp RELATIVE to the row maximum: log_softmax(z) = (z - zmax) - lse.  Adding zmax back first would round lse to an ulp of the
+    // maximum (1e-3 at logits near 1e4) and put that error into every probability, the loss and the gradient.
+    const float lse = logf(se);
 
     const bool have_labels = p.labels != nullptr;
     if (have_labels && (p.mode == 1 || p.nearest)) {
-        const float d2r = 0.017453292519943295f;
-        const float lon1 = p.labels[2 * n] * d2r, lat1 = p.labels[2 * n + 1] * d2r;
+        const float lon1 = deg2rad_f32(p.labels[2 * n]), lat1 = deg2rad_f32(p.labels[2 * n + 1]);
         const float cl1 = cosf(lat1);
         float d[E];
         ArgVal best = {-INFINITY, 0x7fffffff};   // argmax of -d == argmin of d
@@ -97,12 +123,12 @@ __global__ __launch_bounds__(GEO_NT) void geo_head_kernel(GeoParams p) {
         for (int e = 0; e < E; ++e) {
             const int k = e * GEO_NT + tid;
             if (k < p.K) {
-                const float lon2 = p.centroids[2 * k] * d2r, lat2 = p.centroids[2 * k + 1] * d2r;
+                const float lon2 = deg2rad_f32(p.centroids[2 * k]), lat2 = deg2rad_f32(p.centroids[2 * k + 1]);
                 d[e] = haversine_km_f32(lon1, lat1, cl1, lon2, lat2, cosf(lat2));
-                best = argmax_better(best, (ArgVal){-d[e], k});
+                best = arg_better(best, (ArgVal){-d[e], k});
             } else d[e] = INFINITY;
         }
-        best = block_argmax(best, sv, si);
+        best = block_arg_best(best, sv, si);
         const float dmin = -best.v;
         if (p.nearest && tid == 0) p.nearest[n] = best.i;
         if (p.mode == 1) {
@@ -123,8 +149,8 @@ __global__ __launch_bounds__(GEO_NT) void geo_head_kernel(GeoParams p) {
                 const int k = e * GEO_NT + tid;
                 if (k < p.K) {
                     const float t = d[e] * inv;
-                    lr -= t * (z[e] - lse);
-                    if (p.dlogits) geo_store_dlogit(p, (int64_t)n * p.ldd + k, (__expf(z[e] - lse) * tsum - t) * p.grad_scale);
+                    lr -= t * ((z[e] - zmax) - lse);
+                    if (p.dlogits) geo_store_dlogit(p, (int64_t)n * p.ldd + k, (__expf((z[e] - zmax) - lse) * tsum - t) * p.grad_scale);
                 }
             }
             lr = gg_block_sum<GEO_NT>(lr, red);
@@ -142,29 +168,39 @@ __global__ __launch_bounds__(GEO_NT) void geo_head_kernel(GeoParams p) {
         for (int e = 0; e < E; ++e) {
             const int k = e * GEO_NT + tid;
             if (k < p.K) {
-                if (k == lab && p.loss_rows) p.loss_rows[n] = -(z[e] - lse);
+                if (k == lab && p.loss_rows) p.loss_rows[n] = -((z[e] - zmax) - lse);
                 if (p.dlogits)
-                    geo_store_dlogit(p, (int64_t)n * p.ldd + k, lab_ok ? (__expf(z[e] - lse) - (k == lab ? 1.f : 0.f)) * p.grad_scale : __builtin_nanf(""));
+                    geo_store_dlogit(p, (int64_t)n * p.ldd + k, lab_ok ? (__expf((z[e] - zmax) - lse) - (k == lab ? 1.f : 0.f)) * p.grad_scale : __builtin_nanf(""));
             }
         }
     }
     if (p.dlogits && p.mode != 0)
         for (int k = p.K + tid; k < p.ldd; k += GEO_NT) geo_store_dlogit(p, (int64_t)n * p.ldd + k, 0.f);
 
-    // predictions: top-`num_candidates` of softmax == of logits (destroys z)
+    // predictions: top-`num_candidates` of softmax == of logits, ranked by topk_key.  A winner is retired by giving its slot the key no logit has, so a
+    // row with fewer than num_candidates finite logits ranks its -inf entries by index, each once.  The host guarantees num_candidates <= K, so every
+    // round has a live candidate k < K and best.i is a valid centroid row.
     if (p.preds || p.topk_idx) {
-        for (int c = 0; c < p.num_candidates; ++c) {
-            ArgVal best = {-INFINITY, 0x7fffffff};
+        int kz[E];
 #pragma unroll
-            for (int e = 0; e < E; ++e) best = argmax_better(best, (ArgVal){z[e], e * GEO_NT + tid});
-            best = block_argmax(best, sv, si);
+        for (int e = 0; e < E; ++e) kz[e] = e * GEO_NT + tid < p.K ? topk_key(z[e]) : TOPK_NONE;
+        // the reported probabilities (at most 16 a row, one thread) are taken in double from the f32 sum, so that neither the rounded argument (half an
+        // ulp of |z - zmax - lse| ~ 10 is 5e-7 of p) nor the fast exponential shows in them
+        double lse_d = 0.0;
+        if (tid == 0 && p.topk_idx) lse_d = log((double)se);
+        for (int c = 0; c < p.num_candidates; ++c) {
+            ArgKey best = {TOPK_NONE, 0x7fffffff};
+#pragma unroll
+            for (int e = 0; e < E; ++e)      // k ascends with e: the strict comparison keeps the thread's lowest index
+                if (kz[e] > best.v) { best.v = kz[e]; best.i = e * GEO_NT + tid; }
+            best = block_arg_best(best, sk, si);
 #pragma unroll
             for (int e = 0; e < E; ++e)
-                if (e * GEO_NT + tid == best.i) z[e] = -INFINITY;
+                if (e * GEO_NT + tid == best.i) kz[e] = TOPK_NONE;
             if (tid == 0) {
                 if (p.topk_idx) {
                     p.topk_idx[(int64_t)n * p.num_candidates + c] = best.i;
-                    p.topk_vals[(int64_t)n * p.num_candidates + c] = __expf(best.v - lse);
+                    p.topk_vals[(int64_t)n * p.num_candidates + c] = (float)exp(((double)topk_value(best.v) - (double)zmax) - lse_d);
                 }
                 if (c == 0) {
                     if (p.preds) p.preds[n] = best.i;
@@ -185,12 +221,11 @@ __global__ void mean_f32_kernel(const float* __restrict__ x, int n, float* __res
 
 // ---------------------------------------------------------------------------- haversine matrix (debug / parity)
 __global__ void haversine_matrix_kernel(const float* __restrict__ x, const float* __restrict__ cent, float* __restrict__ out, int N, int K) {
-    const float d2r = 0.017453292519943295f;
     const int64_t total = (int64_t)N * K;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int k = (int)(i % K);
         const int n = (int)(i / K);
-        const float lon1 = x[2 * n] * d2r, lat1 = x[2 * n + 1] * d2r, lon2 = cent[2 * k] * d2r, lat2 = cent[2 * k + 1] * d2r;
+        const float lon1 = deg2rad_f32(x[2 * n]), lat1 = deg2rad_f32(x[2 * n + 1]), lon2 = deg2rad_f32(cent[2 * k]), lat2 = deg2rad_f32(cent[2 * k + 1]);
         out[i] = haversine_km_f32(lon1, lat1, cosf(lat1), lon2, lat2, cosf(lat2));
     }
 }
@@ -398,7 +433,10 @@ extern "C" int gg_geo_head(const GgGeoHeadArgs* a, void* stream) {
     if (a->mode == 1) GG_CHECK(a->labels, "gg_geo_head: soft CE needs labels (lon,lat)");
     if (a->mode == 2) GG_CHECK(a->labels_clf, "gg_geo_head: hard CE needs labels_clf");
     if (a->dlogits) GG_CHECK(a->ldd >= a->K, "gg_geo_head: ldd < K");
-    if (a->topk_idx) GG_CHECK(a->topk_vals && a->num_candidates > 0 && a->num_candidates <= 16, "gg_geo_head: bad top-k args");
+    if (a->topk_idx) {
+        GG_CHECK(a->topk_vals && a->num_candidates > 0 && a->num_candidates <= 16, "gg_geo_head: bad top-k args");
+        GG_CHECK(a->num_candidates <= a->K, "gg_geo_head: num_candidates=%d exceeds the K=%d classes there are to rank", a->num_candidates, a->K);
+    }
     GeoParams p;
     p.logits = a->logits; p.ldl = a->ldl; p.N = a->N; p.K = a->K;
     p.labels = a->labels; p.centroids = a->centroids; p.labels_clf = a->labels_clf; p.mode = a->mode;
@@ -406,7 +444,7 @@ extern "C" int gg_geo_head(const GgGeoHeadArgs* a, void* stream) {
     p.grad_scale = a->grad_scale;
     p.loss_rows = a->loss_rows; p.dlogits = a->dlogits; p.ldd = a->ldd; p.dlogits_f32 = a->dlogits_f32;
     p.preds = a->preds; p.llh = a->llh; p.topk_vals = a->topk_vals; p.topk_idx = a->topk_idx;
-    p.num_candidates = a->num_candidates > 0 ? a->num_candidates : 1;
+    p.num_candidates = a->topk_idx ? a->num_candidates : 1;      // preds / llh alone need the first rank only
     p.nearest = a->nearest;
     const int per = (int)gg_cdiv(a->K, GEO_NT);
     GG_PROF(GG_CAT_HEAD, 0, (a->dlogits ? 6.0 : 4.0) * a->N * (double)a->K, stream);

@@ -367,8 +367,16 @@ typedef struct GgGeoHeadArgs {
 } GgGeoHeadArgs;
 /* mode 2 with labels_clf[n] outside [0,K): torch's CrossEntropyLoss raises (models/super_guessr.py:383); here loss_rows[n], the mean
  * loss and row n of dlogits come out NaN. */
+/* Ranking (preds, llh, topk_*): torch.topk / argmax order on the logits -- a NaN logit ranks above every number, then the larger value, then the
+ * lower index; -inf logits rank last, by index.  An all-NaN row gives preds 0, topk_idx 0 .. num_candidates-1, llh = centroids[0] and NaN topk_vals
+ * (and, in modes 1 / 2, a NaN loss row, mean loss and gradient row; other rows are not touched).  num_candidates <= K is required (refused
+ * otherwise), so every index stored or used to gather a centroid lies in [0, K).
+ * A label row with a NaN coordinate (mode 1 / nearest): every distance is NaN, no centroid is nearest -- nearest[n] = 2147483647 (out of range, so a
+ * later hard CE on it is NaN as above), every soft target is nan_to_num'd to 0, and loss_rows[n] and row n of dlogits are 0. */
 int gg_geo_head(const GgGeoHeadArgs* args, void* stream);
-int gg_haversine_matrix(const float* x, const float* centroids, float* out, int N, int K, void* stream);   /* models/utils.py:39 */
+/* models/utils.py:39 in f32: radians rounded before they are subtracted (identical points are exactly 0 km apart), a clamped to 1 before asin (an exact
+ * antipode is pi R, never NaN), a NaN coordinate gives NaN. */
+int gg_haversine_matrix(const float* x, const float* centroids, float* out, int N, int K, void* stream);
 
 /* ---------------------------------------------------------------- hierarchical combine (models/super_guessr.py:89-99,340-345)
  * SuperGuessr(hierarchical=True): PositionalEncoder (position = batch index, models/layers/positional_encoder.py:44) ->
