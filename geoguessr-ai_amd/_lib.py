@@ -124,6 +124,13 @@ class EvalArgs(C.Structure):             # GgEvalArgs
                 ("std", C.c_float * 3), ("dst", C.c_void_p), ("dst_u8", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class PanoArgs(C.Structure):             # GgPanoArgs (include/gg_pano.h)
+    _fields_ = [("src", C.c_void_p), ("src_bytes", C.c_int64), ("offsets", C.c_void_p), ("heights", C.c_void_p), ("widths", C.c_void_p), ("num_images", C.c_int),
+                ("num_slots", C.c_int), ("slot_image", C.c_void_p), ("resize", C.c_int), ("Ht", C.c_int), ("Wt", C.c_int), ("normalize", C.c_int), ("mean", C.c_float * 3),
+                ("std", C.c_float * 3), ("dst", C.c_void_p), ("dst_u8", C.c_void_p), ("u8_offsets", C.c_void_p), ("dst_u8_bytes", C.c_int64), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_int64)]
+
+
 class JpegInfo(C.Structure):             # GgJpegInfo (include/gg_jpeg.h): what the host-side plan found out about one file
     _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("components", C.c_int32), ("hs", C.c_int32), ("vs", C.c_int32), ("segments", C.c_int32),
                 ("refusal", C.c_int32), ("reserved", C.c_int32), ("out_offset", C.c_int64), ("stream_offset", C.c_int64)]
@@ -408,6 +415,15 @@ JSCAN_SIGNATURES = {
 }
 JSCAN_SYMBOLS = list(JSCAN_SIGNATURES)
 
+# every exported symbol of include/gg_pano.h (the panorama fine-tune's input path for whole batches: Pillow resize, ToTensor, bilinear interpolation, normalise, slot table), bound from the same libgg.so
+PANO_MAX_SLOTS, PANO_MAX_IMAGES, PANO_MAX_TARGET = 4096, 4096, 2048        # GG_PANO_MAX_SLOTS, GG_PANO_MAX_IMAGES, GG_PANO_MAX_TARGET
+PANO_SIGNATURES = {
+    "gg_pano_resized_size": (_I, [_I, _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gg_pano_workspace_bytes": (_L, [C.POINTER(PanoArgs)]),
+    "gg_pano_batch": (_I, [C.POINTER(PanoArgs), _P]),
+}
+PANO_SYMBOLS = list(PANO_SIGNATURES)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -416,7 +432,7 @@ def lib() -> C.CDLL:
             raise GgError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JSCAN_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JSCAN_SIGNATURES.items()) + list(PANO_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the library lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -472,6 +488,7 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(root), "include", "gg_eval.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_jpeg.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_jscan.h"))
+    files.append(os.path.join(os.path.dirname(root), "include", "gg_pano.h"))
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

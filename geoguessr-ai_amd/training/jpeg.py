@@ -27,6 +27,7 @@ class PackedImages(NamedTuple):
     sizes: List[Tuple[int, int]]          # (height, width)
     status: torch.Tensor                  # int32 [B] on the device: 0, or why the image's bytes are all 0
     slow: Optional[torch.Tensor] = None   # int32 [B] on the device, decodes with split_bytes > 0 only: sub-segments that took the resolve pass's slow path
+    slots: Optional[np.ndarray] = None    # int32 (N, V) or (N,), DevicePanoramaTransform only: the image of each output slot, -1 for a missing view
 
 
 def is_file_bytes(x) -> bool:

@@ -48,12 +48,24 @@ def _num_rows(ds) -> int:
     return len(ds)
 
 
-def _take(ds, idx) -> Dict[str, torch.Tensor]:
-    """Rows ``idx`` of a column-dict dataset (dict of tensors / arrays) or of a map-style dataset of dict samples."""
+def _take(ds, idx, transform=None) -> Dict[str, torch.Tensor]:
+    """Rows ``idx`` of a column-dict dataset (dict of tensors / arrays) or of a map-style dataset of dict samples.  With a ``transform``
+    (``training.preprocess.DevicePanoramaTransform``) the ``images`` column -- per row a list of views: JPEG file bytes, raw images or ``None`` -- stays a Python
+    list and becomes ``pixel_values`` through it."""
+    if transform is None:
+        if isinstance(ds, dict):
+            return {k: torch.as_tensor(np.asarray(v))[idx] if not torch.is_tensor(v) else v[idx] for k, v in ds.items()}
+        rows = [ds[int(i)] for i in idx]
+        return {k: torch.stack([torch.as_tensor(r[k]) for r in rows]) for k in rows[0]}
     if isinstance(ds, dict):
-        return {k: torch.as_tensor(np.asarray(v))[idx] if not torch.is_tensor(v) else v[idx] for k, v in ds.items()}
-    rows = [ds[int(i)] for i in idx]
-    return {k: torch.stack([torch.as_tensor(r[k]) for r in rows]) for k in rows[0]}
+        images = [ds["images"][int(i)] for i in idx]
+        data = _take({k: v for k, v in ds.items() if k != "images"}, idx)
+    else:
+        rows = [ds[int(i)] for i in idx]
+        images = [r["images"] for r in rows]
+        data = {k: torch.stack([torch.as_tensor(r[k]) for r in rows]) for k in rows[0] if k != "images"}
+    data["pixel_values"] = transform(images)
+    return data
 
 
 def _shard(n: int, shuffle: bool, seed: int, rank: int, world: int) -> torch.Tensor:
@@ -77,10 +89,10 @@ def _num_batches(n: int, batch_size: int, world: int) -> int:
     return (per + batch_size - 1) // batch_size
 
 
-def _batches(ds, batch_size: int, shuffle: bool, seed: int, rank: int, world: int):
+def _batches(ds, batch_size: int, shuffle: bool, seed: int, rank: int, world: int, transform=None):
     mine = _shard(_num_rows(ds), shuffle, seed, rank, world)
     for i in range(0, len(mine), batch_size):
-        yield _take(ds, mine[i:i + batch_size])
+        yield _take(ds, mine[i:i + batch_size], transform)
 
 
 MODEL_KEYS = ("pixel_values", "embedding", "labels", "labels_clf", "index")
@@ -95,8 +107,8 @@ def _gather_rows(arrays, rank: int, world: int):
     return [np.concatenate([b[i] for b in box], 0) for i in range(len(arrays))]
 
 
-def evaluate_model(model, dataset, metrics: Callable, train_args, refiner=None, writer=None, step: int = 0) -> float:
-    """Reference contract (:37-155): returns ``-metrics(results)["Geocell_accuracy"]`` with
+def evaluate_model(model, dataset, metrics: Callable, train_args, refiner=None, writer=None, step: int = 0, transform=None) -> float:
+    """``transform``: see ``train_model``.  Reference contract (:37-155): returns ``-metrics(results)["Geocell_accuracy"]`` with
     ``results = (preds_LLH, preds_geocell, top5_geocells, labels_lla, labels_cell)`` over the WHOLE validation set in dataset
     order.  Under data parallelism each rank evaluates one contiguous slice and the slices are all-gathered (the reference
     has every rank evaluate everything, :62-68 -- same numbers, world times the work)."""
@@ -113,7 +125,7 @@ def evaluate_model(model, dataset, metrics: Callable, train_args, refiner=None, 
     loss_sum, n_seen = 0.0, 0
     with torch.no_grad():
         for s0 in range(lo, hi, ebs):
-            data = _take(dataset, torch.arange(s0, min(hi, s0 + ebs)))
+            data = _take(dataset, torch.arange(s0, min(hi, s0 + ebs)), transform)
             outputs = model(**{k: v for k, v in data.items() if k in MODEL_KEYS})
             bs = _num_rows(data)
             if outputs.loss is not None:
@@ -149,8 +161,10 @@ def evaluate_model(model, dataset, metrics: Callable, train_args, refiner=None, 
 
 def train_model(loaded_model: Any, dataset, on_embeddings: bool, train_args, metrics: Callable, patience: int = None,
                 should_profile: bool = True, refiner=None, log_fn: Optional[Callable] = None, save_path: str = CURRENT_SAVE_PATH,
-                broadcast_buffers: bool = True):
-    """Reference contract (:158-274; ``should_profile`` defaults to True as there, :165: the torch.profiler schedule of ``generate_profiler`` writes its
+                broadcast_buffers: bool = True, transform=None):
+    """``transform`` (a ``training.preprocess.DevicePanoramaTransform``; None, the default, changes nothing): the datasets hold an ``images`` column -- per row the
+    list of a panorama's views as JPEG file bytes, raw images or ``None`` -- instead of ``pixel_values``; every batch's list goes through the transform on the device.
+    Reference contract (:158-274; ``should_profile`` defaults to True as there, :165: the torch.profiler schedule of ``generate_profiler`` writes its
     traces under ``runs/profile``).  DDP start-up semantics of ``accelerator.prepare`` (:200-202) are kept: parameters and
     buffers are broadcast from rank 0 once, BatchNorm running statistics are re-broadcast from rank 0 before every training
     forward (``DistributedDataParallel(broadcast_buffers=True)``, the default), gradients are summed over ranks before each
@@ -173,7 +187,7 @@ def train_model(loaded_model: Any, dataset, on_embeddings: bool, train_args, met
         model.train()
         optimizer.zero_grad()
         for epoch in range(int(train_args.num_train_epochs)):
-            for i, data in enumerate(_batches(dataset["train"], bs, True, getattr(train_args, "seed", 0) + epoch, rank, world)):
+            for i, data in enumerate(_batches(dataset["train"], bs, True, getattr(train_args, "seed", 0) + epoch, rank, world, transform)):
                 last = i % grad_acc_steps == (grad_acc_steps - 1) or (i + 1) == steps
                 if broadcast_buffers:
                     optimizer.broadcast_buffers()
@@ -188,7 +202,7 @@ def train_model(loaded_model: Any, dataset, on_embeddings: bool, train_args, met
                     log_fn("Loss/train", float(output.loss), epoch * steps + i)
                 if prof is not None:
                     prof.step()
-            eval_loss = evaluate_model(model, dataset["val"], metrics, train_args, refiner, log_fn, epoch)
+            eval_loss = evaluate_model(model, dataset["val"], metrics, train_args, refiner, log_fn, epoch, transform)
             if prior_eval_loss is None or eval_loss < prior_eval_loss:
                 if world > 1:
                     dist.barrier()
