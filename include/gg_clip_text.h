@@ -52,10 +52,15 @@ int gg_clip_text_forward(const GgClipTextCfg* cfg, int batch, int tokens, const 
 /* ---------------------------------------------------------------- contrastive head (transformers CLIPModel.forward after the projections; clip_loss)
  * img [Bi][P], txt [Bt][P]: f32 projection outputs, not normalised (row pitch ldi / ldt, multiples of 4).  Forward:
  *   img_n = img / |img|, txt_n = txt / |txt| (rows), logits_per_text [Bt][Bi] = exp(*logit_scale) * txt_n . img_n^T, logits_per_image its transpose.
- * want_loss (needs Bi == Bt == B): loss = (CE_rows + CE_cols) / 2 against the diagonal (row / column log-sum-exp in f32), and the gradients of
+ * want_loss (needs Bi == Bt == B): loss = (CE_rows + CE_cols) / 2 against the diagonal, and the gradients of
  * d_loss_scale * loss:  dS = (softmax_rows + softmax_cols - 2 I) / (2B);  d_logit_scale = sum dS o S;  d txt_n = exp(ls) dS . img_n,
  * d img_n = exp(ls) dS^T . txt_n;  through the normalisation dx = (dn - n (n . dn)) / |x|  ->  d_txt [Bt][P], d_img [Bi][P] (contiguous; either may be NULL).
- * The two B x B x P products and the gradient products are gg_gemm_nt_f32 launches; the reductions are fixed-order trees (no atomics: two calls
+ * Log-softmax is formed as torch forms it, (s - max) - log(sum exp(s - max)): the row / column maxima and the logs of the sums are kept as separate vectors
+ * (their f32 sum would be an ulp of the maximum off, 7.6e-6 at a logit of 100), the sum of the f32 exponentials and its log are taken in double, a softmax term
+ * is exp((s - max) - logsum), on the diagonal dS is expm1 + expm1, and a row's loss is (logsum_r - (s_rr - max_r)) + (logsum_c - (s_rr - max_c)).
+ * exp(*logit_scale) is the double exponential rounded once.  A row's norm is summed in double and the row divided by it there, every element of img_n / txt_n
+ * rounded once; the cosines are sums in double of the (exact) products of those f32 elements, times exp(ls), rounded once.
+ * The gradient products are gg_gemm_nt_f32 launches; the reductions are fixed-order trees (no atomics: two calls
  * give the same bits).  scratch: gg_clip_contrastive_scratch_floats(Bi, Bt, P) floats, 16-byte aligned. */
 typedef struct GgContrastiveArgs {
     const float* img; int64_t ldi;
