@@ -164,7 +164,6 @@ SIGNATURES = {
     "gg_col2im_nhwc_bnbwd_bf16": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     "gg_col2im_nhwc_bnbwd_f32": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     "gg_dwconv_stat_rows": (_I, [_I, _I, _I, _I, _I]),
-    "gg_dwconv_tiled_stat_rows": (_I, [_I, _I]),
     "gg_dwconv_fused_stat_rows": (_I, [_I, _I, _I, _I, _I]),
     "gg_dwconv_fwd_fused_stat_rows": (_I, [_I, _I, _I, _I, _I]),
     "gg_dwconv3x3_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),

@@ -171,19 +171,19 @@ __global__ __launch_bounds__(256) void col2im_nhwc_kernel(const bf16* __restrict
     }
 }
 
-// ---------------------------------------------------------------- column-walking depthwise 3x3 (stride 1)
-// Thread = (8 channels, one output column); the block covers PX adjacent columns x all C channels and walks down the whole
-// image.  Lanes run over channels first, then columns, so every wave-level access is one contiguous run of the NHWC row
-// (16 bytes per lane, full cache lines) -- the LDS-tiled kernel's 128-byte channel chunks at a C*2-byte stride reached only
-// 2.8 TB/s.  A 3x3 input window lives in registers as fp32; each step loads the three columns of one new input row (the
-// left / right neighbours come out of L1: HBM sees every input byte once), rotates the window by renaming (the loop is
-// unrolled by 3) and emits one output row.  Rows / columns outside the image are zero through the buffer range check.
+// ---------------------------------------------------------------- column-walking depthwise 3x3: what the walkers share
+// A walking kernel's block covers PX adjacent output columns x all C channels of one image and walks down it with the input
+// window in registers as fp32: each step loads one new input row (the left / right neighbours come out of L1: HBM sees every
+// input byte once), rotates the window by renaming (the loop is unrolled over the row slots) and emits one output row.
+// Rows / columns outside the image are zero through the buffer range check, branch-free: an invalid column carries bit 31, an
+// invalid row adds bit 30; either pushes the offset past the (< 1 GiB) descriptor, and no combination wraps back into range.
+// (Branches around the loads made the compiler wait for ALL outstanding loads at the join, which serialised the row prefetch.)
 // colstats: one row per block, [gridDim.x][2][C] = per-channel sum / sum of squares of the stored (bf16-rounded) result.
 typedef unsigned int dw_u32x4 __attribute__((ext_vector_type(4)));
 #define DW_COL_OOB 0x80000000u
 #define DW_ROW_OOB 0x40000000u
-// NQ channel pairs per thread: 4 (16-byte accesses; the plain kernel) or 2 (8-byte accesses; the fused backward kernels, whose
-// per-channel state does not fit the register file at 8 channels per thread -- measured 2.8 ms vs 1.9 ms at 56x56x384)
+// NQ channel pairs per thread: 4 (16-byte accesses; the stride-2 forward) or 2 (8-byte accesses; the stride-1 multi-column kernel and
+// the weight-gradient walk, whose per-channel state does not fit the register file at 8 channels per thread)
 template <int NQ> struct DwRaw;
 template <> struct DwRaw<4> {
     typedef unsigned int T __attribute__((ext_vector_type(4)));
@@ -203,7 +203,6 @@ __device__ __forceinline__ unsigned dw_pack2(f32x2 v) {
 //         from (dz, y) while loading -- the separate apply pass and the dy tensor disappear;
 //   EPI : the stored value is  acc * act'(BN(ep_y))  = gradient w.r.t. the pre-activation of the ConvNorm IN FRONT, and colstats
 //         becomes (sum dz, sum dz*xhat): that ConvNorm's "reduce" pass disappears.
-// The per-channel coefficient tables sit in LDS (they are touched once per row; registers go to the window and the taps).
 // Window element: fp32 pairs, or (IN2) the packed bf16 pair the unfused path would have stored in dy, unpacked at use.
 template <bool PACKED> struct DwWin;
 template <> struct DwWin<false> {
@@ -221,201 +220,20 @@ struct DwWalkFuse {
     const bf16* in2; const float* in_coef;                                         // IN2
     const bf16* ep_y; const float* ep_stat; const float* ep_gamma; const float* ep_beta; int ep_act;   // EPI
 };
-template <int IN, bool EPI, int NQ>
-__global__ __launch_bounds__(256, NQ == 4 ? 2 : 3) void dwconv3x3_walk_kernel(const bf16* __restrict__ x, const float* __restrict__ wt,
-                                                                              bf16* __restrict__ y, int H, int W, int C, int CG, int PX, int nbx,
-                                                                              int flip, float* __restrict__ colstats, DwWalkFuse f) {
-    constexpr bool IN2 = IN == 2;              // backward: BatchNorm-backward apply of (x, in2) while loading
-    constexpr bool IN1 = IN == 1;              // forward: act(BatchNorm(x)) of the producer ConvNorm while loading (ctab rows 0 / 1 = scale / shift)
-    typedef typename DwRaw<NQ>::T Raw;
-    typedef typename DwWin<IN == 2>::E WinE;
-    constexpr int NC = 2 * NQ;                 // channels per thread
-    extern __shared__ float dw_red[];          // [PX][2][C] statistics scratch; then (fusions) 16 coefficient rows [C]
-    float* ctab = dw_red + PX * 2 * C;         // [0..2] in coef a,b,c   [3] ep scale  [4] ep shift  [5] ep rstd  [6] ep -mean*rstd  [7..15] taps
-    constexpr bool TAPS_LDS = IN != 0 || EPI;      // the fused variants have no registers left for the tap values
-    const int cg = threadIdx.x % CG, px = threadIdx.x / CG;
-    // the strips of one image are neighbours in the logical block order, and that order is laid out XCD by XCD: the halo columns a
-    // strip shares with the next one are then served by the same L2 (round-robin dispatch put them on different XCDs and every
-    // strip fetched its halo from HBM again: measured 1.85x the algorithmic read traffic)
-    const int bid = gg_xcd_remap(blockIdx.x, gridDim.x);
-    const int bx = bid % nbx, b = bid / nbx;
-    const int xo = bx * PX + px;
-    const int c0 = cg * NC;
-    if (IN != 0 || EPI) {
-        for (int c = threadIdx.x; c < C; c += blockDim.x) {
-            if (IN2) { ctab[c] = f.in_coef[c]; ctab[C + c] = f.in_coef[C + c]; ctab[2 * C + c] = f.in_coef[2 * C + c]; }
-            if (IN1) { const float sc = f.in_stat[C + c] * f.in_gamma[c]; ctab[c] = sc; ctab[C + c] = f.in_beta[c] - f.in_stat[c] * sc; }
-            if (EPI) {
-                const float mu = f.ep_stat[c], rstd = f.ep_stat[C + c], sc = rstd * f.ep_gamma[c];
-                ctab[3 * C + c] = sc; ctab[4 * C + c] = f.ep_beta[c] - mu * sc; ctab[5 * C + c] = rstd; ctab[6 * C + c] = -mu * rstd;
-            }
-#pragma unroll
-            for (int t = 0; t < 9; ++t) ctab[(7 + t) * C + c] = wt[(flip ? 8 - t : t) * C + c];
-        }
-        __syncthreads();
-    }
-    // `cofs` is laundered through an empty asm once per row step: the table reads are loop-invariant, and hoisting them would
-    // put all 16 rows back into registers
-    int cofs = c0;
-    auto ctab2 = [&](int row, int q) { return *reinterpret_cast<const f32x2*>(ctab + row * C + cofs + 2 * q); };
-    f32x2 tap[TAPS_LDS ? 1 : 9][NQ];
-    if (!TAPS_LDS) {
-#pragma unroll
-        for (int t = 0; t < (TAPS_LDS ? 1 : 9); ++t)
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) tap[t][q] = *reinterpret_cast<const f32x2*>(wt + (flip ? 8 - t : t) * C + c0 + 2 * q);
-    }
-    const int64_t img = (int64_t)b * H * W * C;
-    // (the image bases are block-uniform; saying so keeps the descriptors in SGPRs -- otherwise every buffer load is wrapped in a
-    // waterfall loop over "divergent" descriptors)
-    auto uniform_ptr = [](const bf16* ptr) {
-        const unsigned long long a = (unsigned long long)ptr;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-        return (void*)(((unsigned long long)hi << 32) | lo);
-    };
-    const int img_bytes = __builtin_amdgcn_readfirstlane(H * W * C * 2);
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(x + img), 0, img_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr((IN2 ? f.in2 : x) + img), 0, img_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rse = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr((EPI ? f.ep_y : x) + img), 0, img_bytes, 0x00020000);
-    // byte offsets of the three columns inside a row
-    unsigned colo[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int ix = xo + k - 1;
-        colo[k] = (ix >= 0 && ix < W && xo < W) ? (unsigned)(ix * C + c0) * 2u : DW_COL_OOB;
-    }
-    const unsigned rowb = (unsigned)W * C * 2u;
-    // branch-free addressing: an invalid column carries bit 31, an invalid row adds bit 30; either pushes the offset past the
-    // (< 1 GiB) descriptor, and no combination wraps back into range.  (Branches around the loads made the compiler wait for
-    // ALL outstanding loads at the join, which serialised the row prefetch.)
-    auto load_row = [&](int iy, Raw (&raw)[3], Raw (&raw2)[3]) {
-        const unsigned ro = (iy >= 0 && iy < H) ? (unsigned)iy * rowb : DW_ROW_OOB;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const int vo = (int)(colo[k] + ro);
-            raw[k] = DwRaw<NQ>::load(rs, vo);
-            if (IN2) raw2[k] = DwRaw<NQ>::load(rs2, vo);
-        }
-    };
-    // raw row -> window slot; IN2: the BatchNorm-backward apply on the way (positions outside the image stay exactly 0)
-    auto fill = [&](int iy, const Raw (&raw)[3], const Raw (&raw2)[3], WinE (&slot)[3][NQ]) {
-        if constexpr (IN == 0) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-#pragma unroll
-                for (int q = 0; q < NQ; ++q) slot[k][q] = dw_unpack2(raw[k][q]);
-        } else if constexpr (IN1) {
-            const bool rok = iy >= 0 && iy < H;
-            const bool in_gelu = f.in_act == GG_ACT_GELU;
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const f32x2 sc = ctab2(0, q), sh = ctab2(1, q);
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    // the bf16 rounding of the activation tensor the unfused path stores is kept (same numerics)
-                    const f32x2 r = gg_act_v2(dw_unpack2(raw[k][q]) * sc + sh, in_gelu);
-                    slot[k][q] = (rok && colo[k] != DW_COL_OOB) ? dw_unpack2(dw_pack2(r)) : (f32x2)(0.f);
-                }
-            }
-        } else {
-            const bool rok = iy >= 0 && iy < H;
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const f32x2 ca = ctab2(0, q), cb = ctab2(1, q), cc = ctab2(2, q);
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const f32x2 r = ca * dw_unpack2(raw[k][q]) + (cb * dw_unpack2(raw2[k][q]) + cc);
-                    slot[k][q] = (rok && colo[k] != DW_COL_OOB) ? dw_pack2(r) : 0u;
-                }
-            }
-        }
-    };
-    WinE win[3][3][NQ];           // [row slot][column][channel pair]
-    Raw raw[3], raw2[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) win[0][k][q] = DwWin<IN == 2>::zero();          // row -1
-    load_row(0, raw, raw2);
-    fill(0, raw, raw2, win[1]);
-    load_row(1, raw, raw2);
-    f32x2 s2[NQ], q2[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) s2[q] = q2[q] = (f32x2)(0.f);
-    bf16* yb = y + img + (int64_t)xo * C + c0;
-    const bool store_ok = xo < W;
-    const unsigned ctr = store_ok ? (unsigned)(xo * C + c0) * 2u : DW_COL_OOB;
-    const bool ep_gelu = f.ep_act == GG_ACT_GELU;
-    Raw eraw;
-    if (EPI) eraw = DwRaw<NQ>::load(rse, (int)ctr);
-    // one output row: slot RC receives input row yy+1 (already in flight), rows yy-1 / yy sit in slots RA / RB
-#define GG_DW_STEP(RA, RB, RC, yy)                                                                                         \
-    {                                                                                                                      \
-        if (IN != 0 || EPI) asm volatile("" : "+v"(cofs));                                                                     \
-        fill((yy) + 1, raw, raw2, win[RC]);                                                                                \
-        load_row((yy) + 2, raw, raw2);                                                                                     \
-        const float live = (yy) < H ? 1.f : 0.f;                                                                           \
-        f32x2 acc[NQ];                                                                                                     \
-        _Pragma("unroll") for (int q = 0; q < NQ; ++q) {                                                                   \
-            f32x2 a = (f32x2)(0.f);                                                                                        \
-            _Pragma("unroll") for (int t = 0; t < 9; ++t) {                                                                \
-                const int rsl = t < 3 ? RA : (t < 6 ? RB : RC);                                                            \
-                const f32x2 tp = TAPS_LDS ? ctab2(7 + t, q) : tap[TAPS_LDS ? 0 : t][q];                                    \
-                a = DwWin<IN == 2>::get(win[rsl][t % 3][q]) * tp + a;                                                          \
-            }                                                                                                              \
-            acc[q] = a;                                                                                                    \
-        }                                                                                                                  \
-        Raw o;                                                                                                             \
-        if (EPI) {                                                                                                         \
-            const Raw ycur = eraw;                                                                                         \
-            eraw = DwRaw<NQ>::load(rse, (int)(ctr + ((yy) + 1 < H ? (unsigned)((yy) + 1) * rowb : DW_ROW_OOB)));          \
-            _Pragma("unroll") for (int q = 0; q < NQ; ++q) {       /* one channel pair at a time: short live ranges */      \
-                const f32x2 yv = dw_unpack2(ycur[q]);                                                                      \
-                const f32x2 dz = acc[q] * gg_act_grad_v2(yv * ctab2(3, q) + ctab2(4, q), ep_gelu);                         \
-                o[q] = dw_pack2(dz);                                                                                       \
-                const f32x2 r = dw_unpack2(o[q]) * live;                                                                   \
-                s2[q] += r; q2[q] += r * (yv * ctab2(5, q) + ctab2(6, q));                                                 \
-            }                                                                                                              \
-        } else {                                                                                                           \
-            _Pragma("unroll") for (int q = 0; q < NQ; ++q) {                                                               \
-                o[q] = dw_pack2(acc[q]);                                                                                   \
-                const f32x2 r = dw_unpack2(o[q]) * live;                                                                   \
-                s2[q] += r; q2[q] += r * r;                                                                                \
-            }                                                                                                              \
-        }                                                                                                                  \
-        if (store_ok && (yy) < H) *reinterpret_cast<Raw*>(yb + (int64_t)(yy) * W * C) = o;                                 \
-    }
-    // (the tail of the last trip may run 1-2 rows past the image: its loads are out of range, its store and statistics masked)
-    for (int y0 = 0; y0 < H; y0 += 3) {
-        GG_DW_STEP(0, 1, 2, y0)
-        GG_DW_STEP(1, 2, 0, y0 + 1)
-        GG_DW_STEP(2, 0, 1, y0 + 2)
-    }
-#undef GG_DW_STEP
-    if (colstats) {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            // columns beyond the image produced zeros (all inputs out of range): they add nothing
-            dw_red[(px * 2 + 0) * C + c0 + 2 * q] = s2[q].x; dw_red[(px * 2 + 0) * C + c0 + 2 * q + 1] = s2[q].y;
-            dw_red[(px * 2 + 1) * C + c0 + 2 * q] = q2[q].x; dw_red[(px * 2 + 1) * C + c0 + 2 * q + 1] = q2[q].y;
-        }
-        __syncthreads();
-        for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) {
-            float t = 0.f;
-            for (int k = 0; k < PX; ++k) t += dw_red[k * 2 * C + i];
-            colstats[(int64_t)blockIdx.x * 2 * C + i] = t;
-        }
-    }
-}
 
-// ---------------------------------------------------------------- stride-1 walk, NCOL output columns per thread, producer BatchNorm + activation on load
-// MBConv.conv2 over GELU(BN1(y1)): with one column per thread every input element is transformed by the three threads whose windows
-// contain it (the IN = 1 variant of the kernel above: 2.6 ms against 1.24 + 1.0 ms for plain conv + apply pass).  Here a thread owns
-// NCOL adjacent columns x 4 channels: NCOL + 2 loads and transforms per row step for NCOL results -- 1.5 evaluations per element at
-// NCOL = 4 -- and the apply pass with its 2 x [M, C] of traffic disappears.  Forward only; statistics as in the other walkers.
-// IN = 0 plain / 1 producer BatchNorm + activation (forward) / 2 BatchNorm-backward apply of (x, in2) (data gradient); EPI: the stored value
-// is acc * act'(BN(ep_y)) and the statistics are (sum dz, sum dz*xhat) -- the same fusions as dwconv3x3_walk_kernel, whose stride-1 uses
-// this kernel takes over: every per-element transform on the way in runs 1.5 instead of 3 times, and a result costs 1.5 instead of 3 loads.
+// ---------------------------------------------------------------- stride-1 walk, NCOL output columns per thread (every stride-1 forward and data gradient)
+// Thread = (4 channels, NCOL adjacent output columns); the block covers PX such column groups x all C channels and walks down the whole
+// image.  Lanes run over channels first, then columns, so every wave-level access is one contiguous run of the NHWC row (full cache
+// lines); channel chunks at a C*2-byte stride reached only 2.8 TB/s.  The strips of one image are neighbours in the logical block order,
+// and gg_xcd_remap lays that order out XCD by XCD: the halo columns a strip shares with the next one are then served by the same L2
+// (round-robin dispatch put them on different XCDs and every strip fetched its halo from HBM again: measured 1.85x the algorithmic
+// read traffic).  The image bases are block-uniform, and saying so (readfirstlane) keeps the buffer descriptors in SGPRs -- otherwise
+// every buffer load is wrapped in a waterfall loop over "divergent" descriptors.
+// A thread issues NCOL + 2 loads per row step for NCOL results: 1.5 loads per result at NCOL = 4 where one column per thread costs 3,
+// and whatever rides on the load runs 1.5 instead of 3 times per input element (MBConv.conv2 over GELU(BN1(y1)) with one column per
+// thread: 2.6 ms against 1.24 + 1.0 ms for plain conv + apply pass).
+// IN = 0 plain / 1 producer BatchNorm + activation (forward: the apply pass with its 2 x [M, C] of traffic disappears) / 2 BatchNorm-backward
+// apply of (x, in2) (data gradient); EPI: the stored value is acc * act'(BN(ep_y)) and the statistics are (sum dz, sum dz*xhat).
 // `flip` reverses the taps (data gradient).  Per-channel coefficients live in registers (4 channels per thread).
 template <int NCOL, int IN, bool EPI>
 __global__ __launch_bounds__(256, 2) void dwconv3x3_s1_multi_kernel(const bf16* __restrict__ x, const float* __restrict__ wt, bf16* __restrict__ y,
@@ -576,7 +394,7 @@ __global__ __launch_bounds__(256, 2) void dwconv3x3_s1_multi_kernel(const bf16* 
 // ---------------------------------------------------------------- stride-2 column-walking depthwise 3x3 (PatchMerging.conv2 forward)
 // thread = (8 channels, one OUTPUT column), walking down the output rows: output row oy needs input rows 2oy-1 .. 2oy+1, of which
 // 2oy-1 was the last row of the previous step -> two new input rows x three columns per step (6 x 16-byte loads for a 16-byte
-// result; the LDS-tiled kernel staged 17x17 inputs per 8x8 outputs through LDS and ran at 3.6 TB/s).  IN1: the input is the saved
+// result; staging 17x17 inputs per 8x8 outputs through LDS ran at 3.6 TB/s).  IN1: the input is the saved
 // pre-BatchNorm output of the ConvNorm in front and act(BatchNorm(x)) is applied to every loaded element (bf16-rounded like the
 // stored activation; 1.5 evaluations per input element instead of a 2 x [M, C] apply pass); padding stays exactly zero.
 // BatchNorm partial statistics of the bf16-rounded result: one row per block in colstats [gridDim.x][2][C].
@@ -692,179 +510,6 @@ __global__ __launch_bounds__(256, 2) void dwconv3x3_s2_walk_kernel(const bf16* _
             float t = 0.f;
             for (int k = 0; k < PX; ++k) t += dw2_red[k * 2 * C + i];
             colstats[(int64_t)blockIdx.x * 2 * C + i] = t;
-        }
-    }
-}
-
-// ---------------------------------------------------------------- LDS-tiled depthwise 3x3
-// Block = (image, band of 8 output rows, chunk of 64 channels); it walks the band in 8-pixel-wide tiles.  The input
-// tile (+halo) is staged once in LDS (next tile prefetched through registers), so HBM sees every input byte once and
-// each output costs 9 LDS reads instead of 9 global loads.  Optional fused producer: the staged values are
-// act(gamma*(x-mean)*rstd+beta) of the previous ConvNorm (BatchNorm + GELU applied on the fly; zero padding stays
-// zero), which removes the separate bn_apply pass and its 2 x [M,C] of traffic.  `flip` reverses the taps (= the
-// data gradient of a stride-1 depthwise conv).  Per-channel sum / sum-of-squares of the result (BatchNorm partials) are
-// written as one row per (image, band): colstats[row][2][C].
-// MODE 0: plain (forward / flipped-tap data gradient); 1: fused producer BN+act while staging; 2: backward fusions
-// (2-input staging and/or act'(BN) epilogue).  Compile-time so that the plain kernel keeps its register budget.
-template <int S, int MODE>
-__global__ __launch_bounds__(256) void dwconv3x3_tiled_kernel(const bf16* __restrict__ x, const float* __restrict__ wt,
-                                                              bf16* __restrict__ y, int B, int H, int W, int C, int Ho, int Wo,
-                                                              int nbands, int nchunks, int flip, const float* __restrict__ in_stat,
-                                                              const float* __restrict__ in_gamma, const float* __restrict__ in_beta,
-                                                              int in_act, float* __restrict__ colstats,
-                                                              const bf16* __restrict__ in2, const float* __restrict__ in_coef,
-                                                              const bf16* __restrict__ ep_y, const float* __restrict__ ep_stat,
-                                                              const float* __restrict__ ep_gamma, const float* __restrict__ ep_beta,
-                                                              int ep_act) {
-    // backward-pass fusions (both optional):
-    //  in2/in_coef : the staged value is  coef0*x + coef1*in2 + coef2  = BatchNorm-backward "apply" of the ConvNorm BEHIND this
-    //                conv, formed on the fly from (dz, y) -- the separate apply pass and the dy tensor disappear;
-    //  ep_*        : the stored value is  acc * act'(BN(ep_y))  = gradient w.r.t. the pre-activation of the ConvNorm IN FRONT,
-    //                and colstats becomes (sum dz, sum dz*xhat): that ConvNorm's BatchNorm-backward "reduce" pass disappears.
-    // thread = (channel quad g of 16, pixel slot ps of 16): 4 channels (8-byte accesses) keep the 9x4 taps, the
-    // accumulators and the prefetched chunks within ~100 VGPRs
-    constexpr int TH = 8, TW = 8, CT = 64, Q = 4, NG = CT / Q;
-    constexpr int IH = (TH - 1) * S + 3, IW = (TW - 1) * S + 3;
-    constexpr int NCH = IH * IW * NG;
-    constexpr int LPT = (NCH + 255) / 256;
-    __shared__ __attribute__((aligned(16))) bf16 tile[IH * IW * CT];
-    const int cc = blockIdx.x % nchunks;
-    const int band = (blockIdx.x / nchunks) % nbands;
-    const int b = blockIdx.x / (nchunks * nbands);
-    const int c0 = cc * CT;
-    const int g = threadIdx.x & (NG - 1), ps = threadIdx.x / NG;
-    const int cg0 = c0 + g * Q;
-    const bool cok = cg0 < C;                       // C % 8 == 0; the last chunk may be partial (C % 64 != 0)
-    float wreg[9][Q];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int j = 0; j < Q; ++j) wreg[t][j] = cok ? wt[(flip ? 8 - t : t) * C + cg0 + j] : 0.f;
-    float sc[Q], sh[Q], s2[Q];
-    const bool fused = MODE == 1 && in_stat != nullptr, fused2 = MODE == 2 && in_coef != nullptr;
-#pragma unroll
-    for (int j = 0; j < Q; ++j) {
-        sc[j] = (fused && cok) ? in_stat[C + cg0 + j] * in_gamma[cg0 + j] : 1.f;
-        sh[j] = (fused && cok) ? in_beta[cg0 + j] - in_stat[cg0 + j] * sc[j] : 0.f;
-        s2[j] = 0.f;
-        if (fused2 && cok) { sc[j] = in_coef[cg0 + j]; s2[j] = in_coef[C + cg0 + j]; sh[j] = in_coef[2 * C + cg0 + j]; }
-    }
-    float esc[Q], esh[Q], ers[Q], emr[Q];
-    const bool epi = MODE == 2 && ep_y != nullptr;
-#pragma unroll
-    for (int j = 0; j < Q; ++j) {
-        ers[j] = (epi && cok) ? ep_stat[C + cg0 + j] : 0.f;
-        emr[j] = (epi && cok) ? ep_stat[cg0 + j] * ers[j] : 0.f;
-        esc[j] = (epi && cok) ? ers[j] * ep_gamma[cg0 + j] : 0.f;
-        esh[j] = (epi && cok) ? ep_beta[cg0 + j] - ep_stat[cg0 + j] * esc[j] : 0.f;
-    }
-    const bf16* x2b = in2 ? in2 + (int64_t)b * H * W * C : nullptr;
-    const int oy0 = band * TH;
-    const int iy0 = oy0 * S - 1;
-    const bf16* xb = x + (int64_t)b * H * W * C;
-    bf16x4 pre[LPT];
-    const bf16x4 zero4 = {0, 0, 0, 0};
-    auto load_tile = [&](int ox0) {
-        const int ix0 = ox0 * S - 1;
-#pragma unroll
-        for (int i = 0; i < LPT; ++i) {
-            const int ch = threadIdx.x + i * 256;            // chunk = (pixel, channel quad): quad == g for every i
-            const int pix = ch / NG;
-            const int py = pix / IW, px = pix - py * IW;
-            const int iy = iy0 + py, ix = ix0 + px;
-            bf16x4 v = zero4;
-            if (ch < NCH && cok && iy >= 0 && iy < H && ix >= 0 && ix < W) {
-                v = *reinterpret_cast<const bf16x4*>(xb + ((int64_t)iy * W + ix) * C + cg0);
-                if (fused2) {
-                    const bf16x4 w2 = *reinterpret_cast<const bf16x4*>(x2b + ((int64_t)iy * W + ix) * C + cg0);
-#pragma unroll
-                    for (int j = 0; j < Q; ++j) v[j] = (bf16)fmaf(sc[j], (float)v[j], fmaf(s2[j], (float)w2[j], sh[j]));
-                } else if (fused) {
-#pragma unroll
-                    for (int j = 0; j < Q; ++j) v[j] = (bf16)gg_act((float)v[j] * sc[j] + sh[j], in_act);
-                }
-            }
-            pre[i] = v;
-        }
-    };
-    float s[Q], q[Q];
-#pragma unroll
-    for (int j = 0; j < Q; ++j) s[j] = q[j] = 0.f;
-    const int ntx = (Wo + TW - 1) / TW;
-    load_tile(0);
-    for (int tx = 0; tx < ntx; ++tx) {
-#pragma unroll
-        for (int i = 0; i < LPT; ++i) {
-            const int ch = threadIdx.x + i * 256;
-            if (ch < NCH) *reinterpret_cast<bf16x4*>(tile + ch * Q) = pre[i];
-        }
-        __syncthreads();
-        if (tx + 1 < ntx) load_tile((tx + 1) * TW);
-        // fused epilogue: y of the NEXT output pixel is fetched while the current one is computed
-        auto ep_load = [&](int pi) {
-            const int p = ps + 16 * pi;
-            const int oy = oy0 + (p >> 3), ox = tx * TW + (p & 7);
-            return (oy < Ho && ox < Wo && cok) ? *reinterpret_cast<const bf16x4*>(ep_y + (((int64_t)b * Ho + oy) * Wo + ox) * C + cg0) : zero4;
-        };
-        bf16x4 ep_next = zero4;
-        if (epi) ep_next = ep_load(0);
-#pragma unroll 1
-        for (int pi = 0; pi < (TH * TW) / 16; ++pi) {
-            const bf16x4 ep_cur = ep_next;
-            if (epi && pi + 1 < (TH * TW) / 16) ep_next = ep_load(pi + 1);
-            const int p = ps + 16 * pi;
-            const int oyl = p >> 3, oxl = p & 7;
-            const int oy = oy0 + oyl, ox = tx * TW + oxl;
-            float acc[Q] = {0, 0, 0, 0};
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    const bf16x4 v = *reinterpret_cast<const bf16x4*>(tile + ((oyl * S + ky) * IW + oxl * S + kx) * CT + g * Q);
-#pragma unroll
-                    for (int j = 0; j < Q; ++j) acc[j] += (float)v[j] * wreg[ky * 3 + kx][j];
-                }
-            if (oy < Ho && ox < Wo && cok) {
-                bf16x4 o;
-                const int64_t oidx = (((int64_t)b * Ho + oy) * Wo + ox) * C + cg0;
-                if (epi) {
-                    const bf16x4 yv = ep_cur;
-#pragma unroll
-                    for (int j = 0; j < Q; ++j) {
-                        const float yy = (float)yv[j];
-                        const float dzv = acc[j] * gg_act_grad(fmaf(esc[j], yy, esh[j]), ep_act);
-                        o[j] = (bf16)dzv;
-                        s[j] += dzv;
-                        q[j] += dzv * fmaf(ers[j], yy, -emr[j]);
-                    }
-                } else {
-#pragma unroll
-                    for (int j = 0; j < Q; ++j) {
-                        o[j] = (bf16)acc[j];
-                        const float r = (float)o[j];       // statistics of the stored value
-                        s[j] += r;
-                        q[j] += r * r;
-                    }
-                }
-                *reinterpret_cast<bf16x4*>(y + oidx) = o;
-            }
-        }
-        __syncthreads();
-    }
-    if (colstats) {
-        float* red = reinterpret_cast<float*>(tile);        // [16 slots][2][64]  (8 KiB <= tile)
-#pragma unroll
-        for (int j = 0; j < Q; ++j) {
-            red[(ps * 2 + 0) * CT + g * Q + j] = s[j];
-            red[(ps * 2 + 1) * CT + g * Q + j] = q[j];
-        }
-        __syncthreads();
-        if (threadIdx.x < 2 * CT) {
-            const int which = threadIdx.x / CT, col = threadIdx.x % CT;
-            float t = 0.f;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) t += red[(k * 2 + which) * CT + col];
-            if (c0 + col < C) colstats[((int64_t)(b * nbands + band) * 2 + which) * C + c0 + col] = t;
         }
     }
 }
@@ -1349,25 +994,16 @@ static DwGeom dw_geom(int64_t npix, int C, int lds_floats_per_pp) {
     g.nblocks = (int)gg_cdiv(npix, ppb);
     return g;
 }
-// stride-1 convs take the column-walking kernel: PX columns x C/NC channel groups per block (<= 256 threads), whole image height.
-// NC = 8 channels per thread, 4 for the doubly fused backward kernel.
-static int dw_walk_px(int C, int nc = 8) { return std::max(1, 256 / (C / nc)); }
-static bool dw_walk_ok(int C, int stride) { return stride == 1 && (C / 8) <= 256 && gg_dev_env("GG_DW_TILED") == nullptr; }
-static bool dw_walk_fused4(int C) { return (C / 4) <= 256; }       // both fusions at once run 4 channels per thread
-// fused stride-1 forward (producer BatchNorm + activation on load): 4 output columns x 4 channels per thread
+// The one channel contract of the bf16 depthwise family (include/gg.h): every entry point and every row / scratch count checks it first.
+// Inside it a block of either walker has at most 256 threads (<= 256 groups of 4 channels) and its statistics scratch takes <= 24 KB of LDS.
+#define GG_DW_CHECK_C(fn) GG_CHECK(C > 0 && (C & 7) == 0 && C <= 1024, fn ": C must be a multiple of 8, <= 1024 (got C = %d)", C)
+// stride-2 forward: PX output columns x C/8 channel groups per block (<= 256 threads), whole image height
+static int dw_walk_px(int C) { return std::max(1, 256 / (C / 8)); }
+// stride 1: 4 output columns x 4 channels per thread (half the loads per result of one column per thread: -8..15 % on 14x14 / 28x28 maps
+// even without a fusion); the variants with the act'(BN) epilogue take 2 columns (4 spill at 256 registers)
 static const int kDwMultiCols = 4;
-static bool dw_multi_ok(int C) {
-    const int CG = C / 4, PX = std::max(1, 256 / std::max(CG, 1));
-    return (C & 3) == 0 && CG <= 256 && (size_t)PX * 2 * C * sizeof(float) <= 64 * 1024 && gg_dev_env("GG_DW_TILED") == nullptr &&
-           gg_dev_env("GG_DW_NO_MULTI") == nullptr;
-}
-static bool dw_multi_plain(int C) { return gg_dev_env("GG_DW_NO_MULTI_PLAIN") == nullptr && dw_multi_ok(C); }      // the plain stride-1 forward too: half the loads per result (-8..15 % on 14x14 / 28x28 maps)
-static bool dw_multi_bwd(int C) { return gg_dev_env("GG_DW_NO_MULTI_BWD") == nullptr && dw_multi_ok(C); }          // stride-1 data gradients (plain and fused)
-static const int kDwMultiColsEpi = 2;       // variants with the act'(BN) epilogue: 2 columns per thread (4 spill at 256 registers)
+static const int kDwMultiColsEpi = 2;
 static int dw_multi_nbx(int W, int C, int ncol = kDwMultiCols) { return (int)gg_cdiv(W, std::max(1, 256 / (C / 4)) * ncol); }
-// stride-2 forward: the walking kernel when its per-thread state fits (8 channels per thread, <= 256 channel groups) and the image fits the
-// 30-bit offsets; GG_DW_TILED keeps the LDS-tiled kernel
-static bool dw_s2_walk_ok(int C) { return (C / 8) <= 256 && (C & 7) == 0 && gg_dev_env("GG_DW_TILED") == nullptr && gg_dev_env("GG_DW_S2_TILED") == nullptr; }
 static int dwconv_s2_walk_launch(const void* x, const float* wt, void* y, int B, int H, int W, int C, float* colstats, void* stream,
                                  const DwWalkFuse* fuse) {
     GG_CHECK((int64_t)H * W * C * 2 < 0x40000000LL, "dwconv: image too large for 30-bit offsets");
@@ -1377,7 +1013,7 @@ static int dwconv_s2_walk_launch(const void* x, const float* wt, void* y, int B,
     if (fuse) f = *fuse;
     const bool in1 = f.in_stat != nullptr;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const int CG = C / 8, PX = dw_walk_px(C, 8), nbx = (int)gg_cdiv(Wo, PX);
+    const int CG = C / 8, PX = dw_walk_px(C), nbx = (int)gg_cdiv(Wo, PX);
     GG_PROF(GG_CAT_DWCONV, 18.0 * B * Ho * Wo * C, 2.0 * B * C * ((double)H * W + (double)Ho * Wo), stream);
     const size_t lds = ((size_t)PX * 2 * C + (in1 ? 2 * (size_t)C : 0)) * sizeof(float);
     GG_CHECK(lds <= 64 * 1024, "dwconv: C=%d needs %zu bytes of LDS", C, lds);
@@ -1389,27 +1025,21 @@ static int dwconv_s2_walk_launch(const void* x, const float* wt, void* y, int B,
     GG_LAUNCH_CHECK();
     return 0;
 }
+/* one partial-statistics row per block: (Ho, Wo) = the OUTPUT map */
 extern "C" int gg_dwconv_stat_rows(int B, int Ho, int Wo, int C, int stride) {
-    if (stride == 1 && dw_multi_plain(C)) return B * dw_multi_nbx(Wo, C);
-    if (stride == 2 && dw_s2_walk_ok(C)) return B * (int)gg_cdiv(Wo, dw_walk_px(C, 8));
-    if (dw_walk_ok(C, stride)) return B * (int)gg_cdiv(Wo, dw_walk_px(C));
-    return B * (int)gg_cdiv(Ho, 8);
+    GG_DW_CHECK_C("gg_dwconv_stat_rows");
+    (void)Ho;
+    return stride == 1 ? B * dw_multi_nbx(Wo, C) : B * (int)gg_cdiv(Wo, dw_walk_px(C));
 }
-extern "C" int gg_dwconv_tiled_stat_rows(int B, int Ho) { return B * (int)gg_cdiv(Ho, 8); }
 /* rows written by gg_dwconv3x3_bwd_data_fused with an output-side fusion */
 extern "C" int gg_dwconv_fused_stat_rows(int B, int H, int W, int C, int with_input_fusion) {
-    if (dw_multi_bwd(C)) return B * dw_multi_nbx(W, C, kDwMultiColsEpi);
-    if (!dw_walk_ok(C, 1)) return B * (int)gg_cdiv(H, 8);
-    (void)with_input_fusion;
-    const int nc = dw_walk_fused4(C) ? 4 : 8;
-    return B * (int)gg_cdiv(W, dw_walk_px(C, nc));
+    GG_DW_CHECK_C("gg_dwconv_fused_stat_rows");
+    (void)H; (void)with_input_fusion;
+    return B * dw_multi_nbx(W, C, kDwMultiColsEpi);
 }
-/* partial-statistics rows gg_dwconv3x3_fwd_fused writes */
+/* partial-statistics rows gg_dwconv3x3_fwd_fused writes: the plain forward's, on the output map */
 extern "C" int gg_dwconv_fwd_fused_stat_rows(int B, int H, int W, int C, int stride) {
-    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-    if (stride == 2) return gg_dwconv_stat_rows(B, Ho, Wo, C, 2);
-    if (dw_multi_ok(C)) return B * dw_multi_nbx(W, C);
-    return gg_dwconv_fused_stat_rows(B, H, W, C, 1);
+    return gg_dwconv_stat_rows(B, (H - 1) / stride + 1, (W - 1) / stride + 1, C, stride);
 }
 static int dwconv_multi_launch(const void* x, const float* wt, void* y, int B, int H, int W, int C, int flip, float* colstats, void* stream,
                                const DwWalkFuse& f) {
@@ -1432,38 +1062,17 @@ static int dwconv_multi_launch(const void* x, const float* wt, void* y, int B, i
     GG_LAUNCH_CHECK();
     return 0;
 }
-static int dwconv_walk_launch(const void* x, const float* wt, void* y, int B, int H, int W, int C, int flip, float* colstats, void* stream,
-                              const DwWalkFuse* fuse = nullptr) {
-    GG_CHECK((int64_t)H * W * C * 2 < 0x40000000LL, "dwconv: image too large for 30-bit offsets");
-    GG_CHECK(((uintptr_t)wt & 15) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0, "dwconv: operands must be 16-byte aligned");
-    DwWalkFuse f;
-    memset(&f, 0, sizeof(f));
-    if (fuse) f = *fuse;
-    const bool in2 = f.in_coef != nullptr, epi = f.ep_y != nullptr, in1 = f.in_stat != nullptr;
-    const int nc = ((in1 || in2 || epi) && dw_walk_fused4(C)) ? 4 : 8;      // every fused variant: 4 channels per thread
-    const int CG = C / nc, PX = dw_walk_px(C, nc), nbx = (int)gg_cdiv(W, PX);
-    GG_PROF(GG_CAT_DWCONV, 18.0 * B * H * W * C, 2.0 * B * C * (double)H * W * (2 + in2 + epi), stream);
-    const size_t lds = ((size_t)PX * 2 * C + ((in1 || in2 || epi) ? 16 * (size_t)C : 0)) * sizeof(float);
-    GG_CHECK(lds <= 64 * 1024, "dwconv: C=%d needs %zu bytes of LDS", C, lds);
-    const dim3 grid((unsigned)(B * nbx)), block(CG * PX);
-#define GG_DW_WALK(I_, E_, N_) hipLaunchKernelGGL((dwconv3x3_walk_kernel<I_, E_, N_>), grid, block, lds, (hipStream_t)stream, (const bf16*)x, wt, \
-                                                  (bf16*)y, H, W, C, CG, PX, nbx, flip, colstats, f)
-    if (in1) { GG_CHECK(!in2 && !epi, "dwconv: producer fusion excludes the backward fusions"); if (nc == 4) GG_DW_WALK(1, false, 2); else GG_DW_WALK(1, false, 4); }
-    else if (in2 && epi) { if (nc == 4) GG_DW_WALK(2, true, 2); else GG_DW_WALK(2, true, 4); }
-    else if (in2) { if (nc == 4) GG_DW_WALK(2, false, 2); else GG_DW_WALK(2, false, 4); }
-    else if (epi) { if (nc == 4) GG_DW_WALK(0, true, 2); else GG_DW_WALK(0, true, 4); }
-    else GG_DW_WALK(0, false, 4);
-#undef GG_DW_WALK
-    GG_LAUNCH_CHECK();
-    return 0;
-}
 
-// stride-2 data gradient geometry: 8-channel groups x pixel lanes, <= 4096 blocks (= partial statistics rows with ep_y)
-static bool dw_s2_ok(int C) { return (C / 8) <= 256 && (16 + 2 * std::max(1, 256 / (C / 8))) * (int64_t)C * 4 <= 60 * 1024; }
+// stride-2 data gradient geometry: 8-channel groups x pixel lanes, <= 4096 blocks (= partial statistics rows with ep_y); its tables and
+// reduction scratch fit 60 KB of LDS up to C = 768 (above that the plain gradient takes the generic kernel, the fused one refuses)
+static bool dw_s2_ok(int C) { return (16 + 2 * std::max(1, 256 / (C / 8))) * (int64_t)C * 4 <= 60 * 1024; }
 static int dw_s2_blocks(int B, int H, int W, int C) {          // trips are 2x2 input quads = output-resolution pixels
     return (int)std::min<int64_t>(gg_cdiv((int64_t)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1), std::max(1, 256 / (C / 8))), 4096);
 }
-extern "C" int gg_dwconv_s2_fused_stat_rows(int B, int H, int W, int C) { return dw_s2_blocks(B, H, W, C); }
+extern "C" int gg_dwconv_s2_fused_stat_rows(int B, int H, int W, int C) {
+    GG_DW_CHECK_C("gg_dwconv_s2_fused_stat_rows");
+    return dw_s2_blocks(B, H, W, C);
+}
 static int dwconv_s2_bwd_launch(const void* dy, const float* wt, void* dx, int B, int H, int W, int C, const DwS2Fuse* fuse, void* stream) {
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const int CG = C / 8, PP = std::max(1, 256 / CG);
@@ -1486,7 +1095,9 @@ static int dwconv_s2_bwd_launch(const void* dy, const float* wt, void* dx, int B
 extern "C" int gg_dwconv3x3_s2_bwd_data_fused(const void* dz_in, const void* y_in, const float* in_coef, const float* wt, void* out, int B,
                                               int H, int W, int C, const void* ep_y, const float* ep_stat, const float* ep_gamma,
                                               const float* ep_beta, int ep_act, float* ep_part, void* stream) {
-    GG_CHECK(dz_in && wt && out && B > 0 && (C & 7) == 0 && dw_s2_ok(C), "gg_dwconv3x3_s2_bwd_data_fused: bad args");
+    GG_DW_CHECK_C("gg_dwconv3x3_s2_bwd_data_fused");
+    GG_CHECK(dz_in && wt && out && B > 0, "gg_dwconv3x3_s2_bwd_data_fused: bad args");
+    GG_CHECK(dw_s2_ok(C), "gg_dwconv3x3_s2_bwd_data_fused: C = %d needs more than 60 KB of LDS (C <= 768)", C);
     GG_CHECK(!in_coef || y_in, "gg_dwconv3x3_s2_bwd_data_fused: in_coef needs y_in");
     GG_CHECK(!ep_y || (ep_stat && ep_gamma && ep_beta && ep_part), "gg_dwconv3x3_s2_bwd_data_fused: epilogue needs stat/gamma/beta/partials");
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
@@ -1497,122 +1108,68 @@ extern "C" int gg_dwconv3x3_s2_bwd_data_fused(const void* dz_in, const void* y_i
     f.ep_y = (const bf16*)ep_y; f.ep_stat = ep_stat; f.ep_gamma = ep_gamma; f.ep_beta = ep_beta; f.ep_act = ep_act; f.part = ep_part;
     return dwconv_s2_bwd_launch(dz_in, wt, out, B, H, W, C, &f, stream);
 }
-struct DwFuse {
-    const void* in2 = nullptr; const float* in_coef = nullptr;
-    const void* ep_y = nullptr; const float* ep_stat = nullptr; const float* ep_gamma = nullptr; const float* ep_beta = nullptr; int ep_act = 0;
-};
-static int dwconv_tiled_launch(const void* x, const float* wt, void* y, int B, int H, int W, int C, int stride, int flip,
-                               const float* in_stat, const float* in_gamma, const float* in_beta, int in_act, float* colstats,
-                               void* stream, const DwFuse& f = DwFuse()) {
-    const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
-    const int nbands = (int)gg_cdiv(Ho, 8), nchunks = (int)gg_cdiv(C, 64);
-    const int64_t blocks = (int64_t)B * nbands * nchunks;
-    GG_CHECK(blocks < ((int64_t)1 << 31), "dwconv: grid too large");
-    GG_PROF(GG_CAT_DWCONV, 18.0 * B * Ho * Wo * C, 2.0 * B * C * ((double)H * W + (double)Ho * Wo), stream);
-    const int mode = (f.in_coef || f.ep_y) ? 2 : (in_stat ? 1 : 0);
-#define GG_DW_LAUNCH(S_, M_)                                                                                                          \
-    hipLaunchKernelGGL((dwconv3x3_tiled_kernel<S_, M_>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, wt, \
-                       (bf16*)y, B, H, W, C, Ho, Wo, nbands, nchunks, flip, in_stat, in_gamma, in_beta, in_act, colstats,               \
-                       (const bf16*)f.in2, f.in_coef, (const bf16*)f.ep_y, f.ep_stat, f.ep_gamma, f.ep_beta, f.ep_act)
-    if (stride == 1) {
-        if (mode == 0) GG_DW_LAUNCH(1, 0); else if (mode == 1) GG_DW_LAUNCH(1, 1); else GG_DW_LAUNCH(1, 2);
-    } else {
-        GG_CHECK(mode != 2, "dwconv: backward fusions are stride-1 only");
-        if (mode == 0) GG_DW_LAUNCH(2, 0); else GG_DW_LAUNCH(2, 1);
-    }
-#undef GG_DW_LAUNCH
-    GG_LAUNCH_CHECK();
-    return 0;
-}
 extern "C" int gg_dwconv3x3_fwd(const void* x, const float* wt, void* y, int B, int H, int W, int C, int stride, float* colstats,
                                 void* stream) {
-    GG_CHECK(x && wt && y && B > 0 && (C & 7) == 0 && (stride == 1 || stride == 2), "gg_dwconv3x3_fwd: bad args");
-    if (stride == 1 && dw_multi_plain(C)) { DwWalkFuse wf; memset(&wf, 0, sizeof(wf)); return dwconv_multi_launch(x, wt, y, B, H, W, C, 0, colstats, stream, wf); }
-    if (dw_walk_ok(C, stride)) return dwconv_walk_launch(x, wt, y, B, H, W, C, 0, colstats, stream);
-    if (stride == 2 && dw_s2_walk_ok(C)) return dwconv_s2_walk_launch(x, wt, y, B, H, W, C, colstats, stream, nullptr);
-    return dwconv_tiled_launch(x, wt, y, B, H, W, C, stride, 0, nullptr, nullptr, nullptr, 0, colstats, stream);
+    GG_DW_CHECK_C("gg_dwconv3x3_fwd");
+    GG_CHECK(x && wt && y && B > 0 && (stride == 1 || stride == 2), "gg_dwconv3x3_fwd: bad args");
+    if (stride == 2) return dwconv_s2_walk_launch(x, wt, y, B, H, W, C, colstats, stream, nullptr);
+    DwWalkFuse wf;
+    memset(&wf, 0, sizeof(wf));
+    return dwconv_multi_launch(x, wt, y, B, H, W, C, 0, colstats, stream, wf);
 }
-// fused producer: x is the PRE-BatchNorm output of the previous ConvNorm; act(BN(x)) is formed while staging
+// fused producer: x is the PRE-BatchNorm output of the previous ConvNorm; act(BN(x)) is formed while loading
 extern "C" int gg_dwconv3x3_fwd_fused(const void* x, const float* in_stat, const float* in_gamma, const float* in_beta, int in_act,
                                       const float* wt, void* y, int B, int H, int W, int C, int stride, float* colstats, void* stream) {
-    GG_CHECK(x && wt && y && in_stat && in_gamma && in_beta && B > 0 && (C & 7) == 0 && (stride == 1 || stride == 2),
-             "gg_dwconv3x3_fwd_fused: bad args");
-    if (stride == 1 && dw_multi_ok(C)) {
-        DwWalkFuse wf;
-        memset(&wf, 0, sizeof(wf));
-        wf.in_stat = in_stat; wf.in_gamma = in_gamma; wf.in_beta = in_beta; wf.in_act = in_act;
-        return dwconv_multi_launch(x, wt, y, B, H, W, C, 0, colstats, stream, wf);
-    }
-    if (dw_walk_ok(C, stride)) {
-        DwWalkFuse wf;
-        memset(&wf, 0, sizeof(wf));
-        wf.in_stat = in_stat; wf.in_gamma = in_gamma; wf.in_beta = in_beta; wf.in_act = in_act;
-        return dwconv_walk_launch(x, wt, y, B, H, W, C, 0, colstats, stream, &wf);
-    }
-    if (stride == 2 && dw_s2_walk_ok(C)) {
-        DwWalkFuse wf;
-        memset(&wf, 0, sizeof(wf));
-        wf.in_stat = in_stat; wf.in_gamma = in_gamma; wf.in_beta = in_beta; wf.in_act = in_act;
-        return dwconv_s2_walk_launch(x, wt, y, B, H, W, C, colstats, stream, &wf);
-    }
-    return dwconv_tiled_launch(x, wt, y, B, H, W, C, stride, 0, in_stat, in_gamma, in_beta, in_act, colstats, stream);
+    GG_DW_CHECK_C("gg_dwconv3x3_fwd_fused");
+    GG_CHECK(x && wt && y && in_stat && in_gamma && in_beta && B > 0 && (stride == 1 || stride == 2), "gg_dwconv3x3_fwd_fused: bad args");
+    DwWalkFuse wf;
+    memset(&wf, 0, sizeof(wf));
+    wf.in_stat = in_stat; wf.in_gamma = in_gamma; wf.in_beta = in_beta; wf.in_act = in_act;
+    if (stride == 2) return dwconv_s2_walk_launch(x, wt, y, B, H, W, C, colstats, stream, &wf);
+    return dwconv_multi_launch(x, wt, y, B, H, W, C, 0, colstats, stream, wf);
 }
-// stride-1 data gradient with the BatchNorm-backward passes on both sides folded in (see the kernel comment):
+// stride-1 data gradient (== the same conv with flipped taps) with the BatchNorm-backward passes on both sides folded in (see the kernel comment):
 //   input  = coef0*dz_in + coef1*y_in + coef2   when in_coef != NULL (else dz_in is used as is)
 //   output = conv_T(input) * act'(BN(ep_y))      and stats rows (sum, sum*xhat) when ep_y != NULL (else the plain gradient)
 extern "C" int gg_dwconv3x3_bwd_data_fused(const void* dz_in, const void* y_in, const float* in_coef, const float* wt, void* out, int B, int H,
                                            int W, int C, const void* ep_y, const float* ep_stat, const float* ep_gamma,
                                            const float* ep_beta, int ep_act, float* ep_part, void* stream) {
-    GG_CHECK(dz_in && wt && out && B > 0 && (C & 7) == 0, "gg_dwconv3x3_bwd_data_fused: bad args");
+    GG_DW_CHECK_C("gg_dwconv3x3_bwd_data_fused");
+    GG_CHECK(dz_in && wt && out && B > 0, "gg_dwconv3x3_bwd_data_fused: bad args");
     GG_CHECK(!in_coef || y_in, "gg_dwconv3x3_bwd_data_fused: in_coef needs y_in");
     GG_CHECK(!ep_y || (ep_stat && ep_gamma && ep_beta && ep_part), "gg_dwconv3x3_bwd_data_fused: epilogue needs stat/gamma/beta/partials");
-    if (dw_multi_bwd(C)) {
-        DwWalkFuse wf;
-        memset(&wf, 0, sizeof(wf));
-        wf.in2 = in_coef ? (const bf16*)y_in : nullptr; wf.in_coef = in_coef;
-        wf.ep_y = (const bf16*)ep_y; wf.ep_stat = ep_stat; wf.ep_gamma = ep_gamma; wf.ep_beta = ep_beta; wf.ep_act = ep_act;
-        return dwconv_multi_launch(dz_in, wt, out, B, H, W, C, 1, ep_y ? ep_part : nullptr, stream, wf);
-    }
-    if (dw_walk_ok(C, 1)) {
-        DwWalkFuse wf;
-        memset(&wf, 0, sizeof(wf));
-        wf.in2 = in_coef ? (const bf16*)y_in : nullptr; wf.in_coef = in_coef;
-        wf.ep_y = (const bf16*)ep_y; wf.ep_stat = ep_stat; wf.ep_gamma = ep_gamma; wf.ep_beta = ep_beta; wf.ep_act = ep_act;
-        return dwconv_walk_launch(dz_in, wt, out, B, H, W, C, 1, ep_y ? ep_part : nullptr, stream, &wf);
-    }
-    DwFuse f;
-    f.in2 = in_coef ? y_in : nullptr; f.in_coef = in_coef;
-    f.ep_y = ep_y; f.ep_stat = ep_stat; f.ep_gamma = ep_gamma; f.ep_beta = ep_beta; f.ep_act = ep_act;
-    return dwconv_tiled_launch(dz_in, wt, out, B, H, W, C, 1, 1, nullptr, nullptr, nullptr, 0, ep_y ? ep_part : nullptr, stream, f);
+    DwWalkFuse wf;
+    memset(&wf, 0, sizeof(wf));
+    wf.in2 = in_coef ? (const bf16*)y_in : nullptr; wf.in_coef = in_coef;
+    wf.ep_y = (const bf16*)ep_y; wf.ep_stat = ep_stat; wf.ep_gamma = ep_gamma; wf.ep_beta = ep_beta; wf.ep_act = ep_act;
+    return dwconv_multi_launch(dz_in, wt, out, B, H, W, C, 1, ep_y ? ep_part : nullptr, stream, wf);
 }
 extern "C" int gg_dwconv3x3_bwd_data(const void* dy, const float* wt, void* dx, int B, int H, int W, int C, int stride, void* stream) {
-    GG_CHECK(dy && wt && dx && B > 0 && (C & 7) == 0 && (stride == 1 || stride == 2), "gg_dwconv3x3_bwd_data: bad args");
+    GG_DW_CHECK_C("gg_dwconv3x3_bwd_data");
+    GG_CHECK(dy && wt && dx && B > 0 && (stride == 1 || stride == 2), "gg_dwconv3x3_bwd_data: bad args");
     GG_CHECK((int64_t)B * H * W * (C / 8) < ((int64_t)1 << 32), "gg_dwconv3x3_bwd_data: tensor too large for 32-bit indexing");
-    if (stride == 1 && dw_multi_bwd(C)) { DwWalkFuse wf; memset(&wf, 0, sizeof(wf)); return dwconv_multi_launch(dy, wt, dx, B, H, W, C, 1, nullptr, stream, wf); }
-    if (dw_walk_ok(C, stride)) return dwconv_walk_launch(dy, wt, dx, B, H, W, C, 1, nullptr, stream);
-    if (stride == 1)     // data gradient of a stride-1 depthwise conv == the same conv with flipped taps
-        return dwconv_tiled_launch(dy, wt, dx, B, H, W, C, 1, 1, nullptr, nullptr, nullptr, 0, nullptr, stream);
-    const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
+    if (stride == 1) { DwWalkFuse wf; memset(&wf, 0, sizeof(wf)); return dwconv_multi_launch(dy, wt, dx, B, H, W, C, 1, nullptr, stream, wf); }
+    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     GG_PROF(GG_CAT_DWCONV, 18.0 * B * Ho * Wo * C, 2.0 * B * C * ((double)H * W + (double)Ho * Wo), stream);
-    if (stride == 2 && dw_s2_ok(C) && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)dx & 15) == 0 && ((uintptr_t)wt & 15) == 0)
+    if (dw_s2_ok(C) && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)dx & 15) == 0 && ((uintptr_t)wt & 15) == 0)
         return dwconv_s2_bwd_launch(dy, wt, dx, B, H, W, C, nullptr, stream);
     hipLaunchKernelGGL(dwconv3x3_bwd_data_kernel, dim3(grid_for((int64_t)B * H * W * (C / 8), 65536)), dim3(256), 0,
-                       (hipStream_t)stream, (const bf16*)dy, wt, (bf16*)dx, B, H, W, C, Ho, Wo, stride);
+                       (hipStream_t)stream, (const bf16*)dy, wt, (bf16*)dx, B, H, W, C, Ho, Wo, 2);
     GG_LAUNCH_CHECK();
     return 0;
 }
-// walking weight-gradient geometry: channels per thread, columns per block (LDS holds [PX][9][C] floats), image groups
-struct WgGeom { int nc, CG, PX, nbx, BG; };
+// walking weight-gradient geometry (4 channels per thread): columns per block (LDS holds [PX][9][C] floats), image groups
+struct WgGeom { int CG, PX, nbx, BG; };
 static WgGeom wg_geom(int B, int W, int C) {
     WgGeom g;
-    g.nc = (C / 4) <= 256 ? 4 : 8;
-    g.CG = C / g.nc;
+    g.CG = C / 4;
     g.PX = std::max(1, std::min(256 / g.CG, (int)(15360 / (9 * (int64_t)C))));
     g.nbx = (int)gg_cdiv(W, g.PX);
     g.BG = std::max(1, std::min(B, 2048 / g.nbx));
     return g;
 }
 extern "C" int64_t gg_dwconv_wgrad_scratch_floats(int B, int H, int W, int C, int stride) {
+    GG_DW_CHECK_C("gg_dwconv_wgrad_scratch_floats");
     const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
     const WgGeom w = wg_geom(B, W, C);
     const int64_t nb = std::max<int64_t>(dw_geom((int64_t)B * Ho * Wo, C, 9 * C).nblocks, (int64_t)w.nbx * w.BG);
@@ -1620,15 +1177,15 @@ extern "C" int64_t gg_dwconv_wgrad_scratch_floats(int B, int H, int W, int C, in
 }
 extern "C" int gg_dwconv3x3_bwd_weight(const void* x, const void* dy, int B, int H, int W, int C, int stride, float* scratch,
                                        float* grad, int accumulate, void* stream) {
-    GG_CHECK(x && dy && scratch && grad && B > 0 && (C & 7) == 0, "gg_dwconv3x3_bwd_weight: bad args");
+    GG_DW_CHECK_C("gg_dwconv3x3_bwd_weight");
+    GG_CHECK(x && dy && scratch && grad && B > 0, "gg_dwconv3x3_bwd_weight: bad args");
     const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
     GG_PROF(GG_CAT_DWCONV, 18.0 * B * Ho * Wo * C, 2.0 * B * C * ((double)H * W + (double)Ho * Wo), stream);
-    if (dw_walk_ok(C, stride) && (int64_t)H * W * C * 2 < 0x40000000LL && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0) {
+    if (stride == 1 && (int64_t)H * W * C * 2 < 0x40000000LL && ((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0) {
         const WgGeom w = wg_geom(B, W, C);
         const size_t ldsw = (size_t)w.PX * 9 * C * sizeof(float);
         const dim3 grid(w.nbx, w.BG), block(w.CG * w.PX);
-        if (w.nc == 4) hipLaunchKernelGGL((dwconv3x3_wgrad_walk_kernel<2>), grid, block, ldsw, (hipStream_t)stream, (const bf16*)x, (const bf16*)dy, B, H, W, C, w.CG, w.PX, w.nbx, scratch);
-        else hipLaunchKernelGGL((dwconv3x3_wgrad_walk_kernel<4>), grid, block, ldsw, (hipStream_t)stream, (const bf16*)x, (const bf16*)dy, B, H, W, C, w.CG, w.PX, w.nbx, scratch);
+        hipLaunchKernelGGL((dwconv3x3_wgrad_walk_kernel<2>), grid, block, ldsw, (hipStream_t)stream, (const bf16*)x, (const bf16*)dy, B, H, W, C, w.CG, w.PX, w.nbx, scratch);
         const float* rows; int nrows;
         gg_reduce_rows(scratch, w.nbx * w.BG, 9 * C, (hipStream_t)stream, &rows, &nrows);
         hipLaunchKernelGGL(dwconv_wgrad_final_kernel, dim3((unsigned)gg_cdiv(9 * C, 256)), dim3(256), 0, (hipStream_t)stream, rows,

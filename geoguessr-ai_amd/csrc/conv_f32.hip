@@ -167,14 +167,11 @@ __global__ __launch_bounds__(256) void col2im_nhwc_bnbwd_f32_kernel(const float*
 }
 
 // ---------------------------------------------------------------- column-walking depthwise 3x3
-// Thread = (4 channels, one output column); a block covers PX adjacent output columns x all C channels of one image and walks down a
-// strip of output rows.  MODE 0: y = conv(x, taps) (+ per-block partial BatchNorm statistics of y); MODE 1: the same with flipped taps
-// (stride-1 data gradient); MODE 2: weight gradient -- acc[tap] += window[tap] * dy, one partial row [9][C] per block.
-// Fusions (the BatchNorm passes either side of a frozen depthwise ConvNorm ride on its loads / stores; bn_apply / bn_bwd passes and the
-// tensors between them disappear -- the f32 twins of gg_dwconv3x3_fwd_fused / gg_dwconv3x3_bwd_data_fused):
+// Fusions of the depthwise kernels (the BatchNorm passes either side of a frozen depthwise ConvNorm ride on its loads / stores; bn_apply /
+// bn_bwd passes and the tensors between them disappear -- the f32 twins of gg_dwconv3x3_fwd_fused / gg_dwconv3x3_bwd_data_fused):
 //   IN 1: x is the producer ConvNorm's saved PRE-BatchNorm output; act(sc*x + sh) is applied to every in-image load (padding stays 0)
 //   IN 2: x = dz, x2 = y of the ConvNorm whose BatchNorm-backward apply step dy = c0*dz + c1*y + c2 is formed on load
-//   EPI : (MODE 1) o *= act'(BN(ep_y)) at the output position and the partial rows hold (sum dz, sum dz*xhat) for gg_bn_bwd_finalize
+//   EPI : (flipped taps) o *= act'(BN(ep_y)) at the output position and the partial rows hold (sum dz, sum dz*xhat) for gg_bn_bwd_finalize
 enum { DWM_FWD = 0, DWM_FLIP = 1, DWM_WGRAD = 2 };
 struct DwFuse {
     const float* x2;                         // IN 2: second input tensor
@@ -182,7 +179,11 @@ struct DwFuse {
     int in_act;
     const float* ep_y; const float* ep_stat; const float* ep_gamma; const float* ep_beta; int ep_act;
 };
-template <int S, int MODE, int IN = 0, bool EPI = false>
+// One output column per thread: the stride-2 forward (plain, or IN 1) and the weight gradients of both strides.
+// Thread = (4 channels, one output column); a block covers PX adjacent output columns x all C channels of one image and walks down a
+// strip of output rows.  DWM_FWD: y = conv(x, taps) (+ per-block partial BatchNorm statistics of y); DWM_WGRAD: acc[tap] += window[tap] * dy,
+// one partial row [9][C] per block.
+template <int S, int MODE, int IN = 0>
 __global__ __launch_bounds__(256) void dw3x3_walk_f32_kernel(const float* __restrict__ x, const float* __restrict__ taps,
                                                              float* __restrict__ y, const float* __restrict__ dy, int H, int W, int C,
                                                              int Ho, int Wo, int PX, int rows_per_strip, float* __restrict__ part, DwFuse fz) {
@@ -197,50 +198,34 @@ __global__ __launch_bounds__(256) void dw3x3_walk_f32_kernel(const float* __rest
     f32x4 w[9];
     if (MODE != DWM_WGRAD) {
 #pragma unroll
-        for (int k = 0; k < 9; ++k) w[k] = *reinterpret_cast<const f32x4*>(taps + (MODE == DWM_FLIP ? 8 - k : k) * C + cg * 4);
+        for (int k = 0; k < 9; ++k) w[k] = *reinterpret_cast<const f32x4*>(taps + k * C + cg * 4);
     }
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    f32x4 acc[9];                    // MODE 2: the 9 tap gradients;  MODE 0: acc[0], acc[1] = sum / sum of squares of y
+    f32x4 acc[9];                    // DWM_WGRAD: the 9 tap gradients;  DWM_FWD: acc[0], acc[1] = sum / sum of squares of y
 #pragma unroll
     for (int k = 0; k < 9; ++k) acc[k] = zero;
     const int ix0 = ox * S - 1;
     const bool c0 = ix0 >= 0, c2 = ix0 + 2 < W;           // ix0 + 1 < W always holds for a live column
-    // per-channel coefficients of the fused passes (this thread's 4 channels are fixed)
-    f32x4 ia = zero, ib = zero, ic = zero;
+    // per-channel coefficients of the fused pass (this thread's 4 channels are fixed)
+    f32x4 ia = zero, ib = zero;
     if (IN == 1) {
         const f32x4 mu = *reinterpret_cast<const f32x4*>(fz.in_a + cg * 4), rs = *reinterpret_cast<const f32x4*>(fz.in_a + C + cg * 4);
         ia = rs * *reinterpret_cast<const f32x4*>(fz.in_b + cg * 4);
         ib = *reinterpret_cast<const f32x4*>(fz.in_c + cg * 4) - mu * ia;
     }
-    if (IN == 2) {
-        ia = *reinterpret_cast<const f32x4*>(fz.in_a + cg * 4); ib = *reinterpret_cast<const f32x4*>(fz.in_a + C + cg * 4);
-        ic = *reinterpret_cast<const f32x4*>(fz.in_a + 2 * C + cg * 4);
-    }
-    f32x4 esc = zero, esh = zero, ers = zero, enm = zero;
-    if (EPI) {
-        const f32x4 mu = *reinterpret_cast<const f32x4*>(fz.ep_stat + cg * 4);
-        ers = *reinterpret_cast<const f32x4*>(fz.ep_stat + C + cg * 4);
-        esc = ers * *reinterpret_cast<const f32x4*>(fz.ep_gamma + cg * 4);
-        esh = *reinterpret_cast<const f32x4*>(fz.ep_beta + cg * 4) - mu * esc;
-        enm = -mu * ers;
-    }
-    const float* x2b = IN == 2 ? fz.x2 + (int64_t)b * H * W * C + cg * 4 : nullptr;
-    auto ld = [&](const float* p, const float* p2) {
+    auto ld = [&](const float* p) {
         f32x4 v = *reinterpret_cast<const f32x4*>(p);
         if (IN == 1) {
             v = gg_act_f32_v4(v * ia + ib, fz.in_act);
         }
-        if (IN == 2) v = ia * v + (ib * *reinterpret_cast<const f32x4*>(p2) + ic);
         return v;
     };
     auto row = [&](int iy, f32x4 (&r)[3]) {
         if (live && iy >= 0 && iy < H) {
-            const int64_t o = ((int64_t)iy * W + ix0) * C;
-            const float* p = xb + o;
-            const float* p2 = IN == 2 ? x2b + o : nullptr;
-            r[0] = c0 ? ld(p, p2) : zero;
-            r[1] = ld(p + C, IN == 2 ? p2 + C : nullptr);
-            r[2] = c2 ? ld(p + 2 * C, IN == 2 ? p2 + 2 * C : nullptr) : zero;
+            const float* p = xb + ((int64_t)iy * W + ix0) * C;
+            r[0] = c0 ? ld(p) : zero;
+            r[1] = ld(p + C);
+            r[2] = c2 ? ld(p + 2 * C) : zero;
         } else { r[0] = r[1] = r[2] = zero; }
     };
     f32x4 r0[3], r1[3], r2[3];
@@ -261,11 +246,7 @@ __global__ __launch_bounds__(256) void dw3x3_walk_f32_kernel(const float* __rest
             o += r2[0] * w[6]; o += r2[1] * w[7]; o += r2[2] * w[8];
             if (live) {
                 const int64_t oo = (((int64_t)b * Ho + oy) * Wo + ox) * C + cg * 4;
-                if (EPI) {      // dz = da * act'(gamma*xhat + beta); sums of dz and dz*xhat
-                    const f32x4 yv = *reinterpret_cast<const f32x4*>(fz.ep_y + oo);
-                    o *= gg_act_grad_f32_v4(yv * esc + esh, fz.ep_act);
-                    acc[0] += o; acc[1] += o * (yv * ers + enm);
-                } else if (part) { acc[0] += o; acc[1] += o * o; }
+                if (part) { acc[0] += o; acc[1] += o * o; }
                 *reinterpret_cast<f32x4*>(y + oo) = o;
             }
         }
@@ -296,7 +277,7 @@ __global__ __launch_bounds__(256) void dw3x3_walk_f32_kernel(const float* __rest
 
 // Stride 1, FOUR adjacent output columns x 4 channels per thread: 6 loads per 4 results instead of 3 per 1, and whatever rides on the load
 // (BatchNorm + GELU of the ConvNorm in front: IN 1; BatchNorm backward's apply step c0*dz + c1*y + c2: IN 2) is evaluated 1.5 instead of 3
-// times per input element -- with the exact erf of the fp32 mode that is what the one-column kernel spent its time on (2.1 TB/s against
+// times per input element -- with the exact erf of the fp32 mode that is what one column per thread spent its time on (2.1 TB/s against
 // 4.2 TB/s unfused).  Row window held in registers, rotated by renaming (the loop body is unrolled 3x).  MODE: DWM_FWD or DWM_FLIP.
 template <int MODE, int IN, bool EPI>
 __global__ __launch_bounds__(256) void dw3x3_s1_multi_f32_kernel(const float* __restrict__ x, const float* __restrict__ taps, float* __restrict__ y,
@@ -573,10 +554,6 @@ WalkGeom multi_geom(int B, int H, int W, int C) {
     g.strips = (int)gg_cdiv(H, g.rows_per_strip);
     return g;
 }
-bool dw_use_multi(int stride) {
-    static const bool off = gg_dev_env("GG_DW_F32_NO_MULTI") != nullptr;
-    return stride == 1 && !off;
-}
 int grid_for(int64_t n, int cap = 16384) { return (int)std::max<int64_t>(1, std::min<int64_t>(gg_cdiv(n, 256), cap)); }
 
 }  // namespace
@@ -633,68 +610,58 @@ extern "C" int gg_col2im_nhwc_f32(const float* dcol, float* dx, int B, int H, in
 
 // partial rows written by the forward (colstats) and by the fused stride-1 data gradient (ep_partials) for an OUTPUT map of Ho x Wo
 extern "C" int gg_dwconv_f32_stat_rows(int B, int Ho, int Wo, int C, int stride) {
-    const WalkGeom g = dw_use_multi(stride) ? multi_geom(B, Ho, Wo, C) : walk_geom(B, Ho, Wo, C);
+    const WalkGeom g = stride == 1 ? multi_geom(B, Ho, Wo, C) : walk_geom(B, Ho, Wo, C);
     return g.nbx * B * g.strips;
 }
 static int dw_wgrad_rows(int B, int Ho, int Wo, int C) {      // the tap-gradient walk always uses the one-column geometry
     const WalkGeom g = walk_geom(B, Ho, Wo, C);
     return g.nbx * B * g.strips;
 }
-static int dw_walk_launch(int mode, const float* x, const float* taps, float* y, const float* dy, int B, int H, int W, int C, int stride,
-                          float* part, void* stream, const DwFuse* fuse = nullptr, int in_mode = 0, bool epi = false) {
+static int dw_f32_check(int B, int C) {
     GG_CHECK((C & 3) == 0 && C >= 4 && C <= 1024, "gg_dwconv3x3 f32: C must be a multiple of 4, <= 1024 (got %d)", C);
     GG_CHECK(B <= 65535, "gg_dwconv3x3 f32: batch too large for one launch");
-    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-    if (mode != DWM_WGRAD && dw_use_multi(stride)) {
-        const WalkGeom g = multi_geom(B, H, W, C);
-        const dim3 grid(g.nbx, B, g.strips), block(g.threads);
-        const size_t lds = part ? (size_t)g.PX * 2 * C * sizeof(float) : 0;
-        DwFuse fz;
-        memset(&fz, 0, sizeof(fz));
-        if (fuse) fz = *fuse;
-#define GG_DW_MULTI(M_, I_, E_) hipLaunchKernelGGL((dw3x3_s1_multi_f32_kernel<M_, I_, E_>), grid, block, lds, (hipStream_t)stream, x, taps, y, H, W, C, g.PX, g.rows_per_strip, part, fz)
-        if (mode == DWM_FWD && in_mode == 0 && !epi) GG_DW_MULTI(DWM_FWD, 0, false);
-        else if (mode == DWM_FWD && in_mode == 1 && !epi) GG_DW_MULTI(DWM_FWD, 1, false);
-        else if (mode == DWM_FLIP && in_mode == 0 && !epi) GG_DW_MULTI(DWM_FLIP, 0, false);
-        else if (mode == DWM_FLIP && in_mode == 2 && !epi) GG_DW_MULTI(DWM_FLIP, 2, false);
-        else if (mode == DWM_FLIP && in_mode == 0 && epi) GG_DW_MULTI(DWM_FLIP, 0, true);
-        else if (mode == DWM_FLIP && in_mode == 2 && epi) GG_DW_MULTI(DWM_FLIP, 2, true);
-        else { gg_set_error("gg_dwconv3x3 f32: multi-column variant (mode %d, in %d, epi %d) is not built", mode, in_mode, (int)epi); return -1; }
-#undef GG_DW_MULTI
-        GG_LAUNCH_CHECK();
-        return 0;
-    }
-    const WalkGeom g = walk_geom(B, Ho, Wo, C);
+    return 0;
+}
+// stride 1, forward (DWM_FWD; in_mode 0 / 1) and data gradient (DWM_FLIP; in_mode 0 / 2, with or without the epilogue)
+static int dw_multi_launch(int mode, const float* x, const float* taps, float* y, int B, int H, int W, int C, float* part, void* stream,
+                           const DwFuse* fuse = nullptr, int in_mode = 0, bool epi = false) {
+    GG_TRY(dw_f32_check(B, C));
+    const WalkGeom g = multi_geom(B, H, W, C);
     const dim3 grid(g.nbx, B, g.strips), block(g.threads);
-    const int NR = mode == DWM_WGRAD ? 9 : 2;
-    const size_t lds = part ? (size_t)g.PX * NR * C * sizeof(float) : 0;
-    GG_CHECK(lds <= 64 * 1024, "gg_dwconv3x3 f32: reduction tile too large");
-    hipStream_t st = (hipStream_t)stream;
+    const size_t lds = part ? (size_t)g.PX * 2 * C * sizeof(float) : 0;
     DwFuse fz;
     memset(&fz, 0, sizeof(fz));
     if (fuse) fz = *fuse;
-#define GG_DW_LAUNCHF(S_, M_, I_, E_) hipLaunchKernelGGL((dw3x3_walk_f32_kernel<S_, M_, I_, E_>), grid, block, lds, st, x, taps, y, dy, H, W, C, Ho, Wo, g.PX, g.rows_per_strip, part, fz)
-#define GG_DW_LAUNCH(S_, M_) GG_DW_LAUNCHF(S_, M_, 0, false)
-    if (in_mode != 0 || epi) {
-        if (mode == DWM_FWD && in_mode == 1 && !epi) { if (stride == 1) GG_DW_LAUNCHF(1, DWM_FWD, 1, false); else GG_DW_LAUNCHF(2, DWM_FWD, 1, false); }
-        else if (mode == DWM_FLIP && stride == 1 && in_mode == 2 && epi) GG_DW_LAUNCHF(1, DWM_FLIP, 2, true);
-        else if (mode == DWM_FLIP && stride == 1 && in_mode == 2 && !epi) GG_DW_LAUNCHF(1, DWM_FLIP, 2, false);
-        else if (mode == DWM_FLIP && stride == 1 && in_mode == 0 && epi) GG_DW_LAUNCHF(1, DWM_FLIP, 0, true);
-        else { gg_set_error("gg_dwconv3x3 f32: fused variant (mode %d, stride %d, in %d, epi %d) is not built", mode, stride, in_mode, (int)epi); return -1; }
-        GG_LAUNCH_CHECK();
-        return 0;
-    }
-    if (stride == 1) {
-        if (mode == DWM_FWD) GG_DW_LAUNCH(1, DWM_FWD);
-        else if (mode == DWM_FLIP) GG_DW_LAUNCH(1, DWM_FLIP);
-        else GG_DW_LAUNCH(1, DWM_WGRAD);
-    } else {
-        if (mode == DWM_FWD) GG_DW_LAUNCH(2, DWM_FWD);
-        else if (mode == DWM_WGRAD) GG_DW_LAUNCH(2, DWM_WGRAD);
-        else { gg_set_error("gg_dwconv3x3 f32: flipped stride-2 walk does not exist"); return -1; }
-    }
-#undef GG_DW_LAUNCH
-#undef GG_DW_LAUNCHF
+#define GG_DW_MULTI(M_, I_, E_) hipLaunchKernelGGL((dw3x3_s1_multi_f32_kernel<M_, I_, E_>), grid, block, lds, (hipStream_t)stream, x, taps, y, H, W, C, g.PX, g.rows_per_strip, part, fz)
+    if (mode == DWM_FWD && in_mode == 0 && !epi) GG_DW_MULTI(DWM_FWD, 0, false);
+    else if (mode == DWM_FWD && in_mode == 1 && !epi) GG_DW_MULTI(DWM_FWD, 1, false);
+    else if (mode == DWM_FLIP && in_mode == 0 && !epi) GG_DW_MULTI(DWM_FLIP, 0, false);
+    else if (mode == DWM_FLIP && in_mode == 2 && !epi) GG_DW_MULTI(DWM_FLIP, 2, false);
+    else if (mode == DWM_FLIP && in_mode == 0 && epi) GG_DW_MULTI(DWM_FLIP, 0, true);
+    else if (mode == DWM_FLIP && in_mode == 2 && epi) GG_DW_MULTI(DWM_FLIP, 2, true);
+    else { gg_set_error("gg_dwconv3x3 f32: multi-column variant (mode %d, in %d, epi %d) is not built", mode, in_mode, (int)epi); return -1; }
+#undef GG_DW_MULTI
+    GG_LAUNCH_CHECK();
+    return 0;
+}
+// one column per thread: the stride-2 forward (fuse: producer BatchNorm + activation on load) and, with dy, the weight gradient of either stride
+static int dw_walk_launch(const float* x, const float* taps, float* y, const float* dy, int B, int H, int W, int C, int stride, float* part,
+                          void* stream, const DwFuse* fuse = nullptr) {
+    GG_TRY(dw_f32_check(B, C));
+    const bool wgrad = dy != nullptr;
+    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+    const WalkGeom g = walk_geom(B, Ho, Wo, C);
+    const dim3 grid(g.nbx, B, g.strips), block(g.threads);
+    const size_t lds = part ? (size_t)g.PX * (wgrad ? 9 : 2) * C * sizeof(float) : 0;
+    GG_CHECK(lds <= 64 * 1024, "gg_dwconv3x3 f32: reduction tile too large");
+    DwFuse fz;
+    memset(&fz, 0, sizeof(fz));
+    if (fuse) fz = *fuse;
+#define GG_DW_WALK(S_, M_, I_) hipLaunchKernelGGL((dw3x3_walk_f32_kernel<S_, M_, I_>), grid, block, lds, (hipStream_t)stream, x, taps, y, dy, H, W, C, Ho, Wo, g.PX, g.rows_per_strip, part, fz)
+    if (wgrad) { if (stride == 1) GG_DW_WALK(1, DWM_WGRAD, 0); else GG_DW_WALK(2, DWM_WGRAD, 0); }
+    else if (fuse) GG_DW_WALK(2, DWM_FWD, 1);
+    else GG_DW_WALK(2, DWM_FWD, 0);
+#undef GG_DW_WALK
     GG_LAUNCH_CHECK();
     return 0;
 }
@@ -704,14 +671,15 @@ extern "C" int gg_dwconv3x3_fwd_f32(const float* x, const float* taps, float* y,
     GG_CHECK(x && taps && y && B > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2), "gg_dwconv3x3_fwd_f32: bad args");
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     GG_PROF(GG_CAT_DWCONV, 18.0 * B * Ho * Wo * C, 4.0 * B * C * ((double)H * W + (double)Ho * Wo), stream);
-    return dw_walk_launch(DWM_FWD, x, taps, y, nullptr, B, H, W, C, stride, colstats, stream);
+    if (stride == 1) return dw_multi_launch(DWM_FWD, x, taps, y, B, H, W, C, colstats, stream);
+    return dw_walk_launch(x, taps, y, nullptr, B, H, W, C, 2, colstats, stream);
 }
 // dx = gradient of the conv w.r.t. its input; (H, W) = the conv INPUT map
 extern "C" int gg_dwconv3x3_bwd_data_f32(const float* dy, const float* taps, float* dx, int B, int H, int W, int C, int stride, void* stream) {
     GG_CHECK(dy && taps && dx && B > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2) && (C & 3) == 0, "gg_dwconv3x3_bwd_data_f32: bad args");
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     GG_PROF(GG_CAT_DWCONV, 18.0 * B * Ho * Wo * C, 4.0 * B * C * ((double)H * W + (double)Ho * Wo), stream);
-    if (stride == 1) return dw_walk_launch(DWM_FLIP, dy, taps, dx, nullptr, B, H, W, C, 1, nullptr, stream);
+    if (stride == 1) return dw_multi_launch(DWM_FLIP, dy, taps, dx, B, H, W, C, nullptr, stream);
     hipLaunchKernelGGL(dw3x3_s2_bwd_data_f32_kernel, dim3(grid_for((int64_t)B * H * W * (C / 4), 65536)), dim3(256), 0, (hipStream_t)stream, dy, taps,
                        dx, B, H, W, C, Ho, Wo);
     GG_LAUNCH_CHECK();
@@ -761,7 +729,7 @@ extern "C" int gg_dwconv3x3_bwd_weight_f32(const float* x, const float* dy, int 
     GG_CHECK(x && dy && scratch && grad && B > 0 && (stride == 1 || stride == 2), "gg_dwconv3x3_bwd_weight_f32: bad args");
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     GG_PROF(GG_CAT_DWCONV, 18.0 * B * Ho * Wo * C, 4.0 * B * C * ((double)H * W + (double)Ho * Wo), stream);
-    GG_TRY(dw_walk_launch(DWM_WGRAD, x, nullptr, nullptr, dy, B, H, W, C, stride, scratch, stream));
+    GG_TRY(dw_walk_launch(x, nullptr, nullptr, dy, B, H, W, C, stride, scratch, stream));
     const float* rows; int nrows;
     gg_reduce_rows(scratch, dw_wgrad_rows(B, Ho, Wo, C), 9 * C, (hipStream_t)stream, &rows, &nrows);
     hipLaunchKernelGGL(dw_wgrad_final_f32_kernel, dim3((unsigned)gg_cdiv(9 * C, 256)), dim3(256), 0, (hipStream_t)stream, rows, nrows, C, grad, accumulate);
@@ -779,7 +747,8 @@ extern "C" int gg_dwconv3x3_fwd_fused_f32(const float* x_prebn, const float* in_
     DwFuse f;
     memset(&f, 0, sizeof(f));
     f.in_a = in_stat; f.in_b = in_gamma; f.in_c = in_beta; f.in_act = in_act;
-    return dw_walk_launch(DWM_FWD, x_prebn, taps, y, nullptr, B, H, W, C, stride, colstats, stream, &f, 1, false);
+    if (stride == 1) return dw_multi_launch(DWM_FWD, x_prebn, taps, y, B, H, W, C, colstats, stream, &f, 1, false);
+    return dw_walk_launch(x_prebn, taps, y, nullptr, B, H, W, C, 2, colstats, stream, &f);
 }
 // stride-1 data gradient with the BatchNorm-backward passes of the ConvNorms on both sides riding on it:
 //   input : in_coef != NULL -> dy = coef0*dz_in + coef1*y_in + coef2 formed on load (apply step of the ConvNorm this conv belongs to)
@@ -794,5 +763,5 @@ extern "C" int gg_dwconv3x3_bwd_data_fused_f32(const float* dz_in, const float* 
     DwFuse f;
     memset(&f, 0, sizeof(f));
     f.x2 = y_in; f.in_a = in_coef; f.ep_y = ep_y; f.ep_stat = ep_stat; f.ep_gamma = ep_gamma; f.ep_beta = ep_beta; f.ep_act = ep_act;
-    return dw_walk_launch(DWM_FLIP, dz_in, taps, out, nullptr, B, H, W, C, 1, ep_y ? ep_partials : nullptr, stream, &f, in_coef ? 2 : 0, ep_y != nullptr);
+    return dw_multi_launch(DWM_FLIP, dz_in, taps, out, B, H, W, C, ep_y ? ep_partials : nullptr, stream, &f, in_coef ? 2 : 0, ep_y != nullptr);
 }

@@ -41,15 +41,11 @@ struct StageL { MergeL merge; std::vector<BlockL> blocks; int C, heads, ws, res,
 
 // Which fused forms the schedule takes.  The workspace plan decides who owns the tensors a fusion removes and the executor decides who writes
 // them, so there is ONE value per C-ABI call: build_model fills Model::sch from the storage type and the dev switches, both read it there.
-struct Schedule { bool fuse_dw, fuse_dw_s2, fuse_dw_s1, fuse_bnbwd, fuse_bnbwd_epi, fuse_bngemm, fuse_pro, fuse_lncol, fuse_lnbn; };
+struct Schedule { bool fuse_dw_s2, fuse_dw_s1, fuse_bnbwd, fuse_bnbwd_epi, fuse_bngemm, fuse_pro, fuse_lncol, fuse_lnbn; };
 static Schedule schedule_flags(bool f32) {
     Schedule k;
-    // Fusing BatchNorm+GELU of the producer into the depthwise conv's input load removes one [M,C] write+read, but each input is
-    // loaded (and transformed) by its three neighbouring columns: the erf work triples and the conv turns VALU-bound
-    // (measured at 1024 images: +4.7 ms conv vs -2.7 ms elementwise) -> off by default, and always off in f32 storage.
-    k.fuse_dw = gg_dev_env("GG_FUSE_DW") != nullptr && !f32;
-    // the stride-2 depthwise conv of PatchMerging stages its input tile in LDS: BatchNorm1 + GELU are applied once per staged element
-    // (17x17 inputs per 8x8 outputs = 1.13x), the apply pass and the activation tensor disappear
+    // the stride-2 depthwise conv of PatchMerging walks down the map with a 3x3 window per output column: BatchNorm1 + GELU are applied to
+    // every loaded element (6 loads per step where 4 are new: 1.5 evaluations per input element), the apply pass and the activation tensor disappear
     k.fuse_dw_s2 = gg_dev_env("GG_NO_FUSE_DW_S2") == nullptr;
     // MBConv.conv2 likewise through the 4-columns-per-thread stride-1 kernel (1.5 BatchNorm+GELU evaluations per input element)
     k.fuse_dw_s1 = gg_dev_env("GG_NO_FUSE_DW_S1") == nullptr;
@@ -334,7 +330,7 @@ struct Layout {
 
 static int64_t bn_part_floats(int64_t M, int C, int B, int Ho, int Wo, bool dw) {
     const int rows = dw ? std::max(std::max(gg_dwconv_stat_rows(B, Ho, Wo, C, 1), gg_dwconv_stat_rows(B, Ho, Wo, C, 2)),
-                                   std::max(gg_dwconv_tiled_stat_rows(B, Ho), std::max(gg_dwconv_fused_stat_rows(B, Ho, Wo, C, 1), gg_dwconv_fwd_fused_stat_rows(B, Ho, Wo, C, 1))))
+                                   std::max(gg_dwconv_fused_stat_rows(B, Ho, Wo, C, 1), gg_dwconv_fwd_fused_stat_rows(B, Ho, Wo, C, 1)))
                         : gg_gemm_colstats_rows((int)M);
     return (int64_t)gg_stat_rows_capacity(rows) * 2 * C;
 }
@@ -342,7 +338,7 @@ static int64_t bn_part_floats(int64_t M, int C, int B, int Ho, int Wo, bool dw) 
 // The forward routes that decide who writes act1 / act2 of an MBConv or a PatchMerging: the plan gives those tensors their storage by the same
 // predicates the forward (and the backward, where it re-forms act1 for the tap gradient) takes its route by.
 // act1 = GELU(BN1(y1)) is never written by the forward: the depthwise conv (stride 1: MBConv, 2: PatchMerging) forms it while staging its input
-static bool act1_fused_away(const Schedule& k, int stride) { return k.fuse_dw || (stride == 1 ? k.fuse_dw_s1 : k.fuse_dw_s2); }
+static bool act1_fused_away(const Schedule& k, int stride) { return stride == 1 ? k.fuse_dw_s1 : k.fuse_dw_s2; }
 // MBConv conv3 reads BN2 + GELU of conv2's output through its A prologue and act2 is not written -- unless conv3's weight gradient needs that
 // tensor (w_trains: training and conv3.weight trainable; the plan keeps act2 then, and makes it a temporary otherwise whichever route is taken)
 static bool conv3_takes_prologue(const Schedule& k, const DenseW& w, int mid, bool w_trains) {

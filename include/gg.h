@@ -102,8 +102,10 @@ int gg_col2im_nhwc_bnbwd_bf16(const void* dcol, const void* y, const float* stat
                               float* part, int nparts, int B, int H, int W, int C, void* stream);
 int gg_col2im_nhwc_bnbwd_f32(const float* dcol, const float* y, const float* stat, const float* gamma, const float* beta, int act, float* dz,
                              float* part, int nparts, int B, int H, int W, int C /* % 4 */, void* stream);
+/* bf16 depthwise 3x3, one contract for C: a multiple of 8, <= 1024 (the widest depthwise conv of a supported model has 576 channels).
+   Every gg_dwconv3x3_* entry point below and every gg_dwconv_*_rows / _scratch_floats count checks it before anything else and refuses
+   any other C: -1 with gg_last_error() naming C (the counts return -1 too).  gg_dwconv3x3_s2_bwd_data_fused further needs C <= 768. */
 int gg_dwconv_stat_rows(int B, int Ho, int Wo, int C, int stride);   /* partial-statistics rows gg_dwconv3x3_fwd writes */
-int gg_dwconv_tiled_stat_rows(int B, int Ho);                          /* ... the producer-fused forward variant (LDS-tiled kernel) */
 int gg_dwconv_fused_stat_rows(int B, int H, int W, int C, int with_input_fusion);   /* ... the fused data gradient with ep_y */
 int gg_dwconv_fwd_fused_stat_rows(int B, int H, int W, int C, int stride);   /* ... the fused forward; H, W = input size */
 int gg_dwconv3x3_fwd(const void* x, const float* taps, void* y, int B, int H, int W, int C, int stride, float* colstats, void* stream);

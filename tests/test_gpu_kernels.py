@@ -390,7 +390,8 @@ def test_f32_col2im_fused_batchnorm_backward_reduce(ops, act, C, H):
     close(sums[1].float(), (dpre * xh.double()).sum((0, 1, 2)).float(), rtol=1e-4, atol=1e-3, what="f32 sum dz*xhat")
 
 
-@pytest.mark.parametrize("C,stride,H", [(16, 1, 12), (48, 2, 14), (384, 1, 8), (576, 2, 14), (40, 1, 7), (24, 2, 9), (64, 2, 15)])
+@pytest.mark.parametrize("C,stride,H", [(16, 1, 12), (48, 2, 14), (384, 1, 8), (576, 2, 14), (40, 1, 7), (24, 2, 9), (64, 2, 15),
+                                        (1024, 1, 5), (1024, 2, 6)])      # the bound of the C contract, once per route (stride 2: the generic data gradient)
 def test_dwconv(ops, C, stride, H):
     B = 3
     x = rnd(B, H, H, C, seed=20)

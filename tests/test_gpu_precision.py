@@ -103,7 +103,8 @@ def test_f32_gemm_tn_weight_gradient(ops, M, N, K, T):
 
 
 # ------------------------------------------------------------------------------------------- f32 spatial kernels
-@pytest.mark.parametrize("B,H,C,stride", [(2, 14, 384, 1), (3, 9, 64, 1), (2, 28, 192, 2), (2, 7, 576, 1), (1, 13, 40, 2), (2, 56, 24, 1)])
+@pytest.mark.parametrize("B,H,C,stride", [(2, 14, 384, 1), (3, 9, 64, 1), (2, 28, 192, 2), (2, 7, 576, 1), (1, 13, 40, 2), (2, 56, 24, 1),
+                                          (1, 5, 1024, 1), (1, 6, 1024, 2)])      # the widest C the depthwise family takes, once per route
 def test_f32_dwconv_forward_backward(ops, B, H, C, stride):
     x = rnd(B, H, H, C, seed=10)
     w = rnd(C, 1, 3, 3, seed=11, scale=0.4)

@@ -2,7 +2,8 @@
 the fallback the default schedule takes for shapes its fast kernels do not cover (channel counts that are not multiples of 4, single
 windows, K above the prologue table, leading dimensions that are not multiples of 32, ...).  This file runs the same training-step parity check the default path gets (tools/switch_parity.py:
 TinyViT-5M step vs the CPU oracle, fp32 and bf16 modes, per-tensor gradients) with the switches set, in groups, one subprocess per group
-(the library reads a switch once per process)."""
+(the library reads a switch once per process).  The depthwise 3x3 family has no kernel switch: it runs one kernel per route, and only its
+BatchNorm fusions (GG_NO_FUSE_DW_S1 / _S2, GG_NO_FUSE_BNBWD / _EPI) can be taken off."""
 import json
 import os
 import subprocess
@@ -14,16 +15,16 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 GROUPS = {
-    # every fusion off, every multi-column / multi-window / resident / ring form replaced by its plain fallback
+    # every fusion off, every multi-window / resident / ring form replaced by its plain fallback
     "plain_fallbacks": dict(GG_NO_FUSE_DW_S1="1", GG_NO_FUSE_DW_S2="1", GG_NO_FUSE_BNBWD="1", GG_NO_BNGEMM="1", GG_NO_PRO="1", GG_F32_NO_FUSE="1", GG_NO_LN_COLSUM="1",
-                            GG_DW_NO_MULTI="1", GG_DW_F32_NO_MULTI="1", GG_ATTN_SMALL="0", GG_ATTN_FLASH_NO_RES="1", GG_ATTN_DQ_QS1="1",
+                            GG_ATTN_SMALL="0", GG_ATTN_FLASH_NO_RES="1", GG_ATTN_DQ_QS1="1",
                             GG_GEMM_F32_ROWS_EPI="0", GG_ATTN_NO_DS_SCRATCH="1", GG_ATTN_NO_FUSED_BWD="1", GG_ATTN_FWD_NO_TAIL="1", GG_GEMM_F32_PRO_RING="0", GG_GEMM_F32_NO_W96="1",
                             GG_ATTN_NO_SPLIT="1", GG_GEMM_DMA="0", GG_GEMM_TILE="n", GG_GEMM_F32_NO_SMALL="1", GG_SWITCH_PARITY_FROZEN="1"),
-    # the older kernel generation: LDS-tiled depthwise, one-column fused forward, the fp32 GEMM's general epilogue with 64-byte-run stores, the
+    # the older kernel generation: the depthwise data gradient without its act'(BN) epilogue, the fp32 GEMM's general epilogue with 64-byte-run stores, the
     # register-staged prologue GEMMs (the form K > 384 takes; GG_GEMM_F32_NO_PERSIST gives them one workgroup per tile -- at this test's shapes the
     # grid is below their resident count either way, so it is exercised, not distinguished)
-    "older_kernels": dict(GG_DW_TILED="1", GG_FUSE_DW="1", GG_NO_FUSE_BNBWD_EPI="1", GG_GEMM_F32_ROWS_EPI="0", GG_GEMM_F32_PRO_RING="0", GG_GEMM_F32_NO_PERSIST="1",
-                          GG_GEMM_F32_NO_PAIR_STORE="1", GG_DW_NO_MULTI_PLAIN="1", GG_DW_NO_MULTI_BWD="1", GG_DW_S2_TILED="1", GG_GEMM_TILE="w",
+    "older_kernels": dict(GG_NO_FUSE_BNBWD_EPI="1", GG_GEMM_F32_ROWS_EPI="0", GG_GEMM_F32_PRO_RING="0", GG_GEMM_F32_NO_PERSIST="1",
+                          GG_GEMM_F32_NO_PAIR_STORE="1", GG_GEMM_TILE="w",
                           GG_ATTN_NO_FUSED_BWD="1", GG_ATTN_NO_SPLIT="1", GG_GEMM_F32_NO_SPLITK="1", GG_GEMM_F32_SMALL_MAX="64", GG_SWITCH_PARITY_FROZEN="1"),       # (two-pass attention backward with the dS hand-off: the form for windows beyond 256 tokens)
     # the single-pass attention backward with one wave per key strip (no cooperative tail strip): the form every window whose strip count is not 4 n + 1 takes
     "attention_no_tail": dict(GG_ATTN_FUSED_NO_TAIL="1", GG_ATTN_NO_SPLIT="1", GG_SWITCH_PARITY_FROZEN="1"),

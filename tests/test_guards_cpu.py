@@ -126,12 +126,48 @@ EXEMPT = {
                          "gg_dwconv_s2_fused_stat_rows", "gg_dwconv_wgrad_scratch_floats", "gg_dwconv_f32_stat_rows", "gg_dwconv_f32_s2_fused_stat_rows",
                          "gg_dwconv_f32_wgrad_scratch_floats", "gg_preprocess_pil_workspace_bytes", "gg_tinyvit_wcache_bytes", "gg_tinyvit_workspace_bytes",
                          "gg_tinyvit_workspace_bytes_masked", "gg_clip_wcache_bytes", "gg_clip_workspace_bytes")},
-    "gg_dwconv_tiled_stat_rows": "capacity function of the library's own producer-fused forward variant: no exported entry point takes a buffer sized by it",
     **{n: "gg_prof_*: host-side launch log, no caller tensor" for n in ("gg_prof_enable", "gg_prof_reset", "gg_prof_read", "gg_prof_count", "gg_prof_record")},
     **{n: "gg_graph_*: graph-cache control, no caller tensor (replay itself is covered by the whole-step tests)" for n in ("gg_graph_set_mode", "gg_graph_stats", "gg_graph_clear")},
     **{n: "gg_comm_*: RCCL collectives over a communicator; needs several ranks (tests/test_gpu_distributed.py)" for n in
        ("gg_comm_unique_id", "gg_comm_create", "gg_comm_destroy", "gg_comm_rank", "gg_comm_world", "gg_comm_allreduce_sum_f32", "gg_comm_broadcast", "gg_comm_barrier")},
 }
+
+
+@pytest.mark.parametrize("Cc", [1032, 12])
+def test_bf16_depthwise_channel_contract_is_refused_before_the_device(Cc):
+    """include/gg.h: the bf16 depthwise family takes C % 8 == 0, C <= 1024 and nothing else.  Every entry point refuses the first multiple of 8 above the bound and
+    a C that is no multiple of 8 with gg_last_error() naming C, and every row / scratch count answers negative -- on a machine without a GPU and with pointers
+    that are never dereferenced, so the check comes before anything touches the device.  The counts still answer at both ends of the contract."""
+    import ctypes as C
+    from geoguessr_ai_amd import _lib as L
+    lib = L.lib()
+    buf = C.create_string_buffer(256)
+    p = C.cast(buf, C.c_void_p)
+    B, H, W = 1, 6, 6
+    entries = {
+        "gg_dwconv3x3_fwd": lambda s: lib.gg_dwconv3x3_fwd(p, p, p, B, H, W, Cc, s, p, None),
+        "gg_dwconv3x3_fwd_fused": lambda s: lib.gg_dwconv3x3_fwd_fused(p, p, p, p, 1, p, p, B, H, W, Cc, s, p, None),
+        "gg_dwconv3x3_bwd_data": lambda s: lib.gg_dwconv3x3_bwd_data(p, p, p, B, H, W, Cc, s, None),
+        "gg_dwconv3x3_bwd_data_fused": lambda s: lib.gg_dwconv3x3_bwd_data_fused(p, p, p, p, p, B, H, W, Cc, p, p, p, p, 1, p, None),
+        "gg_dwconv3x3_s2_bwd_data_fused": lambda s: lib.gg_dwconv3x3_s2_bwd_data_fused(p, p, p, p, p, B, H, W, Cc, p, p, p, p, 1, p, None),
+        "gg_dwconv3x3_bwd_weight": lambda s: lib.gg_dwconv3x3_bwd_weight(p, p, B, H, W, Cc, s, p, p, 0, None),
+    }
+    counts = {
+        "gg_dwconv_stat_rows": lambda c, s: lib.gg_dwconv_stat_rows(B, H, W, c, s),
+        "gg_dwconv_fwd_fused_stat_rows": lambda c, s: lib.gg_dwconv_fwd_fused_stat_rows(B, H, W, c, s),
+        "gg_dwconv_fused_stat_rows": lambda c, s: lib.gg_dwconv_fused_stat_rows(B, H, W, c, 1),
+        "gg_dwconv_s2_fused_stat_rows": lambda c, s: lib.gg_dwconv_s2_fused_stat_rows(B, H, W, c),
+        "gg_dwconv_wgrad_scratch_floats": lambda c, s: lib.gg_dwconv_wgrad_scratch_floats(B, H, W, c, s),
+    }
+    for stride in (1, 2):
+        for name, call in entries.items():
+            assert call(stride) != 0, (name, stride)
+            err = lib.gg_last_error()
+            assert name.encode() in err and f"C = {Cc}".encode() in err, (name, stride, err)
+        for name, call in counts.items():
+            assert call(Cc, stride) < 0, (name, stride)
+            assert f"C = {Cc}".encode() in lib.gg_last_error(), (name, stride)
+            assert call(8, stride) > 0 and call(1024, stride) > 0, (name, stride)
 
 
 def _declared():

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Depthwise 3x3 kernel timing at the TinyViT-21M-224 / 1024-image shapes (dev tool).  GG_DW_TILED=1 selects the LDS-tiled kernel."""
+"""Depthwise 3x3 kernel timing at the TinyViT-21M-224 / 1024-image shapes (dev tool)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

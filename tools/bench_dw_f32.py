@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""dev: fp32 depthwise 3x3 stride-1 kernels at the TinyViT-21M-224 / 1024-image shapes (GG_DW_F32_NO_MULTI=1: one-column kernel)."""
+"""dev: fp32 depthwise 3x3 stride-1 kernels at the TinyViT-21M-224 / 1024-image shapes."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
