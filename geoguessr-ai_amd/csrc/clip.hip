@@ -34,6 +34,8 @@
 #include "../../include/gg_clip_text.h"
 #include "../../include/gg_clip_text_train.h"
 #include "../../include/gg_fp8.h"
+#include "../../include/gg_attn16.h"
+#include <atomic>
 
 namespace {
 struct TInfo { std::string name; int64_t offset, numel; int ndim; int64_t shape[4]; };
@@ -393,6 +395,7 @@ static void plan(const CModel& m, int B, const Train& tr, bool training, CPlan& 
 struct Exec {
     const CModel* m; const CPlan* L; int B; hipStream_t st;
     const float* params; const char* wc; char* ws; float* grads; const uint8_t* mask;
+    bool attn16 = false;      // gg_clip_forward, inference, switch on (gg_clip_set_attention16), a 16-bit vision tower beyond 256 tokens: attention through gg_attention_flash16_fwd
     const float* P(int t) const { return params + m->t[t].offset; }
     float* Gd(int t) const { return grads + m->t[t].offset; }
     bool tr(int t) const { return mask == nullptr || mask[t] != 0; }
@@ -502,7 +505,8 @@ static int layer_fwd(const Exec& e, int i, int64_t cur, int64_t next, bool sv) {
         GG_TRY(e.gemm8(l.wqkv8, l.sqkv, e.A(QKV), 3 * D, M, 3 * D, D, (const float*)e.W(l.bqkv)));
         GgAttnArgs at8;
         e.attn_args(at8, e.A(QKV), e.A(O), nullptr);
-        GG_TRY(gg_attention_fwd_f16(&at8, e.st));
+        if (e.attn16) GG_TRY(gg_attention_flash16_fwd(&at8, 2, e.st));
+        else GG_TRY(gg_attention_fwd_f16(&at8, e.st));
         GG_TRY(e.quant8(e.A(O), M, D));
         GG_TRY(e.gemm8(l.wo8, l.so, e.A(XMID), D, M, D, D, e.P(l.o_b), 0, e.A(cur)));
         GG_TRY(e.ln_fwd8(e.A(XMID), l.ln2_g, l.ln2_b, M));
@@ -517,6 +521,7 @@ static int layer_fwd(const Exec& e, int i, int64_t cur, int64_t next, bool sv) {
     e.attn_args(at, e.A(QKV), e.A(O), sv ? e.F(a.lse) : nullptr);
     if (m.causal) GG_TRY(gg_attention_causal_fwd(&at, m.split ? 3 : m.f32 ? 1 : 0, e.st));      // the text tower
     else if (m.split) GG_TRY(gg_attention_flash_fwd(&at, 3, e.st));      // split products at every token count
+    else if (e.attn16 && !sv) GG_TRY(gg_attention_flash16_fwd(&at, m.f16 ? 2 : 0, e.st));      // opt-in: both products on the 16-bit MFMA (include/gg_attn16.h)
     else if (m.f16) GG_TRY(gg_attention_fwd_f16(&at, e.st));      // fp16 MFMA for towers of at most 256 tokens (ViT-B/32: 50); beyond: fp16 storage, f32 arithmetic
     else if (m.f32 || sv || T > 256) GG_TRY(gg_attention_flash_fwd(&at, m.f32 ? 1 : 0, e.st));
     else GG_TRY(gg_attention_fwd(&at, e.st));
@@ -721,6 +726,10 @@ static int refresh_model(const CModel& m, const float* params, void* wcache, con
     return 0;
 }
 
+// the opt-in long-row attention of the inference forward (include/gg_attn16.h); process-wide like tinyvit.hip's g_drop_compact
+static std::atomic<int> g_attention16{0};
+extern "C" int gg_clip_set_attention16(int on) { return g_attention16.exchange(on != 0 ? 1 : 0); }
+
 extern "C" int gg_clip_forward(const GgClipCfg* cfg, int batch, int training, const float* params, const void* wcache, const float* x, void* workspace,
                                float* out, float* last_hidden, const uint8_t* trainable, void* stream) {
     CModel m;
@@ -732,6 +741,7 @@ extern "C" int gg_clip_forward(const GgClipCfg* cfg, int batch, int training, co
     GG_CHECK(!(m.f16 && training && tr.l0 < m.cfg.num_layers), "gg_clip_forward: the fp16 mode is inference-only (train in fp32 or bf16)");
     CPlan L; plan(m, batch, tr, training != 0, L);
     Exec e{&m, &L, batch, (hipStream_t)stream, params, (const char*)wcache, (char*)workspace, nullptr, trainable};
+    e.attn16 = !training && g_attention16.load() != 0 && !m.causal && !m.f32 && m.T > 256;      // (m.f32 covers fp32 and fp32_split; fp8 is an fp16 mode)
     const int D = m.cfg.hidden_size, T = m.T, B = batch, nl = m.cfg.num_layers;
     const int64_t M = (int64_t)B * T;
     const bool keep = training && tr.l0 < nl;

@@ -569,6 +569,30 @@ def attention_flash(qkv, *, num_windows, tokens_per_window, num_heads, head_dim,
     return dqkv, dbias
 
 
+def attention_flash16(qkv, *, num_windows, tokens_per_window, num_heads, q_off, k_off, v_off, head_stride, head_dim=64, window_size=0, scale=None,
+                      want_lse=False, out=None):
+    """Online-softmax attention forward with both products on the 16-bit MFMA (include/gg_attn16.h): bf16 or fp16 storage by ``qkv.dtype``, head dim 64, linear
+    tokens, any ``tokens_per_window``, no bias.  Forward only; returns out, or (out, lse) with ``want_lse``.  ``out`` (optional): a (tokens, >= heads * 64) buffer
+    of the storage type to write into (its row stride is the output pitch)."""
+    L.require_gpu()
+    DT = qkv.dtype
+    if DT not in (BF16, torch.float16):
+        raise L.GgError(f"attention_flash16: bf16 or fp16 storage (got {DT})")
+    a = L.AttnArgs()
+    a.qkv, a.ld = _pr(qkv, DT, "qkv"), qkv.stride(0)      # rows may be strided: a column slice of a wider buffer
+    a.q_off, a.k_off, a.v_off, a.head_stride, a.head_dim = q_off, k_off, v_off, head_stride, head_dim
+    a.num_heads, a.num_windows, a.tokens_per_window, a.window_size = num_heads, num_windows, tokens_per_window, window_size
+    a.scale = head_dim ** -0.5 if scale is None else scale
+    tokens = qkv.shape[0]
+    if out is None:
+        out = torch.empty((tokens, num_heads * head_dim), dtype=DT, device=qkv.device)
+    a.out, a.ldo = _pr(out, DT, "out"), out.stride(0)
+    lse_t = torch.empty((tokens, num_heads), dtype=F32, device=qkv.device) if want_lse else None
+    a.lse = _p(lse_t)
+    L.check(L.lib().gg_attention_flash16_fwd(C.byref(a), 2 if DT == torch.float16 else 0, L.stream()), "gg_attention_flash16_fwd")
+    return (out, lse_t) if want_lse else out
+
+
 def attention(qkv, *, num_windows, tokens_per_window, num_heads, head_dim, q_off, k_off, v_off, head_stride,
               window_size=0, map_h=0, map_w=0, bias=None, scale=None, dout=None, want_dbias=False, out=None, lse=None,
               want_lse=False):

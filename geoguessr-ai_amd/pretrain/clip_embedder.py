@@ -13,7 +13,9 @@
 Arithmetic: ``precision="fp32"`` (default; the reference runs the tower in fp32), ``"fp32_split"`` (f32 storage, every GEMM and the attention as
 f32-accurate split-bf16 products: ``GgClipCfg.act_dtype`` 3), ``"bf16"``, ``"fp16"`` (inference only: the precision BASELINE
 config c4 names), or ``"fp8"`` (inference only: fp16's storage and schedule with the four Linears of every encoder layer as W8A8 e4m3 products,
-``GgClipCfg.act_dtype`` 8, include/gg_fp8.h; resolved by ``tower_precision_code``); the default is ``$GG_PRECISION``.  No hub download: weights come from a
+``GgClipCfg.act_dtype`` 8, include/gg_fp8.h; resolved by ``tower_precision_code``); the default is ``$GG_PRECISION``.  ``attention16=True`` (bf16, fp16 and fp8; opt-in,
+not in the reference): the inference forward of a tower beyond 256 tokens (ViT-L/14-336: 577) runs its attention with both products on the 16-bit MFMA
+(``gg_attention_flash16_fwd``, include/gg_attn16.h) instead of the f32-MFMA online-softmax kernel; training forwards are unaffected.  No hub download: weights come from a
 state dict (HF names, with or without the leading ``vision_model.``)."""
 from __future__ import annotations
 
@@ -60,6 +62,13 @@ def tower_precision_code(precision: Optional[str]) -> int:
         raise ValueError(f"{e}; CLIPVisionTower / CLIPEmbedding also take fp8") from None
 
 
+def check_attention16(attention16: bool, code: int, who: str) -> None:
+    """``attention16=True`` is a switch of the 16-bit modes: refused by name for ``fp32`` and ``fp32_split`` (their attention is f32-accurate by contract)."""
+    if attention16 and code in (1, 3):
+        raise L.GgError(f"{who}: attention16=True is a switch of the bf16, fp16 and fp8 modes; precision='{PRECISION_NAMES[code]}' keeps its f32-accurate attention "
+                        "(leave attention16 off)")
+
+
 class _VisionModel(EncoderRuntime):
     """``vision_model`` of the HF module tree: owner of the flat storage and of the HIP workspace.  Its children (``embeddings``, ``pre_layrnorm``,
     ``encoder.layers.N....``, ``post_layernorm``) are rebuilt from the tensor names, so ``encoder.layers[i].parameters()`` is what
@@ -67,6 +76,7 @@ class _VisionModel(EncoderRuntime):
     _name, _switch = "CLIP", "gradient_checkpointing"
     _mask_changed = "requires_grad changed between the CLIP forward and its backward; run the forward again"
     _toggled_gen = None               # generation of a training forward that a gradient_checkpointing toggle made the runtime forget
+    attention16 = False               # CLIPVisionTower(attention16=True): this tower's forwards run with gg_clip_set_attention16(1)
 
     def __init__(self, cfg: L.ClipCfg, seed: int):
         super().__init__()
@@ -131,8 +141,15 @@ class _VisionModel(EncoderRuntime):
         D, T = self.cfg.hidden_size, (S // self.cfg.patch_size) ** 2 + 1
         out = torch.empty((B, D), dtype=torch.float32, device=x.device)
         last = torch.empty((B, T, D), dtype=torch.float32, device=x.device) if return_last_hidden else None
-        L.check(L.lib().gg_clip_forward(C.byref(self.cfg), B, int(training), L.ptr(self._flat), L.ptr(self._wcache), L.ptr(x), L.ptr(ws), L.ptr(out),
-                                        L.ptr(last), mask, L.stream()), "gg_clip_forward")
+        lib = L.lib()
+        prev = lib.gg_clip_set_attention16(1) if self.attention16 else None      # process-wide switch, read when the forward is enqueued: set for this call only
+        try:
+            rc = lib.gg_clip_forward(C.byref(self.cfg), B, int(training), L.ptr(self._flat), L.ptr(self._wcache), L.ptr(x), L.ptr(ws), L.ptr(out),
+                                     L.ptr(last), mask, L.stream())
+        finally:
+            if prev is not None:
+                lib.gg_clip_set_attention16(prev)
+        L.check(rc, "gg_clip_forward")
         if training:
             self._record_forward(B, mask)
         return out, last
@@ -153,10 +170,11 @@ class CLIPVisionTower(nn.Module):
     supports_gradient_checkpointing = True          # (transformers PreTrainedModel's class attribute)
 
     def __init__(self, model_name: str = "openai/clip-vit-base-patch32", seed: int = 0, precision: Optional[str] = None,
-                 gradient_checkpointing: bool = False, **cfg_overrides):
+                 gradient_checkpointing: bool = False, attention16: bool = False, **cfg_overrides):
         super().__init__()
         kw = dict(CLIP_CONFIGS.get(model_name, CLIP_CONFIGS["openai/clip-vit-base-patch32"]))
         kw.update(cfg_overrides)
+        check_attention16(attention16, tower_precision_code(precision), "CLIPVisionTower")
         c = L.ClipCfg()
         c.hidden_size, c.intermediate_size, c.num_layers, c.num_heads = kw["hidden_size"], kw["intermediate_size"], kw["num_layers"], kw["num_heads"]
         c.image_size, c.patch_size, c.ln_eps = kw["image_size"], kw["patch_size"], 1e-5
@@ -166,6 +184,7 @@ class CLIPVisionTower(nn.Module):
         self.precision = PRECISION_NAMES[c.act_dtype]
         self.config = SimpleNamespace(hidden_size=kw["hidden_size"], _name_or_path=model_name, **{k: v for k, v in kw.items() if k != "hidden_size"})
         self.vision_model = _VisionModel(c, seed)
+        self.attention16 = self.vision_model.attention16 = bool(attention16)
         self.num_tokens = (c.image_size // c.patch_size) ** 2 + 1
 
     # ---- activation recompute -----------------------------------------------------------------------------------------------------------
@@ -242,18 +261,21 @@ def clip_preprocess(images, size: int, device) -> Tensor:
 class CLIPEmbedding(nn.Module):
     def __init__(self, model_name: str = "openai/clip-vit-base-patch32", device: str = "cuda", load_checkpoint: bool = False,
                  panorama: bool = False, state_dict: Optional[Dict[str, Tensor]] = None, precision: Optional[str] = None, batch_transform: bool = False,
-                 jpeg_split_bytes: int = 0, **cfg_overrides):
+                 jpeg_split_bytes: int = 0, attention16: bool = False, **cfg_overrides):
         """``batch_transform`` (not in the reference): raw images -- a list of any sizes, or the four panorama views together -- go through ONE ``gg_eval_batch``
         call (``training.preprocess.DeviceEvalTransform``) instead of one ``gg_preprocess_pil`` call per image; same arithmetic.  ``jpeg_split_bytes`` (with
-        ``batch_transform`` only): the ``split_bytes`` of the decoder that takes JPEG files given as bytes (``DeviceEvalTransform``'s keyword)."""
+        ``batch_transform`` only): the ``split_bytes`` of the decoder that takes JPEG files given as bytes (``DeviceEvalTransform``'s keyword).  ``attention16``:
+        ``CLIPVisionTower``'s keyword (opt-in 16-bit-MFMA attention beyond 256 tokens; refused for fp32 / fp32_split)."""
         super().__init__()
+        check_attention16(attention16, tower_precision_code(precision), "CLIPEmbedding")
         self.device = device
         self.batch_transform, self._transform = bool(batch_transform), None
         if jpeg_split_bytes and not batch_transform:
             raise ValueError("CLIPEmbedding: jpeg_split_bytes needs batch_transform=True")
         self.jpeg_split_bytes = int(jpeg_split_bytes)
         self.panorama = panorama
-        self.clip_model = CLIPVisionTower(model_name if not load_checkpoint else "openai/clip-vit-base-patch32", precision=precision, **cfg_overrides)
+        self.clip_model = CLIPVisionTower(model_name if not load_checkpoint else "openai/clip-vit-base-patch32", precision=precision, attention16=attention16,
+                                          **cfg_overrides)
         if load_checkpoint:
             state_dict = torch.load(model_name, map_location="cpu")
             print("Loaded embedder from checkpoint:", model_name)

@@ -11,7 +11,8 @@
  *     hooks (gg_prof_*: off unless enabled), and lazily allocated 16 MiB split-K slab buffers of gg_gemm_nt_f32: one per (device, stream) that issued the form, at
  *     most 8 (least recently used released), plus one per captured graph whose launches use the form; gg_graph_clear() releases them all.  Under a CALLER's own
  *     stream capture no slab can be handed out and the form runs unsplit (same product, different rounding than the eager call); and the DropPath row-compaction
- *     switch gg_tinyvit_set_drop_compact of include/gg_drop.h (default on; it selects between two schedules of the fp32_split TinyViT training step whose results are bit-identical);
+ *     switch gg_tinyvit_set_drop_compact of include/gg_drop.h (default on; it selects between two schedules of the fp32_split TinyViT training step whose results are bit-identical).  One process-global switch DOES change a result, and is off unless
+ *     a caller sets it: gg_clip_set_attention16 of include/gg_attn16.h (the attention kernel of the CLIP vision tower's 16-bit inference forward beyond 256 tokens);
  *   - `stream` is a hipStream_t; work is only enqueued, nothing here synchronises;
  *   - bf16 tensors are passed as void*; matrices are row-major with an explicit leading dimension
  *     in ELEMENTS; activations are NHWC / [tokens, channels].
