@@ -88,8 +88,9 @@ static inline int64_t gg_align(int64_t a, int64_t b) { return gg_cdiv(a, b) * b;
 
 // ---- device math ---------------------------------------------------------------
 // erf(x/sqrt2) as an odd polynomial u*P(u^2), u = |x|/sqrt2, fitted on [0, 3] and clamped to 1 on the way out (least-squares Chebyshev fit, degree 17): no
-// transcendental, and the FMAs pair up into v_pk_fma_f32.  |erf error| <= 2.1e-5 (1 - erf(3) = 2.2e-5 is the clamp),
-// i.e. |GELU error| <= 4.4e-5 absolute, 100x below the bf16 resolution every GELU result is stored with.  libm erff
+// transcendental, and the FMAs pair up into v_pk_fma_f32.  |erf error| <= 2.3e-5: the polynomial crosses 1 near u = 3 (where exactly depends on the rounding of
+// each step), the clamp takes over from there, and 1 - erf(3) = 2.21e-5; i.e. |GELU error| <= 3 sqrt2 / 2 x 2.21e-5 = 4.7e-5 absolute (reached just past
+// |x| = 4.243; tests/act_cases.py restates the form and measures it), 100x below the bf16 resolution every GELU result is stored with.  libm erff
 // and the Abramowitz-Stegun form (rcp + exp) cost 5x / 2.5x more VALU and made the GELU epilogues, not HBM or MFMA,
 // the limiter of the fc1 GEMMs and the BatchNorm+GELU kernels (19 G evaluations per 1024-image step).
 __device__ __forceinline__ float gg_erf_sqrt2(float x) {
@@ -139,7 +140,8 @@ __device__ __forceinline__ float gg_act_f32(float x, int act) {
 }
 __device__ __forceinline__ float gg_act_grad_f32(float x, int act) {
     if (act == 1) return gg_gelu_grad_f32(x);
-    if (act == 2) { const float sg = 1.0f / (1.0f + __expf(-1.702f * x)); return sg + 1.702f * x * sg * (1.0f - sg); }
+    // (the product term's argument is clamped: 1.702 x overflows for |x| > 2e38 and inf * 0 is NaN; sg (1 - sg) is exactly 0 from |x| = 62 on -- sg is 1, or has underflowed to 0 -- so no other result moves)
+    if (act == 2) { const float sg = 1.0f / (1.0f + __expf(-1.702f * x)); return sg + 1.702f * __builtin_amdgcn_fmed3f(x, -1e30f, 1e30f) * sg * (1.0f - sg); }
     return 1.0f;
 }
 // The same fp32 activations four at a time.  The polynomial of Phi runs on float2 values, i.e. as v_pk_fma_f32 (two elements per VALU slot; the
@@ -192,7 +194,7 @@ __device__ __forceinline__ float gg_gelu_grad_exp(float x) {       // Phi-polyno
 __device__ __forceinline__ float gg_quick_gelu(float x) { return x * __frcp_rn(1.0f + __expf(-1.702f * x)); }
 __device__ __forceinline__ float gg_quick_gelu_grad(float x) {
     const float s = __frcp_rn(1.0f + __expf(-1.702f * x));
-    return s + 1.702f * x * s * (1.0f - s);
+    return s + 1.702f * __builtin_amdgcn_fmed3f(x, -1e30f, 1e30f) * s * (1.0f - s);      // (clamped: see gg_act_grad_f32)
 }
 // ---- two-at-a-time forms: every multiply-add below is a v_pk_fma_f32 (2 lanes of work per VALU slot) --------------
 // The GELU epilogues and BatchNorm(+GELU) passes are VALU-bound once their memory traffic is fused away, so the hot
@@ -222,7 +224,8 @@ __device__ __forceinline__ f32x2 gg_gelu_v2(f32x2 x) {
 }
 // GELU'(x) = Phi(x) + x*phi(x) = 0.5 + u*Q(s), u = clamp(x, +-4.75), s = 2u^2/4.75^2 - 1  (odd part fitted directly,
 // degree 23, Horner in the centred variable; |error| <= 1.2e-5 incl. fp32 evaluation; beyond the clamp GELU' is 0 / 1
-// to 2.4e-5).  No exp, no erf: 8 VALU slots per element against 25 for Phi-polynomial + exp.
+// to 2.4e-5: the form returns -1.16e-5 for every finite x below -4.75 and 1.0000116 above 4.75; NaN for NaN and for +-inf, see `half` below).  No exp, no erf:
+// 8 VALU slots per element (9 with `half`) against 25 for Phi-polynomial + exp.
 __device__ __forceinline__ f32x2 gg_gelu_grad_v2(f32x2 x) {
     const f32x2 u = gg_clamp2(x, 4.75f);
     const f32x2 s = (u * u) * 8.864265928e-02f + (f32x2)(-1.0f);
@@ -238,7 +241,10 @@ __device__ __forceinline__ f32x2 gg_gelu_grad_v2(f32x2 x) {
     p = p * s + (f32x2)(7.598317362e-02f);
     p = p * s + (f32x2)(-8.164826059e-02f);
     p = p * s + (f32x2)(1.501617604e-01f);
-    return p * u + (f32x2)(0.5f);
+    // 0.5 exactly for a finite x; NaN for NaN (and for +-inf, where the limit 0 / 1 is given up): the clamp (v_med3_f32) alone would turn NaN into -4.75.  Holds only
+    // while the build honours NaN (no -ffast-math / -ffinite-math-only: the Makefile sets -ffp-contract=fast alone); tests/test_gpu_act_sites.py feeds NaN to every site
+    const f32x2 half = x * (f32x2)(0.0f) + (f32x2)(0.5f);
+    return p * u + half;
 }
 __device__ __forceinline__ float gg_gelu_grad(float x) { return gg_gelu_grad_v2((f32x2){x, x}).x; }
 // act codes shared by GEMM epilogues and norm kernels

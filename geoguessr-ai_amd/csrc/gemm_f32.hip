@@ -204,7 +204,7 @@ __device__ __forceinline__ void gemm_f32_epilogue(const F32GemmParams& p, float*
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
                                 const float sg = 1.0f / (1.0f + expf(-1.702f * h[r]));
-                                v[r] *= (sg + 1.702f * h[r] * sg * (1.0f - sg)) * rs;
+                                v[r] *= (sg + 1.702f * __builtin_amdgcn_fmed3f(h[r], -1e30f, 1e30f) * sg * (1.0f - sg)) * rs;
                             }
                         } else {
                             v *= gg_act_grad_f32_v4(h, GG_ACT_GELU) * rs;
@@ -416,7 +416,7 @@ __device__ __forceinline__ void gemm_f32_epilogue_rows(const F32GemmParams& p, f
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
                                 const float sg = 1.0f / (1.0f + expf(-1.702f * h[r]));
-                                v[r] *= (sg + 1.702f * h[r] * sg * (1.0f - sg)) * rs;
+                                v[r] *= (sg + 1.702f * __builtin_amdgcn_fmed3f(h[r], -1e30f, 1e30f) * sg * (1.0f - sg)) * rs;
                             }
                         } else {
                             v *= gg_act_grad_f32_v4(h, GG_ACT_GELU) * rs;

@@ -54,57 +54,6 @@ struct Split3Params {
 // what the row epilogues need of the compaction: live rows, the C / residual row map, the map of the row-scale index (c_map, else a_map)
 struct S3RowMap { int M; const int* cmap; const int* smap; int rps; };
 
-// one 4-column group of one row in the MFMA result layout (lane: row m, columns n .. n + 3)
-__device__ __forceinline__ void split3_epilogue4(const Split3Params& p, f32x4 v, int m, int n) {
-    if (m >= p.M || n >= p.N) return;
-    const bool full = n + 3 < p.N;
-    if (p.bias) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) if (n + r < p.N) v[r] += p.bias[n + r];
-    }
-    auto ld4 = [&](const float* base, int64_t ld) {
-        f32x4 t = {0.f, 0.f, 0.f, 0.f};
-        const float* q = base + (int64_t)m * ld + n;
-        if (full && (ld & 3) == 0) t = *reinterpret_cast<const f32x4*>(q);
-        else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) if (n + r < p.N) t[r] = q[r];
-        }
-        return t;
-    };
-    auto st4 = [&](float* base, int64_t ld, f32x4 t) {
-        float* q = base + (int64_t)m * ld + n;
-        if (full && (ld & 3) == 0) *reinterpret_cast<f32x4*>(q) = t;
-        else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) if (n + r < p.N) q[r] = t[r];
-        }
-    };
-    if (p.preact) st4(p.preact, p.ldc, v);
-    if (p.dact_preact) v = v * gg_act_grad_f32_v4(ld4(p.dact_preact, p.ldc), p.dact);
-    else if (p.act) v = gg_act_f32_v4(v, p.act);
-    if (p.rowscale) v = v * p.rowscale[m / p.rows_per_scale];
-    if (p.residual) v = v + ld4(p.residual, p.ldr);
-    if (p.C) st4(p.C, p.ldc, v);
-    if (p.c_planes) {
-        bf16x4 p1, p2, p3;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            bf16 s1_, s2_, s3_;
-            gg_split3_rne(v[r], s1_, s2_, s3_);
-            p1[r] = s1_; p2[r] = s2_; p3[r] = s3_;
-        }
-        bf16* q = p.c_planes + (int64_t)m * p.ldp + n;
-        const int64_t plane = (int64_t)p.M * p.ldp;
-        if (full && (p.ldp & 3) == 0) {
-            *reinterpret_cast<bf16x4*>(q) = p1; *reinterpret_cast<bf16x4*>(q + plane) = p2; *reinterpret_cast<bf16x4*>(q + 2 * plane) = p3;
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) if (n + r < p.N) { q[r] = p1[r]; q[plane + r] = p2[r]; q[2 * plane + r] = p3[r]; }
-        }
-    }
-}
-
 // Epilogue classes known at compile time (EC; the host picks one when the shape allows the vector path: N % 8 == 0, row pitches % 4 == 0): the generic row epilogue
 // below decides bias / activation / row scale / residual / planes / statistics per row behind ~40 runtime branches, and the compiler cannot move a row's global loads across
 // them.  Here the aux rows a thread needs (the saved pre-activation of the GELU' data gradient, the residual) are ALL requested before the first tile row is touched (8 rows
@@ -455,7 +404,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_split3_kernel(Split3Para
     }
     // epilogue: lane holds C[m = m0 + (BM / WM) wm + 16 mt + lr][n = n0 + (BN / WN) wn + 16 nt + 4 lg + r]
     constexpr bool ROWS = (size_t)BM * (BN + 4) * 4 <= (size_t)NST * STAGE * 2;      // the idle ring holds the f32 tile: row-layout epilogue
-    if constexpr (ROWS) {
+    static_assert(ROWS, "both tile forms of this kernel leave a ring that holds the f32 tile");
+    {
         float* Ct = reinterpret_cast<float*>(s3mem);
         __builtin_amdgcn_s_barrier();                             // every wave has read its last fragments: the ring is free
 #pragma unroll
@@ -465,12 +415,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_split3_kernel(Split3Para
                 *reinterpret_cast<f32x4*>(Ct + (wm * (BM / WM) + mt * 16 + lr) * (BN + 4) + wn * (BN / WN) + nt * 16 + lg * 4) = acc[nt][mt];
         __syncthreads();
         split3_epilogue_rows<BM, BN, 64 * NW>(p, Ct, m0, n0);
-    } else {
-#pragma unroll
-        for (int nt = 0; nt < TN; ++nt)
-#pragma unroll
-            for (int mt = 0; mt < TM; ++mt)
-                split3_epilogue4(p, acc[nt][mt], m0 + wm * (BM / WM) + mt * 16 + lr, n0 + wn * (BN / WN) + nt * 16 + lg * 4);
     }
 }
 

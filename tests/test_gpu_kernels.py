@@ -828,11 +828,11 @@ def test_split3_gemm_batchnorm_partials(M, N, K):
     assert torch.equal(stats, stats2) and torch.equal(out, out2)            # no atomics: repeatable
 
 
-@pytest.mark.parametrize("M,N,K,act", [(1000, 96, 384, 1), (700, 200, 416, 1), (513, 96, 1024, 0), (300, 128, 384, 2)])
+@pytest.mark.parametrize("M,N,K,act", [(1000, 96, 384, 1), (700, 200, 416, 1), (513, 96, 1024, 0), (300, 128, 384, 2), (513, 96, 416, 2)])
 def test_split3_gemm_batchnorm_act_prologue(M, N, K, act):
     """gg_gemm_nt_split3_af32_pro (the fp32_split mode's MBConv.conv3): C = act(BatchNorm(A)) . W^T with the transform formed in the loader, in front of the split --
     against an fp64 product of the fp64-transformed operand (exact erf GELU / QuickGELU), against gg_gemm_nt_f32's own BatchNorm prologue (GgGemmArgs.a_bn_*), and
-    the BatchNorm partials of the result; 96- and 128-column tiles, a K that is not a multiple of the stage, a ragged M."""
+    the BatchNorm partials of the result; 96- and 128-column tiles, a K that is not a multiple of the stage (with GELU and with QuickGELU), a ragged M."""
     import ctypes as C
     from geoguessr_ai_amd import _lib as L
     lib = L.lib()
