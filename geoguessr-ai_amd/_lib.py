@@ -431,6 +431,14 @@ ATTN16_SIGNATURES = {
 }
 ATTN16_SYMBOLS = list(ATTN16_SIGNATURES)
 
+# every exported symbol of include/gg_attn16w.h (the same forward for TinyViT's windows beyond 256 tokens -- head dim 32, window gather, relative-position bias -- and TinyViT's opt-in switch to it)
+ATTN16W_SIGNATURES = {
+    "gg_attention_flash16_win_fwd": (_I, [C.POINTER(AttnArgs), _I, _P]),
+    "gg_attention_flash16_win_calls": (_L, []),
+    "gg_tinyvit_set_attention16": (_I, [_I]),
+}
+ATTN16W_SYMBOLS = list(ATTN16W_SIGNATURES)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -439,7 +447,7 @@ def lib() -> C.CDLL:
             raise GgError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JSCAN_SIGNATURES.items()) + list(PANO_SIGNATURES.items()) + list(ATTN16_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JSCAN_SIGNATURES.items()) + list(PANO_SIGNATURES.items()) + list(ATTN16_SIGNATURES.items()) + list(ATTN16W_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the library lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -497,6 +505,7 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(root), "include", "gg_jscan.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_pano.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_attn16.h"))
+    files.append(os.path.join(os.path.dirname(root), "include", "gg_attn16w.h"))
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

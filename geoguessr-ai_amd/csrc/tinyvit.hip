@@ -17,6 +17,7 @@
 #include "../../include/gg_cls.h"
 #include "../../include/gg_drop.h"
 #include "../../include/gg_pad.h"
+#include "../../include/gg_attn16w.h"
 
 bool gg_split3_af32_takes_rowmap(int N, int K);      // gemm_split3.hip: the form gg_gemm_nt_split3_af32 would run this shape on accepts row compaction
 
@@ -24,6 +25,8 @@ namespace {
 
 // DropPath row compaction of frozen stage-2 blocks (gg_tinyvit_set_drop_compact; block_compacts below)
 std::atomic<int> g_drop_compact{1};
+// the opt-in 16-bit-MFMA attention of the bf16 inference forward for windows beyond 256 tokens (gg_tinyvit_set_attention16, include/gg_attn16w.h)
+std::atomic<int> g_attention16{0};
 
 struct TensorInfo { std::string name; int64_t offset; int64_t numel; int ndim; int64_t shape[4]; int kind; };
 static const float kAttnScale = 0.17677669529663687f;   // head_dim 32 ^ -0.5; the expanded bias tables are divided by it
@@ -555,6 +558,7 @@ struct Exec {
     // finalised (the forward's .stat checkpoints are reused, the running buffers are not touched) and the segment's output is not rewritten
     bool replay = false;
     bool compact = false;   // DropPath row compaction is on for this call (the process-global switch, read once per call)
+    bool attn16 = false;    // gg_tinyvit_forward, inference, bf16, switch on (gg_tinyvit_set_attention16): windows beyond 256 tokens through gg_attention_flash16_win_fwd
     void done(int stage) const { if (stage_done) stage_done(stage, stage_user); }
     bool f32;               // reference-precision mode: f32 activations / cached weights, f32 MFMA
     Exec(const Model& model, const Layout& layout, int batch, bool train) : m(&model), L(&layout), B(batch), training(train), f32(model.f32) {}
@@ -723,7 +727,11 @@ static void attn_args(const Exec& e, const StageL& st, const BlockL& l, const Bl
     at.scale = kAttnScale;
     at.out = e.A(a.o); at.ldo = C; at.lse = e.F(a.lse);
 }
-static int attention_fwd(const Exec& e, const GgAttnArgs& at) { return e.f32 ? gg_attention_flash_fwd(&at, 1, e.st) : gg_attention_fwd(&at, e.st); }
+// (attn16: only the windows gg_attention_fwd itself hands to gg_attention_flash_fwd -- attention.hip, attn_use_flash -- leave that route)
+static int attention_fwd(const Exec& e, const GgAttnArgs& at) {
+    if (e.attn16 && (at.tokens_per_window > 256 || at.window_size > 16)) return gg_attention_flash16_win_fwd(&at, 0, e.st);
+    return e.f32 ? gg_attention_flash_fwd(&at, 1, e.st) : gg_attention_fwd(&at, e.st);
+}
 static int attention_bwd(const Exec& e, const GgAttnArgs& at) { return e.f32 ? gg_attention_flash_bwd(&at, 1, e.st) : gg_attention_bwd(&at, e.st); }
 // padded block: zero-pad a [B, res, res, C] map of the stage to [B, pres, pres, C]; crop such a map back: y = res_in + rowscale[b] * t (y may be res_in)
 static int window_pad(const Exec& e, const StageL& st, const act_t* x, act_t* y) {
@@ -1539,6 +1547,7 @@ static int refresh_weights(const GgTinyVitCfg* cfg, const float* params, void* w
     return 0;
 }
 extern "C" int gg_tinyvit_set_drop_compact(int on) { return g_drop_compact.exchange(on != 0 ? 1 : 0); }
+extern "C" int gg_tinyvit_set_attention16(int on) { return g_attention16.exchange(on != 0 ? 1 : 0); }
 extern "C" int gg_tinyvit_forward(const GgTinyVitCfg* cfg, int batch, int training, const float* params, float* buffers,
                                   int64_t* counters, const void* wcache, const float* x, const float* drop_scales, void* workspace,
                                   float* out, const uint8_t* trainable, void* stream) {
@@ -1549,19 +1558,21 @@ extern "C" int gg_tinyvit_forward(const GgTinyVitCfg* cfg, int batch, int traini
     Plan p; Layout L;
     plan_make(m, batch, training != 0, p, L, trainable);
     const bool compact = g_drop_compact.load() != 0;
+    const bool attn16 = training == 0 && !m.f32 && g_attention16.load() != 0;      // (m.f32 covers fp32 and fp32_split)
     auto body = [&](hipStream_t st) -> int {
         Exec e(m, L, batch, training != 0);
         e.params = params; e.buffers = buffers; e.counters = counters;
         e.wc = (const char*)wcache; e.ws = (char*)workspace; e.st = st; e.drop = drop_scales; e.grads = nullptr;
         e.trainable = trainable;       // NULL: keep every activation a weight gradient could need
         e.compact = compact;
+        e.attn16 = attn16;
         return forward_impl(e, x, out);
     };
     // launch-bound sizes (a serving panorama, small training batches: a few hundred launches of microseconds each) replay a captured graph
     if (!gg_graph_wanted((int64_t)batch * cfg->img_size * cfg->img_size <= (int64_t)64 * 224 * 224)) return body((hipStream_t)stream);
     GgGraphKey key;
     key.add('F').add_bytes(cfg, sizeof(*cfg)).add(batch).add(training).add(params).add(buffers).add(counters).add(wcache).add(x).add(drop_scales).add(workspace).add(out).add((int)compact)
-       .add_bytes(trainable, trainable ? m.tensors.size() : 0);
+       .add((int)attn16).add_bytes(trainable, trainable ? m.tensors.size() : 0);
     return gg_graph_run(key, (hipStream_t)stream, body);
 }
 extern "C" int gg_tinyvit_backward(const GgTinyVitCfg* cfg, int batch, const float* params, const void* wcache, const float* drop_scales,

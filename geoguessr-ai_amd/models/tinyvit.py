@@ -50,6 +50,15 @@ def default_precision() -> str:
     return p
 
 
+def check_attention16(attention16: bool, precision: Optional[str], who: str) -> None:
+    """``attention16=True`` is a switch of the bf16 mode: refused by name for ``fp32`` and ``fp32_split`` (their attention is f32-accurate by contract; the wording
+    and the reason of ``pretrain.clip_embedder.check_attention16``)."""
+    prec = precision or default_precision()
+    if attention16 and PRECISIONS.get(prec, 0) in (1, 3):
+        raise L.GgError(f"{who}: attention16=True is a switch of the bf16 mode; precision='{'fp32_split' if PRECISIONS[prec] == 3 else 'fp32'}' keeps its f32-accurate "
+                        "attention (leave attention16 off)")
+
+
 def make_cfg(model_name: str, **overrides) -> tuple:
     base = model_name.split(".")[0]
     if base not in VARIANTS:
@@ -114,8 +123,12 @@ class TinyVitBackbone(EncoderRuntime):
     """Owner of the flat parameter / buffer storage and of the HIP workspace (``self.backbone`` of the adapter)."""
     _name, _switch, _gen_why = "TinyViT", "set_grad_checkpointing", "saved activations live in ONE workspace per backbone, so "
 
-    def __init__(self, model_name: str, seed: Optional[int] = None, **overrides):
+    def __init__(self, model_name: str, seed: Optional[int] = None, attention16: bool = False, **overrides):
+        """``attention16=True`` (bf16 only; opt-in): this backbone's inference forwards run with ``gg_tinyvit_set_attention16(1)`` -- windows beyond 256 tokens
+        (tiny_vit_21m_384 / _512 stage 2) through ``gg_attention_flash16_win_fwd`` (include/gg_attn16w.h); training forwards are unaffected."""
         super().__init__()
+        check_attention16(attention16, overrides.get("precision"), type(self).__name__)
+        self.attention16 = bool(attention16)
         self.cfg, self.variant, self.depths = make_cfg(model_name, **overrides)
         self.model_name = model_name.split(".")[0]
         self.precision = "fp32" if self.cfg.act_dtype in (1, 3) else "bf16"          # storage / arithmetic class ("fp32_split" stores and checks like fp32)
@@ -239,10 +252,16 @@ class TinyVitBackbone(EncoderRuntime):
         out = torch.empty((B, self.num_features), dtype=torch.float32, device=x.device)
         if drop_scales is not None:
             assert drop_scales.shape == (self.num_drop_slots, B) and drop_scales.dtype == torch.float32
-        L.check(L.lib().gg_tinyvit_forward(C.byref(cfg), B, int(training), L.ptr(self._flat), L.ptr(self._flat_buf),
+        lib = L.lib()
+        prev = lib.gg_tinyvit_set_attention16(1) if self.attention16 else None      # process-wide switch, read when the forward is enqueued: set for this call only
+        try:
+            L.check(lib.gg_tinyvit_forward(C.byref(cfg), B, int(training), L.ptr(self._flat), L.ptr(self._flat_buf),
                                            L.ptr(self._counters), L.ptr(self._wcache), L.ptr(x), L.ptr(drop_scales), L.ptr(ws),
                                            L.ptr(out), mask, L.stream()),
-                "gg_tinyvit_forward")
+                    "gg_tinyvit_forward")
+        finally:
+            if prev is not None:
+                lib.gg_tinyvit_set_attention16(prev)
         if training:
             self._counters += 1          # num_batches_tracked (int64 bookkeeping)
             self._record_forward(B, mask, drop_scales)
@@ -325,8 +344,10 @@ class TinyViTAdapter(nn.Module):
         """``overrides`` (not in the reference): ``precision="bf16"|"fp32"`` (default ``$GG_PRECISION`` or fp32), ``seed``,
         ``drop_path_rate``, ``img_size`` (any multiple of 32: where the attention window does not divide a stage's map the blocks pad it --
         ``backbone.padded_maps``) ... (timm ``create_model`` kwargs), ``grad_checkpointing=True`` (activation recompute from the start;
-        the same as ``adapter.backbone.set_grad_checkpointing()``)."""
+        the same as ``adapter.backbone.set_grad_checkpointing()``), ``attention16=True`` (bf16 only, opt-in: the inference forward's windows beyond
+        256 tokens on the 16-bit MFMA -- ``TinyVitBackbone``; ``precision="fp32"`` / ``"fp32_split"`` with it raises)."""
         super().__init__()
+        check_attention16(overrides.get("attention16", False), overrides.get("precision"), "TinyViTAdapter")
         if global_pool != "avg":
             raise NotImplementedError("only global_pool='avg' (the reference's setting) is built")
         # features_only=True (models/tinyvit.py:38-46): timm returns the stage feature maps and the adapter's forward pools the last

@@ -593,6 +593,31 @@ def attention_flash16(qkv, *, num_windows, tokens_per_window, num_heads, q_off, 
     return (out, lse_t) if want_lse else out
 
 
+def attention_flash16_win(qkv, *, num_windows, tokens_per_window, num_heads, q_off, k_off, v_off, head_stride, window_size, map_h, map_w, head_dim=32,
+                          bias_table=None, scale=None, want_lse=False, out=None):
+    """Window attention forward beyond 256 tokens with both products on the 16-bit MFMA (include/gg_attn16w.h): bf16 storage, head dim 32, tokens gathered from
+    the ``window_size`` x ``window_size`` windows of a ``map_h`` x ``map_w`` NHWC map, the compact f32 ``bias_table`` [heads][ws * ws] (or None).  Forward only;
+    returns out, or (out, lse) with ``want_lse``.  ``out`` (optional): a (tokens, >= heads * 32) bf16 buffer to write into (its row stride is the output pitch)."""
+    L.require_gpu()
+    if qkv.dtype != BF16:
+        raise L.GgError(f"attention_flash16_win: bf16 storage (got {qkv.dtype})")
+    a = L.AttnArgs()
+    a.qkv, a.ld = _pr(qkv, BF16, "qkv"), qkv.stride(0)      # rows may be strided: a column slice of a wider buffer
+    a.q_off, a.k_off, a.v_off, a.head_stride, a.head_dim = q_off, k_off, v_off, head_stride, head_dim
+    a.num_heads, a.num_windows, a.tokens_per_window = num_heads, num_windows, tokens_per_window
+    a.window_size, a.map_h, a.map_w = window_size, map_h, map_w
+    a.scale = head_dim ** -0.5 if scale is None else scale
+    a.bias_table = _p(bias_table, F32, "bias_table")
+    tokens = qkv.shape[0]
+    if out is None:
+        out = torch.empty((tokens, num_heads * head_dim), dtype=BF16, device=qkv.device)
+    a.out, a.ldo = _pr(out, BF16, "out"), out.stride(0)
+    lse_t = torch.empty((tokens, num_heads), dtype=F32, device=qkv.device) if want_lse else None
+    a.lse = _p(lse_t)
+    L.check(L.lib().gg_attention_flash16_win_fwd(C.byref(a), 0, L.stream()), "gg_attention_flash16_win_fwd")
+    return (out, lse_t) if want_lse else out
+
+
 def attention(qkv, *, num_windows, tokens_per_window, num_heads, head_dim, q_off, k_off, v_off, head_stride,
               window_size=0, map_h=0, map_w=0, bias=None, scale=None, dout=None, want_dbias=False, out=None, lse=None,
               want_lse=False):

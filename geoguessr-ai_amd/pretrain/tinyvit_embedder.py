@@ -8,25 +8,28 @@ from __future__ import annotations
 import torch
 from torch import Tensor
 
-from ..models.tinyvit import VARIANTS, TinyViTAdapter
+from ..models.tinyvit import VARIANTS, TinyViTAdapter, check_attention16
 
 
 class TinyViTEmbedding(torch.nn.Module):
     def __init__(self, model_name: str = "tiny_vit_21m_512.dist_in22k_ft_in1k", device: str = "cuda", load_checkpoint: bool = False,
-                 panorama: bool = False, img_size: int = None, batch_transform: bool = False, jpeg_split_bytes: int = 0):
+                 panorama: bool = False, img_size: int = None, batch_transform: bool = False, jpeg_split_bytes: int = 0, attention16: bool = False):
         """``img_size`` (not in the reference): run the checkpoint at another input side (a multiple of 32; ``TinyViTAdapter``'s override) -- the preprocessing
         resizes to that side, with the crop settings of the checkpoint's own variant.  ``batch_transform`` (not in the reference): raw images -- a list of any
         sizes, or the four panorama views together -- go through ONE ``gg_eval_batch`` call (``training.preprocess.DeviceEvalTransform``) instead of one
         ``gg_preprocess_pil`` call per image; same arithmetic.  ``jpeg_split_bytes`` (with ``batch_transform`` only): the ``split_bytes`` of the decoder that
-        takes JPEG files given as bytes (``DeviceEvalTransform``'s keyword; 0 is one lane per restart segment)."""
+        takes JPEG files given as bytes (``DeviceEvalTransform``'s keyword; 0 is one lane per restart segment).  ``attention16`` (not in the reference; bf16
+        only, opt-in): the attention of windows beyond 256 tokens on the 16-bit MFMA (``TinyViTAdapter``'s keyword); the fp32 modes refuse it by name."""
         super().__init__()
+        check_attention16(attention16, None, "TinyViTEmbedding")
         self.device, self.panorama, self.model_name = device, panorama, model_name
         self.batch_transform, self._transform = bool(batch_transform), None
         if jpeg_split_bytes and not batch_transform:
             raise ValueError("TinyViTEmbedding: jpeg_split_bytes needs batch_transform=True")
         self.jpeg_split_bytes = int(jpeg_split_bytes)
         arch = "tiny_vit_21m_224" if load_checkpoint else model_name
-        self.tinyvit_model = TinyViTAdapter(arch, pretrained=not load_checkpoint, **({} if img_size is None else dict(img_size=int(img_size))))
+        self.tinyvit_model = TinyViTAdapter(arch, pretrained=not load_checkpoint, **({} if img_size is None else dict(img_size=int(img_size))),
+                                            **({"attention16": True} if attention16 else {}))
         if load_checkpoint:
             self.tinyvit_model.backbone.load_state_dict(torch.load(model_name, map_location="cpu"))
             print("Loaded embedder from checkpoint:", model_name)

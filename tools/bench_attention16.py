@@ -112,6 +112,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--kernel-only", action="store_true", help="the kernel cases alone (re-measuring the kernel beside a change that leaves the tower as it is)")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "attention16_bench.jsonl"))
     args = ap.parse_args()
     from geoguessr_ai_amd import _lib as L
@@ -122,7 +123,7 @@ def main():
             lines.append(kernel_case(L, B, H, N, dtype, args))
             print(json.dumps(lines[-1]), flush=True)
             torch.cuda.empty_cache()
-    for precision in ("fp16", "fp8", "bf16"):
+    for precision in (() if args.kernel_only else ("fp16", "fp8", "bf16")):
         lines.append(tower_case(L, precision, TOWER_BATCH, args))
         print(json.dumps(lines[-1]), flush=True)
         torch.cuda.empty_cache()
