@@ -24,8 +24,8 @@ extern "C" {
 /* out [tokens][ldo] (head h at column h * 64) and, when args->lse is given, lse f32 [tokens][num_heads], from qkv [tokens][ld] in the storage type `dtype` names:
  * 0 = bf16, 2 = fp16 (gg_attention_flash_fwd's codes; 1 and 3 -- f32 storage -- are refused).  Of GgAttnArgs it reads qkv, ld, q_off, k_off, v_off, head_stride
  * (both qkv layouts of gg_attention_flash_fwd), head_dim (64), num_heads, num_windows, tokens_per_window (>= 1, any), window_size (0: linear tokens), scale (any),
- * out, ldo, lse.  Alignment as gg_attention_flash_fwd's: qkv and out 16-byte aligned, ld, ldo, the offsets and head_stride multiples of 4 elements (multiples of
- * 8 take 16-byte loads).  head_dim != 64, window_size != 0, bias, bias_table, window_map and num_windows_dev are refused by name. */
+ * out, ldo, lse.  Alignment as gg_attention_flash_fwd's: qkv and out 16-byte aligned, ld, ldo, the offsets and head_stride multiples of 4 elements (on gfx950
+ * either pitch compiles to one 16-byte load per 8 elements).  head_dim != 64, window_size != 0, bias, bias_table, window_map and num_windows_dev are refused by name. */
 int gg_attention_flash16_fwd(const GgAttnArgs* args, int dtype, void* stream);
 /* launches of gg_attention_flash16_fwd's kernel enqueued by this process so far (tests count routes with it) */
 int64_t gg_attention_flash16_calls(void);

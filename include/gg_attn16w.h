@@ -6,7 +6,7 @@
  * Same conventions as include/gg.h (and the same libgg.so): 0 on success, < 0 on error with gg_last_error(); `stream` is a hipStream_t, work is only enqueued;
  * every pointer is a caller-owned device pointer.  A refused call writes nothing.
  *
- * Arithmetic contract: that of include/gg_attn16.h plus the bias (tests/attention16_win_cases.py restates the tiled form on the CPU):
+ * Arithmetic contract: that of include/gg_attn16.h plus the bias (tests/attention16_cases.py restates the tiled form on the CPU):
  *   scores       S = Q K^T on v_mfma_f32_16x16x32_bf16 with f32 accumulation, taken into the exp2 domain in f32 as
  *                acc * (scale * log2 e) + bias_table[h][|dy| * ws + |dx|] * log2 e -- the f32 parameter, unrounded, as gg_attention_flash_fwd reads it (not the
  *                bf16(bias / scale) of the register-resident kernels); the bias joins the score before the running maximum;
@@ -31,7 +31,7 @@ extern "C" {
  * head_dim (32), num_heads, num_windows, tokens_per_window (= window_size^2), window_size (1 .. 32), map_h, map_w, bias_table (the compact f32 [heads][ws * ws]
  * table, or NULL: no bias), scale (any), out, ldo, lse.  `bias` (the expanded bf16 table of the register-resident kernels) is ignored next to bias_table and
  * refused without it.  Alignment as gg_attention_flash16_fwd's: qkv and out 16-byte aligned, ld, ldo, the offsets and head_stride multiples of 4 elements
- * (multiples of 8 take 16-byte loads).  head_dim != 32, window_size == 0 or > 32, window_map, num_windows_dev and dbias are refused by name. */
+ * (on gfx950 either pitch compiles to one 16-byte load per 8 elements).  head_dim != 32, window_size == 0 or > 32, window_map, num_windows_dev and dbias are refused by name. */
 int gg_attention_flash16_win_fwd(const GgAttnArgs* args, int dtype, void* stream);
 /* launches of gg_attention_flash16_win_fwd's kernel enqueued by this process so far (tests count routes with it; gg_attention_flash16_calls does not move) */
 int64_t gg_attention_flash16_win_calls(void);

@@ -26,13 +26,21 @@ def get_case(storage, N, cls):
 
 
 def tiled_contract(c, tile=TILE):
-    """The contract of include/gg_attn16.h in f32 arithmetic on the case's canonical (storage-rounded) q, k, v: scores with f32 accumulation scaled into the exp2
-    domain, online softmax over ``tile``-key tiles with a running maximum, the row sum from the unrounded P, P rounded to the storage type per tile as the operand
-    of P V, O accumulated in f32 (rescaled when the maximum moves) and rounded once after the division, lse = m ln 2 + log l.  Returns canonical out, lse."""
+    """The contract of include/gg_attn16.h and include/gg_attn16w.h in f32 arithmetic on the case's canonical (storage-rounded) q, k, v and its f32 table (if any):
+    scores with f32 accumulation taken into the exp2 domain as acc * (scale log2 e), with a table + table[|dy| ws + |dx|] log2 e (one FMA; the table unrounded),
+    online softmax over ``tile``-key tiles with a running maximum the bias has joined, the row sum from the unrounded P, P rounded to the storage type per tile as
+    the operand of P V, O accumulated in f32 (rescaled when the maximum moves) and rounded once after the division, lse = m ln 2 + log l.  ``c``: a case of
+    ``attention_cases.case`` or a dict with dtype, q, k, v, scale and (optional) table, bidx.  Returns canonical out, lse."""
     st = c["dtype"]
     q, k, v = (c[n].float() for n in ("q", "k", "v"))
     sc2 = float(torch.tensor(c["scale"] * LOG2E, dtype=torch.float32))
-    s = (q @ k.transpose(-1, -2)) * sc2
+    qk = q @ k.transpose(-1, -2)
+    table = c.get("table")
+    if table is None:
+        s = qk * sc2
+    else:
+        bias2 = (table.float() * torch.tensor(LOG2E, dtype=torch.float32))[:, c["bidx"]]      # (H, N, N), the f32 product the kernel stages
+        s = (qk.double() * sc2 + bias2.double()).float()                                        # one rounding: an FMA
     N = s.shape[-1]
     m = torch.full(s.shape[:-1] + (1,), -1e30)
     l = torch.zeros_like(m)
@@ -90,3 +98,44 @@ def flat_qkv(q, k, v, layout, dtype, pad=0):
         AC._flat(c, x, off, into=buf)
     kw = dict(num_windows=W, tokens_per_window=N, num_heads=H, q_off=q_off, k_off=k_off, v_off=v_off, head_stride=hs)
     return buf.to(dtype), kw
+
+
+# ------------------------------------------------------------------------------------------- the bits of the build before the two kernels became one
+# tests/golden/attention16_parent.npz (tools/make_attention16_parent_golden.py) holds out and lse of these calls from the build with one translation unit per head
+# dim; the smallest shapes at which each mechanism of the kernel is live.
+# linear, head dim 64, 2 sequences x 2 heads, (N, layout, row pad, lse given): 17 a ragged 16-key sub-tile and one wave partly live; 65 a second, ragged key tile,
+# also interleaved with rows only 8-byte aligned; 130 a second query tile with two live rows, three key tiles
+PARENT_LINEAR = ((17, "clip", 0, True), (65, "clip", 0, False), (65, "tinyvit", 4, False), (130, "clip", 0, True))
+# window, head dim 32, bf16, 2 heads, (ws, map side in windows, windows, layout, row pad), each with a random f32 table and without: 5 a ragged sub-tile gathered
+# across a 2 x 2 map; 9 a second ragged tile, a 16-query strip straddling a window row, also [q | k | v] with rows only 8-byte aligned; 12 a second query tile
+PARENT_WINDOW = ((5, 2, 4, "tinyvit", 0), (9, 1, 2, "tinyvit", 0), (9, 1, 2, "clip", 4), (12, 1, 2, "tinyvit", 0))
+
+
+def parent_bits(ops, window):
+    """{name: numpy array} of the PARENT_WINDOW (``window``) or PARENT_LINEAR calls on seeded N(0, 1) inputs, run on the GPU through ``ops`` (geoguessr_ai_amd.ops):
+    ``<name>_out`` the int16 view of out, ``<name>_lse`` the f32 lse where the call takes one."""
+    from tests import attention16_win_cases as W16
+    store = {}
+
+    def keep(name, res, want_lse):
+        out, lse = res if want_lse else (res, None)
+        store[name + "_out"] = out.view(torch.int16).cpu().numpy()
+        if want_lse:
+            store[name + "_lse"] = lse.cpu().numpy()
+
+    if not window:
+        for storage, st in (("f16", torch.float16), ("bf16", torch.bfloat16)):
+            for N, layout, pad, want_lse in PARENT_LINEAR:
+                g = torch.Generator().manual_seed(7000 + N)
+                q, k, v = (torch.randn(2, 2, N, 64, generator=g).to(st).double() for _ in range(3))
+                qkv, kw = flat_qkv(q, k, v, layout, st, pad=pad)
+                keep(f"lin_{storage}_{N}_{layout}{pad}", ops.attention_flash16(qkv.cuda()[:, :384], **kw, want_lse=want_lse), want_lse)
+        return store
+    for ws, m, W, layout, pad in PARENT_WINDOW:
+        g = torch.Generator().manual_seed(7100 + ws)
+        q, k, v = (torch.randn(W, 2, ws * ws, 32, generator=g).to(torch.bfloat16).double() for _ in range(3))
+        table = (0.5 * torch.randn(2, ws * ws, generator=g)).float().cuda()
+        qkv, kw, _ = W16.flat_qkv(q, k, v, ws, m, layout=layout, pad=pad)
+        for name, tab in (("bias", table), ("nobias", None)):
+            keep(f"win_{ws}_{layout}{pad}_{name}", ops.attention_flash16_win(qkv.cuda()[:, :192], **kw, bias_table=tab, want_lse=True), True)
+    return store

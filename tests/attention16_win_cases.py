@@ -1,6 +1,6 @@
 """Cases of the 16-bit-MFMA window attention forward beyond 256 tokens (include/gg_attn16w.h) shared by tests/test_attention16_win_cpu.py and
-tests/test_gpu_attention16_win.py, and a torch restatement of the kernel's arithmetic contract -- that of tests/attention16_cases.py plus the bias.  Plain torch on
-the CPU: no GPU, no libgg.
+tests/test_gpu_attention16_win.py; the torch restatement of the kernel's arithmetic contract is tests/attention16_cases.py::tiled_contract (with the bias).  Plain
+torch on the CPU: no GPU, no libgg.
 
 Sizes ``(ws, m, W)``: window side, map side in windows, windows.  A single key (1); an exact and a ragged 16-key sub-tile (4, 5; the latter with four windows per
 image); exactly one 64-key tile over two images of four windows (8); a second, ragged tile (9); four tiles, the last size TinyViT's route does not take (16); 289
@@ -12,6 +12,7 @@ import math
 import torch
 
 from tests import attention_cases as AC
+from tests.attention16_cases import tiled_contract          # noqa: F401  (one restatement serves both entry points: a case without a table takes its no-bias branch)
 
 SIZES = ((1, 1, 2), (4, 1, 2), (5, 2, 4), (8, 2, 8), (9, 1, 2), (16, 1, 2), (17, 2, 4), (24, 1, 2), (32, 1, 2))
 GEOM = {ws: (m, W) for ws, m, W in SIZES}
@@ -28,39 +29,6 @@ def params():
 def get_case(ws, cls):
     m, W = GEOM[ws]
     return AC.case("tinyvit", ws * ws, HD, heads=2, windows=W, ws=ws, storage="bf16", cls=cls, map_hw=m * ws)
-
-
-def tiled_contract(c, tile=TILE):
-    """The contract of include/gg_attn16w.h in f32 arithmetic on the case's canonical (bf16-rounded) q, k, v and its f32 table: scores with f32 accumulation taken
-    into the exp2 domain as acc * (scale log2 e) + table[|dy| ws + |dx|] log2 e (one FMA; the table unrounded), online softmax over ``tile``-key tiles with a
-    running maximum the bias has joined, the row sum from the unrounded P, P rounded to bf16 per tile as the operand of P V, O accumulated in f32 (rescaled when
-    the maximum moves) and rounded once after the division, lse = m ln 2 + log l.  ``c``: a case of ``attention_cases.case`` or a dict with dtype, q, k, v, scale
-    and (optional) table, bidx.  Returns canonical out, lse."""
-    st = c["dtype"]
-    q, k, v = (c[n].float() for n in ("q", "k", "v"))
-    sc2 = float(torch.tensor(c["scale"] * LOG2E, dtype=torch.float32))
-    qk = q @ k.transpose(-1, -2)
-    table = c.get("table")
-    if table is None:
-        s = qk * sc2
-    else:
-        bias2 = (table.float() * torch.tensor(LOG2E, dtype=torch.float32))[:, c["bidx"]]      # (H, N, N), the f32 product the kernel stages
-        s = (qk.double() * sc2 + bias2.double()).float()                                        # one rounding: an FMA
-    N = s.shape[-1]
-    m = torch.full(s.shape[:-1] + (1,), -1e30)
-    l = torch.zeros_like(m)
-    o = torch.zeros_like(q)
-    for t in range(0, N, tile):
-        st_ = s[..., t:t + tile]
-        mn = torch.maximum(m, st_.amax(-1, keepdim=True))
-        alpha = torch.exp2(m - mn)
-        p = torch.exp2(st_ - mn)
-        l = l * alpha + p.sum(-1, keepdim=True)
-        o = o * alpha + p.to(st).float() @ v[..., t:t + tile, :]
-        m = mn
-    out = (o / l).to(st)
-    lse = (m * 0.6931471805599453 + torch.log(l)).squeeze(-1)
-    return {"out": out.double(), "lse": lse.double()}
 
 
 def flat_qkv(q, k, v, ws, m, layout="tinyvit", pad=0):

@@ -144,6 +144,18 @@ def test_refusals_leave_the_output_untouched():
     assert bool((out == 7.0).all()) and bool((lse == 7.0).all())
 
 
+def test_bits_unchanged_from_the_parent_build(golden_dir):
+    """out and lse of the seeded calls of tests/attention16_cases.py::parent_bits equal, bit for bit, what the build before the head-dim 64 and the head-dim 32
+    kernel became one template gave (tests/golden/attention16_parent.npz, tools/make_attention16_parent_golden.py)."""
+    import os
+    import numpy as np
+    gold = np.load(os.path.join(golden_dir, "attention16_parent.npz"))
+    got = A.parent_bits(_ops(), window=False)
+    assert sorted(got) == sorted(k for k in gold.files if k.startswith("lin_")) and got
+    for name, x in got.items():
+        assert x.dtype == gold[name].dtype and np.array_equal(x, gold[name]), name
+
+
 # ------------------------------------------------------------------------------------------- the tower with the switch on
 L14 = "openai/clip-vit-large-patch14-336"
 B32 = "openai/clip-vit-base-patch32"

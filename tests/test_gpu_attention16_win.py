@@ -19,6 +19,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import attention16_cases as AL
 from tests import attention16_win_cases as A
 from tests import attention_cases as AC
 
@@ -193,6 +194,17 @@ def test_refusals_leave_the_output_untouched():
     torch.cuda.synchronize()
     assert bool((out == 7.0).all()) and bool((lse == 7.0).all())
     assert lib.gg_attention_flash16_win_calls() == n0
+
+
+def test_bits_unchanged_from_the_parent_build(golden_dir):
+    """out and lse of the seeded calls of tests/attention16_cases.py::parent_bits equal, bit for bit, what the build before the head-dim 64 and the head-dim 32
+    kernel became one template gave (tests/golden/attention16_parent.npz, tools/make_attention16_parent_golden.py)."""
+    import os
+    gold = np.load(os.path.join(golden_dir, "attention16_parent.npz"))
+    got = AL.parent_bits(_ops(), window=True)
+    assert sorted(got) == sorted(k for k in gold.files if k.startswith("win_")) and got
+    for name, x in got.items():
+        assert x.dtype == gold[name].dtype and np.array_equal(x, gold[name]), name
 
 
 # ------------------------------------------------------------------------------------------- the model with the switch on
