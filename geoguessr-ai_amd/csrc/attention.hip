@@ -1027,7 +1027,9 @@ extern "C" int gg_attention_fwd_f16(const GgAttnArgs* a, void* stream) {
 extern "C" int gg_attention_bwd(const GgAttnArgs* a, void* stream) {
     if (attn_use_flash(a) || attn_use_split_bwd(a)) {
         GG_CHECK(!a->bias || a->bias_table, "gg_attention_bwd: this window shape takes the bias as bias_table (compact f32)");
-        return gg_attention_flash_bwd_impl(a, 0, 1, stream);      // (this forward added the bias as bf16(bias / scale): the backward recomputes P with that value)
+        // attn_use_split_bwd: the forward was this file's and added the bias as bf16(bias / scale); the backward recomputes P with that value.
+        // attn_use_flash: the forward was gg_attention_flash_fwd, which read the unrounded f32 table
+        return gg_attention_flash_bwd_impl(a, 0, attn_use_flash(a) ? 0 : 1, stream);
     }
     AttnParams p;
     GG_TRY(attn_fill(p, a, "gg_attention_bwd"));

@@ -14,7 +14,8 @@
 // MFMA operands are one f32 per lane: row-contiguous fragments come out of LDS as ds_read_b128 (4 consecutive k feed 4 successive
 // MFMA steps, the k permutation is the same on both operands), "k-major" fragments as ds_read_b32 of 16 consecutive floats per row.
 // The relative-position bias is looked up in the compact f32 table attention_biases[h][|dy|*ws+|dx|] (LDS copy), its gradient is
-// summed per workgroup in LDS.  The backward pass runs in two passes (dQ; dK,dV): no atomics on dq/dk/dv, deterministic.
+// summed per workgroup in LDS.  The backward is a single pass per (window, head) where the window fits one CU's LDS, else two streaming passes (dQ; dK,dV):
+// no atomics on dq/dk/dv, deterministic.
 #include "common.h"
 #include "../../include/gg.h"
 #include "../../include/gg_clip_text.h"
@@ -180,17 +181,6 @@ __device__ __forceinline__ void fl_stage(const FlashParams& p, const T* base, in
         if (row < rlim) *reinterpret_cast<f32x4*>(X + row * RS + ch * 4) = v;
     }
 }
-// resident form: all p.npad rows of one head's column block (zero rows beyond N), any block size
-template <typename T, int D>
-__device__ __forceinline__ void fl_stage_all(const FlashParams& p, const T* base, int64_t ld, int col, int64_t origin, float* X) {
-    constexpr int CH = D / 4, RS = D + 4;
-    for (int id = threadIdx.x; id < p.npad * CH; id += blockDim.x) {
-        const int row = id / CH, ch = id % CH;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (row < p.N) v = Ld4<T>::load(base + fl_token(p, origin, row) * ld + col + ch * 4);
-        *reinterpret_cast<f32x4*>(X + row * RS + ch * 4) = v;
-    }
-}
 // Relative-position bias without per-element index arithmetic: the compact table attention_biases[h][|dy|*ws+|dx|] is expanded in LDS to
 // E[(dy + ws-1) * (2ws-1) + (dx + ws-1)] (pre-multiplied by log2 e: the softmax runs in the exp2 domain), so that the entry for a
 // (query, key) pair sits at byte offset qlin4 - klin4[key] with  lin4(t) = 4 * (cy(t) * (2ws-1) + cx(t)),  qlin4 = lin4(q) + 4*(ws-1)*2ws:
@@ -212,11 +202,12 @@ __device__ __forceinline__ void fl_stage_coords(const FlashParams& p, int t0, in
     for (int i = threadIdx.x; i < n; i += blockDim.x) klin[i] = fl_lin4(p, min(t0 + i, p.N - 1));
 }
 
-// RES (resident) variants: windows whose K/V (resp. Q/dO) fit in LDS next to a second workgroup (p.npad rows = tokens rounded up to 16, e.g. the
-// 14x14 windows of TinyViT stage 2) are staged ONCE by one workgroup per (window, head); its four waves then walk the 16-row strips
-// (strip = wave, wave + 4, ...) with no barrier inside.  The streaming form re-staged every K/V tile for each 64-query tile (4x for 196
+// RES (resident) form of the FORWARD: windows whose K/V fit in LDS next to a second workgroup (p.npad rows = tokens rounded up to 16, e.g. the
+// 14x14 windows of TinyViT stage 2) are staged ONCE by one workgroup per (window, head); its waves then walk the 16-row strips
+// (strip = wave, wave + waves, ...) with no barrier inside.  The streaming form re-stages every K/V tile for each 64-query tile (4x for 196
 // tokens) behind two barriers per tile.  Same arithmetic in the same order per row: results are bit-identical between the two forms.
 // LDS carve-up (dynamic): [R][RS] x 2 operand images, the bias table (p.nbpad floats), coordinates and per-row scalars; R = RES ? npad : 64.
+// The backward has no resident two-kernel form: a window that small takes the single-pass kernel (see gg_attention_flash_bwd_impl).
 
 // ------------------------------------------------------------------------------------------- forward
 // CAUSAL (streaming form only; gg_attention_causal_fwd, bf16 storage): query t sees keys 0..t -- key tiles above the workgroup's query tile are not visited,
@@ -465,19 +456,19 @@ __global__ __launch_bounds__(RES ? 1024 : 256) void flash_fwd_kernel(FlashParams
 }
 
 // ------------------------------------------------------------------------------------------- backward, pass A: dQ
-// QS = query strips a wave works on at once: every K / V fragment read from LDS then feeds QS independent score / dP / dQ chains (QS = 2
-// in the resident form: half the LDS reads per MFMA and twice the independent MFMA work per wave).
-template <typename T, int D, bool RES, int QS = 1>
-__global__ __launch_bounds__(RES ? 1024 : 256) void flash_bwd_dq_kernel(FlashParams p) {
+// The two-pass backward is the form of windows the single-pass kernel below cannot hold (more than 256 padded tokens, or three window images beyond 160 KB
+// of LDS).  Its kernels are streaming only: one workgroup per (window, head, 64-row tile), a wave per 16-row strip, the other operand walked in 64-row tiles
+// staged in LDS behind two barriers each.  Here: 64 queries against every K / V tile; S^T and dP^T recomputed from lse, dQ = scale * dS K.
+template <typename T, int D>
+__global__ __launch_bounds__(256) void flash_bwd_dq_kernel(FlashParams p) {
     constexpr int RS = D + 4, DC = D / 16;
     extern __shared__ __attribute__((aligned(16))) float fsm[];
-    const int R = RES ? p.npad : 64;
     float* Ks = fsm;
-    float* Vs = Ks + R * RS;
-    float* btab = Vs + R * RS;
+    float* Vs = Ks + 64 * RS;
+    float* btab = Vs + 64 * RS;
     int* klin = reinterpret_cast<int*>(btab + p.nbpad);            // byte-scaled linear window coordinate of every staged key
-    const int qt = RES ? 0 : blockIdx.x % p.ntile;
-    const int wh = RES ? blockIdx.x : blockIdx.x / p.ntile;
+    const int qt = blockIdx.x % p.ntile;
+    const int wh = blockIdx.x / p.ntile;
     const int h = wh % p.nh, w = wh / p.nh;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lr = lane & 15, lg = lane >> 4;
@@ -488,220 +479,122 @@ __global__ __launch_bounds__(RES ? 1024 : 256) void flash_bwd_dq_kernel(FlashPar
     const int hc = h * p.head_stride;
     const bool has_bias = p.bias_table != nullptr;
     if (has_bias) fl_stage_bias(p, h, btab);
-    if (RES) {
-        fl_stage_all<T, D>(p, qkv, p.ld, p.k_off + hc, origin, Ks);
-        fl_stage_all<T, D>(p, qkv, p.ld, p.v_off + hc, origin, Vs);
-        if (has_bias) fl_stage_coords(p, 0, klin, p.npad);
-        __syncthreads();
-    }
-    const int nstrips = (p.N + 15) >> 4;
-    const int nwaves = (int)(blockDim.x >> 6);
     const float sc2 = p.scale * 1.4426950408889634f;
-    for (int strip0 = RES ? wave * QS : qt * 4 + wave; !RES || strip0 < nstrips; strip0 += nwaves * QS) {
-    bool qok[QS];
-    int64_t qtok[QS];
-    f32x4 qf[QS][DC], dof[QS][DC], dq[QS][DC];
-    float delta[QS], lse2[QS];
-    int qlin[QS];
+    const int strip = qt * 4 + wave;
+    const int qi = strip * 16 + lr;
+    const bool qok = qi < p.N;
+    const int64_t qtok = fl_token(p, origin, min(qi, p.N - 1));
+    f32x4 qf[DC], dof[DC], dq[DC];
+    float delta = 0.f;
 #pragma unroll
-    for (int u = 0; u < QS; ++u) {
-        const int qi = (strip0 + u) * 16 + lr;
-        qok[u] = qi < p.N;
-        qtok[u] = fl_token(p, origin, min(qi, p.N - 1));
-        float d = 0.f;
+    for (int c = 0; c < DC; ++c) {
+        qf[c] = dof[c] = dq[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (qok) {
+            qf[c] = Ld4<T>::load(qkv + qtok * p.ld + p.q_off + hc + 16 * c + 4 * lg);
+            dof[c] = Ld4<T>::load(dout + qtok * p.lddo + h * D + 16 * c + 4 * lg);
+            const f32x4 o = Ld4<T>::load(outp + qtok * p.ldo + h * D + 16 * c + 4 * lg);
 #pragma unroll
-        for (int c = 0; c < DC; ++c) {
-            qf[u][c] = dof[u][c] = dq[u][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (qok[u]) {
-                qf[u][c] = Ld4<T>::load(qkv + qtok[u] * p.ld + p.q_off + hc + 16 * c + 4 * lg);
-                dof[u][c] = Ld4<T>::load(dout + qtok[u] * p.lddo + h * D + 16 * c + 4 * lg);
-                const f32x4 o = Ld4<T>::load(outp + qtok[u] * p.ldo + h * D + 16 * c + 4 * lg);
-#pragma unroll
-                for (int s = 0; s < 4; ++s) d = fmaf(dof[u][c][s], o[s], d);
-            }
+            for (int s = 0; s < 4; ++s) delta = fmaf(dof[c][s], o[s], delta);
         }
-        d += __shfl_xor(d, 16, 64);
-        d += __shfl_xor(d, 32, 64);
-        delta[u] = d;
-        lse2[u] = -1.4426950408889634f * (qok[u] ? p.lse[qtok[u] * p.nh + h] : 0.f);          // -lse in the exp2 domain: joins the bias in the exponent (see fl_stage_rowstats_b)
-        qlin[u] = has_bias ? fl_lin4(p, min(qi, p.N - 1)) + 4 * (p.ws - 1) * 2 * p.ws : 0;       // + the table's centre (dy = dx = 0)
     }
-    const bool wave_on = strip0 * 16 < p.N;
+    delta += __shfl_xor(delta, 16, 64);
+    delta += __shfl_xor(delta, 32, 64);
+    const float lse2 = -1.4426950408889634f * (qok ? p.lse[qtok * p.nh + h] : 0.f);          // -lse in the exp2 domain: joins the bias in the exponent (see fl_stage_rowstats_b)
+    const int qlin = has_bias ? fl_lin4(p, min(qi, p.N - 1)) + 4 * (p.ws - 1) * 2 * p.ws : 0;       // + the table's centre (dy = dx = 0)
+    const bool wave_on = strip * 16 < p.N;
 
     for (int kt0 = 0; kt0 < p.ntile; ++kt0) {
         const int t0 = kt0 * 64;
-        if (!RES) {
-            __syncthreads();
-            fl_stage<T, D>(p, qkv, p.ld, p.k_off + hc, origin, t0, Ks);
-            fl_stage<T, D>(p, qkv, p.ld, p.v_off + hc, origin, t0, Vs);
-            if (has_bias) fl_stage_coords(p, t0, klin);
-            __syncthreads();
-            if (!wave_on) continue;
-        }
-        const float* Kt = Ks + (RES ? t0 * RS : 0);
-        const float* Vt = Vs + (RES ? t0 * RS : 0);
-        const int* klt = klin + (RES ? t0 : 0);
+        __syncthreads();
+        fl_stage<T, D>(p, qkv, p.ld, p.k_off + hc, origin, t0, Ks);
+        fl_stage<T, D>(p, qkv, p.ld, p.v_off + hc, origin, t0, Vs);
+        if (has_bias) fl_stage_coords(p, t0, klin);
+        __syncthreads();
+        if (!wave_on) continue;
         const int nsub = min(4, (p.N - t0 + 15) / 16);
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) {
             if (kt >= nsub) continue;
-            f32x4 st[QS], dp[QS];
-#pragma unroll
-            for (int u = 0; u < QS; ++u) { st[u] = (f32x4){0.f, 0.f, 0.f, 0.f}; dp[u] = (f32x4){-delta[u], -delta[u], -delta[u], -delta[u]}; }
+            f32x4 st = {0.f, 0.f, 0.f, 0.f}, dp = {-delta, -delta, -delta, -delta};
             if (t0 + 16 * kt + 15 >= p.N) {          // wave-uniform: only the window's last sub-tile holds padded keys; -inf there -> P = 0
 #pragma unroll
-                for (int u = 0; u < QS; ++u)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) if (t0 + 16 * kt + 4 * lg + r >= p.N) st[u][r] = -INFINITY;
+                for (int r = 0; r < 4; ++r) if (t0 + 16 * kt + 4 * lg + r >= p.N) st[r] = -INFINITY;
             }
 #pragma unroll
             for (int c = 0; c < DC; ++c) {
-                const f32x4 kf = *reinterpret_cast<const f32x4*>(Kt + (16 * kt + lr) * RS + 16 * c + 4 * lg);
-                const f32x4 vf = *reinterpret_cast<const f32x4*>(Vt + (16 * kt + lr) * RS + 16 * c + 4 * lg);
+                const f32x4 kf = *reinterpret_cast<const f32x4*>(Ks + (16 * kt + lr) * RS + 16 * c + 4 * lg);
+                const f32x4 vf = *reinterpret_cast<const f32x4*>(Vs + (16 * kt + lr) * RS + 16 * c + 4 * lg);
 #pragma unroll
-                for (int s = 0; s < 4; ++s)
-#pragma unroll
-                    for (int u = 0; u < QS; ++u) {
-                        st[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[s], qf[u][c][s], st[u], 0, 0, 0);
-                        dp[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[s], dof[u][c][s], dp[u], 0, 0, 0);
-                    }
-            }
-            // lane holds S^T / dP^T [key = t0 + 16kt + 4lg + r][q = lr] of each strip
-            f32x4 bia[QS];
-#pragma unroll
-            for (int u = 0; u < QS; ++u) bia[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (has_bias) {
-                const i32x4 kl4 = *reinterpret_cast<const i32x4*>(klt + 16 * kt + 4 * lg);
-#pragma unroll
-                for (int u = 0; u < QS; ++u)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) bia[u][r] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(btab) + (qlin[u] - kl4[r]));
-            }
-#pragma unroll
-            for (int u = 0; u < QS; ++u)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float pr = __builtin_amdgcn_exp2f(fmaf(st[u][r], sc2, bia[u][r] + lse2[u]));      // rows beyond N are never stored: no query mask needed in this pass
-                    st[u][r] = pr * dp[u][r];                            // dS^T; the softmax scale is applied once, to dQ
+                for (int s = 0; s < 4; ++s) {
+                    st = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[s], qf[c][s], st, 0, 0, 0);
+                    dp = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[s], dof[c][s], dp, 0, 0, 0);
                 }
+            }
+            // lane holds S^T / dP^T [key = t0 + 16kt + 4lg + r][q = lr]
+            f32x4 bia = {0.f, 0.f, 0.f, 0.f};
+            if (has_bias) {
+                const i32x4 kl4 = *reinterpret_cast<const i32x4*>(klin + 16 * kt + 4 * lg);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) bia[r] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(btab) + (qlin - kl4[r]));
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float pr = __builtin_amdgcn_exp2f(fmaf(st[r], sc2, bia[r] + lse2));      // rows beyond N are never stored: no query mask needed in this pass
+                st[r] = pr * dp[r];                                  // dS^T; the softmax scale is applied once, to dQ
+            }
 #pragma unroll
             for (int r = 0; r < 4; ++r)
 #pragma unroll
                 for (int c = 0; c < DC; ++c) {
-                    const float kfs = Kt[(16 * kt + 4 * lg + r) * RS + 16 * c + lr];
-#pragma unroll
-                    for (int u = 0; u < QS; ++u) dq[u][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(kfs, st[u][r], dq[u][c], 0, 0, 0);
+                    const float kfs = Ks[(16 * kt + 4 * lg + r) * RS + 16 * c + lr];
+                    dq[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(kfs, st[r], dq[c], 0, 0, 0);
                 }
         }
     }
+    if (qok) {
+        T* dqkv = reinterpret_cast<T*>(p.dqkv);
 #pragma unroll
-    for (int u = 0; u < QS; ++u)
-        if (qok[u]) {
-            T* dqkv = reinterpret_cast<T*>(p.dqkv);
-#pragma unroll
-            for (int c = 0; c < DC; ++c) Ld4<T>::store(dqkv + qtok[u] * p.ld + p.q_off + hc + 16 * c + 4 * lg, dq[u][c] * p.scale);
-        }
-    if (!RES) break;
+        for (int c = 0; c < DC; ++c) Ld4<T>::store(dqkv + qtok * p.ld + p.q_off + hc + 16 * c + 4 * lg, dq[c] * p.scale);
     }
 }
 
 // ------------------------------------------------------------------------------------------- backward, pass A from stored dS
 // With a dS scratch (GgAttnArgs.ds_scratch) the dK/dV pass runs FIRST and leaves dS = P o (dP - delta) of every (query, key) pair as f32
 // [window][head][key strip][query][16 keys] (npad^2 floats per head); this pass then is one product, dQ = scale * dS K: no Q K^T, no dO V^T, no exponentials, no bias lookups -- 1 of the
-// two-pass scheme's 7 products instead of 3 (the scratch costs 2 x npad^2 x 4 bytes of HBM traffic per (window, head): 4.2 GB per 14 x 14 layer).
+// two-pass scheme's 7 products instead of 3 (the scratch costs 2 x npad^2 x 4 bytes of HBM traffic per (window, head)).
 // Lane (lr, lg) of a strip reads its query row lr, keys 4 lg .. 4 lg + 3 of a 16-key sub-tile: exactly the B operand of the next 4 MFMA steps.
-// dQ rows of QS query strips from the stored dS and a RESIDENT K image (all p.npad rows in LDS): shared by the stand-alone pass below and by the
-// second phase of the resident dK/dV kernel
-template <typename T, int D, int QS>
-__device__ __forceinline__ void fl_dq_from_ds_resident(const FlashParams& p, const float* Ks, const float* dsb, int strip0, int64_t origin, int hc, int lr, int lg) {
-    constexpr int RS = D + 4, DC = D / 16;
-    f32x4 dq[QS][DC];
-    const float* dsrow[QS];
-#pragma unroll
-    for (int u = 0; u < QS; ++u) {
-#pragma unroll
-        for (int c = 0; c < DC; ++c) dq[u][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        dsrow[u] = dsb + (int64_t)min((strip0 + u) * 16 + lr, p.npad - 1) * 16 + 4 * lg;          // + key strip * npad * 16
-    }
-    for (int kt0 = 0; kt0 < p.ntile; ++kt0) {
-        const int t0 = kt0 * 64;
-        const float* Kt = Ks + t0 * RS;
-        const int nsub = min(4, (p.N - t0 + 15) / 16);
-        f32x4 st[4][QS];
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-            for (int u = 0; u < QS; ++u) st[kt][u] = kt < nsub ? *reinterpret_cast<const f32x4*>(dsrow[u] + (int64_t)(4 * kt0 + kt) * p.npad * 16) : (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt) {
-            if (kt >= nsub) continue;
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int c = 0; c < DC; ++c) {
-                    const float kfs = Kt[(16 * kt + 4 * lg + r) * RS + 16 * c + lr];
-#pragma unroll
-                    for (int u = 0; u < QS; ++u) dq[u][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(kfs, st[kt][u][r], dq[u][c], 0, 0, 0);
-                }
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < QS; ++u) {
-        const int qi = (strip0 + u) * 16 + lr;
-        if (qi < p.N) {
-            T* dqkv = reinterpret_cast<T*>(p.dqkv);
-            const int64_t qtok = fl_token(p, origin, qi);
-#pragma unroll
-            for (int c = 0; c < DC; ++c) Ld4<T>::store(dqkv + qtok * p.ld + p.q_off + hc + 16 * c + 4 * lg, dq[u][c] * p.scale);
-        }
-    }
-}
-template <typename T, int D, bool RES, int QS>
-__global__ __launch_bounds__(RES ? 1024 : 256) void flash_bwd_dq_ds_kernel(FlashParams p) {
+// One workgroup per (window, head, 64-query tile), a wave per 16-query strip; K is walked in 64-key tiles staged in LDS.
+template <typename T, int D>
+__global__ __launch_bounds__(256) void flash_bwd_dq_ds_kernel(FlashParams p) {
     constexpr int RS = D + 4, DC = D / 16;
     extern __shared__ __attribute__((aligned(16))) float fsm[];
     float* Ks = fsm;
-    const int qt = RES ? 0 : blockIdx.x % p.ntile;
-    const int wh = RES ? blockIdx.x : blockIdx.x / p.ntile;
+    const int qt = blockIdx.x % p.ntile;
+    const int wh = blockIdx.x / p.ntile;
     const int h = wh % p.nh, w = wh / p.nh;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lr = lane & 15, lg = lane >> 4;
     const int64_t origin = fl_origin(p, w);
     const T* qkv = reinterpret_cast<const T*>(p.qkv);
     const int hc = h * p.head_stride;
-    if (RES) {
-        fl_stage_all<T, D>(p, qkv, p.ld, p.k_off + hc, origin, Ks);
-        __syncthreads();
-    }
     const float* dsb = p.ds_scratch + (int64_t)wh * p.npad * p.npad;
-    const int nstrips = (p.N + 15) >> 4;
-    const int nwaves = (int)(blockDim.x >> 6);
-    for (int strip0 = RES ? wave * QS : qt * 4 + wave; !RES || strip0 < nstrips; strip0 += nwaves * QS) {
-    f32x4 dq[QS][DC];
-    const float* dsrow[QS];
+    const int strip = qt * 4 + wave;
+    f32x4 dq[DC];
 #pragma unroll
-    for (int u = 0; u < QS; ++u) {
-#pragma unroll
-        for (int c = 0; c < DC; ++c) dq[u][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        dsrow[u] = dsb + (int64_t)min((strip0 + u) * 16 + lr, p.npad - 1) * 16 + 4 * lg;          // + key strip * npad * 16
-    }
-    const bool wave_on = strip0 * 16 < p.N;
+    for (int c = 0; c < DC; ++c) dq[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const float* dsrow = dsb + (int64_t)min(strip * 16 + lr, p.npad - 1) * 16 + 4 * lg;          // + key strip * npad * 16
+    const bool wave_on = strip * 16 < p.N;
     for (int kt0 = 0; kt0 < p.ntile; ++kt0) {
         const int t0 = kt0 * 64;
-        if (!RES) {
-            __syncthreads();
-            fl_stage<T, D>(p, qkv, p.ld, p.k_off + hc, origin, t0, Ks);
-            __syncthreads();
-            if (!wave_on) continue;
-        }
-        const float* Kt = Ks + (RES ? t0 * RS : 0);
+        __syncthreads();
+        fl_stage<T, D>(p, qkv, p.ld, p.k_off + hc, origin, t0, Ks);
+        __syncthreads();
+        if (!wave_on) continue;
         const int nsub = min(4, (p.N - t0 + 15) / 16);
         // all dS fragments of the 64-key tile in flight before its first MFMA (the pass is bound by these loads: 2 x npad^2 floats per (window, head))
-        f32x4 st[4][QS];
+        f32x4 st[4];
 #pragma unroll
-        for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-            for (int u = 0; u < QS; ++u) st[kt][u] = kt < nsub ? *reinterpret_cast<const f32x4*>(dsrow[u] + (int64_t)(4 * kt0 + kt) * p.npad * 16) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int kt = 0; kt < 4; ++kt) st[kt] = kt < nsub ? *reinterpret_cast<const f32x4*>(dsrow + (int64_t)(4 * kt0 + kt) * p.npad * 16) : (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) {
             if (kt >= nsub) continue;
@@ -709,23 +602,17 @@ __global__ __launch_bounds__(RES ? 1024 : 256) void flash_bwd_dq_ds_kernel(Flash
             for (int r = 0; r < 4; ++r)
 #pragma unroll
                 for (int c = 0; c < DC; ++c) {
-                    const float kfs = Kt[(16 * kt + 4 * lg + r) * RS + 16 * c + lr];
-#pragma unroll
-                    for (int u = 0; u < QS; ++u) dq[u][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(kfs, st[kt][u][r], dq[u][c], 0, 0, 0);
+                    const float kfs = Ks[(16 * kt + 4 * lg + r) * RS + 16 * c + lr];
+                    dq[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(kfs, st[kt][r], dq[c], 0, 0, 0);
                 }
         }
     }
+    const int qi = strip * 16 + lr;
+    if (qi < p.N) {
+        T* dqkv = reinterpret_cast<T*>(p.dqkv);
+        const int64_t qtok = fl_token(p, origin, qi);
 #pragma unroll
-    for (int u = 0; u < QS; ++u) {
-        const int qi = (strip0 + u) * 16 + lr;
-        if (qi < p.N) {
-            T* dqkv = reinterpret_cast<T*>(p.dqkv);
-            const int64_t qtok = fl_token(p, origin, qi);
-#pragma unroll
-            for (int c = 0; c < DC; ++c) Ld4<T>::store(dqkv + qtok * p.ld + p.q_off + hc + 16 * c + 4 * lg, dq[u][c] * p.scale);
-        }
-    }
-    if (!RES) break;
+        for (int c = 0; c < DC; ++c) Ld4<T>::store(dqkv + qtok * p.ld + p.q_off + hc + 16 * c + 4 * lg, dq[c] * p.scale);
     }
 }
 
@@ -755,20 +642,22 @@ __device__ __forceinline__ void fl_stage_rowstats(const FlashParams& p, const T*
         if (part == 0 && row < n) { del_s[row] = -dsum; lse_s[row] = ok ? -1.4426950408889634f * p.lse[tok * p.nh + h] : -INFINITY; }      // (-lse, exp2 domain: see fl_stage_rowstats_b)
     }
 }
-template <typename T, int D, bool DBIAS, bool RES, bool STORE_DS = false>
-__global__ __launch_bounds__(RES ? 1024 : 256) void flash_bwd_dkv_kernel(FlashParams p) {
+// One workgroup per (window, head, 64-key tile), a wave per 16-key strip whose K / V rows stay in registers; Q and dO are walked in 64-query tiles staged in LDS
+// with their row scalars.  S and dP are recomputed from lse; dV += P^T dO, dK += dS^T Q; the bias gradient is binned in LDS and leaves as one partial row per
+// workgroup.  STORE_DS: dS of every (query, key) pair is also written to p.ds_scratch for flash_bwd_dq_ds_kernel, which the host launches next.
+template <typename T, int D, bool DBIAS, bool STORE_DS = false>
+__global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(FlashParams p) {
     constexpr int RS = D + 4, DC = D / 16;
     extern __shared__ __attribute__((aligned(16))) float fsm[];
-    const int R = RES ? p.npad : 64;
     float* Qs = fsm;
-    float* Os = Qs + R * RS;                                       // dO image
-    float* btab = Os + R * RS;
+    float* Os = Qs + 64 * RS;                                      // dO image
+    float* btab = Os + 64 * RS;
     float* dbt = btab + p.nbpad;
     float* lse_s = dbt + (DBIAS ? p.nbpad : 0);
-    float* del_s = lse_s + R;
-    int* qlin = reinterpret_cast<int*>(del_s + R);                 // per staged query: byte-scaled linear coordinate + the table's centre
-    const int kvt = RES ? 0 : blockIdx.x % p.ntile;
-    const int wh = RES ? blockIdx.x : blockIdx.x / p.ntile;
+    float* del_s = lse_s + 64;
+    int* qlin = reinterpret_cast<int*>(del_s + 64);                // per staged query: byte-scaled linear coordinate + the table's centre
+    const int kvt = blockIdx.x % p.ntile;
+    const int wh = blockIdx.x / p.ntile;
     const int h = wh % p.nh, w = wh / p.nh;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lr = lane & 15, lg = lane >> 4;
@@ -782,15 +671,7 @@ __global__ __launch_bounds__(RES ? 1024 : 256) void flash_bwd_dkv_kernel(FlashPa
     const int w2 = 2 * p.ws - 1;
     if (has_bias) fl_stage_bias(p, h, btab);
     if (DBIAS) for (int i = threadIdx.x; i < w2 * w2; i += blockDim.x) dbt[i] = 0.f;      // bins in the expanded (signed-offset) index space
-    if (RES) {
-        fl_stage_all<T, D>(p, qkv, p.ld, p.q_off + hc, origin, Qs);
-        fl_stage_all<T, D>(p, dout, p.lddo, h * D, origin, Os);
-        if (has_bias) fl_stage_coords(p, 0, qlin, p.npad);
-        fl_stage_rowstats<T, D>(p, dout, outp, origin, h, 0, p.npad, lse_s, del_s);
-        __syncthreads();
-    }
-    const int nstrips = (p.N + 15) >> 4;
-    for (int strip = RES ? wave : kvt * 4 + wave; !RES || strip < nstrips; strip += (int)(blockDim.x >> 6)) {
+    const int strip = kvt * 4 + wave;
     const int ki = strip * 16 + lr;
     const bool kok = ki < p.N;
     const bool wave_on = strip * 16 < p.N;
@@ -813,29 +694,24 @@ __global__ __launch_bounds__(RES ? 1024 : 256) void flash_bwd_dkv_kernel(FlashPa
 
     for (int qt0 = 0; qt0 < p.ntile; ++qt0) {
         const int t0 = qt0 * 64;
-        if (!RES) {
-            __syncthreads();
-            fl_stage<T, D>(p, qkv, p.ld, p.q_off + hc, origin, t0, Qs);
-            fl_stage<T, D>(p, dout, p.lddo, h * D, origin, t0, Os);
-            if (has_bias) fl_stage_coords(p, t0, qlin);
-            fl_stage_rowstats<T, D>(p, dout, outp, origin, h, t0, 64, lse_s, del_s);
-            __syncthreads();
-            if (!wave_on) continue;
-        }
-        const float* Qt = Qs + (RES ? t0 * RS : 0);
-        const float* Ot = Os + (RES ? t0 * RS : 0);
-        const int ro = RES ? t0 : 0;
+        __syncthreads();
+        fl_stage<T, D>(p, qkv, p.ld, p.q_off + hc, origin, t0, Qs);
+        fl_stage<T, D>(p, dout, p.lddo, h * D, origin, t0, Os);
+        if (has_bias) fl_stage_coords(p, t0, qlin);
+        fl_stage_rowstats<T, D>(p, dout, outp, origin, h, t0, 64, lse_s, del_s);
+        __syncthreads();
+        if (!wave_on) continue;
         const int nsub = min(4, (p.N - t0 + 15) / 16);
 #pragma unroll
         for (int qs = 0; qs < 4; ++qs) {
             if (qs >= nsub) continue;
-            const int q4 = ro + 16 * qs + 4 * lg;                              // this lane's 4 consecutive queries: one 16-byte read per array
+            const int q4 = 16 * qs + 4 * lg;                                   // this lane's 4 consecutive queries: one 16-byte read per array
             const f32x4 nl4 = *reinterpret_cast<const f32x4*>(lse_s + q4);      // -lse (exp2 domain; -inf for padded queries)
             f32x4 st = {0.f, 0.f, 0.f, 0.f}, dp = *reinterpret_cast<const f32x4*>(del_s + q4);      // S, dP - delta
 #pragma unroll
             for (int c = 0; c < DC; ++c) {
-                const f32x4 qa = *reinterpret_cast<const f32x4*>(Qt + (16 * qs + lr) * RS + 16 * c + 4 * lg);
-                const f32x4 oa = *reinterpret_cast<const f32x4*>(Ot + (16 * qs + lr) * RS + 16 * c + 4 * lg);
+                const f32x4 qa = *reinterpret_cast<const f32x4*>(Qs + (16 * qs + lr) * RS + 16 * c + 4 * lg);
+                const f32x4 oa = *reinterpret_cast<const f32x4*>(Os + (16 * qs + lr) * RS + 16 * c + 4 * lg);
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
                     st = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[s], kf[c][s], st, 0, 0, 0);
@@ -867,8 +743,8 @@ __global__ __launch_bounds__(RES ? 1024 : 256) void flash_bwd_dkv_kernel(FlashPa
             for (int r = 0; r < 4; ++r)
 #pragma unroll
                 for (int c = 0; c < DC; ++c) {
-                    const float of = Ot[(16 * qs + 4 * lg + r) * RS + 16 * c + lr];
-                    const float qf = Qt[(16 * qs + 4 * lg + r) * RS + 16 * c + lr];
+                    const float of = Os[(16 * qs + 4 * lg + r) * RS + 16 * c + lr];
+                    const float qf = Qs[(16 * qs + 4 * lg + r) * RS + 16 * c + lr];
                     dv[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(of, pr[r], dv[c], 0, 0, 0);
                     dk[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(qf, ds[r], dk[c], 0, 0, 0);
                 }
@@ -882,11 +758,9 @@ __global__ __launch_bounds__(RES ? 1024 : 256) void flash_bwd_dkv_kernel(FlashPa
             Ld4<T>::store(dqkv + ktok * p.ld + p.v_off + hc + 16 * c + 4 * lg, dv[c]);
         }
     }
-    if (!RES) break;
-    }
     if (DBIAS) {
         __syncthreads();
-        const int prow = RES ? w : w * p.ntile + kvt;
+        const int prow = w * p.ntile + kvt;
         for (int i = threadIdx.x; i < nb; i += blockDim.x) {      // fold the signed offsets back onto attention_biases[|dy| * ws + |dx|]
             const int ady = fl_div(i, p.rcp_ws), adx = i - ady * p.ws, c0 = (p.ws - 1) * w2 + (p.ws - 1);
             float t = dbt[c0 + ady * w2 + adx];
@@ -896,19 +770,6 @@ __global__ __launch_bounds__(RES ? 1024 : 256) void flash_bwd_dkv_kernel(FlashPa
             if (p.dbias_part) p.dbias_part[((int64_t)prow * p.nh + h) * nb + i] = t;
             else atomicAdd(&p.dbias[h * nb + i], t);
         }
-    }
-    if (STORE_DS && RES) {
-        // second phase of the resident form: this workgroup wrote the whole dS of its (window, head); once every wave's stores are visible the same
-        // workgroup turns it into dQ (one strip per wave) -- the dS it reads back is still in L2 / Infinity Cache, and the separate dQ launch is gone
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __syncthreads();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        float* Ks = Qs;                                             // the Q image is dead: K takes its place
-        fl_stage_all<T, D>(p, qkv, p.ld, p.k_off + hc, origin, Ks);
-        __syncthreads();
-        const float* dsb = p.ds_scratch + (int64_t)wh * p.npad * p.npad;
-        for (int strip = wave; strip < nstrips; strip += (int)(blockDim.x >> 6))
-            fl_dq_from_ds_resident<T, D, 1>(p, Ks, dsb, strip, origin, hc, lr, lg);
     }
 }
 
@@ -1218,10 +1079,36 @@ bool flash_fused_ok(const FlashParams& p, int D, bool dbias) {
     static const bool off = gg_dev_env("GG_ATTN_NO_FUSED_BWD") != nullptr;
     return !off && p.npad <= 256 && flash_lds_fused(p, D, dbias) <= 160 * 1024;
 }
-// resident form: more than one 64-row tile (a single tile is already staged once) and two workgroups still fit a CU's 160 KB
-bool flash_resident(const FlashParams& p, int D, bool dbias) {
+// the forward's resident form (flash_fwd_kernel<.., RES = true>): two workgroups still fit a CU's 160 KB (single-tile windows too: same staging, descriptor
+// addressing).  The bound is the one of two whole-window images plus three row scalars -- flash_lds_dkv without gradient bins, a little above the forward's
+// own need -- and is kept at that value: it decides which forward kernel a window takes.  No backward kernel has a resident form.
+bool flash_fwd_resident(const FlashParams& p, int D) {
     static const bool off = gg_dev_env("GG_ATTN_FLASH_NO_RES") != nullptr;
-    return !off && flash_lds_dkv(p, D, p.npad, dbias) <= 64 * 1024;      // (single-tile windows too: same staging, descriptor addressing)
+    return !off && flash_lds_dkv(p, D, p.npad, false) <= 64 * 1024;
+}
+// every partial row of the bias gradient (one per workgroup that binned it) summed in a fixed order, then added to dbias
+void flash_dbias_reduce(const FlashParams& p, int part_rows, hipStream_t s) {
+    if (!p.dbias || !p.dbias_part) return;
+    const int Wd = p.nh * p.ws * p.ws;
+    const float* rows; int nrows;
+    gg_reduce_rows(p.dbias_part, part_rows, Wd, s, &rows, &nrows);
+    hipLaunchKernelGGL(flash_dbias_final_kernel, dim3((unsigned)gg_cdiv(Wd, 256)), dim3(256), 0, s, rows, nrows, Wd, p.dbias);
+}
+// The two-pass (streaming) backward of one storage type and head dim: with a dS scratch the dK/dV pass runs first and hands dS to the one-product dQ pass,
+// without one both passes recompute P from lse.  Grid: one workgroup per (window, head, 64-row tile).
+template <typename T, int D>
+void flash_bwd_streaming(const FlashParams& p, dim3 grid, hipStream_t s) {
+    const dim3 block(256);
+    const size_t lds_q = flash_lds_fwd(p, D, 64), lds_kv = flash_lds_dkv(p, D, 64, p.dbias != nullptr), lds_k = (size_t)64 * (D + 4) * 4;
+    if (p.ds_scratch) {
+        if (p.dbias) hipLaunchKernelGGL((flash_bwd_dkv_kernel<T, D, true, true>), grid, block, lds_kv, s, p);
+        else hipLaunchKernelGGL((flash_bwd_dkv_kernel<T, D, false, true>), grid, block, lds_kv, s, p);
+        hipLaunchKernelGGL((flash_bwd_dq_ds_kernel<T, D>), grid, block, lds_k, s, p);
+        return;
+    }
+    hipLaunchKernelGGL((flash_bwd_dq_kernel<T, D>), grid, block, lds_q, s, p);
+    if (p.dbias) hipLaunchKernelGGL((flash_bwd_dkv_kernel<T, D, true>), grid, block, lds_kv, s, p);
+    else hipLaunchKernelGGL((flash_bwd_dkv_kernel<T, D, false>), grid, block, lds_kv, s, p);
 }
 
 }  // namespace
@@ -1251,7 +1138,7 @@ extern "C" int gg_attention_flash_fwd(const GgAttnArgs* a, int dtype, void* stre
         GG_LAUNCH_CHECK();
         return 0;
     }
-    const bool res = flash_resident(p, a->head_dim, false);
+    const bool res = flash_fwd_resident(p, a->head_dim);
     const bool ftail = res && flash_fwd_tail(p);
     const dim3 grid((unsigned)(a->num_windows * a->num_heads * (res ? 1 : p.ntile))), block(res ? 64 * (ftail ? p.npad / 16 - 1 : std::min(16, p.npad / 16)) : 256);
     const size_t lds = flash_lds_fwd(p, a->head_dim, res ? p.npad : 64) + (ftail ? flash_lds_fwd_tail(p, a->head_dim) : 0);
@@ -1364,11 +1251,6 @@ int gg_attention_flash_bwd_impl(const GgAttnArgs* a, int dtype, int forward_roun
         GG_LAUNCH_CHECK();
         return 0;
     }
-    // resident form also for single-tile windows (7 x 7) when a dS scratch is there: the dQ phase then runs inside the dK/dV kernel
-    const bool res = flash_resident(p, a->head_dim, p.dbias != nullptr) || (p.ds_scratch != nullptr && p.ntile == 1);
-    const dim3 grid((unsigned)(a->num_windows * a->num_heads * (res ? 1 : p.ntile))), block(res ? 64 * std::min(16, p.npad / 16) : 256);
-    const int R = res ? p.npad : 64;
-    const size_t lds_q = flash_lds_fwd(p, a->head_dim, R), lds_kv = flash_lds_dkv(p, a->head_dim, R, p.dbias != nullptr);
     hipStream_t s = (hipStream_t)stream;
     const double es = dtype ? 4.0 : 2.0;
     {
@@ -1399,12 +1281,7 @@ int gg_attention_flash_bwd_impl(const GgAttnArgs* a, int dtype, int forward_roun
 #undef GG_SP_BWD
             if (lds > 64 * 1024) GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(kern)));
             hipLaunchKernelGGL(kern, dim3((unsigned)(a->num_windows * a->num_heads)), dim3(64 * ((nt16 + 1) / 2)), lds, s, p);
-            if (p.dbias && p.dbias_part) {
-                const int Wd = p.nh * p.ws * p.ws;
-                const float* rows; int nrows;
-                gg_reduce_rows(p.dbias_part, a->num_windows, Wd, s, &rows, &nrows);
-                hipLaunchKernelGGL(flash_dbias_final_kernel, dim3((unsigned)gg_cdiv(Wd, 256)), dim3(256), 0, s, rows, nrows, Wd, p.dbias);
-            }
+            flash_dbias_reduce(p, a->num_windows, s);
             GG_LAUNCH_CHECK();
             return 0;
         }
@@ -1428,46 +1305,23 @@ int gg_attention_flash_bwd_impl(const GgAttnArgs* a, int dtype, int forward_roun
         if (dtype == 1) { if (a->head_dim == 32) GG_FL_FUSED(float, 32); else GG_FL_FUSED(float, 64); }
         else { if (a->head_dim == 32) GG_FL_FUSED(bf16, 32); else GG_FL_FUSED(bf16, 64); }
 #undef GG_FL_FUSED
-        if (p.dbias && p.dbias_part) {
-            const int Wd = p.nh * p.ws * p.ws;
-            const float* rows; int nrows;
-            gg_reduce_rows(p.dbias_part, a->num_windows, Wd, s, &rows, &nrows);
-            hipLaunchKernelGGL(flash_dbias_final_kernel, dim3((unsigned)gg_cdiv(Wd, 256)), dim3(256), 0, s, rows, nrows, Wd, p.dbias);
-        }
+        flash_dbias_reduce(p, a->num_windows, s);
         GG_LAUNCH_CHECK();
         return 0;
     }
+    // The two-pass forms, streaming only: the routes of windows beyond 256 padded tokens (head dim 64: beyond 160), and of every window under GG_ATTN_NO_FUSED_BWD.
+    // No resident two-kernel backward exists (one workgroup per (window, head) with whole-window images in LDS, as the forward has), because no shape
+    // could reach one behind the single-pass test above.  Such a form needs flash_lds_dkv(p, D, npad, dbias) <= 64 KB.  flash_lds_fused is
+    // flash_lds_dkv + 4 npad (D + 4) + 160 npad bytes; the first addend is at most half of flash_lds_dkv (<= 32 KB); flash_lds_dkv <= 64 KB forces
+    // npad <= 65536 / (4 (2 * 36 + 3)) = 218, so the last is at most 35 KB: at most 131 KB < 160 KB in all, with npad <= 218 < 256 -- the window is
+    // single-pass.  (A single 64-token tile with a dS scratch, the other case the resident form once served: ws <= 8, flash_lds_fused about 65 KB.)
     // algorithmic: 5 products (S, dP, dV, dK, dQ) = 10 N^2 D, whatever the pass structure recomputes (attention.hip declares the same)
     GG_PROF(GG_CAT_ATTN, 10.0 * a->num_windows * a->num_heads * (double)p.N * p.N * a->head_dim,
             8.0 * es * a->num_windows * a->num_heads * (double)p.N * a->head_dim, stream);
-    // with a dS scratch: dK/dV pass first (stores dS), then the one-product dQ pass
-    const size_t lds_k = ((size_t)R * (a->head_dim + 4)) * 4;
-#define GG_FL_BWD_DS(T_, D_, R_)                                                                              \
-    do {                                                                                                      \
-        if (p.dbias) hipLaunchKernelGGL((flash_bwd_dkv_kernel<T_, D_, true, R_, true>), grid, block, lds_kv, s, p); \
-        else hipLaunchKernelGGL((flash_bwd_dkv_kernel<T_, D_, false, R_, true>), grid, block, lds_kv, s, p);  \
-        if (!R_) hipLaunchKernelGGL((flash_bwd_dq_ds_kernel<T_, D_, false, 1>), grid, block, lds_k, s, p);    /* (resident form: second phase of the kernel above) */ \
-    } while (0)
-#define GG_FL_BWD2(T_, D_, R_)                                                                                \
-    do {                                                                                                      \
-        if (p.ds_scratch) { GG_FL_BWD_DS(T_, D_, R_); break; }                                                \
-        if (R_ && D_ == 32 && !gg_dev_env("GG_ATTN_DQ_QS1")) hipLaunchKernelGGL((flash_bwd_dq_kernel<T_, D_, R_, 2>), grid, dim3(64 * ((p.npad / 16 + 1) / 2)), lds_q, s, p); \
-        else hipLaunchKernelGGL((flash_bwd_dq_kernel<T_, D_, R_>), grid, block, lds_q, s, p);                 \
-        if (p.dbias) hipLaunchKernelGGL((flash_bwd_dkv_kernel<T_, D_, true, R_>), grid, block, lds_kv, s, p); \
-        else hipLaunchKernelGGL((flash_bwd_dkv_kernel<T_, D_, false, R_>), grid, block, lds_kv, s, p);        \
-    } while (0)
-#define GG_FL_BWD(T_, D_) do { if (res) GG_FL_BWD2(T_, D_, true); else GG_FL_BWD2(T_, D_, false); } while (0)
-    if (dtype == 1) { if (a->head_dim == 32) GG_FL_BWD(float, 32); else GG_FL_BWD(float, 64); }
-    else { if (a->head_dim == 32) GG_FL_BWD(bf16, 32); else GG_FL_BWD(bf16, 64); }
-#undef GG_FL_BWD
-#undef GG_FL_BWD2
-#undef GG_FL_BWD_DS
-    if (p.dbias && p.dbias_part) {
-        const int Wd = p.nh * p.ws * p.ws;
-        const float* rows; int nrows;
-        gg_reduce_rows(p.dbias_part, a->num_windows * (res ? 1 : p.ntile), Wd, s, &rows, &nrows);
-        hipLaunchKernelGGL(flash_dbias_final_kernel, dim3((unsigned)gg_cdiv(Wd, 256)), dim3(256), 0, s, rows, nrows, Wd, p.dbias);
-    }
+    const dim3 grid((unsigned)(a->num_windows * a->num_heads * p.ntile));
+    if (dtype == 1) { if (a->head_dim == 32) flash_bwd_streaming<float, 32>(p, grid, s); else flash_bwd_streaming<float, 64>(p, grid, s); }
+    else { if (a->head_dim == 32) flash_bwd_streaming<bf16, 32>(p, grid, s); else flash_bwd_streaming<bf16, 64>(p, grid, s); }
+    flash_dbias_reduce(p, a->num_windows * p.ntile, s);      // one partial row per 64-key tile of every window
     GG_LAUNCH_CHECK();
     return 0;
 }

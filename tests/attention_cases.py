@@ -535,9 +535,9 @@ ROUTES = [
     _route("resident_f32_hd64_50", "flash", "clip", 50, 64, kernels="flash_fwd_kernel<float,64,true> (4 strips, no tail) + flash_bwd_fused_kernel<float,64,false,4>"),
     _route("resident_f32_hd64_80", "flash", "clip", 80, 64, kernels="flash_fwd_kernel<float,64,true> with the cooperative tail + flash_bwd_fused_kernel<float,64,false,0>"),
     _route("fused_f32_16x16", "flash", "tinyvit", 256, 32, ws=16, bias=True, kernels="flash_fwd_kernel<float,32,false> (streaming: 77 KB > 64 KB) + flash_bwd_fused_kernel<float,32,*,0>"),
-    _route("stream_f32_hd64_200", "flash", "clip", 200, 64, kernels="flash_fwd_kernel<float,64,false> + flash_bwd_dq_kernel / flash_bwd_dkv_kernel<float,64,false,false>"),
+    _route("stream_f32_hd64_200", "flash", "clip", 200, 64, kernels="flash_fwd_kernel<float,64,false> + flash_bwd_dq_kernel<float,64> / flash_bwd_dkv_kernel<float,64,false>"),
     _route("stream_f32_hd64_257", "flash", "clip", 257, 64, kernels="the same, 5 tiles with one live row in the last"),
-    _route("stream_f32_24x24", "flash", "tinyvit", 576, 32, ws=24, bias=True, kernels="flash_fwd_kernel<float,32,false> + flash_bwd_dq_kernel / flash_bwd_dkv_kernel<float,32,*,false> with bias"),
+    _route("stream_f32_24x24", "flash", "tinyvit", 576, 32, ws=24, bias=True, kernels="flash_fwd_kernel<float,32,false> + flash_bwd_dq_kernel<float,32> / flash_bwd_dkv_kernel<float,32,*> with bias"),
     _route("handoff_f32_hd64_200", "flash", "clip", 200, 64, ds_handoff=True, kernels="flash_bwd_dkv_kernel<.., ds handoff> + flash_bwd_dq_ds_kernel"),
     _route("handoff_f32_24x24", "flash", "tinyvit", 576, 32, ws=24, bias=True, ds_handoff=True, kernels="the same with bias and dbias"),
     _route("dtype3_65", "flash", "clip", 65, 64, split=True, kernels="flash64_split_q_kernel<3,false|true> + flash64_split_dkv_kernel<3>"),
@@ -574,3 +574,48 @@ def route_case(r, cls):
 def route_params():
     """[(route name, class)] for every class that applies to every route."""
     return [(r["name"], c) for r in ROUTES for c in classes_for(r["bias"], r["causal"])]
+
+
+# ------------------------------------------------------------------------------------------- the bits of the streaming backward before it lost its resident forms
+# tests/golden/attention_bwd_parent.json (tools/make_attention_bwd_parent_golden.py) holds SHA-256 digests of dq, dk, dv of these calls from the build in which
+# flash_bwd_dq_kernel, flash_bwd_dq_ds_kernel and flash_bwd_dkv_kernel still carried their resident (RES) template forms; the smallest shapes that reach each
+# streaming kernel, 2 heads, 2 sequences / images, the `plain` class.  (name, layout, N, head dim, ws, map side, windows, storage, dS hand-off):
+#   161 tokens at head dim 64: npad 176, the single-pass kernel would need 173,904 B of LDS against 163,840 -- the first length that streams at head dim 64;
+#   257 tokens at head dim 32: the first length beyond 256, 5 tiles with one token in the last;
+#   17 x 17 windows on a 34 x 34 map (4 windows an image), bias and dbias: the windowed streaming route.
+PARENT_BWD = (
+    ("lin161_hd64_f32", "clip", 161, 64, 0, 0, 2, "f32", False),
+    ("lin161_hd64_bf16", "clip", 161, 64, 0, 0, 2, "bf16", False),
+    ("lin161_hd64_f32_handoff", "clip", 161, 64, 0, 0, 2, "f32", True),
+    ("lin257_hd32_f32", "clip", 257, 32, 0, 0, 2, "f32", False),
+    ("lin257_hd32_bf16", "clip", 257, 32, 0, 0, 2, "bf16", False),
+    ("win17_hd32_f32", "tinyvit", 289, 32, 17, 34, 8, "f32", False),
+    ("win17_hd32_f32_handoff", "tinyvit", 289, 32, 17, 34, 8, "f32", True),
+    ("win17_hd32_bf16", "tinyvit", 289, 32, 17, 34, 8, "bf16", False),
+)
+
+
+def _sha(t):
+    """SHA-256 of a tensor's raw bytes (f32 or 16-bit storage, C order)."""
+    import hashlib
+    t = t.detach().cpu().contiguous()
+    return hashlib.sha256(t.view(torch.int32 if t.dtype == F32 else torch.int16).numpy().tobytes()).hexdigest()
+
+
+def parent_bwd_bits(ops):
+    """{name: {"inputs": {tensor: digest}, "dq" / "dk" / "dv": digest}} of the PARENT_BWD calls, run on the GPU through ``ops`` (geoguessr_ai_amd.ops).  The
+    inputs are the seeded qkv / dout / table and the forward's own out / lse (the backward recomputes P from them); dq, dk, dv are hashed in canonical form,
+    in the storage type.  dbias is requested on the window cases and not hashed: its bins are filled by floating-point atomics in no fixed order."""
+    store = {}
+    for name, layout, N, hd, ws, map_hw, windows, storage, handoff in PARENT_BWD:
+        c = case(layout, N, hd, 2, windows, ws, False, storage, "plain", map_hw)
+        qkv, dout = c["qkv"].cuda(), c["dout"].cuda()
+        table = c["table"].cuda() if ws else None
+        out, lse = ops.attention_flash(qkv, want_lse=True, bias_table=table, **c["kw"])
+        dqkv, dbias = ops.attention_flash(qkv, dout=dout, out=out, lse=lse, bias_table=table, want_dbias=table is not None, ds_handoff=handoff, **c["kw"])
+        assert (dbias is not None) == bool(ws) and dqkv.dtype == c["dtype"]
+        inputs = dict(qkv=_sha(qkv), dout=_sha(dout), out=_sha(out), lse=_sha(lse))
+        if table is not None:
+            inputs["table"] = _sha(table)
+        store[name] = dict(inputs=inputs, **{n: _sha(t.to(c["dtype"])) for n, t in zip(("dq", "dk", "dv"), canon_dqkv(c, dqkv))})
+    return store

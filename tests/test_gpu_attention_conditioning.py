@@ -23,11 +23,12 @@ gg_attention_flash_bwd_impl, in this order:
                                                                                                                                 through gg_attention_bwd: rounded bias)
   <= 256 padded tokens and the three window images fit  -> flash_bwd_fused_kernel<T,D,dbias,NT> (single pass; 4 n + 1 strips    fused_f32_16x16 (with bias), resident_f32_*
   160 KB (head dim 32: always; head dim 64: <= 160)        and enough waves: one owner wave fewer, cooperative tail)            (hd32_80: 4 owner waves), flash_bf16_hd64_80
-  else, ds_scratch given                                -> flash_bwd_dkv_kernel<.., handoff> + flash_bwd_dq_ds_kernel           handoff_f32_hd64_200, handoff_f32_24x24
-  else                                                  -> flash_bwd_dq_kernel + flash_bwd_dkv_kernel, streaming                stream_f32_hd64_200, _257, stream_f32_24x24,
-                                                                                                                                flash_bf16_hd64_257, flash_bf16_24x24
-  The RESIDENT two-kernel backward (and the resident dS hand-off) is behind the single-pass test: it needs a shape that is resident (<= 208 / 112 tokens) and
-  not single-pass (> 256 / 160 tokens).  There is none: it runs only under GG_ATTN_NO_FUSED_BWD and is not a route of this module.
+  else, ds_scratch given                                -> flash_bwd_dkv_kernel<T,D,dbias,true> + flash_bwd_dq_ds_kernel<T,D>   handoff_f32_hd64_200, handoff_f32_24x24
+                                                           (streaming: a workgroup per 64-row tile; dS handed to the dQ pass)
+  else                                                  -> flash_bwd_dq_kernel<T,D> + flash_bwd_dkv_kernel<T,D,dbias>,          stream_f32_hd64_200, _257, stream_f32_24x24,
+                                                           streaming                                                            flash_bf16_hd64_257, flash_bf16_24x24
+  The resident form of the two-pass kernels (whole-window images in LDS) was removed: a window small enough for it (<= 208 / 112 tokens) always passes the
+  single-pass test before it (derivation in gg_attention_flash_bwd_impl), so GG_ATTN_NO_FUSED_BWD selects these same streaming kernels.
 gg_attention_causal_fwd / _bwd (head dim 64 only, at most 77 tokens):
   dtype 0                                               -> flash_fwd_kernel<bf16,64,false,true> + flash_bwd_fused_kernel<bf16,64,false,0,true>   causal_bf16_17, _77
   dtype 1, 3 (the same kernels)                         -> flash64_split_q_kernel<3,*,true> + flash64_split_dkv_kernel<3,true>                   causal_f32_17, _77, causal_split_17, _77
@@ -128,4 +129,22 @@ def test_split_attention_backward_on_the_rescale_spike_input(ops):
         got = dict(out=A.canon_out(c, g["out"]), lse=A.canon_lse(c, g["lse"]))
         got["dq"], got["dk"], got["dv"] = (A.canon_out(c, g[n]) for n in ("dq", "dk", "dv"))
         bad += A.check(c, got, f"rescale spike hd64 N={N} {'dtype 3' if split else 'dtype 1'}", split_products=split)
+    assert not bad, bad
+
+
+def test_streaming_backward_bits_unchanged_from_the_parent_build(ops):
+    """dq, dk, dv of the seeded streaming-route calls of tests/attention_cases.py::parent_bwd_bits (head dim 64 at 161 tokens, head dim 32 at 257 tokens and on
+    17 x 17 windows with bias and dbias; f32 and bf16 storage; with and without the dS hand-off) equal, bit for bit, what the build gave in which the two-pass
+    backward kernels still had their resident template forms (tests/golden/attention_bwd_parent.json, tools/make_attention_bwd_parent_golden.py).  The inputs'
+    digests -- the forward's out and lse among them -- are compared first, so that a changed input is reported as such.  dbias is not compared here (atomics in
+    no fixed order); the fp64 gates above hold it."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "attention_bwd_parent.json")) as f:
+        gold = json.load(f)
+    got = A.parent_bwd_bits(ops)
+    assert sorted(got) == sorted(gold) == sorted(c[0] for c in A.PARENT_BWD)
+    for name in sorted(got):
+        assert got[name]["inputs"] == gold[name]["inputs"], f"{name}: the inputs differ from the golden file's (not a finding about the backward)"
+    bad = [(name, t) for name in sorted(got) for t in ("dq", "dk", "dv") if got[name][t] != gold[name][t]]
     assert not bad, bad

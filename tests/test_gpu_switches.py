@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GROUPS = {
     # every fusion off, every multi-window / resident / ring form replaced by its plain fallback
     "plain_fallbacks": dict(GG_NO_FUSE_DW_S1="1", GG_NO_FUSE_DW_S2="1", GG_NO_FUSE_BNBWD="1", GG_NO_BNGEMM="1", GG_NO_PRO="1", GG_F32_NO_FUSE="1", GG_NO_LN_COLSUM="1",
-                            GG_ATTN_SMALL="0", GG_ATTN_FLASH_NO_RES="1", GG_ATTN_DQ_QS1="1",
+                            GG_ATTN_SMALL="0", GG_ATTN_FLASH_NO_RES="1",
                             GG_GEMM_F32_ROWS_EPI="0", GG_ATTN_NO_DS_SCRATCH="1", GG_ATTN_NO_FUSED_BWD="1", GG_ATTN_FWD_NO_TAIL="1", GG_GEMM_F32_PRO_RING="0", GG_GEMM_F32_NO_W96="1",
                             GG_ATTN_NO_SPLIT="1", GG_GEMM_DMA="0", GG_GEMM_TILE="n", GG_GEMM_F32_NO_SMALL="1", GG_SWITCH_PARITY_FROZEN="1"),
     # the older kernel generation: the depthwise data gradient without its act'(BN) epilogue, the fp32 GEMM's general epilogue with 64-byte-run stores, the
@@ -25,7 +25,7 @@ GROUPS = {
     # grid is below their resident count either way, so it is exercised, not distinguished)
     "older_kernels": dict(GG_NO_FUSE_BNBWD_EPI="1", GG_GEMM_F32_ROWS_EPI="0", GG_GEMM_F32_PRO_RING="0", GG_GEMM_F32_NO_PERSIST="1",
                           GG_GEMM_F32_NO_PAIR_STORE="1", GG_GEMM_TILE="w",
-                          GG_ATTN_NO_FUSED_BWD="1", GG_ATTN_NO_SPLIT="1", GG_GEMM_F32_NO_SPLITK="1", GG_GEMM_F32_SMALL_MAX="64", GG_SWITCH_PARITY_FROZEN="1"),       # (two-pass attention backward with the dS hand-off: the form for windows beyond 256 tokens)
+                          GG_ATTN_NO_FUSED_BWD="1", GG_ATTN_NO_SPLIT="1", GG_GEMM_F32_NO_SPLITK="1", GG_GEMM_F32_SMALL_MAX="64", GG_SWITCH_PARITY_FROZEN="1"),       # (the streaming two-pass attention backward with the dS hand-off: the form windows beyond 256 tokens take)
     # the single-pass attention backward with one wave per key strip (no cooperative tail strip): the form every window whose strip count is not 4 n + 1 takes
     "attention_no_tail": dict(GG_ATTN_FUSED_NO_TAIL="1", GG_ATTN_NO_SPLIT="1", GG_SWITCH_PARITY_FROZEN="1"),
     # the f32-MFMA window attention (the form head dim 64 and windows other than 7 x 7 / 12 x 12 / 14 x 14 take) with everything else at its default; the
