@@ -1,7 +1,7 @@
 // The device-side training transform of the TinyViT classifier fine-tune (include/gg_aug.h): random-resized-crop, flip, RandAugment, ToTensor and
 // Normalize of timm's create_transform(is_training=True) for a whole batch of raw uint8 images, from one host record per image.  Streaming uint8 work, HBM-bound:
 //   aug_upload_kernel      the record table travels as kernel arguments (a few records per launch): nothing reads the caller's host array after the call returns
-//   aug_coeffs_kernel      Pillow's resampling windows and 22-bit weights of all 2B axes in one launch (pil_coeffs_kernel's statements, per axis of blockIdx.y)
+//   aug_coeffs_kernel      Pillow's resampling windows and 22-bit weights of all 2B axes in one launch (eval_coeffs_row of eval_passes.h, per axis of blockIdx.y)
 //   aug_horizontal_kernel  src[top + y][left + .] -> tmp[y][0 .. S), rows of the crop box only
 //   aug_vertical_kernel    tmp -> image 0 of the ping-pong pair, the flip as a mirrored store
 //   aug_stats_kernel       per layer, only if some image needs it: per-channel histograms (AutoContrast, Equalize) or the grey sum (Contrast), integer atomics in LDS,
@@ -9,8 +9,10 @@
 //   aug_apply_kernel       per layer: the image's op (or a copy when its slot is not applied) from one ping-pong image into the other; table ops build their 768-byte
 //                          table in LDS per workgroup
 //   aug_pack_kernel        (B, S, S, 3) u8 -> (B, 3, S, S) f32 normalised, and the optional uint8 copy
-// One image per blockIdx.y everywhere, so op dispatch, `applied`, the flip and which axes resample are workgroup-uniform.  No float atomics.
+// One image per blockIdx.y everywhere, so op dispatch, `applied`, the flip and which axes resample are workgroup-uniform.  No float atomics.  The resampler's filter,
+// windows, weights, clip8, ksize rule and alignment are eval_passes.h's; the two passes here are this file's own (a box inside an image, the mirrored store).
 #include "common.h"
+#include "eval_passes.h"
 #include "../../include/gg.h"
 #include "augment_math.h"
 #include <string.h>
@@ -35,52 +37,16 @@ __global__ __launch_bounds__(256) void aug_upload_kernel(AugChunk c, int n, AugD
     for (int i = threadIdx.x; i < words; i += 256) d[i] = s[i];
 }
 
-__device__ __forceinline__ double aug_pil_filter(double x, int filter) {
-#pragma clang fp contract(off)
-    if (x < 0.0) x = -x;
-    if (filter == 2) return x < 1.0 ? 1.0 - x : 0.0;                       // BILINEAR
-    const double a = -0.5;                                                 // BICUBIC
-    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-    return 0.0;
-}
 // blockIdx.y = 2 * image + axis (0: columns, 1: rows); bounds[(2 * image + axis) * 2S + 2 xx] = (xmin, xmax); kk at the axis's offset, ksize ints per output index
 __global__ __launch_bounds__(64) void aug_coeffs_kernel(const AugDev* __restrict__ tab, int S, int filter, int* __restrict__ bounds, int* __restrict__ pool) {
-#pragma clang fp contract(off)
     const int b = blockIdx.y >> 1, axis = blockIdx.y & 1;
     const AugDev& d = tab[b];
     const int ksize = axis ? d.ky : d.kx;
     if (ksize == 0) return;                                                 // the axis keeps its size: no pass, no table
-    const int in_size = axis ? d.r.h : d.r.w;
     const int xx = blockIdx.x * 64 + threadIdx.x;
     if (xx >= S) return;
-    const double scale = (double)((float)in_size - 0.0f) / S;
-    const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = (filter == 2 ? 1.0 : 2.0) * filterscale;
-    const double center = 0.0 + (xx + 0.5) * scale;
-    const double ss = 1.0 / filterscale;
-    int xmin = (int)(center - support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)(center + support + 0.5);
-    if (xmax > in_size) xmax = in_size;
-    xmax -= xmin;
-    if (xmax > ksize) xmax = ksize;                                         // never taken (ksize = 2 ceil(support) + 1); keeps every store inside the row
-    int* k = pool + (axis ? d.ky_off : d.kx_off) + (int64_t)xx * ksize;
-    double ww = 0.0;
-    for (int x = 0; x < xmax; ++x) ww += aug_pil_filter((x + xmin - center + 0.5) * ss, filter);
-    for (int x = 0; x < ksize; ++x) {
-        int v = 0;
-        if (x < xmax) {
-            double w = aug_pil_filter((x + xmin - center + 0.5) * ss, filter);
-            if (ww != 0.0) w /= ww;
-            v = w < 0 ? (int)(-0.5 + w * (double)(1 << 22)) : (int)(0.5 + w * (double)(1 << 22));
-        }
-        k[x] = v;
-    }
-    int* bd = bounds + ((int64_t)blockIdx.y * S + xx) * 2;
-    bd[0] = xmin; bd[1] = xmax;
+    eval_coeffs_row(axis ? d.r.h : d.r.w, S, filter, xx, ksize, pool + (axis ? d.ky_off : d.kx_off) + (int64_t)xx * ksize, bounds + ((int64_t)blockIdx.y * S + xx) * 2);
 }
-__device__ __forceinline__ unsigned char aug_clip8(int ss) { return (unsigned char)min(max(ss >> 22, 0), 255); }
 
 // tmp_b[y][x][c], y over the box's rows, x over the S output columns
 __global__ __launch_bounds__(256) void aug_horizontal_kernel(const AugDev* __restrict__ tab, const unsigned char* __restrict__ src, int S, const int* __restrict__ bounds,
@@ -107,7 +73,7 @@ __global__ __launch_bounds__(256) void aug_horizontal_kernel(const AugDev* __res
                 const unsigned char* px = row + (xmin + j) * 3;
                 s0 += px[0] * w; s1 += px[1] * w; s2 += px[2] * w;
             }
-            r = aug_clip8(s0); g = aug_clip8(s1); bl = aug_clip8(s2);
+            r = eval_clip8(s0); g = eval_clip8(s1); bl = eval_clip8(s2);
         }
         unsigned char* o = out + i * 3;
         o[0] = r; o[1] = g; o[2] = bl;
@@ -137,7 +103,7 @@ __global__ __launch_bounds__(256) void aug_vertical_kernel(const AugDev* __restr
                 const unsigned char* q = in + ((int64_t)(ymin + j) * S + x) * 3;
                 s0 += q[0] * w; s1 += q[1] * w; s2 += q[2] * w;
             }
-            px[0] = aug_clip8(s0); px[1] = aug_clip8(s1); px[2] = aug_clip8(s2);
+            px[0] = eval_clip8(s0); px[1] = eval_clip8(s1); px[2] = eval_clip8(s2);
         }
         unsigned char* o = out + ((int64_t)y * S + (flip ? S - 1 - x : x)) * 3;
         o[0] = px[0]; o[1] = px[1]; o[2] = px[2];
@@ -258,16 +224,6 @@ __global__ __launch_bounds__(256) void aug_pack_kernel(const unsigned char* __re
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-static int aug_ksize(int in_size, int out_size, int filter, int* ksize) {
-    // precompute_coeffs of Resample.c, as pil_axis in preprocess.hip: support = filter support * max(scale, 1), ksize = 2 ceil(support) + 1
-    const double scale = (double)((float)in_size - 0.0f) / out_size;
-    const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = (filter == 2 ? 1.0 : 2.0) * filterscale;
-    if (ceil(support) * 2 + 1 > 1 << 20) return -1;
-    *ksize = (int)ceil(support) * 2 + 1;
-    return 0;
-}
-static int64_t aug_align(int64_t b) { return (b + 255) / 256 * 256; }
 struct AugPlan {
     int64_t tab, bounds, pool, tmp, img, hist, grey, total;        // byte offsets of the regions, and the total
     int64_t pool_ints, tmp_bytes;                                  // running sizes while the images are walked
@@ -305,7 +261,7 @@ static int aug_image(const GgAugArgs* a, int b, AugPlan* p, AugDev* d) {
     } else {                                                       // the bound over every record: the whole image as the box, both axes resampled
         d->r.h = H; d->r.w = W;
     }
-    GG_CHECK(aug_ksize(d->r.w, S, a->filter, &d->kx) == 0 && aug_ksize(d->r.h, S, a->filter, &d->ky) == 0, "gg_aug: record %d: reduction factor too large", b);
+    GG_CHECK(eval_ksize(d->r.w, S, a->filter, &d->kx) == 0 && eval_ksize(d->r.h, S, a->filter, &d->ky) == 0, "gg_aug: record %d: reduction factor too large", b);
     if (a->records && d->r.w == S) d->kx = 0;                      // ImagingResample: a pass runs only when that axis changes size
     if (a->records && d->r.h == S) d->ky = 0;
     d->src_off = a->offsets[b]; d->H = H; d->W = W;
@@ -322,13 +278,13 @@ static int aug_plan(const GgAugArgs* a, AugPlan* p) {
     for (int b = 0; b < a->B; ++b) GG_TRY(aug_image(a, b, p, &d));
     const int64_t B = a->B, S = a->S;
     int64_t off = 0;
-    p->tab = off; off += aug_align(B * (int64_t)sizeof(AugDev));
-    p->bounds = off; off += aug_align(2 * B * S * 2 * 4);
-    p->pool = off; off += aug_align(4 * p->pool_ints);
-    p->tmp = off; off += aug_align(p->tmp_bytes);
-    p->img = off; off += 2 * aug_align(3 * B * S * S);
-    p->hist = off; off += aug_align(4 * B * 768);                  // the bins and, right behind them, the grey sums: one memset clears both
-    p->grey = off; off += aug_align(8 * B);
+    p->tab = off; off += eval_align(B * (int64_t)sizeof(AugDev));
+    p->bounds = off; off += eval_align(2 * B * S * 2 * 4);
+    p->pool = off; off += eval_align(4 * p->pool_ints);
+    p->tmp = off; off += eval_align(p->tmp_bytes);
+    p->img = off; off += 2 * eval_align(3 * B * S * S);
+    p->hist = off; off += eval_align(4 * B * 768);                  // the bins and, right behind them, the grey sums: one memset clears both
+    p->grey = off; off += eval_align(8 * B);
     p->total = off;
     return 0;
 }
@@ -351,7 +307,7 @@ extern "C" int gg_aug_batch(const GgAugArgs* a, void* stream) {
     int* bounds = (int*)(w + p.bounds);
     int* pool = (int*)(w + p.pool);
     unsigned char* tmp = (unsigned char*)(w + p.tmp);
-    unsigned char* img[2] = {(unsigned char*)(w + p.img), (unsigned char*)(w + p.img) + aug_align(3LL * B * S * S)};
+    unsigned char* img[2] = {(unsigned char*)(w + p.img), (unsigned char*)(w + p.img) + eval_align(3LL * B * S * S)};
     unsigned* hist = (unsigned*)(w + p.hist);
     unsigned long long* grey = (unsigned long long*)(w + p.grey);
 

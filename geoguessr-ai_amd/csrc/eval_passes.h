@@ -1,7 +1,16 @@
-// Pillow's 8-bit resampler as device code, shared by eval_transform.hip (gg_eval_batch: one crop size per call) and pano_transform.hip (gg_pano_batch: the whole
-// resized image of every image, sizes differ per image): the per-image record, the window and weight statements of precompute_coeffs, the horizontal pass of one
-// image and the vertical pass's pixels.  The kernels around them decide where an image's windows, weights, intermediate and crop size come from.  Everything after
-// the weights is integer arithmetic: no layout choice can change a bit of the uint8 result.  Both objects are built with -ffp-contract=off (Makefile).
+// Pillow's 8-bit resampler (ImagingResample of src/libImaging/Resample.c, Pillow 12.2) as device code: the library's ONLY restatement of it, integer for integer --
+// the uint8 result is bit-identical to Image.resize (tests/golden/preprocess_pil.npz, eval_batch_pil.npz, produced by running Pillow / transformers).  Per axis and
+// output index the window [xmin, xmin + xmax) and double-precision filter weights, normalised by their sum, in 22-bit fixed point (the same double operations in the
+// same order); a horizontal pass into an 8-BIT intermediate image, clip8((2^21 + sum pixel * k) >> 22); then the vertical pass the same way.  Four entry points use it:
+//   gg_eval_batch      eval_transform.hip   one crop size per call: everything here
+//   gg_preprocess_pil  eval_transform.hip   one image: the B = 1 call of gg_eval_batch
+//   gg_pano_batch      pano_transform.hip   the whole resized image of every image, sizes differ per image: everything here
+//   gg_aug_batch       augment.hip          a box inside an image -> S x S: the filter, the window and weight statements, clip8, the ksize rule and the alignment; its
+//                                           two passes are its own (row stride of the image, the flip as a mirrored store)
+// What is shared: the per-image record, the window and weight statements of precompute_coeffs, the horizontal pass of one image, the vertical pass's pixels, and on
+// the host side the ksize rule and the region alignment.  The kernels around them decide where an image's windows, weights, intermediate and crop size come from.
+// Everything after the weights is integer arithmetic: no layout choice can change a bit of the uint8 result.  The weights are double arithmetic that must not be
+// fused: every object that includes this file is built with -ffp-contract=off (Makefile); the pragmas below do not bind the backend.
 #pragma once
 #include "common.h"
 #include <math.h>
@@ -103,9 +112,11 @@ __device__ __forceinline__ void eval_hcolumn(const unsigned char* base, const Of
         if (out[q]) { unsigned char* o = out[q] + x * 3; o[0] = px[q][0]; o[1] = px[q][1]; o[2] = px[q][2]; }
 }
 // The horizontal pass of one image by one workgroup of 256 threads (blockIdx.x strides over the row groups): out[y - row0][x][c], y over the source rows the crop
-// reads, x over the Wc crop columns; tstride bytes per intermediate row; bx / by the image's column / row windows, kk its column weights; lds EVAL_LDS_BYTES
+// reads, x over the Wc crop columns; tstride bytes per intermediate row; bx / by the image's column / row windows, kk its column weights; lds EVAL_LDS_BYTES;
+// rows: the source rows a workgroup takes per step, at most EVAL_ROWS (fewer rows make more workgroups of a call with few images; the launch's grid goes with it)
 __device__ __forceinline__ void eval_horizontal_image(const EvalDev& d, const unsigned char* __restrict__ img, int Hc, int Wc, int tstride, const int* __restrict__ bx,
-                                                      const int* __restrict__ by, const int* __restrict__ kk, unsigned char* __restrict__ out, unsigned int* lds) {
+                                                      const int* __restrict__ by, const int* __restrict__ kk, unsigned char* __restrict__ out, unsigned int* lds,
+                                                      int rows = EVAL_ROWS) {
     int first, last;
     eval_row_range(d, by, Hc, &first, &last);
     // the source columns [c0, c1) the crop's columns read: windows start and end in non-decreasing order along the axis
@@ -116,7 +127,7 @@ __device__ __forceinline__ void eval_horizontal_image(const EvalDev& d, const un
     const int64_t lstride64 = (span + 3 + 3) & ~3LL;                        // an LDS row: the span behind up to 3 bytes of misalignment, in whole dwords
     const bool staged = lstride64 <= EVAL_LDS_BYTES;
     const int lstride = staged ? (int)lstride64 : 0;
-    const int R = staged ? min(EVAL_ROWS, EVAL_LDS_BYTES / lstride) : EVAL_ROWS;
+    const int R = staged ? min(rows, EVAL_LDS_BYTES / lstride) : rows;
     const unsigned char* img_end = img + 3LL * d.H * d.W;
     for (int64_t y0 = first + (int64_t)blockIdx.x * R; y0 < last; y0 += (int64_t)gridDim.x * R) {
         const int nr = (int)min((int64_t)R, last - y0);
@@ -196,7 +207,7 @@ __device__ __forceinline__ void eval_vertical_dword(const EvalDev& d, const unsi
 
 // ---------------------------------------------------------------------------------------------------------------- host side
 static int eval_ksize(int in_size, int out_size, int filter, int* ksize) {
-    // precompute_coeffs of Resample.c, as pil_axis in preprocess.hip: support = filter support * max(scale, 1), ksize = 2 ceil(support) + 1
+    // precompute_coeffs of Resample.c (eval_window's scale and support): support = filter support * max(scale, 1), ksize = 2 ceil(support) + 1, at most 2^20
     const double scale = (double)((float)in_size - 0.0f) / out_size;
     const double filterscale = scale < 1.0 ? 1.0 : scale;
     const double support = (filter == 2 ? 1.0 : 2.0) * filterscale;

@@ -1,13 +1,15 @@
-// The eval transform of the raw-image path for whole batches (include/gg_eval.h): gg_preprocess_pil's arithmetic -- Pillow's 8-bit resize of the whole
-// image, the crop window, 1/255, (x - mean) / std -- for a packed batch of uint8 images of any sizes, one GgEvalGeom per image.  Streaming uint8 work:
+// The eval transform of the raw-image path (include/gg_eval.h, include/gg.h): Pillow's 8-bit resize of the whole image, the crop window, 1/255,
+// (x - mean) / std -- gg_eval_batch for a packed batch of uint8 images of any sizes, one GgEvalGeom per image, and gg_preprocess_pil for one image, which is the B = 1
+// call of the same passes (the raw-image side of the embedders: pretrain/tinyvit_embedder.py:51-53,67-69 timm's eval transform; pretrain/clip_embedder.py:25,51-55
+// CLIPProcessor; inference.py:74-85 a torchvision Compose).  Streaming uint8 work:
 //   eval_upload_kernel      the per-image table travels as kernel arguments (EVAL_CHUNK images per launch): nothing reads the caller's host arrays after the call returns
-//   eval_coeffs_kernel      Pillow's windows and 22-bit weights of all 2B axes in one launch, for the crop window's output indices only (pil_coeffs_kernel's statements)
+//   eval_coeffs_kernel      Pillow's windows and 22-bit weights of all 2B axes in one launch, for the crop window's output indices only (eval_coeffs_row's statements)
 //   eval_horizontal_kernel  only the source rows the crop's vertical windows read; a workgroup stages the column span of up to EVAL_ROWS source rows in LDS with dword
 //                           loads and a thread resamples EVAL_RPT rows of one output column from there (a weight is fetched once per EVAL_RPT rows)
 //   eval_vertical_kernel    a thread takes four consecutive bytes of an intermediate row (one dword load per tap, consecutive lanes on consecutive dwords), then 1/255,
 //                           normalise, the CHW f32 store and the optional HWC u8 store
 // One image per blockIdx.y everywhere, so which axes resample, the row range and the LDS layout are workgroup-uniform.  Everything after the weights is integer
-// arithmetic: no layout choice here can change a bit of the uint8 result.  The passes' statements live in eval_passes.h, which pano_transform.hip shares.
+// arithmetic: no layout choice here can change a bit of the uint8 result.  The passes' statements live in eval_passes.h, which pano_transform.hip and augment.hip share.
 #include "common.h"
 #include "eval_passes.h"
 #include "../../include/gg.h"
@@ -42,11 +44,11 @@ __global__ __launch_bounds__(64) void eval_coeffs_kernel(const EvalDev* __restri
 }
 // tmp_b[y - row0][x][c], y over the source rows the crop reads, x over the Wc crop columns; tstride bytes per intermediate row
 __global__ __launch_bounds__(256) void eval_horizontal_kernel(const EvalDev* __restrict__ tab, const unsigned char* __restrict__ src, int Hc, int Wc, int M, int tstride,
-                                                              const int* __restrict__ bounds, const int* __restrict__ pool, unsigned char* __restrict__ tmp) {
+                                                              const int* __restrict__ bounds, const int* __restrict__ pool, unsigned char* __restrict__ tmp, int rows) {
     __shared__ unsigned int lds[EVAL_LDS_BYTES / 4];
     const int b = blockIdx.y;
     const EvalDev d = tab[b];
-    eval_horizontal_image(d, src + d.src_off, Hc, Wc, tstride, bounds + (int64_t)(2 * b) * M * 2, bounds + (int64_t)(2 * b + 1) * M * 2, pool + d.kx_off, tmp + d.tmp_off, lds);
+    eval_horizontal_image(d, src + d.src_off, Hc, Wc, tstride, bounds + (int64_t)(2 * b) * M * 2, bounds + (int64_t)(2 * b + 1) * M * 2, pool + d.kx_off, tmp + d.tmp_off, lds, rows);
 }
 // vertical pass over tmp_b for the crop's rows, then 1/255 and (x - mean) / std; dst is CHW float32, dst_u8 (optional) the HWC uint8 crop
 __global__ __launch_bounds__(256) void eval_vertical_kernel(const EvalDev* __restrict__ tab, const unsigned char* __restrict__ tmp, int Hc, int Wc, int M, int tstride,
@@ -155,7 +157,9 @@ extern "C" int64_t gg_eval_workspace_bytes(const GgEvalArgs* args) {
     if (eval_plan(args, &p) != 0) return -1;
     return p.total;
 }
-extern "C" int gg_eval_batch(const GgEvalArgs* a, void* stream) {
+// rows: the source rows a workgroup of the horizontal pass takes per step.  EVAL_ROWS for a batch; the one-image call has only its own rows to make workgroups of and
+// takes EVAL_RPT, one step of a thread (with B = 1 the pass lasts as long as one workgroup does, and that grows with its rows)
+static int eval_run(const GgEvalArgs* a, void* stream, int rows) {
     EvalPlan p;
     GG_TRY(eval_plan(a, &p));
     GG_CHECK(a->geom, "gg_eval_batch: null geom");
@@ -190,8 +194,8 @@ extern "C" int gg_eval_batch(const GgEvalArgs* a, void* stream) {
     }
     {
         GG_PROF(GG_CAT_MOVE, 0, (double)p.src_read + (double)p.tmp_bytes, stream);
-        hipLaunchKernelGGL(eval_horizontal_kernel, dim3((unsigned)std::min<int64_t>(gg_cdiv(p.max_rows, EVAL_ROWS), 1024), (unsigned)B), dim3(256), 0, st, tab,
-                           (const unsigned char*)a->src, Hc, Wc, M, tstride, bounds, pool, tmp);
+        hipLaunchKernelGGL(eval_horizontal_kernel, dim3((unsigned)std::min<int64_t>(gg_cdiv(p.max_rows, rows), 1024), (unsigned)B), dim3(256), 0, st, tab,
+                           (const unsigned char*)a->src, Hc, Wc, M, tstride, bounds, pool, tmp, rows);
     }
     {
         GG_PROF(GG_CAT_MOVE, 0, (double)p.tmp_bytes + out_bytes, stream);
@@ -202,4 +206,46 @@ extern "C" int gg_eval_batch(const GgEvalArgs* a, void* stream) {
     }
     GG_LAUNCH_CHECK();
     return 0;
+}
+extern "C" int gg_eval_batch(const GgEvalArgs* a, void* stream) { return eval_run(a, stream, EVAL_ROWS); }
+
+// ---------------------------------------------------------------------------------------------------------------- gg_preprocess_pil
+// One image is a batch of one: the arguments of gg_eval_batch on the stack, the image at offset 0 of a packed buffer of its own size.
+struct EvalOne {
+    GgEvalArgs a;
+    int64_t offset;
+    int32_t H, W;
+    GgEvalGeom g;
+};
+static void eval_one(EvalOne* o, int Hs, int Ws, int filter, int Hc, int Wc) {
+    memset(o, 0, sizeof *o);
+    o->H = Hs; o->W = Ws;
+    o->a.offsets = &o->offset; o->a.heights = &o->H; o->a.widths = &o->W;
+    o->a.src_bytes = 3LL * Hs * Ws;
+    o->a.B = 1; o->a.Hc = Hc; o->a.Wc = Wc; o->a.filter = filter;
+}
+#define EVAL_ONE_SLACK 8                  // the entry point rounds the caller's workspace pointer up to gg_eval_batch's 8-byte alignment
+// No Hc and no top in the signature: the shared plan's bound over every geometry (geom == NULL: the longest windows, every source row in the intermediate) for the
+// tallest crop the call accepts inside Hr.  Every region grows with Hc, so the bound holds for every crop window (top, Hc) inside Hr at this Wc.
+extern "C" int64_t gg_preprocess_pil_workspace_bytes(int Hs, int Ws, int filter, int Hr, int Wr, int Wc) {
+    if (Hr <= 0 || Wr <= 0) return -1;
+    EvalOne o;
+    eval_one(&o, Hs, Ws, filter, std::min(Hr, GG_EVAL_MAX_CROP), Wc);
+    const int64_t need = gg_eval_workspace_bytes(&o.a);
+    return need < 0 ? -1 : need + EVAL_ONE_SLACK;
+}
+extern "C" int gg_preprocess_pil(const void* src_hwc_u8, int Hs, int Ws, int filter, int Hr, int Wr, int crop_top, int crop_left, int Hc, int Wc, int mul_rescale,
+                                 const float* mean3, const float* std3, float* dst_chw, void* dst_u8_hwc, void* workspace, void* stream) {
+    GG_CHECK(src_hwc_u8 && dst_chw && workspace, "gg_preprocess_pil: null src / dst / workspace");
+    GG_CHECK((mean3 == nullptr) == (std3 == nullptr), "gg_preprocess_pil: mean and std come together");
+    EvalOne o;
+    eval_one(&o, Hs, Ws, filter, Hc, Wc);
+    o.g.Hr = Hr; o.g.Wr = Wr; o.g.top = crop_top; o.g.left = crop_left;
+    o.a.geom = &o.g;
+    o.a.src = src_hwc_u8; o.a.dst = dst_chw; o.a.dst_u8 = dst_u8_hwc;
+    o.a.mul_rescale = mul_rescale; o.a.normalize = mean3 != nullptr;
+    for (int c = 0; c < 3 && mean3; ++c) { o.a.mean[c] = mean3[c]; o.a.std[c] = std3[c]; }
+    o.a.workspace = (void*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
+    o.a.workspace_bytes = INT64_MAX;      // this signature carries no size: the caller vouches for gg_preprocess_pil_workspace_bytes bytes
+    return eval_run(&o.a, stream, EVAL_RPT);
 }

@@ -555,8 +555,12 @@ int gg_preprocess_bilinear(const void* src, int src_u8, int N, int Hs, int Ws, f
  * the resized image, 1/255 (mul_rescale 0: x / 255 as torchvision's ToTensor, 1: x * (1/255) as transformers' rescale), (x - mean) / std.  The uint8
  * resize result is bit-identical to PIL.Image.resize (8-bit fixed-point resampling with an 8-bit intermediate image; tests/golden/preprocess_pil.npz).
  * src: device uint8 [Hs, Ws, 3] (HWC, RGB); dst_chw: device f32 [3, Hc, Wc]; dst_u8_hwc: optional device uint8 [Hc, Wc, 3] (the crop before 1/255);
- * mean3 / std3: HOST float[3] or both NULL; workspace: device, gg_preprocess_pil_workspace_bytes(...) bytes (-1: bad arguments).  The geometry rules of
- * the three pipelines (shortest edge, crop rounding) are host arithmetic: geoguessr-ai_amd/training/preprocess.py. */
+ * mean3 / std3: HOST float[3] or both NULL; workspace: device, any alignment, gg_preprocess_pil_workspace_bytes(...) bytes (-1: bad arguments).  The geometry
+ * rules of the three pipelines (shortest edge, crop rounding) are host arithmetic: geoguessr-ai_amd/training/preprocess.py.
+ * The call is gg_eval_batch (include/gg_eval.h) with B = 1: the same plan, the same four launches (table, coefficients, horizontal, vertical), the same
+ * refusals with the plan's messages, and so its limits: Hc, Wc <= GG_EVAL_MAX_CROP (2048), Hr, Wr <= GG_EVAL_MAX_RESIZED (2^20), Hs * Ws < 2^31 / 3, a
+ * filter window of at most 2^20 taps.  The workspace query has no Hc and no crop_top: it is that plan's bound over every crop window inside Hr at this Wc
+ * (every source row in the intermediate), for every Hr the call accepts. */
 int64_t gg_preprocess_pil_workspace_bytes(int Hs, int Ws, int filter, int Hr, int Wr, int Wc);
 int gg_preprocess_pil(const void* src_hwc_u8, int Hs, int Ws, int filter, int Hr, int Wr, int crop_top, int crop_left, int Hc, int Wc, int mul_rescale,
                       const float* mean3 /* host */, const float* std3 /* host */, float* dst_chw, void* dst_u8_hwc, void* workspace, void* stream);

@@ -10,7 +10,7 @@
  * the batch it rides in.
  *
  * Arithmetic (Pillow is the authority):
- *   crop + resize   img.crop(box).resize((S, S), filter): the 8-bit resampler of gg_preprocess_pil (22-bit fixed-point weights, an 8-bit intermediate image after the
+ *   crop + resize   img.crop(box).resize((S, S), filter): the 8-bit resampler of gg_eval_batch (22-bit fixed-point weights, an 8-bit intermediate image after the
  *                   horizontal pass) with the box's width / height as the input size; a pass runs only on an axis whose size changes; flip: out[y][S - 1 - x].
  *   table ops       a 256-entry table per image and channel.  Invert 255 - i; Posterize(bits) i & ~(2^(8 - bits) - 1), bits >= 8 the identity; Solarize(t) i < t ? i :
  *                   255 - i; SolarizeAdd(a) i < 128 ? min(255, i + a) : i; AutoContrast from the first / last occupied histogram bin lo / hi (hi <= lo: identity; else
@@ -86,7 +86,7 @@ int64_t gg_aug_workspace_bytes(const GgAugArgs* args);
  * (only when some image of the batch needs a histogram or a grey mean at that layer) and one apply pass, then the pack / normalise pass; a batch whose records all
  * have num_layers == 0 launches the resize stages and the pack only.  One image per blockIdx.y: every per-image decision is workgroup-uniform.
  * Refused before any launch, with nothing written: NULL pointers, B / S out of range, filter or resample not in {2, 3}, zero std, an image outside the packed
- * buffer, a box outside its image, num_layers outside [0, 4], an unknown op id, a reduction factor beyond gg_preprocess_pil's limit, a workspace smaller than
+ * buffer, a box outside its image, num_layers outside [0, 4], an unknown op id, a reduction factor beyond the resampler's limit (2^20 filter taps), a workspace smaller than
  * gg_aug_workspace_bytes(args). */
 int gg_aug_batch(const GgAugArgs* args, void* stream);
 

@@ -1,5 +1,5 @@
-/* libgg -- the eval transform of the raw-image path for whole batches: what gg_preprocess_pil (include/gg.h) does to one image -- Pillow's resize of
- * the whole image, the crop window, 1/255, (x - mean) / std -- for a packed batch of uint8 images of any sizes per call.  It serves everything that consumes raw
+/* libgg -- the eval transform of the raw-image path for whole batches: Pillow's resize of the whole image, the crop window, 1/255, (x - mean) / std
+ * for a packed batch of uint8 images of any sizes per call (gg_preprocess_pil of include/gg.h is this call with B = 1).  It serves everything that consumes raw
  * images outside the training step: timm's eval transform in front of TinyViT, CLIPImageProcessor in front of the CLIP tower, inference.py's Compose, the
  * classifier fine-tune's collate_val.  Which resized size and crop origin an image gets is the CALLER's decision (training/preprocess.py::raw_image_geometry
  * restates the three upstream pipelines); a call takes one GgEvalGeom per image.
@@ -61,8 +61,8 @@ int64_t gg_eval_workspace_bytes(const GgEvalArgs* args);
 /* The whole batch: the table as kernel arguments (a few images per launch), the coefficients of all 2B axes in one launch, the horizontal pass (source spans staged
  * in LDS with dword loads), the vertical pass fused with 1/255, normalise, the CHW f32 store and the optional u8 store.  One image per blockIdx.y.
  * Refused before any launch, with nothing written: NULL pointers, B / Hc / Wc out of range, a filter not in {2, 3}, zero std with `normalize`, an image outside the
- * packed buffer, a crop window outside Hr x Wr (the upstream transforms pad there: not built, as in gg_preprocess_pil), Hr / Wr out of range, a reduction factor
- * beyond gg_preprocess_pil's limit, a workspace smaller than gg_eval_workspace_bytes(args). */
+ * packed buffer, a crop window outside Hr x Wr (the upstream transforms pad there: not built), Hr / Wr out of range, a reduction factor whose filter window
+ * would pass 2^20 taps (eval_ksize of csrc/eval_passes.h), a workspace smaller than gg_eval_workspace_bytes(args). */
 int gg_eval_batch(const GgEvalArgs* args, void* stream);
 
 #ifdef __cplusplus

@@ -66,7 +66,7 @@ int64_t gg_pano_workspace_bytes(const GgPanoArgs* args);
  * consecutive x of one row for the three channels, missing slots are filled by the same kernel.  Per-image sizes may differ inside a batch.
  * Refused before any launch, with nothing written: NULL pointers, num_slots / num_images out of range, a slot index outside [-1, num_images), Ht / Wt out of range,
  * resize < 0, zero std with `normalize`, an image outside the packed buffer, a resized image outside dst_u8, a resized side above GG_EVAL_MAX_RESIZED, a reduction
- * factor beyond gg_preprocess_pil's limit, a workspace smaller than gg_pano_workspace_bytes(args). */
+ * factor beyond the resampler's limit (2^20 filter taps), a workspace smaller than gg_pano_workspace_bytes(args). */
 int gg_pano_batch(const GgPanoArgs* args, void* stream);
 
 #ifdef __cplusplus

@@ -1,7 +1,8 @@
 """CPU-only checks of the batched eval transform (include/gg_eval.h, geoguessr_ai_amd.training.preprocess.DeviceEvalTransform): the fixture made by Pillow
 (tests/golden/eval_batch_pil.npz, tests/golden/make_golden_eval_batch.py) against the numpy restatement of oracle/preprocess_ref.py, the header as C, the struct
-layouts against the ctypes binding, the exported symbols, and what gg_eval_workspace_bytes answers on the host.  Nothing here needs a GPU; everything here fails
-without the header, the symbols and the classes."""
+layouts against the ctypes binding, the exported symbols, what gg_eval_workspace_bytes answers on the host, and the per-image entry point (gg_preprocess_pil, the
+B = 1 call of the same passes): its workspace bound and its host refusals.  Nothing here needs a GPU; everything here fails without the header, the symbols and the
+classes."""
 import ctypes as C
 import os
 import re
@@ -156,6 +157,53 @@ def test_bad_batches_are_refused_on_the_host_before_anything_touches_a_device(L,
                     (dict(src=p, dst=p, workspace=p, workspace_bytes=need, geom=None), b"null geom")):
         b = _Batch(L, g, SIZE32[:3], 32, **kw)
         assert lib.gg_eval_batch(C.byref(b.args), None) < 0 and msg in lib.gg_last_error(), (msg, lib.gg_last_error())
+    assert bytes(buf) == b"\0" * 64
+
+
+def test_per_image_workspace_query_bounds_every_crop_window(L, fixture):
+    """gg_preprocess_pil_workspace_bytes(Hs, Ws, flt, Hr, Wr, Wc) has no Hc and no top: on the 14 fixture geometries and both filters it is at least
+    gg_eval_workspace_bytes of that image alone for every crop window Hc in {1, Hr // 2, Hr}, top in {0, Hr - Hc}, left = 0.  It answers -1 for what the shared plan
+    refuses and goes on answering for an Hr above the crop limit of 2048."""
+    lib, g = L.lib(), fixture
+    checked = 0
+    for i in range(14):
+        Hs, Ws = g[f"src{i}"].shape[:2]
+        Hr, Wr = (int(v) for v in g["geom"][i][:2])
+        Wc = int(g["size"][i])
+        for flt in (2, 3):
+            bound = lib.gg_preprocess_pil_workspace_bytes(Hs, Ws, flt, Hr, Wr, Wc)
+            assert bound > 0, (i, flt, lib.gg_last_error())
+            for Hc in sorted({1, max(Hr // 2, 1), Hr}):
+                for top in sorted({0, Hr - Hc}):
+                    b = _Batch(L, g, [i], Wc, Hc=Hc, filter=flt)
+                    b.geom[0] = (Hr, Wr, top, 0)
+                    one = lib.gg_eval_workspace_bytes(C.byref(b.args))
+                    assert 0 < one <= bound, (i, flt, Hc, top, one, bound, lib.gg_last_error())
+                    checked += 1
+    assert checked >= 14 * 2 * 4
+    q = lib.gg_preprocess_pil_workspace_bytes
+    assert q(50, 60, 1, 28, 34, 24) == -1 and q(50, 60, 4, 28, 34, 24) == -1
+    for bad in ((0, 60, 3, 28, 34, 24), (50, -1, 3, 28, 34, 24), (50, 60, 3, 0, 34, 24), (50, 60, 3, 28, 0, 24), (50, 60, 3, 28, 34, 0)):
+        assert q(*bad) == -1, bad
+    assert q(1, 30000000, 3, 1, 16, 16) == -1                     # 30 000 000 columns -> 16: the shared ksize rule
+    assert q(8, 8, 3, 3000, 8, 8) > 0                             # Hr above GG_EVAL_MAX_CROP: the call accepts it with Hc <= 2048, so the query answers
+
+
+def test_per_image_call_refuses_on_the_host_before_anything_touches_a_device(L):
+    """gg_preprocess_pil names what only it can (null pointers, mean without std) and leaves the rest to the shared plan, whose messages come back; all of it on the
+    host: a buffer standing in for the device pointers is untouched."""
+    lib = L.lib()
+    buf = (C.c_char * 64)()
+    p = C.addressof(buf)
+    m3 = (C.c_float * 3)(*MEAN)
+    s3 = (C.c_float * 3)(*STD)
+
+    def call(src=p, filter=3, resized=(28, 34), crop=(2, 5, 24, 24), mean=m3, std=s3, dst=p, ws=p):
+        return lib.gg_preprocess_pil(src, 50, 60, filter, resized[0], resized[1], crop[0], crop[1], crop[2], crop[3], 0, mean, std, dst, None, ws, None)
+    for kw, msg in ((dict(src=None), b"null src / dst / workspace"), (dict(dst=None), b"null src / dst / workspace"), (dict(ws=None), b"null src / dst / workspace"),
+                    (dict(std=None), b"mean and std come together"), (dict(filter=4), b"filter must be 2"),
+                    (dict(resized=(24, 30), crop=(2, 0, 24, 24)), b"must lie inside the resized image")):
+        assert call(**kw) < 0 and msg in lib.gg_last_error(), (msg, lib.gg_last_error())
     assert bytes(buf) == b"\0" * 64
 
 

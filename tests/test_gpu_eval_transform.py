@@ -1,6 +1,7 @@
 """The batched eval transform (include/gg_eval.h, csrc/eval_transform.hip, training/preprocess.py::DeviceEvalTransform) on the GPU: the uint8 crops BYTE-IDENTICAL to
 Pillow's own outputs (tests/golden/eval_batch_pil.npz, tests/golden/preprocess_pil.npz) and to the numpy restatement (oracle/preprocess_ref.py) for arbitrary
-geometry, pixel_values within 1e-6 (the gate of test_preprocess_pil_matches_pillow_and_transformers_golden), the per-image path next to it, independence of the
+geometry, pixel_values within 1e-6 (the gate of test_preprocess_pil_matches_pillow_and_transformers_golden), the per-image path next to it (the B = 1 call of the
+same passes: its bits against digests recorded before it was folded in, tests/golden/preprocess_pil_parent.json), independence of the
 batch / the record chunking / the workspace's earlier contents, the row range of the horizontal pass, the refusals, and the consumers.  Every image is at most ~300
 pixels a side (two strips are wider, 8 and 9 rows high: the horizontal pass changes its path where a row's span outgrows the LDS)."""
 import ctypes as C
@@ -170,6 +171,28 @@ def test_batched_keyword_matches_the_per_image_path(L, fx):
     assert one.shape == (1, 3, 32, 32) and torch.equal(one, pv[:1])
     with pytest.raises(L.GgError, match="a 40x40 image resizes to 25x25, smaller than the 32x32 crop"):          # crop_pct > 1: the upstream transform pads
         images_to_pixel_values(np.zeros((40, 40, 3), np.uint8), 32, TV_MEAN, TV_STD, "cuda", crop_pct=1.25, batched=True)
+
+
+def test_per_image_bits_unchanged_from_the_parent_build(L):
+    """gg_preprocess_pil became the B = 1 call of the batch passes.  tests/golden/preprocess_pil_parent.json holds SHA-256 digests of dst_u8 and of dst's bytes that
+    tools/make_preprocess_pil_parent_golden.py recorded on an MI355X with the build BEFORE that change (its own kernels), for seeded images at the smallest shapes where
+    the fold can go wrong: the six guard-band geometries, 17 x 9 -> 33 x 20 with both filters, a horizontal-only and a vertical-only resize, and a 5 x 24 000 strip
+    whose row span is beyond the LDS (the unstaged branch of the horizontal pass).  Every uint8 digest and every f32 digest must come out the same."""
+    import json
+    from geoguessr_ai_amd import ops
+    rec = json.load(open(os.path.join(ROOT, "tests", "golden", "preprocess_pil_parent.json")))
+    assert len(rec["cases"]) == 11 and tuple(rec["mean"]) == TV_MEAN and tuple(rec["std"]) == TV_STD
+    assert any(3 * c["Ws"] > 32768 and c["Wr"] != c["Ws"] for c in rec["cases"])          # the strip beyond the LDS is among them
+    bad = []
+    for c in rec["cases"]:
+        img = torch.from_numpy(np.random.default_rng(c["seed"]).integers(0, 256, (c["Hs"], c["Ws"], 3), dtype=np.uint8)).cuda()
+        stats = (TV_MEAN, TV_STD) if c["normalize"] else (None, None)
+        pv, crop = ops.preprocess_pil(img, c["filter"], (c["Hr"], c["Wr"]), (c["top"], c["left"]), (c["Hc"], c["Wc"]), *stats, mul_rescale=bool(c["mul_rescale"]),
+                                      want_u8=True)
+        u8, f32 = hashlib.sha256(crop.cpu().numpy().tobytes()).hexdigest(), hashlib.sha256(pv.cpu().numpy().tobytes()).hexdigest()
+        print(f"\n[parent bits] {c['name']}: u8 {'same' if u8 == c['u8_sha256'] else 'DIFFERS'}, f32 {'same' if f32 == c['f32_sha256'] else 'DIFFERS'}", end="")
+        bad += [(c["name"], kind) for kind, got in (("u8", u8), ("f32", f32)) if got != c[kind + "_sha256"]]
+    assert not bad, bad
 
 
 # ------------------------------------------------------------------------------------------------- 4. batch independence and chunking
