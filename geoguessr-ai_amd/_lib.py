@@ -439,6 +439,14 @@ ATTN16W_SIGNATURES = {
 }
 ATTN16W_SYMBOLS = list(ATTN16W_SIGNATURES)
 
+# every exported symbol of include/gg_attn16b.h (the long-sequence attention backward on the 16-bit MFMA and the bf16 CLIP tower's opt-in switch that sends its training step to the 16-bit-MFMA pair)
+ATTN16B_SIGNATURES = {
+    "gg_attention_flash16_bwd": (_I, [C.POINTER(AttnArgs), _I, _P]),
+    "gg_attention_flash16_bwd_calls": (_L, []),
+    "gg_clip_set_attention16_train": (_I, [_I]),
+}
+ATTN16B_SYMBOLS = list(ATTN16B_SIGNATURES)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -447,7 +455,7 @@ def lib() -> C.CDLL:
             raise GgError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JSCAN_SIGNATURES.items()) + list(PANO_SIGNATURES.items()) + list(ATTN16_SIGNATURES.items()) + list(ATTN16W_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JSCAN_SIGNATURES.items()) + list(PANO_SIGNATURES.items()) + list(ATTN16_SIGNATURES.items()) + list(ATTN16W_SIGNATURES.items()) + list(ATTN16B_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the library lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -506,6 +514,7 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(root), "include", "gg_pano.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_attn16.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_attn16w.h"))
+    files.append(os.path.join(os.path.dirname(root), "include", "gg_attn16b.h"))
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

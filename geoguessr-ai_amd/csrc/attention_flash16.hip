@@ -33,17 +33,13 @@
 // two calls give the same bits.
 // The template does not preclude what is out of scope today (other head dims, fp16 windows, causal rows).
 #include "common.h"
+#include "attention16.h"
 #include "../../include/gg.h"
 #include "../../include/gg_attn16.h"
 #include "../../include/gg_attn16w.h"
 #include <atomic>
 
 namespace {
-
-typedef short a16_s4 __attribute__((ext_vector_type(4)));
-typedef unsigned int a16_u4 __attribute__((ext_vector_type(4)));
-typedef unsigned int a16_u2 __attribute__((ext_vector_type(2)));
-typedef int a16_i4 __attribute__((ext_vector_type(4)));
 
 struct A16Params {
     const void* qkv; int64_t ld;
@@ -59,35 +55,6 @@ struct A16Params {
     const float* bias_table;  // BIAS: [nh][ws * ws] f32
 };
 
-template <typename T> struct A16Op;
-template <> struct A16Op<f16> {
-    typedef f16x8 v8; typedef f16x4 v4;
-    static __device__ __forceinline__ f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
-template <> struct A16Op<bf16> {
-    typedef bf16x8 v8; typedef bf16x4 v4;
-    static __device__ __forceinline__ f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-
-// 8 consecutive 16-bit elements.  Rows are 8-byte aligned by contract, so the source states two 8-byte loads; on gfx950 they compile to one 16-byte load
-__device__ __forceinline__ a16_u4 a16_ld8(const void* p) {
-    const a16_u2 a = reinterpret_cast<const a16_u2*>(p)[0], b = reinterpret_cast<const a16_u2*>(p)[1];
-    return (a16_u4){a[0], a[1], b[0], b[1]};
-}
-
-// The K / V images of one head dim: 64 rows of 2 D bytes, and where 16-byte chunk ch of row `row` is stored (the header comment derives the swizzles)
-template <int D> struct A16Lds {
-    static constexpr int ROW = 2 * D, TILE = 64 * ROW;          // bytes of a row; of one K or V image
-    static constexpr int CPR = D / 8, NST = D / 32;             // 16-byte chunks per row; staged chunks of each image per thread (256 threads, 64 rows)
-    static __device__ __forceinline__ constexpr int kswz(int row) {            // K chunk swizzle
-        if (D == 64) return (row >> 1) & 7;
-        const int g = (row >> 2) & 3;
-        return g ^ ((g & 1) << 1);
-    }
-    static __device__ __forceinline__ constexpr int vswz(int row) { return D == 64 ? (row >> 1) & 3 : (row >> 2) & 1; }          // V 32-byte block swizzle
-    static __device__ __forceinline__ constexpr int koff(int row, int ch) { return row * ROW + ((ch ^ kswz(row)) << 4); }
-    static __device__ __forceinline__ constexpr int voff(int row, int ch) { return row * ROW + (((ch >> 1) ^ vswz(row)) << 5) + ((ch & 1) << 4); }
-};
 constexpr int A16_EMAX = 63 * 63;            // floats of the expanded bias table at ws = 32
 __device__ __forceinline__ int a16_div(int t, uint32_t rcp) { return (int)(((uint32_t)t * rcp) >> 20); }
 

@@ -35,6 +35,7 @@
 #include "../../include/gg_clip_text_train.h"
 #include "../../include/gg_fp8.h"
 #include "../../include/gg_attn16.h"
+#include "../../include/gg_attn16b.h"
 #include <atomic>
 
 namespace {
@@ -395,6 +396,7 @@ static void plan(const CModel& m, int B, const Train& tr, bool training, CPlan& 
 struct Exec {
     const CModel* m; const CPlan* L; int B; hipStream_t st;
     const float* params; const char* wc; char* ws; float* grads; const uint8_t* mask;
+    bool attn16t = false;     // a training step (gg_clip_forward with training != 0, gg_clip_backward), switch on (gg_clip_set_attention16_train), a bf16 vision tower beyond 256 tokens: attention through gg_attention_flash16_fwd / _bwd (include/gg_attn16b.h)
     bool attn16 = false;      // gg_clip_forward, inference, switch on (gg_clip_set_attention16), a 16-bit vision tower beyond 256 tokens: attention through gg_attention_flash16_fwd
     const float* P(int t) const { return params + m->t[t].offset; }
     float* Gd(int t) const { return grads + m->t[t].offset; }
@@ -521,6 +523,7 @@ static int layer_fwd(const Exec& e, int i, int64_t cur, int64_t next, bool sv) {
     e.attn_args(at, e.A(QKV), e.A(O), sv ? e.F(a.lse) : nullptr);
     if (m.causal) GG_TRY(gg_attention_causal_fwd(&at, m.split ? 3 : m.f32 ? 1 : 0, e.st));      // the text tower
     else if (m.split) GG_TRY(gg_attention_flash_fwd(&at, 3, e.st));      // split products at every token count
+    else if (e.attn16t) GG_TRY(gg_attention_flash16_fwd(&at, 0, e.st));      // opt-in, the training step: kept layers (with lse) and the layers below them alike
     else if (e.attn16 && !sv) GG_TRY(gg_attention_flash16_fwd(&at, m.f16 ? 2 : 0, e.st));      // opt-in: both products on the 16-bit MFMA (include/gg_attn16.h)
     else if (m.f16) GG_TRY(gg_attention_fwd_f16(&at, e.st));      // fp16 MFMA for towers of at most 256 tokens (ViT-B/32: 50); beyond: fp16 storage, f32 arithmetic
     else if (m.f32 || sv || T > 256) GG_TRY(gg_attention_flash_fwd(&at, m.f32 ? 1 : 0, e.st));
@@ -570,6 +573,7 @@ static int layers_bwd(const Exec& e, int l0, bool top_in_region, int64_t& dx, in
         at.dout = e.A(L.g_o); at.lddo = D; at.dqkv = e.A(L.g_qkv);
         if (L.attn_ds >= 0) at.ds_scratch = e.F(L.attn_ds);
         if (m.causal) GG_TRY(gg_attention_causal_bwd(&at, m.split ? 3 : m.f32 ? 1 : 0, e.st));      // the text tower
+        else if (e.attn16t) GG_TRY(gg_attention_flash16_bwd(&at, 0, e.st));      // opt-in: all five products on the 16-bit MFMA; the dS region is not read
         else GG_TRY(gg_attention_flash_bwd(&at, m.split ? 3 : m.f32 ? 1 : 0, e.st));
         const char* dq = (const char*)e.A(L.g_qkv);
         GG_TRY(e.wgrad(l.q_w, dq, 3 * D, e.A(a.a1), D, M, D, D));
@@ -729,6 +733,12 @@ static int refresh_model(const CModel& m, const float* params, void* wcache, con
 // the opt-in long-row attention of the inference forward (include/gg_attn16.h); process-wide like tinyvit.hip's g_drop_compact
 static std::atomic<int> g_attention16{0};
 extern "C" int gg_clip_set_attention16(int on) { return g_attention16.exchange(on != 0 ? 1 : 0); }
+// the same for the training step (include/gg_attn16b.h): a switch of its own, read when gg_clip_forward(training) or gg_clip_backward is enqueued
+static std::atomic<int> g_attention16_train{0};
+extern "C" int gg_clip_set_attention16_train(int on) { return g_attention16_train.exchange(on != 0 ? 1 : 0); }
+static bool attention16_train_route(const CModel& m) {
+    return g_attention16_train.load() != 0 && !m.causal && !m.f32 && !m.f16 && !m.fp8 && m.T > 256;      // bf16 (act_dtype 0) vision towers beyond 256 tokens
+}
 
 extern "C" int gg_clip_forward(const GgClipCfg* cfg, int batch, int training, const float* params, const void* wcache, const float* x, void* workspace,
                                float* out, float* last_hidden, const uint8_t* trainable, void* stream) {
@@ -741,6 +751,7 @@ extern "C" int gg_clip_forward(const GgClipCfg* cfg, int batch, int training, co
     GG_CHECK(!(m.f16 && training && tr.l0 < m.cfg.num_layers), "gg_clip_forward: the fp16 mode is inference-only (train in fp32 or bf16)");
     CPlan L; plan(m, batch, tr, training != 0, L);
     Exec e{&m, &L, batch, (hipStream_t)stream, params, (const char*)wcache, (char*)workspace, nullptr, trainable};
+    e.attn16t = training != 0 && attention16_train_route(m);
     e.attn16 = !training && g_attention16.load() != 0 && !m.causal && !m.f32 && m.T > 256;      // (m.f32 covers fp32 and fp32_split; fp8 is an fp16 mode)
     const int D = m.cfg.hidden_size, T = m.T, B = batch, nl = m.cfg.num_layers;
     const int64_t M = (int64_t)B * T;
@@ -791,6 +802,7 @@ extern "C" int gg_clip_backward(const GgClipCfg* cfg, int batch, const float* pa
     const bool top_in_region = seen >= 0 && (seen & WS_TOP) != 0;
     if (L.rc && tr.l0 < nl - 1) ws_clear_top(workspace);
     Exec e{&m, &L, batch, (hipStream_t)stream, params, (const char*)wcache, (char*)workspace, grads, trainable};
+    e.attn16t = attention16_train_route(m);       // the recompute replay and the attention backward
     const int D = m.cfg.hidden_size, I = m.cfg.intermediate_size, T = m.T, B = batch;
     const int64_t M = (int64_t)B * T, Mp = (int64_t)B * m.G * m.G;
     if (m.f32) hipLaunchKernelGGL(pool_bwd_kernel<float>, dim3(grid1d(M * D)), dim3(256), 0, e.st, d_out, d_last_hidden, (float*)e.A(L.g_x0), B, T, D);

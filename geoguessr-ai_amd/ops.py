@@ -593,6 +593,28 @@ def attention_flash16(qkv, *, num_windows, tokens_per_window, num_heads, q_off, 
     return (out, lse_t) if want_lse else out
 
 
+def attention_flash16_bwd(qkv, out, lse, dout, *, num_windows, tokens_per_window, num_heads, q_off, k_off, v_off, head_stride, scale=None, dqkv=None):
+    """Attention backward with all five products on the 16-bit MFMA (include/gg_attn16b.h): bf16 storage, head dim 64, linear tokens, any ``tokens_per_window``,
+    no bias.  ``out`` / ``lse``: the forward's (``attention_flash16`` or ``attention_flash`` on bf16).  Returns dqkv of qkv's shape: the dq, dk and dv columns of
+    every token are written, every other column keeps the zero fill.  ``dqkv`` (optional): a buffer of qkv's shape and row stride to write into instead."""
+    L.require_gpu()
+    if qkv.dtype != BF16:
+        raise L.GgError(f"attention_flash16_bwd: bf16 storage (got {qkv.dtype})")
+    a = L.AttnArgs()
+    a.qkv, a.ld = _pr(qkv, BF16, "qkv"), qkv.stride(0)      # rows may be strided: a column slice of a wider buffer
+    a.q_off, a.k_off, a.v_off, a.head_stride, a.head_dim = q_off, k_off, v_off, head_stride, 64
+    a.num_heads, a.num_windows, a.tokens_per_window, a.window_size = num_heads, num_windows, tokens_per_window, 0
+    a.scale = 0.125 if scale is None else scale
+    if dqkv is None:
+        dqkv = torch.zeros(qkv.shape[0], qkv.stride(0), dtype=BF16, device=qkv.device)[:, :qkv.shape[1]]
+    elif dqkv.shape != qkv.shape or dqkv.stride(0) != qkv.stride(0):
+        raise L.GgError("attention_flash16_bwd: dqkv must have qkv's shape and row stride")
+    a.out, a.ldo, a.lse = _pr(out, BF16, "out"), out.stride(0), _p(lse, F32, "lse")
+    a.dout, a.lddo, a.dqkv = _pr(dout, BF16, "dout"), dout.stride(0), _pr(dqkv, BF16, "dqkv")
+    L.check(L.lib().gg_attention_flash16_bwd(C.byref(a), 0, L.stream()), "gg_attention_flash16_bwd")
+    return dqkv
+
+
 def attention_flash16_win(qkv, *, num_windows, tokens_per_window, num_heads, q_off, k_off, v_off, head_stride, window_size, map_h, map_w, head_dim=32,
                           bias_table=None, scale=None, want_lse=False, out=None):
     """Window attention forward beyond 256 tokens with both products on the 16-bit MFMA (include/gg_attn16w.h): bf16 storage, head dim 32, tokens gathered from

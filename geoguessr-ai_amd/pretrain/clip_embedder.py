@@ -15,7 +15,9 @@ f32-accurate split-bf16 products: ``GgClipCfg.act_dtype`` 3), ``"bf
 config c4 names), or ``"fp8"`` (inference only: fp16's storage and schedule with the four Linears of every encoder layer as W8A8 e4m3 products,
 ``GgClipCfg.act_dtype`` 8, include/gg_fp8.h; resolved by ``tower_precision_code``); the default is ``$GG_PRECISION``.  ``attention16=True`` (bf16, fp16 and fp8; opt-in,
 not in the reference): the inference forward of a tower beyond 256 tokens (ViT-L/14-336: 577) runs its attention with both products on the 16-bit MFMA
-(``gg_attention_flash16_fwd``, include/gg_attn16.h) instead of the f32-MFMA online-softmax kernel; training forwards are unaffected.  No hub download: weights come from a
+(``gg_attention_flash16_fwd``, include/gg_attn16.h) instead of the f32-MFMA online-softmax kernel; training forwards are unaffected.  ``attention16_train=True`` (bf16 only; opt-in, not in the reference, independent of
+``attention16``): the TRAINING step of such a tower -- the training forward, the recompute replay and the attention backward -- runs on the 16-bit MFMA
+(``gg_attention_flash16_fwd`` / ``gg_attention_flash16_bwd``, include/gg_attn16b.h).  No hub download: weights come from a
 state dict (HF names, with or without the leading ``vision_model.``)."""
 from __future__ import annotations
 
@@ -69,6 +71,17 @@ def check_attention16(attention16: bool, code: int, who: str) -> None:
                         "(leave attention16 off)")
 
 
+def check_attention16_train(attention16_train: bool, code: int, who: str) -> None:
+    """``attention16_train=True`` is a switch of the bf16 training step: refused by name for ``fp32`` and ``fp32_split`` (their attention is f32-accurate by
+    contract) and for ``fp16`` and ``fp8`` (inference-only modes: they have no training step)."""
+    if attention16_train and code in (1, 3):
+        raise L.GgError(f"{who}: attention16_train=True is a switch of the bf16 mode; precision='{PRECISION_NAMES[code]}' keeps its f32-accurate attention "
+                        "(leave attention16_train off)")
+    if attention16_train and code != 0:
+        raise L.GgError(f"{who}: attention16_train=True is a switch of the bf16 mode; precision='{PRECISION_NAMES[code]}' is inference-only (attention16 is the "
+                        "switch of its forward)")
+
+
 class _VisionModel(EncoderRuntime):
     """``vision_model`` of the HF module tree: owner of the flat storage and of the HIP workspace.  Its children (``embeddings``, ``pre_layrnorm``,
     ``encoder.layers.N....``, ``post_layernorm``) are rebuilt from the tensor names, so ``encoder.layers[i].parameters()`` is what
@@ -77,6 +90,7 @@ class _VisionModel(EncoderRuntime):
     _mask_changed = "requires_grad changed between the CLIP forward and its backward; run the forward again"
     _toggled_gen = None               # generation of a training forward that a gradient_checkpointing toggle made the runtime forget
     attention16 = False               # CLIPVisionTower(attention16=True): this tower's forwards run with gg_clip_set_attention16(1)
+    attention16_train = False         # CLIPVisionTower(attention16_train=True): its training forwards and backwards run with gg_clip_set_attention16_train(1)
 
     def __init__(self, cfg: L.ClipCfg, seed: int):
         super().__init__()
@@ -143,12 +157,15 @@ class _VisionModel(EncoderRuntime):
         last = torch.empty((B, T, D), dtype=torch.float32, device=x.device) if return_last_hidden else None
         lib = L.lib()
         prev = lib.gg_clip_set_attention16(1) if self.attention16 else None      # process-wide switch, read when the forward is enqueued: set for this call only
+        prev_t = lib.gg_clip_set_attention16_train(1) if self.attention16_train and training else None      # the same, the training step's switch
         try:
             rc = lib.gg_clip_forward(C.byref(self.cfg), B, int(training), L.ptr(self._flat), L.ptr(self._wcache), L.ptr(x), L.ptr(ws), L.ptr(out),
                                      L.ptr(last), mask, L.stream())
         finally:
             if prev is not None:
                 lib.gg_clip_set_attention16(prev)
+            if prev_t is not None:
+                lib.gg_clip_set_attention16_train(prev_t)
         L.check(rc, "gg_clip_forward")
         if training:
             self._record_forward(B, mask)
@@ -160,8 +177,15 @@ class _VisionModel(EncoderRuntime):
         fg = self.attach_grads()
         f = lambda t: None if t is None else t.to(torch.float32).contiguous()
         d_out, d_last = f(d_out), f(d_last)
-        L.check(L.lib().gg_clip_backward(C.byref(self.cfg), B, L.ptr(self._flat), L.ptr(self._wcache), L.ptr(ws), L.ptr(d_out), L.ptr(d_last),
-                                         L.ptr(fg), mask, L.stream()), "gg_clip_backward")
+        lib = L.lib()
+        prev_t = lib.gg_clip_set_attention16_train(1) if self.attention16_train else None      # read when the backward is enqueued (its recompute replay included)
+        try:
+            rc = lib.gg_clip_backward(C.byref(self.cfg), B, L.ptr(self._flat), L.ptr(self._wcache), L.ptr(ws), L.ptr(d_out), L.ptr(d_last), L.ptr(fg), mask,
+                                      L.stream())
+        finally:
+            if prev_t is not None:
+                lib.gg_clip_set_attention16_train(prev_t)
+        L.check(rc, "gg_clip_backward")
         if self._grad_ready_hook is not None:          # (no stage callback in the CLIP backward: the buckets leave after it)
             self._grad_ready_hook(0, self.param_floats)
 
@@ -170,11 +194,15 @@ class CLIPVisionTower(nn.Module):
     supports_gradient_checkpointing = True          # (transformers PreTrainedModel's class attribute)
 
     def __init__(self, model_name: str = "openai/clip-vit-base-patch32", seed: int = 0, precision: Optional[str] = None,
-                 gradient_checkpointing: bool = False, attention16: bool = False, **cfg_overrides):
+                 gradient_checkpointing: bool = False, attention16: bool = False, attention16_train: bool = False, **cfg_overrides):
+        """``attention16_train=True`` (bf16 only; opt-in, independent of ``attention16``): this tower's training steps run with
+        ``gg_clip_set_attention16_train(1)`` -- with more than 256 tokens the training forward, the recompute replay and the attention backward go through
+        ``gg_attention_flash16_fwd`` / ``gg_attention_flash16_bwd`` (include/gg_attn16b.h); inference forwards are unaffected."""
         super().__init__()
         kw = dict(CLIP_CONFIGS.get(model_name, CLIP_CONFIGS["openai/clip-vit-base-patch32"]))
         kw.update(cfg_overrides)
         check_attention16(attention16, tower_precision_code(precision), "CLIPVisionTower")
+        check_attention16_train(attention16_train, tower_precision_code(precision), "CLIPVisionTower")
         c = L.ClipCfg()
         c.hidden_size, c.intermediate_size, c.num_layers, c.num_heads = kw["hidden_size"], kw["intermediate_size"], kw["num_layers"], kw["num_heads"]
         c.image_size, c.patch_size, c.ln_eps = kw["image_size"], kw["patch_size"], 1e-5
@@ -185,6 +213,7 @@ class CLIPVisionTower(nn.Module):
         self.config = SimpleNamespace(hidden_size=kw["hidden_size"], _name_or_path=model_name, **{k: v for k, v in kw.items() if k != "hidden_size"})
         self.vision_model = _VisionModel(c, seed)
         self.attention16 = self.vision_model.attention16 = bool(attention16)
+        self.attention16_train = self.vision_model.attention16_train = bool(attention16_train)
         self.num_tokens = (c.image_size // c.patch_size) ** 2 + 1
 
     # ---- activation recompute -----------------------------------------------------------------------------------------------------------
