@@ -145,6 +145,7 @@ SIGNATURES = {
     "gg_last_error": (C.c_char_p, []),
     "gg_gemm_nt": (_I, [C.POINTER(GemmArgs), _P]),
     "gg_gemm_colstats_rows": (_I, [_I]),
+    "gg_gemm_nt_route": (_I, [C.POINTER(GemmArgs), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "gg_stat_rows_capacity": (_I, [_I]),
     "gg_gemm_tn_splits": (_I, [_I, _I, _I]),
     "gg_gemm_tn": (_I, [_P, _L, _P, _L, _I, _I, _I, _P, _I, _P, _I, _P]),

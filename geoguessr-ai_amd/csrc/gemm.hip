@@ -658,7 +658,7 @@ __global__ __launch_bounds__(128 * NWN, 2) void gemm_nt_dma_kernel(GemmParams p)
     for (int j = 0; j < PB; ++j) voffB[j] = (unsigned)((wave + NW * j) * 8 + (lane >> 3)) * (unsigned)p.ldb * 2u + dchunk * 16u;
     auto issue_stage = [&](const __amdgpu_buffer_rsrc_t& rsA, const __amdgpu_buffer_rsrc_t& rsB, int st, ge_t* base) {
         const int k0 = st * SK;
-        const bool kin = k0 + dchunk * 8 < p.K;                  // K % 8 == 0: a chunk is entirely inside or outside K
+        const bool kin = k0 + dchunk * 8 < p.K;                  // K % 8 == 0: a chunk is entirely inside or outside K; outside, the DMA writes zeros to LDS (held bit for bit, with NaN behind K, by tests/test_gpu_gemm16_forms.py)
 #pragma unroll
         for (int j = 0; j < PA; ++j)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void*)(base + (wave + NW * j) * 512), 16,
@@ -1049,7 +1049,8 @@ __global__ void colsum_final_kernel(const float* __restrict__ part, int nparts, 
 #ifndef GG_GEMM_NT_NAME
 #define GG_GEMM_NT_NAME gg_gemm_nt
 #endif
-extern "C" int GG_GEMM_NT_NAME(const GgGemmArgs* a, void* stream) {
+// The argument contract of the NT entry points (everything the launch refuses), shared with the route report.
+static int gemm_nt_check(const GgGemmArgs* a) {
     GG_CHECK(a && a->A && a->B && a->C, "gg_gemm_nt: null operand");
 #ifdef GG_GEMM_SECOND_TYPE
     GG_CHECK(!a->a_bn_stat && !a->A2 && !a->bn_y && !a->colstats && a->split_k <= 1, "gg_gemm_nt_f16: the BatchNorm-fused / two-source / split-K forms exist in the ge_t build only");
@@ -1094,8 +1095,61 @@ extern "C" int GG_GEMM_NT_NAME(const GgGemmArgs* a, void* stream) {
         GG_CHECK(a->a_bn_act == GG_ACT_NONE || a->a_bn_act == GG_ACT_GELU,
                  "gg_gemm_nt: the BatchNorm prologue applies GG_ACT_CODE_NONE or GG_ACT_CODE_GELU only (a_bn_act = %d; gg_gemm_nt_f32 has the QuickGELU form)", a->a_bn_act);
     }
+    return 0;
+}
+// Which kernel a launch takes, its tile grid and its tile walk: the ONE place that decides it.  The entry point launches what this returns and
+// gg_gemm_nt_route reports it, dev switches included, so a test that asks for the route of its arguments cannot be told about another kernel than the one it runs.
+struct GemmRoute {
+    int epi;                      // epilogue class
+    int kernel;                   // GG_GEMM_ROUTE_*
+    int tilesM, tilesN, group_m;  // grid = tilesM x tilesN tiles; group_m: the LDS-DMA form's tile walk (0: row-major)
+};
+static GemmRoute gemm_nt_route(const GgGemmArgs* a) {
+    GemmRoute r;
+    const int split = a->split_k > 1 ? a->split_k : 1;
+    if (a->out_f32 || split > 1) r.epi = EPI_F32;
+    else if (a->bn_y) r.epi = EPI_BNBWD;
+    else if (a->dact_preact && a->dact) r.epi = EPI_DGELU;
+    else if (a->act == GG_ACT_GELU || (a->act == GG_ACT_QUICK_GELU && a->preact)) r.epi = EPI_GELU;      // (row-phase epilogue: pre-activation copy)
+    else if (a->act == GG_ACT_QUICK_GELU) r.epi = EPI_QGELU;
+    else if (a->bias || a->rowscale || a->residual) r.epi = EPI_LINEAR;
+    else r.epi = EPI_PLAIN;
+    // tile choice: HBM-bound shapes (short K loop or a single narrow N tile) take the light 128x64 tile
+    static const char* force = gg_dev_env("GG_GEMM_TILE");
+    const int rem = a->N % 128;
+    bool narrow = a->N <= 64 || (rem != 0 && rem <= 64);     // a 128-wide tile would be at most half full
+    if (force) narrow = force[0] == 'n';
+    r.kernel = narrow ? GG_GEMM_ROUTE_128x64 : GG_GEMM_ROUTE_128x128;
+    r.tilesM = (int)gg_cdiv(a->M, 128); r.tilesN = (int)gg_cdiv(a->N, narrow ? 64 : 128);
+    r.group_m = 0;
+    // the MFMA-bound shapes (the transformer Linears and their data gradients) take the LDS-DMA form: 192 x 128 or 256 x 256 tiles
+    // (its epilogue has no general-shape fallbacks: whole 16-byte column chunks, 16-byte aligned rows of every tensor it touches)
+    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+    bool dma = !a->a_bn_stat && !a->A2 && !a->bn_y && !a->colstats && split == 1 && !a->out_f32 && a->K >= 192 && a->N >= 128 && a->M >= 1024 &&
+               (rem == 0 || rem > 64) && a->lda * 512 < 0xFFFFFF00LL && a->ldb * 256 < 0xFFFFFF00LL && a->ldc * 512 < 0xFFFFFF00LL &&
+               (!a->residual || (a->ldr * 512 < 0xFFFFFF00LL && (a->ldr & 7) == 0 && al16(a->residual))) && (a->N & 7) == 0 && (a->ldc & 7) == 0 && al16(a->C) &&
+               (!a->preact || al16(a->preact)) && (!a->dact_preact || al16(a->dact_preact)) && (!a->bias || al16(a->bias));
+    if (const char* dma_sw = gg_dev_env("GG_GEMM_DMA")) dma = dma && atoi(dma_sw) != 0;      // (not cached: tools/bench_gemm16.py flips it between launches of one process)
+    if (dma) {
+        // the 256 x 256 geometry (one workgroup per CU) where its k-loop outweighs a lone workgroup's exposed prologue / epilogue: measured (tools/bench_gemm16.py,
+        // profiles/r05_gemm16_forms.txt) 1.37-1.41 PFLOP/s against 1.13-1.15 at K = 4096 / 8192, a tie at K = 3072 (CLIP fc2), 5-12 % slower at K = 384 ... 768
+        // -- except under the heaviest epilogue (GELU + pre-activation copy: two output tensors), where its eight waves finish the tile 3-5 % sooner
+        const char* tile_sw = gg_dev_env("GG_GEMM_DMA_TILE");
+        bool big = (a->K >= 4096 || (r.epi == EPI_GELU && a->preact && a->N >= 1536)) && a->N % 256 == 0 && (int64_t)gg_cdiv(a->M, 256) * gg_cdiv(a->N, 256) >= 512 &&
+                   a->ldb * 512 < 0xFFFFFF00LL;
+        if (tile_sw) big = atoi(tile_sw) == 256 && a->ldb * 512 < 0xFFFFFF00LL;
+        const int bm = big ? 256 : 192, bn = big ? 256 : 128;
+        r.kernel = big ? GG_GEMM_ROUTE_DMA_256x256 : GG_GEMM_ROUTE_DMA_192x128;
+        r.tilesM = (int)gg_cdiv(a->M, bm); r.tilesN = (int)gg_cdiv(a->N, bn);
+        r.group_m = r.tilesN > (big ? 4 : 8) ? (big ? 4 : 8) : 0;
+    }
+    return r;
+}
+extern "C" int GG_GEMM_NT_NAME(const GgGemmArgs* a, void* stream) {
+    if (const int rc = gemm_nt_check(a)) return rc;
+    const int split = a->split_k > 1 ? a->split_k : 1;
+    const GemmRoute route = gemm_nt_route(a);
     GemmParams p;
-    p.group_m = 0;
     p.a_stat = a->a_bn_stat; p.a_gamma = a->a_bn_gamma; p.a_beta = a->a_bn_beta; p.a_act = a->a_bn_act;
     p.A2 = (const ge_t*)a->A2; p.k_split = a->k_split;
     p.bn_y = (const ge_t*)a->bn_y; p.bn_stat = a->bn_stat; p.bn_gamma = a->bn_gamma; p.bn_beta = a->bn_beta; p.bn_act = a->bn_act;
@@ -1110,13 +1164,8 @@ extern "C" int GG_GEMM_NT_NAME(const GgGemmArgs* a, void* stream) {
     int kps = (int)gg_cdiv(a->K, split);
     kps = (int)gg_align(kps, BK);
     p.k_per_split = kps;
-    // tile choice: HBM-bound shapes (short K loop or a single narrow N tile) take the light 128x64 tile
-    static const char* force = gg_dev_env("GG_GEMM_TILE");
-    const int rem = a->N % 128;
-    bool narrow = a->N <= 64 || (rem != 0 && rem <= 64);     // a 128-wide tile would be at most half full
-    if (force) narrow = force[0] == 'n';
-    const int bn = narrow ? 64 : 128;
-    p.tilesM = (int)gg_cdiv(a->M, 128); p.tilesN = (int)gg_cdiv(a->N, bn);
+    const bool narrow = route.kernel == GG_GEMM_ROUTE_128x64;
+    p.tilesM = route.tilesM; p.tilesN = route.tilesN; p.group_m = route.group_m;
     // algorithmic bytes: A, B, C once each (bf16; f32 C = 4 bytes) plus every second tensor the epilogue reads or writes
     const double mn = (double)a->M * a->N;
     // algorithmic flops: the two-source dgrad (A2) contracts [dz | y] against the folded [c0 W ; c1 W] weights -- a doubled K that exists only
@@ -1126,35 +1175,11 @@ extern "C" int GG_GEMM_NT_NAME(const GgGemmArgs* a, void* stream) {
                 2.0 * mn * ((a->preact != nullptr) + (a->residual != nullptr) + (a->dact_preact != nullptr) + (a->bn_y != nullptr)),
             stream);
     dim3 grid(p.tilesM * p.tilesN, split);
-    int epi;
-    if (a->out_f32 || split > 1) epi = EPI_F32;
-    else if (p.bn_y) epi = EPI_BNBWD;
-    else if (p.dact) epi = EPI_DGELU;
-    else if (a->act == GG_ACT_GELU || (a->act == GG_ACT_QUICK_GELU && a->preact)) epi = EPI_GELU;      // (row-phase epilogue: pre-activation copy)
-    else if (a->act == GG_ACT_QUICK_GELU) epi = EPI_QGELU;
-    else if (a->bias || a->rowscale || a->residual) epi = EPI_LINEAR;
-    else epi = EPI_PLAIN;
+    const int epi = route.epi;
     hipStream_t st = (hipStream_t)stream;
-    // the MFMA-bound shapes (the transformer Linears and their data gradients) take the LDS-DMA form: 256 x 128 tiles
-    // (its epilogue has no general-shape fallbacks: whole 16-byte column chunks, 16-byte aligned rows of every tensor it touches)
-    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-    bool dma = !p.a_stat && !p.A2 && !p.bn_y && !p.colstats && split == 1 && !a->out_f32 && a->K >= 192 && a->N >= 128 && a->M >= 1024 &&
-               (rem == 0 || rem > 64) && a->lda * 512 < 0xFFFFFF00LL && a->ldb * 256 < 0xFFFFFF00LL && a->ldc * 512 < 0xFFFFFF00LL &&
-               (!a->residual || (a->ldr * 512 < 0xFFFFFF00LL && (a->ldr & 7) == 0 && al16(a->residual))) && (a->N & 7) == 0 && (a->ldc & 7) == 0 && al16(a->C) &&
-               (!a->preact || al16(a->preact)) && (!a->dact_preact || al16(a->dact_preact)) && (!a->bias || al16(a->bias));
-    if (const char* dma_sw = gg_dev_env("GG_GEMM_DMA")) dma = dma && atoi(dma_sw) != 0;      // (not cached: tools/bench_gemm16.py flips it between launches of one process)
-    if (dma) {
-        // the 256 x 256 geometry (one workgroup per CU) where its k-loop outweighs a lone workgroup's exposed prologue / epilogue: measured (tools/bench_gemm16.py,
-        // profiles/r05_gemm16_forms.txt) 1.37-1.41 PFLOP/s against 1.13-1.15 at K = 4096 / 8192, a tie at K = 3072 (CLIP fc2), 5-12 % slower at K = 384 ... 768
-        // -- except under the heaviest epilogue (GELU + pre-activation copy: two output tensors), where its eight waves finish the tile 3-5 % sooner
-        const char* tile_sw = gg_dev_env("GG_GEMM_DMA_TILE");
-        bool big = (a->K >= 4096 || (epi == EPI_GELU && a->preact && a->N >= 1536)) && a->N % 256 == 0 && (int64_t)gg_cdiv(a->M, 256) * gg_cdiv(a->N, 256) >= 512 &&
-                   a->ldb * 512 < 0xFFFFFF00LL;
-        if (tile_sw) big = atoi(tile_sw) == 256 && a->ldb * 512 < 0xFFFFFF00LL;
-        const int bm = big ? 256 : 192, bn = big ? 256 : 128;
-        p.tilesM = (int)gg_cdiv(a->M, bm); p.tilesN = (int)gg_cdiv(a->N, bn);
+    if (route.kernel == GG_GEMM_ROUTE_DMA_192x128 || route.kernel == GG_GEMM_ROUTE_DMA_256x256) {
+        const bool big = route.kernel == GG_GEMM_ROUTE_DMA_256x256;
         const dim3 g2((unsigned)(p.tilesM * p.tilesN)), blk(big ? 512 : 256);
-        p.group_m = p.tilesN > (big ? 4 : 8) ? (big ? 4 : 8) : 0;
 #define GG_DMA_LAUNCH(E, X)                                                                                             \
     do {                                                                                                                \
         if (big) hipLaunchKernelGGL((gemm_nt_dma_kernel<E, X, 8, 4>), g2, blk, 0, st, p);                               \
@@ -1200,6 +1225,16 @@ extern "C" int GG_GEMM_NT_NAME(const GgGemmArgs* a, void* stream) {
 }
 #ifndef GG_GEMM_SECOND_TYPE      // (the helpers below are type-independent or bf16-only: exported by the bf16 build)
 extern "C" int gg_gemm_colstats_rows(int M) { return (int)gg_cdiv(M, 128); }
+// Host arithmetic only (no launch, no device): the kernel gg_gemm_nt / gg_gemm_nt_f16 take for these arguments (GG_GEMM_ROUTE_*), its tile grid and its
+// tile walk -- what gemm_nt_route answers, which is what the launch obeys.  Arguments the launch refuses are refused here too (-1).
+extern "C" int gg_gemm_nt_route(const GgGemmArgs* a, int* group_m, int* tilesM, int* tilesN) {
+    if (const int rc = gemm_nt_check(a)) return rc;
+    const GemmRoute r = gemm_nt_route(a);
+    if (group_m) *group_m = r.group_m;
+    if (tilesM) *tilesM = r.tilesM;
+    if (tilesN) *tilesN = r.tilesN;
+    return r.kernel;
+}
 extern "C" int gg_stat_rows_capacity(int rows) { return rows + GG_REDUCE_SLICES; }
 
 // many slabs of a small matrix (patch_embed.conv1: 1536 x 6 KB): 64 float4 columns x 16 slab lanes per block, so a thread walks

@@ -66,6 +66,14 @@ typedef struct GgGemmArgs {
 } GgGemmArgs;
 int gg_gemm_nt(const GgGemmArgs* args, void* stream);
 int gg_gemm_colstats_rows(int M);
+/* Which kernel gg_gemm_nt / gg_gemm_nt_f16 launch for these arguments: host arithmetic only (no launch, no device needed), answered by the code the launch itself
+ * obeys, development switches included.  Returns a GG_GEMM_ROUTE_* code, or -1 for arguments the launch refuses; *group_m (0: row-major tile walk; else the LDS-DMA
+ * form walks groups of group_m M-tiles column by column), *tilesM and *tilesN (the tile grid) are written when not NULL. */
+#define GG_GEMM_ROUTE_128x128 0      /* register-staged, 128 x 128 tile */
+#define GG_GEMM_ROUTE_128x64 1       /* register-staged, 128 x 64 tile */
+#define GG_GEMM_ROUTE_DMA_192x128 2  /* LDS-DMA, 192 x 128 tile */
+#define GG_GEMM_ROUTE_DMA_256x256 3  /* LDS-DMA, 256 x 256 tile */
+int gg_gemm_nt_route(const GgGemmArgs* args, int* group_m, int* tilesM, int* tilesN);
 int gg_stat_rows_capacity(int rows);       /* rows a partial-statistics buffer must hold (valid rows + reduction scratch) */
 /* weight-gradient form: partials[splits][N][K] (f32) = per m-split  dY[M,N]^T . X[M,K]  (no transposed operand copies) */
 int gg_gemm_tn_splits(int M, int N, int K);

@@ -29,6 +29,11 @@ def test_header_symbols_exported_and_bound(L):
     for name in declared:
         assert hasattr(lib, name), name
     assert lib.gg_version() == 1
+    # a host-only helper answers without a device: the route report of the 16-bit NT GEMM (tests/test_gemm16_cases_cpu.py holds it to the dispatch rules)
+    a = L.GemmArgs()
+    a.A, a.B, a.C, a.lda, a.ldb, a.ldc, a.M, a.N, a.K, a.split_k = 0x10000, 0x10000, 0x10000, 192, 192, 200, 1030, 200, 192, 1
+    g, tm, tn = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+    assert lib.gg_gemm_nt_route(C.byref(a), C.byref(g), C.byref(tm), C.byref(tn)) == 2 and (g.value, tm.value, tn.value) == (0, 6, 2)
     # argument counts of the ctypes signatures agree with the header
     for n in L.SYMBOLS:
         m = re.search(r"\b" + n + r"\s*\(([^;]*?)\)\s*;", hdr, re.S)

@@ -54,8 +54,10 @@ def test_mfma_fragment_layout(ops):
 
 
 @pytest.mark.parametrize("M,N,K", [(128, 128, 32), (300, 200, 96), (1000, 48, 32), (4099, 384, 96), (96, 576, 2304),
-                                   (64, 12647, 576), (257, 96, 432)])
+                                   (64, 12647, 576), (257, 96, 432), (1030, 200, 192)])
 def test_gemm_plain(ops, M, N, K):
+    """Random operands on the register-staged kernel (f32 and bf16 output).  Only the bf16-output call of the last shape reaches the LDS-DMA form (M >= 1024, N >= 128,
+    K >= 192, no f32 output); that form's own tests are tests/test_gpu_gemm16_forms.py."""
     A, B = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=0.1)
     ref = A @ B.t()
     got = ops.gemm_nt(dev(A, BF), dev(B, BF), out_f32=True)
