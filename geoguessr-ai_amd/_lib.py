@@ -448,6 +448,15 @@ ATTN16B_SIGNATURES = {
 }
 ATTN16B_SYMBOLS = list(ATTN16B_SIGNATURES)
 
+# every exported symbol of include/gg_attn16wb.h (the same backward for TinyViT's windows beyond 256 tokens -- head dim 32, window gather, relative-position bias and its gradient -- and the bf16 TinyViT's opt-in switch that sends its training step to the 16-bit-MFMA kernels)
+ATTN16WB_SIGNATURES = {
+    "gg_attention_flash16_win_bwd": (_I, [C.POINTER(AttnArgs), _I, _P]),
+    "gg_attention_flash16_win_bwd_calls": (_L, []),
+    "gg_attention_flash16_win_dbias_rows": (_L, [_I, _I]),
+    "gg_tinyvit_set_attention16_train": (_I, [_I]),
+}
+ATTN16WB_SYMBOLS = list(ATTN16WB_SIGNATURES)
+
 
 def lib() -> C.CDLL:
     global _lib
@@ -456,7 +465,7 @@ def lib() -> C.CDLL:
             raise GgError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JSCAN_SIGNATURES.items()) + list(PANO_SIGNATURES.items()) + list(ATTN16_SIGNATURES.items()) + list(ATTN16W_SIGNATURES.items()) + list(ATTN16B_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JSCAN_SIGNATURES.items()) + list(PANO_SIGNATURES.items()) + list(ATTN16_SIGNATURES.items()) + list(ATTN16W_SIGNATURES.items()) + list(ATTN16B_SIGNATURES.items()) + list(ATTN16WB_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the library lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -516,6 +525,7 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(root), "include", "gg_attn16.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_attn16w.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_attn16b.h"))
+    files.append(os.path.join(os.path.dirname(root), "include", "gg_attn16wb.h"))
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

@@ -42,4 +42,8 @@ template <int D> struct A16Lds {
     static __device__ __forceinline__ constexpr int voff(int row, int ch) { return row * ROW + (((ch >> 1) ^ vswz(row)) << 5) + ((ch & 1) << 4); }
 };
 
+constexpr int A16_EMAX = 63 * 63;            // floats of the expanded (signed-offset) bias table at ws = 32
+// t / d by the reciprocal rcp = ceil(2^20 / d): exact for every index the kernels form (checked on the host)
+__device__ __forceinline__ int a16_div(int t, uint32_t rcp) { return (int)(((uint32_t)t * rcp) >> 20); }
+
 }  // namespace

@@ -55,9 +55,6 @@ struct A16Params {
     const float* bias_table;  // BIAS: [nh][ws * ws] f32
 };
 
-constexpr int A16_EMAX = 63 * 63;            // floats of the expanded bias table at ws = 32
-__device__ __forceinline__ int a16_div(int t, uint32_t rcp) { return (int)(((uint32_t)t * rcp) >> 20); }
-
 template <typename T, int D, bool WIN, bool BIAS>
 __global__ __launch_bounds__(256) void flash16_fwd_kernel(A16Params p) {
     constexpr int QS = 2;

@@ -18,6 +18,7 @@
 #include "../../include/gg_drop.h"
 #include "../../include/gg_pad.h"
 #include "../../include/gg_attn16w.h"
+#include "../../include/gg_attn16wb.h"
 
 bool gg_split3_af32_takes_rowmap(int N, int K);      // gemm_split3.hip: the form gg_gemm_nt_split3_af32 would run this shape on accepts row compaction
 
@@ -27,6 +28,8 @@ namespace {
 std::atomic<int> g_drop_compact{1};
 // the opt-in 16-bit-MFMA attention of the bf16 inference forward for windows beyond 256 tokens (gg_tinyvit_set_attention16, include/gg_attn16w.h)
 std::atomic<int> g_attention16{0};
+// the opt-in 16-bit-MFMA attention of the bf16 TRAINING step for windows beyond 256 tokens (gg_tinyvit_set_attention16_train, include/gg_attn16wb.h)
+std::atomic<int> g_attention16_train{0};
 
 struct TensorInfo { std::string name; int64_t offset; int64_t numel; int ndim; int64_t shape[4]; int kind; };
 static const float kAttnScale = 0.17677669529663687f;   // head_dim 32 ^ -0.5; the expanded bias tables are divided by it
@@ -558,6 +561,7 @@ struct Exec {
     // finalised (the forward's .stat checkpoints are reused, the running buffers are not touched) and the segment's output is not rewritten
     bool replay = false;
     bool compact = false;   // DropPath row compaction is on for this call (the process-global switch, read once per call)
+    bool attn16_train = false;      // training forward / backward, bf16, switch on (gg_tinyvit_set_attention16_train): the same windows through gg_attention_flash16_win_fwd / _bwd
     bool attn16 = false;    // gg_tinyvit_forward, inference, bf16, switch on (gg_tinyvit_set_attention16): windows beyond 256 tokens through gg_attention_flash16_win_fwd
     void done(int stage) const { if (stage_done) stage_done(stage, stage_user); }
     bool f32;               // reference-precision mode: f32 activations / cached weights, f32 MFMA
@@ -728,11 +732,22 @@ static void attn_args(const Exec& e, const StageL& st, const BlockL& l, const Bl
     at.out = e.A(a.o); at.ldo = C; at.lse = e.F(a.lse);
 }
 // (attn16: only the windows gg_attention_fwd itself hands to gg_attention_flash_fwd -- attention.hip, attn_use_flash -- leave that route)
+static bool attn_beyond_256(const GgAttnArgs& at) { return at.tokens_per_window > 256 || at.window_size > 16; }
 static int attention_fwd(const Exec& e, const GgAttnArgs& at) {
-    if (e.attn16 && (at.tokens_per_window > 256 || at.window_size > 16)) return gg_attention_flash16_win_fwd(&at, 0, e.st);
+    if ((e.attn16 || e.attn16_train) && attn_beyond_256(at)) return gg_attention_flash16_win_fwd(&at, 0, e.st);
     return e.f32 ? gg_attention_flash_fwd(&at, 1, e.st) : gg_attention_fwd(&at, e.st);
 }
-static int attention_bwd(const Exec& e, const GgAttnArgs& at) { return e.f32 ? gg_attention_flash_bwd(&at, 1, e.st) : gg_attention_bwd(&at, e.st); }
+// (attn16_train: the same windows; a compacted block -- window_map -- is an fp32_split form and never meets the switch)
+static bool attn16_bwd_takes(const Exec& e, const GgAttnArgs& at) { return e.attn16_train && attn_beyond_256(at) && !at.window_map; }
+static int attention_bwd(const Exec& e, const GgAttnArgs& at) {
+    if (attn16_bwd_takes(e, at)) return gg_attention_flash16_win_bwd(&at, 0, e.st);
+    return e.f32 ? gg_attention_flash_bwd(&at, 1, e.st) : gg_attention_bwd(&at, e.st);
+}
+// partial rows of the bias gradient's scratch for the kernel the call will reach
+static int64_t attn_dbias_rows(const Exec& e, const GgAttnArgs& at, bool flash) {
+    if (attn16_bwd_takes(e, at)) return gg_attention_flash16_win_dbias_rows(at.num_windows, at.tokens_per_window);
+    return flash ? gg_attention_flash_dbias_rows(at.num_windows, at.tokens_per_window) : (int64_t)at.num_windows + 64;
+}
 // padded block: zero-pad a [B, res, res, C] map of the stage to [B, pres, pres, C]; crop such a map back: y = res_in + rowscale[b] * t (y may be res_in)
 static int window_pad(const Exec& e, const StageL& st, const act_t* x, act_t* y) {
     return gg_window_pad(x, y, e.B, st.res, st.res, st.pres, st.pres, st.C, e.f32 ? 1 : 0, e.st);
@@ -1191,7 +1206,7 @@ static int block_bwd(const Exec& e, int s, size_t i, int slot, const GradBufs& g
         at.dout = t_a; at.lddo = C; at.dqkv = t_b;                                                         // dqkv -> t_b  [Mp, 3C]
         at.dbias = e.tr(l.t_ab) ? e.Gd(l.t_ab) : nullptr;
         const bool flash = e.f32 || at.tokens_per_window > 256 || st.ws > 16;
-        const int64_t prow = flash ? gg_attention_flash_dbias_rows(at.num_windows, at.tokens_per_window) : (int64_t)at.num_windows + 64;
+        const int64_t prow = attn_dbias_rows(e, at, flash);
         if (at.dbias && prow * st.heads * st.ws * st.ws * 4 <= ((int64_t)64 << 20)) at.dbias_scratch = e.F(L.splitk);
         static const bool ds_off_p = gg_dev_env("GG_ATTN_NO_DS_SCRATCH") != nullptr;
         if (e.f32 && L.attn_ds >= 0 && !ds_off_p) at.ds_scratch = e.F(L.attn_ds);
@@ -1220,7 +1235,7 @@ static int block_bwd(const Exec& e, int s, size_t i, int slot, const GradBufs& g
     at.dout = t_a; at.lddo = C; at.dqkv = t_b;
     at.dbias = e.tr(l.t_ab) ? e.Gd(l.t_ab) : nullptr;
     const bool flash = e.f32 || at.tokens_per_window > 256 || st.ws > 16;
-    const int64_t prow = flash ? gg_attention_flash_dbias_rows(at.num_windows, at.tokens_per_window) : (int64_t)at.num_windows + 64;
+    const int64_t prow = attn_dbias_rows(e, at, flash);
     if (at.dbias && prow * st.heads * st.ws * st.ws * 4 <= ((int64_t)64 << 20))
         at.dbias_scratch = e.F(L.splitk);      // per-workgroup partials -> deterministic second stage
     static const bool ds_off = gg_dev_env("GG_ATTN_NO_DS_SCRATCH") != nullptr;
@@ -1548,6 +1563,7 @@ static int refresh_weights(const GgTinyVitCfg* cfg, const float* params, void* w
 }
 extern "C" int gg_tinyvit_set_drop_compact(int on) { return g_drop_compact.exchange(on != 0 ? 1 : 0); }
 extern "C" int gg_tinyvit_set_attention16(int on) { return g_attention16.exchange(on != 0 ? 1 : 0); }
+extern "C" int gg_tinyvit_set_attention16_train(int on) { return g_attention16_train.exchange(on != 0 ? 1 : 0); }
 extern "C" int gg_tinyvit_forward(const GgTinyVitCfg* cfg, int batch, int training, const float* params, float* buffers,
                                   int64_t* counters, const void* wcache, const float* x, const float* drop_scales, void* workspace,
                                   float* out, const uint8_t* trainable, void* stream) {
@@ -1559,6 +1575,7 @@ extern "C" int gg_tinyvit_forward(const GgTinyVitCfg* cfg, int batch, int traini
     plan_make(m, batch, training != 0, p, L, trainable);
     const bool compact = g_drop_compact.load() != 0;
     const bool attn16 = training == 0 && !m.f32 && g_attention16.load() != 0;      // (m.f32 covers fp32 and fp32_split)
+    const bool attn16_train = training != 0 && !m.f32 && g_attention16_train.load() != 0;
     auto body = [&](hipStream_t st) -> int {
         Exec e(m, L, batch, training != 0);
         e.params = params; e.buffers = buffers; e.counters = counters;
@@ -1566,13 +1583,14 @@ extern "C" int gg_tinyvit_forward(const GgTinyVitCfg* cfg, int batch, int traini
         e.trainable = trainable;       // NULL: keep every activation a weight gradient could need
         e.compact = compact;
         e.attn16 = attn16;
+        e.attn16_train = attn16_train;
         return forward_impl(e, x, out);
     };
     // launch-bound sizes (a serving panorama, small training batches: a few hundred launches of microseconds each) replay a captured graph
     if (!gg_graph_wanted((int64_t)batch * cfg->img_size * cfg->img_size <= (int64_t)64 * 224 * 224)) return body((hipStream_t)stream);
     GgGraphKey key;
     key.add('F').add_bytes(cfg, sizeof(*cfg)).add(batch).add(training).add(params).add(buffers).add(counters).add(wcache).add(x).add(drop_scales).add(workspace).add(out).add((int)compact)
-       .add((int)attn16).add_bytes(trainable, trainable ? m.tensors.size() : 0);
+       .add((int)attn16).add((int)attn16_train).add_bytes(trainable, trainable ? m.tensors.size() : 0);
     return gg_graph_run(key, (hipStream_t)stream, body);
 }
 extern "C" int gg_tinyvit_backward(const GgTinyVitCfg* cfg, int batch, const float* params, const void* wcache, const float* drop_scales,
@@ -1588,6 +1606,7 @@ extern "C" int gg_tinyvit_backward(const GgTinyVitCfg* cfg, int batch, const flo
     e.wc = (const char*)wcache; e.ws = (char*)workspace; e.st = (hipStream_t)stream; e.drop = drop_scales; e.grads = grads;
     e.trainable = trainable; e.stage_done = stage_done; e.stage_user = stage_user;
     e.compact = g_drop_compact.load() != 0;
+    e.attn16_train = !m.f32 && g_attention16_train.load() != 0;      // the attention backward and the recompute replay (a training forward)
     if (trainable) {
         // The schedule forms the two gradients of a (weight, bias) / (gamma, beta) pair together (BatchNorm / LayerNorm finalize kernels, the fused
         // frozen-chain forms): a mask that trains one tensor of a pair and freezes the other has no schedule -- refuse it by name instead of silently
@@ -1611,7 +1630,7 @@ extern "C" int gg_tinyvit_backward(const GgTinyVitCfg* cfg, int batch, const flo
         return backward_impl(g, d_out);
     };
     GgGraphKey key;
-    key.add('B').add_bytes(cfg, sizeof(*cfg)).add(batch).add(params).add(wcache).add(drop_scales).add(workspace).add(d_out).add(grads).add((int)e.compact)
+    key.add('B').add_bytes(cfg, sizeof(*cfg)).add(batch).add(params).add(wcache).add(drop_scales).add(workspace).add(d_out).add(grads).add((int)e.compact).add((int)e.attn16_train)
        .add_bytes(trainable, trainable ? m.tensors.size() : 0);
     return gg_graph_run(key, (hipStream_t)stream, body);
 }

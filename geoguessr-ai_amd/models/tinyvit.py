@@ -59,6 +59,15 @@ def check_attention16(attention16: bool, precision: Optional[str], who: str) -> 
                         "attention (leave attention16 off)")
 
 
+def check_attention16_train(attention16_train: bool, precision: Optional[str], who: str) -> None:
+    """``attention16_train=True`` is a switch of the bf16 training step: refused by name for ``fp32`` and ``fp32_split`` (their attention is f32-accurate by
+    contract; ``check_attention16``'s wording)."""
+    prec = precision or default_precision()
+    if attention16_train and PRECISIONS.get(prec, 0) in (1, 3):
+        raise L.GgError(f"{who}: attention16_train=True is a switch of the bf16 mode; precision='{'fp32_split' if PRECISIONS[prec] == 3 else 'fp32'}' keeps its "
+                        "f32-accurate attention (leave attention16_train off)")
+
+
 def make_cfg(model_name: str, **overrides) -> tuple:
     base = model_name.split(".")[0]
     if base not in VARIANTS:
@@ -123,12 +132,17 @@ class TinyVitBackbone(EncoderRuntime):
     """Owner of the flat parameter / buffer storage and of the HIP workspace (``self.backbone`` of the adapter)."""
     _name, _switch, _gen_why = "TinyViT", "set_grad_checkpointing", "saved activations live in ONE workspace per backbone, so "
 
-    def __init__(self, model_name: str, seed: Optional[int] = None, attention16: bool = False, **overrides):
+    def __init__(self, model_name: str, seed: Optional[int] = None, attention16: bool = False, attention16_train: bool = False, **overrides):
         """``attention16=True`` (bf16 only; opt-in): this backbone's inference forwards run with ``gg_tinyvit_set_attention16(1)`` -- windows beyond 256 tokens
-        (tiny_vit_21m_384 / _512 stage 2) through ``gg_attention_flash16_win_fwd`` (include/gg_attn16w.h); training forwards are unaffected."""
+        (tiny_vit_21m_384 / _512 stage 2) through ``gg_attention_flash16_win_fwd`` (include/gg_attn16w.h); training forwards are unaffected.
+        ``attention16_train=True`` (bf16 only; opt-in, independent of ``attention16``): this backbone's training forwards and backwards run with
+        ``gg_tinyvit_set_attention16_train(1)`` -- the same windows' training forward, recompute replay and attention backward through
+        ``gg_attention_flash16_win_fwd`` / ``gg_attention_flash16_win_bwd`` (include/gg_attn16wb.h); inference forwards are unaffected."""
         super().__init__()
         check_attention16(attention16, overrides.get("precision"), type(self).__name__)
+        check_attention16_train(attention16_train, overrides.get("precision"), type(self).__name__)
         self.attention16 = bool(attention16)
+        self.attention16_train = bool(attention16_train)
         self.cfg, self.variant, self.depths = make_cfg(model_name, **overrides)
         self.model_name = model_name.split(".")[0]
         self.precision = "fp32" if self.cfg.act_dtype in (1, 3) else "bf16"          # storage / arithmetic class ("fp32_split" stores and checks like fp32)
@@ -254,6 +268,7 @@ class TinyVitBackbone(EncoderRuntime):
             assert drop_scales.shape == (self.num_drop_slots, B) and drop_scales.dtype == torch.float32
         lib = L.lib()
         prev = lib.gg_tinyvit_set_attention16(1) if self.attention16 else None      # process-wide switch, read when the forward is enqueued: set for this call only
+        prev_t = lib.gg_tinyvit_set_attention16_train(1) if self.attention16_train and training else None      # the same, the training step's switch
         try:
             L.check(lib.gg_tinyvit_forward(C.byref(cfg), B, int(training), L.ptr(self._flat), L.ptr(self._flat_buf),
                                            L.ptr(self._counters), L.ptr(self._wcache), L.ptr(x), L.ptr(drop_scales), L.ptr(ws),
@@ -262,6 +277,8 @@ class TinyVitBackbone(EncoderRuntime):
         finally:
             if prev is not None:
                 lib.gg_tinyvit_set_attention16(prev)
+            if prev_t is not None:
+                lib.gg_tinyvit_set_attention16_train(prev_t)
         if training:
             self._counters += 1          # num_batches_tracked (int64 bookkeeping)
             self._record_forward(B, mask, drop_scales)
@@ -303,9 +320,15 @@ class TinyVitBackbone(EncoderRuntime):
                 except BaseException as exc:      # noqa: BLE001 -- must not escape into the C caller
                     failed.append(exc)
             cb = L.STAGE_DONE_FN(_stage_done)
-        L.check(L.lib().gg_tinyvit_backward(C.byref(self.cfg), B, L.ptr(self._flat), L.ptr(self._wcache), L.ptr(drop), L.ptr(ws),
+        lib = L.lib()
+        prev_t = lib.gg_tinyvit_set_attention16_train(1) if self.attention16_train else None      # read when the backward is enqueued (its recompute replay included)
+        try:
+            L.check(lib.gg_tinyvit_backward(C.byref(self.cfg), B, L.ptr(self._flat), L.ptr(self._wcache), L.ptr(drop), L.ptr(ws),
                                             L.ptr(d_out.contiguous(), torch.float32, "d_out"), L.ptr(fg), mask, L.stream(), cb, None),
-                "gg_tinyvit_backward")
+                    "gg_tinyvit_backward")
+        finally:
+            if prev_t is not None:
+                lib.gg_tinyvit_set_attention16_train(prev_t)
         if failed:
             raise L.GgError(f"TinyViT backward: the gradient-ready hook failed ({type(failed[0]).__name__}: {failed[0]}); the gradients are "
                             "complete, but no further bucket was sent from inside this backward pass") from failed[0]
@@ -345,9 +368,12 @@ class TinyViTAdapter(nn.Module):
         ``drop_path_rate``, ``img_size`` (any multiple of 32: where the attention window does not divide a stage's map the blocks pad it --
         ``backbone.padded_maps``) ... (timm ``create_model`` kwargs), ``grad_checkpointing=True`` (activation recompute from the start;
         the same as ``adapter.backbone.set_grad_checkpointing()``), ``attention16=True`` (bf16 only, opt-in: the inference forward's windows beyond
-        256 tokens on the 16-bit MFMA -- ``TinyVitBackbone``; ``precision="fp32"`` / ``"fp32_split"`` with it raises)."""
+        256 tokens on the 16-bit MFMA -- ``TinyVitBackbone``; ``precision="fp32"`` / ``"fp32_split"`` with it raises), ``attention16_train=True`` (bf16 only, opt-in,
+        independent of ``attention16``: the training step's windows beyond 256 tokens -- forward, recompute replay and backward -- on the 16-bit MFMA; the same
+        refusals)."""
         super().__init__()
         check_attention16(overrides.get("attention16", False), overrides.get("precision"), "TinyViTAdapter")
+        check_attention16_train(overrides.get("attention16_train", False), overrides.get("precision"), "TinyViTAdapter")
         if global_pool != "avg":
             raise NotImplementedError("only global_pool='avg' (the reference's setting) is built")
         # features_only=True (models/tinyvit.py:38-46): timm returns the stage feature maps and the adapter's forward pools the last

@@ -21,7 +21,7 @@ from torch.nn.modules.module import _IncompatibleKeys
 
 from .. import _lib as L
 from .. import ops
-from .tinyvit import TinyVitBackbone, check_attention16
+from .tinyvit import TinyVitBackbone, check_attention16, check_attention16_train
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -121,7 +121,7 @@ class _Head(nn.Module):
 
 class TinyViTClassifier(nn.Module):
     """``overrides`` as ``TinyViTAdapter``: ``precision`` ("fp32" | "fp32_split" | "bf16"; default ``$GG_PRECISION`` or fp32), ``seed``, ``drop_path_rate``,
-    ``grad_checkpointing``, ``img_size``, ``attention16`` (bf16 only: the inference forward's windows beyond 256 tokens on the 16-bit MFMA) ...  ``pretrained=True`` cannot download: ``$GG_PRETRAINED_DIR/<model_name>.pt`` (a timm state dict, any head size)
+    ``grad_checkpointing``, ``img_size``, ``attention16`` (bf16 only: the inference forward's windows beyond 256 tokens on the 16-bit MFMA), ``attention16_train`` (bf16 only: the training step's) ...  ``pretrained=True`` cannot download: ``$GG_PRETRAINED_DIR/<model_name>.pt`` (a timm state dict, any head size)
     is loaded with ``strict=False`` when it exists, otherwise a warning is issued and the timm initialisation stands."""
 
     def __init__(self, model_name: str = "tiny_vit_5m_224", num_classes: int = 1000, pretrained: bool = False, **overrides):
@@ -131,6 +131,7 @@ class TinyViTClassifier(nn.Module):
         if overrides.get("features_only"):
             raise ValueError("features_only belongs to TinyViTAdapter; the classifier exports features through forward_features / pooled_features")
         check_attention16(overrides.get("attention16", False), overrides.get("precision"), "TinyViTClassifier")
+        check_attention16_train(overrides.get("attention16_train", False), overrides.get("precision"), "TinyViTClassifier")
         self.backbone = TinyVitBackbone(model_name, **overrides)
         self.num_classes, self.num_features = int(num_classes), self.backbone.num_features
         seed = overrides.get("seed")

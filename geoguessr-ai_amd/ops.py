@@ -640,6 +640,39 @@ def attention_flash16_win(qkv, *, num_windows, tokens_per_window, num_heads, q_o
     return (out, lse_t) if want_lse else out
 
 
+def attention_flash16_win_bwd(qkv, out, lse, dout, *, num_windows, tokens_per_window, num_heads, q_off, k_off, v_off, head_stride, window_size, map_h, map_w,
+                              head_dim=32, bias_table=None, want_dbias=False, deterministic_dbias=True, scale=None, dqkv=None):
+    """Window attention backward beyond 256 tokens with all five products on the 16-bit MFMA (include/gg_attn16wb.h): bf16 storage, head dim 32, tokens gathered
+    from the ``window_size`` x ``window_size`` windows of a ``map_h`` x ``map_w`` NHWC map, the compact f32 ``bias_table`` [heads][ws * ws] (or None).  ``out`` /
+    ``lse``: the forward's (``attention_flash16_win`` or ``attention_flash`` on bf16).  Returns (dqkv, dbias): dqkv of qkv's shape -- the dq, dk and dv columns of
+    every token are written, every other column keeps the zero fill (``dqkv``, optional: a buffer of qkv's shape and row stride to write into instead) -- and, with
+    ``want_dbias`` and a table, the bias gradient (else None); ``deterministic_dbias=False`` leaves out the partial-row scratch (global float atomics)."""
+    L.require_gpu()
+    if qkv.dtype != BF16:
+        raise L.GgError(f"attention_flash16_win_bwd: bf16 storage (got {qkv.dtype})")
+    a = L.AttnArgs()
+    a.qkv, a.ld = _pr(qkv, BF16, "qkv"), qkv.stride(0)      # rows may be strided: a column slice of a wider buffer
+    a.q_off, a.k_off, a.v_off, a.head_stride, a.head_dim = q_off, k_off, v_off, head_stride, head_dim
+    a.num_heads, a.num_windows, a.tokens_per_window = num_heads, num_windows, tokens_per_window
+    a.window_size, a.map_h, a.map_w = window_size, map_h, map_w
+    a.scale = head_dim ** -0.5 if scale is None else scale
+    a.bias_table = _p(bias_table, F32, "bias_table")
+    if dqkv is None:
+        dqkv = torch.zeros(qkv.shape[0], qkv.stride(0), dtype=BF16, device=qkv.device)[:, :qkv.shape[1]]
+    elif dqkv.shape != qkv.shape or dqkv.stride(0) != qkv.stride(0):
+        raise L.GgError("attention_flash16_win_bwd: dqkv must have qkv's shape and row stride")
+    dbias = torch.zeros_like(bias_table) if (want_dbias and bias_table is not None) else None
+    scratch = None
+    if dbias is not None and deterministic_dbias:
+        rows = L.lib().gg_attention_flash16_win_dbias_rows(num_windows, tokens_per_window)
+        scratch = torch.empty((rows * num_heads * window_size * window_size,), dtype=F32, device=qkv.device)
+    a.dbias, a.dbias_scratch = _p(dbias), _p(scratch)
+    a.out, a.ldo, a.lse = _pr(out, BF16, "out"), out.stride(0), _p(lse, F32, "lse")
+    a.dout, a.lddo, a.dqkv = _pr(dout, BF16, "dout"), dout.stride(0), _pr(dqkv, BF16, "dqkv")
+    L.check(L.lib().gg_attention_flash16_win_bwd(C.byref(a), 0, L.stream()), "gg_attention_flash16_win_bwd")
+    return dqkv, dbias
+
+
 def attention(qkv, *, num_windows, tokens_per_window, num_heads, head_dim, q_off, k_off, v_off, head_stride,
               window_size=0, map_h=0, map_w=0, bias=None, scale=None, dout=None, want_dbias=False, out=None, lse=None,
               want_lse=False):
