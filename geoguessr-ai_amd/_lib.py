@@ -458,6 +458,35 @@ ATTN16WB_SIGNATURES = {
 ATTN16WB_SYMBOLS = list(ATTN16WB_SIGNATURES)
 
 
+# every exported symbol of include/gg_attn_route.h (the route report of the attention entry points: host arithmetic, no device), its struct and its two enums
+class AttnRoutePass(C.Structure):
+    _fields_ = [("grid", C.c_uint32), ("block", C.c_uint32), ("lds", C.c_uint32)]
+
+
+class AttnRoute(C.Structure):           # GgAttnRoute
+    _fields_ = [("kernel", C.c_int), ("variant", C.c_int), ("passes", C.c_int), ("pass_", AttnRoutePass * 2), ("dbias_rows", C.c_int64),
+                ("reads_ds_scratch", C.c_int), ("rounded_bias", C.c_int)]
+
+
+ATTN_ENTRIES = ("FWD", "FWD_F16", "BWD", "FLASH_FWD", "FLASH_BWD", "CAUSAL_FWD", "CAUSAL_BWD", "FLASH16_FWD", "FLASH16_WIN_FWD", "FLASH16_BWD", "FLASH16_WIN_BWD")      # GG_ATTN_ENTRY_*
+ATTN_KERNELS = ("NONE", "FWD", "FWD_GROUPED", "BWD", "BWD_GROUPED", "FLASH_FWD_RESIDENT", "FLASH_FWD_STREAM", "FLASH_FWD_SPLIT", "FLASH64_FWD_SPLIT", "FLASH_BWD_SPLIT",
+                "FLASH_BWD_FUSED", "FLASH_BWD_STREAM", "FLASH_BWD_STREAM_DS", "FLASH64_BWD_SPLIT", "FLASH16_FWD", "FLASH16_WIN_FWD", "FLASH16_BWD", "FLASH16_WIN_BWD")      # GG_ATTN_KERNEL_*
+ATTN_ENTRY = {n: i for i, n in enumerate(ATTN_ENTRIES)}
+ATTN_KERNEL = {n: i for i, n in enumerate(ATTN_KERNELS)}
+ATTN_ROUTE_SIGNATURES = {
+    "gg_attention_route": (_I, [C.POINTER(AttnArgs), _I, _I, C.POINTER(AttnRoute)]),
+}
+ATTN_ROUTE_SYMBOLS = list(ATTN_ROUTE_SIGNATURES)
+
+
+def attention_route(args: "AttnArgs", entry: str, dtype: int = 0) -> "AttnRoute":
+    """What ``gg_attention_route`` reports for exactly these arguments (``entry``: a name of ATTN_ENTRIES); a refusal raises with the entry point's own text."""
+    r = AttnRoute()
+    if lib().gg_attention_route(C.byref(args), ATTN_ENTRY[entry], dtype, C.byref(r)) != 0:
+        raise GgError(lib().gg_last_error().decode(errors="replace"))
+    return r
+
+
 def lib() -> C.CDLL:
     global _lib
     if _lib is None:
@@ -465,7 +494,7 @@ def lib() -> C.CDLL:
             raise GgError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JSCAN_SIGNATURES.items()) + list(PANO_SIGNATURES.items()) + list(ATTN16_SIGNATURES.items()) + list(ATTN16W_SIGNATURES.items()) + list(ATTN16B_SIGNATURES.items()) + list(ATTN16WB_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JSCAN_SIGNATURES.items()) + list(PANO_SIGNATURES.items()) + list(ATTN16_SIGNATURES.items()) + list(ATTN16W_SIGNATURES.items()) + list(ATTN16B_SIGNATURES.items()) + list(ATTN16WB_SIGNATURES.items()) + list(ATTN_ROUTE_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the library lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -526,6 +555,7 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(root), "include", "gg_attn16w.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_attn16b.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_attn16wb.h"))
+    files.append(os.path.join(os.path.dirname(root), "include", "gg_attn_route.h"))
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

@@ -14,7 +14,7 @@
 #include "common.h"
 #include <stdlib.h>
 #include "../../include/gg.h"
-int gg_attention_flash_bwd_impl(const GgAttnArgs* a, int dtype, int forward_rounded_bias, void* stream);      // attention_flash.hip
+#include "attention_route.h"
 
 struct AttnParams {
     const bf16* qkv; int64_t ld;
@@ -907,15 +907,6 @@ __global__ __launch_bounds__(256) void attn_bwd_small_kernel(AttnParams p, int n
     }
 }
 
-// dbias[h][t] += sum over the (folded) window rows of part[row][h][t]
-__global__ void attn_dbias_final_kernel(const float* __restrict__ rows, int nrows, int W, float* __restrict__ dbias) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= W) return;
-    double s = 0.0;
-    for (int r = 0; r < nrows; ++r) s += (double)rows[(int64_t)r * W + i];
-    dbias[i] += (float)s;
-}
-
 // ------------------------------------------------------------------------------------------- host
 static int attn_fill(AttnParams& p, const GgAttnArgs* a, const char* who) {
     GG_CHECK(a && a->qkv, "%s: null qkv", who);
@@ -926,9 +917,7 @@ static int attn_fill(AttnParams& p, const GgAttnArgs* a, const char* who) {
     GG_CHECK((a->ld & 7) == 0 && (a->q_off & 7) == 0 && (a->k_off & 7) == 0 && (a->v_off & 7) == 0 && (a->head_stride & 7) == 0,
              "%s: qkv offsets/strides must be multiples of 8 elements", who);
     if (a->window_size > 0) {
-        GG_CHECK(a->window_size * a->window_size == a->tokens_per_window, "%s: window_size^2 != tokens_per_window", who);
-        GG_CHECK(a->map_h % a->window_size == 0 && a->map_w % a->window_size == 0, "%s: map not divisible by window", who);
-        GG_CHECK(a->num_windows % ((a->map_h / a->window_size) * (a->map_w / a->window_size)) == 0, "%s: window count", who);
+        GG_TRY(attn_check_windows(a, false, who));
         GG_CHECK(a->window_size <= 16, "%s: window_size > 16 unsupported", who);
     }
     if (a->bias || a->dbias) GG_CHECK(a->window_size > 0 && a->tokens_per_window <= 256, "%s: bias needs a window geometry", who);
@@ -958,109 +947,125 @@ extern "C" int gg_attention_expand_bias(const float* table, int num_heads, int w
     return 0;
 }
 
-// beyond 256 tokens per window (tiny_vit_21m_384 / _512 stage 2, CLIP ViT-L/14-336) a score row no longer fits a wave's registers:
-// those shapes run on the online-softmax kernels of attention_flash.hip (bias from the compact f32 table)
-static bool attn_use_flash(const GgAttnArgs* a) { return a && (a->tokens_per_window > 256 || a->window_size > 16); }
-// The BACKWARD of 12 x 12 / 14 x 14 windows of head dim 32 also leaves this file: attention_split.h's single-pass kernel (bf16 storage, one plane) reads q, k, v,
-// dO, O once and forms five products instead of the seven of attn_bwd_kernel's two phases, and gathers the bias from the compact f32 table in LDS instead of
-// reading the expanded [heads][Np][Np] table from memory twice per workgroup (590 against 756 us per 14 x 14 layer; the expanded table's re-reads were the
-// 1.49x HBM traffic of round 4's bf16 attention class).  7 x 7 windows stay on the grouped kernels below, every forward stays here.
-static bool attn_use_split_bwd(const GgAttnArgs* a) {
-    static const bool nosplit = gg_dev_env("GG_ATTN_NO_SPLIT") != nullptr;
-    if (!a || nosplit || a->head_dim != 32 || a->window_size <= 0) return false;
-    const int nt16 = (a->tokens_per_window + 15) / 16;
-    return (nt16 == 13 || nt16 == 9) && (!a->bias || a->bias_table);
-}
-extern "C" int gg_attention_fwd(const GgAttnArgs* a, void* stream) {
-    if (attn_use_flash(a)) {
-        GG_CHECK(!a->bias || a->bias_table, "gg_attention_fwd: this window shape takes the bias as bias_table (compact f32)");
-        return gg_attention_flash_fwd(a, 0, stream);
-    }
-    AttnParams p;
-    GG_TRY(attn_fill(p, a, "gg_attention_fwd"));
-    GG_CHECK(a->out && (a->ldo & 3) == 0, "gg_attention_fwd: bad out");
-    dim3 grid((unsigned)(a->num_windows * a->num_heads)), block(256);
-    hipStream_t s = (hipStream_t)stream;
-    GG_PROF(GG_CAT_ATTN, 4.0 * a->num_windows * a->num_heads * (double)p.N * p.N * a->head_dim, 8.0 * a->num_windows * a->num_heads * (double)p.N * a->head_dim, stream);
-    const int nkt = attn_nkt(p.N);
-#define GG_FWD(D_, K_) hipLaunchKernelGGL((attn_fwd_kernel<D_, K_>), grid, block, 0, s, p)
-    static const char* small_env = gg_dev_env("GG_ATTN_SMALL");
-    if (a->head_dim == 32 && nkt == 4 && !(small_env && small_env[0] == '0') && a->num_windows >= 64) {
-        constexpr int GW = 8;          // windows per workgroup
-        const dim3 g2((unsigned)(gg_cdiv(a->num_windows, GW) * a->num_heads));
-        hipLaunchKernelGGL((attn_fwd_small_kernel<32, GW>), g2, block, 0, s, p, a->num_windows);
-        GG_LAUNCH_CHECK();
+// Which kernel gg_attention_fwd, gg_attention_fwd_f16 and gg_attention_bwd (`entry`) launch for checked arguments: the ONE place of this file that decides it.
+// The launchers execute the route this fills, gg_attention_route reports it.  Two shapes leave this file, and then `to` names the flash entry, dtype and bias
+// rounding the call is forwarded with (flash_route decides the rest) and nothing else is filled:
+//   * beyond 256 tokens per window (tiny_vit_21m_384 / _512 stage 2, CLIP ViT-L/14-336) a score row no longer fits a wave's registers: those shapes run on the
+//     online-softmax kernels of attention_flash.hip (bias from the compact f32 table);
+//   * the BACKWARD of 12 x 12 / 14 x 14 windows of head dim 32: attention_split.h's single-pass kernel (bf16 storage, one plane) reads q, k, v, dO, O once and
+//     forms five products instead of the seven of attn_bwd_kernel's two phases, and gathers the bias from the compact f32 table in LDS instead of reading the
+//     expanded [heads][Np][Np] table from memory twice per workgroup (590 against 756 us per 14 x 14 layer; the expanded table's re-reads were the 1.49x HBM
+//     traffic of round 4's bf16 attention class).  That forward was this file's and added the bias as bf16(bias / scale): the backward recomputes P with that
+//     value (rounded_bias); beyond 256 tokens the forward was gg_attention_flash_fwd, which read the unrounded f32 table.
+// 7 x 7 windows stay on the grouped kernels (ATTN_GW consecutive windows of a head per workgroup, from 64 windows on), every other forward stays here.
+constexpr int ATTN_GW = 8;
+struct AttnForward { int entry, dtype, rounded_bias; };      // entry < 0: the route is this file's
+static int attn_route(const GgAttnArgs* a, int entry, AttnParams& p, GgAttnRoute& r, AttnForward& to) {
+    const AttnSwitches& sw = attn_switches();
+    const bool bwd = entry == GG_ATTN_ENTRY_BWD, f16e = entry == GG_ATTN_ENTRY_FWD_F16;
+    const char* who = bwd ? "gg_attention_bwd" : f16e ? "gg_attention_fwd_f16" : "gg_attention_fwd";
+    r = GgAttnRoute{};
+    to = AttnForward{-1, 0, 0};
+    if (f16e) GG_CHECK(a && !a->bias && !a->bias_table, "gg_attention_fwd_f16: the fp16 forward takes no bias");
+    const bool beyond = a && (a->tokens_per_window > 256 || a->window_size > 16);
+    const int nt16 = a ? (a->tokens_per_window + 15) / 16 : 0;
+    const bool split_bwd = bwd && a && !sw.no_split && a->head_dim == 32 && a->window_size > 0 && (nt16 == 13 || nt16 == 9) && (!a->bias || a->bias_table);
+    if (beyond || split_bwd) {
+        if (!f16e) GG_CHECK(!a->bias || a->bias_table, "%s: this window shape takes the bias as bias_table (compact f32)", who);
+        to = AttnForward{bwd ? GG_ATTN_ENTRY_FLASH_BWD : GG_ATTN_ENTRY_FLASH_FWD, f16e ? 2 : 0, beyond ? 0 : 1};
         return 0;
     }
-    if (a->head_dim == 32) {
-        if (nkt == 4) GG_FWD(32, 4); else if (nkt == 10) GG_FWD(32, 10); else if (nkt == 14) GG_FWD(32, 14); else GG_FWD(32, 16);
+    GG_TRY(attn_fill(p, a, who));
+    if (bwd) {
+        GG_CHECK(a->dout && a->dqkv && (a->lddo & 7) == 0, "gg_attention_bwd: bad dout/dqkv");
+        GG_CHECK(a->lse && a->out && (a->ldo & 7) == 0, "gg_attention_bwd: needs the forward's lse and out");
+        GG_CHECK(a->head_dim == 32, "gg_attention_bwd: only head_dim 32 (TinyViT) is built");
     } else {
-        if (nkt == 4) GG_FWD(64, 4); else if (nkt == 10) GG_FWD(64, 10); else if (nkt == 14) GG_FWD(64, 14); else GG_FWD(64, 16);
+        GG_CHECK(a->out && (a->ldo & 3) == 0, "%s: bad out", who);
+    }
+    const int nkt = attn_nkt(p.N);
+    const bool grouped = !f16e && a->head_dim == 32 && nkt == 4 && !sw.no_grouped && a->num_windows >= 64;
+    const int64_t part_rows = grouped ? gg_cdiv(a->num_windows, ATTN_GW) : a->num_windows;      // one partial dbias row per (workgroup, head)
+    r.kernel = grouped ? (bwd ? GG_ATTN_KERNEL_BWD_GROUPED : GG_ATTN_KERNEL_FWD_GROUPED) : (bwd ? GG_ATTN_KERNEL_BWD : GG_ATTN_KERNEL_FWD);
+    r.variant = grouped ? 0 : nkt;
+    attn_route_pass(r, part_rows * a->num_heads, 256, 0);
+    if (bwd && a->dbias) r.dbias_rows = attn_dbias_scratch_rows(part_rows);
+    return 0;
+}
+// The forward of bf16 (gg_attention_fwd) and fp16 storage (gg_attention_fwd_f16: inference of the CLIP tower's fp16 mode, pretrain/clip_embedder.py:63-65 at
+// BASELINE config c4's precision: QK^T and PV on v_mfma_f32_16x16x32_f16, f32 accumulation and softmax, no relative-position bias -- the CLIP tower has none).
+template <typename T>
+static int attn_fwd_launch(const GgAttnArgs* a, int entry, void* stream) {
+    AttnParams p;
+    GgAttnRoute r;
+    AttnForward to;
+    GG_TRY(attn_route(a, entry, p, r, to));
+    if (to.entry >= 0) return gg_attention_flash_fwd(a, to.dtype, stream);
+    const dim3 grid(r.pass[0].grid), block(r.pass[0].block);
+    hipStream_t s = (hipStream_t)stream;
+    GG_PROF(GG_CAT_ATTN, 4.0 * a->num_windows * a->num_heads * (double)p.N * p.N * a->head_dim, 8.0 * a->num_windows * a->num_heads * (double)p.N * a->head_dim, stream);
+#define GG_FWD(D_)                                                                                  \
+    switch (r.variant) {                                                                            \
+        case 4: hipLaunchKernelGGL((attn_fwd_kernel<D_, 4, T>), grid, block, 0, s, p); break;       \
+        case 10: hipLaunchKernelGGL((attn_fwd_kernel<D_, 10, T>), grid, block, 0, s, p); break;     \
+        case 14: hipLaunchKernelGGL((attn_fwd_kernel<D_, 14, T>), grid, block, 0, s, p); break;     \
+        default: hipLaunchKernelGGL((attn_fwd_kernel<D_, 16, T>), grid, block, 0, s, p); break;     \
+    }
+    switch (r.kernel) {
+        case GG_ATTN_KERNEL_FWD_GROUPED: hipLaunchKernelGGL((attn_fwd_small_kernel<32, ATTN_GW>), grid, block, 0, s, p, a->num_windows); break;
+        default:
+            if (a->head_dim == 32) GG_FWD(32) else GG_FWD(64)
+            break;
     }
 #undef GG_FWD
     GG_LAUNCH_CHECK();
     return 0;
 }
-// fp16 twin of the forward (inference of the CLIP tower's fp16 mode: pretrain/clip_embedder.py:63-65 at BASELINE config c4's precision): fp16 storage,
-// QK^T and PV on v_mfma_f32_16x16x32_f16, f32 accumulation and softmax.  No relative-position bias (the CLIP tower has none); sequences beyond 256
-// tokens go to the online-softmax kernel (fp16 storage, f32 arithmetic).
-extern "C" int gg_attention_fwd_f16(const GgAttnArgs* a, void* stream) {
-    GG_CHECK(a && !a->bias && !a->bias_table, "gg_attention_fwd_f16: the fp16 forward takes no bias");
-    if (attn_use_flash(a)) return gg_attention_flash_fwd(a, 2, stream);
-    AttnParams p;
-    GG_TRY(attn_fill(p, a, "gg_attention_fwd_f16"));
-    GG_CHECK(a->out && (a->ldo & 3) == 0, "gg_attention_fwd_f16: bad out");
-    dim3 grid((unsigned)(a->num_windows * a->num_heads)), block(256);
-    hipStream_t s = (hipStream_t)stream;
-    GG_PROF(GG_CAT_ATTN, 4.0 * a->num_windows * a->num_heads * (double)p.N * p.N * a->head_dim, 8.0 * a->num_windows * a->num_heads * (double)p.N * a->head_dim, stream);
-    const int nkt = attn_nkt(p.N);
-#define GG_FWD16(D_, K_) hipLaunchKernelGGL((attn_fwd_kernel<D_, K_, f16>), grid, block, 0, s, p)
-    if (a->head_dim == 32) {
-        if (nkt == 4) GG_FWD16(32, 4); else if (nkt == 10) GG_FWD16(32, 10); else if (nkt == 14) GG_FWD16(32, 14); else GG_FWD16(32, 16);
-    } else {
-        if (nkt == 4) GG_FWD16(64, 4); else if (nkt == 10) GG_FWD16(64, 10); else if (nkt == 14) GG_FWD16(64, 14); else GG_FWD16(64, 16);
-    }
-#undef GG_FWD16
-    GG_LAUNCH_CHECK();
-    return 0;
-}
+extern "C" int gg_attention_fwd(const GgAttnArgs* a, void* stream) { return attn_fwd_launch<bf16>(a, GG_ATTN_ENTRY_FWD, stream); }
+extern "C" int gg_attention_fwd_f16(const GgAttnArgs* a, void* stream) { return attn_fwd_launch<f16>(a, GG_ATTN_ENTRY_FWD_F16, stream); }
 extern "C" int gg_attention_bwd(const GgAttnArgs* a, void* stream) {
-    if (attn_use_flash(a) || attn_use_split_bwd(a)) {
-        GG_CHECK(!a->bias || a->bias_table, "gg_attention_bwd: this window shape takes the bias as bias_table (compact f32)");
-        // attn_use_split_bwd: the forward was this file's and added the bias as bf16(bias / scale); the backward recomputes P with that value.
-        // attn_use_flash: the forward was gg_attention_flash_fwd, which read the unrounded f32 table
-        return gg_attention_flash_bwd_impl(a, 0, attn_use_flash(a) ? 0 : 1, stream);
-    }
     AttnParams p;
-    GG_TRY(attn_fill(p, a, "gg_attention_bwd"));
-    GG_CHECK(a->dout && a->dqkv && (a->lddo & 7) == 0, "gg_attention_bwd: bad dout/dqkv");
-    GG_CHECK(a->lse && a->out && (a->ldo & 7) == 0, "gg_attention_bwd: needs the forward's lse and out");
-    GG_CHECK(a->head_dim == 32, "gg_attention_bwd: only head_dim 32 (TinyViT) is built");
-    dim3 grid((unsigned)(a->num_windows * a->num_heads)), block(256);
+    GgAttnRoute r;
+    AttnForward to;
+    GG_TRY(attn_route(a, GG_ATTN_ENTRY_BWD, p, r, to));
+    if (to.entry >= 0) return gg_attention_flash_bwd_impl(a, to.dtype, to.rounded_bias, stream);
+    const dim3 grid(r.pass[0].grid), block(r.pass[0].block);
     hipStream_t s = (hipStream_t)stream;
     GG_PROF(GG_CAT_ATTN, 10.0 * a->num_windows * a->num_heads * (double)p.N * p.N * a->head_dim, 16.0 * a->num_windows * a->num_heads * (double)p.N * a->head_dim, stream);
-    const int nkt = attn_nkt(p.N);
 #define GG_BWD(K_)                                                                                       \
     do {                                                                                                 \
         if (p.dbias) hipLaunchKernelGGL((attn_bwd_kernel<32, K_, true>), grid, block, 0, s, p);          \
         else hipLaunchKernelGGL((attn_bwd_kernel<32, K_, false>), grid, block, 0, s, p);                 \
     } while (0)
-    static const char* small_env = gg_dev_env("GG_ATTN_SMALL");
-    int part_rows = a->num_windows;
-    if (nkt == 4 && !(small_env && small_env[0] == '0') && a->num_windows >= 64) {
-        constexpr int GW = 8;
-        part_rows = (int)gg_cdiv(a->num_windows, GW);
-        const dim3 g2((unsigned)(part_rows * a->num_heads));
-        if (p.dbias) hipLaunchKernelGGL((attn_bwd_small_kernel<32, GW, true>), g2, block, 0, s, p, a->num_windows);
-        else hipLaunchKernelGGL((attn_bwd_small_kernel<32, GW, false>), g2, block, 0, s, p, a->num_windows);
-    } else if (nkt == 4) GG_BWD(4); else if (nkt == 10) GG_BWD(10); else if (nkt == 14) GG_BWD(14); else GG_BWD(16);
-#undef GG_BWD
-    if (p.dbias && p.dbias_part) {
-        const int Wd = p.nh * p.nbias;
-        const float* rows; int nrows;
-        gg_reduce_rows(p.dbias_part, part_rows, Wd, s, &rows, &nrows);
-        hipLaunchKernelGGL(attn_dbias_final_kernel, dim3((unsigned)gg_cdiv(Wd, 256)), dim3(256), 0, s, rows, nrows, Wd, p.dbias);
+    switch (r.kernel) {
+        case GG_ATTN_KERNEL_BWD_GROUPED:
+            if (p.dbias) hipLaunchKernelGGL((attn_bwd_small_kernel<32, ATTN_GW, true>), grid, block, 0, s, p, a->num_windows);
+            else hipLaunchKernelGGL((attn_bwd_small_kernel<32, ATTN_GW, false>), grid, block, 0, s, p, a->num_windows);
+            break;
+        default:
+            if (r.variant == 4) GG_BWD(4); else if (r.variant == 10) GG_BWD(10); else if (r.variant == 14) GG_BWD(14); else GG_BWD(16);
+            break;
     }
+#undef GG_BWD
+    attn_dbias_reduce(p.dbias, p.dbias_part, (int)attn_dbias_part_rows(r), p.nh * p.nbias, s);
     GG_LAUNCH_CHECK();
     return 0;
+}
+// include/gg_attn_route.h: the route of any entry, from the function its launcher executes
+extern "C" int gg_attention_route(const GgAttnArgs* a, int entry, int dtype, GgAttnRoute* out) {
+    GG_CHECK(out, "gg_attention_route: null out");
+    switch (entry) {
+        case GG_ATTN_ENTRY_FWD: case GG_ATTN_ENTRY_FWD_F16: case GG_ATTN_ENTRY_BWD: {
+            AttnParams p;
+            AttnForward to;
+            GG_TRY(attn_route(a, entry, p, *out, to));
+            return to.entry < 0 ? 0 : gg_attn_route_flash(a, to.entry, to.dtype, to.rounded_bias, out);
+        }
+        case GG_ATTN_ENTRY_FLASH_FWD: case GG_ATTN_ENTRY_FLASH_BWD: case GG_ATTN_ENTRY_CAUSAL_FWD: case GG_ATTN_ENTRY_CAUSAL_BWD:
+            return gg_attn_route_flash(a, entry, dtype, 0, out);
+        case GG_ATTN_ENTRY_FLASH16_FWD: case GG_ATTN_ENTRY_FLASH16_WIN_FWD: return gg_attn_route_flash16_fwd(a, entry, dtype, out);
+        case GG_ATTN_ENTRY_FLASH16_BWD: case GG_ATTN_ENTRY_FLASH16_WIN_BWD: return gg_attn_route_flash16_bwd(a, entry, dtype, out);
+    }
+    GG_CHECK(false, "gg_attention_route: unknown entry %d", entry);
+    return -1;
 }

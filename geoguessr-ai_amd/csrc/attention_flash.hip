@@ -20,6 +20,7 @@
 #include "../../include/gg.h"
 #include "../../include/gg_clip_text.h"
 #include "../../include/gg_clip_text_train.h"
+#include "attention_route.h"
 
 namespace {
 
@@ -994,14 +995,6 @@ __global__ __launch_bounds__(NT ? (NT < 4 ? 256 : 64 * NT) : 1024) void flash_bw
 #include "attention_split.h"
 #include "attention_split64.h"
 
-__global__ void flash_dbias_final_kernel(const float* __restrict__ rows, int nrows, int W, float* __restrict__ dbias) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= W) return;
-    double s = 0.0;
-    for (int r = 0; r < nrows; ++r) s += (double)rows[(int64_t)r * W + i];
-    dbias[i] += (float)s;
-}
-
 int flash_fill(FlashParams& p, const GgAttnArgs* a, int dtype, const char* who, bool takes_map = false) {
     GG_CHECK(a && a->qkv, "%s: null qkv", who);
     GG_CHECK(dtype >= 0 && dtype <= 3, "%s: dtype must be 0 (bf16), 1 (f32), 2 (fp16, forward only) or 3 (f32 storage, split-bf16 products)", who);
@@ -1016,9 +1009,7 @@ int flash_fill(FlashParams& p, const GgAttnArgs* a, int dtype, const char* who, 
              "%s: qkv offsets/strides must be multiples of 4 elements", who);
     GG_CHECK(((uintptr_t)a->qkv & 15) == 0, "%s: qkv must be 16-byte aligned", who);
     if (a->window_size > 0) {
-        GG_CHECK(a->window_size * a->window_size == a->tokens_per_window, "%s: window_size^2 != tokens_per_window", who);
-        GG_CHECK(a->map_h % a->window_size == 0 && a->map_w % a->window_size == 0, "%s: map not divisible by window", who);
-        GG_CHECK(a->num_windows % ((a->map_h / a->window_size) * (a->map_w / a->window_size)) == 0, "%s: window count", who);
+        GG_TRY(attn_check_windows(a, false, who));
         GG_CHECK(a->window_size <= 32, "%s: window_size > 32 unsupported (bias table of at most 1024 entries)", who);
     }
     if (a->bias_table || a->dbias) GG_CHECK(a->window_size > 0, "%s: the relative-position bias needs a window geometry", who);
@@ -1037,7 +1028,7 @@ int flash_fill(FlashParams& p, const GgAttnArgs* a, int dtype, const char* who, 
     p.nbpad = (int)gg_align(std::max(4, (2 * a->window_size - 1) * (2 * a->window_size - 1)), 4);      // expanded (signed-offset) bias table
     p.rcp_ws = p.rcp_w2 = p.rcp_img = p.rcp_nwx = 0;
     p.neg_inv_scale = -1.0f / p.scale;
-    p.round_bias = 0;                                     // (set by gg_attention_flash_bwd_impl when the forward was attention.hip's)
+    p.round_bias = 0;                                     // (set by flash_route when the forward was attention.hip's)
     p.window_map = nullptr; p.nwin_dev = nullptr;         // (likewise, for the one kernel that takes a window map)
     GG_CHECK((a->window_map != nullptr) == (a->num_windows_dev != nullptr), "%s: window_map and num_windows_dev go together", who);
     GG_CHECK(takes_map || !a->window_map, "%s: window_map is a form of gg_attention_flash_bwd only", who);
@@ -1046,172 +1037,239 @@ int flash_fill(FlashParams& p, const GgAttnArgs* a, int dtype, const char* who, 
         p.rcp_img = magic(p.nWx * p.nWy); p.rcp_nwx = magic(p.nWx);
         GG_CHECK((int64_t)a->num_windows * (p.nWx * p.nWy) < ((int64_t)1 << 31), "%s: too many windows", who);
     }
-    if (p.ws > 0) {
-        const int w2 = 2 * p.ws - 1;
-        p.rcp_ws = (uint32_t)(((1u << 20) + p.ws - 1) / p.ws);
-        p.rcp_w2 = (uint32_t)(((1u << 20) + w2 - 1) / w2);
-        for (int t = 0; t < p.npad + 64; ++t) GG_CHECK((int)(((uint32_t)t * p.rcp_ws) >> 20) == t / p.ws, "%s: reciprocal division fails at %d / %d", who, t, p.ws);
-        for (int t = 0; t < w2 * w2; ++t) GG_CHECK((int)(((uint32_t)t * p.rcp_w2) >> 20) == t / w2, "%s: reciprocal division fails at %d / %d", who, t, w2);
-    }
+    if (p.ws > 0) GG_TRY(attn_window_reciprocals(p.ws, p.npad + 64, p.rcp_ws, p.rcp_w2, who));
     return 0;
 }
 // dynamic LDS of the forward / dQ kernels (two operand images, bias table, coordinates) and of the dK/dV kernel (+ bias-gradient bins,
 // lse, delta) for R staged rows
 size_t flash_lds_fwd(const FlashParams& p, int D, int R) { return ((size_t)2 * R * (D + 4) + p.nbpad + R) * 4; }
-// resident forward with a cooperative tail strip (strips = 4 n + 1: one wave fewer than strips): partial (O, max, sum) of every key sub-tile for the strip's live queries
-bool flash_fwd_tail(const FlashParams& p) {
-    static const bool notail = gg_dev_env("GG_ATTN_FWD_NO_TAIL") != nullptr;
-    const int strips = p.npad / 16;
-    return !notail && strips > 4 && strips <= 17 && strips % 4 == 1;
-}
+// resident forward with a cooperative tail strip: partial (O, max, sum) of every key sub-tile for the strip's live queries
 size_t flash_lds_fwd_tail(const FlashParams& p, int D) { const int strips = p.npad / 16, nlive = p.N - 16 * (strips - 1); return (size_t)strips * nlive * (D + 2) * 4; }
 size_t flash_lds_dkv(const FlashParams& p, int D, int R, bool dbias) { return ((size_t)2 * R * (D + 4) + p.nbpad * (dbias ? 2 : 1) + 3 * R) * 4; }
 // single-pass backward: three window images, bias table (+ bins), row scalars, one 16 x 20 slot per wave
 size_t flash_lds_fused(const FlashParams& p, int D, bool dbias) { return ((size_t)3 * p.npad * (D + 4) + p.nbpad * (dbias ? 2 : 1) + 3 * p.npad + 2 * (p.npad / 16) * 320) * 4; }
-// owner waves of the single-pass kernel: one per key strip, or -- when that would leave one SIMD with an extra wave (strips = 4 n + 1, e.g. the 13 strips
-// of a 14 x 14 window) -- one fewer, the last strip then being the cooperative tail
-int flash_fused_waves(const FlashParams& p, int D) {
-    static const bool notail = gg_dev_env("GG_ATTN_FUSED_NO_TAIL") != nullptr;
-    const int strips = p.npad / 16;
-    return (!notail && strips > 4 && strips % 4 == 1 && strips - 1 >= 2 * (D / 16)) ? strips - 1 : strips;
+// the single-pass backward holds the window: at most 256 padded tokens and one CU's LDS (flash_route's test, and gg_attention_flash_single_pass's answer)
+bool flash_fused_ok(const FlashParams& p, int D, bool dbias) { return !attn_switches().no_fused_bwd && p.npad <= 256 && flash_lds_fused(p, D, dbias) <= 160 * 1024; }
+// partial dbias rows of the two-pass backward: one per 64-key tile of every window -- the most of any flash route (the single-pass kernels write one per window)
+int64_t flash_stream_part_rows(int64_t num_windows, int tokens_per_window) { return num_windows * gg_cdiv(tokens_per_window, 64); }
+
+// Which kernels gg_attention_flash_fwd, gg_attention_flash_bwd (gg_attention_flash_bwd_impl) and the two causal entries (`entry`) launch: the ONE place of this
+// file that decides it, after the entry's own argument checks and flash_fill.  The launchers execute the route this fills, gg_attention_route reports it.
+//
+// Forward.  dtype 3: the split-product kernel of attention_split64.h at every length.  fp32 storage, head dim 32, windows of 4 / 9 / 13 strips (7 x 7, 12 x 12,
+// 14 x 14): the products run as split-bf16 MFMAs (attention_split.h).  (The same kernel instantiated for bf16 storage -- one plane -- measured 403 us per
+// 14 x 14 layer with a wave per strip and 497 us with two strips per wave, against 301 us of attention.hip's attn_fwd_kernel: the bf16 forward stays there.)
+// Else flash_fwd_kernel, in its resident form (RES) while two workgroups still fit a CU's 160 KB (single-tile windows too: same staging, descriptor
+// addressing).  That bound is the one of two whole-window images plus three row scalars -- flash_lds_dkv without gradient bins, a little above the forward's
+// own need -- and is kept at that value: it decides which forward kernel a window takes.  The resident form has a cooperative tail strip where strips = 4 n + 1
+// (one wave fewer than strips).
+//
+// Backward.  dtype 3: two passes at every length (dQ; dK, dV), each recomputing P from lse: no dS hand-off (ds_scratch is not read), no atomics.  Head dim 32,
+// 4 / 9 / 13 strips: the single-pass backward of attention_split.h (fp32 storage: split-bf16 products; bf16 storage: plain bf16 products), the one kernel that
+// takes a window map.  Else, where flash_fused_ok, the single-pass kernel (no dS scratch, no second phase); its owner waves are one per key strip, or -- when
+// that would leave one SIMD with an extra wave (strips = 4 n + 1, e.g. the 13 strips of a 14 x 14 window) -- one fewer, the last strip then being the
+// cooperative tail.  Else the two-pass forms, streaming only: the routes of windows beyond 256 padded tokens (head dim 64: beyond 160), and of every window
+// under GG_ATTN_NO_FUSED_BWD; with a dS scratch the dK/dV pass runs first and hands dS to the one-product dQ pass, without one both passes recompute P from lse.
+// No resident two-kernel backward exists (one workgroup per (window, head) with whole-window images in LDS, as the forward has), because no shape
+// could reach one behind the single-pass test.  Such a form needs flash_lds_dkv(p, D, npad, dbias) <= 64 KB.  flash_lds_fused is
+// flash_lds_dkv + 4 npad (D + 4) + 160 npad bytes; the first addend is at most half of flash_lds_dkv (<= 32 KB); flash_lds_dkv <= 64 KB forces
+// npad <= 65536 / (4 (2 * 36 + 3)) = 218, so the last is at most 35 KB: at most 131 KB < 160 KB in all, with npad <= 218 < 256 -- the window is
+// single-pass.  (A single 64-token tile with a dS scratch, the other case the resident form once served: ws <= 8, flash_lds_fused about 65 KB.)
+//
+// forward_rounded_bias: the forward that produced `lse` was gg_attention_fwd's bf16 kernel, which adds the bias as bf16(bias / scale) from the expanded table: P is
+// recomputed with that value.  Only gg_attention_bwd passes 1 (attention.hip); the public entry point pairs with gg_attention_flash_fwd, which reads the compact
+// f32 table -- a caller who fills both `bias` and `bias_table` and calls the flash pair directly gets the same bias in both passes.
+//
+// Causal entries (CLIP text tower; include/gg_clip_text.h, gg_clip_text_train.h).  f32 storage (dtype 1 and 3): the split-product kernels of dtype 3; bf16
+// storage: the streaming online-softmax forward and the single-pass backward (at most 80 padded tokens: five key strips, one wave each).  Everything else is
+// refused before flash_fill's own checks can pass a shape these instantiations do not cover.  Neither backward reads ds_scratch, neither uses an atomic.
+int flash_route(const GgAttnArgs* a, int entry, int dtype, int forward_rounded_bias, FlashParams& p, GgAttnRoute& r) {
+    const AttnSwitches& sw = attn_switches();
+    const bool causal = entry == GG_ATTN_ENTRY_CAUSAL_FWD || entry == GG_ATTN_ENTRY_CAUSAL_BWD;
+    const bool bwd = entry == GG_ATTN_ENTRY_FLASH_BWD || entry == GG_ATTN_ENTRY_CAUSAL_BWD;
+    const char* who = causal ? (bwd ? "gg_attention_causal_bwd" : "gg_attention_causal_fwd") : (bwd ? "gg_attention_flash_bwd" : "gg_attention_flash_fwd");
+    r = GgAttnRoute{};
+    if (causal) {
+        GG_CHECK(a, "%s: null args", who);
+        GG_CHECK(dtype == 0 || dtype == 1 || dtype == 3, "%s: dtype must be 0 (bf16), 1 (f32) or 3 (f32, split products); got %d", who, dtype);
+        GG_CHECK(a->head_dim == 64 && a->window_size == 0 && !a->bias && !a->bias_table && !a->dbias,
+                 "%s: head dim 64, linear tokens, no bias (got head_dim %d, window_size %d)", who, a->head_dim, a->window_size);
+        GG_CHECK(a->tokens_per_window <= GG_CLIP_TEXT_MAX_POSITIONS, "%s: %d tokens exceed the position table (%d)", who, a->tokens_per_window, GG_CLIP_TEXT_MAX_POSITIONS);
+        GG_TRY(flash_fill(p, a, dtype == 0 ? 0 : 3, who));
+        if (bwd) {
+            GG_CHECK(a->dout && a->dqkv && (a->lddo & 3) == 0 && ((uintptr_t)a->dout & 15) == 0 && ((uintptr_t)a->dqkv & 15) == 0 && a->lddo >= (int64_t)a->num_heads * 64,
+                     "gg_attention_causal_bwd: bad dout/dqkv");
+            GG_CHECK(a->lse && a->out && (a->ldo & 3) == 0 && ((uintptr_t)a->out & 15) == 0 && a->ldo >= (int64_t)a->num_heads * 64, "gg_attention_causal_bwd: needs the forward's lse and out");
+        } else {
+            GG_CHECK(a->out && (a->ldo & 3) == 0 && ((uintptr_t)a->out & 15) == 0 && a->ldo >= (int64_t)a->num_heads * 64, "gg_attention_causal_fwd: bad out");
+        }
+        GG_CHECK(a->ld >= 64 && a->head_stride >= 0, "%s: bad qkv pitch", who);
+    } else if (bwd) {
+        GG_CHECK(dtype != 2, "gg_attention_flash_bwd: fp16 storage is inference-only");
+        GG_TRY(flash_fill(p, a, dtype, who, true));
+        p.round_bias = (forward_rounded_bias && dtype == 0 && a->bias != nullptr) ? 1 : 0;
+        GG_CHECK(a->dout && a->dqkv && (a->lddo & 3) == 0 && ((uintptr_t)a->dout & 15) == 0 && ((uintptr_t)a->dqkv & 15) == 0,
+                 "gg_attention_flash_bwd: bad dout/dqkv");
+        GG_CHECK(a->lse && a->out && (a->ldo & 3) == 0, "gg_attention_flash_bwd: needs the forward's lse and out");
+    } else {
+        GG_TRY(flash_fill(p, a, dtype, who));
+        GG_CHECK(a->out && (a->ldo & 3) == 0 && ((uintptr_t)a->out & 15) == 0, "gg_attention_flash_fwd: bad out");
+    }
+    const int D = a->head_dim, strips = p.npad / 16;
+    const int64_t wh = (int64_t)a->num_windows * a->num_heads, tiles = wh * p.ntile;
+    const bool split_strips = D == 32 && !sw.no_split && (strips == 4 || strips == 9 || strips == 13);
+    r.rounded_bias = p.round_bias;
+    if (dtype == 3 || (causal && dtype == 1)) {
+        r.kernel = bwd ? GG_ATTN_KERNEL_FLASH64_BWD_SPLIT : GG_ATTN_KERNEL_FLASH64_FWD_SPLIT;
+        attn_route_pass(r, tiles, 256, sp64_lds(3, false));
+        if (bwd) attn_route_pass(r, tiles, 256, sp64_lds(3, true));
+        return 0;
+    }
+    if (causal && !bwd) {
+        r.kernel = GG_ATTN_KERNEL_FLASH_FWD_STREAM;
+        attn_route_pass(r, tiles, 256, flash_lds_fwd(p, 64, 64));
+        return 0;
+    }
+    if (causal) {
+        static_assert(GG_CLIP_TEXT_MAX_POSITIONS <= 256, "the single-pass kernel holds a sequence of at most 256 tokens");
+        const size_t lds = flash_lds_fused(p, 64, false);
+        GG_CHECK(lds <= 160 * 1024, "gg_attention_causal_bwd: %zu bytes of LDS", lds);
+        r.kernel = GG_ATTN_KERNEL_FLASH_BWD_FUSED;
+        attn_route_pass(r, wh, 64 * strips, lds);
+        return 0;
+    }
+    if (!bwd) {
+        if (dtype == 1 && split_strips) {
+            r.kernel = GG_ATTN_KERNEL_FLASH_FWD_SPLIT; r.variant = strips;
+            attn_route_pass(r, wh, 64 * strips, sp_lds_fwd(p, 3));
+            return 0;
+        }
+        const bool res = !sw.no_resident && flash_lds_dkv(p, D, p.npad, false) <= 64 * 1024;
+        const bool tail = res && !sw.fwd_no_tail && strips > 4 && strips <= 17 && strips % 4 == 1;
+        r.kernel = res ? GG_ATTN_KERNEL_FLASH_FWD_RESIDENT : GG_ATTN_KERNEL_FLASH_FWD_STREAM; r.variant = tail;
+        attn_route_pass(r, res ? wh : tiles, res ? 64 * (tail ? strips - 1 : std::min(16, strips)) : 256,
+                        flash_lds_fwd(p, D, res ? p.npad : 64) + (tail ? flash_lds_fwd_tail(p, D) : 0));
+        return 0;
+    }
+    const bool dbias = p.dbias != nullptr;
+    const int npl = dtype == 1 ? 3 : 1;
+    int64_t part_rows = a->num_windows;
+    if (split_strips && sp_lds_bwd(p, dbias, npl) <= 160 * 1024) {
+        GG_CHECK(dtype == 1 || ((a->ld & 7) == 0 && (a->ldo & 7) == 0 && (a->lddo & 7) == 0 && ((a->q_off | a->k_off | a->v_off | a->head_stride) & 7) == 0),
+                 "gg_attention_flash_bwd: bf16 rows must be 16-byte aligned");
+        if (a->window_map) {
+            GG_CHECK(dtype == 1 && !p.dbias, "gg_attention_flash_bwd: window_map is f32 storage without a bias gradient");
+            p.window_map = a->window_map; p.nwin_dev = a->num_windows_dev;
+        }
+        r.kernel = GG_ATTN_KERNEL_FLASH_BWD_SPLIT; r.variant = strips;
+        attn_route_pass(r, wh, 64 * ((strips + 1) / 2), sp_lds_bwd(p, dbias, npl));
+    } else {
+        GG_CHECK(a->window_map == nullptr, "gg_attention_flash_bwd: window_map needs the single-pass split kernel (f32 storage, head dim 32, 7 x 7 / 12 x 12 / 14 x 14 windows)");
+        if (flash_fused_ok(p, D, dbias)) {
+            const int waves = (!sw.fused_no_tail && strips > 4 && strips % 4 == 1 && strips - 1 >= 2 * (D / 16)) ? strips - 1 : strips;
+            r.kernel = GG_ATTN_KERNEL_FLASH_BWD_FUSED; r.variant = strips == 13 ? 13 : strips == 4 ? 4 : 0;
+            attn_route_pass(r, wh, 64 * waves, flash_lds_fused(p, D, dbias));
+        } else {
+            const size_t lds_q = flash_lds_fwd(p, D, 64), lds_kv = flash_lds_dkv(p, D, 64, dbias), lds_k = (size_t)64 * (D + 4) * 4;
+            r.reads_ds_scratch = p.ds_scratch != nullptr;
+            r.kernel = r.reads_ds_scratch ? GG_ATTN_KERNEL_FLASH_BWD_STREAM_DS : GG_ATTN_KERNEL_FLASH_BWD_STREAM;
+            if (!r.reads_ds_scratch) attn_route_pass(r, tiles, 256, lds_q);
+            attn_route_pass(r, tiles, 256, lds_kv);
+            if (r.reads_ds_scratch) attn_route_pass(r, tiles, 256, lds_k);
+            part_rows = flash_stream_part_rows(a->num_windows, p.N);
+        }
+    }
+    if (dbias) r.dbias_rows = attn_dbias_scratch_rows(part_rows);
+    return 0;
 }
-bool flash_fused_ok(const FlashParams& p, int D, bool dbias) {
-    static const bool off = gg_dev_env("GG_ATTN_NO_FUSED_BWD") != nullptr;
-    return !off && p.npad <= 256 && flash_lds_fused(p, D, dbias) <= 160 * 1024;
-}
-// the forward's resident form (flash_fwd_kernel<.., RES = true>): two workgroups still fit a CU's 160 KB (single-tile windows too: same staging, descriptor
-// addressing).  The bound is the one of two whole-window images plus three row scalars -- flash_lds_dkv without gradient bins, a little above the forward's
-// own need -- and is kept at that value: it decides which forward kernel a window takes.  No backward kernel has a resident form.
-bool flash_fwd_resident(const FlashParams& p, int D) {
-    static const bool off = gg_dev_env("GG_ATTN_FLASH_NO_RES") != nullptr;
-    return !off && flash_lds_dkv(p, D, p.npad, false) <= 64 * 1024;
-}
-// every partial row of the bias gradient (one per workgroup that binned it) summed in a fixed order, then added to dbias
-void flash_dbias_reduce(const FlashParams& p, int part_rows, hipStream_t s) {
-    if (!p.dbias || !p.dbias_part) return;
-    const int Wd = p.nh * p.ws * p.ws;
-    const float* rows; int nrows;
-    gg_reduce_rows(p.dbias_part, part_rows, Wd, s, &rows, &nrows);
-    hipLaunchKernelGGL(flash_dbias_final_kernel, dim3((unsigned)gg_cdiv(Wd, 256)), dim3(256), 0, s, rows, nrows, Wd, p.dbias);
-}
-// The two-pass (streaming) backward of one storage type and head dim: with a dS scratch the dK/dV pass runs first and hands dS to the one-product dQ pass,
-// without one both passes recompute P from lse.  Grid: one workgroup per (window, head, 64-row tile).
+// The two-pass (streaming) backward of one storage type and head dim.  Grid: one workgroup per (window, head, 64-row tile).
 template <typename T, int D>
-void flash_bwd_streaming(const FlashParams& p, dim3 grid, hipStream_t s) {
-    const dim3 block(256);
-    const size_t lds_q = flash_lds_fwd(p, D, 64), lds_kv = flash_lds_dkv(p, D, 64, p.dbias != nullptr), lds_k = (size_t)64 * (D + 4) * 4;
-    if (p.ds_scratch) {
-        if (p.dbias) hipLaunchKernelGGL((flash_bwd_dkv_kernel<T, D, true, true>), grid, block, lds_kv, s, p);
-        else hipLaunchKernelGGL((flash_bwd_dkv_kernel<T, D, false, true>), grid, block, lds_kv, s, p);
-        hipLaunchKernelGGL((flash_bwd_dq_ds_kernel<T, D>), grid, block, lds_k, s, p);
+void flash_bwd_streaming(const FlashParams& p, const GgAttnRoute& r, hipStream_t s) {
+    const dim3 grid(r.pass[0].grid), block(r.pass[0].block);
+    if (r.kernel == GG_ATTN_KERNEL_FLASH_BWD_STREAM_DS) {
+        if (p.dbias) hipLaunchKernelGGL((flash_bwd_dkv_kernel<T, D, true, true>), grid, block, r.pass[0].lds, s, p);
+        else hipLaunchKernelGGL((flash_bwd_dkv_kernel<T, D, false, true>), grid, block, r.pass[0].lds, s, p);
+        hipLaunchKernelGGL((flash_bwd_dq_ds_kernel<T, D>), grid, block, r.pass[1].lds, s, p);
         return;
     }
-    hipLaunchKernelGGL((flash_bwd_dq_kernel<T, D>), grid, block, lds_q, s, p);
-    if (p.dbias) hipLaunchKernelGGL((flash_bwd_dkv_kernel<T, D, true>), grid, block, lds_kv, s, p);
-    else hipLaunchKernelGGL((flash_bwd_dkv_kernel<T, D, false>), grid, block, lds_kv, s, p);
+    hipLaunchKernelGGL((flash_bwd_dq_kernel<T, D>), grid, block, r.pass[0].lds, s, p);
+    if (p.dbias) hipLaunchKernelGGL((flash_bwd_dkv_kernel<T, D, true>), grid, block, r.pass[1].lds, s, p);
+    else hipLaunchKernelGGL((flash_bwd_dkv_kernel<T, D, false>), grid, block, r.pass[1].lds, s, p);
 }
 
 }  // namespace
 
+int gg_attn_route_flash(const GgAttnArgs* a, int entry, int dtype, int forward_rounded_bias, GgAttnRoute* out) {
+    FlashParams p;
+    return flash_route(a, entry, dtype, forward_rounded_bias, p, *out);
+}
 extern "C" int gg_attention_flash_fwd(const GgAttnArgs* a, int dtype, void* stream) {
     FlashParams p;
-    GG_TRY(flash_fill(p, a, dtype, "gg_attention_flash_fwd"));
-    GG_CHECK(a->out && (a->ldo & 3) == 0 && ((uintptr_t)a->out & 15) == 0, "gg_attention_flash_fwd: bad out");
-    // fp32 storage, head dim 32, windows of 4 / 9 / 13 tiles (7 x 7, 12 x 12, 14 x 14): the products run as split-bf16 MFMAs (attention_split.h).  (The same
-    // kernel instantiated for bf16 storage -- one plane -- measured 403 us per 14 x 14 layer with a wave per strip and 497 us with two strips per wave, against
-    // 301 us of attention.hip's attn_fwd_kernel: the bf16 forward stays there.)
-    if (dtype == 3) {
-        const size_t lds = sp64_lds(3, false);
-        GG_PROF(GG_CAT_ATTN, 4.0 * a->num_windows * a->num_heads * (double)p.N * p.N * a->head_dim, 16.0 * a->num_windows * a->num_heads * (double)p.N * a->head_dim, stream);
-        hipLaunchKernelGGL((flash64_split_q_kernel<3, false>), dim3((unsigned)(a->num_windows * a->num_heads * p.ntile)), dim3(256), lds, (hipStream_t)stream, p);
-        GG_LAUNCH_CHECK();
-        return 0;
-    }
-    static const bool nosplit = gg_dev_env("GG_ATTN_NO_SPLIT") != nullptr;
-    const int nt16 = p.npad / 16;
-    if (dtype == 1 && a->head_dim == 32 && !nosplit && (nt16 == 4 || nt16 == 9 || nt16 == 13)) {
-        const size_t lds = sp_lds_fwd(p, 3);
-        GG_PROF(GG_CAT_ATTN, 4.0 * a->num_windows * a->num_heads * (double)p.N * p.N * a->head_dim, 16.0 * a->num_windows * a->num_heads * (double)p.N * a->head_dim, stream);
-        void (*kern)(FlashParams) = nt16 == 13 ? flash_fwd_split_kernel<float, 3, 13> : nt16 == 9 ? flash_fwd_split_kernel<float, 3, 9> : flash_fwd_split_kernel<float, 3, 4>;
-        if (lds > 64 * 1024) GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(kern)));
-        hipLaunchKernelGGL(kern, dim3((unsigned)(a->num_windows * a->num_heads)), dim3(64 * nt16), lds, (hipStream_t)stream, p);
-        GG_LAUNCH_CHECK();
-        return 0;
-    }
-    const bool res = flash_fwd_resident(p, a->head_dim);
-    const bool ftail = res && flash_fwd_tail(p);
-    const dim3 grid((unsigned)(a->num_windows * a->num_heads * (res ? 1 : p.ntile))), block(res ? 64 * (ftail ? p.npad / 16 - 1 : std::min(16, p.npad / 16)) : 256);
-    const size_t lds = flash_lds_fwd(p, a->head_dim, res ? p.npad : 64) + (ftail ? flash_lds_fwd_tail(p, a->head_dim) : 0);
+    GgAttnRoute r;
+    GG_TRY(flash_route(a, GG_ATTN_ENTRY_FLASH_FWD, dtype, 0, p, r));
+    const dim3 grid(r.pass[0].grid), block(r.pass[0].block);
+    const size_t lds = r.pass[0].lds;
     hipStream_t s = (hipStream_t)stream;
-    const double es = dtype == 1 ? 4.0 : 2.0;
-    GG_PROF(GG_CAT_ATTN, 4.0 * a->num_windows * a->num_heads * (double)p.N * p.N * a->head_dim,
-            4.0 * es * a->num_windows * a->num_heads * (double)p.N * a->head_dim, stream);
+    const double es = (dtype == 1 || dtype == 3) ? 4.0 : 2.0;
+    GG_PROF(GG_CAT_ATTN, 4.0 * a->num_windows * a->num_heads * (double)p.N * p.N * a->head_dim, 4.0 * es * a->num_windows * a->num_heads * (double)p.N * a->head_dim, stream);
 #define GG_FL_FWD(T_, D_)                                                                                     \
     do {                                                                                                      \
         if (res && lds > 64 * 1024) GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(flash_fwd_kernel<T_, D_, true>)));      \
         if (res) hipLaunchKernelGGL((flash_fwd_kernel<T_, D_, true>), grid, block, lds, s, p);                \
         else hipLaunchKernelGGL((flash_fwd_kernel<T_, D_, false>), grid, block, lds, s, p);                   \
     } while (0)
-    if (dtype == 1) { if (a->head_dim == 32) GG_FL_FWD(float, 32); else GG_FL_FWD(float, 64); }
-    else if (dtype == 2) { if (a->head_dim == 32) GG_FL_FWD(f16, 32); else GG_FL_FWD(f16, 64); }
-    else { if (a->head_dim == 32) GG_FL_FWD(bf16, 32); else GG_FL_FWD(bf16, 64); }
+    switch (r.kernel) {
+        case GG_ATTN_KERNEL_FLASH64_FWD_SPLIT: hipLaunchKernelGGL((flash64_split_q_kernel<3, false>), grid, block, lds, s, p); break;
+        case GG_ATTN_KERNEL_FLASH_FWD_SPLIT: {
+            void (*kern)(FlashParams) = r.variant == 13 ? flash_fwd_split_kernel<float, 3, 13> : r.variant == 9 ? flash_fwd_split_kernel<float, 3, 9> : flash_fwd_split_kernel<float, 3, 4>;
+            if (lds > 64 * 1024) GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(kern)));
+            hipLaunchKernelGGL(kern, grid, block, lds, s, p);
+        } break;
+        default: {
+            const bool res = r.kernel == GG_ATTN_KERNEL_FLASH_FWD_RESIDENT;
+            if (dtype == 1) { if (a->head_dim == 32) GG_FL_FWD(float, 32); else GG_FL_FWD(float, 64); }
+            else if (dtype == 2) { if (a->head_dim == 32) GG_FL_FWD(f16, 32); else GG_FL_FWD(f16, 64); }
+            else { if (a->head_dim == 32) GG_FL_FWD(bf16, 32); else GG_FL_FWD(bf16, 64); }
+        } break;
+    }
 #undef GG_FL_FWD
     GG_LAUNCH_CHECK();
     return 0;
 }
-// Causal forward (CLIP text tower; include/gg_clip_text.h).  f32 storage (dtype 1 and 3): the split-product kernel of dtype 3; bf16 storage: the streaming
-// online-softmax forward.  Everything else is refused before flash_fill's own checks can pass a shape these two instantiations do not cover.
 extern "C" int gg_attention_causal_fwd(const GgAttnArgs* a, int dtype, void* stream) {
-    GG_CHECK(a, "gg_attention_causal_fwd: null args");
-    GG_CHECK(dtype == 0 || dtype == 1 || dtype == 3, "gg_attention_causal_fwd: dtype must be 0 (bf16), 1 (f32) or 3 (f32, split products); got %d", dtype);
-    GG_CHECK(a->head_dim == 64 && a->window_size == 0 && !a->bias && !a->bias_table && !a->dbias,
-             "gg_attention_causal_fwd: head dim 64, linear tokens, no bias (got head_dim %d, window_size %d)", a->head_dim, a->window_size);
-    GG_CHECK(a->tokens_per_window <= GG_CLIP_TEXT_MAX_POSITIONS, "gg_attention_causal_fwd: %d tokens exceed the position table (%d)", a->tokens_per_window,
-             GG_CLIP_TEXT_MAX_POSITIONS);
     FlashParams p;
-    GG_TRY(flash_fill(p, a, dtype == 0 ? 0 : 3, "gg_attention_causal_fwd"));
-    GG_CHECK(a->out && (a->ldo & 3) == 0 && ((uintptr_t)a->out & 15) == 0 && a->ldo >= (int64_t)a->num_heads * 64, "gg_attention_causal_fwd: bad out");
-    GG_CHECK(a->ld >= 64 && a->head_stride >= 0, "gg_attention_causal_fwd: bad qkv pitch");
-    const dim3 grid((unsigned)(a->num_windows * a->num_heads * p.ntile));
+    GgAttnRoute r;
+    GG_TRY(flash_route(a, GG_ATTN_ENTRY_CAUSAL_FWD, dtype, 0, p, r));
+    const dim3 grid(r.pass[0].grid), block(r.pass[0].block);
     // (declared work: the lower triangle, half of the 4 N^2 D flops of the full forward)
     GG_PROF(GG_CAT_ATTN, 2.0 * a->num_windows * a->num_heads * (double)p.N * p.N * 64, (dtype == 0 ? 8.0 : 16.0) * a->num_windows * a->num_heads * (double)p.N * 64, stream);
-    if (dtype == 0) hipLaunchKernelGGL((flash_fwd_kernel<bf16, 64, false, true>), grid, dim3(256), flash_lds_fwd(p, 64, 64), (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((flash64_split_q_kernel<3, false, true>), grid, dim3(256), sp64_lds(3, false), (hipStream_t)stream, p);
+    switch (r.kernel) {
+        case GG_ATTN_KERNEL_FLASH_FWD_STREAM: hipLaunchKernelGGL((flash_fwd_kernel<bf16, 64, false, true>), grid, block, r.pass[0].lds, (hipStream_t)stream, p); break;
+        default: hipLaunchKernelGGL((flash64_split_q_kernel<3, false, true>), grid, block, r.pass[0].lds, (hipStream_t)stream, p); break;
+    }
     GG_LAUNCH_CHECK();
     return 0;
 }
-// Causal backward (include/gg_clip_text_train.h): the backward of gg_attention_causal_fwd on the same geometry.  f32 storage (dtype 1 and 3): the two split-product
-// passes of dtype 3 (dQ; dK, dV), each recomputing P from lse; bf16 storage: the single-pass kernel (at most 80 padded tokens: five key strips, one wave each).
-// Neither reads ds_scratch, neither uses an atomic: two runs give the same bits.  Every refusal comes before the first launch.
+// Two runs give the same bits.  Every refusal comes before the first launch.
 extern "C" int gg_attention_causal_bwd(const GgAttnArgs* a, int dtype, void* stream) {
-    GG_CHECK(a, "gg_attention_causal_bwd: null args");
-    GG_CHECK(dtype == 0 || dtype == 1 || dtype == 3, "gg_attention_causal_bwd: dtype must be 0 (bf16), 1 (f32) or 3 (f32, split products); got %d", dtype);
-    GG_CHECK(a->head_dim == 64 && a->window_size == 0 && !a->bias && !a->bias_table && !a->dbias,
-             "gg_attention_causal_bwd: head dim 64, linear tokens, no bias (got head_dim %d, window_size %d)", a->head_dim, a->window_size);
-    GG_CHECK(a->tokens_per_window <= GG_CLIP_TEXT_MAX_POSITIONS, "gg_attention_causal_bwd: %d tokens exceed the position table (%d)", a->tokens_per_window,
-             GG_CLIP_TEXT_MAX_POSITIONS);
     FlashParams p;
-    GG_TRY(flash_fill(p, a, dtype == 0 ? 0 : 3, "gg_attention_causal_bwd"));
-    GG_CHECK(a->dout && a->dqkv && (a->lddo & 3) == 0 && ((uintptr_t)a->dout & 15) == 0 && ((uintptr_t)a->dqkv & 15) == 0 && a->lddo >= (int64_t)a->num_heads * 64,
-             "gg_attention_causal_bwd: bad dout/dqkv");
-    GG_CHECK(a->lse && a->out && (a->ldo & 3) == 0 && ((uintptr_t)a->out & 15) == 0 && a->ldo >= (int64_t)a->num_heads * 64, "gg_attention_causal_bwd: needs the forward's lse and out");
-    GG_CHECK(a->ld >= 64 && a->head_stride >= 0, "gg_attention_causal_bwd: bad qkv pitch");
+    GgAttnRoute r;
+    GG_TRY(flash_route(a, GG_ATTN_ENTRY_CAUSAL_BWD, dtype, 0, p, r));
+    const dim3 grid(r.pass[0].grid), block(r.pass[0].block);
     hipStream_t s = (hipStream_t)stream;
     // (declared work: the lower triangle, half of the 10 N^2 D flops of the full backward)
     GG_PROF(GG_CAT_ATTN, 5.0 * a->num_windows * a->num_heads * (double)p.N * p.N * 64, (dtype == 0 ? 16.0 : 32.0) * a->num_windows * a->num_heads * (double)p.N * 64, stream);
-    if (dtype != 0) {
-        const dim3 g3((unsigned)(a->num_windows * a->num_heads * p.ntile));
-        hipLaunchKernelGGL((flash64_split_q_kernel<3, true, true>), g3, dim3(256), sp64_lds(3, false), s, p);
-        hipLaunchKernelGGL((flash64_split_dkv_kernel<3, true>), g3, dim3(256), sp64_lds(3, true), s, p);
-        GG_LAUNCH_CHECK();
-        return 0;
+    switch (r.kernel) {
+        case GG_ATTN_KERNEL_FLASH64_BWD_SPLIT:
+            hipLaunchKernelGGL((flash64_split_q_kernel<3, true, true>), grid, block, r.pass[0].lds, s, p);
+            hipLaunchKernelGGL((flash64_split_dkv_kernel<3, true>), grid, block, r.pass[1].lds, s, p);
+            break;
+        default: {
+            void (*kern)(FlashParams) = flash_bwd_fused_kernel<bf16, 64, false, 0, true>;
+            if (r.pass[0].lds > 64 * 1024) GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(kern)));
+            hipLaunchKernelGGL(kern, grid, block, r.pass[0].lds, s, p);
+        } break;
     }
-    static_assert(GG_CLIP_TEXT_MAX_POSITIONS <= 256, "the single-pass kernel holds a sequence of at most 256 tokens");
-    const size_t lds = flash_lds_fused(p, 64, false);
-    GG_CHECK(lds <= 160 * 1024, "gg_attention_causal_bwd: %zu bytes of LDS", lds);
-    void (*kern)(FlashParams) = flash_bwd_fused_kernel<bf16, 64, false, 0, true>;
-    if (lds > 64 * 1024) GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(kern)));
-    hipLaunchKernelGGL(kern, dim3((unsigned)(a->num_windows * a->num_heads)), dim3(64 * (p.npad / 16)), lds, s, p);
     GG_LAUNCH_CHECK();
     return 0;
 }
@@ -1226,102 +1284,55 @@ extern "C" int64_t gg_attention_flash_ds_scratch_floats(int num_windows, int num
     return (int64_t)num_windows * num_heads * npad * npad;
 }
 extern "C" int64_t gg_attention_flash_dbias_rows(int num_windows, int tokens_per_window) {
-    return (int64_t)num_windows * gg_cdiv(tokens_per_window, 64) + GG_REDUCE_SLICES;
+    return attn_dbias_scratch_rows(flash_stream_part_rows(num_windows, tokens_per_window));
 }
-// forward_rounded_bias: the forward that produced `lse` was gg_attention_fwd's bf16 kernel, which adds the bias as bf16(bias / scale) from the expanded table: P is
-// recomputed with that value.  Only gg_attention_bwd passes 1 (attention.hip); the public entry point pairs with gg_attention_flash_fwd, which reads the compact
-// f32 table -- a caller who fills both `bias` and `bias_table` and calls the flash pair directly gets the same bias in both passes
-int gg_attention_flash_bwd_impl(const GgAttnArgs* a, int dtype, int forward_rounded_bias, void* stream);
 extern "C" int gg_attention_flash_bwd(const GgAttnArgs* a, int dtype, void* stream) { return gg_attention_flash_bwd_impl(a, dtype, 0, stream); }
 int gg_attention_flash_bwd_impl(const GgAttnArgs* a, int dtype, int forward_rounded_bias, void* stream) {
     FlashParams p;
-    GG_CHECK(dtype != 2, "gg_attention_flash_bwd: fp16 storage is inference-only");
-    GG_TRY(flash_fill(p, a, dtype, "gg_attention_flash_bwd", true));
-    p.round_bias = (forward_rounded_bias && dtype == 0 && a->bias != nullptr) ? 1 : 0;
-    bool map_taken = false;
-    GG_CHECK(a->dout && a->dqkv && (a->lddo & 3) == 0 && ((uintptr_t)a->dout & 15) == 0 && ((uintptr_t)a->dqkv & 15) == 0,
-             "gg_attention_flash_bwd: bad dout/dqkv");
-    GG_CHECK(a->lse && a->out && (a->ldo & 3) == 0, "gg_attention_flash_bwd: needs the forward's lse and out");
-    if (dtype == 3) {
-        // two passes at every length (dQ; dK, dV), each recomputing P from lse: no dS hand-off (ds_scratch is not read), no atomics
-        GG_PROF(GG_CAT_ATTN, 10.0 * a->num_windows * a->num_heads * (double)p.N * p.N * a->head_dim, 32.0 * a->num_windows * a->num_heads * (double)p.N * a->head_dim, stream);
-        const dim3 g3((unsigned)(a->num_windows * a->num_heads * p.ntile));
-        hipLaunchKernelGGL((flash64_split_q_kernel<3, true>), g3, dim3(256), sp64_lds(3, false), (hipStream_t)stream, p);
-        hipLaunchKernelGGL((flash64_split_dkv_kernel<3>), g3, dim3(256), sp64_lds(3, true), (hipStream_t)stream, p);
-        GG_LAUNCH_CHECK();
-        return 0;
-    }
+    GgAttnRoute r;
+    GG_TRY(flash_route(a, GG_ATTN_ENTRY_FLASH_BWD, dtype, forward_rounded_bias, p, r));
+    const dim3 grid(r.pass[0].grid), block(r.pass[0].block);
+    const size_t lds = r.pass[0].lds;
     hipStream_t s = (hipStream_t)stream;
-    const double es = dtype ? 4.0 : 2.0;
-    {
-        // head dim 32: the single-pass backward of attention_split.h (fp32 storage: split-bf16 products; bf16 storage: plain bf16 products)
-        static const bool nosplit = gg_dev_env("GG_ATTN_NO_SPLIT") != nullptr;
-        const int nt16 = p.npad / 16;
-        const int npl = dtype == 1 ? 3 : 1;
-        if ((dtype == 1 || dtype == 0) && a->head_dim == 32 && !nosplit && (nt16 == 4 || nt16 == 9 || nt16 == 13) && sp_lds_bwd(p, p.dbias != nullptr, npl) <= 160 * 1024) {
-            GG_CHECK(dtype == 1 || ((a->ld & 7) == 0 && (a->ldo & 7) == 0 && (a->lddo & 7) == 0 && ((a->q_off | a->k_off | a->v_off | a->head_stride) & 7) == 0),
-                     "gg_attention_flash_bwd: bf16 rows must be 16-byte aligned");
-            double nwin = a->num_windows;
-            if (a->window_map) {
-                GG_CHECK(dtype == 1 && !p.dbias, "gg_attention_flash_bwd: window_map is f32 storage without a bias gradient");
-                p.window_map = a->window_map; p.nwin_dev = a->num_windows_dev;
-                map_taken = true;
-                nwin = gg_prof_live_groups(a->num_windows_dev, a->num_windows, stream);      // declared work: the live windows'
-            }
-            GG_PROF(GG_CAT_ATTN, 10.0 * nwin * a->num_heads * (double)p.N * p.N * a->head_dim,
-                    8.0 * es * nwin * a->num_heads * (double)p.N * a->head_dim, stream);
-            const size_t lds = sp_lds_bwd(p, p.dbias != nullptr, npl);
+    // algorithmic: 5 products (S, dP, dV, dK, dQ) = 10 N^2 D, whatever the pass structure recomputes (attention.hip declares the same); a window map: the live windows'
+    const double es = dtype ? 4.0 : 2.0, nwin = p.window_map ? gg_prof_live_groups(a->num_windows_dev, a->num_windows, stream) : (double)a->num_windows;
+    GG_PROF(GG_CAT_ATTN, 10.0 * nwin * a->num_heads * (double)p.N * p.N * a->head_dim, 8.0 * es * nwin * a->num_heads * (double)p.N * a->head_dim, stream);
+    switch (r.kernel) {
+        case GG_ATTN_KERNEL_FLASH64_BWD_SPLIT:
+            hipLaunchKernelGGL((flash64_split_q_kernel<3, true>), grid, block, lds, s, p);
+            hipLaunchKernelGGL((flash64_split_dkv_kernel<3>), grid, block, r.pass[1].lds, s, p);
+            break;
+        case GG_ATTN_KERNEL_FLASH_BWD_SPLIT: {
             void (*kern)(FlashParams);
 #define GG_SP_BWD(T_, N_)                                                                                                                     \
     do {                                                                                                                                      \
-        if (p.dbias) kern = nt16 == 13 ? flash_bwd_split_kernel<T_, N_, true, 13> : nt16 == 9 ? flash_bwd_split_kernel<T_, N_, true, 9> : flash_bwd_split_kernel<T_, N_, true, 4>;      \
-        else kern = nt16 == 13 ? flash_bwd_split_kernel<T_, N_, false, 13> : nt16 == 9 ? flash_bwd_split_kernel<T_, N_, false, 9> : flash_bwd_split_kernel<T_, N_, false, 4>;        \
+        if (p.dbias) kern = r.variant == 13 ? flash_bwd_split_kernel<T_, N_, true, 13> : r.variant == 9 ? flash_bwd_split_kernel<T_, N_, true, 9> : flash_bwd_split_kernel<T_, N_, true, 4>;      \
+        else kern = r.variant == 13 ? flash_bwd_split_kernel<T_, N_, false, 13> : r.variant == 9 ? flash_bwd_split_kernel<T_, N_, false, 9> : flash_bwd_split_kernel<T_, N_, false, 4>;        \
     } while (0)
             if (dtype == 1) GG_SP_BWD(float, 3); else GG_SP_BWD(bf16, 1);
 #undef GG_SP_BWD
             if (lds > 64 * 1024) GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(kern)));
-            hipLaunchKernelGGL(kern, dim3((unsigned)(a->num_windows * a->num_heads)), dim3(64 * ((nt16 + 1) / 2)), lds, s, p);
-            flash_dbias_reduce(p, a->num_windows, s);
-            GG_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    GG_CHECK(a->window_map == nullptr || map_taken, "gg_attention_flash_bwd: window_map needs the single-pass split kernel (f32 storage, head dim 32, 7 x 7 / 12 x 12 / 14 x 14 windows)");
-    if (flash_fused_ok(p, a->head_dim, p.dbias != nullptr)) {
-        // windows of at most 256 tokens: the single-pass kernel (no dS scratch, no second phase)
-        GG_PROF(GG_CAT_ATTN, 10.0 * a->num_windows * a->num_heads * (double)p.N * p.N * a->head_dim,
-                8.0 * es * a->num_windows * a->num_heads * (double)p.N * a->head_dim, stream);
-        const size_t lds = flash_lds_fused(p, a->head_dim, p.dbias != nullptr);
-        const dim3 fgrid((unsigned)(a->num_windows * a->num_heads)), fblock(64 * flash_fused_waves(p, a->head_dim));
+            hipLaunchKernelGGL(kern, grid, block, lds, s, p);
+        } break;
+        case GG_ATTN_KERNEL_FLASH_BWD_FUSED: {
 #define GG_FL_FUSED(T_, D_)                                                                                   \
     do {                                                                                                      \
         void (*kern)(FlashParams);                                                                            \
-        const int nt_ = p.npad / 16;                                                                          \
-        if (p.dbias) kern = nt_ == 13 ? flash_bwd_fused_kernel<T_, D_, true, 13> : nt_ == 4 ? flash_bwd_fused_kernel<T_, D_, true, 4> : flash_bwd_fused_kernel<T_, D_, true, 0>; \
-        else kern = nt_ == 13 ? flash_bwd_fused_kernel<T_, D_, false, 13> : nt_ == 4 ? flash_bwd_fused_kernel<T_, D_, false, 4> : flash_bwd_fused_kernel<T_, D_, false, 0>; \
+        if (p.dbias) kern = r.variant == 13 ? flash_bwd_fused_kernel<T_, D_, true, 13> : r.variant == 4 ? flash_bwd_fused_kernel<T_, D_, true, 4> : flash_bwd_fused_kernel<T_, D_, true, 0>; \
+        else kern = r.variant == 13 ? flash_bwd_fused_kernel<T_, D_, false, 13> : r.variant == 4 ? flash_bwd_fused_kernel<T_, D_, false, 4> : flash_bwd_fused_kernel<T_, D_, false, 0>; \
         if (lds > 64 * 1024) GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(kern)));                  \
-        hipLaunchKernelGGL(kern, fgrid, fblock, lds, s, p);                                                   \
+        hipLaunchKernelGGL(kern, grid, block, lds, s, p);                                                     \
     } while (0)
-        if (dtype == 1) { if (a->head_dim == 32) GG_FL_FUSED(float, 32); else GG_FL_FUSED(float, 64); }
-        else { if (a->head_dim == 32) GG_FL_FUSED(bf16, 32); else GG_FL_FUSED(bf16, 64); }
+            if (dtype == 1) { if (a->head_dim == 32) GG_FL_FUSED(float, 32); else GG_FL_FUSED(float, 64); }
+            else { if (a->head_dim == 32) GG_FL_FUSED(bf16, 32); else GG_FL_FUSED(bf16, 64); }
 #undef GG_FL_FUSED
-        flash_dbias_reduce(p, a->num_windows, s);
-        GG_LAUNCH_CHECK();
-        return 0;
+        } break;
+        default:
+            if (dtype == 1) { if (a->head_dim == 32) flash_bwd_streaming<float, 32>(p, r, s); else flash_bwd_streaming<float, 64>(p, r, s); }
+            else { if (a->head_dim == 32) flash_bwd_streaming<bf16, 32>(p, r, s); else flash_bwd_streaming<bf16, 64>(p, r, s); }
+            break;
     }
-    // The two-pass forms, streaming only: the routes of windows beyond 256 padded tokens (head dim 64: beyond 160), and of every window under GG_ATTN_NO_FUSED_BWD.
-    // No resident two-kernel backward exists (one workgroup per (window, head) with whole-window images in LDS, as the forward has), because no shape
-    // could reach one behind the single-pass test above.  Such a form needs flash_lds_dkv(p, D, npad, dbias) <= 64 KB.  flash_lds_fused is
-    // flash_lds_dkv + 4 npad (D + 4) + 160 npad bytes; the first addend is at most half of flash_lds_dkv (<= 32 KB); flash_lds_dkv <= 64 KB forces
-    // npad <= 65536 / (4 (2 * 36 + 3)) = 218, so the last is at most 35 KB: at most 131 KB < 160 KB in all, with npad <= 218 < 256 -- the window is
-    // single-pass.  (A single 64-token tile with a dS scratch, the other case the resident form once served: ws <= 8, flash_lds_fused about 65 KB.)
-    // algorithmic: 5 products (S, dP, dV, dK, dQ) = 10 N^2 D, whatever the pass structure recomputes (attention.hip declares the same)
-    GG_PROF(GG_CAT_ATTN, 10.0 * a->num_windows * a->num_heads * (double)p.N * p.N * a->head_dim,
-            8.0 * es * a->num_windows * a->num_heads * (double)p.N * a->head_dim, stream);
-    const dim3 grid((unsigned)(a->num_windows * a->num_heads * p.ntile));
-    if (dtype == 1) { if (a->head_dim == 32) flash_bwd_streaming<float, 32>(p, grid, s); else flash_bwd_streaming<float, 64>(p, grid, s); }
-    else { if (a->head_dim == 32) flash_bwd_streaming<bf16, 32>(p, grid, s); else flash_bwd_streaming<bf16, 64>(p, grid, s); }
-    flash_dbias_reduce(p, a->num_windows * p.ntile, s);      // one partial row per 64-key tile of every window
+    attn_dbias_reduce(p.dbias, p.dbias_part, (int)attn_dbias_part_rows(r), p.nh * p.ws * p.ws, s);
     GG_LAUNCH_CHECK();
     return 0;
 }

@@ -34,6 +34,7 @@
 // The template does not preclude what is out of scope today (other head dims, fp16 windows, causal rows).
 #include "common.h"
 #include "attention16.h"
+#include "attention_route.h"
 #include "../../include/gg.h"
 #include "../../include/gg_attn16.h"
 #include "../../include/gg_attn16w.h"
@@ -269,14 +270,10 @@ std::atomic<int64_t> g_flash16_calls{0}, g_flash16_win_calls{0};
 
 // What the two entry points check and fill alike, after each has refused the arguments that are the other's: window_map / num_windows_dev, the counts, the
 // window geometry (where there is one), pitches, alignment, out, lse, the params, the grid.
-int a16_fill(A16Params& p, dim3& grid, const GgAttnArgs* a, int D, const char* who) {
+int a16_fill(A16Params& p, int64_t& nblk, const GgAttnArgs* a, int D, const char* who) {
     GG_CHECK(!a->window_map && !a->num_windows_dev, "%s: window_map / num_windows_dev are a form of gg_attention_flash_bwd only", who);
     GG_CHECK(a->tokens_per_window > 0 && a->num_windows > 0 && a->num_heads > 0, "%s: bad window/head/token count", who);
-    if (a->window_size) {
-        GG_CHECK(a->window_size * a->window_size == a->tokens_per_window, "%s: window_size^2 != tokens_per_window", who);
-        GG_CHECK(a->map_h > 0 && a->map_w > 0 && a->map_h % a->window_size == 0 && a->map_w % a->window_size == 0, "%s: map not divisible by window", who);
-        GG_CHECK(a->num_windows % ((a->map_h / a->window_size) * (a->map_w / a->window_size)) == 0, "%s: window count", who);
-    }
+    if (a->window_size) GG_TRY(attn_check_windows(a, true, who));
     GG_CHECK((a->ld & 3) == 0 && (a->q_off & 3) == 0 && (a->k_off & 3) == 0 && (a->v_off & 3) == 0 && (a->head_stride & 3) == 0,
              "%s: qkv offsets/strides must be multiples of 4 elements", who);
     GG_CHECK(a->q_off >= 0 && a->k_off >= 0 && a->v_off >= 0 && a->head_stride >= 0 && a->ld >= D, "%s: bad qkv pitch", who);
@@ -293,16 +290,38 @@ int a16_fill(A16Params& p, dim3& grid, const GgAttnArgs* a, int D, const char* w
     if (a->window_size) {
         p.ws = a->window_size; p.H = a->map_h; p.W = a->map_w;
         p.nWx = a->map_w / a->window_size; p.nWy = a->map_h / a->window_size;
-        const int w2 = 2 * p.ws - 1;
-        p.rcp_ws = (uint32_t)(((1u << 20) + p.ws - 1) / p.ws);
-        p.rcp_w2 = (uint32_t)(((1u << 20) + w2 - 1) / w2);
-        for (int t = 0; t < p.N + 128; ++t) GG_CHECK((int)(((uint32_t)t * p.rcp_ws) >> 20) == t / p.ws, "%s: reciprocal division fails at %d / %d", who, t, p.ws);
-        for (int t = 0; t < w2 * w2; ++t) GG_CHECK((int)(((uint32_t)t * p.rcp_w2) >> 20) == t / w2, "%s: reciprocal division fails at %d / %d", who, t, w2);
+        GG_TRY(attn_window_reciprocals(p.ws, p.N + 128, p.rcp_ws, p.rcp_w2, who));
         GG_CHECK((int64_t)a->num_windows / (p.nWx * p.nWy) * a->map_h * a->map_w < ((int64_t)1 << 31), "%s: too many tokens", who);
     }
-    const int64_t nblk = (int64_t)a->num_windows * a->num_heads * p.nqt;
+    nblk = (int64_t)a->num_windows * a->num_heads * p.nqt;
     GG_CHECK(nblk < ((int64_t)1 << 31), "%s: grid too large", who);
-    grid = dim3((unsigned)nblk);
+    return 0;
+}
+// The one route of gg_attention_flash16_fwd and of gg_attention_flash16_win_fwd (`entry`): each entry's refusals, the shared fill, one kernel on one grid.
+int flash16_fwd_route(const GgAttnArgs* a, int entry, int dtype, A16Params& p, GgAttnRoute& r) {
+    const bool win = entry == GG_ATTN_ENTRY_FLASH16_WIN_FWD;
+    const char* who = win ? "gg_attention_flash16_win_fwd" : "gg_attention_flash16_fwd";
+    r = GgAttnRoute{};
+    GG_CHECK(a && a->qkv, "%s: null qkv", who);
+    if (win) {
+        GG_CHECK(dtype == 0, "%s: dtype must be 0 (bf16 storage; TinyViT has no fp16 mode, 1 and 3 are f32 storage); got %d", who, dtype);
+        GG_CHECK(a->head_dim == 32, "%s: head_dim must be 32 (got %d)", who, a->head_dim);
+        GG_CHECK(a->window_size != 0, "%s: window_size must be 1 .. 32 (got 0: linear tokens are gg_attention_flash16_fwd's)", who);
+        GG_CHECK(a->window_size > 0 && a->window_size <= 32, "%s: window_size must be 1 .. 32 (got %d: the expanded bias table holds at most 63 x 63 entries)", who, a->window_size);
+        GG_CHECK(!a->bias || a->bias_table, "%s: bias (the expanded bf16 table) without bias_table: this kernel reads the compact f32 table", who);
+        GG_CHECK(!a->dbias, "%s: dbias is the backward's; this is a forward", who);
+    } else {
+        GG_CHECK(dtype == 0 || dtype == 2, "%s: dtype must be 0 (bf16) or 2 (fp16) storage; got %d", who, dtype);
+        GG_CHECK(a->head_dim == 64, "%s: head_dim must be 64 (got %d)", who, a->head_dim);
+        GG_CHECK(a->window_size == 0, "%s: window_size must be 0 (linear tokens; got %d)", who, a->window_size);
+        GG_CHECK(!a->bias, "%s: bias (the expanded relative-position bias) is not taken", who);
+        GG_CHECK(!a->bias_table, "%s: bias_table is not taken", who);
+    }
+    int64_t nblk;
+    GG_TRY(a16_fill(p, nblk, a, win ? 32 : 64, who));
+    r.kernel = win ? GG_ATTN_KERNEL_FLASH16_WIN_FWD : GG_ATTN_KERNEL_FLASH16_FWD;
+    r.variant = win && a->bias_table;
+    attn_route_pass(r, nblk, 256, 0);
     return 0;
 }
 
@@ -310,19 +329,16 @@ int a16_fill(A16Params& p, dim3& grid, const GgAttnArgs* a, int D, const char* w
 
 extern "C" int64_t gg_attention_flash16_calls(void) { return g_flash16_calls.load(); }
 extern "C" int64_t gg_attention_flash16_win_calls(void) { return g_flash16_win_calls.load(); }
+int gg_attn_route_flash16_fwd(const GgAttnArgs* a, int entry, int dtype, GgAttnRoute* out) {
+    A16Params p;
+    return flash16_fwd_route(a, entry, dtype, p, *out);
+}
 
 extern "C" int gg_attention_flash16_fwd(const GgAttnArgs* a, int dtype, void* stream) {
-    const char* who = "gg_attention_flash16_fwd";
-    GG_CHECK(a && a->qkv, "%s: null qkv", who);
-    GG_CHECK(dtype == 0 || dtype == 2, "%s: dtype must be 0 (bf16) or 2 (fp16) storage; got %d", who, dtype);
-    GG_CHECK(a->head_dim == 64, "%s: head_dim must be 64 (got %d)", who, a->head_dim);
-    GG_CHECK(a->window_size == 0, "%s: window_size must be 0 (linear tokens; got %d)", who, a->window_size);
-    GG_CHECK(!a->bias, "%s: bias (the expanded relative-position bias) is not taken", who);
-    GG_CHECK(!a->bias_table, "%s: bias_table is not taken", who);
     A16Params p;
-    dim3 grid;
-    GG_TRY(a16_fill(p, grid, a, 64, who));
-    const dim3 block(256);
+    GgAttnRoute r;
+    GG_TRY(flash16_fwd_route(a, GG_ATTN_ENTRY_FLASH16_FWD, dtype, p, r));
+    const dim3 grid(r.pass[0].grid), block(r.pass[0].block);
     hipStream_t s = (hipStream_t)stream;
     GG_PROF(GG_CAT_ATTN, 4.0 * a->num_windows * a->num_heads * (double)p.N * p.N * 64, 8.0 * a->num_windows * a->num_heads * (double)p.N * 64, stream);
     if (dtype == 2) hipLaunchKernelGGL((flash16_fwd_kernel<f16, 64, false, false>), grid, block, 0, s, p);
@@ -333,21 +349,13 @@ extern "C" int gg_attention_flash16_fwd(const GgAttnArgs* a, int dtype, void* st
 }
 
 extern "C" int gg_attention_flash16_win_fwd(const GgAttnArgs* a, int dtype, void* stream) {
-    const char* who = "gg_attention_flash16_win_fwd";
-    GG_CHECK(a && a->qkv, "%s: null qkv", who);
-    GG_CHECK(dtype == 0, "%s: dtype must be 0 (bf16 storage; TinyViT has no fp16 mode, 1 and 3 are f32 storage); got %d", who, dtype);
-    GG_CHECK(a->head_dim == 32, "%s: head_dim must be 32 (got %d)", who, a->head_dim);
-    GG_CHECK(a->window_size != 0, "%s: window_size must be 1 .. 32 (got 0: linear tokens are gg_attention_flash16_fwd's)", who);
-    GG_CHECK(a->window_size > 0 && a->window_size <= 32, "%s: window_size must be 1 .. 32 (got %d: the expanded bias table holds at most 63 x 63 entries)", who, a->window_size);
-    GG_CHECK(!a->bias || a->bias_table, "%s: bias (the expanded bf16 table) without bias_table: this kernel reads the compact f32 table", who);
-    GG_CHECK(!a->dbias, "%s: dbias is the backward's; this is a forward", who);
     A16Params p;
-    dim3 grid;
-    GG_TRY(a16_fill(p, grid, a, 32, who));
-    const dim3 block(256);
+    GgAttnRoute r;
+    GG_TRY(flash16_fwd_route(a, GG_ATTN_ENTRY_FLASH16_WIN_FWD, dtype, p, r));
+    const dim3 grid(r.pass[0].grid), block(r.pass[0].block);
     hipStream_t s = (hipStream_t)stream;
     GG_PROF(GG_CAT_ATTN, 4.0 * a->num_windows * a->num_heads * (double)p.N * p.N * 32, 8.0 * a->num_windows * a->num_heads * (double)p.N * 32, stream);
-    if (a->bias_table) hipLaunchKernelGGL((flash16_fwd_kernel<bf16, 32, true, true>), grid, block, 0, s, p);
+    if (r.variant) hipLaunchKernelGGL((flash16_fwd_kernel<bf16, 32, true, true>), grid, block, 0, s, p);
     else hipLaunchKernelGGL((flash16_fwd_kernel<bf16, 32, true, false>), grid, block, 0, s, p);
     GG_LAUNCH_CHECK();
     g_flash16_win_calls.fetch_add(1);

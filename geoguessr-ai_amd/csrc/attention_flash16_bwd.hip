@@ -45,7 +45,7 @@
 //       for a dQ pass with the bins (56.3 KB); (2) the f32-pipe backward bins there too (flash_bwd_dkv_kernel), so the partial rows keep their shape: one per
 //       (window, key block).  The UNROUNDED f32 dS of every live (query, key) pair is added to bin qlin4[query] - klin4[key] of (2 ws - 1)^2 floats by an LDS
 //       float add (ds_add_f32, no return value); at the end of the workgroup the bins are folded onto |dy|, |dx| (four reads per entry, thread i -> entry i:
-//       consecutive words, conflict-free) and leave as one row of dbias_scratch -- flash_dbias_reduce's pattern, the second stage sums the rows in a fixed order --
+//       consecutive words, conflict-free) and leave as one row of dbias_scratch -- attn_dbias_reduce (attention_route.h): the second stage sums the rows in a fixed order --
 //       or, without a scratch, by global vector atomics.  The adds touch the words of the gather (c + 4 lg - lr); an LDS add is banked as a 4-byte store (two
 //       32-lane halves, 32 banks), but equal addresses do not broadcast: they are added one after the other.  Of the 32 lanes of a half 20 words are distinct, the
 //       middle ones shared by two lanes (lr, lg = 0) and (lr + 4, lg = 1): 2 passes per half where the gather needs one, plus the straddle runs above.  The
@@ -56,6 +56,7 @@
 // the table): 48 KB at D = 64; 24 KB / 40.4 KB at D = 32; double-buffered as the forward, one barrier per tile.
 #include "common.h"
 #include "attention16.h"
+#include "attention_route.h"
 #include "../../include/gg.h"
 #include "../../include/gg_attn16b.h"
 #include "../../include/gg_attn16wb.h"
@@ -537,19 +538,10 @@ __global__ __launch_bounds__(256) void flash16_bwd_dq_kernel(A16BParams p) {
     }
 }
 
-// second stage of the bias gradient: the folded partial rows summed in a fixed order, added to dbias (flash_dbias_reduce's pattern)
-__global__ void a16b_dbias_final_kernel(const float* __restrict__ rows, int nrows, int W, float* __restrict__ dbias) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= W) return;
-    double s = 0.0;
-    for (int r = 0; r < nrows; ++r) s += (double)rows[(int64_t)r * W + i];
-    dbias[i] += (float)s;
-}
-
 std::atomic<int64_t> g_flash16_bwd_calls{0}, g_flash16_win_bwd_calls{0};
 
 // what the two entry points check and fill alike, after each has refused the arguments that are the other's
-int a16b_fill(A16BParams& p, dim3& grid, const GgAttnArgs* a, int D, const char* who) {
+int a16b_fill(A16BParams& p, int64_t& nblk, const GgAttnArgs* a, int D, const char* who) {
     GG_CHECK(!a->window_map && !a->num_windows_dev, "%s: window_map / num_windows_dev are a form of gg_attention_flash_bwd only", who);
     GG_CHECK(a->tokens_per_window > 0 && a->num_windows > 0 && a->num_heads > 0, "%s: bad window/head/token count", who);
     GG_CHECK(a->lse, "%s: needs the forward's lse", who);
@@ -569,9 +561,54 @@ int a16b_fill(A16BParams& p, dim3& grid, const GgAttnArgs* a, int D, const char*
     p.N = a->tokens_per_window; p.nh = a->num_heads;
     p.ntile = (int)gg_cdiv(p.N, 64); p.nblk = (int)gg_cdiv(p.N, 128);
     p.sc2 = a->scale * A16_LOG2E; p.scale = a->scale;
-    const int64_t nblk = (int64_t)a->num_windows * a->num_heads * p.nblk;
+    nblk = (int64_t)a->num_windows * a->num_heads * p.nblk;
     GG_CHECK(nblk < ((int64_t)1 << 31), "%s: grid too large", who);
-    grid = dim3((unsigned)nblk);
+    return 0;
+}
+// partial dbias rows of the window backward: one per workgroup of the dK / dV pass and head (window, 128-key block)
+int64_t a16b_part_rows(int64_t num_windows, int tokens_per_window) { return num_windows * gg_cdiv(tokens_per_window, 128); }
+// The one route of gg_attention_flash16_bwd and of gg_attention_flash16_win_bwd (`entry`): each entry's refusals, the shared fill, the dK / dV pass and the
+// dQ pass on one grid.
+int flash16_bwd_route(const GgAttnArgs* a, int entry, int dtype, A16BParams& p, GgAttnRoute& r) {
+    const bool win = entry == GG_ATTN_ENTRY_FLASH16_WIN_BWD;
+    const char* who = win ? "gg_attention_flash16_win_bwd" : "gg_attention_flash16_bwd";
+    r = GgAttnRoute{};
+    GG_CHECK(a && a->qkv, "%s: null qkv", who);
+    int64_t nblk;
+    if (!win) {
+        GG_CHECK(dtype != 2, "%s: fp16 storage is inference-only", who);
+        GG_CHECK(dtype == 0, "%s: dtype must be 0 (bf16 storage; 1 and 3 are f32 storage); got %d", who, dtype);
+        GG_CHECK(a->head_dim == 64, "%s: head_dim must be 64 (got %d)", who, a->head_dim);
+        GG_CHECK(a->window_size == 0, "%s: window_size must be 0 (linear tokens; got %d)", who, a->window_size);
+        GG_CHECK(!a->bias, "%s: bias (the expanded relative-position bias) is not taken", who);
+        GG_CHECK(!a->bias_table, "%s: bias_table is not taken", who);
+        GG_CHECK(!a->dbias, "%s: dbias is not taken (there is no bias)", who);
+        GG_TRY(a16b_fill(p, nblk, a, 64, who));
+        r.kernel = GG_ATTN_KERNEL_FLASH16_BWD;
+    } else {
+        GG_CHECK(dtype != 2, "%s: fp16 storage is inference-only (TinyViT has no fp16 mode)", who);
+        GG_CHECK(dtype == 0, "%s: dtype must be 0 (bf16 storage; 1 and 3 are f32 storage); got %d", who, dtype);
+        GG_CHECK(a->head_dim == 32, "%s: head_dim must be 32 (got %d: head dim 64 is gg_attention_flash16_bwd's)", who, a->head_dim);
+        GG_CHECK(a->window_size != 0, "%s: window_size must be 1 .. 32 (got 0: linear tokens are gg_attention_flash16_bwd's)", who);
+        GG_CHECK(a->window_size > 0 && a->window_size <= 32, "%s: window_size must be 1 .. 32 (got %d: the expanded bias table holds at most 63 x 63 entries)", who, a->window_size);
+        GG_CHECK(!a->bias || a->bias_table, "%s: bias (the expanded bf16 table) without bias_table: this kernel reads the compact f32 table", who);
+        GG_CHECK(!a->dbias || a->bias_table, "%s: dbias without bias_table", who);
+        GG_TRY(a16b_fill(p, nblk, a, 32, who));
+        GG_TRY(attn_check_windows(a, true, who));
+        GG_CHECK(!a->bias_table || ((uintptr_t)a->bias_table & 3) == 0, "%s: bias_table must be 4-byte aligned", who);
+        GG_CHECK(!a->dbias || ((uintptr_t)a->dbias & 3) == 0, "%s: dbias must be 4-byte aligned", who);
+        GG_CHECK(!a->dbias || !a->dbias_scratch || ((uintptr_t)a->dbias_scratch & 3) == 0, "%s: dbias_scratch must be 4-byte aligned", who);
+        p.ws = a->window_size; p.H = a->map_h; p.W = a->map_w;
+        p.nWx = a->map_w / a->window_size; p.nWy = a->map_h / a->window_size;
+        GG_TRY(attn_window_reciprocals(p.ws, p.N + 128, p.rcp_ws, p.rcp_w2, who));
+        GG_CHECK((int64_t)a->num_windows / (p.nWx * p.nWy) * a->map_h * a->map_w < ((int64_t)1 << 31), "%s: too many tokens", who);
+        p.bias_table = a->bias_table; p.dbias = a->dbias; p.dbias_part = a->dbias ? a->dbias_scratch : nullptr;
+        r.kernel = GG_ATTN_KERNEL_FLASH16_WIN_BWD;
+        r.variant = p.dbias ? 2 : p.bias_table ? 1 : 0;
+        if (p.dbias) r.dbias_rows = attn_dbias_scratch_rows(a16b_part_rows(a->num_windows, p.N));
+    }
+    attn_route_pass(r, nblk, 256, 0);
+    attn_route_pass(r, nblk, 256, 0);
     return 0;
 }
 
@@ -580,23 +617,18 @@ int a16b_fill(A16BParams& p, dim3& grid, const GgAttnArgs* a, int D, const char*
 extern "C" int64_t gg_attention_flash16_bwd_calls(void) { return g_flash16_bwd_calls.load(); }
 extern "C" int64_t gg_attention_flash16_win_bwd_calls(void) { return g_flash16_win_bwd_calls.load(); }
 extern "C" int64_t gg_attention_flash16_win_dbias_rows(int num_windows, int tokens_per_window) {
-    return (int64_t)num_windows * gg_cdiv(tokens_per_window, 128) + GG_REDUCE_SLICES;
+    return attn_dbias_scratch_rows(a16b_part_rows(num_windows, tokens_per_window));
+}
+int gg_attn_route_flash16_bwd(const GgAttnArgs* a, int entry, int dtype, GgAttnRoute* out) {
+    A16BParams p;
+    return flash16_bwd_route(a, entry, dtype, p, *out);
 }
 
 extern "C" int gg_attention_flash16_bwd(const GgAttnArgs* a, int dtype, void* stream) {
-    const char* who = "gg_attention_flash16_bwd";
-    GG_CHECK(a && a->qkv, "%s: null qkv", who);
-    GG_CHECK(dtype != 2, "%s: fp16 storage is inference-only", who);
-    GG_CHECK(dtype == 0, "%s: dtype must be 0 (bf16 storage; 1 and 3 are f32 storage); got %d", who, dtype);
-    GG_CHECK(a->head_dim == 64, "%s: head_dim must be 64 (got %d)", who, a->head_dim);
-    GG_CHECK(a->window_size == 0, "%s: window_size must be 0 (linear tokens; got %d)", who, a->window_size);
-    GG_CHECK(!a->bias, "%s: bias (the expanded relative-position bias) is not taken", who);
-    GG_CHECK(!a->bias_table, "%s: bias_table is not taken", who);
-    GG_CHECK(!a->dbias, "%s: dbias is not taken (there is no bias)", who);
     A16BParams p;
-    dim3 grid;
-    GG_TRY(a16b_fill(p, grid, a, 64, who));
-    const dim3 block(256);
+    GgAttnRoute r;
+    GG_TRY(flash16_bwd_route(a, GG_ATTN_ENTRY_FLASH16_BWD, dtype, p, r));
+    const dim3 grid(r.pass[0].grid), block(r.pass[0].block);
     hipStream_t s = (hipStream_t)stream;
     // algorithmic: 5 products (S, dP, dV, dK, dQ) = 10 N^2 D, whatever the two passes recompute (gg_attention_flash_bwd declares the same)
     GG_PROF(GG_CAT_ATTN, 10.0 * a->num_windows * a->num_heads * (double)p.N * p.N * 64, 16.0 * a->num_windows * a->num_heads * (double)p.N * 64, stream);
@@ -608,47 +640,20 @@ extern "C" int gg_attention_flash16_bwd(const GgAttnArgs* a, int dtype, void* st
 }
 
 extern "C" int gg_attention_flash16_win_bwd(const GgAttnArgs* a, int dtype, void* stream) {
-    const char* who = "gg_attention_flash16_win_bwd";
-    GG_CHECK(a && a->qkv, "%s: null qkv", who);
-    GG_CHECK(dtype != 2, "%s: fp16 storage is inference-only (TinyViT has no fp16 mode)", who);
-    GG_CHECK(dtype == 0, "%s: dtype must be 0 (bf16 storage; 1 and 3 are f32 storage); got %d", who, dtype);
-    GG_CHECK(a->head_dim == 32, "%s: head_dim must be 32 (got %d: head dim 64 is gg_attention_flash16_bwd's)", who, a->head_dim);
-    GG_CHECK(a->window_size != 0, "%s: window_size must be 1 .. 32 (got 0: linear tokens are gg_attention_flash16_bwd's)", who);
-    GG_CHECK(a->window_size > 0 && a->window_size <= 32, "%s: window_size must be 1 .. 32 (got %d: the expanded bias table holds at most 63 x 63 entries)", who, a->window_size);
-    GG_CHECK(!a->bias || a->bias_table, "%s: bias (the expanded bf16 table) without bias_table: this kernel reads the compact f32 table", who);
-    GG_CHECK(!a->dbias || a->bias_table, "%s: dbias without bias_table", who);
     A16BParams p;
-    dim3 grid;
-    GG_TRY(a16b_fill(p, grid, a, 32, who));
-    GG_CHECK(a->window_size * a->window_size == a->tokens_per_window, "%s: window_size^2 != tokens_per_window", who);
-    GG_CHECK(a->map_h > 0 && a->map_w > 0 && a->map_h % a->window_size == 0 && a->map_w % a->window_size == 0, "%s: map not divisible by window", who);
-    GG_CHECK(a->num_windows % ((a->map_h / a->window_size) * (a->map_w / a->window_size)) == 0, "%s: window count", who);
-    GG_CHECK(!a->bias_table || ((uintptr_t)a->bias_table & 3) == 0, "%s: bias_table must be 4-byte aligned", who);
-    GG_CHECK(!a->dbias || ((uintptr_t)a->dbias & 3) == 0, "%s: dbias must be 4-byte aligned", who);
-    GG_CHECK(!a->dbias || !a->dbias_scratch || ((uintptr_t)a->dbias_scratch & 3) == 0, "%s: dbias_scratch must be 4-byte aligned", who);
-    p.ws = a->window_size; p.H = a->map_h; p.W = a->map_w;
-    p.nWx = a->map_w / a->window_size; p.nWy = a->map_h / a->window_size;
-    const int w2 = 2 * p.ws - 1;
-    p.rcp_ws = (uint32_t)(((1u << 20) + p.ws - 1) / p.ws);
-    p.rcp_w2 = (uint32_t)(((1u << 20) + w2 - 1) / w2);
-    for (int t = 0; t < p.N + 128; ++t) GG_CHECK((int)(((uint32_t)t * p.rcp_ws) >> 20) == t / p.ws, "%s: reciprocal division fails at %d / %d", who, t, p.ws);
-    for (int t = 0; t < w2 * w2; ++t) GG_CHECK((int)(((uint32_t)t * p.rcp_w2) >> 20) == t / w2, "%s: reciprocal division fails at %d / %d", who, t, w2);
-    GG_CHECK((int64_t)a->num_windows / (p.nWx * p.nWy) * a->map_h * a->map_w < ((int64_t)1 << 31), "%s: too many tokens", who);
-    p.bias_table = a->bias_table; p.dbias = a->dbias; p.dbias_part = a->dbias ? a->dbias_scratch : nullptr;
-    const dim3 block(256);
+    GgAttnRoute r;
+    GG_TRY(flash16_bwd_route(a, GG_ATTN_ENTRY_FLASH16_WIN_BWD, dtype, p, r));
+    const dim3 grid(r.pass[0].grid), block(r.pass[0].block);
     hipStream_t s = (hipStream_t)stream;
     GG_PROF(GG_CAT_ATTN, 10.0 * a->num_windows * a->num_heads * (double)p.N * p.N * 32, 16.0 * a->num_windows * a->num_heads * (double)p.N * 32, stream);
-    if (p.dbias) hipLaunchKernelGGL((flash16_bwd_dkv_kernel<bf16, 32, true, true, true>), grid, block, 0, s, p);
-    else if (p.bias_table) hipLaunchKernelGGL((flash16_bwd_dkv_kernel<bf16, 32, true, true, false>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((flash16_bwd_dkv_kernel<bf16, 32, true, false, false>), grid, block, 0, s, p);
-    if (p.bias_table) hipLaunchKernelGGL((flash16_bwd_dq_kernel<bf16, 32, true, true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((flash16_bwd_dq_kernel<bf16, 32, true, false>), grid, block, 0, s, p);
-    if (p.dbias && p.dbias_part) {      // every partial row (one per window and key block) summed in a fixed order, then added to dbias
-        const int Wd = p.nh * p.ws * p.ws;
-        const float* rows; int nrows;
-        gg_reduce_rows(p.dbias_part, a->num_windows * p.nblk, Wd, s, &rows, &nrows);
-        hipLaunchKernelGGL(a16b_dbias_final_kernel, dim3((unsigned)gg_cdiv(Wd, 256)), dim3(256), 0, s, rows, nrows, Wd, p.dbias);
+    switch (r.variant) {
+        case 2: hipLaunchKernelGGL((flash16_bwd_dkv_kernel<bf16, 32, true, true, true>), grid, block, 0, s, p); break;
+        case 1: hipLaunchKernelGGL((flash16_bwd_dkv_kernel<bf16, 32, true, true, false>), grid, block, 0, s, p); break;
+        default: hipLaunchKernelGGL((flash16_bwd_dkv_kernel<bf16, 32, true, false, false>), grid, block, 0, s, p); break;
     }
+    if (r.variant) hipLaunchKernelGGL((flash16_bwd_dq_kernel<bf16, 32, true, true>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((flash16_bwd_dq_kernel<bf16, 32, true, false>), grid, block, 0, s, p);
+    attn_dbias_reduce(p.dbias, p.dbias_part, (int)attn_dbias_part_rows(r), p.nh * p.ws * p.ws, s);      // (one partial row per window and key block)
     GG_LAUNCH_CHECK();
     g_flash16_win_bwd_calls.fetch_add(1);
     return 0;

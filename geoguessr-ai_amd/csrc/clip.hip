@@ -36,6 +36,7 @@
 #include "../../include/gg_fp8.h"
 #include "../../include/gg_attn16.h"
 #include "../../include/gg_attn16b.h"
+#include "attention_route.h"
 #include <atomic>
 
 namespace {
@@ -335,6 +336,45 @@ struct CPlan {
 };
 // ds_force: whether attn_ds exists is taken from the recompute-off plan of the same (batch, mask) (1 / 0; -1: decided here) -- its test depends on
 // the planned size, and both settings must take the same route through the attention backward
+// attention arguments of one layer on B sequences (forward fields; the backward adds its own)
+static void clip_attn_args(const CModel& m, int B, GgAttnArgs& at, const void* qkv, void* out, float* lse) {
+    const int D = m.cfg.hidden_size;
+    memset(&at, 0, sizeof(at));
+    at.qkv = qkv; at.ld = 3 * D; at.q_off = 0; at.k_off = D; at.v_off = 2 * D; at.head_stride = 64; at.head_dim = 64;
+    at.num_heads = m.cfg.num_heads; at.num_windows = B; at.tokens_per_window = m.T; at.window_size = 0;
+    at.scale = 0.125f; at.out = out; at.ldo = D; at.lse = lse;
+}
+// The ONE place that picks the attention entry point (GG_ATTN_ENTRY_*) and dtype code of a layer: the forward, the backward and the attn_ds plan all ask it,
+// and gg_attention_route then says what that entry runs.  Backward: the text tower's causal entry; the opt-in 16-bit-MFMA pair (the dS region is not read);
+// else the flash backward.  Forward: the fp8 mode's fp16 attention; the text tower; split products at every token count; the opt-in 16-bit-MFMA forward --
+// the training step's kept layers (with lse) and the layers below them alike, the inference forward where nothing is kept --; fp16 MFMA for towers of at most
+// 256 tokens (ViT-B/32: 50; beyond: fp16 storage, f32 arithmetic -- gg_attention_fwd_f16 forwards those itself); the flash forward for f32 storage, for kept
+// layers (lse) and beyond 256 tokens; else the register-resident forward.
+struct AttnCall { int entry, dtype; };
+static AttnCall clip_attn_call(bool bwd, bool causal, bool split, bool f32, bool f16, bool fp8, bool attn16, bool attn16t, bool sv, int T) {
+    const int dt = split ? 3 : f32 ? 1 : 0;
+    if (bwd) return causal ? AttnCall{GG_ATTN_ENTRY_CAUSAL_BWD, dt} : attn16t ? AttnCall{GG_ATTN_ENTRY_FLASH16_BWD, 0} : AttnCall{GG_ATTN_ENTRY_FLASH_BWD, dt};
+    if (fp8) return attn16 ? AttnCall{GG_ATTN_ENTRY_FLASH16_FWD, 2} : AttnCall{GG_ATTN_ENTRY_FWD_F16, 0};
+    if (causal) return {GG_ATTN_ENTRY_CAUSAL_FWD, dt};
+    if (split) return {GG_ATTN_ENTRY_FLASH_FWD, 3};
+    if (attn16t) return {GG_ATTN_ENTRY_FLASH16_FWD, 0};
+    if (attn16 && !sv) return {GG_ATTN_ENTRY_FLASH16_FWD, f16 ? 2 : 0};
+    if (f16) return {GG_ATTN_ENTRY_FWD_F16, 0};
+    if (f32 || sv || T > 256) return {GG_ATTN_ENTRY_FLASH_FWD, dt};
+    return {GG_ATTN_ENTRY_FWD, 0};
+}
+static int clip_attn_launch(const AttnCall& c, const GgAttnArgs& at, hipStream_t st) {
+    switch (c.entry) {
+        case GG_ATTN_ENTRY_CAUSAL_FWD: return gg_attention_causal_fwd(&at, c.dtype, st);
+        case GG_ATTN_ENTRY_CAUSAL_BWD: return gg_attention_causal_bwd(&at, c.dtype, st);
+        case GG_ATTN_ENTRY_FLASH16_FWD: return gg_attention_flash16_fwd(&at, c.dtype, st);
+        case GG_ATTN_ENTRY_FLASH16_BWD: return gg_attention_flash16_bwd(&at, c.dtype, st);
+        case GG_ATTN_ENTRY_FLASH_FWD: return gg_attention_flash_fwd(&at, c.dtype, st);
+        case GG_ATTN_ENTRY_FLASH_BWD: return gg_attention_flash_bwd(&at, c.dtype, st);
+        case GG_ATTN_ENTRY_FWD_F16: return gg_attention_fwd_f16(&at, st);
+        default: return gg_attention_fwd(&at, st);
+    }
+}
 static void plan(const CModel& m, int B, const Train& tr, bool training, CPlan& L, int ds_force = -1) {
     const int D = m.cfg.hidden_size, I = m.cfg.intermediate_size, nl = m.cfg.num_layers;
     const int64_t Mp = (int64_t)B * m.G * m.G, M = (int64_t)B * m.T, es = m.es;
@@ -382,11 +422,17 @@ static void plan(const CModel& m, int B, const Train& tr, bool training, CPlan& 
         // dS hand-off between the two passes of the attention backward: only towers beyond 256 tokens (ViT-L/14-336: 577 tokens, 22 MB per image) use it -- the
         // 50-token towers run the single-pass kernel --, and only while it stays at most 4 GB and 1/8 of the workspace planned so far
         const int64_t dsb = gg_attention_flash_ds_scratch_floats(B, m.cfg.num_heads, m.T) * 4;
-        static const bool ds_off = gg_dev_env("GG_ATTN_NO_DS_SCRATCH") != nullptr;
-        // (the fp32_split mode's attention backward recomputes P in both passes: no hand-off at any length)
-        // (nor does the text tower's causal backward, at most 77 tokens, read one)
-        const bool ds = m.split || m.causal ? false : ds_force >= 0 ? ds_force != 0
-                                      : !ds_off && !gg_attention_flash_single_pass(m.T, D / m.cfg.num_heads, 0, 0) && dsb <= ((int64_t)4 << 30) && dsb <= off / 8;
+        // the route of the layer's backward when a dS region is given says whether it reads one (placeholder pointers: the report never dereferences them):
+        // the fp32_split mode's attention backward recomputes P in both passes (no hand-off at any length), nor does the text tower's causal backward, at most
+        // 77 tokens, read one
+        GgAttnArgs at;
+        GgAttnRoute r;
+        void* const given = (void*)(uintptr_t)256;
+        clip_attn_args(m, B, at, given, given, (float*)given);
+        at.dout = given; at.lddo = D; at.dqkv = given; at.ds_scratch = (float*)given;
+        const AttnCall call = clip_attn_call(true, m.causal, m.split, m.f32, m.f16, m.fp8, false, false, true, m.T);
+        const bool reads = gg_attention_route(&at, call.entry, call.dtype, &r) == 0 && r.reads_ds_scratch;
+        const bool ds = !reads ? false : ds_force >= 0 ? ds_force != 0 : !attn_switches().no_ds_scratch && dsb <= ((int64_t)4 << 30) && dsb <= off / 8;
         if (ds) L.attn_ds = al(dsb);
     }
     L.total = off;
@@ -466,12 +512,9 @@ struct Exec {
         if (m->f32) return gg_colsum_f32((const float*)dY, ld, (int)M, N, nullptr, 0, F(L->colsum), Gd(tb), 1, st);
         return gg_colsum_bf16(dY, ld, (int)M, N, nullptr, 0, F(L->colsum), Gd(tb), 1, st);
     }
-    void attn_args(GgAttnArgs& at, const void* qkv, void* out, float* lse) const {
-        const int D = m->cfg.hidden_size;
-        memset(&at, 0, sizeof(at));
-        at.qkv = qkv; at.ld = 3 * D; at.q_off = 0; at.k_off = D; at.v_off = 2 * D; at.head_stride = 64; at.head_dim = 64;
-        at.num_heads = m->cfg.num_heads; at.num_windows = B; at.tokens_per_window = m->T; at.window_size = 0;
-        at.scale = 0.125f; at.out = out; at.ldo = D; at.lse = lse;
+    void attn_args(GgAttnArgs& at, const void* qkv, void* out, float* lse) const { clip_attn_args(*m, B, at, qkv, out, lse); }
+    int attention(const GgAttnArgs& at, bool bwd, bool sv) const {
+        return clip_attn_launch(clip_attn_call(bwd, m->causal, m->split, m->f32, m->f16, m->fp8, attn16, attn16t, sv, m->T), at, st);
     }
 };
 template <typename T> static int embed_fwd(const Exec& e, const float* x, void* tok_out) {
@@ -507,8 +550,7 @@ static int layer_fwd(const Exec& e, int i, int64_t cur, int64_t next, bool sv) {
         GG_TRY(e.gemm8(l.wqkv8, l.sqkv, e.A(QKV), 3 * D, M, 3 * D, D, (const float*)e.W(l.bqkv)));
         GgAttnArgs at8;
         e.attn_args(at8, e.A(QKV), e.A(O), nullptr);
-        if (e.attn16) GG_TRY(gg_attention_flash16_fwd(&at8, 2, e.st));
-        else GG_TRY(gg_attention_fwd_f16(&at8, e.st));
+        GG_TRY(e.attention(at8, false, sv));
         GG_TRY(e.quant8(e.A(O), M, D));
         GG_TRY(e.gemm8(l.wo8, l.so, e.A(XMID), D, M, D, D, e.P(l.o_b), 0, e.A(cur)));
         GG_TRY(e.ln_fwd8(e.A(XMID), l.ln2_g, l.ln2_b, M));
@@ -521,13 +563,7 @@ static int layer_fwd(const Exec& e, int i, int64_t cur, int64_t next, bool sv) {
     GG_TRY(e.gemm(e.A(A1), D, e.W(l.wqkv, l.wqkv3), D, e.A(QKV), 3 * D, M, 3 * D, D, (const float*)e.W(l.bqkv)));
     GgAttnArgs at;
     e.attn_args(at, e.A(QKV), e.A(O), sv ? e.F(a.lse) : nullptr);
-    if (m.causal) GG_TRY(gg_attention_causal_fwd(&at, m.split ? 3 : m.f32 ? 1 : 0, e.st));      // the text tower
-    else if (m.split) GG_TRY(gg_attention_flash_fwd(&at, 3, e.st));      // split products at every token count
-    else if (e.attn16t) GG_TRY(gg_attention_flash16_fwd(&at, 0, e.st));      // opt-in, the training step: kept layers (with lse) and the layers below them alike
-    else if (e.attn16 && !sv) GG_TRY(gg_attention_flash16_fwd(&at, m.f16 ? 2 : 0, e.st));      // opt-in: both products on the 16-bit MFMA (include/gg_attn16.h)
-    else if (m.f16) GG_TRY(gg_attention_fwd_f16(&at, e.st));      // fp16 MFMA for towers of at most 256 tokens (ViT-B/32: 50); beyond: fp16 storage, f32 arithmetic
-    else if (m.f32 || sv || T > 256) GG_TRY(gg_attention_flash_fwd(&at, m.f32 ? 1 : 0, e.st));
-    else GG_TRY(gg_attention_fwd(&at, e.st));
+    GG_TRY(e.attention(at, false, sv));
     // x_mid = x + out_proj(o)   (in place when nothing is kept: each element is read then written by the same lane)
     GG_TRY(e.gemm(e.A(O), D, e.W(l.wo, l.wo3), D, e.A(XMID), D, M, D, D, e.P(l.o_b), 0, nullptr, e.A(cur)));
     GG_TRY(e.ln_fwd(e.A(XMID), l.ln2_g, l.ln2_b, M, e.A(A2), sv ? e.F(a.mean2) : nullptr, sv ? e.F(a.rstd2) : nullptr));
@@ -572,9 +608,7 @@ static int layers_bwd(const Exec& e, int l0, bool top_in_region, int64_t& dx, in
         e.attn_args(at, e.A(a.qkv), e.A(a.o), e.F(a.lse));
         at.dout = e.A(L.g_o); at.lddo = D; at.dqkv = e.A(L.g_qkv);
         if (L.attn_ds >= 0) at.ds_scratch = e.F(L.attn_ds);
-        if (m.causal) GG_TRY(gg_attention_causal_bwd(&at, m.split ? 3 : m.f32 ? 1 : 0, e.st));      // the text tower
-        else if (e.attn16t) GG_TRY(gg_attention_flash16_bwd(&at, 0, e.st));      // opt-in: all five products on the 16-bit MFMA; the dS region is not read
-        else GG_TRY(gg_attention_flash_bwd(&at, m.split ? 3 : m.f32 ? 1 : 0, e.st));
+        GG_TRY(e.attention(at, true, true));
         const char* dq = (const char*)e.A(L.g_qkv);
         GG_TRY(e.wgrad(l.q_w, dq, 3 * D, e.A(a.a1), D, M, D, D));
         GG_TRY(e.wgrad(l.k_w, dq + (int64_t)D * m.es, 3 * D, e.A(a.a1), D, M, D, D));

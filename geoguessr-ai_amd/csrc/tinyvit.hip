@@ -19,6 +19,7 @@
 #include "../../include/gg_pad.h"
 #include "../../include/gg_attn16w.h"
 #include "../../include/gg_attn16wb.h"
+#include "attention_route.h"
 
 bool gg_split3_af32_takes_rowmap(int N, int K);      // gemm_split3.hip: the form gg_gemm_nt_split3_af32 would run this shape on accepts row compaction
 
@@ -44,6 +45,35 @@ struct MBConvL { ConvBNDense c1; ConvBNDw c2; ConvBNDense c3; };
 struct MergeL { ConvBNDense c1; ConvBNDw c2; ConvBNDense c3; };
 struct BlockL { int t_ab = -1; int64_t bias_full = 0; LNP ln1; DenseW qkv, proj; LNP ln2; DenseW fc1, fc2; ConvBNDw local; };
 struct StageL { MergeL merge; std::vector<BlockL> blocks; int C, heads, ws, res, pres; };      // pres: the map side the attention branch runs at -- res rounded up to a multiple of ws (timm pads bottom / right)
+// The geometry and layout of a stage's window attention on B images.  The pointers a forward needs hold a placeholder (16-byte aligned, never dereferenced):
+// gg_attention_route only asks whether a pointer is given and aligned, so the planner and the compaction test ask it about these arguments as they are;
+// attn_args overwrites them with the block's tensors.
+static void attn_shape(const StageL& st, int B, GgAttnArgs& at) {
+    const int C = st.C;
+    memset(&at, 0, sizeof(at));
+    at.ld = 3 * C; at.q_off = 0; at.k_off = 32; at.v_off = 64; at.head_stride = 96; at.head_dim = 32;
+    at.num_heads = st.heads; at.tokens_per_window = st.ws * st.ws;
+    at.num_windows = B * (st.pres / st.ws) * (st.pres / st.ws);
+    at.window_size = st.ws; at.map_h = st.pres; at.map_w = st.pres;      // (a padded block: the padded map)
+    at.scale = kAttnScale;
+    at.ldo = C;
+    at.qkv = at.out = (void*)(uintptr_t)256;
+    at.lse = (float*)(uintptr_t)256; at.bias_table = (const float*)(uintptr_t)256;
+}
+// The ONE place that picks the attention entry point of a block (GG_ATTN_ENTRY_*; the dtype code that goes with it is attn_dtype): the launches, the
+// dbias_scratch sizing and the scratch.attn_ds plan all ask it, and gg_attention_route then says what that entry runs.  fp32 / fp32_split: the flash pair.
+// bf16: gg_attention_fwd / _bwd -- except, under the opt-in switches, the windows gg_attention_fwd itself hands to the online-softmax forward (what its
+// route reports: beyond 256 tokens), which take the 16-bit-MFMA window kernels: any forward under attn16 or attn16_train, the backward under attn16_train
+// (a compacted block -- window_map -- is an fp32_split form and never meets the switch).
+static int attn_entry(bool f32, bool attn16, bool attn16_train, const GgAttnArgs& at, bool bwd) {
+    if (f32) return bwd ? GG_ATTN_ENTRY_FLASH_BWD : GG_ATTN_ENTRY_FLASH_FWD;
+    GgAttnRoute fwd;
+    if ((bwd ? attn16_train && !at.window_map : attn16 || attn16_train) && gg_attention_route(&at, GG_ATTN_ENTRY_FWD, 0, &fwd) == 0 &&
+        (fwd.kernel == GG_ATTN_KERNEL_FLASH_FWD_STREAM || fwd.kernel == GG_ATTN_KERNEL_FLASH_FWD_RESIDENT))
+        return bwd ? GG_ATTN_ENTRY_FLASH16_WIN_BWD : GG_ATTN_ENTRY_FLASH16_WIN_FWD;
+    return bwd ? GG_ATTN_ENTRY_BWD : GG_ATTN_ENTRY_FWD;
+}
+static int attn_dtype(bool f32) { return f32 ? 1 : 0; }
 
 // Which fused forms the schedule takes.  The workspace plan decides who owns the tensors a fusion removes and the executor decides who writes
 // them, so there is ONE value per C-ABI call: build_model fills Model::sch from the storage type and the dev switches, both read it there.
@@ -482,7 +512,13 @@ static void plan_build(const Model& m, int B, Plan& p, Layout& L) {
             for (int s = 1; s < 4; ++s) {
                 const auto& st = m.stages[s - 1];
                 const int nw = B * (st.pres / st.ws) * (st.pres / st.ws);
-                if (!gg_attention_flash_single_pass(st.ws * st.ws, 32, st.ws, 1))
+                // the route of this stage's backward with every optional tensor given (bias gradient included: the call with the largest LDS need, so the
+                // one that leaves the single-pass kernels first -- DESIGN.md 5, "One attention route"): does it read a dS region?
+                GgAttnArgs at;
+                GgAttnRoute r;
+                attn_shape(st, B, at);
+                at.dout = at.qkv; at.lddo = at.ldo; at.dqkv = at.out; at.dbias = at.lse; at.ds_scratch = at.lse;
+                if (gg_attention_route(&at, attn_entry(true, false, false, at, true), attn_dtype(true), &r) == 0 && r.reads_ds_scratch)
                     dsmax = std::max(dsmax, gg_attention_flash_ds_scratch_floats(nw, st.heads, st.ws * st.ws) * 4);
             }
             // (under recompute the recompute-off plan decides: p.total differs, and the region selects the flash backward's route)
@@ -720,33 +756,34 @@ static int bn_apply(const Exec& e, const BNP& bn, const Act& a, int64_t M, int a
 }
 // window attention arguments of one TinyVitBlock (forward fields; the caller adds the backward ones)
 static void attn_args(const Exec& e, const StageL& st, const BlockL& l, const BlockAct& a, int B, GgAttnArgs& at) {
-    const int C = st.C;
-    memset(&at, 0, sizeof(at));
-    at.qkv = e.A(a.qkv); at.ld = 3 * C; at.q_off = 0; at.k_off = 32; at.v_off = 64; at.head_stride = 96; at.head_dim = 32;
-    at.num_heads = st.heads; at.tokens_per_window = st.ws * st.ws;
-    at.num_windows = B * (st.pres / st.ws) * (st.pres / st.ws);
-    at.window_size = st.ws; at.map_h = st.pres; at.map_w = st.pres;      // (a padded block: the padded map)
+    attn_shape(st, B, at);
+    at.qkv = e.A(a.qkv);
     at.bias = l.bias_full >= 0 ? e.wc + l.bias_full : nullptr;      // expanded bf16 table (register-resident kernels)
     at.bias_table = e.P(l.t_ab);                                     // compact f32 parameter (online-softmax kernels)
-    at.scale = kAttnScale;
-    at.out = e.A(a.o); at.ldo = C; at.lse = e.F(a.lse);
+    at.out = e.A(a.o); at.lse = e.F(a.lse);
 }
-// (attn16: only the windows gg_attention_fwd itself hands to gg_attention_flash_fwd -- attention.hip, attn_use_flash -- leave that route)
-static bool attn_beyond_256(const GgAttnArgs& at) { return at.tokens_per_window > 256 || at.window_size > 16; }
-static int attention_fwd(const Exec& e, const GgAttnArgs& at) {
-    if ((e.attn16 || e.attn16_train) && attn_beyond_256(at)) return gg_attention_flash16_win_fwd(&at, 0, e.st);
-    return e.f32 ? gg_attention_flash_fwd(&at, 1, e.st) : gg_attention_fwd(&at, e.st);
+static int attention_run(const Exec& e, const GgAttnArgs& at, bool bwd) {
+    switch (attn_entry(e.f32, e.attn16, e.attn16_train, at, bwd)) {
+        case GG_ATTN_ENTRY_FLASH_FWD: return gg_attention_flash_fwd(&at, attn_dtype(e.f32), e.st);
+        case GG_ATTN_ENTRY_FLASH_BWD: return gg_attention_flash_bwd(&at, attn_dtype(e.f32), e.st);
+        case GG_ATTN_ENTRY_FLASH16_WIN_FWD: return gg_attention_flash16_win_fwd(&at, 0, e.st);
+        case GG_ATTN_ENTRY_FLASH16_WIN_BWD: return gg_attention_flash16_win_bwd(&at, 0, e.st);
+        case GG_ATTN_ENTRY_BWD: return gg_attention_bwd(&at, e.st);
+        default: return gg_attention_fwd(&at, e.st);
+    }
 }
-// (attn16_train: the same windows; a compacted block -- window_map -- is an fp32_split form and never meets the switch)
-static bool attn16_bwd_takes(const Exec& e, const GgAttnArgs& at) { return e.attn16_train && attn_beyond_256(at) && !at.window_map; }
-static int attention_bwd(const Exec& e, const GgAttnArgs& at) {
-    if (attn16_bwd_takes(e, at)) return gg_attention_flash16_win_bwd(&at, 0, e.st);
-    return e.f32 ? gg_attention_flash_bwd(&at, 1, e.st) : gg_attention_bwd(&at, e.st);
-}
-// partial rows of the bias gradient's scratch for the kernel the call will reach
-static int64_t attn_dbias_rows(const Exec& e, const GgAttnArgs& at, bool flash) {
-    if (attn16_bwd_takes(e, at)) return gg_attention_flash16_win_dbias_rows(at.num_windows, at.tokens_per_window);
-    return flash ? gg_attention_flash_dbias_rows(at.num_windows, at.tokens_per_window) : (int64_t)at.num_windows + 64;
+static int attention_fwd(const Exec& e, const GgAttnArgs& at) { return attention_run(e, at, false); }
+// The backward with its scratch: the bias gradient's partial rows go to the split-K region where the rows the route's second stage needs (at.dbias is set:
+// the report is about this very call) fit 64 MB -- per-workgroup partials, a deterministic second stage; else float atomics -- and the planned dS region
+// is passed along in the f32 modes (the route says whether it is read).
+static int attention_bwd(const Exec& e, const StageL& st, GgAttnArgs& at) {
+    const Layout& L = *e.L;
+    GgAttnRoute r;
+    if (at.dbias && gg_attention_route(&at, attn_entry(e.f32, e.attn16, e.attn16_train, at, true), attn_dtype(e.f32), &r) == 0 &&
+        r.dbias_rows * st.heads * st.ws * st.ws * 4 <= ((int64_t)64 << 20))
+        at.dbias_scratch = e.F(L.splitk);
+    if (e.f32 && L.attn_ds >= 0 && !attn_switches().no_ds_scratch) at.ds_scratch = e.F(L.attn_ds);
+    return attention_run(e, at, true);
 }
 // padded block: zero-pad a [B, res, res, C] map of the stage to [B, pres, pres, C]; crop such a map back: y = res_in + rowscale[b] * t (y may be res_in)
 static int window_pad(const Exec& e, const StageL& st, const act_t* x, act_t* y) {
@@ -846,9 +883,13 @@ static bool block_compacts(const Exec& e, int s, size_t i) {
                   l.local.w.t_w, l.local.bn.t_g, l.local.bn.t_b})
         if (e.tr(t)) return false;
     if (!(k.fuse_lnbn && k.fuse_lncol && k.fuse_bnbwd)) return false;
-    static const bool attn_nosplit = gg_dev_env("GG_ATTN_NO_SPLIT") != nullptr;      // (dev: the attention backward would leave the kernel that takes the window map)
-    const int nt16 = (int)gg_align(rps, 16) / 16;                                      // (the window shapes of the single-pass split attention backward: 14 x 14, 12 x 12, 7 x 7)
-    if (attn_nosplit || (nt16 != 13 && nt16 != 9 && nt16 != 4)) return false;
+    {   // the attention backward must take the window map: one route does (the single-pass split kernel: 14 x 14, 12 x 12, 7 x 7 windows), every other refuses it
+        GgAttnArgs at;
+        GgAttnRoute r;
+        attn_shape(st, e.B, at);
+        at.dout = at.qkv; at.lddo = at.ldo; at.dqkv = at.out; at.window_map = at.num_windows_dev = (const int*)at.qkv;
+        if (gg_attention_route(&at, GG_ATTN_ENTRY_FLASH_BWD, 1, &r) != 0) return false;
+    }
     struct Lin { const DenseW* w; bool t; int N, K; };
     const Lin lins[8] = {{&l.qkv, false, 3 * C, l.qkv.Kp}, {&l.proj, false, C, l.proj.Kp}, {&l.fc1, false, hid, l.fc1.Kp}, {&l.fc2, false, C, l.fc2.Kp},
                          {&l.fc2, true, hid, C}, {&l.fc1, true, C, hid}, {&l.proj, true, C, C}, {&l.qkv, true, C, 3 * C}};
@@ -1148,7 +1189,7 @@ static int block_bwd(const Exec& e, int s, size_t i, int slot, const GradBufs& g
         attn_args(e, st, l, a, B, at);
         at.dout = t_a; at.lddo = C; at.dqkv = t_b;
         at.window_map = l1 + GG_DROP_LIST_HEAD; at.num_windows_dev = l1;
-        GG_TRY(attention_bwd(e, at));
+        GG_TRY(attention_run(e, at, true));      // (frozen block, single-pass kernel: no bias gradient, no dS region)
         GG_TRY(gemm(e, t_b, 3 * C, e.Wt(l.qkv), l.qkv.Np, t_a, C, M, C, 3 * C, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, &cc1));
         return gg_layernorm_bwd_map((const float*)t_a, (const float*)e.A(a.x0), e.F(a.mean1), e.F(a.rstd1), e.P(l.ln1.t_g), M, C, (const float*)t_c, (float*)dx, nullptr,
                                     l1 + GG_DROP_LIST_HEAD + B, rps, e.st);
@@ -1205,12 +1246,7 @@ static int block_bwd(const Exec& e, int s, size_t i, int slot, const GradBufs& g
         attn_args(e, st, l, a, B, at);
         at.dout = t_a; at.lddo = C; at.dqkv = t_b;                                                         // dqkv -> t_b  [Mp, 3C]
         at.dbias = e.tr(l.t_ab) ? e.Gd(l.t_ab) : nullptr;
-        const bool flash = e.f32 || at.tokens_per_window > 256 || st.ws > 16;
-        const int64_t prow = attn_dbias_rows(e, at, flash);
-        if (at.dbias && prow * st.heads * st.ws * st.ws * 4 <= ((int64_t)64 << 20)) at.dbias_scratch = e.F(L.splitk);
-        static const bool ds_off_p = gg_dev_env("GG_ATTN_NO_DS_SCRATCH") != nullptr;
-        if (e.f32 && L.attn_ds >= 0 && !ds_off_p) at.ds_scratch = e.F(L.attn_ds);
-        GG_TRY(attention_bwd(e, at));
+        GG_TRY(attention_bwd(e, st, at));
         GG_TRY(gemm(e, t_b, 3 * C, e.Wt(l.qkv), l.qkv.Np, t_a, C, Mp, C, 3 * C));                          // da -> t_a  [Mp, C]
         if (e.tr(l.qkv.t_w)) {
             GG_TRY(dense_wgrad(e, l.qkv, e.A(a.a), C, t_b, 3 * C, Mp, nullptr, 0, false));
@@ -1234,13 +1270,7 @@ static int block_bwd(const Exec& e, int s, size_t i, int slot, const GradBufs& g
     attn_args(e, st, l, a, B, at);
     at.dout = t_a; at.lddo = C; at.dqkv = t_b;
     at.dbias = e.tr(l.t_ab) ? e.Gd(l.t_ab) : nullptr;
-    const bool flash = e.f32 || at.tokens_per_window > 256 || st.ws > 16;
-    const int64_t prow = attn_dbias_rows(e, at, flash);
-    if (at.dbias && prow * st.heads * st.ws * st.ws * 4 <= ((int64_t)64 << 20))
-        at.dbias_scratch = e.F(L.splitk);      // per-workgroup partials -> deterministic second stage
-    static const bool ds_off = gg_dev_env("GG_ATTN_NO_DS_SCRATCH") != nullptr;
-    if (e.f32 && L.attn_ds >= 0 && !ds_off) at.ds_scratch = e.F(L.attn_ds);
-    GG_TRY(attention_bwd(e, at));
+    GG_TRY(attention_bwd(e, st, at));
     // da = dqkv . Wqkv                                                 -> t_a  [M, C]
     GG_TRY(gemm(e, t_b, 3 * C, e.Wt(l.qkv), l.qkv.Np, t_a, C, M, C, 3 * C));
     if (e.tr(l.qkv.t_w)) {

@@ -555,16 +555,16 @@ def attention_flash(qkv, *, num_windows, tokens_per_window, num_heads, head_dim,
     dqkv = torch.zeros_like(qkv)
     dbias = torch.zeros_like(bias_table) if (want_dbias and bias_table is not None) else None
     a.dout, a.lddo, a.dqkv, a.dbias = _p(dout, DT, "dout"), dout.stride(0), _p(dqkv), _p(dbias)
-    scratch = None
-    if dbias is not None and deterministic_dbias:
-        rows = L.lib().gg_attention_flash_dbias_rows(num_windows, tokens_per_window)
-        scratch = torch.empty((rows * num_heads * window_size * window_size,), dtype=F32, device=qkv.device)
-        a.dbias_scratch = _p(scratch)
     a.out, a.ldo, a.lse = _p(out, DT, "out"), out.stride(0), _p(lse, F32, "lse")
     ds = None
     if ds_handoff:
         ds = torch.empty((L.lib().gg_attention_flash_ds_scratch_floats(num_windows, num_heads, tokens_per_window),), dtype=F32, device=qkv.device)
         a.ds_scratch = _p(ds)
+    scratch = None
+    if dbias is not None and deterministic_dbias:      # the partial rows of the route these very arguments take
+        rows = L.attention_route(a, "FLASH_BWD", dt).dbias_rows
+        scratch = torch.empty((rows * num_heads * window_size * window_size,), dtype=F32, device=qkv.device)
+        a.dbias_scratch = _p(scratch)
     L.check(L.lib().gg_attention_flash_bwd(C.byref(a), dt, L.stream()), "gg_attention_flash_bwd")
     return dqkv, dbias
 
@@ -711,11 +711,11 @@ def attention(qkv, *, num_windows, tokens_per_window, num_heads, head_dim, q_off
     dqkv = torch.zeros_like(qkv)
     dbias = torch.zeros_like(bias) if (want_dbias and bias is not None) else None
     a.dout, a.lddo, a.dqkv, a.dbias = _p(dout, BF16, "dout"), dout.stride(0), _p(dqkv), _p(dbias)
-    scratch = None
-    if dbias is not None:      # per-window partials, summed deterministically in a second stage
-        scratch = torch.empty(((num_windows + 64) * num_heads * window_size * window_size,), dtype=F32, device=qkv.device)
-        a.dbias_scratch = _p(scratch)
     a.out, a.ldo, a.lse = _p(out, BF16, "out"), out.stride(0), _p(lse, F32, "lse")
+    scratch = None
+    if dbias is not None:      # per-workgroup partials of the route these very arguments take, summed deterministically in a second stage
+        scratch = torch.empty((L.attention_route(a, "BWD").dbias_rows * num_heads * window_size * window_size,), dtype=F32, device=qkv.device)
+        a.dbias_scratch = _p(scratch)
     L.check(L.lib().gg_attention_bwd(C.byref(a), L.stream()), "gg_attention_bwd")
     return dqkv, dbias
 

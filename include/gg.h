@@ -196,8 +196,9 @@ typedef struct GgAttnArgs {
     const void* dout; int64_t lddo;       /* backward */
     void* dqkv;                           /* backward: same layout as qkv */
     float* dbias;                         /* backward: f32 [num_heads][ws*ws], ACCUMULATED, or NULL */
-    float* dbias_scratch;                 /* optional f32 [(num_windows + 64) * num_heads * ws*ws]: per-window partials, reduced in a
-                                             second deterministic stage; NULL: float atomics */
+    float* dbias_scratch;                 /* optional f32 [rows][num_heads][ws*ws], rows = GgAttnRoute.dbias_rows of gg_attention_route (include/
+                                             gg_attn_route.h) for this call: per-workgroup partials, reduced in a second deterministic stage;
+                                             NULL: float atomics */
     float* lse;                           /* f32 [tokens][num_heads] row log-sum-exp: forward writes (may be NULL), backward reads;
                                              backward also reads `out` (the forward result) */
     const float* bias_table;              /* COMPACT attention_biases f32 [num_heads][ws*ws] (index |dy|*ws+|dx|, timm's first-seen order)
@@ -238,10 +239,13 @@ int gg_attention_fwd_f16(const GgAttnArgs* args, void* stream);
  * give the same bits.  Error against fp64 at or below dtype 1's. */
 int gg_attention_flash_fwd(const GgAttnArgs* args, int dtype, void* stream);
 int gg_attention_flash_bwd(const GgAttnArgs* args, int dtype, void* stream);
+/* dbias_scratch rows that suffice for every route of gg_attention_flash_bwd: the two-pass route's (one partial row per 64-key tile of every window, plus
+ * the 64 rows they are folded into) -- the maximum over the routes; the single-pass routes need num_windows + 64 (gg_attention_route has each call's own) */
 int64_t gg_attention_flash_dbias_rows(int num_windows, int tokens_per_window);
 int64_t gg_attention_flash_ds_scratch_floats(int num_windows, int num_heads, int tokens_per_window);
-/* 1 when gg_attention_flash_bwd runs its single-pass kernel for this window (at most 256 tokens: Q, dO and the dQ accumulator of a whole window fit
- * one CU's LDS): ds_scratch is then neither needed nor read -- workspace planners skip it. */
+/* 1 when the window fits gg_attention_flash_bwd's single-pass kernel (at most 256 tokens: Q, dO and the dQ accumulator of a whole window fit one CU's
+ * LDS): the test the route decision applies behind its split kernels, which are single-pass too -- so 1 means ds_scratch is neither needed nor read.
+ * (GgAttnRoute.reads_ds_scratch of gg_attention_route answers for a whole call, dtype included: what the workspace planners ask.) */
 int gg_attention_flash_single_pass(int tokens_per_window, int head_dim, int window_size, int with_dbias);
 
 /* ---------------------------------------------------------------- experiment: fp32-accurate GEMM on the bf16 matrix pipe

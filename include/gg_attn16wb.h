@@ -46,7 +46,7 @@ int gg_attention_flash16_win_bwd(const GgAttnArgs* args, int dtype, void* stream
 /* calls of gg_attention_flash16_win_bwd enqueued by this process so far: one count per call, however many kernels it launches (tests count routes with it) */
 int64_t gg_attention_flash16_win_bwd_calls(void);
 /* partial rows of dbias_scratch a caller must provide: one per workgroup of the dK / dV pass and head (num_windows * ceil(tokens_per_window / 128)) plus the
- * GG_REDUCE_SLICES (64) rows the second stage folds into */
+ * GG_REDUCE_SLICES (64) rows the second stage folds into -- the entry's one route (GgAttnRoute.dbias_rows of include/gg_attn_route.h) */
 int64_t gg_attention_flash16_win_dbias_rows(int num_windows, int tokens_per_window);
 
 /* on != 0: a TRAINING step of TinyViT in the bf16 mode (act_dtype 0) sends the attention of every block whose window gg_attention_fwd would hand to

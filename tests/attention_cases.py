@@ -517,52 +517,62 @@ def check(c, got, label, rounded_bias=False, tensors=None, split_products=False)
 
 # ------------------------------------------------------------------------------------------- the routes of tests/test_gpu_attention_conditioning.py
 def _route(name, api, layout, N, hd, *, ws=0, map_hw=0, windows=2, storage="f32", bias=False, causal=False, bwd=True, split=False, ds_handoff=False, dtype_code=None,
-           kernels=""):
+           kernels=()):
     split_products = storage == "f32" and (split or api == "causal" or (hd == 32 and (N + 15) // 16 in (4, 9, 13)))
+    assert len(kernels) == (2 if bwd else 1)
     return dict(name=name, api=api, layout=layout, N=N, hd=hd, ws=ws, map_hw=map_hw or ws, windows=windows, heads=2, storage=storage, bias=bias, causal=causal, bwd=bwd,
-                split=split, ds_handoff=ds_handoff, dtype_code=dtype_code, kernels=kernels, split_products=split_products)
+                split=split, ds_handoff=ds_handoff, dtype_code=dtype_code, kernels=tuple(kernels), split_products=split_products)
 
 
 # api: "flash" = ops.attention_flash (gg_attention_flash_fwd / _bwd), "attention" = ops.attention (gg_attention_fwd / _fwd_f16 / _bwd), "causal" = gg_attention_causal_fwd / _bwd.
 # The table and the reading of the dispatch behind it are in the docstring of tests/test_gpu_attention_conditioning.py.
+# kernels: ((GG_ATTN_KERNEL_* name, variant) of the forward, the same of the backward) that gg_attention_route (include/gg_attn_route.h) must report for the case --
+# names as in geoguessr_ai_amd._lib.ATTN_KERNELS; tests/test_attention_route_cpu.py holds the report to them, the GPU digest test asserts them on the arguments it launches.
+_SPLIT = lambda n: (("FLASH_FWD_SPLIT", n), ("FLASH_BWD_SPLIT", n))
+_RES, _RES_TAIL, _FWD_STREAM = ("FLASH_FWD_RESIDENT", 0), ("FLASH_FWD_RESIDENT", 1), ("FLASH_FWD_STREAM", 0)
+_FUSED = lambda n=0: ("FLASH_BWD_FUSED", n)
+_STREAM, _STREAM_DS = (_FWD_STREAM, ("FLASH_BWD_STREAM", 0)), (_FWD_STREAM, ("FLASH_BWD_STREAM_DS", 0))
+_SPLIT64 = (("FLASH64_FWD_SPLIT", 0), ("FLASH64_BWD_SPLIT", 0))
+_CAUSAL_BF16 = (_FWD_STREAM, _FUSED())
+_ATTN = lambda n: (("FWD", n), ("BWD", n))
 ROUTES = [
-    _route("split_f32_7x7", "flash", "tinyvit", 49, 32, ws=7, map_hw=14, windows=8, bias=True, kernels="flash_fwd_split_kernel<float,3,4> + flash_bwd_split_kernel<float,3,*,4>"),
-    _route("split_f32_12x12", "flash", "tinyvit", 144, 32, ws=12, bias=True, kernels="flash_fwd_split_kernel<float,3,9> + flash_bwd_split_kernel<float,3,*,9>"),
-    _route("split_f32_14x14", "flash", "tinyvit", 196, 32, ws=14, bias=True, kernels="flash_fwd_split_kernel<float,3,13> + flash_bwd_split_kernel<float,3,*,13>"),
-    _route("split_f32_linear200", "flash", "clip", 200, 32, kernels="the 13-strip split kernels without a window geometry or bias"),
-    _route("resident_f32_hd32_17", "flash", "clip", 17, 32, kernels="flash_fwd_kernel<float,32,true> (2 strips, no tail) + flash_bwd_fused_kernel<float,32,false,0>"),
-    _route("resident_f32_hd32_80", "flash", "clip", 80, 32, kernels="flash_fwd_kernel<float,32,true> with the cooperative tail + flash_bwd_fused_kernel<float,32> with 4 owner waves"),
-    _route("resident_f32_hd64_50", "flash", "clip", 50, 64, kernels="flash_fwd_kernel<float,64,true> (4 strips, no tail) + flash_bwd_fused_kernel<float,64,false,4>"),
-    _route("resident_f32_hd64_80", "flash", "clip", 80, 64, kernels="flash_fwd_kernel<float,64,true> with the cooperative tail + flash_bwd_fused_kernel<float,64,false,0>"),
-    _route("fused_f32_16x16", "flash", "tinyvit", 256, 32, ws=16, bias=True, kernels="flash_fwd_kernel<float,32,false> (streaming: 77 KB > 64 KB) + flash_bwd_fused_kernel<float,32,*,0>"),
-    _route("stream_f32_hd64_200", "flash", "clip", 200, 64, kernels="flash_fwd_kernel<float,64,false> + flash_bwd_dq_kernel<float,64> / flash_bwd_dkv_kernel<float,64,false>"),
-    _route("stream_f32_hd64_257", "flash", "clip", 257, 64, kernels="the same, 5 tiles with one live row in the last"),
-    _route("stream_f32_24x24", "flash", "tinyvit", 576, 32, ws=24, bias=True, kernels="flash_fwd_kernel<float,32,false> + flash_bwd_dq_kernel<float,32> / flash_bwd_dkv_kernel<float,32,*> with bias"),
-    _route("handoff_f32_hd64_200", "flash", "clip", 200, 64, ds_handoff=True, kernels="flash_bwd_dkv_kernel<.., ds handoff> + flash_bwd_dq_ds_kernel"),
-    _route("handoff_f32_24x24", "flash", "tinyvit", 576, 32, ws=24, bias=True, ds_handoff=True, kernels="the same with bias and dbias"),
-    _route("dtype3_65", "flash", "clip", 65, 64, split=True, kernels="flash64_split_q_kernel<3,false|true> + flash64_split_dkv_kernel<3>"),
-    _route("dtype3_200", "flash", "clip", 200, 64, split=True, kernels="the same, 4 tiles"),
-    _route("flash_bf16_hd64_80", "flash", "clip", 80, 64, storage="bf16", kernels="flash_fwd_kernel<bf16,64,true> + flash_bwd_fused_kernel<bf16,64>"),
-    _route("flash_bf16_hd64_257", "flash", "clip", 257, 64, storage="bf16", kernels="flash_fwd_kernel<bf16,64,false> + the two-pass bf16 backward"),
-    _route("flash_bf16_24x24", "flash", "tinyvit", 576, 32, ws=24, bias=True, storage="bf16", kernels="the streaming bf16 kernels with bias (tiny_vit_21m_384 stage 2)"),
-    _route("causal_bf16_17", "causal", "clip", 17, 64, storage="bf16", causal=True, dtype_code=0, kernels="flash_fwd_kernel<bf16,64,false,true> + flash_bwd_fused_kernel<bf16,64,false,0,true>"),
-    _route("causal_bf16_77", "causal", "clip", 77, 64, storage="bf16", causal=True, dtype_code=0, kernels="the same, 2 tiles / 5 strips"),
-    _route("causal_f32_17", "causal", "clip", 17, 64, causal=True, dtype_code=1, kernels="flash64_split_q_kernel<3,*,true> + flash64_split_dkv_kernel<3,true>"),
-    _route("causal_f32_77", "causal", "clip", 77, 64, causal=True, dtype_code=1, kernels="the same, 2 tiles"),
-    _route("causal_split_17", "causal", "clip", 17, 64, causal=True, dtype_code=3, kernels="dtype 3: the same kernels as dtype 1"),
-    _route("causal_split_77", "causal", "clip", 77, 64, causal=True, dtype_code=3, kernels="dtype 3: the same kernels as dtype 1"),
-    _route("attn_bf16_7x7", "attention", "tinyvit", 49, 32, ws=7, map_hw=14, windows=8, storage="bf16", bias=True, kernels="attn_fwd_kernel<32,4> + attn_bwd_kernel<32,4,*>"),
-    _route("attn_bf16_10x10", "attention", "tinyvit", 100, 32, ws=10, storage="bf16", bias=True, kernels="attn_fwd_kernel<32,10> + attn_bwd_kernel<32,10,*>"),
-    _route("attn_bf16_13x13", "attention", "tinyvit", 169, 32, ws=13, storage="bf16", bias=True, kernels="attn_fwd_kernel<32,14> + attn_bwd_kernel<32,14,*>"),
-    _route("attn_bf16_16x16", "attention", "tinyvit", 256, 32, ws=16, storage="bf16", bias=True, kernels="attn_fwd_kernel<32,16> + attn_bwd_kernel<32,16,*>"),
-    _route("attn_bf16_12x12", "attention", "tinyvit", 144, 32, ws=12, storage="bf16", bias=True, kernels="attn_fwd_kernel<32,10> + flash_bwd_split_kernel<bf16,1,*,9> (rounded bias)"),
-    _route("attn_bf16_14x14", "attention", "tinyvit", 196, 32, ws=14, storage="bf16", bias=True, kernels="attn_fwd_kernel<32,14> + flash_bwd_split_kernel<bf16,1,*,13> (rounded bias)"),
+    _route("split_f32_7x7", "flash", "tinyvit", 49, 32, ws=7, map_hw=14, windows=8, bias=True, kernels=_SPLIT(4)),
+    _route("split_f32_12x12", "flash", "tinyvit", 144, 32, ws=12, bias=True, kernels=_SPLIT(9)),
+    _route("split_f32_14x14", "flash", "tinyvit", 196, 32, ws=14, bias=True, kernels=_SPLIT(13)),
+    _route("split_f32_linear200", "flash", "clip", 200, 32, kernels=_SPLIT(13)),      # the 13-strip split kernels without a window geometry or bias
+    _route("resident_f32_hd32_17", "flash", "clip", 17, 32, kernels=(_RES, _FUSED())),      # 2 strips, no tail
+    _route("resident_f32_hd32_80", "flash", "clip", 80, 32, kernels=(_RES_TAIL, _FUSED())),      # 5 strips: the cooperative tail; single pass with 4 owner waves
+    _route("resident_f32_hd64_50", "flash", "clip", 50, 64, kernels=(_RES, _FUSED(4))),      # 4 strips, no tail
+    _route("resident_f32_hd64_80", "flash", "clip", 80, 64, kernels=(_RES_TAIL, _FUSED())),      # head dim 64: 5 owner waves (4 < 2 * 64 / 16)
+    _route("fused_f32_16x16", "flash", "tinyvit", 256, 32, ws=16, bias=True, kernels=(_FWD_STREAM, _FUSED())),      # forward streams: 77 KB > 64 KB
+    _route("stream_f32_hd64_200", "flash", "clip", 200, 64, kernels=_STREAM),
+    _route("stream_f32_hd64_257", "flash", "clip", 257, 64, kernels=_STREAM),      # 5 tiles with one live row in the last
+    _route("stream_f32_24x24", "flash", "tinyvit", 576, 32, ws=24, bias=True, kernels=_STREAM),
+    _route("handoff_f32_hd64_200", "flash", "clip", 200, 64, ds_handoff=True, kernels=_STREAM_DS),
+    _route("handoff_f32_24x24", "flash", "tinyvit", 576, 32, ws=24, bias=True, ds_handoff=True, kernels=_STREAM_DS),
+    _route("dtype3_65", "flash", "clip", 65, 64, split=True, kernels=_SPLIT64),
+    _route("dtype3_200", "flash", "clip", 200, 64, split=True, kernels=_SPLIT64),      # 4 tiles
+    _route("flash_bf16_hd64_80", "flash", "clip", 80, 64, storage="bf16", kernels=(_RES_TAIL, _FUSED())),
+    _route("flash_bf16_hd64_257", "flash", "clip", 257, 64, storage="bf16", kernels=_STREAM),
+    _route("flash_bf16_24x24", "flash", "tinyvit", 576, 32, ws=24, bias=True, storage="bf16", kernels=_STREAM),      # tiny_vit_21m_384 stage 2
+    _route("causal_bf16_17", "causal", "clip", 17, 64, storage="bf16", causal=True, dtype_code=0, kernels=_CAUSAL_BF16),
+    _route("causal_bf16_77", "causal", "clip", 77, 64, storage="bf16", causal=True, dtype_code=0, kernels=_CAUSAL_BF16),      # 2 tiles / 5 strips
+    _route("causal_f32_17", "causal", "clip", 17, 64, causal=True, dtype_code=1, kernels=_SPLIT64),
+    _route("causal_f32_77", "causal", "clip", 77, 64, causal=True, dtype_code=1, kernels=_SPLIT64),
+    _route("causal_split_17", "causal", "clip", 17, 64, causal=True, dtype_code=3, kernels=_SPLIT64),      # dtype 3: the same kernels as dtype 1
+    _route("causal_split_77", "causal", "clip", 77, 64, causal=True, dtype_code=3, kernels=_SPLIT64),
+    _route("attn_bf16_7x7", "attention", "tinyvit", 49, 32, ws=7, map_hw=14, windows=8, storage="bf16", bias=True, kernels=_ATTN(4)),
+    _route("attn_bf16_10x10", "attention", "tinyvit", 100, 32, ws=10, storage="bf16", bias=True, kernels=_ATTN(10)),
+    _route("attn_bf16_13x13", "attention", "tinyvit", 169, 32, ws=13, storage="bf16", bias=True, kernels=_ATTN(14)),
+    _route("attn_bf16_16x16", "attention", "tinyvit", 256, 32, ws=16, storage="bf16", bias=True, kernels=_ATTN(16)),
+    _route("attn_bf16_12x12", "attention", "tinyvit", 144, 32, ws=12, storage="bf16", bias=True, kernels=(("FWD", 10), ("FLASH_BWD_SPLIT", 9))),      # rounded bias
+    _route("attn_bf16_14x14", "attention", "tinyvit", 196, 32, ws=14, storage="bf16", bias=True, kernels=(("FWD", 14), ("FLASH_BWD_SPLIT", 13))),      # rounded bias
     _route("attn_bf16_grouped_7x7", "attention", "tinyvit", 49, 32, ws=7, map_hw=35, windows=75, storage="bf16", bias=True,
-           kernels="attn_fwd_small_kernel<32,8> + attn_bwd_small_kernel<32,8,*>, 75 windows: a ragged last group"),
-    _route("attn_bf16_clip_50", "attention", "clip", 50, 64, storage="bf16", bwd=False, kernels="attn_fwd_kernel<64,4> (the backward of head dim 64 is the flash one above)"),
-    _route("attn_f16_50", "attention", "clip", 50, 64, storage="f16", bwd=False, kernels="attn_fwd_kernel<64,4,f16>"),
-    _route("attn_f16_197", "attention", "clip", 197, 64, storage="f16", bwd=False, kernels="attn_fwd_kernel<64,14,f16>"),
-    _route("attn_f16_257", "attention", "clip", 257, 64, storage="f16", bwd=False, kernels="flash_fwd_kernel<f16,64,false> (beyond 256 tokens)"),
+           kernels=(("FWD_GROUPED", 0), ("BWD_GROUPED", 0))),      # 75 windows: a ragged last group
+    _route("attn_bf16_clip_50", "attention", "clip", 50, 64, storage="bf16", bwd=False, kernels=(("FWD", 4),)),      # (the backward of head dim 64 is the flash one above)
+    _route("attn_f16_50", "attention", "clip", 50, 64, storage="f16", bwd=False, kernels=(("FWD", 4),)),
+    _route("attn_f16_197", "attention", "clip", 197, 64, storage="f16", bwd=False, kernels=(("FWD", 14),)),
+    _route("attn_f16_257", "attention", "clip", 257, 64, storage="f16", bwd=False, kernels=(_FWD_STREAM,)),      # beyond 256 tokens
 ]
 ROUTE = {r["name"]: r for r in ROUTES}
 

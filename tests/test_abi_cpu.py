@@ -53,6 +53,11 @@ def test_struct_layouts_match_header(L):
         sizes = [int(v) for v in subprocess.check_output([os.path.join(d, "t")]).split()]
     got = [C.sizeof(x) for x in (L.GemmArgs, L.AttnArgs, L.GeoHeadArgs, L.ProtoRefineArgs, L.TinyVitCfg, L.ClipCfg, L.Split3Args)]
     assert got == sizes
+    src = '#include <stdio.h>\n#include "gg_attn_route.h"\nint main(){printf("%zu %d %d\\n",sizeof(GgAttnRoute),GG_ATTN_ENTRY_COUNT,GG_ATTN_KERNEL_COUNT);return 0;}'
+    with tempfile.TemporaryDirectory() as d:
+        open(os.path.join(d, "t.c"), "w").write(src)
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "t.c"), "-o", os.path.join(d, "t")])
+        assert [int(v) for v in subprocess.check_output([os.path.join(d, "t")]).split()] == [C.sizeof(L.AttnRoute), len(L.ATTN_ENTRIES), len(L.ATTN_KERNELS)]
 
 
 def test_tinyvit_table_matches_oracle_spec(L):
