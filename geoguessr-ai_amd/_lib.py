@@ -415,6 +415,18 @@ JSCAN_SIGNATURES = {
 }
 JSCAN_SYMBOLS = list(JSCAN_SIGNATURES)
 
+# every exported symbol of include/gg_jprog.h (the JPEG decoder's opt-in mode for progressive files: a plan that also takes SOF2, with a scan table; the entropy decode in rounds of scans), bound from the same libgg.so
+JPROG_MAX_SCANS = 64                      # GG_JPROG_MAX_SCANS
+JPROG_SIGNATURES = {
+    "gg_jprog_refusal_name": (C.c_char_p, [_I]),
+    "gg_jprog_plan_create": (_I, [_P, _P, _I, C.POINTER(_P)]),
+    "gg_jprog_plan_scans": (_I, [_P, _I]),
+    "gg_jprog_plan_rounds": (_I, [_P]),
+    "gg_jprog_workspace_bytes": (_L, [_P]),
+    "gg_jprog_decode": (_I, [_P, _P, _L, _P, _L, _P, _P, _L, _P]),
+}
+JPROG_SYMBOLS = list(JPROG_SIGNATURES)
+
 # every exported symbol of include/gg_pano.h (the panorama fine-tune's input path for whole batches: Pillow resize, ToTensor, bilinear interpolation, normalise, slot table), bound from the same libgg.so
 PANO_MAX_SLOTS, PANO_MAX_IMAGES, PANO_MAX_TARGET = 4096, 4096, 2048        # GG_PANO_MAX_SLOTS, GG_PANO_MAX_IMAGES, GG_PANO_MAX_TARGET
 PANO_SIGNATURES = {
@@ -494,7 +506,7 @@ def lib() -> C.CDLL:
             raise GgError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JSCAN_SIGNATURES.items()) + list(PANO_SIGNATURES.items()) + list(ATTN16_SIGNATURES.items()) + list(ATTN16W_SIGNATURES.items()) + list(ATTN16B_SIGNATURES.items()) + list(ATTN16WB_SIGNATURES.items()) + list(ATTN_ROUTE_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JSCAN_SIGNATURES.items()) + list(JPROG_SIGNATURES.items()) + list(PANO_SIGNATURES.items()) + list(ATTN16_SIGNATURES.items()) + list(ATTN16W_SIGNATURES.items()) + list(ATTN16B_SIGNATURES.items()) + list(ATTN16WB_SIGNATURES.items()) + list(ATTN_ROUTE_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the library lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -550,6 +562,7 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(root), "include", "gg_eval.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_jpeg.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_jscan.h"))
+    files.append(os.path.join(os.path.dirname(root), "include", "gg_jprog.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_pano.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_attn16.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_attn16w.h"))

@@ -11,11 +11,17 @@
 // The opt-in mode of include/gg_jscan.h (a plan with a sub-segment table; gg_jscan_decode) puts four passes in the place of jpeg_entropy_kernel for segments that are
 // long enough to be cut -- jscan_speculate_kernel, jscan_resolve_kernel, jscan_write_kernel, jscan_dc_prefix_kernel + jscan_dc_apply_kernel: their lanes run the
 // jscan_* functions of jpeg_entropy.h -- and keeps the other three kernels.
+// The opt-in mode of include/gg_jprog.h (a plan that also takes SOF2 files, with a scan table; gg_jprog_decode) zero-fills the progressive images' coefficients
+// (jprog_fill_kernel) and runs jprog_entropy_kernel once per ROUND of scans: one lane per (scan, restart segment) runs jprog_decode_segment (jpeg_progressive.h), or
+// jpeg_decode_segment for the one scan of a baseline image; scans of one round touch disjoint coefficients, the stream orders the rounds.  The other three kernels
+// are kept as they are.
 #include "common.h"
 #include "../../include/gg.h"
 #include "../../include/gg_jpeg.h"
 #include "../../include/gg_jscan.h"
+#include "../../include/gg_jprog.h"
 #include "jpeg_entropy.h"
+#include "jpeg_progressive.h"
 #include <string.h>
 #include <algorithm>
 #include <map>
@@ -32,14 +38,21 @@ struct JpegImgDev {
     int32_t H, W, ncomp, hs, vs;          // hs, vs: luma sampling (chroma is 1 x 1)
     int32_t mcux, mcuy, bpm;              // MCUs per row / column, blocks per MCU
     int32_t seg0, nseg;
-    int32_t dc[3], ac[3];                 // Huffman table indices per component
-    int32_t pad[2];
+    int32_t dc[3], ac[3];                 // Huffman table indices per component (baseline images)
+    int32_t prog, scan0;                  // plans of gg_jprog_plan_create: 1 for a progressive image; the image's first scan in the scan table
 };
 struct JpegSegDev {
     int64_t begin, end;                   // byte range in the stream buffer
-    int32_t img, mcu0, mcus, pad;
+    int32_t img, mcu0, mcus, scan;        // mcu0, mcus: in a non-interleaved progressive scan, blocks of the component in raster order; scan: gg_jprog_plan_create only
 };
-static_assert(sizeof(JpegImgDev) == 112 && sizeof(JpegSegDev) == 32, "table layout");
+struct JprogScanDev {                     // one scan (gg_jprog_plan_create); a baseline image has one, with base = 1
+    int32_t img, base, cmask;             // cmask: the scan's components, bit c
+    int32_t Ss, Se, Ah, Al;
+    int32_t dc[3], ac;                    // Huffman table indices: DC by component (DC first scans), AC (AC scans)
+    int32_t bw, bh;                       // the block grid a non-interleaved scan walks; MCUs per row / column for an interleaved one
+    int32_t round, seg0, nseg;
+};
+static_assert(sizeof(JpegImgDev) == 112 && sizeof(JpegSegDev) == 32 && sizeof(JprogScanDev) == 64, "table layout");
 static_assert(sizeof(GgJpegInfo) == 48, "info layout");
 
 #define JPEG_LDS_MAX_BYTES (48 * 1024)    // unique Huffman tables of a batch up to this size are staged in LDS (128 tables; the four standard ones take 1.5 KB)
@@ -73,6 +86,61 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
     for (int c = 0; c < 3; ++c) { job.dc[c] = tabs + d.dc[c] * JPEG_HUFF_WORDS; job.ac[c] = tabs + d.ac[c] * JPEG_HUFF_WORDS; }
     job.coef = coef + (d.coef_off >> 1) + (int64_t)sg.mcu0 * d.bpm * 64;
     seg_status[s] = jpeg_decode_segment(job);
+}
+
+// ---- include/gg_jprog.h: blockIdx.y: image; the coefficients of a progressive image are zeroed (its scans write only what they code)
+__global__ __launch_bounds__(256) void jprog_fill_kernel(const JpegImgDev* __restrict__ imgs, int16_t* __restrict__ coef) {
+    const JpegImgDev d = imgs[blockIdx.y];
+    if (!d.prog) return;
+    const int64_t n = (int64_t)d.mcux * d.mcuy * d.bpm * 8;                 // 16-byte groups: a block is eight of them
+    uint4* o = reinterpret_cast<uint4*>(coef + (d.coef_off >> 1));
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) o[i] = make_uint4(0, 0, 0, 0);
+}
+// one lane per (scan, restart segment) of one round: order[0, n) names the round's segments
+template <bool LDS>
+__global__ __launch_bounds__(64) void jprog_entropy_kernel(const uint8_t* __restrict__ stream, const JpegImgDev* __restrict__ imgs, const JpegSegDev* __restrict__ segs,
+                                                           const JprogScanDev* __restrict__ scans, const int32_t* __restrict__ order, const uint32_t* __restrict__ huff,
+                                                           int nhuff, int n, int lanes, int16_t* __restrict__ coef, int32_t* __restrict__ seg_status) {
+    extern __shared__ uint32_t jpeg_lds[];
+    const uint32_t* tabs = huff;
+    if (LDS) {
+        for (int i = threadIdx.x; i < nhuff * JPEG_HUFF_WORDS; i += 64) jpeg_lds[i] = huff[i];
+        __syncthreads();
+        tabs = jpeg_lds;
+    }
+    if ((int)threadIdx.x >= lanes) return;
+    const int i = blockIdx.x * lanes + threadIdx.x;
+    if (i >= n) return;
+    const int s = order[i];
+    const JpegSegDev sg = segs[s];
+    const JpegImgDev& d = imgs[sg.img];
+    const JprogScanDev sc = scans[sg.scan];
+    int16_t* cimg = coef + (d.coef_off >> 1);
+    if (sc.base) {                                                          // the lane of jpeg_entropy_kernel
+        JpegSegJob job;
+        job.data = stream + sg.begin;
+        job.nbytes = sg.end - sg.begin;
+        job.mcus = sg.mcus;
+        job.ncomp = d.ncomp;
+        job.blocks[0] = d.hs * d.vs; job.blocks[1] = job.blocks[2] = d.ncomp == 3 ? 1 : 0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { job.dc[c] = tabs + d.dc[c] * JPEG_HUFF_WORDS; job.ac[c] = tabs + d.ac[c] * JPEG_HUFF_WORDS; }
+        job.coef = cimg + (int64_t)sg.mcu0 * d.bpm * 64;
+        seg_status[s] = jpeg_decode_segment(job);
+        return;
+    }
+    JprogJob job;
+    job.data = stream + sg.begin;
+    job.nbytes = sg.end - sg.begin;
+    job.unit0 = sg.mcu0; job.units = sg.mcus;
+    job.cmask = sc.cmask; job.Ss = sc.Ss; job.Se = sc.Se; job.Ah = sc.Ah; job.Al = sc.Al;
+    job.ncomp = d.ncomp; job.hs = d.hs; job.vs = d.vs; job.mcux = d.mcux; job.bpm = d.bpm;
+    job.bw = sc.bw; job.bh = sc.bh;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) job.dc[c] = tabs + sc.dc[c] * JPEG_HUFF_WORDS;
+    job.ac = tabs + sc.ac * JPEG_HUFF_WORDS;
+    job.coef = cimg;
+    seg_status[s] = jprog_decode_segment(job);
 }
 
 __device__ const unsigned char JPEG_ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28,
@@ -381,6 +449,15 @@ struct JpegParsed {
     uint16_t q[4][64];
     JpegHuffRaw huff[2][4];               // [class: 0 DC, 1 AC][id]
     std::vector<std::pair<int64_t, int64_t>> segs;      // byte ranges in the file
+    // jprog_parse only: a progressive file's scans, and the Huffman tables in force at their SOS (the scans name them by index)
+    bool prog = false;
+    struct Scan {
+        int cmask = 0, Ss = 0, Se = 0, Ah = 0, Al = 0, ri = 0, bw = 0, bh = 0, round = 0, units = 0;
+        int dc[3] = {-1, -1, -1}, ac = -1;
+        std::vector<std::pair<int64_t, int64_t>> segs;
+    };
+    std::vector<Scan> scans;
+    std::vector<JpegHuffRaw> scan_huff;
 };
 static inline int jpeg_cdiv(int a, int b) { return (a + b - 1) / b; }
 
@@ -525,6 +602,214 @@ static int jpeg_parse(const uint8_t* p, int64_t n, JpegParsed& P) {
     return GG_JPEG_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- host: parsing a progressive file (gg_jprog.h)
+static const char* const JPROG_REFUSAL_NAMES[GG_JPROG_END_REFUSALS - GG_JPROG_BAD_SCRIPT] = {
+    "bad progressive scan script", "incomplete progression", "more than 64 scans", "DNL marker or a frame height of 0"};
+static_assert(GG_JPROG_MAX_SCANS == 64, "the name of GG_JPROG_TOO_MANY_SCANS says 64");
+extern "C" const char* gg_jprog_refusal_name(int code) {
+    if (code == GG_JPEG_SCANS) return "a baseline file with more than one scan or a non-interleaved scan";
+    if (code >= GG_JPROG_BAD_SCRIPT && code < GG_JPROG_END_REFUSALS) return JPROG_REFUSAL_NAMES[code - GG_JPROG_BAD_SCRIPT];
+    return gg_jpeg_refusal_name(code);
+}
+
+// The entropy-coded data of one scan from pos on: RSTn splits it, any other marker ends it (*end: that marker's FF, or n).  The loop of jpeg_parse.
+static int jprog_scan_data(const uint8_t* p, int64_t n, int64_t pos, int ri, std::vector<std::pair<int64_t, int64_t>>& segs, int64_t* end) {
+    int64_t begin = pos, q = pos;
+    int expect = 0;
+    *end = n;
+    while (q < n) {
+        const uint8_t* f = (const uint8_t*)memchr(p + q, 0xFF, (size_t)(n - q));
+        if (!f) break;
+        const int64_t i = f - p;
+        if (i + 1 >= n) break;
+        const int m = p[i + 1];
+        if (m == 0x00) { q = i + 2; continue; }
+        if (m == 0xFF) { q = i + 1; continue; }
+        if (m >= 0xD0 && m <= 0xD7) {
+            if (ri == 0 || (m & 7) != expect) return GG_JPEG_RESTART;
+            segs.push_back({begin, i});
+            begin = q = i + 2;
+            expect = (expect + 1) & 7;
+            continue;
+        }
+        *end = i;
+        break;
+    }
+    segs.push_back({begin, *end});
+    return GG_JPEG_OK;
+}
+
+// A file whose frame is SOF2 (jpeg_parse has found that out, and that the file starts with SOI): every scan up to EOI or the end of the file.
+static int jprog_parse(const uint8_t* p, int64_t n, JpegParsed& P) {
+    P.prog = true;
+    int64_t pos = 2;
+    bool have_sof = false, jfif = false, adobe = false, latched[3] = {false, false, false};
+    int adobe_transform = 0;
+    int coded[3][64];                                                       // the Al last coded for a coefficient, -1: never coded (libjpeg's coef_bits)
+    uint16_t ql[3][64];
+    for (int c = 0; c < 3; ++c)
+        for (int k = 0; k < 64; ++k) coded[c][k] = -1;
+    for (;;) {
+        while (pos < n && p[pos] != 0xFF) ++pos;
+        while (pos < n && p[pos] == 0xFF) ++pos;
+        if (pos >= n) break;
+        const int m = p[pos++];
+        if (m == 0x00 || m == 0x01 || (m >= 0xD0 && m <= 0xD8)) continue;
+        if (m == 0xD9) break;
+        if (pos + 2 > n) return GG_JPEG_TRUNCATED_HEADER;
+        const int L = p[pos] << 8 | p[pos + 1];
+        if (L < 2 || pos + L > n) return GG_JPEG_TRUNCATED_HEADER;
+        const uint8_t* s = p + pos + 2;
+        const int sl = L - 2;
+        pos += L;
+        if (m == 0xC3 || (m >= 0xC5 && m <= 0xC7) || m == 0xC8) return GG_JPEG_UNSUPPORTED_SOF;
+        if ((m >= 0xC9 && m <= 0xCB) || (m >= 0xCC && m <= 0xCF)) return GG_JPEG_ARITHMETIC;
+        if (m == 0xDC) return GG_JPROG_DNL;
+        if (m == 0xC0 || m == 0xC1 || m == 0xC2) {
+            if (have_sof || m != 0xC2) return GG_JPEG_UNSUPPORTED_SOF;      // a second frame: hierarchical
+            if (sl < 6) return GG_JPEG_TRUNCATED_HEADER;
+            if (s[0] != 8) return GG_JPEG_PRECISION;
+            P.H = s[1] << 8 | s[2]; P.W = s[3] << 8 | s[4]; P.ncomp = s[5];
+            if (P.H == 0) return GG_JPROG_DNL;
+            if (P.W == 0 || P.H > GG_JPEG_MAX_DIM || P.W > GG_JPEG_MAX_DIM) return GG_JPEG_SIZE;
+            if (P.ncomp != 1 && P.ncomp != 3) return GG_JPEG_COMPONENTS;
+            if (sl < 6 + 3 * P.ncomp) return GG_JPEG_TRUNCATED_HEADER;
+            for (int c = 0; c < P.ncomp; ++c) {
+                P.cid[c] = s[6 + 3 * c]; P.ch[c] = s[7 + 3 * c] >> 4; P.cv[c] = s[7 + 3 * c] & 15; P.tq[c] = s[8 + 3 * c];
+                if (P.tq[c] > 3) return GG_JPEG_MISSING_TABLE;
+            }
+            if (P.ncomp == 3) {
+                const bool chroma11 = P.ch[1] == 1 && P.cv[1] == 1 && P.ch[2] == 1 && P.cv[2] == 1;
+                const bool luma_ok = (P.ch[0] == 1 && P.cv[0] == 1) || (P.ch[0] == 2 && P.cv[0] == 1) || (P.ch[0] == 2 && P.cv[0] == 2);
+                if (!chroma11 || !luma_ok) return GG_JPEG_SAMPLING;
+                P.hs = P.ch[0]; P.vs = P.cv[0];
+            } else {
+                if (P.ch[0] < 1 || P.ch[0] > 4 || P.cv[0] < 1 || P.cv[0] > 4) return GG_JPEG_SAMPLING;
+                P.hs = P.vs = 1;
+            }
+            have_sof = true;
+        } else if (m == 0xDB) {
+            for (int i = 0; i < sl;) {
+                const int pq = s[i] >> 4, id = s[i] & 15;
+                const int need = 1 + 64 * (pq ? 2 : 1);
+                if (pq > 1 || id > 3) return GG_JPEG_MISSING_TABLE;
+                if (i + need > sl) return GG_JPEG_TRUNCATED_HEADER;
+                for (int k = 0; k < 64; ++k) P.q[id][k] = pq ? (uint16_t)(s[i + 1 + 2 * k] << 8 | s[i + 2 + 2 * k]) : s[i + 1 + k];
+                P.have_q[id] = true;
+                i += need;
+            }
+        } else if (m == 0xC4) {
+            for (int i = 0; i < sl;) {
+                if (i + 17 > sl) return GG_JPEG_TRUNCATED_HEADER;
+                const int tc = s[i] >> 4, id = s[i] & 15;
+                if (tc > 1 || id > 3) return GG_JPEG_MISSING_TABLE;
+                JpegHuffRaw& h = P.huff[tc][id];
+                int total = 0;
+                for (int l = 0; l < 16; ++l) { h.counts[l] = s[i + 1 + l]; total += h.counts[l]; }
+                if (total > 256) return GG_JPEG_MISSING_TABLE;
+                if (i + 17 + total > sl) return GG_JPEG_TRUNCATED_HEADER;
+                memset(h.vals, 0, sizeof h.vals);
+                memcpy(h.vals, s + i + 17, total);
+                h.nvals = total; h.have = true;
+                i += 17 + total;
+            }
+        } else if (m == 0xDD) {
+            if (sl < 2) return GG_JPEG_TRUNCATED_HEADER;
+            P.ri = s[0] << 8 | s[1];
+        } else if (m == 0xE0) {
+            if (sl >= 5 && memcmp(s, "JFIF\0", 5) == 0) jfif = true;
+        } else if (m == 0xEE) {
+            if (sl >= 12 && memcmp(s, "Adobe", 5) == 0) { adobe = true; adobe_transform = s[11]; }
+        } else if (m == 0xDA) {
+            if (!have_sof) return GG_JPEG_TRUNCATED_HEADER;
+            if (P.scans.empty() && P.ncomp == 3) {                          // libjpeg's colour-space guess, as in jpeg_parse
+                bool ycc = true;
+                if (jfif) ycc = true;
+                else if (adobe) ycc = adobe_transform != 0;
+                else ycc = !(P.cid[0] == 'R' && P.cid[1] == 'G' && P.cid[2] == 'B');
+                if (!ycc) return GG_JPEG_NOT_YCBCR;
+            }
+            if ((int)P.scans.size() >= GG_JPROG_MAX_SCANS) return GG_JPROG_TOO_MANY_SCANS;
+            if (sl < 1) return GG_JPEG_TRUNCATED_HEADER;
+            const int ns = s[0];
+            if (ns < 1 || ns > P.ncomp) return GG_JPROG_BAD_SCRIPT;
+            if (sl < 1 + 2 * ns + 3) return GG_JPEG_TRUNCATED_HEADER;
+            JpegParsed::Scan sc;
+            int comp[3], td[3], ta[3], prev = -1;
+            for (int j = 0; j < ns; ++j) {
+                int c = -1;
+                for (int t = 0; t < P.ncomp; ++t)
+                    if (s[1 + 2 * j] == P.cid[t]) { c = t; break; }
+                if (c <= prev) return GG_JPROG_BAD_SCRIPT;                  // not a component of the frame, twice in the scan, or out of the frame's order
+                prev = c;
+                comp[j] = c; td[j] = s[2 + 2 * j] >> 4; ta[j] = s[2 + 2 * j] & 15;
+                sc.cmask |= 1 << c;
+            }
+            sc.Ss = s[1 + 2 * ns]; sc.Se = s[2 + 2 * ns]; sc.Ah = s[3 + 2 * ns] >> 4; sc.Al = s[3 + 2 * ns] & 15;
+            if (sc.Ss == 0) { if (sc.Se != 0) return GG_JPROG_BAD_SCRIPT; }
+            else if (sc.Ss > sc.Se || sc.Se > 63 || ns != 1) return GG_JPROG_BAD_SCRIPT;
+            if (sc.Al > 13 || (sc.Ah != 0 && sc.Al != sc.Ah - 1)) return GG_JPROG_BAD_SCRIPT;
+            for (int j = 0; j < ns; ++j) {
+                const int c = comp[j];
+                if (sc.Ss > 0 && coded[c][0] < 0) return GG_JPROG_BAD_SCRIPT;                      // AC before DC
+                for (int k = sc.Ss; k <= sc.Se; ++k) {
+                    if (sc.Ah == 0 ? coded[c][k] >= 0 : coded[c][k] != sc.Ah) return GG_JPROG_BAD_SCRIPT;
+                    coded[c][k] = sc.Al;
+                }
+            }
+            for (int j = 0; j < ns; ++j) {                                  // the tables in force here; the quantiser of a component at its first scan
+                const int c = comp[j];
+                if (sc.Ss == 0 && sc.Ah == 0) {
+                    if (td[j] > 3 || !P.huff[0][td[j]].have) return GG_JPEG_MISSING_TABLE;
+                    sc.dc[c] = (int)P.scan_huff.size();
+                    P.scan_huff.push_back(P.huff[0][td[j]]);
+                }
+                if (sc.Ss > 0) {
+                    if (ta[j] > 3 || !P.huff[1][ta[j]].have) return GG_JPEG_MISSING_TABLE;
+                    sc.ac = (int)P.scan_huff.size();
+                    P.scan_huff.push_back(P.huff[1][ta[j]]);
+                }
+                if (!latched[c]) {
+                    if (!P.have_q[P.tq[c]]) return GG_JPEG_MISSING_TABLE;
+                    memcpy(ql[c], P.q[P.tq[c]], 128);
+                    latched[c] = true;
+                }
+            }
+            if (ns == 1) {                                                  // a non-interleaved scan walks the component's own blocks
+                const int c = comp[0], hc = c == 0 ? P.hs : 1, vc = c == 0 ? P.vs : 1;
+                sc.bw = jpeg_cdiv(jpeg_cdiv(P.W * hc, P.hs), 8); sc.bh = jpeg_cdiv(jpeg_cdiv(P.H * vc, P.vs), 8);
+            } else { sc.bw = jpeg_cdiv(P.W, 8 * P.hs); sc.bh = jpeg_cdiv(P.H, 8 * P.vs); }
+            sc.units = sc.bw * sc.bh;
+            sc.ri = P.ri;
+            int64_t end = n;
+            const int rc = jprog_scan_data(p, n, pos, sc.ri, sc.segs, &end);
+            if (rc != GG_JPEG_OK) return rc;
+            const int64_t expected = sc.ri ? ((int64_t)sc.units + sc.ri - 1) / sc.ri : 1;
+            if ((int64_t)sc.segs.size() != expected) return GG_JPEG_RESTART;
+            pos = end;
+            P.scans.push_back(std::move(sc));
+        }                                                                   // APPn, COM, ...: skipped
+    }
+    if (P.scans.empty()) return GG_JPEG_TRUNCATED_HEADER;
+    for (int c = 0; c < P.ncomp; ++c)
+        for (int k = 0; k < 64; ++k)
+            if (coded[c][k] != 0) return GG_JPROG_INCOMPLETE;
+    int last[3][64];
+    memset(last, 0, sizeof last);
+    for (auto& sc : P.scans) {                                              // rounds: one more than the latest earlier scan that shares a (component, zigzag index) pair
+        int r = 0;
+        for (int c = 0; c < 3; ++c)
+            if ((sc.cmask >> c) & 1)
+                for (int k = sc.Ss; k <= sc.Se; ++k) r = std::max(r, last[c][k]);
+        sc.round = r + 1;
+        for (int c = 0; c < 3; ++c)
+            if ((sc.cmask >> c) & 1)
+                for (int k = sc.Ss; k <= sc.Se; ++k) last[c][k] = sc.round;
+    }
+    for (int c = 0; c < P.ncomp; ++c) { memcpy(P.q[c], ql[c], 128); P.tq[c] = c; P.have_q[c] = true; }
+    return GG_JPEG_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host: the plan
 struct GgJpegPlan {
     int B = 0, nseg = 0, nhuff = 0, first_refused = -1;
@@ -540,12 +825,20 @@ struct GgJpegPlan {
     int64_t nsub = 0, segsub_off = 0, sub_off = 0;
     std::vector<int32_t> img_subs;
     int64_t ws_slow = 0, ws_recs = 0, ws_outs = 0, ws_sums = 0, ws_scan_total = 0;
+    // gg_jprog_plan_create only (prog): the scan table and the segments in round order behind the Huffman tables
+    bool prog = false;
+    int first_progressive = -1, rounds = 0, nscan = 0;
+    int64_t scan_off = 0, order_off = 0;
+    std::vector<int32_t> img_scans, round_begin;                            // round r's segments: order[round_begin[r - 1], round_begin[r])
 };
 static int64_t jpeg_align(int64_t b, int64_t a = 256) { return (b + a - 1) / a * a; }
 
-static int jpeg_plan_build(const void* const* files, const int64_t* lengths, int B, int split, GgJpegPlan* pl) {
+static int jpeg_plan_build(const void* const* files, const int64_t* lengths, int B, int split, bool prog, GgJpegPlan* pl) {
     pl->B = B;
     pl->split = split;
+    pl->prog = prog;
+    pl->img_scans.assign(B, 0);
+    std::vector<JprogScanDev> scans;
     pl->img_subs.assign(B, 0);
     pl->info.resize(B);
     pl->len.assign(lengths, lengths + B);
@@ -563,26 +856,54 @@ static int jpeg_plan_build(const void* const* files, const int64_t* lengths, int
         JpegImgDev& d = imgs[b];
         memset(&d, 0, sizeof d);
         I.refusal = jpeg_parse((const uint8_t*)files[b], lengths[b], P);
+        if (prog && I.refusal == GG_JPEG_PROGRESSIVE) {
+            P = JpegParsed();
+            I.refusal = jprog_parse((const uint8_t*)files[b], lengths[b], P);
+        }
         I.height = P.H; I.width = P.W; I.components = P.ncomp; I.hs = P.hs; I.vs = P.vs;
         I.out_offset = out_off;
-        if (I.refusal == GG_JPEG_OK) {                                      // the scan's Huffman tables, de-duplicated over the batch
+        auto intern = [&](const JpegHuffRaw& h, int32_t& id) -> bool {      // a scan's Huffman table, de-duplicated over the batch
+            std::string key((const char*)h.counts, 16);
+            key.append((const char*)h.vals, h.nvals);
+            auto it = huff_ids.find(key);
+            if (it != huff_ids.end()) { id = it->second; return true; }
+            uint32_t t[JPEG_HUFF_WORDS];
+            if (!jpeg_build_huff(h.counts, h.vals, h.nvals, t)) return false;
+            id = (int)huff_ids.size();
+            huff_ids.emplace(key, id);
+            huff.insert(huff.end(), t, t + JPEG_HUFF_WORDS);
+            return true;
+        };
+        const size_t scans_before = scans.size();
+        if (I.refusal == GG_JPEG_OK && !P.prog) {
             for (int c = 0; c < P.ncomp && I.refusal == GG_JPEG_OK; ++c)
-                for (int cls = 0; cls < 2; ++cls) {
-                    const JpegHuffRaw& h = P.huff[cls][cls ? P.ta[c] : P.td[c]];
-                    std::string key((const char*)h.counts, 16);
-                    key.append((const char*)h.vals, h.nvals);
-                    auto it = huff_ids.find(key);
-                    int id;
-                    if (it != huff_ids.end()) id = it->second;
-                    else {
-                        uint32_t t[JPEG_HUFF_WORDS];
-                        if (!jpeg_build_huff(h.counts, h.vals, h.nvals, t)) { I.refusal = GG_JPEG_MISSING_TABLE; break; }
-                        id = (int)huff_ids.size();
-                        huff_ids.emplace(key, id);
-                        huff.insert(huff.end(), t, t + JPEG_HUFF_WORDS);
-                    }
-                    (cls ? d.ac : d.dc)[c] = id;
-                }
+                for (int cls = 0; cls < 2; ++cls)
+                    if (!intern(P.huff[cls][cls ? P.ta[c] : P.td[c]], (cls ? d.ac : d.dc)[c])) { I.refusal = GG_JPEG_MISSING_TABLE; break; }
+        }
+        if (I.refusal == GG_JPEG_OK && prog) {                              // the image's scans: one for a baseline file
+            int seg_at = (int)seg_count;
+            if (!P.prog) {
+                JprogScanDev sd;
+                memset(&sd, 0, sizeof sd);
+                sd.img = b; sd.base = 1; sd.cmask = P.ncomp == 3 ? 7 : 1; sd.Se = 63;
+                sd.bw = jpeg_cdiv(P.W, 8 * P.hs); sd.bh = jpeg_cdiv(P.H, 8 * P.vs);
+                sd.round = 1; sd.seg0 = seg_at; sd.nseg = (int)P.segs.size();
+                scans.push_back(sd);
+            }
+            for (const auto& sc : P.scans) {
+                JprogScanDev sd;
+                memset(&sd, 0, sizeof sd);
+                sd.img = b; sd.cmask = sc.cmask; sd.Ss = sc.Ss; sd.Se = sc.Se; sd.Ah = sc.Ah; sd.Al = sc.Al; sd.bw = sc.bw; sd.bh = sc.bh;
+                sd.round = sc.round; sd.seg0 = seg_at; sd.nseg = (int)sc.segs.size();
+                seg_at += sd.nseg;
+                bool ok = true;
+                for (int c = 0; c < 3 && ok; ++c)
+                    if (sc.dc[c] >= 0) ok = intern(P.scan_huff[sc.dc[c]], sd.dc[c]);
+                if (ok && sc.ac >= 0) ok = intern(P.scan_huff[sc.ac], sd.ac);
+                if (!ok) { I.refusal = GG_JPEG_MISSING_TABLE; break; }
+                scans.push_back(sd);
+            }
+            if (I.refusal != GG_JPEG_OK) scans.resize(scans_before);
         }
         if (I.refusal != GG_JPEG_OK) {
             if (pl->first_refused < 0) pl->first_refused = b;
@@ -590,6 +911,13 @@ static int jpeg_plan_build(const void* const* files, const int64_t* lengths, int
             continue;
         }
         I.segments = (int)P.segs.size();
+        if (P.prog) {
+            I.segments = 0;
+            for (const auto& sc : P.scans) I.segments += (int)sc.segs.size();
+            d.prog = 1;
+            if (pl->first_progressive < 0) pl->first_progressive = b;
+        }
+        if (prog) { d.scan0 = (int)scans_before; pl->img_scans[b] = (int)(scans.size() - scans_before); }
         d.out_off = out_off; d.coef_off = coef_off;
         d.H = P.H; d.W = P.W; d.ncomp = P.ncomp; d.hs = P.hs; d.vs = P.vs;
         d.mcux = jpeg_cdiv(P.W, 8 * P.hs); d.mcuy = jpeg_cdiv(P.H, 8 * P.vs);
@@ -649,6 +977,11 @@ static int jpeg_plan_build(const void* const* files, const int64_t* lengths, int
         pl->segsub_off = off; off += jpeg_align(std::max<int64_t>((int64_t)seg_sub0.size(), 1) * 4);
         pl->sub_off = off; off += jpeg_align(std::max<int64_t>(pl->nsub, 1) * (int64_t)sizeof(JscanSub));
     }
+    if (prog) {
+        pl->nscan = (int)scans.size();
+        pl->scan_off = off; off += jpeg_align(std::max<int64_t>(pl->nscan, 1) * (int64_t)sizeof(JprogScanDev));
+        pl->order_off = off; off += jpeg_align(std::max<int64_t>(nseg, 1) * 4);
+    }
     const int64_t table_bytes = off;
     for (int b = 0; b < B; ++b) {
         pl->info[b].stream_offset = off;
@@ -661,10 +994,19 @@ static int jpeg_plan_build(const void* const* files, const int64_t* lengths, int
         if (pl->info[b].refusal != GG_JPEG_OK) continue;
         const JpegParsed& P = parsed[b];
         const int total_mcus = imgs[b].mcux * imgs[b].mcuy;
+        for (size_t k = 0; k < P.scans.size(); ++k) {                       // a progressive image: the segments of every scan, in file order
+            const JpegParsed::Scan& sc = P.scans[k];
+            for (size_t i = 0; i < sc.segs.size(); ++i) {
+                JpegSegDev s;
+                s.begin = pl->info[b].stream_offset + sc.segs[i].first; s.end = pl->info[b].stream_offset + sc.segs[i].second;
+                s.img = b; s.mcu0 = sc.ri ? (int)i * sc.ri : 0; s.mcus = sc.ri ? std::min(sc.ri, sc.units - s.mcu0) : sc.units; s.scan = imgs[b].scan0 + (int)k;
+                segs.push_back(s);
+            }
+        }
         for (size_t i = 0; i < P.segs.size(); ++i) {
             JpegSegDev s;
             s.begin = pl->info[b].stream_offset + P.segs[i].first; s.end = pl->info[b].stream_offset + P.segs[i].second;
-            s.img = b; s.mcu0 = P.ri ? (int)i * P.ri : 0; s.mcus = P.ri ? std::min(P.ri, total_mcus - s.mcu0) : total_mcus; s.pad = 0;
+            s.img = b; s.mcu0 = P.ri ? (int)i * P.ri : 0; s.mcus = P.ri ? std::min(P.ri, total_mcus - s.mcu0) : total_mcus; s.scan = pl->prog ? imgs[b].scan0 : 0;
             segs.push_back(s);
         }
     }
@@ -674,6 +1016,26 @@ static int jpeg_plan_build(const void* const* files, const int64_t* lengths, int
     if (!segs.empty()) memcpy(&pl->tables[pl->seg_off], segs.data(), segs.size() * sizeof(JpegSegDev));
     memcpy(&pl->tables[pl->quant_off], quant.data(), quant.size() * 2);
     if (!huff.empty()) memcpy(&pl->tables[pl->huff_off], huff.data(), huff.size() * 4);
+    if (prog) {
+        // The segments by round, and inside a round by the form of their scan (baseline, DC first, DC refinement, AC first, AC refinement), then image, scan and
+        // segment: the lanes of a wave then run the same statements, where neighbours of different forms would take turns.
+        for (const auto& sd : scans) pl->rounds = std::max(pl->rounds, sd.round);
+        std::vector<int32_t> scan_key(scans.size());
+        for (size_t k = 0; k < scans.size(); ++k) {
+            const JprogScanDev& sd = scans[k];
+            scan_key[k] = sd.round * 8 + (sd.base ? 0 : 1 + (sd.Ss == 0 ? (sd.Ah == 0 ? 0 : 1) : (sd.Ah == 0 ? 2 : 3)));
+        }
+        std::vector<int64_t> at((size_t)(pl->rounds + 1) * 8 + 1, 0);       // a counting sort: the keys are few, the segments can be many
+        for (const auto& sg : segs) at[(size_t)scan_key[sg.scan] + 1] += 1;
+        for (size_t k = 1; k < at.size(); ++k) at[k] += at[k - 1];
+        std::vector<int32_t> order(segs.size());
+        for (size_t i = 0; i < segs.size(); ++i) order[(size_t)at[(size_t)scan_key[segs[i].scan]]++] = (int32_t)i;
+        pl->round_begin.assign((size_t)pl->rounds + 1, 0);
+        for (const auto& sg : segs) pl->round_begin[scans[sg.scan].round] += 1;
+        for (int r = 1; r <= pl->rounds; ++r) pl->round_begin[r] += pl->round_begin[r - 1];
+        if (!scans.empty()) memcpy(&pl->tables[pl->scan_off], scans.data(), scans.size() * sizeof(JprogScanDev));
+        if (!order.empty()) memcpy(&pl->tables[pl->order_off], order.data(), order.size() * 4);
+    }
     pl->coef_bytes = coef_off; pl->plane_bytes = plane_off;
     int64_t w = 0;
     pl->ws_status = w; w += jpeg_align(std::max<int64_t>(pl->nseg, 1) * 4);
@@ -693,7 +1055,7 @@ static int jpeg_plan_build(const void* const* files, const int64_t* lengths, int
     return 0;
 }
 // the C boundary: nothing is thrown across it; running out of host memory is an error like any other
-static int jpeg_plan_create(const char* who, const void* const* files, const int64_t* lengths, int B, int split, GgJpegPlan** out) {
+static int jpeg_plan_create(const char* who, const void* const* files, const int64_t* lengths, int B, int split, bool prog, GgJpegPlan** out) {
     GG_CHECK(files && lengths && out, "%s: null files / lengths / plan", who);
     GG_CHECK(B > 0 && B <= GG_JPEG_MAX_B, "%s: B=%d outside [1, %d]", who, B, GG_JPEG_MAX_B);
     for (int b = 0; b < B; ++b) GG_CHECK(files[b] && lengths[b] >= 0, "%s: file %d is null or has a negative length", who, b);
@@ -701,7 +1063,7 @@ static int jpeg_plan_create(const char* who, const void* const* files, const int
     int rc = -1;
     try {
         pl = new GgJpegPlan;
-        rc = jpeg_plan_build(files, lengths, B, split, pl);
+        rc = jpeg_plan_build(files, lengths, B, split, prog, pl);
     } catch (const std::bad_alloc&) {
         gg_set_error("%s: out of host memory for a plan of %d files", who, B);
     } catch (const std::exception& e) {
@@ -712,13 +1074,19 @@ static int jpeg_plan_create(const char* who, const void* const* files, const int
     return 0;
 }
 extern "C" int gg_jpeg_plan_create(const void* const* files, const int64_t* lengths, int B, GgJpegPlan** out) {
-    return jpeg_plan_create("gg_jpeg_plan_create", files, lengths, B, 0, out);
+    return jpeg_plan_create("gg_jpeg_plan_create", files, lengths, B, 0, false, out);
 }
 extern "C" int gg_jscan_plan_create(const void* const* files, const int64_t* lengths, int B, int split_bytes, GgJpegPlan** out) {
     GG_CHECK(split_bytes >= GG_JSCAN_MIN_SPLIT && split_bytes <= GG_JSCAN_MAX_SPLIT, "gg_jscan_plan_create: split_bytes=%d outside [%d, %d]", split_bytes,
              GG_JSCAN_MIN_SPLIT, GG_JSCAN_MAX_SPLIT);
-    return jpeg_plan_create("gg_jscan_plan_create", files, lengths, B, split_bytes, out);
+    return jpeg_plan_create("gg_jscan_plan_create", files, lengths, B, split_bytes, false, out);
 }
+extern "C" int gg_jprog_plan_create(const void* const* files, const int64_t* lengths, int B, GgJpegPlan** out) {
+    return jpeg_plan_create("gg_jprog_plan_create", files, lengths, B, 0, true, out);
+}
+extern "C" int gg_jprog_plan_scans(const GgJpegPlan* plan, int b) { return plan && plan->prog && b >= 0 && b < plan->B ? plan->img_scans[b] : -1; }
+extern "C" int gg_jprog_plan_rounds(const GgJpegPlan* plan) { return plan && plan->prog ? plan->rounds : -1; }
+extern "C" int64_t gg_jprog_workspace_bytes(const GgJpegPlan* plan) { return plan && plan->prog ? plan->ws_total : -1; }
 extern "C" int gg_jscan_plan_subsegments(const GgJpegPlan* plan, int b) { return plan && plan->split > 0 && b >= 0 && b < plan->B ? plan->img_subs[b] : -1; }
 extern "C" int64_t gg_jscan_plan_total_subsegments(const GgJpegPlan* plan) { return plan && plan->split > 0 ? plan->nsub : -1; }
 extern "C" int64_t gg_jscan_workspace_bytes(const GgJpegPlan* plan) { return plan && plan->split > 0 ? plan->ws_scan_total : -1; }
@@ -755,6 +1123,7 @@ static int jpeg_lanes(int64_t items) { return (int)std::min<int64_t>(64, std::ma
 extern "C" int gg_jscan_decode(const GgJpegPlan* plan, const void* stream_buf, int64_t stream_bytes, void* out, int64_t out_bytes, int32_t* status, int32_t* slow,
                                void* workspace, int64_t workspace_bytes, void* stream) {
     GG_CHECK(plan, "gg_jscan_decode: null plan");
+    GG_CHECK(plan->first_progressive < 0, "gg_jscan_decode: image %d is progressive (SOF2): a plan of gg_jprog_plan_create is decoded by gg_jprog_decode", plan->first_progressive);
     GG_CHECK(plan->split > 0, "gg_jscan_decode: the plan has no sub-segment table (it was made by gg_jpeg_plan_create, not gg_jscan_plan_create)");
     if (plan->first_refused >= 0) {
         const int b = plan->first_refused;
@@ -838,8 +1207,9 @@ extern "C" int gg_jpeg_decode(const GgJpegPlan* plan, const void* stream_buf, in
     GG_CHECK(plan, "gg_jpeg_decode: null plan");
     if (plan->first_refused >= 0) {
         const int b = plan->first_refused;
-        GG_CHECK(false, "gg_jpeg_decode: image %d is refused: %s", b, gg_jpeg_refusal_name(plan->info[b].refusal));
+        GG_CHECK(false, "gg_jpeg_decode: image %d is refused: %s", b, plan->prog ? gg_jprog_refusal_name(plan->info[b].refusal) : gg_jpeg_refusal_name(plan->info[b].refusal));
     }
+    GG_CHECK(plan->first_progressive < 0, "gg_jpeg_decode: image %d is progressive (SOF2): a plan of gg_jprog_plan_create is decoded by gg_jprog_decode", plan->first_progressive);
     GG_CHECK(stream_buf && out && status && workspace, "gg_jpeg_decode: null stream buffer / out / status / workspace");
     GG_CHECK((((uintptr_t)stream_buf | (uintptr_t)out | (uintptr_t)workspace) & 15) == 0 && ((uintptr_t)status & 3) == 0,
              "gg_jpeg_decode: the stream buffer, the output and the workspace must be 16-byte aligned");
@@ -870,6 +1240,67 @@ extern "C" int gg_jpeg_decode(const GgJpegPlan* plan, const void* stream_buf, in
             hipLaunchKernelGGL(jpeg_entropy_kernel<true>, dim3(blocks), dim3(64), lds, st, sb, imgs, segs, huff, plan->nhuff, nseg, lanes, coef, seg_status);
         else
             hipLaunchKernelGGL(jpeg_entropy_kernel<false>, dim3(blocks), dim3(64), 0, st, sb, imgs, segs, huff, plan->nhuff, nseg, lanes, coef, seg_status);
+    }
+    {
+        GG_PROF(GG_CAT_MOVE, 0, (double)plan->coef_bytes + (double)plan->plane_bytes, stream);
+        hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)std::min<int64_t>(gg_cdiv(plan->max_blocks, 256), 1024), (unsigned)B), dim3(256), 0, st, imgs, quant, coef, planes);
+    }
+    {
+        GG_PROF(GG_CAT_MOVE, 0, (double)plan->plane_bytes + (double)plan->out_bytes, stream);
+        hipLaunchKernelGGL(jpeg_status_kernel, dim3((unsigned)B), dim3(64), 0, st, imgs, seg_status, status);
+        hipLaunchKernelGGL(jpeg_pack_kernel, dim3((unsigned)std::min<int64_t>(gg_cdiv(gg_cdiv(plan->max_pixels, 4), 256), 1024), (unsigned)B), dim3(256), 0, st, imgs, planes,
+                           status, (uint8_t*)out);
+    }
+    GG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int gg_jprog_decode(const GgJpegPlan* plan, const void* stream_buf, int64_t stream_bytes, void* out, int64_t out_bytes, int32_t* status, void* workspace,
+                               int64_t workspace_bytes, void* stream) {
+    GG_CHECK(plan, "gg_jprog_decode: null plan");
+    GG_CHECK(plan->prog, "gg_jprog_decode: the plan was not made by gg_jprog_plan_create");
+    if (plan->first_refused >= 0) {
+        const int b = plan->first_refused;
+        GG_CHECK(false, "gg_jprog_decode: image %d is refused: %s", b, gg_jprog_refusal_name(plan->info[b].refusal));
+    }
+    GG_CHECK(stream_buf && out && status && workspace, "gg_jprog_decode: null stream buffer / out / status / workspace");
+    GG_CHECK((((uintptr_t)stream_buf | (uintptr_t)out | (uintptr_t)workspace) & 15) == 0 && ((uintptr_t)status & 3) == 0,
+             "gg_jprog_decode: the stream buffer, the output and the workspace must be 16-byte aligned");
+    GG_CHECK(stream_bytes >= plan->stream_bytes, "gg_jprog_decode: the stream buffer has %lld bytes, the plan needs %lld (gg_jpeg_plan_stream_bytes)", (long long)stream_bytes,
+             (long long)plan->stream_bytes);
+    GG_CHECK(out_bytes >= plan->out_bytes, "gg_jprog_decode: the output has %lld bytes, the plan needs %lld (gg_jpeg_plan_output_bytes)", (long long)out_bytes,
+             (long long)plan->out_bytes);
+    GG_CHECK(workspace_bytes >= plan->ws_total, "gg_jprog_decode: the workspace has %lld bytes, the plan needs %lld (gg_jprog_workspace_bytes)", (long long)workspace_bytes,
+             (long long)plan->ws_total);
+    hipStream_t st = (hipStream_t)stream;
+    const uint8_t* sb = (const uint8_t*)stream_buf;
+    const JpegImgDev* imgs = (const JpegImgDev*)(sb + plan->img_off);
+    const JpegSegDev* segs = (const JpegSegDev*)(sb + plan->seg_off);
+    const uint16_t* quant = (const uint16_t*)(sb + plan->quant_off);
+    const uint32_t* huff = (const uint32_t*)(sb + plan->huff_off);
+    const JprogScanDev* scans = (const JprogScanDev*)(sb + plan->scan_off);
+    const int32_t* order = (const int32_t*)(sb + plan->order_off);
+    char* w = (char*)workspace;
+    int32_t* seg_status = (int32_t*)(w + plan->ws_status);
+    int16_t* coef = (int16_t*)(w + plan->ws_coef);
+    uint8_t* planes = (uint8_t*)(w + plan->ws_planes);
+    const int B = plan->B;
+    // one profiler scope per stage, in launch order, as gg_jpeg_decode: entropy (the zero fill and every round), inverse DCT, status + pack
+    {
+        GG_PROF(GG_CAT_MOVE, 0, (double)plan->file_bytes + 2.0 * (double)plan->coef_bytes, stream);
+        if (plan->first_progressive >= 0)
+            hipLaunchKernelGGL(jprog_fill_kernel, dim3((unsigned)std::min<int64_t>(gg_cdiv(plan->max_blocks * 8, 256), 1024), (unsigned)B), dim3(256), 0, st, imgs, coef);
+        const size_t lds = (size_t)plan->nhuff * JPEG_HUFF_WORDS * 4;
+        for (int r = 1; r <= plan->rounds; ++r) {
+            const int first = plan->round_begin[r - 1], n = plan->round_begin[r] - first;
+            if (n <= 0) continue;
+            const int lanes = jpeg_lanes(n);
+            const unsigned blocks = (unsigned)gg_cdiv(n, lanes);
+            if (lds <= JPEG_LDS_MAX_BYTES)
+                hipLaunchKernelGGL(jprog_entropy_kernel<true>, dim3(blocks), dim3(64), lds, st, sb, imgs, segs, scans, order + first, huff, plan->nhuff, n, lanes, coef, seg_status);
+            else
+                hipLaunchKernelGGL(jprog_entropy_kernel<false>, dim3(blocks), dim3(64), 0, st, sb, imgs, segs, scans, order + first, huff, plan->nhuff, n, lanes, coef, seg_status);
+        }
     }
     {
         GG_PROF(GG_CAT_MOVE, 0, (double)plan->coef_bytes + (double)plan->plane_bytes, stream);

@@ -202,10 +202,12 @@ class DeviceTrainTransform:
     batch after the last op).  ``params``: a record table to replay (``sample_params``' layout); otherwise one is drawn from the transform's own generator and kept in
     ``.last_params``.  The workspace is the transform's own and is reused from call to call (it grows when a batch needs more).  ``images`` may also be a list in
     which every item is a JPEG file as bytes (decoded on the device by a ``training.jpeg.DeviceJpegDecoder`` the transform owns) or that decoder's ``PackedImages``.
-    ``jpeg_split_bytes`` is that decoder's ``split_bytes`` (0, the default: one lane per restart segment; positive: many lanes inside a scan, the same pixels)."""
+    ``jpeg_split_bytes`` is that decoder's ``split_bytes`` (0, the default: one lane per restart segment; positive: many lanes inside a scan, the same pixels),
+    ``jpeg_progressive`` its ``progressive`` (off, the default: a progressive file is refused by name; on: decoded next to baseline files)."""
 
     def __init__(self, img_size: int = 224, mean: Sequence[float] = TINYVIT_MEAN, std: Sequence[float] = TINYVIT_STD, auto_augment: str = "rand-m9-mstd0.5-inc1",
-                 interpolation: str = "bicubic", seed: int = 0, device="cuda", jpeg_split_bytes: int = 0):
+                 interpolation: str = "bicubic", seed: int = 0, device="cuda", jpeg_split_bytes: int = 0,
+                 jpeg_progressive: bool = False):
         if interpolation not in ("bilinear", "bicubic", "random"):
             raise ValueError(f"DeviceTrainTransform: interpolation must be bilinear, bicubic or random, got {interpolation!r}")
         parse_config(auto_augment)
@@ -216,6 +218,7 @@ class DeviceTrainTransform:
         self._workspace: Optional[torch.Tensor] = None
         self._decoder = None                              # training.jpeg.DeviceJpegDecoder, made when file bytes first arrive
         self.jpeg_split_bytes = int(jpeg_split_bytes)
+        self.jpeg_progressive = bool(jpeg_progressive)
 
     def _filter(self) -> int:
         if self.interpolation == "random":
@@ -229,7 +232,7 @@ class DeviceTrainTransform:
             images = [images]
         if is_file_bytes_list(images):                    # JPEG files as bytes: decoded on the device, consumed where the decoded batch lies
             if self._decoder is None:
-                self._decoder = DeviceJpegDecoder(self.device, self.jpeg_split_bytes)
+                self._decoder = DeviceJpegDecoder(self.device, self.jpeg_split_bytes, self.jpeg_progressive)
             images = self._decoder.decode(images)
         decoded = images if isinstance(images, PackedImages) else None
         hwc = [] if decoded is not None else _as_hwc_list(images)
@@ -271,20 +274,22 @@ class DeviceTrainTransform:
         return (dst, dst_u8) if return_u8 else dst
 
 
-def _hand_split_bytes(transform, jpeg_split_bytes: int) -> None:
+def _hand_split_bytes(transform, jpeg_split_bytes: int, jpeg_progressive: bool = False) -> None:
     if jpeg_split_bytes and getattr(transform, "jpeg_split_bytes", 0) != int(jpeg_split_bytes):
         transform.jpeg_split_bytes, transform._decoder = int(jpeg_split_bytes), None
+    if jpeg_progressive and not getattr(transform, "jpeg_progressive", False):
+        transform.jpeg_progressive, transform._decoder = True, None
 
 
 class augmented:
     """``{"images", "labels"}`` batches -> ``{"pixel_values", "labels"}`` batches, lazily, one ``transform`` call per batch: ``train(model, augmented(raw_batches,
     tfm), val_batches, ...)`` is the reference's loop with its training transform.  Iterating is a generator over ``batches``; like a DataLoader the object can be
     walked once per epoch (when ``batches`` can), and every walk draws new records.  ``jpeg_split_bytes`` other than 0 is handed to the transform (its decoder of
-    file bytes is made anew with it); 0 leaves the transform as it is."""
+    file bytes is made anew with it); 0 leaves the transform as it is.  ``jpeg_progressive=True`` is handed on the same way; off leaves the transform as it is."""
 
-    def __init__(self, batches: Iterable, transform: DeviceTrainTransform, jpeg_split_bytes: int = 0):
+    def __init__(self, batches: Iterable, transform: DeviceTrainTransform, jpeg_split_bytes: int = 0, jpeg_progressive: bool = False):
         self.batches, self.transform = batches, transform
-        _hand_split_bytes(transform, jpeg_split_bytes)
+        _hand_split_bytes(transform, jpeg_split_bytes, jpeg_progressive)
 
     def __iter__(self):
         for batch in self.batches:
@@ -298,11 +303,11 @@ class eval_transformed:
     """The twin of ``augmented`` for the validation side -- the reference's ``collate_val``: ``{"images", "labels"}`` batches -> ``{"pixel_values", "labels"}``
     batches, lazily, one ``transform`` call (``training.preprocess.DeviceEvalTransform``: one ``gg_eval_batch``) per batch, so
     ``evaluate(model, eval_transformed(raw_val, tfm))`` and ``extract_embeddings(model, eval_transformed(...))`` run on raw images.  Nothing is drawn: every walk
-    yields the same batches.  ``jpeg_split_bytes``: as in ``augmented``."""
+    yields the same batches.  ``jpeg_split_bytes``, ``jpeg_progressive``: as in ``augmented``."""
 
-    def __init__(self, batches: Iterable, transform, jpeg_split_bytes: int = 0):
+    def __init__(self, batches: Iterable, transform, jpeg_split_bytes: int = 0, jpeg_progressive: bool = False):
         self.batches, self.transform = batches, transform
-        _hand_split_bytes(transform, jpeg_split_bytes)
+        _hand_split_bytes(transform, jpeg_split_bytes, jpeg_progressive)
 
     def __iter__(self):
         for batch in self.batches:

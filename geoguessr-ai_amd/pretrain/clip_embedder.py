@@ -290,10 +290,11 @@ def clip_preprocess(images, size: int, device) -> Tensor:
 class CLIPEmbedding(nn.Module):
     def __init__(self, model_name: str = "openai/clip-vit-base-patch32", device: str = "cuda", load_checkpoint: bool = False,
                  panorama: bool = False, state_dict: Optional[Dict[str, Tensor]] = None, precision: Optional[str] = None, batch_transform: bool = False,
-                 jpeg_split_bytes: int = 0, attention16: bool = False, **cfg_overrides):
+                 jpeg_split_bytes: int = 0, attention16: bool = False, jpeg_progressive: bool = False, **cfg_overrides):
         """``batch_transform`` (not in the reference): raw images -- a list of any sizes, or the four panorama views together -- go through ONE ``gg_eval_batch``
         call (``training.preprocess.DeviceEvalTransform``) instead of one ``gg_preprocess_pil`` call per image; same arithmetic.  ``jpeg_split_bytes`` (with
-        ``batch_transform`` only): the ``split_bytes`` of the decoder that takes JPEG files given as bytes (``DeviceEvalTransform``'s keyword).  ``attention16``:
+        ``batch_transform`` only): the ``split_bytes`` of the decoder that takes JPEG files given as bytes (``DeviceEvalTransform``'s keyword); ``jpeg_progressive`` (with
+        ``batch_transform`` only): that decoder's ``progressive`` (progressive files are decoded next to baseline ones; off by default).  ``attention16``:
         ``CLIPVisionTower``'s keyword (opt-in 16-bit-MFMA attention beyond 256 tokens; refused for fp32 / fp32_split)."""
         super().__init__()
         check_attention16(attention16, tower_precision_code(precision), "CLIPEmbedding")
@@ -302,6 +303,9 @@ class CLIPEmbedding(nn.Module):
         if jpeg_split_bytes and not batch_transform:
             raise ValueError("CLIPEmbedding: jpeg_split_bytes needs batch_transform=True")
         self.jpeg_split_bytes = int(jpeg_split_bytes)
+        if jpeg_progressive and not batch_transform:
+            raise ValueError("CLIPEmbedding: jpeg_progressive needs batch_transform=True")
+        self.jpeg_progressive = bool(jpeg_progressive)
         self.panorama = panorama
         self.clip_model = CLIPVisionTower(model_name if not load_checkpoint else "openai/clip-vit-base-patch32", precision=precision, attention16=attention16,
                                           **cfg_overrides)
@@ -320,7 +324,7 @@ class CLIPEmbedding(nn.Module):
         if self._transform is None:
             from ..training.preprocess import DeviceEvalTransform
             self._transform = DeviceEvalTransform(self.clip_model.cfg.image_size, CLIP_MEAN, CLIP_STD, "clip", device=next(self.clip_model.parameters()).device,
-                                                  jpeg_split_bytes=self.jpeg_split_bytes)
+                                                  jpeg_split_bytes=self.jpeg_split_bytes, jpeg_progressive=self.jpeg_progressive)
         return self._transform
 
     def _get_embedding(self, image) -> Tensor:

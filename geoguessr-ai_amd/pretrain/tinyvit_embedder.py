@@ -13,12 +13,14 @@ from ..models.tinyvit import VARIANTS, TinyViTAdapter, check_attention16
 
 class TinyViTEmbedding(torch.nn.Module):
     def __init__(self, model_name: str = "tiny_vit_21m_512.dist_in22k_ft_in1k", device: str = "cuda", load_checkpoint: bool = False,
-                 panorama: bool = False, img_size: int = None, batch_transform: bool = False, jpeg_split_bytes: int = 0, attention16: bool = False):
+                 panorama: bool = False, img_size: int = None, batch_transform: bool = False, jpeg_split_bytes: int = 0, attention16: bool = False,
+                 jpeg_progressive: bool = False):
         """``img_size`` (not in the reference): run the checkpoint at another input side (a multiple of 32; ``TinyViTAdapter``'s override) -- the preprocessing
         resizes to that side, with the crop settings of the checkpoint's own variant.  ``batch_transform`` (not in the reference): raw images -- a list of any
         sizes, or the four panorama views together -- go through ONE ``gg_eval_batch`` call (``training.preprocess.DeviceEvalTransform``) instead of one
         ``gg_preprocess_pil`` call per image; same arithmetic.  ``jpeg_split_bytes`` (with ``batch_transform`` only): the ``split_bytes`` of the decoder that
-        takes JPEG files given as bytes (``DeviceEvalTransform``'s keyword; 0 is one lane per restart segment).  ``attention16`` (not in the reference; bf16
+        takes JPEG files given as bytes (``DeviceEvalTransform``'s keyword; 0 is one lane per restart segment); ``jpeg_progressive`` (with ``batch_transform`` only): that decoder's
+        ``progressive`` (progressive files are decoded next to baseline ones; off by default).  ``attention16`` (not in the reference; bf16
         only, opt-in): the attention of windows beyond 256 tokens on the 16-bit MFMA (``TinyViTAdapter``'s keyword); the fp32 modes refuse it by name."""
         super().__init__()
         check_attention16(attention16, None, "TinyViTEmbedding")
@@ -27,6 +29,9 @@ class TinyViTEmbedding(torch.nn.Module):
         if jpeg_split_bytes and not batch_transform:
             raise ValueError("TinyViTEmbedding: jpeg_split_bytes needs batch_transform=True")
         self.jpeg_split_bytes = int(jpeg_split_bytes)
+        if jpeg_progressive and not batch_transform:
+            raise ValueError("TinyViTEmbedding: jpeg_progressive needs batch_transform=True")
+        self.jpeg_progressive = bool(jpeg_progressive)
         arch = "tiny_vit_21m_224" if load_checkpoint else model_name
         self.tinyvit_model = TinyViTAdapter(arch, pretrained=not load_checkpoint, **({} if img_size is None else dict(img_size=int(img_size))),
                                             **({"attention16": True} if attention16 else {}))
@@ -43,7 +48,8 @@ class TinyViTEmbedding(torch.nn.Module):
             bb = self.tinyvit_model.backbone
             native = VARIANTS[bb.model_name]["img_size"]
             self._transform = DeviceEvalTransform(bb.img_size, TINYVIT_MEAN, TINYVIT_STD, "timm", 0.95 if native == 224 else 1.0,
-                                                  "squash" if native == 512 else "center", bb.flat_params.device, jpeg_split_bytes=self.jpeg_split_bytes)
+                                                  "squash" if native == 512 else "center", bb.flat_params.device, jpeg_split_bytes=self.jpeg_split_bytes,
+                                                  jpeg_progressive=self.jpeg_progressive)
         return self._transform
 
     def _get_embedding(self, image) -> Tensor:

@@ -7,7 +7,11 @@ the files, four kernels decode.  Nothing comes back to the host but the per-imag
 ``split_bytes`` (``JpegPlan``, ``DeviceJpegDecoder``; 0, the default, is the path above, call for call) turns on the decode with many lanes inside one scan
 (include/gg_jscan.h): every restart segment -- the whole scan of a file without restart markers -- is cut into sub-segments of about that many bytes, and
 speculate / resolve / write / DC passes take the place of the one-lane-per-segment entropy kernel.  The bytes are the same whatever the value; ``PackedImages.slow``
-then counts, per image, the sub-segments no speculative lane reached in the true decoder state."""
+then counts, per image, the sub-segments no speculative lane reached in the true decoder state.
+
+``progressive=True`` (``JpegPlan``, ``DeviceJpegDecoder``; off by default, and with it off a progressive file is refused as before) turns on the decode of
+progressive Huffman files (SOF2; include/gg_jprog.h) next to baseline ones in the same batch: the plan walks every scan of such a file, and the entropy decode runs
+in rounds of scans that touch disjoint coefficients (``JpegPlan.scans``, ``JpegPlan.rounds``).  It does not combine with ``split_bytes``."""
 import ctypes as C
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
@@ -43,9 +47,11 @@ class JpegPlan:
     """The host-side plan of one batch (``gg_jpeg_plan_create``): ``info`` (one ``_lib.JpegInfo`` per file: height, width, components, hs, vs, segments, refusal,
     out_offset, stream_offset), ``stream_bytes`` / ``table_bytes`` / ``output_bytes`` / ``workspace_bytes``.  Needs no GPU.  With ``split_bytes`` > 0 the plan is
     ``gg_jscan_plan_create``'s: the same answers, a sub-segment table in the table block, ``subsegments`` (per image), ``total_subsegments`` and a
-    ``workspace_bytes`` that is ``gg_jscan_decode``'s (``base_workspace_bytes`` stays ``gg_jpeg_decode``'s, which takes such a plan too)."""
+    ``workspace_bytes`` that is ``gg_jscan_decode``'s (``base_workspace_bytes`` stays ``gg_jpeg_decode``'s, which takes such a plan too).  With ``progressive`` the plan
+    is ``gg_jprog_plan_create``'s: SOF2 files are accepted too, ``scans`` (per image: 1 for a baseline file, 0 for a refused one) and ``rounds`` (the entropy
+    launches ``gg_jprog_decode`` needs) are set, and the refusal names are ``gg_jprog_refusal_name``'s."""
 
-    def __init__(self, files: Sequence, split_bytes: int = 0):
+    def __init__(self, files: Sequence, split_bytes: int = 0, progressive: bool = False):
         if not is_file_bytes_list(files):
             raise GgError("JpegPlan: files must be a non-empty list of bytes / bytearray / memoryview")
         if len(files) > _lib.JPEG_MAX_B:
@@ -57,7 +63,12 @@ class JpegPlan:
         self._lens = (C.c_int64 * B)(*[v.size for v in self._views])
         self._h = C.c_void_p()
         self.split_bytes = int(split_bytes)
-        if self.split_bytes:
+        self.progressive = bool(progressive)
+        if self.progressive and self.split_bytes:
+            raise GgError("JpegPlan: progressive=True does not combine with split_bytes > 0: progressive scans are not cut into sub-segments")
+        if self.progressive:
+            _lib.check(lib.gg_jprog_plan_create(self._ptrs, self._lens, B, C.byref(self._h)), "gg_jprog_plan_create")
+        elif self.split_bytes:
             _lib.check(lib.gg_jscan_plan_create(self._ptrs, self._lens, B, self.split_bytes, C.byref(self._h)), "gg_jscan_plan_create")
         else:
             _lib.check(lib.gg_jpeg_plan_create(self._ptrs, self._lens, B, C.byref(self._h)), "gg_jpeg_plan_create")
@@ -76,9 +87,15 @@ class JpegPlan:
             self.subsegments = [lib.gg_jscan_plan_subsegments(self._h, b) for b in range(B)]
             self.total_subsegments = lib.gg_jscan_plan_total_subsegments(self._h)
             self.workspace_bytes = lib.gg_jscan_workspace_bytes(self._h)
+        self.scans, self.rounds = None, None
+        if self.progressive:
+            self.scans = [lib.gg_jprog_plan_scans(self._h, b) for b in range(B)]
+            self.rounds = lib.gg_jprog_plan_rounds(self._h)
+            self.workspace_bytes = lib.gg_jprog_workspace_bytes(self._h)
 
     def refusal_name(self, b: int) -> str:
-        return _lib.lib().gg_jpeg_refusal_name(self.info[b].refusal).decode()
+        name = _lib.lib().gg_jprog_refusal_name if self.progressive else _lib.lib().gg_jpeg_refusal_name
+        return name(self.info[b].refusal).decode()
 
     def require_accepted(self) -> None:
         if self.first_refused >= 0:
@@ -112,18 +129,22 @@ class DeviceJpegDecoder:
     is read back), with ``check=False`` its image is all zeros and ``status`` says why.  The read-back of ``check=True`` waits for the decode: one host
     synchronisation per batch, also on the transforms' and embedders' paths, which decode with the default; a pipeline that must not wait decodes with
     ``check=False`` itself, hands the ``PackedImages`` on and looks at ``status`` later.  ``split_bytes`` > 0: the decode with many lanes inside one scan
-    (``gg_jscan_decode``), for files without restart markers; the same bytes, and ``PackedImages.slow``."""
+    (``gg_jscan_decode``), for files without restart markers; the same bytes, and ``PackedImages.slow``.  ``progressive=True``: progressive files (SOF2) are decoded
+    too (``gg_jprog_decode``), next to baseline ones; not together with ``split_bytes``."""
 
-    def __init__(self, device="cuda", split_bytes: int = 0):
+    def __init__(self, device="cuda", split_bytes: int = 0, progressive: bool = False):
         self.device = torch.device(device)
         self.split_bytes = int(split_bytes)
+        self.progressive = bool(progressive)
+        if self.progressive and self.split_bytes:
+            raise GgError("DeviceJpegDecoder: progressive=True does not combine with split_bytes > 0: progressive scans are not cut into sub-segments")
         self._staging: Optional[torch.Tensor] = None
         self._uploaded: Optional[torch.cuda.Event] = None
         self._workspace: Optional[torch.Tensor] = None
 
     def decode(self, files: Sequence, check: bool = True) -> PackedImages:
         _lib.require_gpu()
-        plan = JpegPlan(list(files) if isinstance(files, (list, tuple)) else [files], self.split_bytes)
+        plan = JpegPlan(list(files) if isinstance(files, (list, tuple)) else [files], self.split_bytes, self.progressive)
         try:
             plan.require_accepted()
             if self._uploaded is not None:
@@ -141,7 +162,10 @@ class DeviceJpegDecoder:
                 packed = torch.empty(max(plan.output_bytes, 1), dtype=torch.uint8, device=self.device)
                 status = torch.empty(plan.B, dtype=torch.int32, device=self.device)
                 slow = None
-                if self.split_bytes:
+                if self.progressive:
+                    _lib.check(_lib.lib().gg_jprog_decode(plan.handle, stream_buf.data_ptr(), stream_buf.numel(), packed.data_ptr(), packed.numel(), status.data_ptr(),
+                                                          self._workspace.data_ptr(), self._workspace.numel(), _lib.stream()), "gg_jprog_decode")
+                elif self.split_bytes:
                     slow = torch.empty(plan.B, dtype=torch.int32, device=self.device)
                     _lib.check(_lib.lib().gg_jscan_decode(plan.handle, stream_buf.data_ptr(), stream_buf.numel(), packed.data_ptr(), packed.numel(), status.data_ptr(),
                                                           slow.data_ptr(), self._workspace.data_ptr(), self._workspace.numel(), _lib.stream()), "gg_jscan_decode")

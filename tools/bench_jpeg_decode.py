@@ -18,6 +18,11 @@ Prints one JSON line per row and appends them to --out; per (B, restart) configu
 Timing: the variants alternate within one process after --warmup calls, --repeats times; every row reports the median and the spread (min, max).
     python tools/bench_jpeg_decode.py [--batches 256 1024 --src 640 --quality 90] [--out profiles/jpeg_decode_bench.jsonl]
     python tools/bench_jpeg_decode.py --batches 64 256 1024 --split-bytes 256 512 1024 2048 --skip-e2e --out profiles/jpeg_split_bench.jsonl
+    python tools/bench_jpeg_decode.py --progressive [--batches 256 1024] [--out profiles/jpeg_progressive_bench.jsonl]
+--progressive: the same source images saved with progressive=True, through DeviceJpegDecoder(progressive=True) (gg_jprog_decode, include/gg_jprog.h); three things
+alternate in one process: the device decode of the progressive files (row device_progressive), the 16-thread Pillow pool on those same files (pillow_16_threads)
+and the device baseline decode of the baseline twins (device_baseline_twins; the ratio is recorded, not gated), then one profiled call (device_progressive_stages).
+THE GATE is this path's usual one: at B = 1024 without restart markers device_progressive takes no longer than pillow_16_threads, and every byte equals Pillow's.
 The files: --unique seeded synthetic images (smooth structure plus noise, tools/bench_augment.py's generator), encoded once and repeated to fill the batch; every
 copy is decoded on its own."""
 import argparse
@@ -55,6 +60,88 @@ def pil_decode(f):
     return np.asarray(Image.open(io.BytesIO(f)).convert("RGB"))
 
 
+def progressive_main(a):
+    from PIL import Image
+    from bench_augment import make_sources
+    from geoguessr_ai_amd import _lib as L
+    from geoguessr_ai_amd.training.jpeg import DeviceJpegDecoder, JpegPlan
+    L.require_gpu()
+    lib = L.lib()
+    H = a.src
+    out_path = a.out or os.path.join(ROOT, "profiles", "jpeg_progressive_bench.jsonl")
+    common = dict(tool="bench_jpeg_decode --progressive", src=f"{H}x{H}", quality=a.quality, subsampling="4:2:0", unique=a.unique, seed=a.seed, threads=a.threads,
+                  device=torch.cuda.get_device_name(0), source_hash=L.source_hash()[:12])
+    src = make_sources(a.unique, H, H, a.seed).cpu().numpy()
+
+    def save(im, **kw):
+        buf = io.BytesIO()
+        Image.fromarray(im).save(buf, "JPEG", quality=a.quality, subsampling="4:2:0", **kw)
+        return buf.getvalue()
+    encoded = {False: ([save(im, progressive=True) for im in src], [save(im) for im in src])}
+    try:
+        encoded[True] = ([save(im, progressive=True, restart_marker_rows=1) for im in src], [save(im, restart_marker_rows=1) for im in src])
+    except OSError as e:                                                 # Pillow's progressive encoder can run out of buffer when restart markers are asked for
+        print(json.dumps(dict(common, row="note", note=f"Pillow could not write the progressive files with restart markers: {e}")))
+    pool = ThreadPoolExecutor(a.threads)
+    pdec, bdec = DeviceJpegDecoder("cuda", progressive=True), DeviceJpegDecoder("cuda")
+    rows, gate_ok = [], True
+    for B in a.batches:
+        for restart, (prog, twins) in encoded.items():
+            files, base = [prog[b % a.unique] for b in range(B)], [twins[b % a.unique] for b in range(B)]
+            plan = JpegPlan(files, progressive=True)
+            cfg = dict(common, batch=B, restart="one interval per MCU row" if restart else "none", file_kib=round(sum(len(f) for f in files) / B / 1024, 1),
+                       twin_file_kib=round(sum(len(f) for f in base) / B / 1024, 1), scans_per_file=plan.scans[0], rounds=plan.rounds,
+                       lanes=int(sum(i.segments for i in plan.info)))
+            plan.close()
+            ref = [pil_decode(f) for f in prog]
+            got = pdec.unpack(pdec.decode(files))
+            identical = all(np.array_equal(got[b].cpu().numpy(), ref[b % a.unique]) for b in range(B))
+            del got
+
+            def host16():
+                return list(pool.map(pil_decode, files))
+            for _ in range(a.warmup):
+                host16(); pdec.decode(files); bdec.decode(base)
+            t16, tp, tb = [], [], []
+            for _ in range(a.repeats):                                    # the three alternate: a drift of the machine reaches all of them
+                t = time.perf_counter()
+                host16()
+                t16.append((time.perf_counter() - t) * 1e3)
+                tp.append(wall(lambda: pdec.decode(files)))
+                tb.append(wall(lambda: bdec.decode(base)))
+            s16, sp, sb = spread(t16), spread(tp), spread(tb)
+            gated = B == 1024 and not restart
+            ok = bool(sp["ms"] <= s16["ms"])
+            rows.append(dict(cfg, row="pillow_16_threads", **s16, unit="ms per batch", images_per_s=round(B / s16["ms"] * 1e3, 1)))
+            rows.append(dict(cfg, row="device_progressive", **sp, unit="ms per batch, wall clock, synchronised", images_per_s=round(B / sp["ms"] * 1e3, 1),
+                             pillow_16_threads_over_device=round(s16["ms"] / sp["ms"], 2), byte_identical_to_pillow=identical, gated=gated, device_no_slower=ok))
+            rows.append(dict(cfg, row="device_baseline_twins", **sb, unit="ms per batch, wall clock, synchronised", images_per_s=round(B / sb["ms"] * 1e3, 1),
+                             progressive_over_baseline=round(sp["ms"] / sb["ms"], 2)))
+            gate_ok = gate_ok and identical and (ok or not gated)
+            names = ["fill_and_entropy_rounds", "idct", "status_upsample_colour_pack"]
+            lib.gg_prof_reset()
+            lib.gg_prof_enable(1)
+            pdec.decode(files)
+            torch.cuda.synchronize()
+            lib.gg_prof_enable(0)
+            assert lib.gg_prof_count() == len(names), lib.gg_prof_count()
+            stages, ms = {}, C.c_double()
+            for i, n in enumerate(names):
+                L.check(lib.gg_prof_record(i, None, C.byref(ms), None, None), "gg_prof_record")
+                stages[n] = round(ms.value, 4)
+            lib.gg_prof_reset()
+            rows.append(dict(cfg, row="device_progressive_stages", stage_ms=stages, stage_sum_ms=round(sum(stages.values()), 4), dominant_stage=max(stages, key=stages.get)))
+    for r in rows:
+        print(json.dumps(r))
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "a") as f:
+        for r in rows:
+            f.write(json.dumps(r) + "\n")
+    if not gate_ok:
+        print("GATE MISSED: the progressive device decode is slower than the 16-thread Pillow pool at B = 1024 without restart markers, or bytes differ", file=sys.stderr)
+        sys.exit(1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[256, 1024])
@@ -70,7 +157,10 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--split-bytes", type=int, nargs="*", default=[], help="also time DeviceJpegDecoder(split_bytes=S) for every S given")
     ap.add_argument("--skip-e2e", action="store_true", help="leave out the end_to_end rows (and the embedder they need)")
+    ap.add_argument("--progressive", action="store_true", help="time the progressive decode (gg_jprog_decode) instead; rows go to profiles/jpeg_progressive_bench.jsonl")
     a = ap.parse_args()
+    if a.progressive:
+        return progressive_main(a)
     import warnings
     from PIL import Image
     from bench_augment import make_sources
