@@ -36,6 +36,10 @@ class Split3Args(C.Structure):          # GgSplit3Args (the fp32_split mode's GE
                 ("groups_dev", C.c_void_p), ("group_rows", C.c_int), ("a_map", C.c_void_p), ("c_map", C.c_void_p)]      # row compaction (device-side live row count, row maps)
 
 
+class Split3Route(C.Structure):         # GgSplit3Route (gg_gemm_nt_split3_route: kernel, tile width, epilogue class, mapped form, tile grid, dynamic LDS)
+    _fields_ = [("kernel", C.c_int), ("tile_n", C.c_int), ("epilogue", C.c_int), ("mapped", C.c_int), ("tilesM", C.c_int), ("tilesN", C.c_int), ("lds_bytes", C.c_int64)]
+
+
 class AttnArgs(C.Structure):
     _fields_ = [("qkv", C.c_void_p), ("ld", C.c_int64), ("q_off", C.c_int), ("k_off", C.c_int), ("v_off", C.c_int),
                 ("head_stride", C.c_int), ("head_dim", C.c_int), ("num_heads", C.c_int), ("num_windows", C.c_int),
@@ -216,6 +220,7 @@ SIGNATURES = {
     "gg_gemm_nt_split3_af32": (_I, [C.POINTER(Split3Args), _P, _L, _L, _P]),
     "gg_gemm_nt_split3_af32_stats": (_I, [C.POINTER(Split3Args), _P, _L, _L, _P, _P]),
     "gg_gemm_nt_split3_af32_pro": (_I, [C.POINTER(Split3Args), _P, _L, _L, _P, _P, _P, _I, _P, _P]),
+    "gg_gemm_nt_split3_route": (_I, [C.POINTER(Split3Args), _I, _I, _I, C.POINTER(Split3Route)]),
     "gg_gemm_tn_split3_splits": (_I, [_I, _I, _I]),
     "gg_gemm_tn_split3": (_I, [_P, _L, _P, _L, _I, _I, _I, _P, _I, _P, _I, _P]),
     "gg_gemm_nt_f32": (_I, [C.POINTER(GemmArgs), _P]),

@@ -993,14 +993,26 @@ extern "C" int gg_split3_bf16(const float* x, int64_t rows, int cols, int64_t ld
     return 0;
 }
 
-static int split3_launch(Split3Params& p, void* stream) {
-    const int M = p.M, N = p.N, K = p.K;
+// Which kernel a launch takes, its tile grid, its epilogue class and its LDS: decided in ONE place per entry family (split3_planes_route, split3_af32_route).  The
+// launchers launch what these return and gg_gemm_nt_split3_route reports it, dev switches included, so a test that asks for the route of its arguments cannot be
+// told about another kernel than the one it runs.  The argument checks (split3_planes_check, split3_af32_check) are shared the same way.
+static GgSplit3Route split3_planes_route(int M, int N) {
     // 256 x 128 tile, 4 x 2 waves of 64 x 64 (96 MFMAs per 24 fragment reads, two waves per SIMD), 2-stage ring; a single row of tiles (M <= 128) takes the
     // 128 x 128 tile, 2 x 4 waves, 3-stage ring
     const bool big = M > 128;
-    void (*kern)(Split3Params) = big ? gemm_nt_split3_kernel<256, 128, 4, 2, 2> : gemm_nt_split3_kernel<128, 128, 2, 4, 3>;
-    p.tilesM = (int)gg_cdiv(M, big ? 256 : 128); p.tilesN = (int)gg_cdiv(N, S3_BN);
-    const size_t lds = big ? (size_t)2 * 3 * (256 + 128) * S3_SK * sizeof(bf16) : (size_t)3 * S3_STAGE * sizeof(bf16);
+    GgSplit3Route r;
+    r.kernel = big ? GG_SPLIT3_ROUTE_PLANES_256 : GG_SPLIT3_ROUTE_PLANES_128;
+    r.tile_n = S3_BN; r.epilogue = 0; r.mapped = 0;
+    r.tilesM = (int)gg_cdiv(M, big ? 256 : 128); r.tilesN = (int)gg_cdiv(N, S3_BN);
+    r.lds_bytes = big ? (int64_t)2 * 3 * (256 + 128) * S3_SK * sizeof(bf16) : (int64_t)3 * S3_STAGE * sizeof(bf16);
+    return r;
+}
+static int split3_launch(Split3Params& p, void* stream) {
+    const int M = p.M, N = p.N, K = p.K;
+    const GgSplit3Route r = split3_planes_route(M, N);
+    void (*kern)(Split3Params) = r.kernel == GG_SPLIT3_ROUTE_PLANES_256 ? gemm_nt_split3_kernel<256, 128, 4, 2, 2> : gemm_nt_split3_kernel<128, 128, 2, 4, 3>;
+    p.tilesM = r.tilesM; p.tilesN = r.tilesN;
+    const size_t lds = (size_t)r.lds_bytes;
     GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(kern)));
     // algorithmic work = the fp32 product it replaces: 2 M N K flop; bytes: three bf16 planes per operand + the result (+ the epilogue's tensors)
     const double mn = (double)M * N;
@@ -1012,7 +1024,7 @@ static int split3_launch(Split3Params& p, void* stream) {
     return 0;
 }
 
-extern "C" int gg_gemm_nt_split3_ex(const GgSplit3Args* a, void* stream) {
+static int split3_planes_check(const GgSplit3Args* a) {
     GG_CHECK(a && a->a_planes && a->b_planes && (a->C || a->c_planes) && a->M > 0 && a->N > 0 && a->K > 0, "gg_gemm_nt_split3: null pointer / bad shape");
     GG_CHECK((a->K & 7) == 0 && (a->lda & 7) == 0 && (a->ldb & 7) == 0 && a->lda >= a->K && a->ldb >= a->K, "gg_gemm_nt_split3: K, lda, ldb must be multiples of 8, ld >= K");
     GG_CHECK(((uintptr_t)a->a_planes & 15) == 0 && ((uintptr_t)a->b_planes & 15) == 0 && ((uintptr_t)a->C & 15) == 0 && ((uintptr_t)a->c_planes & 7) == 0,
@@ -1022,6 +1034,11 @@ extern "C" int gg_gemm_nt_split3_ex(const GgSplit3Args* a, void* stream) {
     GG_CHECK((!a->preact && !a->dact_preact) || a->ldc >= a->N, "gg_gemm_nt_split3: preact / dact_preact use ldc");
     GG_CHECK(!a->rowscale || a->rows_per_scale > 0, "gg_gemm_nt_split3: rowscale needs rows_per_scale");
     GG_CHECK(!(a->dact_preact && a->act), "gg_gemm_nt_split3: act and dact_preact are exclusive");
+    GG_CHECK(!a->groups_dev && !a->a_map && !a->c_map, "gg_gemm_nt_split3: row compaction is a form of gg_gemm_nt_split3_af32 only");
+    return 0;
+}
+extern "C" int gg_gemm_nt_split3_ex(const GgSplit3Args* a, void* stream) {
+    GG_TRY(split3_planes_check(a));
     Split3Params p;
     p.a_stat = p.a_gamma = p.a_beta = nullptr; p.a_act = 0;
     p.A = (const bf16*)a->a_planes; p.lda = a->lda; p.plane_a = (int64_t)a->M * a->lda; p.Af = nullptr; p.ldaf = 0;
@@ -1029,7 +1046,6 @@ extern "C" int gg_gemm_nt_split3_ex(const GgSplit3Args* a, void* stream) {
     p.C = a->C; p.ldc = a->ldc ? a->ldc : a->N; p.bias = a->bias; p.M = a->M; p.N = a->N; p.K = a->K;
     p.act = a->act; p.preact = a->preact; p.rowscale = a->rowscale; p.rows_per_scale = a->rows_per_scale; p.residual = a->residual; p.ldr = a->ldr;
     p.dact_preact = a->dact_preact; p.dact = a->dact; p.c_planes = (bf16*)a->c_planes; p.ldp = a->ldp; p.colstats = nullptr;
-    GG_CHECK(!a->groups_dev && !a->a_map && !a->c_map, "gg_gemm_nt_split3: row compaction is a form of gg_gemm_nt_split3_af32 only");
     p.groups_dev = nullptr; p.group_rows = 0; p.a_map = p.c_map = nullptr;
     return split3_launch(p, stream);
 }
@@ -1053,14 +1069,19 @@ static int split3_af32_launch(const GgSplit3Args* a, const float* A, int64_t lda
 extern "C" int gg_gemm_nt_split3_af32_stats(const GgSplit3Args* a, const float* A, int64_t lda, int64_t b_plane_stride, float* colstats, void* stream) {
     return split3_af32_launch(a, A, lda, b_plane_stride, colstats, nullptr, nullptr, nullptr, 0, stream);
 }
+// what the prologue form asks of its arguments beyond split3_af32_check (shared with gg_gemm_nt_split3_route)
+static int split3_pro_check(const GgSplit3Args* a, int bn_act) {
+    GG_CHECK(a && a->K >= 384 && a->K <= 1024, "gg_gemm_nt_split3_af32_pro: K must be 384 ... 1024");
+    GG_CHECK(bn_act >= 0 && bn_act <= 2, "gg_gemm_nt_split3_af32_pro: act must be GG_ACT_NONE, GG_ACT_GELU or GG_ACT_QUICK_GELU");
+    GG_CHECK(!(a->bias || a->act || a->rowscale || a->residual || a->dact_preact || a->preact || a->c_planes), "gg_gemm_nt_split3_af32_pro: plain epilogue only");
+    return 0;
+}
 // A := act(BatchNorm(A)) formed in the loader (bn_stat = [mean | rstd][K] as gg_bn_finalize leaves it; act GG_ACT_NONE / GELU / QUICK_GELU): the split twin of
 // GgGemmArgs.a_bn_* (gg_gemm_nt_f32's BatchNorm prologue).  K >= 384 (the 256 x 128 form), K <= 1024, plain epilogue (optionally with colstats)
 extern "C" int gg_gemm_nt_split3_af32_pro(const GgSplit3Args* a, const float* A, int64_t lda, int64_t b_plane_stride, const float* bn_stat, const float* bn_gamma,
                                           const float* bn_beta, int bn_act, float* colstats, void* stream) {
     GG_CHECK(bn_stat && bn_gamma && bn_beta, "gg_gemm_nt_split3_af32_pro: the BatchNorm prologue needs stat, gamma, beta");
-    GG_CHECK(a && a->K >= 384 && a->K <= 1024, "gg_gemm_nt_split3_af32_pro: K must be 384 ... 1024");
-    GG_CHECK(bn_act >= 0 && bn_act <= 2, "gg_gemm_nt_split3_af32_pro: act must be GG_ACT_NONE, GG_ACT_GELU or GG_ACT_QUICK_GELU");
-    GG_CHECK(!(a->bias || a->act || a->rowscale || a->residual || a->dact_preact || a->preact || a->c_planes), "gg_gemm_nt_split3_af32_pro: plain epilogue only");
+    GG_TRY(split3_pro_check(a, bn_act));
     return split3_af32_launch(a, A, lda, b_plane_stride, colstats, bn_stat, bn_gamma, bn_beta, bn_act, stream);
 }
 // the tile form split3_af32_launch picks for (N, K) without a prologue: 256-row tiles from K = 384 on, 96-column tiles where they save a fifth of the columns
@@ -1077,8 +1098,8 @@ bool gg_split3_af32_takes_rowmap(int N, int K) {
     split3_af32_form(N, K, big, n96);
     return big && !n96;
 }
-static int split3_af32_launch(const GgSplit3Args* a, const float* A, int64_t lda, int64_t b_plane_stride, float* colstats, const float* bn_stat, const float* bn_gamma,
-                              const float* bn_beta, int bn_act, void* stream) {
+// the argument checks of every A-as-f32 call (with_colstats: the call passes a colstats buffer; pro: it carries the BatchNorm prologue)
+static int split3_af32_check(const GgSplit3Args* a, const float* A, int64_t lda, bool with_colstats, bool pro) {
     GG_CHECK(a && A && a->b_planes && (a->C || a->c_planes) && a->M > 0 && a->N > 0 && a->K > 0, "gg_gemm_nt_split3_af32: null pointer / bad shape");
     GG_CHECK((a->K & 7) == 0 && (lda & 3) == 0 && (a->ldb & 7) == 0 && lda >= a->K && a->ldb >= a->K, "gg_gemm_nt_split3_af32: K %% 8, lda %% 4, ldb %% 8, ld >= K");
     GG_CHECK(((uintptr_t)A & 15) == 0 && ((uintptr_t)a->b_planes & 15) == 0 && ((uintptr_t)a->C & 15) == 0 && ((uintptr_t)a->c_planes & 7) == 0, "gg_gemm_nt_split3_af32: alignment");
@@ -1087,7 +1108,7 @@ static int split3_af32_launch(const GgSplit3Args* a, const float* A, int64_t lda
     GG_CHECK((!a->preact && !a->dact_preact) || a->ldc >= a->N, "gg_gemm_nt_split3_af32: preact / dact_preact use ldc");
     GG_CHECK(!a->rowscale || a->rows_per_scale > 0, "gg_gemm_nt_split3_af32: rowscale needs rows_per_scale");
     GG_CHECK(!(a->dact_preact && a->act), "gg_gemm_nt_split3_af32: act and dact_preact are exclusive");
-    GG_CHECK(!colstats || !(a->bias || a->act || a->rowscale || a->residual || a->dact_preact || a->preact || a->c_planes), "gg_gemm_nt_split3_af32: colstats needs the plain epilogue");
+    GG_CHECK(!with_colstats || !(a->bias || a->act || a->rowscale || a->residual || a->dact_preact || a->preact || a->c_planes), "gg_gemm_nt_split3_af32: colstats needs the plain epilogue");
     GG_CHECK(((uintptr_t)a->preact & 15) == 0 && ((uintptr_t)a->residual & 15) == 0 && ((uintptr_t)a->dact_preact & 15) == 0,
              "gg_gemm_nt_split3_af32: preact, residual and dact_preact must be 16-byte aligned (the row epilogue moves them 16 bytes at a time)");
     // row compaction: the device-side live row count and the optional row maps (the 256 x 128 form without prologue, 128-column tiles, f32 result)
@@ -1095,53 +1116,73 @@ static int split3_af32_launch(const GgSplit3Args* a, const float* A, int64_t lda
     GG_CHECK(mapped || (!a->a_map && !a->c_map), "gg_gemm_nt_split3_af32: a_map / c_map need groups_dev");
     if (mapped) {
         GG_CHECK(a->group_rows > 0 && a->M % a->group_rows == 0, "gg_gemm_nt_split3_af32: groups_dev needs group_rows > 0 that divides M");
-        GG_CHECK(a->C && !a->c_planes && !colstats && !bn_stat, "gg_gemm_nt_split3_af32: row compaction takes the f32 result only (no planes, column statistics or prologue)");
+        GG_CHECK(a->C && !a->c_planes && !with_colstats && !pro, "gg_gemm_nt_split3_af32: row compaction takes the f32 result only (no planes, column statistics or prologue)");
         GG_CHECK(!a->rowscale || !(a->a_map || a->c_map) || a->rows_per_scale == a->group_rows, "gg_gemm_nt_split3_af32: with a row map the row scale is per group (rows_per_scale == group_rows)");
         GG_CHECK(!a->a_map || (int64_t)a->M * lda * 4 < ((int64_t)1 << 31), "gg_gemm_nt_split3_af32: a mapped A must stay below 2 GiB");
     }
-    Split3Params p;
-    p.colstats = colstats;
-    p.groups_dev = a->groups_dev; p.group_rows = a->group_rows; p.a_map = a->a_map; p.c_map = a->c_map;
-    p.a_stat = bn_stat; p.a_gamma = bn_gamma; p.a_beta = bn_beta; p.a_act = bn_act;
-    const bool pro = bn_stat != nullptr;
-    p.A = nullptr; p.lda = 0; p.plane_a = 0; p.Af = A; p.ldaf = lda;
-    p.B = (const bf16*)a->b_planes; p.ldb = a->ldb; p.plane_b = b_plane_stride > 0 ? b_plane_stride : (int64_t)a->N * a->ldb;
-    p.C = a->C; p.ldc = a->ldc ? a->ldc : a->N; p.bias = a->bias; p.M = a->M; p.N = a->N; p.K = a->K;
-    p.act = a->act; p.preact = a->preact; p.rowscale = a->rowscale; p.rows_per_scale = a->rows_per_scale; p.residual = a->residual; p.ldr = a->ldr;
-    p.dact_preact = a->dact_preact; p.dact = a->dact; p.c_planes = (bf16*)a->c_planes; p.ldp = a->ldp;
+    return 0;
+}
+// the route of an A-as-f32 call that passed split3_af32_check; -1 for the shapes the chosen form cannot serve
+static int split3_af32_route(const GgSplit3Args* a, bool with_colstats, bool pro, GgSplit3Route& r) {
+    const bool mapped = a->groups_dev != nullptr;
     // 256 x 128 (one 144 KB workgroup per CU) from K = 384 on; 128 x 128 (two per CU) for the short contractions of stage 1, where a tile lives only 6 stages and
     // the second workgroup hides its prologue / epilogue (K = 192: 1.30 x against 1.22 x the f32-MFMA GEMM; at K >= 384 the big tile wins by 1-2 %)
     // 96-column tiles where 128-column ones would waste a fifth or more of their work on columns beyond N that 96-column ones do not (N = 192: 25 % -> -8...-11 %
     // in time; N = 576, 10 %: the narrower tile's higher LDS traffic per MFMA costs more than the waste)
     bool big, n96;
-    split3_af32_form(p.N, p.K, big, n96);
+    split3_af32_form(a->N, a->K, big, n96);
     big = big || pro;
     const int bn = n96 ? 96 : 128;
-    GG_CHECK(!mapped || (big && !n96), "gg_gemm_nt_split3_af32: row compaction runs on the 256 x 128 form only (K >= 384, N not better served by 96-column tiles; got N %d K %d)", p.N, p.K);
-    p.tilesM = (int)gg_cdiv(p.M, big ? 256 : 128); p.tilesN = (int)gg_cdiv(p.N, bn);
+    GG_CHECK(!mapped || (big && !n96), "gg_gemm_nt_split3_af32: row compaction runs on the 256 x 128 form only (K >= 384, N not better served by 96-column tiles; got N %d K %d)", a->N, a->K);
+    r.kernel = big ? GG_SPLIT3_ROUTE_AF32_256 : GG_SPLIT3_ROUTE_AF32_128;
+    r.tile_n = bn; r.mapped = mapped ? 1 : 0;
+    r.tilesM = (int)gg_cdiv(a->M, big ? 256 : 128); r.tilesN = (int)gg_cdiv(a->N, bn);
     // epilogue class (split3_epilogue_rows_ec) when the shape takes the vector path and the options are one of the models' six combinations; 0 = the generic epilogue
     static const char* eenv = gg_dev_env("GG_SPLIT3_NO_EC");       // dev: the generic epilogue everywhere
+    const int64_t ldc = a->ldc ? a->ldc : a->N;
     int ec = 0;
-    if (!eenv && p.C && !p.c_planes && !p.colstats && (p.N & 7) == 0 && (p.ldc & 3) == 0 && (!p.residual || (p.ldr & 3) == 0) && (!p.bias || ((uintptr_t)p.bias & 15) == 0)) {
-        if ((p.act == 1 || p.act == 2) && p.preact && !p.rowscale && !p.residual && !p.dact_preact) ec = p.act == 1 ? 2 : 5;
-        else if (p.dact_preact && (p.dact == 1 || p.dact == 2) && !p.bias && !p.act && !p.preact && !p.residual) ec = p.dact == 1 ? 3 : 6;
-        else if (p.residual && !p.act && !p.preact && !p.dact_preact) ec = 4;
-        else if (!p.act && !p.preact && !p.rowscale && !p.residual && !p.dact_preact) ec = 1;
+    if (!pro && !eenv && a->C && !a->c_planes && !with_colstats && (a->N & 7) == 0 && (ldc & 3) == 0 && (!a->residual || (a->ldr & 3) == 0) && (!a->bias || ((uintptr_t)a->bias & 15) == 0)) {
+        if ((a->act == 1 || a->act == 2) && a->preact && !a->rowscale && !a->residual && !a->dact_preact) ec = a->act == 1 ? 2 : 5;
+        else if (a->dact_preact && (a->dact == 1 || a->dact == 2) && !a->bias && !a->act && !a->preact && !a->residual) ec = a->dact == 1 ? 3 : 6;
+        else if (a->residual && !a->act && !a->preact && !a->dact_preact) ec = 4;
+        else if (!a->act && !a->preact && !a->rowscale && !a->residual && !a->dact_preact) ec = 1;
     }
+    if (mapped && ec > 4) ec = 0;                                   // (the QuickGELU classes have no compacted user: the generic epilogue serves them)
+    r.epilogue = ec;
+    r.lds_bytes = (int64_t)(big ? (size_t)2 * 3 * (256 + bn) * S3_SK * sizeof(bf16) : (size_t)3 * (128 + 2 * bn) * S3_SK * sizeof(bf16)) +
+                  (int64_t)(pro ? (size_t)2 * (((a->K + 31) & ~31) + 3 * S3_SK) * sizeof(float) : 0);
+    GG_CHECK(r.lds_bytes <= 160 * 1024, "gg_gemm_nt_split3_af32: the ring plus the prologue table exceed the LDS");
+    return 0;
+}
+static int split3_af32_launch(const GgSplit3Args* a, const float* A, int64_t lda, int64_t b_plane_stride, float* colstats, const float* bn_stat, const float* bn_gamma,
+                              const float* bn_beta, int bn_act, void* stream) {
+    const bool pro = bn_stat != nullptr;
+    GG_TRY(split3_af32_check(a, A, lda, colstats != nullptr, pro));
+    GgSplit3Route r;
+    GG_TRY(split3_af32_route(a, colstats != nullptr, pro, r));
+    const bool mapped = r.mapped != 0, big = r.kernel == GG_SPLIT3_ROUTE_AF32_256, n96 = r.tile_n == 96;
+    const int ec = r.epilogue;
+    Split3Params p;
+    p.colstats = colstats;
+    p.groups_dev = a->groups_dev; p.group_rows = a->group_rows; p.a_map = a->a_map; p.c_map = a->c_map;
+    p.a_stat = bn_stat; p.a_gamma = bn_gamma; p.a_beta = bn_beta; p.a_act = bn_act;
+    p.A = nullptr; p.lda = 0; p.plane_a = 0; p.Af = A; p.ldaf = lda;
+    p.B = (const bf16*)a->b_planes; p.ldb = a->ldb; p.plane_b = b_plane_stride > 0 ? b_plane_stride : (int64_t)a->N * a->ldb;
+    p.C = a->C; p.ldc = a->ldc ? a->ldc : a->N; p.bias = a->bias; p.M = a->M; p.N = a->N; p.K = a->K;
+    p.act = a->act; p.preact = a->preact; p.rowscale = a->rowscale; p.rows_per_scale = a->rows_per_scale; p.residual = a->residual; p.ldr = a->ldr;
+    p.dact_preact = a->dact_preact; p.dact = a->dact; p.c_planes = (bf16*)a->c_planes; p.ldp = a->ldp;
+    p.tilesM = r.tilesM; p.tilesN = r.tilesN;
 #define S3_EC(K, ...) (ec == 1 ? K<__VA_ARGS__, 1> : ec == 2 ? K<__VA_ARGS__, 2> : ec == 3 ? K<__VA_ARGS__, 3> : ec == 4 ? K<__VA_ARGS__, 4> : ec == 5 ? K<__VA_ARGS__, 5> : ec == 6 ? K<__VA_ARGS__, 6> : K<__VA_ARGS__, 0>)
     void (*kern)(Split3Params) = pro ? (n96 ? (bn_act == 1 ? gemm_nt_split3a_kernel<3, 0, 2> : bn_act == 2 ? gemm_nt_split3a_kernel<3, 0, 3> : gemm_nt_split3a_kernel<3, 0, 1>)
                                             : (bn_act == 1 ? gemm_nt_split3a_kernel<4, 0, 2> : bn_act == 2 ? gemm_nt_split3a_kernel<4, 0, 3> : gemm_nt_split3a_kernel<4, 0, 1>)) :
                                  !big ? (n96 ? S3_EC(gemm_nt_split3b_kernel, 3) : S3_EC(gemm_nt_split3b_kernel, 4)) :
                                         (n96 ? S3_EC(gemm_nt_split3a_kernel, 3) : S3_EC(gemm_nt_split3a_kernel, 4));
     if (mapped) {
-        if (ec > 4) ec = 0;                                         // (the QuickGELU classes have no compacted user: the generic epilogue serves them)
         kern = ec == 1 ? gemm_nt_split3a_kernel<4, 1, 0, true> : ec == 2 ? gemm_nt_split3a_kernel<4, 2, 0, true> : ec == 3 ? gemm_nt_split3a_kernel<4, 3, 0, true> :
                ec == 4 ? gemm_nt_split3a_kernel<4, 4, 0, true> : gemm_nt_split3a_kernel<4, 0, 0, true>;
     }
 #undef S3_EC
-    const size_t lds = (big ? (size_t)2 * 3 * (256 + bn) * S3_SK * sizeof(bf16) : (size_t)3 * (128 + 2 * bn) * S3_SK * sizeof(bf16)) +
-                       (pro ? (size_t)2 * (((p.K + 31) & ~31) + 3 * S3_SK) * sizeof(float) : 0);
-    GG_CHECK(lds <= 160 * 1024, "gg_gemm_nt_split3_af32: the ring plus the prologue table exceed the LDS");
+    const size_t lds = (size_t)r.lds_bytes;
     GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(kern)));
     // (declared work: the live rows' -- while the profiling hooks are on the count is read back, a blocking copy)
     const double Mp = mapped ? (double)gg_prof_live_groups(a->groups_dev, p.M / a->group_rows, stream) * a->group_rows : (double)p.M;
@@ -1152,6 +1193,22 @@ static int split3_af32_launch(const GgSplit3Args* a, const float* A, int64_t lda
     hipLaunchKernelGGL(kern, dim3((unsigned)(p.tilesM * p.tilesN)), dim3(big ? 512 : 256), lds, (hipStream_t)stream, p);
     GG_LAUNCH_CHECK();
     return 0;
+}
+
+// Host arithmetic only (no launch, no device): what split3_planes_route / split3_af32_route answer for these arguments behind the launches' own argument checks.
+// af32 = 1: the f32 operand's address and pitch are args->a_planes / args->lda; pro: 0 or 1 + the prologue's activation code
+extern "C" int gg_gemm_nt_split3_route(const GgSplit3Args* a, int af32, int pro, int with_colstats, GgSplit3Route* out) {
+    GG_CHECK(a && out, "gg_gemm_nt_split3_route: null pointer");
+    GG_CHECK(pro == 0 || af32, "gg_gemm_nt_split3_route: the BatchNorm prologue is a form of gg_gemm_nt_split3_af32 only");
+    GG_CHECK(!with_colstats || af32, "gg_gemm_nt_split3_route: column statistics are a form of gg_gemm_nt_split3_af32 only");
+    if (!af32) {
+        GG_TRY(split3_planes_check(a));
+        *out = split3_planes_route(a->M, a->N);
+        return 0;
+    }
+    if (pro) GG_TRY(split3_pro_check(a, pro - 1));
+    GG_TRY(split3_af32_check(a, (const float*)a->a_planes, a->lda, with_colstats != 0, pro != 0));
+    return split3_af32_route(a, with_colstats != 0, pro != 0, *out);
 }
 
 extern "C" int gg_gemm_tn_f32_splits(int M, int N, int K);

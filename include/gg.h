@@ -296,6 +296,24 @@ int gg_gemm_nt_split3_af32_stats(const GgSplit3Args* args, const float* A, int64
  * tensor ever being written (timm MBConv.forward, reached from models/tinyvit.py:135).  384 <= K <= 1024, plain epilogue, colstats optional. */
 int gg_gemm_nt_split3_af32_pro(const GgSplit3Args* args, const float* A, int64_t lda, int64_t b_plane_stride, const float* bn_stat, const float* bn_gamma,
                                const float* bn_beta, int bn_act, float* colstats, void* stream);
+/* Which kernel the NT split GEMMs launch for these arguments: host arithmetic only (no launch, no device needed), answered by the code the launches themselves obey,
+ * development switches included.  af32 = 0: gg_gemm_nt_split3_ex (operands as planes).  af32 = 1: gg_gemm_nt_split3_af32 / _stats / _pro, with the f32 operand's address
+ * and row pitch passed in args->a_planes / args->lda and the weight's planes N * ldb apart.  pro: 0, or 1 + the activation code of the BatchNorm prologue (_pro);
+ * with_colstats: the call passes a colstats buffer.  Pointers are tested for null and alignment, never dereferenced.  Returns 0 and fills *out, or -1 for arguments
+ * the launch refuses. */
+#define GG_SPLIT3_ROUTE_PLANES_256 0   /* plane-fed, 256 x 128 tile, two-stage ring (M > 128) */
+#define GG_SPLIT3_ROUTE_PLANES_128 1   /* plane-fed, 128 x 128 tile, three-stage ring */
+#define GG_SPLIT3_ROUTE_AF32_256 2     /* A as f32, 256-row tile */
+#define GG_SPLIT3_ROUTE_AF32_128 3     /* A as f32, 128-row tile */
+typedef struct {
+    int kernel;                 /* GG_SPLIT3_ROUTE_* */
+    int tile_n;                 /* tile width: 128 or 96 columns */
+    int epilogue;               /* 0: the generic row epilogue; 1-6: the compile-time epilogue classes */
+    int mapped;                 /* 1: the row-compaction form (groups_dev) */
+    int tilesM, tilesN;         /* the grid is tilesM x tilesN workgroups */
+    int64_t lds_bytes;          /* dynamic LDS of the launch */
+} GgSplit3Route;
+int gg_gemm_nt_split3_route(const GgSplit3Args* args, int af32, int pro, int with_colstats, GgSplit3Route* out);
 /* weight gradient dW[N][K] = sum_m s_m dY[m][n] X[m][k] as split products (both f32 operands split in the kernel's loader): the arguments and the slab protocol
  * of gg_gemm_tn_f32 (partials [splits][N][K], reduced by gg_splitk_reduce); splits from gg_gemm_tn_split3_splits. */
 int gg_gemm_tn_split3_splits(int M, int N, int K);

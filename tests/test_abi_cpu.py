@@ -34,6 +34,11 @@ def test_header_symbols_exported_and_bound(L):
     a.A, a.B, a.C, a.lda, a.ldb, a.ldc, a.M, a.N, a.K, a.split_k = 0x10000, 0x10000, 0x10000, 192, 192, 200, 1030, 200, 192, 1
     g, tm, tn = C.c_int(-1), C.c_int(-1), C.c_int(-1)
     assert lib.gg_gemm_nt_route(C.byref(a), C.byref(g), C.byref(tm), C.byref(tn)) == 2 and (g.value, tm.value, tn.value) == (0, 6, 2)
+    # ... and the route report of the NT split GEMMs (tests/test_split3_cases_cpu.py): A as f32 [1030][200], weight planes [200][200], K = 192 -> the 128-row kernel
+    s3, r3 = L.Split3Args(), L.Split3Route()
+    s3.a_planes, s3.lda, s3.b_planes, s3.ldb, s3.C, s3.ldc, s3.M, s3.N, s3.K = 0x10000, 200, 0x10000, 200, 0x10000, 208, 1030, 200, 192
+    assert lib.gg_gemm_nt_split3_route(C.byref(s3), 1, 0, 0, C.byref(r3)) == 0
+    assert (r3.kernel, r3.tile_n, r3.epilogue, r3.mapped, r3.tilesM, r3.tilesN, r3.lds_bytes) == (3, 128, 1, 0, 9, 2, 73728)
     # argument counts of the ctypes signatures agree with the header
     for n in L.SYMBOLS:
         m = re.search(r"\b" + n + r"\s*\(([^;]*?)\)\s*;", hdr, re.S)

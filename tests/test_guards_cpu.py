@@ -121,6 +121,7 @@ EXEMPT = {
                            "gg_clip_first_trained_layer", "gg_tinyvit_num_tensors", "gg_tinyvit_tensor_info", "gg_tinyvit_param_floats", "gg_tinyvit_buffer_floats",
                            "gg_tinyvit_num_counters", "gg_tinyvit_num_drop_slots", "gg_tinyvit_activation_info", "gg_tinyvit_activation_info_masked")},
     "gg_gemm_nt_route": "route report: host arithmetic on a GgGemmArgs whose pointers are only tested for alignment, never dereferenced (tests/test_gemm16_cases_cpu.py)",
+    "gg_gemm_nt_split3_route": "route report: host arithmetic on a GgSplit3Args whose pointers are only tested for null and alignment, never dereferenced (tests/test_split3_cases_cpu.py)",
     "gg_attention_route": "route report: host arithmetic on a GgAttnArgs whose pointers are only tested for null and alignment, never dereferenced (tests/test_attention_route_cpu.py)",
     **{n: _CAP for n in ("gg_gemm_colstats_rows", "gg_stat_rows_capacity", "gg_gemm_tn_splits", "gg_gemm_tn_f32_splits", "gg_gemm_tn_split3_splits", "gg_colsum_scratch_floats",
                          "gg_bn_bwd_rows", "gg_bn_bwd_scratch_floats", "gg_layernorm_bwd_scratch_floats", "gg_layernorm_bwd_colsum_rows", "gg_attention_flash_dbias_rows",
@@ -199,7 +200,7 @@ def test_every_entry_point_is_guarded_or_exempt():
     assert all(isinstance(r, str) and len(r) > 10 for r in EXEMPT.values())
     # only the kinds of entry point that take none of the caller's tensors may be exempt
     ok = ("_rows", "_floats", "_splits", "_bytes", "_capacity", "_info", "_num_", "gg_prof_", "gg_graph_", "gg_comm_", "gg_version", "gg_last_error", "_padded_tokens",
-          "_single_pass", "_first_trained_layer", "_workspace_bytes_masked", "_info_masked", "_nt_route", "gg_attention_route")
+          "_single_pass", "_first_trained_layer", "_workspace_bytes_masked", "_info_masked", "_nt_route", "gg_attention_route", "_split3_route")
     assert all(any(k in n for k in ok) for n in EXEMPT), [n for n in EXEMPT if not any(k in n for k in ok)]
     # the detector itself: taking any one entry point out of the registry is reported by name
     for victim in ("gg_gemm_nt", "gg_proto_refine", "gg_tinyvit_backward", "gg_dwconv3x3_s2_bwd_data_fused_f32"):
