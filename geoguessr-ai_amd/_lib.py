@@ -474,6 +474,22 @@ ATTN16WB_SIGNATURES = {
 }
 ATTN16WB_SYMBOLS = list(ATTN16WB_SIGNATURES)
 
+# every exported symbol of include/gg_wgrad_resident.h (the fp32_split weight gradient of a small dense convolution with the whole output resident in one workgroup), bound from the same libgg.so
+WGRAD_RESIDENT_SIGNATURES = {
+    "gg_gemm_tn_split3_resident_fits": (_I, [_I, _I]),
+    "gg_gemm_tn_split3_resident_splits": (_I, [_I, _I, _I]),
+    "gg_gemm_tn_split3_resident": (_I, [_P, _L, _P, _L, _I, _I, _I, _P, _I, _P]),
+}
+WGRAD_RESIDENT_SYMBOLS = list(WGRAD_RESIDENT_SIGNATURES)
+
+# every exported symbol of include/gg_conv_dgrad_parity.h (the fp32_split data gradient of a 3 x 3 stride-2 convolution by input parity with the BatchNorm-backward epilogue), bound from the same libgg.so
+DGRAD_PARITY_SIGNATURES = {
+    "gg_conv3x3s2_dgrad_fits": (_I, [_I, _I, _I, _I]),
+    "gg_conv3x3s2_dgrad_planes_bytes": (_L, [_I, _I]),
+    "gg_conv3x3s2_dgrad_bnbwd_split3": (_I, [_P, _P, _L, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
+}
+DGRAD_PARITY_SYMBOLS = list(DGRAD_PARITY_SIGNATURES)
+
 
 # every exported symbol of include/gg_attn_route.h (the route report of the attention entry points: host arithmetic, no device), its struct and its two enums
 class AttnRoutePass(C.Structure):
@@ -511,7 +527,7 @@ def lib() -> C.CDLL:
             raise GgError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JSCAN_SIGNATURES.items()) + list(JPROG_SIGNATURES.items()) + list(PANO_SIGNATURES.items()) + list(ATTN16_SIGNATURES.items()) + list(ATTN16W_SIGNATURES.items()) + list(ATTN16B_SIGNATURES.items()) + list(ATTN16WB_SIGNATURES.items()) + list(ATTN_ROUTE_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JSCAN_SIGNATURES.items()) + list(JPROG_SIGNATURES.items()) + list(PANO_SIGNATURES.items()) + list(ATTN16_SIGNATURES.items()) + list(ATTN16W_SIGNATURES.items()) + list(ATTN16B_SIGNATURES.items()) + list(ATTN16WB_SIGNATURES.items()) + list(ATTN_ROUTE_SIGNATURES.items()) + list(WGRAD_RESIDENT_SIGNATURES.items()) + list(DGRAD_PARITY_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the library lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -574,6 +590,8 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(root), "include", "gg_attn16b.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_attn16wb.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_attn_route.h"))
+    files.append(os.path.join(os.path.dirname(root), "include", "gg_wgrad_resident.h"))
+    files.append(os.path.join(os.path.dirname(root), "include", "gg_conv_dgrad_parity.h"))
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

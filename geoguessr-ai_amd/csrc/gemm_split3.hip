@@ -27,6 +27,8 @@
 #include <stdlib.h>
 #include <string.h>
 #include "../../include/gg.h"
+#include "../../include/gg_wgrad_resident.h"
+#include "../../include/gg_conv_dgrad_parity.h"
 
 namespace {
 
@@ -960,6 +962,410 @@ __global__ __launch_bounds__(512) void gemm_tn_split3_kernel(Split3TnParams p) {
     }
 }
 
+// ------------------------------------------------------------------------------------------- weight gradient (TN), the whole output resident in one workgroup
+// The same product for a SMALL output (N <= 96, K <= 448: patch_embed.conv2's dW[96][432] over 3.2 M rows): the tiled kernel above covers 432 x 96 with four
+// 256 x 128 tiles of which 63 % is output, and every tile reads the slab's dY and X rows again.  Here one workgroup holds all 6 x 27 MFMA tiles (2 x 4 waves; a wave
+// owns 3 n-tiles x the 7 k-tiles wk, wk + 4, ... : 84 accumulator registers) and contracts its row slab over them: both operands are read once and no tile is padding
+// but the 28th k-tile.  The three planes of a 32-row stage of X (84 KB) leave no room for a second stage, so the X image is single-buffered in two HALVES (columns
+// 0 - 255: every wave's first four k-tiles; 256 - 447: its last three) and a stage runs in two phases of one barrier each:
+//   phase 0 (s): MFMAs over half 0 of stage s  |  the split of half 1 of stage s and of dY of stage s + 1 is written (that half was last read in phase 1 (s - 1))
+//   phase 1 (s): MFMAs over half 1 of stage s  |  the split of half 0 of stage s + 1 is written (last read in phase 0 (s))
+// dY (18 KB per stage) is double-buffered and its nine fragments stay in registers for both phases.  The f32 rows of the next writes are loaded a full stage ahead
+// (nine f32x4 per thread), as the kernels above hold A.  Products, plane order (small terms first) and the slab protocol are gemm_tn_split3_kernel's.
+constexpr int S3R_N = 96, S3R_K = 448, S3R_KH = 256;              // capacity of the resident output; the column where the second half of the X image starts
+struct Split3TnResParams { const float* dY; int64_t ldy; const float* X; int64_t ldx; int M, N, K; float* part; int rows_per_split; };
+__global__ __launch_bounds__(512) void gemm_tn_split3_resident_kernel(Split3TnResParams p) {
+    constexpr int SUB = 1024, PY = (S3R_N / 32) * SUB, PX = (S3R_K / 32) * SUB;      // plane images as sub-images of 32 columns x 32 rows (gemm_tn_split3_kernel's)
+    extern __shared__ __attribute__((aligned(16))) bf16 s3mem[];
+    bf16* const Xim = s3mem;                                        // [3][PX]
+    bf16* const Yim = s3mem + 3 * PX;                               // [2][3][PY]
+    const int slab = blockIdx.x;
+    const int m_begin = slab * p.rows_per_split, rows = min(p.M - m_begin, p.rows_per_split);
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wn = wave >> 2, wk = wave & 3;                        // wave: n range 48 wn, k-tiles wk + 4 j
+    const int lr = lane & 15, lg = lane >> 4;
+    const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc((void*)(p.dY + (int64_t)m_begin * p.ldy), 0, (int)((unsigned)rows * (unsigned)p.ldy * 4u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)(p.X + (int64_t)m_begin * p.ldx), 0, (int)((unsigned)rows * (unsigned)p.ldx * 4u), 0x00020000);
+    const int nk = (rows + 31) >> 5;
+    // loader items of a thread (one f32x4 each): 0 - 3 X half 0 (64 per row), 4 - 6 X half 1 (48 per row), 7 - 8 dY (24 per row; the second only for the first 256
+    // threads); columns beyond K / N are masked and come back as zeros, so the images hold zeros there
+    unsigned voff[9];
+    int ldso[9];
+#pragma unroll
+    for (int it = 0; it < 9; ++it) {
+        int row, col;
+        bool in;
+        if (it < 4) { row = (int)(threadIdx.x >> 6) + 8 * it; col = (int)(threadIdx.x & 63) * 4; in = col < p.K; }
+        else if (it < 7) { const int idx = (int)threadIdx.x + 512 * (it - 4); row = idx / 48; col = S3R_KH + (idx % 48) * 4; in = col < p.K; }
+        else { const int idx = (int)threadIdx.x + 512 * (it - 7); row = min(idx / 24, 31); col = (idx % 24) * 4; in = idx < 32 * 24 && col < p.N; }
+        voff[it] = in ? (unsigned)row * (unsigned)(it < 7 ? p.ldx : p.ldy) * 4u + (unsigned)col * 4u : 0xFFFFFFF0u;
+        ldso[it] = (col >> 5) * SUB + s3_img_off(row, (col & 31) >> 3) + (col & 4);
+    }
+    const bool y2 = threadIdx.x < 32 * 24 - 512;                    // item 8 exists for this thread
+    auto load1 = [&](int it, int st) -> f32x4 {                     // (rows beyond the slab fail the descriptor's range check: zeros)
+        const unsigned vo = st < nk ? voff[it] : 0xFFFFFFF0u;
+        if (it < 7) return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsX, (int)vo, (int)((unsigned)st * 32u * (unsigned)p.ldx * 4u), 0));
+        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsY, (int)vo, (int)((unsigned)st * 32u * (unsigned)p.ldy * 4u), 0));
+    };
+    auto split2 = [&](const f32x4& v, int e0, bf16x4& p1, bf16x4& p2, bf16x4& p3) {
+#pragma unroll
+        for (int e = e0; e < e0 + 2; ++e) {
+            bf16 s1_, s2_, s3_;
+            gg_split3_rne(v[e], s1_, s2_, s3_);
+            p1[e] = s1_; p2[e] = s2_; p3[e] = s3_;
+        }
+    };
+    auto store3 = [&](int it, bf16* ybase, const bf16x4& p1, const bf16x4& p2, const bf16x4& p3) {
+        bf16* const base = it < 7 ? Xim : ybase;
+        const int pl = it < 7 ? PX : PY;
+        if (it == 8 && !y2) return;
+        *reinterpret_cast<bf16x4*>(base + ldso[it]) = p1; *reinterpret_cast<bf16x4*>(base + pl + ldso[it]) = p2; *reinterpret_cast<bf16x4*>(base + 2 * pl + ldso[it]) = p3;
+    };
+    // fragment addresses (element offsets within a plane; + 16 rows = + 512): lane (lr, lg) supplies row 4 lg + (lr >> 2), columns 4 (lr & 3) .. of the 16-column block
+    int yoff[3], xoff[7];
+    {
+        const int row = 4 * lg + (lr >> 2);
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            const int cy = 48 * wn + 16 * t + 4 * (lr & 3);
+            yoff[t] = (cy >> 5) * SUB + s3_img_off(row, (cy & 31) >> 3) + (cy & 7);
+        }
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            const int cx = 16 * (wk + 4 * j) + 4 * (lr & 3);
+            xoff[j] = (cx >> 5) * SUB + s3_img_off(row, (cx & 31) >> 3) + (cx & 7);
+        }
+    }
+    f32x4 acc[3][7];                                                // [n-tile][k-tile]; lane: n = lr, k = 4 lg + r
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 7; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    // r[it] between its uses: items 0 - 3 hold half 0 of stage s + 1, items 4 - 6 half 1 of stage s, items 7 - 8 dY of stage s + 1 (at the top of stage s)
+    f32x4 r[9];
+    {
+        f32x4 t0[6];
+#pragma unroll
+        for (int it = 0; it < 4; ++it) t0[it] = load1(it, 0);
+        t0[4] = load1(7, 0); t0[5] = load1(8, 0);
+#pragma unroll
+        for (int it = 4; it < 7; ++it) r[it] = load1(it, 0);
+        r[7] = load1(7, 1); r[8] = load1(8, 1);
+#pragma unroll
+        for (int it = 0; it < 4; ++it) r[it] = load1(it, 1);
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            bf16x4 p1, p2, p3;
+            split2(t0[i], 0, p1, p2, p3); split2(t0[i], 2, p1, p2, p3);
+            store3(i < 4 ? i : i + 3, Yim, p1, p2, p3);
+        }
+    }
+    union Fr { s3_s4 h[2]; bf16x8 v; };
+    Fr yf[3][3], xf[2][3];                                          // dY^T fragments [plane][n-tile] (both phases of a stage); X^T fragments [ring][plane] of one k-tile
+    auto rd_y = [&](const bf16* ycur, int pl, int t) {
+#pragma unroll
+        for (int half = 0; half < 2; ++half)
+            yf[pl][t].h[half] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s3_s4*)(ycur + pl * PY + yoff[t] + half * 512));
+    };
+    auto rd_x = [&](int ring, int j) {
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+            for (int half = 0; half < 2; ++half)
+                xf[ring][pl].h[half] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s3_s4*)(Xim + pl * PX + xoff[j] + half * 512));
+    };
+    // One phase: the k-tiles J0 .. J0 + NJ - 1 of every wave (6 products x 3 n-tiles each; the next k-tile's fragments are read under the current one's MFMAs), and in
+    // 3 NIT slices between the product groups the split, the plane writes and the reload of the loader items IT0 .. IT0 + NIT - 1.  A scheduling barrier after every
+    // group keeps that order (gemm_nt_split3a_kernel's reason).
+    auto phase = [&](auto j0_, auto nj_, auto it0_, auto nit_, int s, bf16* ynxt) {
+        constexpr int J0 = decltype(j0_)::value, NJ = decltype(nj_)::value, IT0 = decltype(it0_)::value, NIT = decltype(nit_)::value;
+        constexpr int Q = 6 * NJ, S = 3 * NIT;
+        constexpr int PA[6] = {0, 1, 2, 0, 1, 0}, PB[6] = {2, 1, 0, 1, 0, 0};      // small terms first
+        bf16x4 p1, p2, p3;
+#pragma unroll
+        for (int jj = 0; jj < NJ; ++jj) {
+            if (jj + 1 < NJ) rd_x((jj + 1) & 1, J0 + jj + 1);
+#pragma unroll
+            for (int g = 0; g < 6; ++g) {
+#pragma unroll
+                for (int nt = 0; nt < 3; ++nt)
+                    acc[nt][J0 + jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[jj & 1][PA[g]].v, yf[PB[g]][nt].v, acc[nt][J0 + jj], 0, 0, 0);
+                const int qi = jj * 6 + g;
+                if ((qi * S) % Q < S) {
+                    const int ms = (qi * S) / Q, it = IT0 + ms / 3, part = ms % 3;
+                    if (part < 2) split2(r[it], 2 * part, p1, p2, p3);
+                    else {
+                        store3(it, ynxt, p1, p2, p3);
+                        r[it] = load1(it, it >= 4 && it < 7 ? s + 1 : s + 2);
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    };
+    for (int s = 0; s < nk; ++s) {
+        const bf16* const ycur = Yim + (s & 1) * 3 * PY;
+        bf16* const ynxt = Yim + ((s + 1) & 1) * 3 * PY;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // own plane writes of half 0 (s) are done ...
+        __builtin_amdgcn_s_barrier();                               // ... everybody's are (dY (s) since the barrier before); every wave is past its reads of half 1 (s - 1)
+        rd_x(0, 0);
+#pragma unroll
+        for (int t = 0; t < 3; ++t) rd_y(ycur, 2, t);
+#pragma unroll
+        for (int t = 0; t < 3; ++t) rd_y(ycur, 1, t);
+#pragma unroll
+        for (int t = 0; t < 3; ++t) rd_y(ycur, 0, t);
+        phase(std::integral_constant<int, 0>{}, std::integral_constant<int, 4>{}, std::integral_constant<int, 4>{}, std::integral_constant<int, 5>{}, s, ynxt);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // own plane writes of half 1 (s) and dY (s + 1) are done ...
+        __builtin_amdgcn_s_barrier();                               // ... everybody's are; every wave is past its reads of half 0 (s) and of dY (s)
+        rd_x(0, 4);
+        phase(std::integral_constant<int, 4>{}, std::integral_constant<int, 3>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 4>{}, s, ynxt);
+    }
+    wait_vm<0>();
+    float* out = p.part + (int64_t)slab * p.N * p.K;
+#pragma unroll
+    for (int nt = 0; nt < 3; ++nt) {
+        const int n = 48 * wn + 16 * nt + lr;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            const int k = 16 * (wk + 4 * j) + 4 * lg;
+            if (n < p.N && k < p.K) *reinterpret_cast<f32x4*>(out + (int64_t)n * p.K + k) = acc[nt][j];
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------- data gradient of a 3 x 3, stride 2, pad 1 convolution by input parity
+// da[b, iy, ix, c] = sum over the taps (ky, kx) with iy + 1 - ky and ix + 1 - kx even of dy[b, (iy + 1 - ky) / 2, (ix + 1 - kx) / 2, :] . W[:, ky, kx, c].  With iy = 2 m + py,
+// ix = 2 n + px an input pixel of parity (py, px) takes 1 + py taps in y (py = 0: ky 1 at oy = m; py = 1: ky 2 at oy = m, ky 0 at oy = m + 1) and 1 + px in x: four plain
+// GEMMs with T = 1, 2, 2, 4 taps, A row = the T rows of dy at the class's output pixels (a tap beyond the map: a zero row), K = Cout T, B[c][t Cout + co] (pe_dgrad_pack_kernel
+// repacks and splits it: conv2 trains, so once per step), N = Cin = 48.  No column gradient is written (gemm + col2im: 5.5 GB each way at 1024 images).  The result row IS da
+// at (b, iy, ix); it leaves through the BatchNorm-backward epilogue of col2im_nhwc_bnbwd_f32_kernel: dz = da * act'(BN(y)), per-block partial rows (sum dz, sum dz xhat).
+// Kernel: gemm_nt_split3b_kernel's loop (A as f32 split in the loader into single-buffered planes, B planes double-buffered by LDS-DMA, k-stage 32) on a 128-pixel x 48 tile,
+// 4 waves of 32 x 48.  A tile lies inside one image and one class; a workgroup walks a contiguous run of tiles ordered (image, tile, class), so the four classes' reads of the
+// same dy rows follow each other, and consecutive workgroups of an XCD work on neighbouring images: every dy row comes from HBM once and up to eight times from L2.
+struct PeDgradParams {
+    const float* dy; const bf16* Bp; const float* y; const float* stat; const float* gamma; const float* beta; int act;
+    float* dz; float* part;
+    int H, W, Cout, tiles_per_img, total_tiles, tiles_per_block;      // [H][W]: the convolution's INPUT map (even); tiles_per_img: per class
+};
+constexpr int PED_N = 48, PED_BM = 128;
+// class cls = 2 py + px: element offset of its planes [3][48][Cout T] in the packed buffer = 3 * 48 * Cout * (taps of the classes before it)
+__device__ __host__ __forceinline__ int ped_taps_before(int cls) { return cls == 0 ? 0 : cls == 1 ? 1 : cls == 2 ? 3 : 5; }
+__global__ __launch_bounds__(256) void pe_dgrad_pack_kernel(const float* __restrict__ Wt, int64_t ldw, int Cout, bf16* __restrict__ out) {
+    // Wt [(ky 3 + kx) 48 + c][co] -> for every class, tap and c the row segment [t Cout + co], as three planes
+    const int c4n = Cout / 4, total = PED_N * 9 * c4n;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const int co = (i % c4n) * 4, u = (i / c4n) % 9, c = i / (9 * c4n);
+        const int cls = u < 1 ? 0 : u < 3 ? 1 : u < 5 ? 2 : 3, t = u - ped_taps_before(cls);
+        const int py = cls >> 1, px = cls & 1, nx = 1 + px, ty = t / nx, tx = t % nx;
+        const int ky = py ? (ty ? 0 : 2) : 1, kx = px ? (tx ? 0 : 2) : 1;
+        const int Kc = Cout * (1 + py) * (1 + px);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(Wt + (int64_t)((ky * 3 + kx) * PED_N + c) * ldw + co);
+        bf16x4 p1, p2, p3;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            bf16 s1_, s2_, s3_;
+            gg_split3_rne(v[j], s1_, s2_, s3_);
+            p1[j] = s1_; p2[j] = s2_; p3[j] = s3_;
+        }
+        bf16* q = out + (int64_t)3 * PED_N * Cout * ped_taps_before(cls) + (int64_t)c * Kc + t * Cout + co;
+        *reinterpret_cast<bf16x4*>(q) = p1; *reinterpret_cast<bf16x4*>(q + PED_N * Kc) = p2; *reinterpret_cast<bf16x4*>(q + 2 * PED_N * Kc) = p3;
+    }
+}
+__global__ __launch_bounds__(256) void pe_dgrad_split3_kernel(PeDgradParams p) {
+    constexpr int BM = PED_BM, BN = PED_N, TM = 2, TN = 3, LDT = BN + 4;
+    constexpr int TA = BM * S3_SK, TB = BN * S3_SK;
+    constexpr int CPR = BN / 4, RPP = 256 / CPR, NR = (BM + RPP - 1) / RPP;      // epilogue: 12 f32x4 per row, 21 rows per pass, 7 passes
+    extern __shared__ __attribute__((aligned(16))) bf16 s3mem[];
+    bf16* const Abuf = s3mem;                                      // [3][TA]
+    bf16* const Bbuf = s3mem + 3 * TA;                             // [2][3][TB]
+    float* const Ct = reinterpret_cast<float*>(s3mem);             // the tile image [BM][LDT] (after the k-loop), then the partial sums [RPP][2][BN]
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lr = lane & 15, lg = lane >> 4;
+    const int H0 = p.H >> 1, W0 = p.W >> 1, npc = H0 * W0, spt = p.Cout >> 5;      // output map = class map; pixels per class and image; stages per tap
+    const int dchunk = (lane & 3) ^ s3_swz(lane >> 4);
+    const int kq = threadIdx.x & 7, arow = threadIdx.x >> 3;
+    int ldsA[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int row = arow + 32 * j;
+        ldsA[j] = row * S3_SK + (((kq >> 1) ^ s3_swz((row >> 2) & 3)) << 3) + ((kq & 1) << 2);
+    }
+    const int fslot = (lg ^ s3_swz((lr >> 2) & 3)) * 8;
+    const int a_off = (wave * 32 + lr) * S3_SK + fslot, b_off = lr * S3_SK + fslot;
+    // epilogue geometry: thread -> f32x4 number chunk of rows r0 + RPP i; its channel's BatchNorm constants; its share of the two sums over all of the block's tiles
+    const int chunk = threadIdx.x % CPR, r0 = threadIdx.x / CPR, c0 = chunk * 4;
+    const bool elive = r0 < RPP;
+    const f32x4 mu = *reinterpret_cast<const f32x4*>(p.stat + c0), rstd = *reinterpret_cast<const f32x4*>(p.stat + BN + c0);
+    const f32x4 ga = *reinterpret_cast<const f32x4*>(p.gamma + c0), be = *reinterpret_cast<const f32x4*>(p.beta + c0);
+    f32x4 ssum = {0.f, 0.f, 0.f, 0.f}, qsum = ssum;
+    auto split2 = [&](const f32x4& v, int e0, bf16x4& p1, bf16x4& p2, bf16x4& p3) {
+#pragma unroll
+        for (int e = e0; e < e0 + 2; ++e) {
+            bf16 s1_, s2_, s3_;
+            gg_split3_rne(v[e], s1_, s2_, s3_);
+            p1[e] = s1_; p2[e] = s2_; p3[e] = s3_;
+        }
+    };
+    const int lid = gg_xcd_remap(blockIdx.x, gridDim.x);
+    const int t_begin = lid * p.tiles_per_block, t_end = min(t_begin + p.tiles_per_block, p.total_tiles);
+    for (int tile = t_begin; tile < t_end; ++tile) {
+        const int img = tile / (4 * p.tiles_per_img), rem = tile - img * 4 * p.tiles_per_img;
+        const int tin = rem >> 2, cls = rem & 3, py = cls >> 1, px = cls & 1, nx = 1 + px;
+        const int Kc = p.Cout * (1 + py) * nx, nk = spt * (1 + py) * nx;
+        const int q0 = tin * BM;
+        // A: the image's dy [H0 W0][Cout]; thread -> f32x4 number kq of the stage's 32 columns of rows arow + 32 j (class pixel q0 + row = (m, n): dy row (m + dy_t, n + dx_t))
+        const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)(p.dy + (int64_t)img * npc * p.Cout), 0, (int)((unsigned)npc * (unsigned)p.Cout * 4u), 0x00020000);
+        unsigned voffA[4];
+        bool yin[4], xin[4];                                        // the row below / the column to the right exists
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int q = q0 + arow + 32 * j, m = q / W0, n = q - m * W0;
+            voffA[j] = q < npc ? (unsigned)q * (unsigned)p.Cout * 4u + kq * 16u : 0xFFFFFFF0u;
+            yin[j] = m + 1 < H0; xin[j] = n + 1 < W0;
+        }
+        __amdgpu_buffer_rsrc_t rsB[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+            rsB[i] = __builtin_amdgcn_make_buffer_rsrc((void*)(p.Bp + (int64_t)3 * BN * p.Cout * ped_taps_before(cls) + (int64_t)i * BN * Kc), 0, (int)((unsigned)BN * (unsigned)Kc * 2u), 0x00020000);
+        const unsigned voffB = (unsigned)(wave * 16 + (lane >> 2)) * (unsigned)Kc * 2u + dchunk * 16u;
+        auto issue_b = [&](int st) {
+            if (wave < BN / 16 && st < nk) {                        // (wave-uniform: three slices of 16 rows per plane)
+                bf16* const base = Bbuf + (st & 1) * 3 * TB;
+#pragma unroll
+                for (int i = 0; i < 3; ++i)
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB[i], (__attribute__((address_space(3))) void*)(base + i * TB + wave * 512), 16, (int)voffB, st * S3_SK * 2, 0, 0);
+            }
+        };
+        auto load_a1 = [&](int st, int j) -> f32x4 {
+            // stage st: tap t = st / spt = (ty, tx), columns 32 (st % spt) ..; a tap beyond the map (or a stage beyond K) loads nothing: zeros
+            const int t = st / spt, kk = (st - t * spt) * S3_SK, ty = t / nx, tx = t - ty * nx;
+            const bool dyv = py && ty, dxv = px && tx;
+            const int soff = (((int)dyv * W0 + (int)dxv) * p.Cout + kk) * 4;
+            const bool ok = st < nk && (!dyv || yin[j]) && (!dxv || xin[j]);
+            return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, (int)(ok ? voffA[j] : 0xFFFFFFF0u), soff, 0));
+        };
+        auto load_a = [&](int st, f32x4 (&r)[4]) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) r[j] = load_a1(st, j);
+        };
+        // Two accumulators per element: the five small products of a stage (at most 2^-8 of the leading one) and the leading product a1 b1.  One accumulator over all
+        // K = Cout T columns would round every small product against the running sum of up to 12 stages; today's path keeps a tap's 3 stages apart and adds the taps
+        // afterwards.  Kept apart, the small terms round against their own sum only and the leading chain has one addition per stage: the error stays below that path's.
+        f32x4 acc[TN][TM], accs[TN][TM];
+#pragma unroll
+        for (int i = 0; i < TN; ++i)
+#pragma unroll
+            for (int j = 0; j < TM; ++j) acc[i][j] = accs[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        f32x4 ra[2][4];
+        issue_b(0);
+        load_a(0, ra[0]);
+        load_a(1, ra[1]);
+        wait_vm<4>();                                               // B(0) and A(0)
+        {
+            bf16x4 p1, p2, p3;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                split2(ra[0][j], 0, p1, p2, p3); split2(ra[0][j], 2, p1, p2, p3);
+                *reinterpret_cast<bf16x4*>(Abuf + ldsA[j]) = p1; *reinterpret_cast<bf16x4*>(Abuf + TA + ldsA[j]) = p2; *reinterpret_cast<bf16x4*>(Abuf + 2 * TA + ldsA[j]) = p3;
+            }
+        }
+        load_a(2, ra[0]);
+        auto stage = [&](int s, f32x4 (&rnext)[4]) {
+            const bf16* const curB = Bbuf + (s & 1) * 3 * TB;
+            wait_vm<4>();                                           // B(s) and A(s + 1) have landed; A(s + 2) may be in flight
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            issue_b(s + 1);
+            bf16x8 xf[3][TM], wf[3][TN];
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+                for (int mt = 0; mt < TM; ++mt) xf[pl][mt] = *reinterpret_cast<const bf16x8*>(Abuf + pl * TA + a_off + mt * 16 * S3_SK);
+            auto rd_b1 = [&](int pl, int nt) { wf[pl][nt] = *reinterpret_cast<const bf16x8*>(curB + pl * TB + b_off + nt * 16 * S3_SK); };
+#pragma unroll
+            for (int t = 0; t < TN; ++t) rd_b1(2, t);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the six A fragments (and b3) are in registers ...
+            __builtin_amdgcn_s_barrier();                           // ... everybody's are: the A buffer is free for the planes of A(s + 1)
+            bf16x4 p1, p2, p3;
+            constexpr int PA[6] = {0, 1, 2, 0, 1, 0}, PB[6] = {2, 1, 0, 1, 0, 0};      // small terms first
+#pragma unroll
+            for (int g = 0; g < 6; ++g) {
+#pragma unroll
+                for (int nt = 0; nt < TN; ++nt) {
+#pragma unroll
+                    for (int mt = 0; mt < TM; ++mt) {
+                        if (g < 5) accs[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[PB[g]][nt], xf[PA[g]][mt], accs[nt][mt], 0, 0, 0);
+                        else acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[PB[g]][nt], xf[PA[g]][mt], acc[nt][mt], 0, 0, 0);
+                    }
+                    constexpr int Q = 6 * TN;
+                    const int qi = g * TN + nt;
+                    if (g < 2 && 2 * nt < TN) { rd_b1(1 - g, 2 * nt); if (2 * nt + 1 < TN) rd_b1(1 - g, 2 * nt + 1); }
+                    if ((qi * 12) % Q < 12) {
+                        const int ms = (qi * 12) / Q, jj = ms / 3, part = ms % 3;
+                        if (part < 2) split2(rnext[jj], 2 * part, p1, p2, p3);
+                        else {
+                            *reinterpret_cast<bf16x4*>(Abuf + ldsA[jj]) = p1;
+                            *reinterpret_cast<bf16x4*>(Abuf + TA + ldsA[jj]) = p2;
+                            *reinterpret_cast<bf16x4*>(Abuf + 2 * TA + ldsA[jj]) = p3;
+                            rnext[jj] = load_a1(s + 3, jj);         // (four loads per stage, as the counted wait at the top of the next stage assumes)
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        };
+        for (int s = 0; s < nk; s += 2) {
+            stage(s, ra[1]);
+            if (s + 1 < nk) stage(s + 1, ra[0]);
+        }
+        wait_vm<0>();
+        // epilogue: this thread's y rows are requested first, the accumulators cross LDS to whole rows, dz = da * act'(BN(y)) and the two sums
+        f32x4 yv[NR];
+        int64_t pix[NR];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            const int rr = r0 + i * RPP, q = q0 + rr;
+            const bool on = elive && rr < BM && q < npc;
+            const int m = on ? q / W0 : 0, n = on ? q - m * W0 : 0;
+            pix[i] = on ? ((int64_t)img * p.H + 2 * m + py) * p.W + 2 * n + px : -1;
+            yv[i] = on ? *reinterpret_cast<const f32x4*>(p.y + pix[i] * BN + c0) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+#pragma unroll
+        for (int nt = 0; nt < TN; ++nt)
+#pragma unroll
+            for (int mt = 0; mt < TM; ++mt)
+                *reinterpret_cast<f32x4*>(Ct + (wave * 32 + mt * 16 + lr) * LDT + nt * 16 + lg * 4) = acc[nt][mt] + accs[nt][mt];
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            if (pix[i] < 0) continue;
+            const f32x4 a = *reinterpret_cast<const f32x4*>(Ct + (r0 + i * RPP) * LDT + c0);
+            const f32x4 xh = (yv[i] - mu) * rstd;
+            f32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = a[j] * gg_act_grad_f32(fmaf(ga[j], xh[j], be[j]), p.act);
+            ssum += o;
+            qsum += o * xh;
+            __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(p.dz + pix[i] * BN + c0));
+        }
+        __syncthreads();                                            // the tile image is read: the planes of the next tile may be written
+    }
+    // the block's partial row: thread sums -> LDS [RPP][2][BN] -> one thread per (which, column) adds the RPP rows in order
+    if (elive) {
+        *reinterpret_cast<f32x4*>(Ct + (r0 * 2 + 0) * BN + c0) = ssum;
+        *reinterpret_cast<f32x4*>(Ct + (r0 * 2 + 1) * BN + c0) = qsum;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * BN) {
+        float t = 0.f;
+        for (int k = 0; k < RPP; ++k) t += Ct[k * 2 * BN + threadIdx.x];
+        p.part[(int64_t)blockIdx.x * 2 * BN + threadIdx.x] = t;
+    }
+}
+
 // x (f32, [rows][ldx]) -> planes [3][rows][cols] bf16: x1 = bf16(x), x2 = bf16(x - x1), x3 = bf16(x - x1 - x2)
 __global__ __launch_bounds__(256) void split3_kernel(const float* __restrict__ x, int64_t rows, int cols, int64_t ldx, bf16* __restrict__ out) {
     const int64_t n4 = rows * (cols / 4);
@@ -1247,6 +1653,72 @@ extern "C" int gg_gemm_tn_split3(const float* dY, int64_t ldy, const float* X, i
     GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(gemm_tn_split3_kernel)));
     GG_PROF(GG_CAT_GEMM | GG_CAT_SPLIT_FLAG, 2.0 * M * (double)N * K, 4.0 * ((double)M * N + (double)M * K) + 8.0 * splits * (double)N * K, stream);
     hipLaunchKernelGGL(gemm_tn_split3_kernel, dim3((unsigned)(p.tilesN * p.tilesK * splits)), dim3(512), (size_t)2 * 3 * (256 / 32 + 128 / 32) * 1024 * sizeof(bf16), (hipStream_t)stream, p);
+    GG_LAUNCH_CHECK();
+    return 0;
+}
+
+// The resident form (gemm_tn_split3_resident_kernel; include/gg_wgrad_resident.h): same operands and slab protocol, one workgroup per slab
+extern "C" int gg_gemm_tn_split3_resident_fits(int N, int K) { return N > 0 && K > 0 && N <= S3R_N && K <= S3R_K; }
+extern "C" int gg_gemm_tn_split3_resident_splits(int M, int N, int K) {
+    GG_CHECK(M > 0 && N > 0 && K > 0, "gg_gemm_tn_split3_resident_splits: bad shape");
+    GG_CHECK(gg_gemm_tn_split3_resident_fits(N, K), "gg_gemm_tn_split3_resident: the %d x %d output does not fit one workgroup (at most %d x %d)", N, K, S3R_N, S3R_K);
+    const int64_t cap = std::max<int64_t>(1, ((int64_t)128 << 20) / ((int64_t)N * K * 4));        // 128 MiB of slabs at most (scratch.splitk)
+    // one slab per CU when every slab keeps at least 8 stages; never fewer than a quarter more slabs than gg_gemm_tn_f32 takes (gg_gemm_tn_split3_splits' rule: the
+    // error is that of a slab's f32 accumulation chain)
+    int64_t s = std::max<int64_t>(1, std::min<int64_t>(256, M / 256));
+    s = std::max<int64_t>(s, (5 * (int64_t)gg_gemm_tn_f32_splits(M, N, K) + 3) / 4);
+    s = std::min<int64_t>(std::min<int64_t>(s, cap), gg_cdiv(M, 32));
+    const int64_t rows = gg_cdiv(gg_cdiv(M, s), 32) * 32;          // slabs are whole 32-row stages
+    return (int)gg_cdiv(M, rows);
+}
+extern "C" int gg_gemm_tn_split3_resident(const float* dY, int64_t ldy, const float* X, int64_t ldx, int M, int N, int K, float* partials, int splits, void* stream) {
+    GG_CHECK(dY && X && partials && M > 0 && N > 0 && K > 0 && splits > 0, "gg_gemm_tn_split3_resident: bad args");
+    GG_CHECK(gg_gemm_tn_split3_resident_fits(N, K), "gg_gemm_tn_split3_resident: the %d x %d output does not fit one workgroup (at most %d x %d)", N, K, S3R_N, S3R_K);
+    GG_CHECK((N & 3) == 0 && (K & 3) == 0 && (ldy & 3) == 0 && (ldx & 3) == 0 && ldy >= N && ldx >= K, "gg_gemm_tn_split3_resident: N, K, ldy, ldx must be multiples of 4, ld >= columns");
+    GG_CHECK(((uintptr_t)dY & 15) == 0 && ((uintptr_t)X & 15) == 0 && ((uintptr_t)partials & 15) == 0, "gg_gemm_tn_split3_resident: operands and partials must be 16-byte aligned");
+    Split3TnResParams p;
+    p.dY = dY; p.ldy = ldy; p.X = X; p.ldx = ldx; p.M = M; p.N = N; p.K = K; p.part = partials;
+    p.rows_per_split = (int)(gg_cdiv(gg_cdiv(M, splits), 32) * 32);
+    GG_CHECK((int64_t)p.rows_per_split * (splits - 1) < M, "gg_gemm_tn_split3_resident: more splits than 32-row stages");
+    GG_CHECK(((int64_t)p.rows_per_split + 96) * std::max(ldy, ldx) * 4 < ((int64_t)1 << 31), "gg_gemm_tn_split3_resident: a slab exceeds the 2 GiB descriptor range");
+    GG_TRY(gg_allow_lds_160k(reinterpret_cast<const void*>(gemm_tn_split3_resident_kernel)));      // (raised once per (device, kernel))
+    GG_PROF(GG_CAT_GEMM | GG_CAT_SPLIT_FLAG, 2.0 * M * (double)N * K, 4.0 * ((double)M * N + (double)M * K) + 8.0 * splits * (double)N * K, stream);
+    hipLaunchKernelGGL(gemm_tn_split3_resident_kernel, dim3((unsigned)splits), dim3(512), (size_t)3 * (S3R_K / 32 + 2 * (S3R_N / 32)) * 1024 * sizeof(bf16), (hipStream_t)stream, p);
+    GG_LAUNCH_CHECK();
+    return 0;
+}
+
+// The data gradient of a 3 x 3, stride 2, pad 1 convolution by input parity with the BatchNorm-backward epilogue (pe_dgrad_split3_kernel; include/gg_conv_dgrad_parity.h)
+extern "C" int gg_conv3x3s2_dgrad_fits(int H, int W, int Cin, int Cout) {
+    return H > 0 && W > 0 && (H & 1) == 0 && (W & 1) == 0 && Cin == PED_N && Cout >= 32 && (Cout & 31) == 0 && (int64_t)(H / 2) * (W / 2) * Cout * 4 < ((int64_t)1 << 31);
+}
+extern "C" int64_t gg_conv3x3s2_dgrad_planes_bytes(int Cin, int Cout) { return (int64_t)3 * 9 * Cin * Cout * (int64_t)sizeof(bf16); }
+extern "C" int gg_conv3x3s2_dgrad_bnbwd_split3(const float* dy, const float* Wt, int64_t ldw, const float* y, const float* stat, const float* gamma, const float* beta, int act,
+                                               float* dz, float* part, int nparts, void* planes, int B, int H, int W, int Cin, int Cout, void* stream) {
+    GG_CHECK(dy && Wt && y && stat && gamma && beta && dz && part && planes && nparts > 0 && nparts <= 65535 && B > 0, "gg_conv3x3s2_dgrad_bnbwd_split3: bad args");
+    GG_CHECK(gg_conv3x3s2_dgrad_fits(H, W, Cin, Cout), "gg_conv3x3s2_dgrad_bnbwd_split3: needs an even input map, Cin = %d and Cout a multiple of 32 (got %d x %d, Cin %d, Cout %d)",
+             PED_N, H, W, Cin, Cout);
+    GG_CHECK(ldw >= Cout && (ldw & 3) == 0, "gg_conv3x3s2_dgrad_bnbwd_split3: ldw must be a multiple of 4, >= Cout");
+    GG_CHECK(((uintptr_t)dy & 15) == 0 && ((uintptr_t)Wt & 15) == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)dz & 15) == 0 && ((uintptr_t)stat & 15) == 0 &&
+             ((uintptr_t)gamma & 15) == 0 && ((uintptr_t)beta & 15) == 0 && ((uintptr_t)planes & 15) == 0, "gg_conv3x3s2_dgrad_bnbwd_split3: operands must be 16-byte aligned");
+    PeDgradParams p;
+    p.dy = dy; p.Bp = (const bf16*)planes; p.y = y; p.stat = stat; p.gamma = gamma; p.beta = beta; p.act = act; p.dz = dz; p.part = part;
+    p.H = H; p.W = W; p.Cout = Cout;
+    const int64_t npc = (int64_t)(H / 2) * (W / 2);
+    p.tiles_per_img = (int)gg_cdiv(npc, PED_BM);
+    const int64_t total = (int64_t)B * 4 * p.tiles_per_img;
+    GG_CHECK(total < ((int64_t)1 << 31), "gg_conv3x3s2_dgrad_bnbwd_split3: too many tiles");
+    p.total_tiles = (int)total;
+    p.tiles_per_block = (int)gg_cdiv(total, nparts);
+    const double M0 = (double)B * npc;
+    {
+        GG_PROF(GG_CAT_MOVE, 0, 4.0 * 9 * Cin * Cout + 6.0 * 9 * Cin * Cout, stream);
+        hipLaunchKernelGGL(pe_dgrad_pack_kernel, dim3((unsigned)gg_cdiv((int64_t)PED_N * 9 * (Cout / 4), 256)), dim3(256), 0, (hipStream_t)stream, Wt, ldw, Cout, (bf16*)planes);
+        GG_LAUNCH_CHECK();
+    }
+    // algorithmic work: the product it replaces (dcol = dy . W: 2 M0 (9 Cin) Cout); bytes: dy once, the planes, y and dz of the 4 M0 input pixels
+    GG_PROF(GG_CAT_GEMM | GG_CAT_SPLIT_FLAG, 2.0 * M0 * 9.0 * Cin * Cout, 4.0 * M0 * Cout + 6.0 * 9 * Cin * Cout + 2.0 * 4.0 * 4.0 * M0 * Cin + 8.0 * nparts * Cin, stream);
+    hipLaunchKernelGGL(pe_dgrad_split3_kernel, dim3((unsigned)nparts), dim3(256), (size_t)(3 * PED_BM + 6 * PED_N) * S3_SK * sizeof(bf16), (hipStream_t)stream, p);
     GG_LAUNCH_CHECK();
     return 0;
 }

@@ -19,6 +19,8 @@
 #include "../../include/gg_pad.h"
 #include "../../include/gg_attn16w.h"
 #include "../../include/gg_attn16wb.h"
+#include "../../include/gg_wgrad_resident.h"
+#include "../../include/gg_conv_dgrad_parity.h"
 #include "attention_route.h"
 
 bool gg_split3_af32_takes_rowmap(int N, int K);      // gemm_split3.hip: the form gg_gemm_nt_split3_af32 would run this shape on accepts row compaction
@@ -1045,8 +1047,17 @@ static int dense_wgrad(const Exec& e, const DenseW& w, const act_t* X, int64_t l
     static const char* tn_min_env = gg_dev_env("GG_SPLIT_TN_MIN_M");      // (dev: the same for the weight gradients' row threshold)
     static const int64_t tn_min_m = tn_min_env ? atoll(tn_min_env) : 1024;
     const bool sp = e.m->split && w.wn3 >= 0 && !conv_reorder && M >= tn_min_m;
-    const int split = sp ? gg_gemm_tn_split3_splits((int)M, w.N, K) : e.f32 ? gg_gemm_tn_f32_splits((int)M, w.N, K) : gg_gemm_tn_splits((int)M, w.N, K);
-    if (sp) GG_TRY(gg_gemm_tn_split3((const float*)dY, ldy, (const float*)X, ldx, (int)M, w.N, K, rowscale, rps, e.F(e.L->splitk), split, e.st));
+    // ... and that of a dense convolution whose whole output fits one workgroup (patch_embed.conv2: 96 x 432) on the resident form, from the row count at which
+    // its one-workgroup-per-slab grid fills the chip (256 slabs of 8 stages); below it, and for every larger output, gg_gemm_tn_f32 as before
+    const char* res_min_env = gg_dev_env("GG_SPLIT_TN_RESIDENT_MIN_M");      // (dev: the resident form's row threshold; read per call, so that one process can
+    const int64_t res_min_m = res_min_env ? atoll(res_min_env) : 65536;      // compare both routes -- tools/patch_embed_bwd_check.py)
+    const bool res = e.m->split && e.f32 && conv_reorder && M >= res_min_m && gg_gemm_tn_split3_resident_fits(w.N, K) != 0;
+    const int split = res ? gg_gemm_tn_split3_resident_splits((int)M, w.N, K) :
+                      sp ? gg_gemm_tn_split3_splits((int)M, w.N, K) : e.f32 ? gg_gemm_tn_f32_splits((int)M, w.N, K) : gg_gemm_tn_splits((int)M, w.N, K);
+    if (res) {
+        GG_CHECK(split > 0, "dense_wgrad: no slab count for the resident weight gradient");
+        GG_TRY(gg_gemm_tn_split3_resident((const float*)dY, ldy, (const float*)X, ldx, (int)M, w.N, K, e.F(e.L->splitk), split, e.st));
+    } else if (sp) GG_TRY(gg_gemm_tn_split3((const float*)dY, ldy, (const float*)X, ldx, (int)M, w.N, K, rowscale, rps, e.F(e.L->splitk), split, e.st));
     else if (e.f32) GG_TRY(gg_gemm_tn_f32(dY, ldy, X, ldx, (int)M, w.N, K, rowscale, rps, e.F(e.L->splitk), split, e.st));
     else GG_TRY(gg_gemm_tn(dY, ldy, X, ldx, (int)M, w.N, K, rowscale, rps, e.F(e.L->splitk), split, e.st));
     float* gw = e.Gd(w.t_w);
@@ -1072,11 +1083,15 @@ static int col2im_bnbwd(const Exec& e, const act_t* dcol, const BNP& bn, const A
 // weight gradient of a ConvNorm whose dy feeds nothing else (the first conv of the network): BatchNorm backward stops after
 // reduce + finalize, and the TN GEMM forms dy = c0*dz + c1*y + c2 from (dz, y) while loading -- no apply pass, no dy tensor
 // The output gradient does not exist yet either: the reduce rides on the col2im that would have produced it from dcol ([B, H, W] map, stride 2).
+// `next` (fp32_split): no dcol -- the stride-2 convolution `next` behind this ConvNorm hands over its output gradient dy_next and the data gradient is formed by input
+// parity in the same launch (gg_conv3x3s2_dgrad_bnbwd_split3; `dcol` is then its plane scratch)
 static int convnorm_wgrad_from_dz(const Exec& e, const ConvBNDense& c, const Act& a, int64_t M, int act, act_t* dz, const act_t* X, int64_t ldx,
-                                  const act_t* dcol, int B, int H, int W) {
+                                  const act_t* dcol, int B, int H, int W, const ConvBNDense* next = nullptr, const act_t* dy_next = nullptr) {
     const BNP& bn = c.bn; const DenseW& w = c.w;
     const int nb = std::min(gg_bn_bwd_rows(M, bn.C), 65535), K = w.Kp;
-    GG_TRY(col2im_bnbwd(e, dcol, bn, a, act, dz, nb, B, H, W));
+    if (next) GG_TRY(gg_conv3x3s2_dgrad_bnbwd_split3((const float*)dy_next, (const float*)e.Wt(next->w), next->w.Np, (const float*)e.A(a.y), e.F(a.stat), e.P(bn.t_g), e.P(bn.t_b),
+                                                     act, (float*)dz, e.F(e.L->bnscratch), nb, (void*)dcol, B, H, W, bn.C, next->w.N, e.st));
+    else GG_TRY(col2im_bnbwd(e, dcol, bn, a, act, dz, nb, B, H, W));
     GG_TRY(bn_bwd_fin(e, bn, a, M, e.F(e.L->bnscratch), nb));
     if (!e.tr(w.t_w)) return 0;
     const int split = e.f32 ? gg_gemm_tn_f32_splits((int)M, w.N, K) : gg_gemm_tn_splits((int)M, w.N, K);
@@ -1395,8 +1410,16 @@ static int patch_embed_bwd(const Exec& e, const GradBufs& g) {
         if (e.tr(m.pe2.w.t_w)) GG_TRY(dense_wgrad(e, m.pe2.w, e.A(L.col2), m.pe2.w.Kp, t_a, C0, M0, nullptr, 0, true));
     }
     if (!need1) return 0;
+    const bool fuse1 = m.sch.fuse_bnbwd && m.pe1.w.N == m.pe1.bn.C && (m.pe1.bn.C & (e.f32 ? 3 : 7)) == 0;
+    // fp32_split: conv2's data gradient by input parity with BN1's backward reduce as epilogue -- no dcol2 (5.5 GB at 1024 images, written once and read once).  Taken
+    // exactly where the dcol2 product below would run as a split product (so the split launch count of a step does not depend on the route) and the shape qualifies:
+    // an even map, 48 input channels, Cout % 32 == 0.  Everything else keeps the two launches.  (The backward alone decides: the forward saves nothing for either route.)
+    const bool parity = fuse1 && m.split && e.f32 && !gg_dev_env("GG_NO_PE2_DGRAD_PARITY") && m.pe2.w.Np == C0 &&
+                        ((M0 + 127) / 128) * ((m.pe2.w.Kp + 127) / 128) >= split_min_tiles() && planes_of(e, e.Wt(m.pe2.w), m.pe2.w.Np, m.pe2.w.Kp) != nullptr &&
+                        gg_conv3x3s2_dgrad_fits(H1, H1, C0 / 2, C0) != 0 && gg_conv3x3s2_dgrad_planes_bytes(C0 / 2, C0) <= M0 * m.pe2.w.Kp * (int64_t)sizeof(float);
+    if (parity) return convnorm_wgrad_from_dz(e, m.pe1, L.pe1, M1, GG_ACT_GELU, t_d, e.A(L.col1), 32, t_b, B, H1, H1, &m.pe2, t_a);      // (t_b: the weight's plane scratch)
     GG_TRY(gemm(e, t_a, C0, e.Wt(m.pe2.w), m.pe2.w.Np, t_b, m.pe2.w.Kp, M0, m.pe2.w.Kp, C0));          // dcol2 -> t_b
-    if (m.sch.fuse_bnbwd && m.pe1.w.N == m.pe1.bn.C && (m.pe1.bn.C & (e.f32 ? 3 : 7)) == 0) {
+    if (fuse1) {
         // col2im + BN1-backward reduce in one pass (dz1 -> t_d; da1 and dy1 are never formed), weight gradient from (dz1, y1, coef)
         return convnorm_wgrad_from_dz(e, m.pe1, L.pe1, M1, GG_ACT_GELU, t_d, e.A(L.col1), 32, t_b, B, H1, H1);
     }

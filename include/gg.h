@@ -315,7 +315,10 @@ typedef struct {
 } GgSplit3Route;
 int gg_gemm_nt_split3_route(const GgSplit3Args* args, int af32, int pro, int with_colstats, GgSplit3Route* out);
 /* weight gradient dW[N][K] = sum_m s_m dY[m][n] X[m][k] as split products (both f32 operands split in the kernel's loader): the arguments and the slab protocol
- * of gg_gemm_tn_f32 (partials [splits][N][K], reduced by gg_splitk_reduce); splits from gg_gemm_tn_split3_splits. */
+ * of gg_gemm_tn_f32 (partials [splits][N][K], reduced by gg_splitk_reduce); splits from gg_gemm_tn_split3_splits.
+ * Two more fp32_split entry points live in headers of their own (the backward of patch_embed.conv2): include/gg_wgrad_resident.h -- this product for an
+ * output of at most 96 x 448 held by one workgroup -- and include/gg_conv_dgrad_parity.h -- the data gradient of a 3 x 3 stride-2 convolution by input parity with the
+ * BatchNorm-backward epilogue, in place of a dcol product and its col2im gather. */
 int gg_gemm_tn_split3_splits(int M, int N, int K);
 int gg_gemm_tn_split3(const float* dY, int64_t ldy, const float* X, int64_t ldx, int M, int N, int K, const float* rowscale, int rows_per_scale, float* partials,
                       int splits, void* stream);
