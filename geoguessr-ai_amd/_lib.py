@@ -78,7 +78,7 @@ class TinyVitCfg(C.Structure):
 class ClipCfg(C.Structure):
     _fields_ = [("hidden_size", C.c_int), ("intermediate_size", C.c_int), ("num_layers", C.c_int), ("num_heads", C.c_int),
                 ("image_size", C.c_int), ("patch_size", C.c_int), ("ln_eps", C.c_float), ("act_dtype", C.c_int),
-                ("recompute", C.c_int)]
+                ("recompute", C.c_int), ("input_h", C.c_int), ("input_w", C.c_int)]      # input_h / input_w: the size of the call, 0 = image_size (include/gg_clip_interp.h)
 
 
 class ClipTextCfg(C.Structure):          # GgClipTextCfg (include/gg_clip_text.h)
@@ -490,6 +490,14 @@ DGRAD_PARITY_SIGNATURES = {
 }
 DGRAD_PARITY_SYMBOLS = list(DGRAD_PARITY_SIGNATURES)
 
+# every exported symbol of include/gg_clip_interp.h (the CLIP position table resampled to the grid of a foreign input size, and the adjoint), bound from the same libgg.so
+CLIP_INTERP_MAX_SIDE = 64                # GG_CLIP_INTERP_MAX_SIDE
+CLIP_INTERP_SIGNATURES = {
+    "gg_clip_pos_interp_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "gg_clip_pos_interp_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+}
+CLIP_INTERP_SYMBOLS = list(CLIP_INTERP_SIGNATURES)
+
 
 # every exported symbol of include/gg_attn_route.h (the route report of the attention entry points: host arithmetic, no device), its struct and its two enums
 class AttnRoutePass(C.Structure):
@@ -527,7 +535,7 @@ def lib() -> C.CDLL:
             raise GgError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JSCAN_SIGNATURES.items()) + list(JPROG_SIGNATURES.items()) + list(PANO_SIGNATURES.items()) + list(ATTN16_SIGNATURES.items()) + list(ATTN16W_SIGNATURES.items()) + list(ATTN16B_SIGNATURES.items()) + list(ATTN16WB_SIGNATURES.items()) + list(ATTN_ROUTE_SIGNATURES.items()) + list(WGRAD_RESIDENT_SIGNATURES.items()) + list(DGRAD_PARITY_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JSCAN_SIGNATURES.items()) + list(JPROG_SIGNATURES.items()) + list(PANO_SIGNATURES.items()) + list(ATTN16_SIGNATURES.items()) + list(ATTN16W_SIGNATURES.items()) + list(ATTN16B_SIGNATURES.items()) + list(ATTN16WB_SIGNATURES.items()) + list(ATTN_ROUTE_SIGNATURES.items()) + list(WGRAD_RESIDENT_SIGNATURES.items()) + list(DGRAD_PARITY_SIGNATURES.items()) + list(CLIP_INTERP_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the library lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -592,6 +600,7 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(root), "include", "gg_attn_route.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_wgrad_resident.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_conv_dgrad_parity.h"))
+    files.append(os.path.join(os.path.dirname(root), "include", "gg_clip_interp.h"))
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

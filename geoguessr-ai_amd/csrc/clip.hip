@@ -36,6 +36,7 @@
 #include "../../include/gg_fp8.h"
 #include "../../include/gg_attn16.h"
 #include "../../include/gg_attn16b.h"
+#include "../../include/gg_clip_interp.h"
 #include "attention_route.h"
 #include <atomic>
 
@@ -55,6 +56,9 @@ struct CModel {
     int64_t wpatch, wpatch3 = -1;
     std::vector<LayerP> layers;
     int T, G, Kpatch, Kraw;
+    // the size of the call (GgClipCfg.input_h / input_w; include/gg_clip_interp.h): G x G is the grid of the position TABLE (image_size), Gh x Gw the grid of the
+    // input, T = Gh * Gw + 1.  interp: the two differ -- the table is resampled into the weight cache at wpos (T x D f32, the LAST region of the cache)
+    int H = 0, W = 0, Gh = 0, Gw = 0; bool interp = false; int64_t wpos = -1;
     // the text tower (gg_clip_text_*) is the same layer stack over T = the call's token count with causal attention: embeddings and the final norm differ
     bool causal = false; int tok_emb = -1, fin_g = -1, fin_b = -1, vocab = 0;
     bool f32, f16, split, fp8 = false; int es;      // fp8: the fp16 mode (f16 is set too) with the encoder Linears as e4m3 products; f32: f32 storage (fp32 and fp32_split modes); split: fp32_split; activation / cached-weight element size: 4 or 2 (bf16 / fp16 modes)
@@ -112,15 +116,24 @@ static int build(const GgClipCfg* c, CModel& m) {
     GG_CHECK(P > 0 && c->image_size % P == 0 && I % 8 == 0 && c->num_layers > 0, "clip: bad patch/image/intermediate size or layer count");
     // patch-embedding contraction 3*P*P is padded to a multiple of 8 (ViT-L/14: 588 -> 592 zero columns); sequences beyond 256 tokens
     // (ViT-L/14-336: 577, the reference's CLIP_MODEL, config.py:6) run on the online-softmax attention kernels
-    m.G = c->image_size / P; m.T = m.G * m.G + 1; m.Kraw = 3 * P * P; m.Kpatch = (int)gg_align(m.Kraw, 8);
+    GG_CHECK(c->input_h >= 0 && c->input_w >= 0, "clip: input_h / input_w must be 0 (= image_size) or a size in pixels, got %d x %d", c->input_h, c->input_w);
+    m.H = c->input_h ? c->input_h : c->image_size; m.W = c->input_w ? c->input_w : c->image_size;
+    GG_CHECK(m.H % P == 0 && m.W % P == 0, "clip: input size %d x %d is not a multiple of the patch size %d", m.H, m.W, P);
+    m.G = c->image_size / P; m.Gh = m.H / P; m.Gw = m.W / P; m.interp = m.Gh != m.G || m.Gw != m.G;
+    // what gg_clip_pos_interp_fwd / _bwd would refuse is refused here, not mid-forward (D % 4 == 0 follows from D % 64 == 0 above)
+    GG_CHECK(!m.interp || (m.G >= 1 && m.Gh >= 1 && m.Gw >= 1), "clip: a grid side below 1 (table %d, input %d x %d patches)", m.G, m.Gh, m.Gw);
+    GG_CHECK(!m.interp || (m.G <= GG_CLIP_INTERP_MAX_SIDE && m.Gh <= GG_CLIP_INTERP_MAX_SIDE && m.Gw <= GG_CLIP_INTERP_MAX_SIDE),
+             "clip: a grid side above the cap of %d patches for a resampled position table (table %d, input %d x %d patches)", GG_CLIP_INTERP_MAX_SIDE, m.G, m.Gh, m.Gw);
+    m.T = m.Gh * m.Gw + 1; m.Kraw = 3 * P * P; m.Kpatch = (int)gg_align(m.Kraw, 8);
     m.cls = addt(m, "embeddings.class_embedding", {D});
     m.patch_w = addt(m, "embeddings.patch_embedding.weight", {D, 3, P, P});
-    m.pos = addt(m, "embeddings.position_embedding.weight", {m.T, D});
+    m.pos = addt(m, "embeddings.position_embedding.weight", {m.G * m.G + 1, D});      // image_size shapes the parameter table, whatever the size of the call
     m.pre_g = addt(m, "pre_layrnorm.weight", {D}); m.pre_b = addt(m, "pre_layrnorm.bias", {D});
     m.wpatch = wca(m, (int64_t)D * m.Kpatch * m.es);
     m.wpatch3 = m.split ? wca(m, 3 * (int64_t)D * m.Kpatch * 2) : (int64_t)-1;              // fp32_split: bf16 planes [3][n] of a cached matrix (no W^T of the patch embedding in either mode: the pixels take no gradient)
     add_layers(m);
     m.post_g = addt(m, "post_layernorm.weight", {D}); m.post_b = addt(m, "post_layernorm.bias", {D});
+    if (m.interp) m.wpos = wca(m, (int64_t)m.T * D * 4);      // after everything else: the cache of the native size is a prefix of this one
     return 0;
 }
 // the text tower's model over `tokens` positions per sequence (the tensor table does not depend on it)
@@ -179,22 +192,22 @@ __global__ void cast_kernel(const TI* __restrict__ in, TO* __restrict__ out, int
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = (TO)(float)in[i];
 }
 
-// x f32 NCHW (B,3,S,S) -> col [B*G*G, K], k = (c, py, px)  (== Conv2d(kernel=stride=P) weight flatten); K = 3*P*P padded to 8 (zero columns)
-// VEC (P % 8 == 0, S % 4 == 0, 16-byte aligned x): a thread's 8 consecutive k are 8 consecutive pixels of one image row -- two 16-byte loads, one 16-byte
+// x f32 NCHW (B,3,H,W) -> col [B*Gh*Gw, K], k = (c, py, px)  (== Conv2d(kernel=stride=P) weight flatten); K = 3*P*P padded to 8 (zero columns)
+// VEC (P % 8 == 0, W % 4 == 0, 16-byte aligned x): a thread's 8 consecutive k are 8 consecutive pixels of one image row -- two 16-byte loads, one 16-byte
 // store, the (c, py, px) split done once per thread instead of once per element (the scalar form ran at 2.5 TB/s on the batch-1024 ViT-B/32 input)
 template <typename T, bool VEC>
-__global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__ x, T* __restrict__ col, int B, int S, int P, int G, int K) {
+__global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__ x, T* __restrict__ col, int B, int H, int W, int P, int Gh, int Gw, int K) {
     const int Kraw = 3 * P * P;
-    const int64_t total = (int64_t)B * G * G * (K / 8);
+    const int64_t total = (int64_t)B * Gh * Gw * (K / 8);
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int kc = (int)(i % (K / 8)) * 8;
         const int64_t p = i / (K / 8);
-        const int gx = (int)(p % G), gy = (int)((p / G) % G), b = (int)(p / ((int64_t)G * G));
+        const int gx = (int)(p % Gw), gy = (int)((p / Gw) % Gh), b = (int)(p / ((int64_t)Gh * Gw));
         T o[8];
         if (VEC) {
             if (kc < Kraw) {
                 const int c = kc / (P * P), r = kc - c * P * P, py = r / P, px = r - py * P;
-                const float* src = x + (((int64_t)b * 3 + c) * S + gy * P + py) * S + gx * P + px;
+                const float* src = x + (((int64_t)b * 3 + c) * H + gy * P + py) * W + gx * P + px;
                 const f32x4 v0 = *reinterpret_cast<const f32x4*>(src), v1 = *reinterpret_cast<const f32x4*>(src + 4);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { o[j] = from_f<T>(v0[j]); o[4 + j] = from_f<T>(v1[j]); }
@@ -207,7 +220,7 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__
             for (int j = 0; j < 8; ++j) {
                 const int k = kc + j;
                 const int c = k / (P * P), py = (k / P) % P, px = k % P;
-                o[j] = from_f<T>(k < Kraw ? x[(((int64_t)b * 3 + c) * S + gy * P + py) * S + gx * P + px] : 0.f);
+                o[j] = from_f<T>(k < Kraw ? x[(((int64_t)b * 3 + c) * H + gy * P + py) * W + gx * P + px] : 0.f);
             }
         }
         T* dst = col + p * K + kc;
@@ -330,6 +343,7 @@ struct CPlan {
     int64_t q8 = -1, qs = -1;                                 // fp8: the e4m3 codes of the Linear input at hand (M x max(D, I) bytes, reused) and its scale row
     std::vector<LayerA> la;
     int64_t xfinal;
+    int64_t dpos_r = -1;                                      // resampled position table (CModel.interp) with a trainable table: embed_bwd's (T, D) f32 sums, which gg_clip_pos_interp_bwd adds into the table's gradient
     int64_t g_x0, g_x1, g_a, g_qkv, g_o, g_h, splitk, colsum, lnscr, lndump, attn_ds = -1;      // lndump: where a frozen LayerNorm tensor's half of a (gamma, beta) gradient pair goes      // backward scratch (attn_ds: GgAttnArgs.ds_scratch)
     int64_t total;
     bool rc = false;                                          // checkpointed layout: every la[i] of a kept layer names the shared segment region but .xin
@@ -377,7 +391,7 @@ static int clip_attn_launch(const AttnCall& c, const GgAttnArgs& at, hipStream_t
 }
 static void plan(const CModel& m, int B, const Train& tr, bool training, CPlan& L, int ds_force = -1) {
     const int D = m.cfg.hidden_size, I = m.cfg.intermediate_size, nl = m.cfg.num_layers;
-    const int64_t Mp = (int64_t)B * m.G * m.G, M = (int64_t)B * m.T, es = m.es;
+    const int64_t Mp = (int64_t)B * m.Gh * m.Gw, M = (int64_t)B * m.T, es = m.es;
     int64_t off = 0;
     auto al = [&](int64_t bytes) { int64_t o = off; off += gg_align(std::max<int64_t>(bytes, 1), 256); return o; };
     L.col = al(Mp * m.Kpatch * es); L.patches = al(Mp * D * es); L.tok = al(M * D * es); L.mean0 = al(M * 4); L.rstd0 = al(M * 4);
@@ -434,6 +448,7 @@ static void plan(const CModel& m, int B, const Train& tr, bool training, CPlan& 
         const bool reads = gg_attention_route(&at, call.entry, call.dtype, &r) == 0 && r.reads_ds_scratch;
         const bool ds = !reads ? false : ds_force >= 0 ? ds_force != 0 : !attn_switches().no_ds_scratch && dsb <= ((int64_t)4 << 30) && dsb <= off / 8;
         if (ds) L.attn_ds = al(dsb);
+        if (m.interp && tr.embed && !m.causal) L.dpos_r = al((int64_t)m.T * D * 4);      // (after every region of the native plan)
     }
     L.total = off;
 }
@@ -520,13 +535,13 @@ struct Exec {
 template <typename T> static int embed_fwd(const Exec& e, const float* x, void* tok_out) {
     const CModel& m = *e.m; const CPlan& L = *e.L;
     const int D = m.cfg.hidden_size, B = e.B;
-    const int64_t Mp = (int64_t)B * m.G * m.G, M = (int64_t)B * m.T;
-    const bool pvec = (m.cfg.patch_size & 7) == 0 && (m.cfg.image_size & 3) == 0 && ((uintptr_t)x & 15) == 0;
-    if (pvec) hipLaunchKernelGGL((patchify_kernel<T, true>), dim3(grid1d(Mp * (m.Kpatch / 8))), dim3(256), 0, e.st, x, (T*)e.A(L.col), B, m.cfg.image_size, m.cfg.patch_size, m.G, m.Kpatch);
-    else hipLaunchKernelGGL((patchify_kernel<T, false>), dim3(grid1d(Mp * (m.Kpatch / 8))), dim3(256), 0, e.st, x, (T*)e.A(L.col), B, m.cfg.image_size, m.cfg.patch_size, m.G, m.Kpatch);
+    const int64_t Mp = (int64_t)B * m.Gh * m.Gw, M = (int64_t)B * m.T;
+    const bool pvec = (m.cfg.patch_size & 7) == 0 && (m.W & 3) == 0 && ((uintptr_t)x & 15) == 0;
+    if (pvec) hipLaunchKernelGGL((patchify_kernel<T, true>), dim3(grid1d(Mp * (m.Kpatch / 8))), dim3(256), 0, e.st, x, (T*)e.A(L.col), B, m.H, m.W, m.cfg.patch_size, m.Gh, m.Gw, m.Kpatch);
+    else hipLaunchKernelGGL((patchify_kernel<T, false>), dim3(grid1d(Mp * (m.Kpatch / 8))), dim3(256), 0, e.st, x, (T*)e.A(L.col), B, m.H, m.W, m.cfg.patch_size, m.Gh, m.Gw, m.Kpatch);
     GG_LAUNCH_CHECK();
     GG_TRY(e.gemm(e.A(L.col), m.Kpatch, e.W(m.wpatch, m.wpatch3), m.Kpatch, e.A(L.patches), D, Mp, D, m.Kpatch, nullptr));
-    hipLaunchKernelGGL(assemble_tokens_kernel<T>, dim3(grid1d(M * D / 4)), dim3(256), 0, e.st, (const T*)e.A(L.patches), e.P(m.cls), e.P(m.pos), (T*)tok_out,
+    hipLaunchKernelGGL(assemble_tokens_kernel<T>, dim3(grid1d(M * D / 4)), dim3(256), 0, e.st, (const T*)e.A(L.patches), e.P(m.cls), m.interp ? (const float*)e.W(m.wpos) : e.P(m.pos), (T*)tok_out,
                        B, m.T, D);
     GG_LAUNCH_CHECK();
     return 0;
@@ -703,6 +718,7 @@ extern "C" int gg_clip_refresh_weights(const GgClipCfg* cfg, const float* params
 // (the text tower comes through here too: it has no patch embedding)
 static int refresh_model(const CModel& m, const float* params, void* wcache, const uint8_t* only, void* stream) {
     GG_CHECK(params && wcache, "gg_clip_refresh_weights: null pointer");
+    GG_CHECK(!m.interp || (((uintptr_t)params & 15) == 0 && ((uintptr_t)wcache & 15) == 0), "gg_clip_refresh_weights: a resampled position table needs 16-byte aligned params and wcache");
     char* wc = (char*)wcache;
     hipStream_t st = (hipStream_t)stream;
     const int D = m.cfg.hidden_size, I = m.cfg.intermediate_size;
@@ -734,6 +750,7 @@ static int refresh_model(const CModel& m, const float* params, void* wcache, con
     else hipLaunchKernelGGL(cast_pad_rows_kernel<bf16>, dim3(grid1d((int64_t)D * m.Kpatch)), dim3(256), 0, st, P(m.patch_w), (bf16*)(wc + m.wpatch), D, m.Kraw, m.Kpatch);
     GG_LAUNCH_CHECK();
     if (!m.causal && ch(m.patch_w)) GG_TRY(split3(m.wpatch, D, m.Kpatch, m.wpatch3));
+    if (m.interp && ch(m.pos)) GG_TRY(gg_clip_pos_interp_fwd(P(m.pos), m.G, m.Gh, m.Gw, D, (float*)(wc + m.wpos), stream));      // the table at the size of the call
     for (auto& l : m.layers) {
         GG_TRY(put(l.q_w, D, D, l.wqkv, 0, l.wqkvT, 3 * D, 0));
         GG_TRY(put(l.k_w, D, D, l.wqkv, D, l.wqkvT, 3 * D, D));
@@ -823,6 +840,7 @@ extern "C" int gg_clip_backward(const GgClipCfg* cfg, int batch, const float* pa
     GG_TRY(build(cfg, m));
     GG_CHECK(batch > 0 && params && wcache && workspace && grads && (d_out || d_last_hidden), "gg_clip_backward: null pointer / bad batch");
     GG_CHECK(!m.fp8, "gg_clip_backward: the fp8 mode is inference-only");
+    GG_CHECK(!m.interp || (((uintptr_t)grads & 15) == 0 && ((uintptr_t)workspace & 15) == 0), "gg_clip_backward: a resampled position table needs 16-byte aligned grads and workspace");
     const Train tr = train_of(m, 1, trainable);
     const int nl = m.cfg.num_layers;
     if (tr.l0 >= nl) return 0;                    // nothing in the tower is trainable
@@ -838,7 +856,7 @@ extern "C" int gg_clip_backward(const GgClipCfg* cfg, int batch, const float* pa
     Exec e{&m, &L, batch, (hipStream_t)stream, params, (const char*)wcache, (char*)workspace, grads, trainable};
     e.attn16t = attention16_train_route(m);       // the recompute replay and the attention backward
     const int D = m.cfg.hidden_size, I = m.cfg.intermediate_size, T = m.T, B = batch;
-    const int64_t M = (int64_t)B * T, Mp = (int64_t)B * m.G * m.G;
+    const int64_t M = (int64_t)B * T, Mp = (int64_t)B * m.Gh * m.Gw;
     if (m.f32) hipLaunchKernelGGL(pool_bwd_kernel<float>, dim3(grid1d(M * D)), dim3(256), 0, e.st, d_out, d_last_hidden, (float*)e.A(L.g_x0), B, T, D);
     else hipLaunchKernelGGL(pool_bwd_kernel<bf16>, dim3(grid1d(M * D)), dim3(256), 0, e.st, d_out, d_last_hidden, (bf16*)e.A(L.g_x0), B, T, D);
     GG_LAUNCH_CHECK();
@@ -848,13 +866,17 @@ extern "C" int gg_clip_backward(const GgClipCfg* cfg, int batch, const float* pa
     // ---- embeddings: x_0 = pre_layrnorm(tokens), tokens = [cls ; patches . W^T] + pos
     GG_TRY(e.ln_bwd(e.A(dx), e.A(L.tok), e.F(L.mean0), e.F(L.rstd0), m.pre_g, m.pre_b, M, nullptr, e.A(other)));
     const bool wp = e.tr(m.patch_w);
-    float* dpos = e.tr(m.pos) ? e.Gd(m.pos) : nullptr;
+    // a resampled table: the sums over the batch are the gradient of the (T, D) table the forward read; its adjoint resampling adds them into the parameter's
+    const bool rpos = m.interp && e.tr(m.pos);
+    if (rpos) GG_HIP(hipMemsetAsync(e.A(L.dpos_r), 0, (size_t)T * D * 4, e.st));
+    float* dpos = rpos ? e.F(L.dpos_r) : e.tr(m.pos) ? e.Gd(m.pos) : nullptr;
     float* dcls = e.tr(m.cls) ? e.Gd(m.cls) : nullptr;
     if (m.f32) hipLaunchKernelGGL(embed_bwd_kernel<float>, dim3((unsigned)gg_cdiv((int64_t)T * D, 256)), dim3(256), 0, e.st, (const float*)e.A(other), dpos, dcls,
                                   wp ? (float*)e.A(L.g_a) : nullptr, B, T, D);
     else hipLaunchKernelGGL(embed_bwd_kernel<bf16>, dim3((unsigned)gg_cdiv((int64_t)T * D, 256)), dim3(256), 0, e.st, (const bf16*)e.A(other), dpos, dcls,
                             wp ? (bf16*)e.A(L.g_a) : nullptr, B, T, D);
     GG_LAUNCH_CHECK();
+    if (rpos) GG_TRY(gg_clip_pos_interp_bwd(e.F(L.dpos_r), m.G, m.Gh, m.Gw, D, e.Gd(m.pos), e.st));
     if (wp) {
         int sp;
         GG_TRY(e.tn(e.A(L.g_a), D, e.A(L.col), m.Kpatch, Mp, D, m.Kpatch, &sp));

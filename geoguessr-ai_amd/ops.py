@@ -478,6 +478,38 @@ def window_crop_add(t, H, W, res=None, rowscale=None, out=None):
     return out
 
 
+def _interp_grids(rows: int, grid_hw, what: str):
+    Gs = int(round((rows - 1) ** 0.5))
+    if Gs * Gs + 1 != rows:
+        raise L.GgError(f"{what}: a position table has Gs * Gs + 1 rows, got {rows}")
+    return Gs, int(grid_hw[0]), int(grid_hw[1])
+
+
+def clip_pos_interp(pos, grid_hw, out=None):
+    """The CLIP position table ``pos`` (Gs * Gs + 1, D) f32 resampled to the patch grid ``grid_hw`` = (Gh, Gw): (Gh * Gw + 1, D) f32 (``gg_clip_pos_interp_fwd``,
+    include/gg_clip_interp.h -- transformers' ``interpolate_pos_encoding``: bicubic, A = -0.75, align_corners = False, the class row kept)."""
+    Gs, Gh, Gw = _interp_grids(pos.shape[0], grid_hw, "clip_pos_interp")
+    D = pos.shape[1]
+    if out is None:
+        out = torch.empty((max(Gh, 0) * max(Gw, 0) + 1, D), dtype=F32, device=pos.device)
+    L.check(L.lib().gg_clip_pos_interp_fwd(_p(pos, F32, "pos"), Gs, Gh, Gw, D, _p(out, F32, "out"), L.stream()), "gg_clip_pos_interp_fwd")
+    return out
+
+
+def clip_pos_interp_bwd(d_out, source_rows: int, grid_hw, accumulate_into=None):
+    """The adjoint of ``clip_pos_interp``: the gradient (source_rows, D) f32 of the table from ``d_out`` (Gh * Gw + 1, D) f32 (``gg_clip_pos_interp_bwd``).  The
+    kernel ADDS: into ``accumulate_into`` when given, else into zeros."""
+    Gs, Gh, Gw = _interp_grids(source_rows, grid_hw, "clip_pos_interp_bwd")
+    D = d_out.shape[1]
+    if d_out.shape[0] != Gh * Gw + 1:
+        raise L.GgError(f"clip_pos_interp_bwd: d_out has {d_out.shape[0]} rows, the grid {Gh} x {Gw} has {Gh * Gw + 1}")
+    d_pos = accumulate_into if accumulate_into is not None else torch.zeros((source_rows, D), dtype=F32, device=d_out.device)
+    if tuple(d_pos.shape) != (source_rows, D):
+        raise L.GgError(f"clip_pos_interp_bwd: accumulate_into must be ({source_rows}, {D}), got {tuple(d_pos.shape)}")
+    L.check(L.lib().gg_clip_pos_interp_bwd(_p(d_out, F32, "d_out"), Gs, Gh, Gw, D, _p(d_pos, F32, "accumulate_into"), L.stream()), "gg_clip_pos_interp_bwd")
+    return d_pos
+
+
 def layernorm_bwd_colsum(dout, x, mean, rstd, gamma, dres=None):
     """LayerNorm backward that also leaves the per-block column sums (sum dx*x, sum dx) of its result; returns (dx, part, rows)."""
     M, Cc = x.shape

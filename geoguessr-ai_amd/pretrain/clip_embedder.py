@@ -17,7 +17,8 @@ config c4 names), or ``"fp8"`` (inference only: fp16's storage and schedule with
 not in the reference): the inference forward of a tower beyond 256 tokens (ViT-L/14-336: 577) runs its attention with both products on the 16-bit MFMA
 (``gg_attention_flash16_fwd``, include/gg_attn16.h) instead of the f32-MFMA online-softmax kernel; training forwards are unaffected.  ``attention16_train=True`` (bf16 only; opt-in, not in the reference, independent of
 ``attention16``): the TRAINING step of such a tower -- the training forward, the recompute replay and the attention backward -- runs on the 16-bit MFMA
-(``gg_attention_flash16_fwd`` / ``gg_attention_flash16_bwd``, include/gg_attn16b.h).  No hub download: weights come from a
+(``gg_attention_flash16_fwd`` / ``gg_attention_flash16_bwd``, include/gg_attn16b.h).  ``interpolate_pos_encoding=True`` (transformers' keyword; opt-in, as a
+tower default or per call): pixel_values of another size than ``image_size`` run on the position table resampled to their grid (include/gg_clip_interp.h).  No hub download: weights come from a
 state dict (HF names, with or without the leading ``vision_model.``)."""
 from __future__ import annotations
 
@@ -91,6 +92,8 @@ class _VisionModel(EncoderRuntime):
     _toggled_gen = None               # generation of a training forward that a gradient_checkpointing toggle made the runtime forget
     attention16 = False               # CLIPVisionTower(attention16=True): this tower's forwards run with gg_clip_set_attention16(1)
     attention16_train = False         # CLIPVisionTower(attention16_train=True): its training forwards and backwards run with gg_clip_set_attention16_train(1)
+    _hw = (0, 0)                      # GgClipCfg.input_h / input_w of the call at hand ((0, 0): the native size); the weight cache holds the position table resampled for it
+    _wc_hw = (0, 0)                   # ... and the size the weight cache was last rebuilt for
 
     def __init__(self, cfg: L.ClipCfg, seed: int):
         super().__init__()
@@ -121,14 +124,58 @@ class _VisionModel(EncoderRuntime):
             return torch.randn(shape, generator=g) * 0.02
         self._register_table(init)
 
+    def _cfg_at(self, hw) -> L.ClipCfg:
+        """``self.cfg`` with ``input_h`` / ``input_w`` of a call ((0, 0): the native size -- the struct as it is)."""
+        c = L.ClipCfg.from_buffer_copy(self.cfg)
+        c.input_h, c.input_w = hw
+        return c
+
+    def _call_size(self, x: Tensor, interpolate: bool):
+        """(input_h, input_w) of ``GgClipCfg`` for these pixel_values: (0, 0) at the native size; a foreign size needs ``interpolate_pos_encoding``."""
+        S, P = self.cfg.image_size, self.cfg.patch_size
+        native = x.dim() == 4 and x.shape[1] == 3 and x.shape[2] == S and x.shape[3] == S
+        if native:
+            return (0, 0)
+        if not interpolate or x.dim() != 4 or x.shape[1] != 3:
+            raise L.GgError(f"CLIPVisionTower expects (B,3,{S},{S}) pixel_values, got {tuple(x.shape)}")
+        H, W = int(x.shape[2]), int(x.shape[3])
+        if H < P or W < P or H % P or W % P:
+            raise L.GgError(f"CLIPVisionTower(interpolate_pos_encoding=True): input size {H} x {W} is not a multiple of the patch size {P}")
+        return (H, W)
+
+    def _set_call_size(self, hw):
+        """The weight cache carries the position table of ONE call size in its last region.  A cache too small for this size's table is let go (``_ensure_weights``
+        allocates and rebuilds it whole); otherwise ``_sync_table`` rebuilds the table alone."""
+        self._hw = hw
+        if hw != self._wc_hw and self._wcache is not None and self._wcache.numel() < self._wcache_bytes():
+            self._wcache = None
+
+    def _sync_table(self):
+        """After ``_ensure_weights``: the cache is current for the parameters; if its table is another call size's, resample the table alone
+        (``gg_clip_pos_interp_fwd`` into the cache's last region, whose offset is the native cache's size: include/gg.h, ``GgClipCfg.input_h``)."""
+        if self._hw == self._wc_hw:
+            return
+        if self._hw != (0, 0):
+            from .. import ops
+            P, D = self.cfg.patch_size, self.cfg.hidden_size
+            gh, gw = self._hw[0] // P, self._hw[1] // P
+            off = L.lib().gg_clip_wcache_bytes(C.byref(self.cfg))
+            region = self._wcache[off:off + (gh * gw + 1) * D * 4].view(torch.float32).view(gh * gw + 1, D)
+            ops.clip_pos_interp(self._params["embeddings.position_embedding.weight"].data, (gh, gw), out=region)
+        self._wc_hw = self._hw
+
     def _wcache_bytes(self) -> int:
-        return L.lib().gg_clip_wcache_bytes(C.byref(self.cfg))
+        n = L.lib().gg_clip_wcache_bytes(C.byref(self._cfg_at(self._hw)))
+        if n < 0:
+            raise L.GgError(L.lib().gg_last_error().decode())
+        return n
 
     def _refresh(self, only):             # (no masked refresh: the whole cache is rebuilt, in the fp32_split mode the bf16 planes with it)
-        L.check(L.lib().gg_clip_refresh_weights(C.byref(self.cfg), L.ptr(self._flat), L.ptr(self._wcache), L.stream()), "gg_clip_refresh_weights")
+        L.check(L.lib().gg_clip_refresh_weights(C.byref(self._cfg_at(self._hw)), L.ptr(self._flat), L.ptr(self._wcache), L.stream()), "gg_clip_refresh_weights")
+        self._wc_hw = self._hw
 
     def _workspace_bytes(self, batch: int, training: bool, mask) -> int:
-        return L.lib().gg_clip_workspace_bytes(C.byref(self.cfg), batch, int(training), mask)
+        return L.lib().gg_clip_workspace_bytes(C.byref(self._cfg_at(self._hw)), batch, int(training), mask)
 
     def set_recompute(self, enable: bool) -> bool:
         changed = super().set_recompute(enable)
@@ -142,24 +189,29 @@ class _VisionModel(EncoderRuntime):
                             "released, the other layout keeps other tensors; run the forward again")
         return super()._pending(gen, batch)
 
-    def forward_hip(self, x: Tensor, training: bool, return_last_hidden: bool):
+    def forward_hip(self, x: Tensor, training: bool, return_last_hidden: bool, interpolate_pos_encoding: bool = False):
+        """``interpolate_pos_encoding``: a (B,3,H,W) input of another size than ``image_size`` (H, W multiples of the patch size) runs on the position table
+        resampled to its grid (``GgClipCfg.input_h`` / ``input_w``); without it such an input is refused.  The workspaces (one per ``training`` flag) grow to
+        the largest call; the record of a training forward carries its size, and its backward runs at that size."""
         L.require_gpu()
         if not self._flat.is_cuda:
             raise L.GgError("CLIPVisionTower parameters are on the CPU; call .to('cuda') -- there is no CPU fallback")
-        S = self.cfg.image_size
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != S or x.shape[3] != S:
-            raise L.GgError(f"CLIPVisionTower expects (B,3,{S},{S}) pixel_values, got {tuple(x.shape)}")
+        hw = self._call_size(x, interpolate_pos_encoding)
+        cfg = self._cfg_at(hw)
+        S, P = self.cfg.image_size, self.cfg.patch_size
         x = x.to(device=self._flat.device, dtype=torch.float32).contiguous()
         B = x.shape[0]
+        self._set_call_size(hw)
         mask, ws = self._prepare(B, training)
-        D, T = self.cfg.hidden_size, (S // self.cfg.patch_size) ** 2 + 1
+        self._sync_table()
+        D, T = self.cfg.hidden_size, ((hw[0] // P) * (hw[1] // P) if hw != (0, 0) else (S // P) ** 2) + 1
         out = torch.empty((B, D), dtype=torch.float32, device=x.device)
         last = torch.empty((B, T, D), dtype=torch.float32, device=x.device) if return_last_hidden else None
         lib = L.lib()
         prev = lib.gg_clip_set_attention16(1) if self.attention16 else None      # process-wide switch, read when the forward is enqueued: set for this call only
         prev_t = lib.gg_clip_set_attention16_train(1) if self.attention16_train and training else None      # the same, the training step's switch
         try:
-            rc = lib.gg_clip_forward(C.byref(self.cfg), B, int(training), L.ptr(self._flat), L.ptr(self._wcache), L.ptr(x), L.ptr(ws), L.ptr(out),
+            rc = lib.gg_clip_forward(C.byref(cfg), B, int(training), L.ptr(self._flat), L.ptr(self._wcache), L.ptr(x), L.ptr(ws), L.ptr(out),
                                      L.ptr(last), mask, L.stream())
         finally:
             if prev is not None:
@@ -168,19 +220,20 @@ class _VisionModel(EncoderRuntime):
                 lib.gg_clip_set_attention16_train(prev_t)
         L.check(rc, "gg_clip_forward")
         if training:
-            self._record_forward(B, mask)
+            self._record_forward(B, mask, payload=hw)
         return out, last
 
     def backward_hip(self, d_out: Optional[Tensor], d_last: Optional[Tensor], gen: int):
-        B, _, ws = self._pending(gen)
+        B, hw, ws = self._pending(gen)
         mask = self._same_mask()
+        cfg = self._cfg_at(hw)      # the size of ITS forward (the backward reads no position table: an eval forward at another size in between changes nothing)
         fg = self.attach_grads()
         f = lambda t: None if t is None else t.to(torch.float32).contiguous()
         d_out, d_last = f(d_out), f(d_last)
         lib = L.lib()
         prev_t = lib.gg_clip_set_attention16_train(1) if self.attention16_train else None      # read when the backward is enqueued (its recompute replay included)
         try:
-            rc = lib.gg_clip_backward(C.byref(self.cfg), B, L.ptr(self._flat), L.ptr(self._wcache), L.ptr(ws), L.ptr(d_out), L.ptr(d_last), L.ptr(fg), mask,
+            rc = lib.gg_clip_backward(C.byref(cfg), B, L.ptr(self._flat), L.ptr(self._wcache), L.ptr(ws), L.ptr(d_out), L.ptr(d_last), L.ptr(fg), mask,
                                       L.stream())
         finally:
             if prev_t is not None:
@@ -194,8 +247,14 @@ class CLIPVisionTower(nn.Module):
     supports_gradient_checkpointing = True          # (transformers PreTrainedModel's class attribute)
 
     def __init__(self, model_name: str = "openai/clip-vit-base-patch32", seed: int = 0, precision: Optional[str] = None,
-                 gradient_checkpointing: bool = False, attention16: bool = False, attention16_train: bool = False, **cfg_overrides):
-        """``attention16_train=True`` (bf16 only; opt-in, independent of ``attention16``): this tower's training steps run with
+                 gradient_checkpointing: bool = False, attention16: bool = False, attention16_train: bool = False, interpolate_pos_encoding: bool = False,
+                 **cfg_overrides):
+        """``interpolate_pos_encoding`` (transformers' ``CLIPVisionModel.forward`` keyword, here also a tower default for callers that pass ``pixel_values`` alone,
+        as ``SuperGuessr`` does): pixel_values of another size than ``image_size`` -- any (H, W) of patch multiples, square or not -- run on the pretrained
+        position table resampled to their grid (bicubic, the class row kept; include/gg_clip_interp.h), gradients flowing back into the table.  Off: such
+        input is refused, as before.  ``image_size`` keeps naming the size the weights were trained at.
+
+        ``attention16_train=True`` (bf16 only; opt-in, independent of ``attention16``): this tower's training steps run with
         ``gg_clip_set_attention16_train(1)`` -- with more than 256 tokens the training forward, the recompute replay and the attention backward go through
         ``gg_attention_flash16_fwd`` / ``gg_attention_flash16_bwd`` (include/gg_attn16b.h); inference forwards are unaffected."""
         super().__init__()
@@ -214,7 +273,8 @@ class CLIPVisionTower(nn.Module):
         self.vision_model = _VisionModel(c, seed)
         self.attention16 = self.vision_model.attention16 = bool(attention16)
         self.attention16_train = self.vision_model.attention16_train = bool(attention16_train)
-        self.num_tokens = (c.image_size // c.patch_size) ** 2 + 1
+        self.interpolate_pos_encoding = bool(interpolate_pos_encoding)
+        self.num_tokens = (c.image_size // c.patch_size) ** 2 + 1      # (at the native size)
 
     # ---- activation recompute -----------------------------------------------------------------------------------------------------------
     @property
@@ -250,21 +310,23 @@ class CLIPVisionTower(nn.Module):
                     views[k].copy_(torch.as_tensor(v).to(views[k].device, torch.float32))
         self.vision_model.mark_params_dirty()
 
-    def forward_hip(self, x: Tensor, training: bool, return_last_hidden: bool):          # (the HIP calls are the vision model's)
-        return self.vision_model.forward_hip(x, training, return_last_hidden)
+    def forward_hip(self, x: Tensor, training: bool, return_last_hidden: bool, interpolate_pos_encoding: bool = False):          # (the HIP calls are the vision model's)
+        return self.vision_model.forward_hip(x, training, return_last_hidden, interpolate_pos_encoding)
 
     def backward_hip(self, d_out: Optional[Tensor], d_last: Optional[Tensor], gen: int):
         self.vision_model.backward_hip(d_out, d_last, gen)
 
-    def forward(self, pixel_values: Tensor = None, return_last_hidden: bool = True):
+    def forward(self, pixel_values: Tensor = None, return_last_hidden: bool = True, interpolate_pos_encoding: Optional[bool] = None):
+        """``interpolate_pos_encoding``: ``None`` = the tower's default (the constructor's keyword)."""
         vm = self.vision_model
+        interp = self.interpolate_pos_encoding if interpolate_pos_encoding is None else bool(interpolate_pos_encoding)
         need = vm.wants_grad()      # (no dropout / BatchNorm: train and eval compute the same)
         if need and self.precision in ("fp16", "fp8"):
             raise L.GgError(f"CLIPVisionTower(precision='{self.precision}') is inference-only: run under torch.no_grad() / freeze it, or train in fp32 / bf16")
         if not need:
-            out, last = vm.forward_hip(pixel_values, False, return_last_hidden)
+            out, last = vm.forward_hip(pixel_values, False, return_last_hidden, interp)
         else:
-            out, last = _ClipFn.apply(vm, pixel_values, vm._anchor(), return_last_hidden)
+            out, last = _ClipFn.apply(vm, pixel_values, vm._anchor(), return_last_hidden, interp)
         return SimpleNamespace(last_hidden_state=last, pooled_mean=out, pooler_output=out)
 
 
@@ -272,8 +334,8 @@ class _ClipFn(EncoderNode):
     """Whole-tower autograd node (the counterpart of the TinyViT backbone's; ``EncoderRuntime._anchor``)."""
 
     @staticmethod
-    def forward(ctx, vm: _VisionModel, x: Tensor, anchor: Tensor, want_last: bool):
-        out, last = vm.forward_hip(x, True, want_last)
+    def forward(ctx, vm: _VisionModel, x: Tensor, anchor: Tensor, want_last: bool, interpolate: bool = False):
+        out, last = vm.forward_hip(x, True, want_last, interpolate)
         vm._enter_node(ctx)
         ctx.set_materialize_grads(False)          # an unused last_hidden_state must not cost a (B,T,D) zero gradient
         return out, last
@@ -290,8 +352,12 @@ def clip_preprocess(images, size: int, device) -> Tensor:
 class CLIPEmbedding(nn.Module):
     def __init__(self, model_name: str = "openai/clip-vit-base-patch32", device: str = "cuda", load_checkpoint: bool = False,
                  panorama: bool = False, state_dict: Optional[Dict[str, Tensor]] = None, precision: Optional[str] = None, batch_transform: bool = False,
-                 jpeg_split_bytes: int = 0, attention16: bool = False, jpeg_progressive: bool = False, **cfg_overrides):
-        """``batch_transform`` (not in the reference): raw images -- a list of any sizes, or the four panorama views together -- go through ONE ``gg_eval_batch``
+                 jpeg_split_bytes: int = 0, attention16: bool = False, jpeg_progressive: bool = False, image_size: Optional[int] = None, **cfg_overrides):
+        """``image_size`` (not in the reference): raw images are resized and cropped to this size instead of the tower's own (``DeviceEvalTransform`` /
+        ``clip_preprocess`` at that size; a multiple of the patch size) and the tower runs them on its resampled position table
+        (``CLIPVisionTower(interpolate_pos_encoding=True)``); the weights keep the size they were trained at.  ``None``: the tower's size.
+
+        ``batch_transform`` (not in the reference): raw images -- a list of any sizes, or the four panorama views together -- go through ONE ``gg_eval_batch``
         call (``training.preprocess.DeviceEvalTransform``) instead of one ``gg_preprocess_pil`` call per image; same arithmetic.  ``jpeg_split_bytes`` (with
         ``batch_transform`` only): the ``split_bytes`` of the decoder that takes JPEG files given as bytes (``DeviceEvalTransform``'s keyword); ``jpeg_progressive`` (with
         ``batch_transform`` only): that decoder's ``progressive`` (progressive files are decoded next to baseline ones; off by default).  ``attention16``:
@@ -308,7 +374,10 @@ class CLIPEmbedding(nn.Module):
         self.jpeg_progressive = bool(jpeg_progressive)
         self.panorama = panorama
         self.clip_model = CLIPVisionTower(model_name if not load_checkpoint else "openai/clip-vit-base-patch32", precision=precision, attention16=attention16,
-                                          **cfg_overrides)
+                                          interpolate_pos_encoding=image_size is not None, **cfg_overrides)
+        self.image_size = int(image_size) if image_size is not None else self.clip_model.cfg.image_size      # the size raw images are brought to
+        if self.image_size <= 0 or self.image_size % self.clip_model.cfg.patch_size:
+            raise ValueError(f"CLIPEmbedding: image_size={image_size} is not a multiple of the patch size {self.clip_model.cfg.patch_size}")
         if load_checkpoint:
             state_dict = torch.load(model_name, map_location="cpu")
             print("Loaded embedder from checkpoint:", model_name)
@@ -323,7 +392,7 @@ class CLIPEmbedding(nn.Module):
         """The processor's tensor side as a batch transform (``batch_transform=True``); it keeps its workspace from call to call."""
         if self._transform is None:
             from ..training.preprocess import DeviceEvalTransform
-            self._transform = DeviceEvalTransform(self.clip_model.cfg.image_size, CLIP_MEAN, CLIP_STD, "clip", device=next(self.clip_model.parameters()).device,
+            self._transform = DeviceEvalTransform(self.image_size, CLIP_MEAN, CLIP_STD, "clip", device=next(self.clip_model.parameters()).device,
                                                   jpeg_split_bytes=self.jpeg_split_bytes, jpeg_progressive=self.jpeg_progressive)
         return self._transform
 
@@ -336,7 +405,7 @@ class CLIPEmbedding(nn.Module):
         elif self.batch_transform:
             pixel_values = self._eval_transform()(image)
         else:
-            pixel_values = clip_preprocess(image, self.clip_model.cfg.image_size, dev)
+            pixel_values = clip_preprocess(image, self.image_size, dev)
         with torch.no_grad():
             return self.clip_model(pixel_values=pixel_values, return_last_hidden=False).pooled_mean
 

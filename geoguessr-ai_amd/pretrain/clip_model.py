@@ -406,11 +406,11 @@ class CLIPModel(nn.Module):
         self.text_model.mark_params_dirty()
 
     # ---- features -------------------------------------------------------------------------------------------------------------------------
-    def _image_pooled(self, pixel_values: Tensor) -> Tensor:
+    def _image_pooled(self, pixel_values: Tensor, interpolate_pos_encoding: Optional[bool] = None) -> Tensor:
         if not torch.is_tensor(pixel_values) or not pixel_values.is_cuda:
             raise L.GgError("pixel_values must live on the GPU; there is no CPU fallback")
         vm = self.vision_model
-        last = self.vision_tower(pixel_values=pixel_values, return_last_hidden=True).last_hidden_state
+        last = self.vision_tower(pixel_values=pixel_values, return_last_hidden=True, interpolate_pos_encoding=interpolate_pos_encoding).last_hidden_state
         if last.requires_grad:
             return _PoolerFn.apply(vm, last)
         return ops.layernorm_fwd(_row0(last), vm._params["post_layernorm.weight"].data, vm._params["post_layernorm.bias"].data, eps=vm.cfg.ln_eps,
@@ -422,17 +422,19 @@ class CLIPModel(nn.Module):
             return _TextFn.apply(tm, input_ids, tm._anchor(), False)[0]
         return tm.forward_hip(input_ids, None, False)[0]
 
-    def get_image_features(self, pixel_values: Tensor = None, **_) -> Tensor:
+    def get_image_features(self, pixel_values: Tensor = None, interpolate_pos_encoding: Optional[bool] = None, **_) -> Tensor:
+        """``interpolate_pos_encoding``: transformers' keyword, passed to the vision tower (``None``: the tower's default)."""
         with torch.no_grad():
-            return ops.gemm_nt(self._image_pooled(pixel_values), self.visual_projection.weight.detach())
+            return ops.gemm_nt(self._image_pooled(pixel_values, interpolate_pos_encoding), self.visual_projection.weight.detach())
 
     def get_text_features(self, input_ids: Tensor = None, attention_mask=None, **_) -> Tensor:
         with torch.no_grad():
             return ops.gemm_nt(self._text_pooled(input_ids), self.text_projection.weight.detach())
 
-    def forward(self, input_ids: Tensor = None, pixel_values: Tensor = None, attention_mask=None, return_loss: bool = False, **_):
+    def forward(self, input_ids: Tensor = None, pixel_values: Tensor = None, attention_mask=None, return_loss: bool = False,
+                interpolate_pos_encoding: Optional[bool] = None, **_):
         pooled_txt = self._text_pooled(input_ids)
-        pooled_img = self._image_pooled(pixel_values)
+        pooled_img = self._image_pooled(pixel_values, interpolate_pos_encoding)
         if return_loss and pooled_img.shape[0] != pooled_txt.shape[0]:
             raise L.GgError(f"return_loss needs as many images as texts (got {pooled_img.shape[0]} images, {pooled_txt.shape[0]} texts)")
         loss, lpi, lpt, te, ie = _HeadFn.apply(self, pooled_img, pooled_txt, self.visual_projection.weight, self.text_projection.weight, self.logit_scale,

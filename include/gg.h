@@ -640,6 +640,18 @@ typedef struct GgClipCfg {
                                attention backward's dS hand-off exists is taken from the recompute = 0 plan of the same batch and mask.
                                The workspace size and layout depend on the field: forward and backward must see the same value
                                (gg_clip_backward refuses the other value for a workspace whose last training forward it has seen). */
+    int input_h, input_w;  /* the size of the CALL in pixels, (batch, 3, input_h, input_w); 0 = image_size (a zeroed tail is the plan, the launch list and the byte
+                              counts of the struct without the fields).  image_size keeps shaping the parameter table -- position_embedding.weight is
+                              ((image_size / patch_size)^2 + 1, hidden) whatever the call --; a foreign size (either grid side differs) runs with
+                              T = (input_h / patch_size) * (input_w / patch_size) + 1 tokens on the position table resampled as transformers'
+                              interpolate_pos_encoding=True does (include/gg_clip_interp.h: bicubic, A = -0.75, align_corners = False, the class row kept).
+                              The resampled f32 table (T x hidden) is the LAST region of the weight cache -- gg_clip_wcache_bytes grows by it, every other
+                              offset is the native cache's --, rebuilt by gg_clip_refresh_weights and read by the token assembly in every act_dtype; a
+                              training step sums the table's gradient over the batch into a zeroed (T, hidden) f32 workspace region (the last one of the
+                              plan) and gg_clip_pos_interp_bwd adds its adjoint resampling into the parameter's gradient.  Refused by name: a size that is
+                              no multiple of patch_size, a negative size, and with a foreign size a grid side (table or call) above
+                              GG_CLIP_INTERP_MAX_SIDE.  Every entry point that takes the struct honours the fields; forward, backward, refresh and the
+                              byte counts must see the same values. */
 } GgClipCfg;
 int gg_clip_num_tensors(const GgClipCfg* cfg);
 int gg_clip_tensor_info(const GgClipCfg* cfg, int i, char* name, int name_cap, int64_t* offset, int64_t* numel, int* ndim, int64_t* shape4);
