@@ -498,6 +498,16 @@ CLIP_INTERP_SIGNATURES = {
 }
 CLIP_INTERP_SYMBOLS = list(CLIP_INTERP_SIGNATURES)
 
+# every exported symbol of include/gg_attn_dbias.h (the relative-position bias gradient as a kernel of its own that adds in a fixed order, and TinyViT's opt-in switch that makes the training step use it), bound from the same libgg.so
+ATTN_DBIAS_SIGNATURES = {
+    "gg_attention_dbias_rows": (_L, [C.POINTER(AttnArgs), _I]),
+    "gg_attention_dbias": (_I, [C.POINTER(AttnArgs), _I, _I, _P]),
+    "gg_attention_dbias_calls": (_L, []),
+    "gg_tinyvit_set_deterministic_dbias": (_I, [_I]),
+}
+ATTN_DBIAS_SYMBOLS = list(ATTN_DBIAS_SIGNATURES)
+PROF_CAT_ATTN_DBIAS = 8                   # GG_CAT_ATTN_DBIAS (csrc/prof.h): the launch profiler's category of gg_attention_dbias
+
 
 # every exported symbol of include/gg_attn_route.h (the route report of the attention entry points: host arithmetic, no device), its struct and its two enums
 class AttnRoutePass(C.Structure):
@@ -535,7 +545,7 @@ def lib() -> C.CDLL:
             raise GgError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JSCAN_SIGNATURES.items()) + list(JPROG_SIGNATURES.items()) + list(PANO_SIGNATURES.items()) + list(ATTN16_SIGNATURES.items()) + list(ATTN16W_SIGNATURES.items()) + list(ATTN16B_SIGNATURES.items()) + list(ATTN16WB_SIGNATURES.items()) + list(ATTN_ROUTE_SIGNATURES.items()) + list(WGRAD_RESIDENT_SIGNATURES.items()) + list(DGRAD_PARITY_SIGNATURES.items()) + list(CLIP_INTERP_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(TEXT_SIGNATURES.items()) + list(TEXT_TRAIN_SIGNATURES.items()) + list(CLS_SIGNATURES.items()) + list(DROP_SIGNATURES.items()) + list(PAD_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(FP8_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(JPEG_SIGNATURES.items()) + list(JSCAN_SIGNATURES.items()) + list(JPROG_SIGNATURES.items()) + list(PANO_SIGNATURES.items()) + list(ATTN16_SIGNATURES.items()) + list(ATTN16W_SIGNATURES.items()) + list(ATTN16B_SIGNATURES.items()) + list(ATTN16WB_SIGNATURES.items()) + list(ATTN_ROUTE_SIGNATURES.items()) + list(WGRAD_RESIDENT_SIGNATURES.items()) + list(DGRAD_PARITY_SIGNATURES.items()) + list(CLIP_INTERP_SIGNATURES.items()) + list(ATTN_DBIAS_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the library lacks a declared symbol
             fn.restype, fn.argtypes = res, args
         _lib = l
@@ -601,6 +611,7 @@ def source_hash() -> str:
     files.append(os.path.join(os.path.dirname(root), "include", "gg_wgrad_resident.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_conv_dgrad_parity.h"))
     files.append(os.path.join(os.path.dirname(root), "include", "gg_clip_interp.h"))
+    files.append(os.path.join(os.path.dirname(root), "include", "gg_attn_dbias.h"))
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.basename(f).encode() + b"\0")

@@ -19,6 +19,7 @@
 #include "../../include/gg_pad.h"
 #include "../../include/gg_attn16w.h"
 #include "../../include/gg_attn16wb.h"
+#include "../../include/gg_attn_dbias.h"
 #include "../../include/gg_wgrad_resident.h"
 #include "../../include/gg_conv_dgrad_parity.h"
 #include "attention_route.h"
@@ -33,6 +34,8 @@ std::atomic<int> g_drop_compact{1};
 std::atomic<int> g_attention16{0};
 // the opt-in 16-bit-MFMA attention of the bf16 TRAINING step for windows beyond 256 tokens (gg_tinyvit_set_attention16_train, include/gg_attn16wb.h)
 std::atomic<int> g_attention16_train{0};
+// the opt-in fixed-order bias gradient of the training step (gg_tinyvit_set_deterministic_dbias, include/gg_attn_dbias.h)
+std::atomic<int> g_deterministic_dbias{0};
 
 struct TensorInfo { std::string name; int64_t offset; int64_t numel; int ndim; int64_t shape[4]; int kind; };
 static const float kAttnScale = 0.17677669529663687f;   // head_dim 32 ^ -0.5; the expanded bias tables are divided by it
@@ -599,6 +602,7 @@ struct Exec {
     // finalised (the forward's .stat checkpoints are reused, the running buffers are not touched) and the segment's output is not rewritten
     bool replay = false;
     bool compact = false;   // DropPath row compaction is on for this call (the process-global switch, read once per call)
+    bool det_dbias = false;         // backward, switch on (gg_tinyvit_set_deterministic_dbias): trainable attention_biases take gg_attention_dbias, the attention backward gets dbias = NULL
     bool attn16_train = false;      // training forward / backward, bf16, switch on (gg_tinyvit_set_attention16_train): the same windows through gg_attention_flash16_win_fwd / _bwd
     bool attn16 = false;    // gg_tinyvit_forward, inference, bf16, switch on (gg_tinyvit_set_attention16): windows beyond 256 tokens through gg_attention_flash16_win_fwd
     void done(int stage) const { if (stage_done) stage_done(stage, stage_user); }
@@ -781,6 +785,33 @@ static int attention_fwd(const Exec& e, const GgAttnArgs& at) { return attention
 static int attention_bwd(const Exec& e, const StageL& st, GgAttnArgs& at) {
     const Layout& L = *e.L;
     GgAttnRoute r;
+    if (at.dbias && e.det_dbias) {
+        // the fixed-order bias gradient: dq / dk / dv from the route's backward without dbias (their bits do not depend on it), then the bias gradient alone
+        // from the same qkv / out / lse / dout, with P as that route recomputes it; its partial rows take the split-K region
+        GgAttnArgs db = at;
+        const int64_t rows = gg_attention_dbias_rows(&db, attn_dtype(e.f32));
+        if (rows < 0) return -1;
+        const int64_t table_bytes = (int64_t)st.heads * st.ws * st.ws * 4, region = (int64_t)128 << 20;
+        GG_CHECK(rows * table_bytes <= region / 2, "gg_tinyvit_backward: the fixed-order bias gradient's %lld partial rows do not fit the split-K region", (long long)rows);
+        db.dbias_scratch = e.F(L.splitk);
+        if (e.f32 && L.attn_ds >= 0 && !attn_switches().no_ds_scratch) at.ds_scratch = e.F(L.attn_ds);
+        const int entry = attn_entry(e.f32, e.attn16, e.attn16_train, at, true);
+        GG_TRY(gg_attention_route(&at, entry, attn_dtype(e.f32), &r));
+        if (e.f32 && r.kernel == GG_ATTN_KERNEL_FLASH_BWD_SPLIT) {
+            // the one exception: the f32 split single-pass kernel's two instantiations round dS's split residuals differently (dq / dk / dv differ by an ulp,
+            // measured), so this route keeps the instantiation the switch-off step runs and lets it bin into a table nobody reads -- the last table-sized
+            // piece of the region, with its partial rows in front where they fit the region's first half (else float atomics into that table)
+            at.dbias = (float*)((char*)e.F(L.splitk) + region - gg_align(table_bytes, 256));
+            if (r.dbias_rows * table_bytes <= region / 2) at.dbias_scratch = e.F(L.splitk);
+        } else {
+            at.dbias = nullptr;
+            GG_TRY(gg_attention_route(&at, entry, attn_dtype(e.f32), &r));
+        }
+        GG_TRY(attention_run(e, at, true));
+        // P must meet the forward's lse: the resident bf16 kernels start their scores from the expanded table, which holds bf16(bias / scale), like the routes that say so
+        const bool rounded = r.rounded_bias || r.kernel == GG_ATTN_KERNEL_BWD || r.kernel == GG_ATTN_KERNEL_BWD_GROUPED;
+        return gg_attention_dbias(&db, attn_dtype(e.f32), rounded, e.st);
+    }
     if (at.dbias && gg_attention_route(&at, attn_entry(e.f32, e.attn16, e.attn16_train, at, true), attn_dtype(e.f32), &r) == 0 &&
         r.dbias_rows * st.heads * st.ws * st.ws * 4 <= ((int64_t)64 << 20))
         at.dbias_scratch = e.F(L.splitk);
@@ -1617,6 +1648,7 @@ static int refresh_weights(const GgTinyVitCfg* cfg, const float* params, void* w
 extern "C" int gg_tinyvit_set_drop_compact(int on) { return g_drop_compact.exchange(on != 0 ? 1 : 0); }
 extern "C" int gg_tinyvit_set_attention16(int on) { return g_attention16.exchange(on != 0 ? 1 : 0); }
 extern "C" int gg_tinyvit_set_attention16_train(int on) { return g_attention16_train.exchange(on != 0 ? 1 : 0); }
+extern "C" int gg_tinyvit_set_deterministic_dbias(int on) { return g_deterministic_dbias.exchange(on != 0 ? 1 : 0); }
 extern "C" int gg_tinyvit_forward(const GgTinyVitCfg* cfg, int batch, int training, const float* params, float* buffers,
                                   int64_t* counters, const void* wcache, const float* x, const float* drop_scales, void* workspace,
                                   float* out, const uint8_t* trainable, void* stream) {
@@ -1660,6 +1692,7 @@ extern "C" int gg_tinyvit_backward(const GgTinyVitCfg* cfg, int batch, const flo
     e.trainable = trainable; e.stage_done = stage_done; e.stage_user = stage_user;
     e.compact = g_drop_compact.load() != 0;
     e.attn16_train = !m.f32 && g_attention16_train.load() != 0;      // the attention backward and the recompute replay (a training forward)
+    e.det_dbias = g_deterministic_dbias.load() != 0;
     if (trainable) {
         // The schedule forms the two gradients of a (weight, bias) / (gamma, beta) pair together (BatchNorm / LayerNorm finalize kernels, the fused
         // frozen-chain forms): a mask that trains one tensor of a pair and freezes the other has no schedule -- refuse it by name instead of silently
@@ -1683,7 +1716,7 @@ extern "C" int gg_tinyvit_backward(const GgTinyVitCfg* cfg, int batch, const flo
         return backward_impl(g, d_out);
     };
     GgGraphKey key;
-    key.add('B').add_bytes(cfg, sizeof(*cfg)).add(batch).add(params).add(wcache).add(drop_scales).add(workspace).add(d_out).add(grads).add((int)e.compact).add((int)e.attn16_train)
+    key.add('B').add_bytes(cfg, sizeof(*cfg)).add(batch).add(params).add(wcache).add(drop_scales).add(workspace).add(d_out).add(grads).add((int)e.compact).add((int)e.attn16_train).add((int)e.det_dbias)
        .add_bytes(trainable, trainable ? m.tensors.size() : 0);
     return gg_graph_run(key, (hipStream_t)stream, body);
 }

@@ -132,17 +132,22 @@ class TinyVitBackbone(EncoderRuntime):
     """Owner of the flat parameter / buffer storage and of the HIP workspace (``self.backbone`` of the adapter)."""
     _name, _switch, _gen_why = "TinyViT", "set_grad_checkpointing", "saved activations live in ONE workspace per backbone, so "
 
-    def __init__(self, model_name: str, seed: Optional[int] = None, attention16: bool = False, attention16_train: bool = False, **overrides):
+    def __init__(self, model_name: str, seed: Optional[int] = None, attention16: bool = False, attention16_train: bool = False,
+                 deterministic_bias_grad: bool = False, **overrides):
         """``attention16=True`` (bf16 only; opt-in): this backbone's inference forwards run with ``gg_tinyvit_set_attention16(1)`` -- windows beyond 256 tokens
         (tiny_vit_21m_384 / _512 stage 2) through ``gg_attention_flash16_win_fwd`` (include/gg_attn16w.h); training forwards are unaffected.
         ``attention16_train=True`` (bf16 only; opt-in, independent of ``attention16``): this backbone's training forwards and backwards run with
         ``gg_tinyvit_set_attention16_train(1)`` -- the same windows' training forward, recompute replay and attention backward through
-        ``gg_attention_flash16_win_fwd`` / ``gg_attention_flash16_win_bwd`` (include/gg_attn16wb.h); inference forwards are unaffected."""
+        ``gg_attention_flash16_win_fwd`` / ``gg_attention_flash16_win_bwd`` (include/gg_attn16wb.h); inference forwards are unaffected.
+        ``deterministic_bias_grad=True`` (every precision; opt-in, composes with the other switches, recompute, padded sizes and trainable masks): this
+        backbone's backwards run with ``gg_tinyvit_set_deterministic_dbias(1)`` -- the gradient of every trainable ``attention_biases`` comes from
+        ``gg_attention_dbias`` (include/gg_attn_dbias.h), which adds in a fixed order: every gradient of a step is then bit-reproducible."""
         super().__init__()
         check_attention16(attention16, overrides.get("precision"), type(self).__name__)
         check_attention16_train(attention16_train, overrides.get("precision"), type(self).__name__)
         self.attention16 = bool(attention16)
         self.attention16_train = bool(attention16_train)
+        self.deterministic_bias_grad = bool(deterministic_bias_grad)
         self.cfg, self.variant, self.depths = make_cfg(model_name, **overrides)
         self.model_name = model_name.split(".")[0]
         self.precision = "fp32" if self.cfg.act_dtype in (1, 3) else "bf16"          # storage / arithmetic class ("fp32_split" stores and checks like fp32)
@@ -322,6 +327,7 @@ class TinyVitBackbone(EncoderRuntime):
             cb = L.STAGE_DONE_FN(_stage_done)
         lib = L.lib()
         prev_t = lib.gg_tinyvit_set_attention16_train(1) if self.attention16_train else None      # read when the backward is enqueued (its recompute replay included)
+        prev_d = lib.gg_tinyvit_set_deterministic_dbias(1) if self.deterministic_bias_grad else None      # the same: the fixed-order bias gradient
         try:
             L.check(lib.gg_tinyvit_backward(C.byref(self.cfg), B, L.ptr(self._flat), L.ptr(self._wcache), L.ptr(drop), L.ptr(ws),
                                             L.ptr(d_out.contiguous(), torch.float32, "d_out"), L.ptr(fg), mask, L.stream(), cb, None),
@@ -329,6 +335,8 @@ class TinyVitBackbone(EncoderRuntime):
         finally:
             if prev_t is not None:
                 lib.gg_tinyvit_set_attention16_train(prev_t)
+            if prev_d is not None:
+                lib.gg_tinyvit_set_deterministic_dbias(prev_d)
         if failed:
             raise L.GgError(f"TinyViT backward: the gradient-ready hook failed ({type(failed[0]).__name__}: {failed[0]}); the gradients are "
                             "complete, but no further bucket was sent from inside this backward pass") from failed[0]
@@ -370,7 +378,8 @@ class TinyViTAdapter(nn.Module):
         the same as ``adapter.backbone.set_grad_checkpointing()``), ``attention16=True`` (bf16 only, opt-in: the inference forward's windows beyond
         256 tokens on the 16-bit MFMA -- ``TinyVitBackbone``; ``precision="fp32"`` / ``"fp32_split"`` with it raises), ``attention16_train=True`` (bf16 only, opt-in,
         independent of ``attention16``: the training step's windows beyond 256 tokens -- forward, recompute replay and backward -- on the 16-bit MFMA; the same
-        refusals)."""
+        refusals), ``deterministic_bias_grad=True`` (every precision, opt-in: the ``attention_biases`` gradients from the fixed-order kernel of
+        include/gg_attn_dbias.h, so that every gradient of a step is bit-reproducible -- ``TinyVitBackbone``)."""
         super().__init__()
         check_attention16(overrides.get("attention16", False), overrides.get("precision"), "TinyViTAdapter")
         check_attention16_train(overrides.get("attention16_train", False), overrides.get("precision"), "TinyViTAdapter")

@@ -121,7 +121,7 @@ class _Head(nn.Module):
 
 class TinyViTClassifier(nn.Module):
     """``overrides`` as ``TinyViTAdapter``: ``precision`` ("fp32" | "fp32_split" | "bf16"; default ``$GG_PRECISION`` or fp32), ``seed``, ``drop_path_rate``,
-    ``grad_checkpointing``, ``img_size``, ``attention16`` (bf16 only: the inference forward's windows beyond 256 tokens on the 16-bit MFMA), ``attention16_train`` (bf16 only: the training step's) ...  ``pretrained=True`` cannot download: ``$GG_PRETRAINED_DIR/<model_name>.pt`` (a timm state dict, any head size)
+    ``grad_checkpointing``, ``img_size``, ``attention16`` (bf16 only: the inference forward's windows beyond 256 tokens on the 16-bit MFMA), ``attention16_train`` (bf16 only: the training step's), ``deterministic_bias_grad`` (every precision: the ``attention_biases`` gradients in a fixed order of adds, include/gg_attn_dbias.h) ...  ``pretrained=True`` cannot download: ``$GG_PRETRAINED_DIR/<model_name>.pt`` (a timm state dict, any head size)
     is loaded with ``strict=False`` when it exists, otherwise a warning is issued and the timm initialisation stands."""
 
     def __init__(self, model_name: str = "tiny_vit_5m_224", num_classes: int = 1000, pretrained: bool = False, **overrides):

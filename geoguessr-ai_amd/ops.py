@@ -705,6 +705,42 @@ def attention_flash16_win_bwd(qkv, out, lse, dout, *, num_windows, tokens_per_wi
     return dqkv, dbias
 
 
+def attention_dbias_args(qkv, out, lse, dout, bias_table, *, num_windows, tokens_per_window, num_heads, q_off, k_off, v_off, head_stride, window_size, map_h,
+                         map_w, head_dim=32, scale=None):
+    """The GgAttnArgs of ``attention_dbias`` for these tensors (no dbias / dbias_scratch yet); rows of qkv / out / dout may be strided."""
+    DT = qkv.dtype
+    a = L.AttnArgs()
+    a.qkv, a.ld = _pr(qkv, DT, "qkv"), qkv.stride(0)
+    a.q_off, a.k_off, a.v_off, a.head_stride, a.head_dim = q_off, k_off, v_off, head_stride, head_dim
+    a.num_heads, a.num_windows, a.tokens_per_window = num_heads, num_windows, tokens_per_window
+    a.window_size, a.map_h, a.map_w = window_size, map_h, map_w
+    a.scale = head_dim ** -0.5 if scale is None else scale
+    a.bias_table = _p(bias_table, F32, "bias_table")
+    a.out, a.ldo, a.lse = _pr(out, DT, "out"), out.stride(0), _p(lse, F32, "lse")
+    a.dout, a.lddo = _pr(dout, DT, "dout"), dout.stride(0)
+    return a
+
+
+def attention_dbias(qkv, out, lse, dout, bias_table, *, round_bias=False, dbias=None, scratch=None, **geometry):
+    """The relative-position bias gradient alone, in a fixed order of adds (include/gg_attn_dbias.h): bf16 or f32 storage by ``qkv.dtype``, head dim 32, the
+    ``window_size`` x ``window_size`` windows of a ``map_h`` x ``map_w`` NHWC map.  ``out`` / ``lse``: the forward's; ``round_bias``: that forward added the bias
+    as bf16(bias / scale) (GgAttnRoute.rounded_bias).  Returns dbias (heads, ws * ws) f32: ``dbias`` (optional) is ACCUMULATED into, else a zero table is;
+    ``scratch`` (optional): the f32 buffer of gg_attention_dbias_rows(...) * heads * ws * ws floats to use."""
+    L.require_gpu()
+    a = attention_dbias_args(qkv, out, lse, dout, bias_table, **geometry)
+    dt = int(qkv.dtype == F32)
+    rows = L.lib().gg_attention_dbias_rows(C.byref(a), dt)
+    if rows < 0:
+        raise L.GgError(L.lib().gg_last_error().decode(errors="replace"))
+    if dbias is None:
+        dbias = torch.zeros_like(bias_table)
+    if scratch is None:
+        scratch = torch.empty((rows * a.num_heads * a.window_size * a.window_size,), dtype=F32, device=qkv.device)
+    a.dbias, a.dbias_scratch = _p(dbias, F32, "dbias"), _p(scratch, F32, "scratch")
+    L.check(L.lib().gg_attention_dbias(C.byref(a), dt, int(bool(round_bias)), L.stream()), "gg_attention_dbias")
+    return dbias
+
+
 def attention(qkv, *, num_windows, tokens_per_window, num_heads, head_dim, q_off, k_off, v_off, head_stride,
               window_size=0, map_h=0, map_w=0, bias=None, scale=None, dout=None, want_dbias=False, out=None, lse=None,
               want_lse=False):

@@ -523,6 +523,8 @@ typedef struct GgTinyVitCfg {
                                Contract: output, every parameter gradient, the running statistics and the counters are bit-identical to recompute = 0
                                (the recompute takes the forward's routes on the same inputs) -- except the attention-bias tables' gradients, with or
                                without recompute: they are summed with float atomics in LDS, so their last bits vary between ANY two steps.
+                               With gg_tinyvit_set_deterministic_dbias(1) (include/gg_attn_dbias.h; opt-in, default 0) the exception is gone: those
+                               gradients come from a kernel that adds in a fixed order, and every gradient is bit-identical, between steps too.
                                The recompute reuses the (mean, rstd) the forward saved in each .stat: the BatchNorm running buffers are updated ONCE
                                per step, by the forward (unlike torch.utils.checkpoint, whose recompute updates them a second time).  The workspace size and layout depend on the field: forward and backward must see the same value. */
 } GgTinyVitCfg;

@@ -9,7 +9,7 @@ from geoguessr_ai_amd.models.tinyvit import TinyViTAdapter
 from geoguessr_ai_amd.models.super_guessr import SuperGuessr
 from geoguessr_ai_amd.optim import AdamW
 
-CATS = ["gemm", "attention", "dwconv", "norm", "head", "optim", "move", "pad"]
+CATS = ["gemm", "attention", "dwconv", "norm", "head", "optim", "move", "pad", "attn_dbias"]
 dev = torch.device("cuda", 0)
 torch.manual_seed(0)
 PREC = "fp32" if "--fp32" in sys.argv else "bf16"
